@@ -2,6 +2,13 @@
 """Benchmark of the hot path: energy + forces of M3GNet (default model) on the HIP engine.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config3|config4] [--precision fp32|f16x3|bf16x3]
+                    [--dump-outputs DIR] [--full [--no-secondary] [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = wall time of the timed region / K, `config`); every other figure below comes
+with `--full`.  `--dump-outputs DIR` writes what the last timed step returned (config3: total_energy, forces, stresses,
+scaled_total_energy, scaled_atomic_energies; config4: the per-structure energies) as DIR/<name>.npy, float32, at most 64 MB
+in all (above that a fixed, seeded sample of rows); the inputs are seeded, so two builds can be compared array by array.
 
 `--gpus N` (N > 1) without a torch.distributed launcher in the environment starts the N ranks itself (one child
 process per GPU, before anything touches the GPU in the parent) and relays rank 0's JSON line; under
@@ -11,12 +18,12 @@ Workloads
   config3 (default; BASELINE.json configs[2], the "10k-atom PBC batch" the metric is quoted on): one jittered fcc-Cu
           supercell of 10 x 10 x 25 cells = 10,000 atoms per GPU, cutoff 5 A / three-body cutoff 4 A (E = 420,000
           directed edges, T = 3,060,000 triplets).  A single cell does not shard: with N > 1
-          every rank owns one independent supercell -- replicas, weak scaling, nothing crosses ranks inside a step; after
-          the timed region the replicas' energies are all-gathered over RCCL once and compared.
+          every rank owns one independent supercell -- replicas, weak scaling, nothing crosses ranks inside a step; with
+          `--full`, after the timed region the replicas' energies are all-gathered over RCCL once and compared.
   config4 (BASELINE.json configs[3]): 512 x N independent 64-atom random-species cells (seeds 0 .. 512 N - 1)
           partitioned over the N ranks by `torch_m3gnet.distributed.ShardedBatch` (greedy by triplet/edge cost, priced
           cooperatively, shard graphs built on the GPU), one RCCL all-gather of the per-structure energies per step.
-          Also measured as a secondary figure (`config4_sharded`) after every default run.
+          Also measured as a secondary figure (`config4_sharded`) by `--full`.
 Model: default M3GNet (l_max = n_max = 3, D = 64, 3 blocks, 95 species), random-init weights (seed 0), synthetic data.
 A step = one `model(graph)` call = the m3g_energy_forces launch sequence (forward + analytic reverse pass + virial),
 graph tensors resident in HBM.
@@ -24,9 +31,9 @@ graph tensors resident in HBM.
 Precision: the headline runs the engine's default exact `fp32` mode (every dense product on v_mfma_f32_16x16x4_f32, bitwise an fp32
 fmaf chain: the reference's arithmetic); the opt-in split modes -- `f16x3` (every operand as two power-of-two-scaled fp16 parts,
 three f16 MFMA products, fp32 accumulate: 22-24 significant bits, NARROWER than fp32) and `bf16x3` (~2^-16 relative product error)
--- are timed beside it and reported under `f16x3` / `bf16x3`, each with its operand format first in `dtype`.
+-- are timed beside it by `--full` and reported under `f16x3` / `bf16x3`, each with its operand format first in `dtype`.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0; with `--full` it carries these extra objects:
   roofline      the dominant kernel against the roofline that bounds it (fp32 mode: the fp32 matrix peak, `frac` on the USEFUL
                 FLOPs of the factorised formulation with the executed-MFMA figure beside it; bf16x3: HBM), its duration measured
                 live with HIP events in the library.  Bytes on three bases, never mixed: `algorithmic_bytes_8d` (SURVEY.md 8(d):
@@ -35,7 +42,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
                 kernel sources than the ones being timed)
   roofline_other_kernels   every other kernel of the step with its bound, bytes and achieved rate
   step_traffic_bytes       PMC traffic of one whole step against SURVEY.md 8(d)'s ideal-fusion bytes
-  beside        (n_gpus = 1, default run) step latency of the 32-atom Cu cell of BASELINE configs[0] and one MD-style iteration on
+  beside        (n_gpus = 1, 10 x 10 x 25 cells) step latency of the 32-atom Cu cell of BASELINE configs[0] and one MD-style iteration on
                 the headline cell with device-resident positions: skin-list test (lists reused) or full rebuild, then the step
   cpu_baseline  the CPU oracle (oracle/m3gnet_oracle.py, a plain-torch port of the reference) timed on the host cores ON THE
                 HEADLINE CONFIGURATION ITSELF (the 10,000-atom cell; 1 warm-up + 3 steps at all cores, 1 step at 1 thread,
@@ -165,6 +172,29 @@ def csrc_digest():
         h.update(f.name.encode())
         h.update(f.read_bytes())
     return h.hexdigest()[:16]
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, cap=DUMP_CAP_BYTES):
+    """Write {name: tensor} as DIR/<name>.npy, float32 (float64 stays float64).  Above `cap` bytes in all, every array keeps a
+    fixed sample of its rows (numpy default_rng(0), sorted), sized so that the whole set fits."""
+    out = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    out = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in out.items()}
+    rows = {k for k, v in out.items() if v.ndim and v.shape[0] > 1}
+    fixed = sum(v.nbytes for k, v in out.items() if k not in rows)
+    if fixed + sum(out[k].nbytes for k in rows) > cap:
+        frac = (cap - fixed) / sum(out[k].nbytes for k in rows)
+        for k in rows:
+            v = out[k]
+            keep = max(1, int(v.shape[0] * frac))
+            out[k] = v[np.sort(np.random.default_rng(0).choice(v.shape[0], keep, replace=False))]
+    path = Path(dirname)
+    path.mkdir(parents=True, exist_ok=True)
+    for k, v in out.items():
+        np.save(path / f"{k}.npy", np.ascontiguousarray(v))
+    log(f"outputs of the last timed step -> {path}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in out.items()))
 
 
 def physical_cores():
@@ -527,8 +557,9 @@ def rooflines(per_launch, n_atoms, n_edges, n_trip, n_active, precision, pmc, mo
     return views
 
 
-def measure_config4(job, model, steps, warmup):
-    """BASELINE config 4: 512 x world independent 64-atom cells sharded by ShardedBatch; returns the record."""
+def measure_config4(job, model, steps, warmup, outputs=None):
+    """BASELINE config 4: 512 x world independent 64-atom cells sharded by ShardedBatch; returns the record (and, into `outputs`
+    when given, the per-structure energies of the last timed step)."""
     from torch_m3gnet.data import MaterialGraphKey as K
     from torch_m3gnet.data.synthetic import random_cell_arrays
     from torch_m3gnet.distributed import ShardedBatch
@@ -547,6 +578,8 @@ def measure_config4(job, model, steps, warmup):
 
     step()
     elapsed = job.timed(step, steps, warmup)
+    if outputs is not None:
+        outputs["energies"] = energies.detach().cpu()
     n_atoms = sum(sb.sizes)
     loads = [sum(sb.costs[i] for i in s) for s in sb.shards]
     return {"workload": f"{n_structs} independent 64-atom random-species cells (L = 9.1 A, seeds 0..{n_structs - 1}), "
@@ -705,8 +738,13 @@ def main():
     ap.add_argument("--cells", type=int, nargs=3, default=[10, 10, 25], help="config3: fcc cells per axis (4 atoms each)")
     ap.add_argument("--engine-option", action="append", default=[], metavar="NAME=INT",
                     help="engine option for A/B timing (m3g_plan_set_option), e.g. threebody_moments=0; recorded in config.engine_options")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other-precision and config4 secondary figures")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: step-time series and clock, stage times and rooflines, launch count, topology "
+                         "build time, replica check, the other precisions, config4_sharded, `beside` and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the other-precision, config4 and `beside` figures")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32; rank 0)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -726,7 +764,10 @@ def main():
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic", "dtype": DTYPE[args.precision]}
 
     if args.workload == "config4":
-        rec = measure_config4(job, model, args.steps, args.warmup)
+        outputs = {}
+        rec = measure_config4(job, model, args.steps, args.warmup, outputs=outputs)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
         out.update(value=rec["value"], ms_per_step=rec["ms_per_step"],
                    config={"workload": rec.pop("workload"), **{k: v for k, v in rec.items() if k not in ("value", "unit", "ms_per_step", "steps")}})
         if rank == 0:
@@ -753,6 +794,32 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = world * n_atoms * args.steps / elapsed
     log(f"timed region done ({args.precision}): {ms_per_step:.3f} ms/step")
+    if args.dump_outputs and rank == 0:   # what a caller of the timed path receives, from its last step
+        dump_outputs(args.dump_outputs, {k: graph[k] for k in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES, K.SCALED_TOTAL_ENERGY,
+                                                                K.SCALED_ATOMIC_ENERGIES)})
+    out.update(value=value, ms_per_step=ms_per_step,
+               config={"workload": f"single {n_atoms}-atom fcc Cu PBC supercell per GPU ({'x'.join(map(str, args.cells))} cells, "
+                                   "a=3.61 A, jitter 0.025 A), r_cut 5 A / 3-body 4 A, default M3GNet (l_max=n_max=3, D=64, "
+                                   "3 blocks), energy+forces+stress",
+                       "precision": args.precision, **({"engine_options": args.engine_option} if args.engine_option else {}),
+                       "atoms_per_gpu": n_atoms, "edges_per_gpu": n_edges, "triplets_per_gpu": n_trip,
+                       "first_call_s_incl_topology_build": first_call_s,
+                       "multi_gpu": "replicas (a single cell does not shard; no collective inside the timed steps); config4_sharded below runs the sharded path"})
+    if args.full:
+        full_figures(args, job, model, graph, step, out, other_modes)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    job.close()
+
+
+def full_figures(args, job, model, graph, step, out, other_modes):
+    """--full: every figure beside the headline, measured after its timed region and added to `out` (the headline stays as timed)."""
+    from torch_m3gnet.data import MaterialGraphKey as K
+
+    world, rank, device = job.world, job.rank, job.device
+    cfg = out["config"]
+    n_atoms, n_edges, n_trip = cfg["atoms_per_gpu"], cfg["edges_per_gpu"], cfg["triplets_per_gpu"]
+    ms_per_step, value = out["ms_per_step"], out["value"]
     replica_spread = None
     if job.dist is not None:   # after the timed region: the replicas' energies side by side (same cell, same weights: they must agree)
         energies_all = torch.empty(world, 1, device=job.comm_device)
@@ -816,18 +883,12 @@ def main():
     clk = (timing.get("clock_mhz") or {}).get("median")
     if clk:   # the peaks of MI355X_MICROARCH.md are quoted at 2,400 MHz; the card holds less under this load
         roofline["frac_at_measured_clock"] = roofline["frac"] * 2400.0 / clk
-    out.update(value=value, ms_per_step=ms_per_step, ms_per_step_min=timing["ms_per_step_min"], ms_per_step_median=timing["ms_per_step_median"],
+    out.update(ms_per_step_min=timing["ms_per_step_min"], ms_per_step_median=timing["ms_per_step_median"],
                clock_mhz=(timing.get("clock_mhz") or {}).get("median"), step_timing=timing, kernel_launches_per_step=launches[0],
-               other_stream_operations_per_step=launches[1], roofline=roofline, roofline_other_kernels=others, step_traffic_bytes=step_bytes,
-               config={"workload": f"single {n_atoms}-atom fcc Cu PBC supercell per GPU ({'x'.join(map(str, args.cells))} cells, "
-                                   "a=3.61 A, jitter 0.025 A), r_cut 5 A / 3-body 4 A, default M3GNet (l_max=n_max=3, D=64, "
-                                   "3 blocks), energy+forces+stress",
-                       "precision": args.precision, **({"engine_options": args.engine_option} if args.engine_option else {}),
-                       "atoms_per_gpu": n_atoms, "edges_per_gpu": n_edges, "triplets_per_gpu": n_trip,
-                       "active_edges_per_gpu": n_active, "topology_hints": topo_hints, "kernel_launches_per_step": launches[0], "first_call_s_incl_topology_build": first_call_s,
-                       "topology_build_ms": topo_ms, "stage_ms_per_step": stage_ms,
-                       "multi_gpu": "replicas (a single cell does not shard; no collective inside the timed steps); config4_sharded below runs the sharded path",
-                       **({"replica_energy_rel_spread": replica_spread} if replica_spread is not None else {})})
+               other_stream_operations_per_step=launches[1], roofline=roofline, roofline_other_kernels=others, step_traffic_bytes=step_bytes)
+    cfg.update({"active_edges_per_gpu": n_active, "topology_hints": topo_hints, "kernel_launches_per_step": launches[0],
+                "topology_build_ms": topo_ms, "stage_ms_per_step": stage_ms,
+                **({"replica_energy_rel_spread": replica_spread} if replica_spread is not None else {})})
     if not args.no_secondary:
         for other in other_modes:   # the other arithmetic modes of the same engine, same workload, same timed-region rules
             model.engine.set_precision(other)
@@ -868,14 +929,11 @@ def main():
             if k in md:
                 sec[short] = md[k]["total"]
         out["config"].update({k: round(float(v), 4) for k, v in sec.items()})
-    if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(tuple(args.cells))
-            out["vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]   # (vs_baseline stays null: nothing published)
-            out["config"]["sec_cpu_all_cores_ms"] = round(out["cpu_baseline"]["ms_per_step"], 1)
-            out["config"]["sec_cpu_cores"] = out["cpu_baseline"]["cores"]
-        print(json.dumps(out), flush=True)
-    job.close()
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(tuple(args.cells))
+        out["vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]   # (vs_baseline stays null: nothing published)
+        out["config"]["sec_cpu_all_cores_ms"] = round(out["cpu_baseline"]["ms_per_step"], 1)
+        out["config"]["sec_cpu_cores"] = out["cpu_baseline"]["cores"]
 
 
 if __name__ == "__main__":

@@ -114,7 +114,8 @@ def test_bench_nccl_branch_with_one_rank():
     from pathlib import Path
 
     bench = Path(__file__).resolve().parent.parent / "bench.py"
-    proc = _run_child([str(bench), "--gpus", "1", "--steps", "3", "--warmup", "1", "--cells", "4", "4", "4", "--no-cpu-baseline", "--no-secondary"],
+    proc = _run_child([str(bench), "--gpus", "1", "--steps", "3", "--warmup", "1", "--cells", "4", "4", "4", "--full", "--no-cpu-baseline",
+                       "--no-secondary"],
                       env={"M3G_BENCH_FORCE_DIST": "1", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1",
                            "MASTER_PORT": "29547"})
     assert proc.returncode == 0, proc.stderr[-3000:]

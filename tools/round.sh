@@ -16,7 +16,7 @@ cd $R
 mkdir -p gpurun_out
 case $verb in
 ab)
-  python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-secondary "$@" 2>/dev/null | python -c "
+  python bench.py --steps 100 --warmup 20 --full --no-cpu-baseline --no-secondary "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('ms/step', round(d['ms_per_step'],4), 'min', round(d['ms_per_step_min'],4), 'MHz', d['clock_mhz'], 'launches', d['kernel_launches_per_step']); print(d['config']['stage_ms_per_step'])"
   python tools/time_small_systems.py fp32 2 5 6 8 10 2>/dev/null
   python tools/time_config5.py 2>/dev/null | tail -2
@@ -34,7 +34,7 @@ seq)
     tail -2 $R/gpurun_out/${tag}_step_sequence_$((4*n*n*n))_atoms.txt
   done
   rm -rf /tmp/seq
-  rocprofv3 --kernel-trace --output-format csv -d /tmp/seq -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2>&1
+  rocprofv3 --kernel-trace --output-format csv -d /tmp/seq -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary > /dev/null 2>&1
   python3 $R/tools/step_sequence.py /tmp/seq 4 > $R/gpurun_out/${tag}_step_sequence_fp32.txt
   tail -3 $R/gpurun_out/${tag}_step_sequence_fp32.txt
   ;;
@@ -54,9 +54,11 @@ final)
   timeout -k 10 1100 python -m pytest tests -m gpu -x -q > gpurun_out/${tag}_gputest_final.log 2>&1; rc=$?
   tail -3 gpurun_out/${tag}_gputest_final.log
   [ $rc -eq 0 ] || exit $rc
-  python bench.py > gpurun_out/${tag}_bench_default_run.json 2> gpurun_out/${tag}_bench_default_run.err || exit 1
+  bench_line=$(mktemp --suffix=_${tag}_bench_full_run.json)
+  python bench.py --full > $bench_line 2> ${bench_line%.json}.err || { tail -5 ${bench_line%.json}.err; exit 1; }
+  echo "bench line: $bench_line"
   python -c "
-import json; d=json.load(open('gpurun_out/${tag}_bench_default_run.json')); print(d['ms_per_step'], d['roofline']['frac'], d['roofline'].get('traffic'), d['cpu_baseline']['value'], d['cpu_baseline']['cores']); print({k: v for k, v in d['config'].items() if k.startswith('sec_')})"
+import json; d=json.load(open('$bench_line')); print(d['ms_per_step'], d['roofline']['frac'], d['roofline'].get('traffic'), d['cpu_baseline']['value'], d['cpu_baseline']['cores']); print({k: v for k, v in d['config'].items() if k.startswith('sec_')})"
   bash tools/round.sh seq $tag 2 6
   python3 tools/time_small_systems.py fp32 2 3 4 5 6 8 10 > gpurun_out/${tag}_small_cells_timing.txt 2>/dev/null
   for m in reuse refill rebuild; do python tools/profile_md_iteration.py $m 30 2>/dev/null | tail -1; done > gpurun_out/${tag}_md_times.txt

@@ -2,8 +2,8 @@
 """Kernel sequence of ONE step from a `rocprofv3 --kernel-trace --output-format csv` run: every dispatch between the last two
 k_geometry<> launches, with its duration and the gap to the previous dispatch's end (us).
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/seq -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary
-    python tools/step_sequence.py gpurun_out/seq [k [marker]]     (marker: substring of the kernel that starts an iteration, default
+    rocprofv3 --kernel-trace --output-format csv -d /tmp/seq -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary
+    python tools/step_sequence.py /tmp/seq [k [marker]]           (marker: substring of the kernel that starts an iteration, default
                                                           k_geometry<; k: which step, counted from the end; default 1 = the last one.  bench.py
                                                           ends with `--steps` PROFILED steps -- stage events between the kernels --,
                                                           so k = steps + 1 is the last step of the timed region)
