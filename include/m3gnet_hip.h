@@ -428,6 +428,46 @@ int m3g_md_invalidate(m3g_md* md);   /* the caller has rewritten cand_state / th
 int m3g_md_step(m3g_md* md, const m3g_plan* plan, const double* pos, float* total_energy, float* forces, float* stresses,
                 int32_t force_refill, m3g_md_result* host_result, void* stream);
 
+/* ---- batched structure relaxation: FIRE, fixed or variable cell (csrc/m3g_relax.hip) ---------------------------------------------
+ * Replaces the reference's relaxation script (scripts/relax_org.py -> m3gnet's Relaxer: ASE's FIRE over a UnitCellFilter, one
+ * optimiser per structure on the host).  Every structure of a batch is relaxed on its own, with the semantics of ASE's FIRE applied to
+ * that structure alone (unit masses; the loop of ASE's Optimizer.run: evaluate -> converged? -> step).  relax_cell = 1 relaxes the cell
+ * through ASE's UnitCellFilter (linear deformation gradient F = solve(L0, L)^T, cell_factor = the structure's atom count): generalized
+ * coordinates X = [pos F^-T ; cell_factor F], generalized forces g = [f F ; W F^-T / cell_factor] with the virial W = V * stresses of
+ * the PAIR-VIRIAL stresses (m3g_plan_set_option "stress_mode" = 1: the strain derivative; mode 0 is not one).  Converged means
+ * max_i |g_i| < fmax over every row of the structure, cell rows included; a converged structure is FROZEN (positions, cell and FIRE
+ * state bitwise unchanged by later calls); a structure whose g holds a non-finite value gets M3G_FIRE_ERROR and is never moved.
+ * The state buffer (m3g_fire_state_bytes) is caller-owned device memory holding X, v, L0, F in fp64, the per-structure dt, a, n, flags
+ * and step counts, and a chunk table of the batch made by m3g_fire_init (which waits for the stream). */
+typedef struct {
+  double dt, maxstep, dtmax, finc, fdec, astart, fa;   /* ASE defaults: 0.1, 0.2, 1.0, 1.1, 0.5, 0.1, 0.99 */
+  double fmax;                                         /* > 0 */
+  int32_t nmin;                                        /* 5 */
+  int32_t relax_cell;                                  /* 0 positions only, 1 positions and cell */
+} m3g_fire_params;
+#define M3G_FIRE_STARTED 1     /* the structure has taken a step (ASE's v is no longer None) */
+#define M3G_FIRE_CONVERGED 2   /* frozen: max_i |g_i| < fmax was seen */
+#define M3G_FIRE_ERROR 4       /* frozen: its generalized forces held a non-finite value */
+int m3g_fire_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* bytes);
+/* host_offsets: HOST int64 [S+1], 0 = o_0 < o_1 < ... < o_S = N (atoms of structure s: [o_s, o_s+1)).  pos [N,3] and lattice [S,3,3]
+ * (rows = lattice vectors; may be NULL with the cell fixed) DEVICE fp64: the starting point (L0).  Invalid parameters (fmax <= 0, ...) or
+ * offsets -> M3G_ERR_VALUE.  Waits for the stream. */
+int m3g_fire_init(const m3g_fire_params* params, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* pos,
+                  const double* lattice, void* state, size_t state_bytes, void* stream);
+/* One FIRE iteration of the batch at the forces [N,3] / stresses [S,6] (f32 DEVICE, Voigt xx,yy,zz,yz,zx,xy, pair-virial convention;
+ * stresses may be NULL with the cell fixed) evaluated at the current pos: convergence and error verdicts, then one step of every other
+ * structure, which updates pos [N,3] fp64 and (relax_cell) lattice [S,3,3] fp64 / lattice32 [S,3,3] f32 (may be NULL) IN PLACE.  params:
+ * those of m3g_fire_init.  check_only != 0: the verdicts only, nothing moves (the evaluation after the last step).  `unconverged` (may be
+ * NULL; device or pinned host memory) receives the number of structures that are neither converged nor failed after this call.  Three
+ * launches whatever S (two with check_only), no allocation and no wait: capture-safe.  A cell relaxation without stresses or lattice
+ * -> M3G_ERR_VALUE. */
+int m3g_fire_step(const m3g_fire_params* params, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
+                  const float* stresses, double* pos, double* lattice, float* lattice32, int32_t check_only, int32_t* unconverged, void* stream);
+/* Per-structure flags (M3G_FIRE_*), step counts, dt, a, n [S] and the generalized coordinates / velocities [N + 3S, 3] (the N atom
+ * rows, then three cell rows per structure) to HOST memory; every output may be NULL.  Waits for the stream. */
+int m3g_fire_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes, int32_t* host_flags, int32_t* host_steps,
+                  double* host_dt, double* host_a, int32_t* host_n, double* host_x, double* host_v, void* stream);
+
 /* ---- measurement: per-stage device time from HIP events recorded on the call's own stream ---------
  * m3g_profile_enable(plan, 1) makes every following m3g_energy_forces record an event pair around each
  * stage launch; m3g_profile_read synchronises those events, returns per-stage totals since the last
@@ -459,12 +499,13 @@ int m3g_debug_radix_sort(int32_t key_bytes, int64_t n, void* keys, int32_t* vals
 int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes, int32_t* kernel_launches,
                        int32_t* other_operations);
 
-#define M3G_ABI_VERSION 6   /* 2: m3g_io.topo_hints, m3g_topology_hints; 3: m3g_verlet_*, m3g_topology_status, hints word certified on the buffer,
+#define M3G_ABI_VERSION 7   /* 2: m3g_io.topo_hints, m3g_topology_hints; 3: m3g_verlet_*, m3g_topology_status, hints word certified on the buffer,
                              * canonical edge order by the shift relative to the given coordinates, default precision fp32;
                              * 4: m3g_verlet_fill_lists, m3g_topology_build_canonical, M3G_TOPO_ERR_SYNC, options small_tiles / small_launches / fuse_node_tb;
                              * 5: m3g_topology_build_canonical_begin / _end, m3g_topology_data_bytes, option legendre_backward, m3g_md_*;
                              * 6: M3G_TOPO_ERR_SPECIES (species checked on the library side, m3g_md_step returns M3G_ERR_VALUE), m3g_count_launches,
-                             *    m3g_debug_exclusive_scan / m3g_debug_radix_sort (the library's own scan and sort: no hipCUB) */
+                             *    m3g_debug_exclusive_scan / m3g_debug_radix_sort (the library's own scan and sort: no hipCUB);
+                             * 7: m3g_fire_* (batched FIRE relaxation, fixed or variable cell) */
 
 #ifdef __cplusplus
 }

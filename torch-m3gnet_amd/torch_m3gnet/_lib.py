@@ -10,7 +10,7 @@ _PKG_ROOT = Path(__file__).resolve().parent.parent  # .../torch-m3gnet_amd
 LIB_PATH = _PKG_ROOT / "lib" / "libm3gnet_hip.so"
 
 M3G_OK, M3G_ERR_VALUE, M3G_ERR_STATE, M3G_ERR_SIZE, M3G_ERR_HIP, M3G_ERR_UNSUPPORTED = range(6)
-ABI_VERSION = 6
+ABI_VERSION = 7
 VERLET_FILL_LISTS_MAX_ROW = 1024   # M3G_VERLET_FILL_LISTS_MAX_ROW (include/m3gnet_hip.h)
 
 
@@ -58,6 +58,14 @@ class M3GMdResult(C.Structure):   # m3g_md_result
 
 
 MD_REUSE, MD_REFILL, MD_NEED_SEARCH, MD_UNSUPPORTED = range(4)
+
+
+class M3GFireParams(C.Structure):   # m3g_fire_params
+    _fields_ = [("dt", C.c_double), ("maxstep", C.c_double), ("dtmax", C.c_double), ("finc", C.c_double), ("fdec", C.c_double),
+                ("astart", C.c_double), ("fa", C.c_double), ("fmax", C.c_double), ("nmin", C.c_int32), ("relax_cell", C.c_int32)]
+
+
+FIRE_STARTED, FIRE_CONVERGED, FIRE_ERROR = 1, 2, 4   # M3G_FIRE_* flag bits
 
 # name -> (restype, argtypes); every symbol include/m3gnet_hip.h declares
 SYMBOLS = {
@@ -140,6 +148,13 @@ SYMBOLS = {
     "m3g_debug_exclusive_scan": (C.c_int, [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_debug_radix_sort": (C.c_int, [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "m3g_count_launches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "m3g_fire_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "m3g_fire_init": (C.c_int, [C.POINTER(M3GFireParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                C.c_void_p]),
+    "m3g_fire_step": (C.c_int, [C.POINTER(M3GFireParams), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "m3g_fire_read": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "m3g_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_float),
                                    C.POINTER(C.c_int32)]),
