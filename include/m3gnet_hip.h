@@ -468,6 +468,67 @@ int m3g_fire_step(const m3g_fire_params* params, int64_t n_atoms, int64_t n_stru
 int m3g_fire_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes, int32_t* host_flags, int32_t* host_steps,
                   double* host_dt, double* host_a, int32_t* host_n, double* host_x, double* host_v, void* stream);
 
+/* ---- batched molecular dynamics: NVE, NVT (Berendsen, Langevin BAOAB), NPT Berendsen (csrc/m3g_dynamics.hip) -------------------
+ * Replaces the m3gnet package's MolecularDynamics (m3gnet.models.MolecularDynamics, the interface the reference stands in for: ASE's
+ * VelocityVerlet "nve", NVTBerendsen "nvt" and NPTBerendsen "npt_berendsen" on one structure, on the host) for a whole batch, each
+ * structure with its own target temperature and random stream.  Units: A, fs, amu, eV; velocities A/fs (fp64); a_i = kappa F_i / m_i
+ * with kappa = 9.648533215665e-3; k_B = 8.617333262e-5 eV/K; KE_s = sum_i m_i |v_i|^2 / (2 kappa); T_s = 2 KE_s / (3 n_s k_B);
+ * P_s = (tr W_s + lambda^2 2 KE_s) / (3 V_s) with the virial W = V * stresses of the PAIR-VIRIAL stresses (stress_mode 1).
+ * One m3g_dyn_step at the forces F(x_k) of every structure not frozen:
+ *   finish  (a structure that has started): v += dt/2 a;
+ *   observables at the full step: KE, T, P (lambda = 1; NaN without stresses or lattice), V (NaN without lattice) -> obs[s] =
+ *           {KE, T, P, V};
+ *   start   (not with finish_only, which instead clears M3G_DYN_STARTED: the next call starts without a finish kick)
+ *     NVE            ASE's VelocityVerlet: v += dt/2 a; fix_com: v_i -= pbar / m_i (pbar = sum_j m_j v_j / n after the kick); x += dt v
+ *     NVT_BERENDSEN  ASE's NVTBerendsen: lambda = sqrt(max(1 + dt/taut (T0/T - 1), 0)) clamped to [0.9, 1.1] (1.1 when T = 0),
+ *                    v = lambda v, then as NVE
+ *     NPT_BERENDSEN  ASE's NPTBerendsen, isotropic: lambda as NVT, v = lambda v; mu = 1 - dt compressibility / (3 taup) (pressure -
+ *                    P); lattice = mu lattice, x = mu x; then as NVE with the forces of the unscaled positions (as ASE)
+ *     NVT_LANGEVIN   BAOAB (NOT ASE's Langevin scheme): v += dt/2 a; x += dt/2 v; v = c1 v + sqrt((1 - c1^2) k_B T0 kappa / m) xi,
+ *                    c1 = exp(-friction dt); x += dt/2 v (the next finish is the final B).  xi: Philox4x64-10, key (seed_s, 0), counter
+ *                    (k_s, i - o_s, 0, 0) with k_s the structure's count of starts; u_j = ((w_j >> 11) + 0.5) 2^-53, Box-Muller on
+ *                    (u0, u1) -> xi_x, xi_y and (u2, u3) -> xi_z: a structure's noise does not depend on the rest of the batch.
+ * A structure whose forces (or, in NPT, stresses) hold a non-finite value gets M3G_DYN_ERROR and is FROZEN: positions, cell,
+ * velocities and its obs row are never written again.  No atomics: every result is bitwise the same alone or in any batch.
+ * The state buffer (m3g_dyn_state_bytes) is caller-owned device memory: masses, velocities, target temperatures, seeds, flags, step
+ * counts and the chunk table of the batch (the one of m3g_fire_*). */
+typedef struct {
+  int32_t ensemble;         /* M3G_DYN_NVE, M3G_DYN_NVT_BERENDSEN, M3G_DYN_NVT_LANGEVIN, M3G_DYN_NPT_BERENDSEN */
+  int32_t fix_com;          /* 0 / 1: zero the total momentum at every start (not with NVT_LANGEVIN) */
+  double dt;                /* fs, > 0 */
+  double taut;              /* fs, > 0 (NVT_BERENDSEN, NPT_BERENDSEN) */
+  double friction;          /* 1/fs, >= 0 (NVT_LANGEVIN) */
+  double pressure;          /* eV/A^3, finite (NPT_BERENDSEN) */
+  double taup;              /* fs, > 0 (NPT_BERENDSEN) */
+  double compressibility;   /* A^3/eV, > 0 (NPT_BERENDSEN) */
+} m3g_dyn_params;
+#define M3G_DYN_NVE 0
+#define M3G_DYN_NVT_BERENDSEN 1
+#define M3G_DYN_NVT_LANGEVIN 2
+#define M3G_DYN_NPT_BERENDSEN 3
+#define M3G_DYN_STARTED 1   /* the structure's last call started a step: the next one finishes it */
+#define M3G_DYN_ERROR 2     /* frozen: its forces (NPT: or stresses) held a non-finite value */
+int m3g_dyn_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* bytes);
+/* host_offsets: HOST int64 [S+1] as m3g_fire_init; host_masses [N] (amu, > 0), host_temperatures [S] (target T0_s in K, finite, >= 0;
+ * unused by NVE), host_seeds [S] (Philox keys): HOST.  vel [N,3] DEVICE fp64: the starting velocities (copied into the state).
+ * Everything is validated on the host before any HIP call: an unknown ensemble, dt / taut / taup / compressibility not finite and > 0
+ * where the ensemble uses it, friction < 0, a bad pressure, temperature or mass, bad offsets, or NVT_LANGEVIN with fix_com ->
+ * M3G_ERR_VALUE.  Waits for the stream. */
+int m3g_dyn_init(const m3g_dyn_params* params, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
+                 const double* host_temperatures, const uint64_t* host_seeds, const double* vel, void* state, size_t state_bytes,
+                 void* stream);
+/* One call per force evaluation (see above): forces [N,3] f32 DEVICE evaluated at pos; stresses [S,6] f32 DEVICE (Voigt xx,yy,zz,yz,zx,xy,
+ * pair-virial convention; may be NULL except in NPT); pos [N,3] fp64 DEVICE (unwrapped), lattice [S,3,3] fp64 / lattice32 [S,3,3] f32
+ * DEVICE (may be NULL except in NPT; lattice32 may be NULL always), all updated IN PLACE; obs [S,4] fp64 DEVICE or NULL.  params: those
+ * of m3g_dyn_init.  Three launches whatever S, no allocation, copy or wait: capture-safe.  NPT without stresses or lattice ->
+ * M3G_ERR_VALUE. */
+int m3g_dyn_step(const m3g_dyn_params* params, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
+                 const float* stresses, double* pos, double* lattice, float* lattice32, int32_t finish_only, double* obs, void* stream);
+/* Per-structure flags (M3G_DYN_*) and step counts (starts taken) [S] and the velocities [N,3] to HOST memory; every output may be
+ * NULL.  Waits for the stream. */
+int m3g_dyn_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes, int32_t* host_flags, int64_t* host_steps,
+                 double* host_vel, void* stream);
+
 /* ---- measurement: per-stage device time from HIP events recorded on the call's own stream ---------
  * m3g_profile_enable(plan, 1) makes every following m3g_energy_forces record an event pair around each
  * stage launch; m3g_profile_read synchronises those events, returns per-stage totals since the last
@@ -499,13 +560,14 @@ int m3g_debug_radix_sort(int32_t key_bytes, int64_t n, void* keys, int32_t* vals
 int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes, int32_t* kernel_launches,
                        int32_t* other_operations);
 
-#define M3G_ABI_VERSION 7   /* 2: m3g_io.topo_hints, m3g_topology_hints; 3: m3g_verlet_*, m3g_topology_status, hints word certified on the buffer,
+#define M3G_ABI_VERSION 8   /* 2: m3g_io.topo_hints, m3g_topology_hints; 3: m3g_verlet_*, m3g_topology_status, hints word certified on the buffer,
                              * canonical edge order by the shift relative to the given coordinates, default precision fp32;
                              * 4: m3g_verlet_fill_lists, m3g_topology_build_canonical, M3G_TOPO_ERR_SYNC, options small_tiles / small_launches / fuse_node_tb;
                              * 5: m3g_topology_build_canonical_begin / _end, m3g_topology_data_bytes, option legendre_backward, m3g_md_*;
                              * 6: M3G_TOPO_ERR_SPECIES (species checked on the library side, m3g_md_step returns M3G_ERR_VALUE), m3g_count_launches,
                              *    m3g_debug_exclusive_scan / m3g_debug_radix_sort (the library's own scan and sort: no hipCUB);
-                             * 7: m3g_fire_* (batched FIRE relaxation, fixed or variable cell) */
+                             * 7: m3g_fire_* (batched FIRE relaxation, fixed or variable cell);
+                             * 8: m3g_dyn_* (batched molecular dynamics: NVE, NVT Berendsen / Langevin, NPT Berendsen) */
 
 #ifdef __cplusplus
 }

@@ -11,28 +11,25 @@
 // No atomics: every sum depends on the structure's own rows only (chunks never straddle structures), so results are bitwise
 // reproducible and independent of the rest of the batch.  No allocation, copy or wait in m3g_fire_step (capture-safe).
 #include <cmath>
-#include <vector>
 
+#include "m3g_chunks.h"
 #include "m3g_internal.h"
 
 namespace m3g {
 namespace {
-constexpr int kFireRows = 256;   // atoms per chunk == threads per workgroup of the row kernels
+constexpr int kFireRows = kChunkRows;   // atoms per chunk == threads per workgroup of the row kernels (m3g_chunks.h)
 constexpr int kCoef = 24;        // per structure: move, c_v, c_g, step scale, F before [9], F after [9], (pad)
 
 struct FireLayout {
-  size_t offsets, chunk_struct, chunk_begin, first_chunk, partial, x, v, l0, f, dt, a, n, flags, steps, coef, total;
+  ChunkLayout chunks;
+  size_t partial, x, v, l0, f, dt, a, n, flags, steps, coef, total;
 };
-int64_t fire_chunk_bound(int64_t N, int64_t S) { return (N + kFireRows - 1) / kFireRows + S; }
 FireLayout fire_layout(int64_t N, int64_t S) {
   FireLayout L{};
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
-  const int64_t C = fire_chunk_bound(N, S), R = N + 3 * S;
-  L.offsets = take(8 * (S + 1));
-  L.chunk_struct = take(4 * C);
-  L.chunk_begin = take(8 * C);
-  L.first_chunk = take(4 * (S + 1));   // [S] = number of chunks
+  const int64_t C = chunk_bound(N, S), R = N + 3 * S;
+  L.chunks = chunk_layout(N, S, take);
   L.partial = take(8 * 4 * C);
   L.x = take(8 * 3 * R);                // rows: the N atoms, then 3 cell rows per structure
   L.v = take(8 * 3 * R);
@@ -60,9 +57,9 @@ struct FireView {
 FireView fire_view(int64_t N, int64_t S, void* state) {
   const FireLayout L = fire_layout(N, S);
   char* b = (char*)state;
-  return FireView{N, S, (const int64_t*)(b + L.offsets), (const int32_t*)(b + L.chunk_struct), (const int64_t*)(b + L.chunk_begin),
-                  (const int32_t*)(b + L.first_chunk), (double*)(b + L.partial), (double*)(b + L.x), (double*)(b + L.v),
-                  (double*)(b + L.l0), (double*)(b + L.f), (double*)(b + L.dt), (double*)(b + L.a), (double*)(b + L.coef),
+  return FireView{N, S, (const int64_t*)(b + L.chunks.offsets), (const int32_t*)(b + L.chunks.chunk_struct),
+                  (const int64_t*)(b + L.chunks.chunk_begin), (const int32_t*)(b + L.chunks.first_chunk), (double*)(b + L.partial),
+                  (double*)(b + L.x), (double*)(b + L.v), (double*)(b + L.l0), (double*)(b + L.f), (double*)(b + L.dt), (double*)(b + L.a), (double*)(b + L.coef),
                   (int32_t*)(b + L.n), (int32_t*)(b + L.flags), (int32_t*)(b + L.steps)};
 }
 
@@ -304,28 +301,12 @@ extern "C" int m3g_fire_init(const m3g_fire_params* p, int64_t n_atoms, int64_t 
     return M3G_ERR_VALUE;
   }
   const int64_t N = n_atoms, S = n_structs;
-  if (host_offsets[0] != 0 || host_offsets[S] != N) { set_error("m3g_fire_init: offsets must run from 0 to n_atoms"); return M3G_ERR_VALUE; }
-  for (int64_t s = 0; s < S; ++s)
-    if (host_offsets[s + 1] <= host_offsets[s]) { set_error("m3g_fire_init: offsets must increase strictly (every structure holds an atom)"); return M3G_ERR_VALUE; }
+  if (!chunk_offsets_ok("m3g_fire_init", host_offsets, N, S)) return M3G_ERR_VALUE;
   const FireLayout L = fire_layout(N, S);
   if (state_bytes < L.total) { set_error("m3g_fire_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
-  // the chunk table: chunks of <= kFireRows atoms that never straddle a structure
-  std::vector<int32_t> chunk_struct, first_chunk(S + 1);
-  std::vector<int64_t> chunk_begin;
-  for (int64_t s = 0; s < S; ++s) {
-    first_chunk[s] = (int32_t)chunk_struct.size();
-    for (int64_t b = host_offsets[s]; b < host_offsets[s + 1]; b += kFireRows) {
-      chunk_struct.push_back((int32_t)s);
-      chunk_begin.push_back(b);
-    }
-  }
-  first_chunk[S] = (int32_t)chunk_struct.size();
+  const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  char* b = (char*)state;
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.offsets, host_offsets, 8 * (S + 1), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.chunk_struct, chunk_struct.data(), 4 * chunk_struct.size(), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.chunk_begin, chunk_begin.data(), 8 * chunk_begin.size(), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.first_chunk, first_chunk.data(), 4 * (S + 1), hipMemcpyHostToDevice, s));
+  if (int rc = table.upload(L.chunks, (char*)state, host_offsets, S, s)) return rc;
   const int64_t work = 3 * N > S ? 3 * N : S;
   hipLaunchKernelGGL(k_fire_init, dim3((unsigned)((work + kFireRows - 1) / kFireRows)), dim3(kFireRows), 0, s, fire_view(N, S, state), pos,
                      lattice, p->dt, p->astart);
@@ -344,7 +325,7 @@ extern "C" int m3g_fire_step(const m3g_fire_params* p, int64_t n_atoms, int64_t 
   if (state_bytes < fire_layout(N, S).total) { set_error("m3g_fire_step: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
   const FireView st = fire_view(N, S, state);
-  const dim3 grid((unsigned)fire_chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
+  const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_fire_partials, grid, dim3(kFireRows), 0, s, st, p->relax_cell, forces);
   hipLaunchKernelGGL(k_fire_finalize, dim3(1), dim3(kFireRows), 0, s, st, *p, check_only, stresses, lattice, lattice32, unconverged);
   if (!check_only) hipLaunchKernelGGL(k_fire_apply, grid, dim3(kFireRows), 0, s, st, p->relax_cell, forces, pos);

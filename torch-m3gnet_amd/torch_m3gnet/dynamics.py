@@ -1,0 +1,271 @@
+"""Batched molecular dynamics on the device: NVE, NVT (Berendsen, Langevin) and isotropic NPT Berendsen (C ABI: m3g_dyn_*,
+csrc/m3g_dynamics.hip).
+
+The m3gnet package the reference stands in for runs MD through `MolecularDynamics` (ASE's VelocityVerlet "nve", NVTBerendsen "nvt",
+NPTBerendsen "npt_berendsen") on one structure at a time.  `MolecularDynamics.run` takes a whole batch: every structure is integrated
+on its own, with its own target temperature and its own random stream, and its numbers are bitwise the same alone or in any batch.
+Per step the energies, forces and (pair-virial) stresses come from `VerletGraph.step` -- whose skin-test verdict is the loop's only
+wait -- and the integrator of the whole batch is three kernel launches (`dyn_step`); the host copies observables only on log steps.
+NPT moves the cells at every step, so the candidates are searched again at every step (`VerletGraph.set_lattice`), as in the
+variable-cell `Relaxer`.
+
+Units: A, fs, amu, eV; velocities in A/fs; `MolecularDynamics` takes the pressure in GPa and the compressibility in 1/GPa (ASE's
+NPTBerendsen convention), the C ABI in eV/A^3 and A^3/eV."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from . import _cuda, _lib
+from .data import MaterialGraphKey as K
+from .data.atomic_masses import masses_of
+from .data.graph_gpu import _ptr, _stream
+from .data.md import VerletGraph
+from .nn.modules import Gradient
+from .relax import Relaxer
+
+KAPPA = 9.648533215665e-3    # A/fs^2 per eV/(A amu)
+KB = 8.617333262e-5          # eV/K
+EV_PER_A3_IN_GPA = 160.21766208
+ENSEMBLES = {"nve": _lib.DYN_NVE, "nvt_berendsen": _lib.DYN_NVT_BERENDSEN, "nvt_langevin": _lib.DYN_NVT_LANGEVIN,
+             "npt_berendsen": _lib.DYN_NPT_BERENDSEN}
+
+
+def _positive(name, x) -> float:
+    x = float(x)
+    if not (math.isfinite(x) and x > 0.0):
+        raise ValueError(f"{name} must be a finite number > 0; got {x}")
+    return x
+
+
+def maxwell_boltzmann(masses, temperature: float, seed: int = 0) -> np.ndarray:
+    """Velocities [n, 3] (A/fs, host numpy) of one structure drawn from the Maxwell-Boltzmann distribution at `temperature` (K), seeded,
+    with zero total momentum and rescaled to exactly `temperature` (3n degrees of freedom, as ASE's get_temperature).  A single atom,
+    or T = 0, gets zero velocity."""
+    m = np.asarray(masses, dtype=np.float64).reshape(-1)
+    temperature = float(temperature)
+    if not (math.isfinite(temperature) and temperature >= 0.0) or not (np.isfinite(m).all() and (m > 0).all()):
+        raise ValueError("maxwell_boltzmann needs a finite temperature >= 0 and finite masses > 0")
+    rng = np.random.default_rng(seed)
+    v = rng.normal(size=(len(m), 3)) * np.sqrt(KB * temperature * KAPPA / m)[:, None]
+    v -= (m[:, None] * v).sum(0) / m.sum()
+    t_now = (m * (v * v).sum(1)).sum() / KAPPA / (3.0 * len(m) * KB)
+    if temperature == 0.0 or t_now == 0.0:
+        return np.zeros_like(v)
+    return v * np.sqrt(temperature / t_now)
+
+
+def structure_seeds(seed, n_structs: int) -> np.ndarray:
+    """Per-structure 64-bit Philox keys: `seed` itself when it is a sequence of S integers, else derived from (seed, s)."""
+    if np.ndim(seed) == 1:
+        seeds = np.asarray(seed, dtype=np.uint64)
+        if len(seeds) != n_structs:
+            raise ValueError(f"seed: expected one per structure ({n_structs}); got {len(seeds)}")
+        return seeds
+    return np.array([np.random.SeedSequence([int(seed), s]).generate_state(1, np.uint64)[0] for s in range(n_structs)], dtype=np.uint64)
+
+
+class DynState:
+    """MD state of a batch on the device (m3g_dyn_init): masses, velocities (fp64), target temperatures, seeds, flags and step counts.
+    `pos` ([N,3] fp64, unwrapped) and `lattice` ([S,3,3] fp64, may be None except in NPT) are the caller's tensors: `dyn_step` moves
+    them IN PLACE (and `lattice32`, their fp32 copy).  `velocities` [N,3] fp64 device: copied.  `offsets`: S + 1 atom offsets, strictly
+    increasing.  Parameters in the C ABI's units: dt, taut, taup in fs, friction in 1/fs, pressure in eV/A^3, compressibility in
+    A^3/eV.  `obs` [S,4] (KE eV, T K, P eV/A^3, V A^3) is written by every `dyn_step`."""
+
+    def __init__(self, pos: torch.Tensor, lattice: torch.Tensor | None, offsets: Sequence[int], masses, velocities: torch.Tensor,
+                 temperatures, seeds, ensemble: str = "nve", dt: float = 1.0, taut: float = 100.0, friction: float = 0.01,
+                 pressure: float = 0.0, taup: float = 1000.0, compressibility: float = 1.0, fix_com: bool = False):
+        if ensemble not in ENSEMBLES:
+            raise ValueError(f"unknown ensemble {ensemble!r}; expected one of {sorted(ENSEMBLES)}")
+        self.ensemble = ensemble
+        self.params = _lib.M3GDynParams(ensemble=ENSEMBLES[ensemble], fix_com=1 if fix_com else 0, dt=dt, taut=taut, friction=friction,
+                                        pressure=pressure, taup=taup, compressibility=compressibility)
+        if pos.dtype != torch.float64 or pos.dim() != 2 or pos.size(1) != 3 or not pos.is_contiguous():
+            raise ValueError("pos must be a contiguous [N, 3] float64 tensor")
+        self.offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+        self.N, self.S = int(pos.size(0)), int(len(self.offsets) - 1)
+        if self.S < 1:
+            raise ValueError("offsets must hold S + 1 >= 2 entries")
+        if lattice is not None and (lattice.dtype != torch.float64 or tuple(lattice.shape) != (self.S, 3, 3) or not lattice.is_contiguous()):
+            raise ValueError(f"lattice must be a contiguous [{self.S}, 3, 3] float64 tensor")
+        if ensemble == "npt_berendsen" and lattice is None:
+            raise ValueError("NPT needs the lattice")
+        if velocities.dtype != torch.float64 or tuple(velocities.shape) != (self.N, 3) or velocities.device != pos.device:
+            raise ValueError(f"velocities must be a [{self.N}, 3] float64 tensor on {pos.device}")
+        self.masses = np.ascontiguousarray(np.asarray(masses, dtype=np.float64).reshape(-1))
+        self.temperatures = np.ascontiguousarray(np.broadcast_to(np.asarray(temperatures, dtype=np.float64), (self.S,)))
+        self.seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+        if len(self.masses) != self.N or len(self.seeds) != self.S:
+            raise ValueError(f"expected {self.N} masses and {self.S} seeds")
+        self.pos, self.lattice = pos, lattice
+        self.lattice32 = lattice.to(torch.float32) if lattice is not None else None
+        self.device = pos.device
+        self.lib = _lib.load_library()
+        nbytes = C.c_size_t()
+        _lib.check(self.lib.m3g_dyn_state_bytes(self.N, self.S, C.byref(nbytes)))
+        self.state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self.obs = torch.full((self.S, 4), float("nan"), dtype=torch.float64, device=self.device)
+        vel = velocities.contiguous()
+        with _cuda.on_device(self.device):
+            _lib.check(self.lib.m3g_dyn_init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, self.masses.ctypes.data,
+                                             self.temperatures.ctypes.data, self.seeds.ctypes.data, _ptr(vel), _ptr(self.state),
+                                             self.state.numel(), _stream()))
+
+    def read(self) -> dict:
+        """flags / n_steps [S] and the velocities [N, 3], copied to the host (waits for the stream)."""
+        out = {"flags": np.empty(self.S, np.int32), "n_steps": np.empty(self.S, np.int64), "v": np.empty((self.N, 3))}
+        with _cuda.on_device(self.device):
+            _lib.check(self.lib.m3g_dyn_read(self.N, self.S, _ptr(self.state), self.state.numel(), out["flags"].ctypes.data,
+                                             out["n_steps"].ctypes.data, out["v"].ctypes.data, _stream()))
+        return out
+
+
+def dyn_step(state: DynState, forces: torch.Tensor, stresses: torch.Tensor | None = None, finish_only: bool = False) -> None:
+    """One MD call of the batch (m3g_dyn_step) at `forces` [N,3] and `stresses` [S,6] (float32, pair-virial convention; required in
+    NPT) evaluated at `state.pos`: finish the step that ends here, write `state.obs`, start the next one (not with `finish_only`).
+    Queued on the current stream; no wait, capture-safe."""
+    if forces.dtype != torch.float32 or tuple(forces.shape) != (state.N, 3) or not forces.is_contiguous():
+        raise ValueError(f"forces must be a contiguous [{state.N}, 3] float32 tensor")
+    if stresses is not None and (stresses.dtype != torch.float32 or tuple(stresses.shape) != (state.S, 6) or not stresses.is_contiguous()):
+        raise ValueError(f"stresses must be a contiguous [{state.S}, 6] float32 tensor")
+    with _cuda.on_device(state.device):
+        _lib.check(state.lib.m3g_dyn_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
+                                          _ptr(stresses), _ptr(state.pos), _ptr(state.lattice), _ptr(state.lattice32), 1 if finish_only else 0,
+                                          _ptr(state.obs), _stream()))
+
+
+class MolecularDynamics:
+    """Batched counterpart of m3gnet's `MolecularDynamics`.
+
+    `model`: the `Gradient` returned by `build_model`; the run evaluates a `pair_virial=True` engine made from its `Sequential` (the
+    pressure needs the strain derivative).  ensemble: "nvt_langevin" (BAOAB with `friction`, 1/fs), "nve", "nvt_berendsen" (`taut`, fs)
+    or "npt_berendsen" (`taut`, `taup`, `pressure` in GPa, `compressibility` in 1/GPa -- required).  `temperature`: K, one value or one
+    per structure (the target of the thermostats and the temperature of the starting velocities).  `fix_com` (zero the total momentum
+    at every step) defaults to True where the ensemble allows it (not with Langevin).  `seed`: an integer, or one per structure."""
+
+    def __init__(self, model: Gradient, ensemble: str = "nvt_langevin", timestep: float = 1.0, temperature=300.0, taut: float | None = None,
+                 friction: float = 0.01, pressure: float = 0.0, taup: float | None = None, compressibility: float | None = None,
+                 fix_com: bool | None = None, skin: float = 0.5, seed=0, device="cuda"):
+        if not isinstance(model, Gradient):
+            raise TypeError("MolecularDynamics needs the Gradient model returned by build_model")
+        if not isinstance(ensemble, str) or ensemble not in ENSEMBLES:
+            raise ValueError(f"unknown ensemble {ensemble!r}; expected one of {sorted(ENSEMBLES)}")
+        self.ensemble = ensemble
+        self.timestep = _positive("timestep", timestep)
+        self.taut = _positive("taut", 100.0 * self.timestep if taut is None else taut)
+        self.taup = _positive("taup", 1000.0 * self.timestep if taup is None else taup)
+        friction = float(friction)
+        if not (math.isfinite(friction) and friction >= 0.0):
+            raise ValueError(f"friction must be a finite number >= 0; got {friction}")
+        self.friction = friction
+        self.pressure = float(pressure)
+        if not math.isfinite(self.pressure):
+            raise ValueError(f"pressure must be finite; got {self.pressure}")
+        if ensemble == "npt_berendsen":
+            if compressibility is None:
+                raise ValueError("npt_berendsen needs the compressibility (1/GPa)")
+            compressibility = _positive("compressibility", compressibility)
+        self.compressibility = compressibility
+        if fix_com is None:
+            fix_com = ensemble != "nvt_langevin"
+        if fix_com and ensemble == "nvt_langevin":
+            raise ValueError("fix_com is not supported with the Langevin thermostat")
+        self.fix_com = bool(fix_com)
+        t = np.asarray(temperature, dtype=np.float64)
+        if t.ndim > 1 or not (np.isfinite(t).all() and (t >= 0).all()):
+            raise ValueError("temperature must be one finite value >= 0 (K) or one per structure")
+        self.temperature = t
+        self.skin = _positive("skin", skin)
+        self.seed = seed
+        self.model = Gradient(model.model, pair_virial=True, legendre_backward=model.legendre_backward)
+        if model._engine is not None:
+            self.model.engine.set_precision(model._engine.precision)
+        self.device = torch.device(device)
+
+    def _params(self) -> dict:
+        beta = 1.0 if self.compressibility is None else self.compressibility * EV_PER_A3_IN_GPA   # 1/GPa -> A^3/eV
+        return dict(ensemble=self.ensemble, dt=self.timestep, taut=self.taut, friction=self.friction,
+                    pressure=self.pressure / EV_PER_A3_IN_GPA, taup=self.taup, compressibility=beta, fix_com=self.fix_com)
+
+    def run(self, lattices: Sequence, positions: Sequence, atomic_numbers: Sequence, steps: int, velocities: Sequence | None = None,
+            masses: Sequence | None = None, loginterval: int = 10) -> list:
+        """Integrate every structure (lattices: [3,3] rows = lattice vectors, positions: [n_s,3] Cartesian, atomic_numbers: [n_s])
+        for `steps` steps.  velocities: [n_s,3] A/fs per structure (default: Maxwell-Boltzmann at the temperature, zero momentum);
+        masses: [n_s] amu per structure (default: standard atomic weights).  Returns one dict per structure: positions (unwrapped),
+        velocities, lattice, total_energy, forces, stresses (pair virial) at the final step, n_steps, error (its forces became
+        non-finite: it was stopped where it stood), and `log`: arrays step, e_pot, ke (eV), t (K), p (GPa), v (A^3) every
+        `loginterval` steps and at the last one."""
+        if isinstance(steps, bool) or int(steps) != steps or steps < 0:
+            raise ValueError(f"steps must be an integer >= 0; got {steps}")
+        if isinstance(loginterval, bool) or int(loginterval) != loginterval or loginterval < 1:
+            raise ValueError(f"loginterval must be an integer >= 1; got {loginterval}")
+        steps, loginterval = int(steps), int(loginterval)
+        lat, pos, z = Relaxer._arrays(lattices, positions, atomic_numbers)
+        S = len(z)
+        temps = np.broadcast_to(self.temperature, (S,)) if self.temperature.ndim == 0 or len(self.temperature) == S else None
+        if temps is None:
+            raise ValueError(f"temperature: expected one value or one per structure ({S}); got {len(self.temperature)}")
+        seeds = structure_seeds(self.seed, S)
+        if masses is None:
+            m = [masses_of(a) for a in z]
+        else:
+            if len(masses) != S:
+                raise ValueError("masses: expected one array per structure")
+            m = [np.asarray(x, dtype=np.float64).reshape(-1) for x in masses]
+            for s, (ms, a) in enumerate(zip(m, z)):
+                if len(ms) != len(a) or not (np.isfinite(ms).all() and (ms > 0).all()):
+                    raise ValueError(f"structure {s}: masses must be {len(a)} finite values > 0")
+        if velocities is None:
+            vel = [maxwell_boltzmann(ms, t, int(sd)) for ms, t, sd in zip(m, temps, seeds)]
+        else:
+            if len(velocities) != S:
+                raise ValueError("velocities: expected one array per structure")
+            vel = [np.asarray(v, dtype=np.float64) for v in velocities]
+            for s, (v, a) in enumerate(zip(vel, z)):
+                if v.shape != (len(a), 3) or not np.isfinite(v).all():
+                    raise ValueError(f"structure {s}: velocities must be a finite [{len(a)}, 3] array")
+        model = self.model
+        cfg = model.engine.cfg
+        vg = VerletGraph(lat, z, cfg.cutoff, cfg.threebody_cutoff, skin=self.skin, device=self.device)
+        pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=vg.device)
+        offsets = np.concatenate([[0], np.cumsum([len(a) for a in z])])
+        lat64 = vg.lattice.clone()   # the NPT launches write the scaled cells here
+        npt = self.ensemble == "npt_berendsen"
+        dyn = DynState(pos_t, lat64, offsets, np.concatenate(m), torch.tensor(np.concatenate(vel), device=vg.device), temps, seeds,
+                       **self._params())
+        log = {key: [] for key in ("step", "e_pot", "ke", "t", "p", "v")}
+        out = None
+        for k in range(steps + 1):
+            out = vg.step(model, pos_t)   # waits for the skin test (the previous dyn_step has been queued before it)
+            dyn_step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=(k == steps))
+            if k % loginterval == 0 or k == steps:   # (host copies on log steps only)
+                obs = dyn.obs.cpu().numpy()
+                log["step"].append(np.full(S, k))
+                log["e_pot"].append(out[K.TOTAL_ENERGY].double().cpu().numpy())
+                for j, key in enumerate(("ke", "t", "p", "v")):
+                    log[key].append(obs[:, j] * (EV_PER_A3_IN_GPA if key == "p" else 1.0))
+            if npt and k < steps:
+                vg.set_lattice(list(lat64.cpu().numpy()))   # (waits: the candidate search in the new cells needs them on the host)
+        # the sticky error bits of the last step's topology (m3g_md_step checks those of the EARLIER steps only)
+        if vg._md_buffers is not None and vg._lists_owner == "c":
+            n_e, n_t = vg._step_sizes
+            status = C.c_int32()
+            with _cuda.on_device(vg.device):
+                _lib.check(vg.lib.m3g_topology_status(vg.N, n_e, n_t, vg.S, _ptr(vg._md_buffers["topo"]), C.byref(status), _stream()))
+            if status.value:
+                raise RuntimeError(f"molecular dynamics: the last evaluation left error bits {status.value:#x} on its topology (M3G_TOPO_ERR_*)")
+        st = dyn.read()
+        e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
+        p_host, l_host = pos_t.cpu().numpy(), lat64.cpu().numpy()
+        logs = {key: np.stack(val, axis=1) for key, val in log.items()}   # [S, n_log]
+        res = []
+        for s in range(S):
+            a, b = int(offsets[s]), int(offsets[s + 1])
+            res.append({"positions": p_host[a:b].copy(), "velocities": st["v"][a:b].copy(), "lattice": l_host[s].copy(),
+                        "total_energy": float(e[s]), "forces": f[a:b].copy(), "stresses": sv[s].copy(), "n_steps": int(st["n_steps"][s]),
+                        "error": bool(st["flags"][s] & _lib.DYN_ERROR), "log": {key: val[s].copy() for key, val in logs.items()}})
+        return res
