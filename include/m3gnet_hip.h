@@ -529,6 +529,43 @@ int m3g_dyn_step(const m3g_dyn_params* params, int64_t n_atoms, int64_t n_struct
 int m3g_dyn_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes, int32_t* host_flags, int64_t* host_steps,
                  double* host_vel, void* stream);
 
+/* ---- batched nudged elastic band: climbing-image NEB force projection (csrc/m3g_neb.hip) ----------------------------------------
+ * Replaces ASE's NEB.get_forces (NEB(images, k, climb, method="improvedtangent"), the forces an ASE optimiser drives on the host, one
+ * image at a time) for a whole batch of bands.  A band has M >= 3 images: fixed endpoints 0 and M-1 (given once, to m3g_neb_init) and
+ * M-2 interior images (the rows of `pos`); all images of a band share the atom count, species order and cell.  For interior image i
+ * with energies V and positions R (3n vectors, never wrapped):
+ *   tau+ = R_i+1 - R_i, tau- = R_i - R_i-1;
+ *   tau  = tau+ if V_i+1 > V_i > V_i-1;  tau- if V_i+1 < V_i < V_i-1;  otherwise, with dVmax / dVmin the max / min of |V_i+1 - V_i| and
+ *          |V_i-1 - V_i|: dVmax tau+ + dVmin tau- if V_i+1 > V_i-1, else dVmin tau+ + dVmax tau-  (the f32 energies, compared exactly);
+ *   ordinary image:  F_neb = F - (F.tau_hat) tau_hat + k (|tau+| - |tau-|) tau_hat  (ASE's improved parallel spring, one k per band);
+ *   climbing image (a band with climb = 1: its interior image of highest energy, LOWEST index on ties -- ASE takes the last entry of
+ *          an argsort -- re-chosen at every call):  F_neb = F - 2 (F.tau_hat) tau_hat, no spring.
+ * Every F_neb is F + alpha tau+ + beta tau- with two scalars per image, which follow in closed form from five per-image sums (|tau+|^2,
+ * |tau-|^2, tau+.tau-, F.tau+, F.tau-).  An image with a non-finite position (its own or a neighbour's), energy or force, or with
+ * |tau| = 0, gets NaN rows: m3g_fire_step then flags its band M3G_FIRE_ERROR and freezes it.  The optimiser is ASE's: m3g_fire_step
+ * with relax_cell = 0 over the NEB forces, with FIRE offsets of one structure per band covering all of its interior atoms (ASE's FIRE
+ * over the NEB optimizable: one dt / v per band, maxstep clipped over the norm of the whole band, converged when max |F_neb| < fmax
+ * over the band's interior rows).  No atomics: a band's results are bitwise the same alone or in any batch.
+ * The state buffer (m3g_neb_state_bytes) is caller-owned device memory: the chunk table of the interior images, the neighbour table,
+ * k, climb, the endpoint rows and energies, per-image scalars. */
+#define M3G_NEB_ROWS 5   /* observables per interior image: |tau+|, |tau-|, F.tau_hat, spring term (0 at the climbing image), climbing (0 / 1) */
+/* 1 <= n_bands <= n_images <= n_atoms, else M3G_ERR_VALUE. */
+int m3g_neb_state_bytes(int64_t n_atoms, int64_t n_images, int64_t n_bands, size_t* bytes);
+/* n_atoms: interior atoms of the batch; n_images: interior images I; n_bands: B.  HOST host_image_offsets [I+1] (int64, 0 = o_0 < ... <
+ * o_I = n_atoms: atoms of interior image i), host_band_images [B+1] (int32, 0 = b_0 < ... < b_B = I: interior images of band b; the images
+ * of a band in path order), host_k [B] (eV/A^2, finite, > 0), host_climb [B] (0 / 1), host_endpoint_energies [2B] (initial, final per
+ * band; finite).  endpoint_pos DEVICE fp64 [2 sum_b n_b, 3]: per band its initial image rows, then its final image rows (copied into the
+ * state).  Everything is checked on the host before any HIP call: bad offsets, a band without interior image, images of one band with
+ * different atom counts, k <= 0 or not finite, climb not 0 / 1, non-finite endpoint energies -> M3G_ERR_VALUE.  Waits for the stream. */
+int m3g_neb_init(int64_t n_atoms, int64_t n_images, int64_t n_bands, const int64_t* host_image_offsets, const int32_t* host_band_images,
+                 const double* host_k, const int32_t* host_climb, const double* endpoint_pos, const double* host_endpoint_energies,
+                 void* state, size_t state_bytes, void* stream);
+/* NEB forces of every interior image: pos [N,3] fp64, energies [I] f32, forces [N,3] f32 (evaluated at pos) DEVICE; neb_forces [N,3]
+ * f32 DEVICE (written: the forces m3g_fire_step takes); rows [I, M3G_NEB_ROWS] fp64 DEVICE or NULL.  Three launches whatever the batch,
+ * no allocation, copy or wait: capture-safe. */
+int m3g_neb_forces(int64_t n_atoms, int64_t n_images, int64_t n_bands, void* state, size_t state_bytes, const double* pos,
+                   const float* energies, const float* forces, float* neb_forces, double* rows, void* stream);
+
 /* ---- measurement: per-stage device time from HIP events recorded on the call's own stream ---------
  * m3g_profile_enable(plan, 1) makes every following m3g_energy_forces record an event pair around each
  * stage launch; m3g_profile_read synchronises those events, returns per-stage totals since the last
@@ -560,14 +597,15 @@ int m3g_debug_radix_sort(int32_t key_bytes, int64_t n, void* keys, int32_t* vals
 int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes, int32_t* kernel_launches,
                        int32_t* other_operations);
 
-#define M3G_ABI_VERSION 8   /* 2: m3g_io.topo_hints, m3g_topology_hints; 3: m3g_verlet_*, m3g_topology_status, hints word certified on the buffer,
+#define M3G_ABI_VERSION 9   /* 2: m3g_io.topo_hints, m3g_topology_hints; 3: m3g_verlet_*, m3g_topology_status, hints word certified on the buffer,
                              * canonical edge order by the shift relative to the given coordinates, default precision fp32;
                              * 4: m3g_verlet_fill_lists, m3g_topology_build_canonical, M3G_TOPO_ERR_SYNC, options small_tiles / small_launches / fuse_node_tb;
                              * 5: m3g_topology_build_canonical_begin / _end, m3g_topology_data_bytes, option legendre_backward, m3g_md_*;
                              * 6: M3G_TOPO_ERR_SPECIES (species checked on the library side, m3g_md_step returns M3G_ERR_VALUE), m3g_count_launches,
                              *    m3g_debug_exclusive_scan / m3g_debug_radix_sort (the library's own scan and sort: no hipCUB);
                              * 7: m3g_fire_* (batched FIRE relaxation, fixed or variable cell);
-                             * 8: m3g_dyn_* (batched molecular dynamics: NVE, NVT Berendsen / Langevin, NPT Berendsen) */
+                             * 8: m3g_dyn_* (batched molecular dynamics: NVE, NVT Berendsen / Langevin, NPT Berendsen);
+                             * 9: m3g_neb_* (batched climbing-image NEB force projection, improved tangent; replaces ASE's NEB.get_forces) */
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ _PKG_ROOT = Path(__file__).resolve().parent.parent  # .../torch-m3gnet_amd
 LIB_PATH = _PKG_ROOT / "lib" / "libm3gnet_hip.so"
 
 M3G_OK, M3G_ERR_VALUE, M3G_ERR_STATE, M3G_ERR_SIZE, M3G_ERR_HIP, M3G_ERR_UNSUPPORTED = range(6)
-ABI_VERSION = 8
+ABI_VERSION = 9
 VERLET_FILL_LISTS_MAX_ROW = 1024   # M3G_VERLET_FILL_LISTS_MAX_ROW (include/m3gnet_hip.h)
 
 
@@ -75,6 +75,7 @@ class M3GDynParams(C.Structure):   # m3g_dyn_params
 
 DYN_NVE, DYN_NVT_BERENDSEN, DYN_NVT_LANGEVIN, DYN_NPT_BERENDSEN = range(4)   # M3G_DYN_* ensembles
 DYN_STARTED, DYN_ERROR = 1, 2                                               # M3G_DYN_* flag bits
+NEB_ROWS = 5                                                                 # M3G_NEB_ROWS
 
 # name -> (restype, argtypes); every symbol include/m3gnet_hip.h declares
 SYMBOLS = {
@@ -170,6 +171,11 @@ SYMBOLS = {
     "m3g_dyn_step": (C.c_int, [C.POINTER(M3GDynParams), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "m3g_dyn_read": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_neb_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "m3g_neb_init": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_size_t, C.c_void_p]),
+    "m3g_neb_forces": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
     "m3g_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "m3g_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_float),
                                    C.POINTER(C.c_int32)]),
