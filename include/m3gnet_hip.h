@@ -566,6 +566,55 @@ int m3g_neb_init(int64_t n_atoms, int64_t n_images, int64_t n_bands, const int64
 int m3g_neb_forces(int64_t n_atoms, int64_t n_images, int64_t n_bands, void* state, size_t state_bytes, const double* pos,
                    const float* energies, const float* forces, float* neb_forces, double* rows, void* stream);
 
+/* ---- batched finite-displacement phonons: force constants and dynamical matrices (csrc/m3g_phonons.hip) ---------------------------
+ * Replaces phonopy's finite-displacement workflow over an ASE calculator (Phonopy(unitcell, supercell_matrix=diag(n1, n2, n3))
+ * .generate_displacements(distance=delta, is_plusminus=True, no symmetry) -> one calculator call per displaced supercell ->
+ * produce_force_constants -> symmetrize nothing but the acoustic sum rule -> get_dynamical_matrix_at_q) for a whole batch of structures.
+ * Structure s: n_u unit atoms at r_b (Cartesian, A), cell L (rows = lattice vectors), diagonal supercell n1 x n2 x n3, N_s = n_u n1 n2 n3.
+ *   supercell atom j = l n_u + b, l = (l1 n2 + l2) n3 + l3, at r_b + l1 L_0 + l2 L_1 + l3 L_2 (the home copy of atom u is j = u);
+ *   displaced batch: per structure 1 + 6 n_u copies of its N_s rows -- copy 0 undisplaced (the residual forces), copy 1 + 6u + 2a + k
+ *          with the home atom u moved by +delta (k = 0) or -delta (k = 1) along Cartesian axis a; structures one after another;
+ *   force constants (phonopy's compact layout, fp64 from the fp32 forces): Phi[u, j, a, b] = -(F+_jb - F-_jb) / (2 delta) over the
+ *          copies of (u, a); with asr the self term Phi[u, u] is replaced so that sum_j Phi[u, j, a, b] = 0; the raw sums over j are
+ *          reported either way.  A structure with a non-finite force in any of its copies gets NaN force constants and sums and a
+ *          non-zero count; the others are unaffected;
+ *   dynamical matrix (phonopy's convention, q in fractional coordinates of the reciprocal lattice of the unit cell):
+ *          D_ua,vb(q) = sum_l sum_m w_m Phi[u, l n_u + v, a, b] exp(2 pi i q.d_m) / sqrt(m_u m_v), d_m the shortest vectors from home
+ *          atom u to supercell atom l n_u + v in the supercell's periodicity (unit-cell fractional coordinates; supercell translations
+ *          {-2..2}^3 searched, images within 1e-5 A of the shortest tied), w_m = 1 / multiplicity; then (D + D^H) / 2.
+ * The image table is built once by m3g_ph_init on the host in fp64.  No atomics: a structure's results are bitwise the same alone or in
+ * any batch. */
+#define M3G_PH_MAX_MULTIPLICITY 27   /* tied shortest images per (u, j) pair the table holds */
+typedef struct {
+  int64_t n_structs;      /* S */
+  int64_t n_unit_atoms;   /* U = sum_s n_u */
+  int64_t n_super_atoms;  /* sum_s N_s; the displaced batch has 6 n_pairs + n_super_atoms rows */
+  int64_t n_pairs;        /* sum_s n_u N_s: rows of Phi */
+} m3g_ph_sizes;
+/* 1 <= n_structs <= n_unit_atoms <= n_super_atoms <= n_pairs, else M3G_ERR_VALUE. */
+int m3g_ph_state_bytes(const m3g_ph_sizes* sizes, size_t* bytes);
+/* HOST host_unit_offsets [S+1] (int64, 0 = o_0 < ... < o_S = U), host_supercells [S,3] (int32, >= 1), host_lattices [S,3,3] fp64,
+ * host_positions [U,3] fp64 (unit cells, Cartesian), host_masses [U] fp64 (amu); delta (A).  Everything is checked on the host before
+ * any HIP call: bad offsets, supercell dims < 1, delta not finite or <= 0, masses not finite or <= 0, a singular or non-finite cell,
+ * non-finite positions, sizes that do not match the offsets and supercells, more than M3G_PH_MAX_MULTIPLICITY tied images of one pair
+ * -> M3G_ERR_VALUE.  Waits for the stream. */
+int m3g_ph_init(const m3g_ph_sizes* sizes, const int64_t* host_unit_offsets, const int32_t* host_supercells, const double* host_lattices,
+                const double* host_positions, const double* host_masses, double delta, void* state, size_t state_bytes, void* stream);
+/* The positions of every row of the displaced batch: pos [6 n_pairs + n_super_atoms, 3] fp64 DEVICE (written).  One launch, no
+ * allocation, copy or wait: capture-safe. */
+int m3g_ph_displace(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, double* pos, void* stream);
+/* forces [6 n_pairs + n_super_atoms, 3] f32 DEVICE (of the displaced batch, in its row order); asr 0 / 1; phi [n_pairs, 3, 3] fp64, sums
+ * [U, 9] fp64 (raw sum_j Phi[u, j]), nonfinite [S] int32 (non-finite force values of the structure) DEVICE, written.  One launch,
+ * capture-safe. */
+int m3g_ph_force_constants(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const float* forces, int32_t asr, double* phi,
+                           double* sums, int32_t* nonfinite, void* stream);
+/* Dynamical matrices of n_q q-points: q [n_q, 3] fp64 (fractional), q_struct [n_q] int32 (the structure of each q) DEVICE; dynmat
+ * [n_q, 3 max_unit_atoms, 3 max_unit_atoms] complex128 (interleaved re, im) DEVICE: the leading 3 n_u x 3 n_u block of each q is
+ * written, the rest left as it is; a q whose structure has more than max_unit_atoms atoms or lies outside [0, S) is skipped.  One
+ * launch, capture-safe. */
+int m3g_ph_dynmat(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const double* phi, int64_t n_q, const double* q,
+                  const int32_t* q_struct, int32_t max_unit_atoms, double* dynmat, void* stream);
+
 /* ---- measurement: per-stage device time from HIP events recorded on the call's own stream ---------
  * m3g_profile_enable(plan, 1) makes every following m3g_energy_forces record an event pair around each
  * stage launch; m3g_profile_read synchronises those events, returns per-stage totals since the last
@@ -597,7 +646,7 @@ int m3g_debug_radix_sort(int32_t key_bytes, int64_t n, void* keys, int32_t* vals
 int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes, int32_t* kernel_launches,
                        int32_t* other_operations);
 
-#define M3G_ABI_VERSION 9   /* 2: m3g_io.topo_hints, m3g_topology_hints; 3: m3g_verlet_*, m3g_topology_status, hints word certified on the buffer,
+#define M3G_ABI_VERSION 10  /* 2: m3g_io.topo_hints, m3g_topology_hints; 3: m3g_verlet_*, m3g_topology_status, hints word certified on the buffer,
                              * canonical edge order by the shift relative to the given coordinates, default precision fp32;
                              * 4: m3g_verlet_fill_lists, m3g_topology_build_canonical, M3G_TOPO_ERR_SYNC, options small_tiles / small_launches / fuse_node_tb;
                              * 5: m3g_topology_build_canonical_begin / _end, m3g_topology_data_bytes, option legendre_backward, m3g_md_*;
@@ -605,7 +654,8 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *    m3g_debug_exclusive_scan / m3g_debug_radix_sort (the library's own scan and sort: no hipCUB);
                              * 7: m3g_fire_* (batched FIRE relaxation, fixed or variable cell);
                              * 8: m3g_dyn_* (batched molecular dynamics: NVE, NVT Berendsen / Langevin, NPT Berendsen);
-                             * 9: m3g_neb_* (batched climbing-image NEB force projection, improved tangent; replaces ASE's NEB.get_forces) */
+                             * 9: m3g_neb_* (batched climbing-image NEB force projection, improved tangent; replaces ASE's NEB.get_forces);
+                             * 10: m3g_ph_* (batched finite-displacement phonons: displaced supercells, force constants, dynamical matrices) */
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,410 @@
+// Batched finite-displacement phonons (phonopy's method: diagonal supercell, no symmetry reduction; phonopy's
+// produce_force_constants / get_dynamical_matrix_at_q over an ASE calculator).  Without it, every displaced supercell is one host
+// round trip to a calculator.  Here the displaced supercells of every structure of a batch are one batch of the engine, and the three
+// stages around that evaluation are one launch each:
+//   k_ph_displace          a thread per row of the displaced batch: the supercell position of the row, written from the unit cells in
+//                          the state straight into the fp64 `pos` the engine reads;
+//   k_ph_force_constants   one workgroup per (structure, home atom u): Phi[u, j] from the + and - force rows of u's six displaced
+//                          copies, the nine row sums over j (lane-strided, then a fixed tree), the ASR self term, and the count of
+//                          non-finite forces of the whole structure (every workgroup of the structure counts the same rows in the same
+//                          order; a structure with one gets NaN force constants);
+//   k_ph_dynmat            a thread per (q, u <= v): the two 3x3 blocks D(u,v), D(v,u) over the image table (one sincospi per image for
+//                          all nine entries, q.d reduced mod 1 first), mass weighting, Hermitisation, blocks (u,v) and (v,u) written.
+// No atomics: every result depends on its structure's own inputs only, so it is bitwise the same alone or in any batch.  No allocation,
+// copy or wait in the three compute calls (capture-safe).
+//
+// Layouts (structure s: n_u unit atoms, supercell n1 x n2 x n3, N_s = n_u n1 n2 n3 supercell atoms).  Supercell atom j = l n_u + b with
+// l = (l1 n2 + l2) n3 + l3, at r_b + l1 L_0 + l2 L_1 + l3 L_2.  The displaced batch holds per structure 1 + 6 n_u copies of N_s rows:
+// copy 0 undisplaced, copy 1 + 6u + 2a + k the home atom u (j = u) moved by +delta (k = 0) or -delta (k = 1) along axis a.
+// Phi [sum_s n_u N_s, 3, 3]: structure s from 9 pair_off[s], row u N_s + j.
+#include <cmath>
+#include <vector>
+
+#include "m3g_internal.h"
+
+namespace m3g {
+namespace {
+constexpr int kMaxMult = M3G_PH_MAX_MULTIPLICITY;   // shortest images per (u, j) pair kept in the table
+constexpr int kFcThreads = 256;
+constexpr int kDynThreads = 64;
+
+struct PhLayout {
+  size_t row_off, unit_off, pair_off, dims, lat, unit_pos, mass, unit_struct, delta, img_count, img_d, total;
+};
+PhLayout ph_layout(const m3g_ph_sizes& z) {
+  PhLayout L{};
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
+  const int64_t S = z.n_structs, U = z.n_unit_atoms, P = z.n_pairs;
+  L.row_off = take(8 * (S + 1));
+  L.unit_off = take(8 * (S + 1));
+  L.pair_off = take(8 * (S + 1));
+  L.dims = take(4 * 3 * S);
+  L.lat = take(8 * 9 * S);
+  L.unit_pos = take(8 * 3 * U);
+  L.mass = take(8 * U);
+  L.unit_struct = take(4 * U);
+  L.delta = take(8);
+  L.img_count = take(4 * P);
+  L.img_d = take(8 * 3 * kMaxMult * P);
+  L.total = o;
+  return L;
+}
+
+struct PhView {
+  int64_t S, U, rows;
+  const int64_t *row_off, *unit_off, *pair_off;   // [S+1]: displaced rows, unit atoms, (u, j) pairs
+  const int32_t* dims;                            // [S, 3]
+  const double* lat;                              // [S, 9] rows = lattice vectors
+  const double* unit_pos;                         // [U, 3]
+  const double* mass;                             // [U]
+  const int32_t* unit_struct;                     // [U]
+  const double* delta;                            // [1]
+  const int32_t* img_count;                       // [P]
+  const double* img_d;                            // [P, kMaxMult, 3] unit-cell fractional
+};
+PhView ph_view(const m3g_ph_sizes& z, const void* state) {
+  const PhLayout L = ph_layout(z);
+  const char* b = (const char*)state;
+  return PhView{z.n_structs, z.n_unit_atoms, 6 * z.n_pairs + z.n_super_atoms,
+                (const int64_t*)(b + L.row_off), (const int64_t*)(b + L.unit_off), (const int64_t*)(b + L.pair_off),
+                (const int32_t*)(b + L.dims), (const double*)(b + L.lat), (const double*)(b + L.unit_pos), (const double*)(b + L.mass),
+                (const int32_t*)(b + L.unit_struct), (const double*)(b + L.delta), (const int32_t*)(b + L.img_count),
+                (const double*)(b + L.img_d)};
+}
+
+__global__ void __launch_bounds__(256) k_ph_displace(PhView st, double* __restrict__ pos) {
+#pragma clang fp contract(off)
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= st.rows) return;
+  int64_t lo = 0, hi = st.S - 1;   // the structure of row r: the last s with row_off[s] <= r
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) / 2;
+    if (st.row_off[mid] <= r) lo = mid; else hi = mid - 1;
+  }
+  const int64_t s = lo;
+  const int64_t nu = st.unit_off[s + 1] - st.unit_off[s];
+  const int n1 = st.dims[3 * s], n2 = st.dims[3 * s + 1], n3 = st.dims[3 * s + 2];
+  const int64_t ns = nu * n1 * n2 * n3;
+  const int64_t local = r - st.row_off[s];
+  const int64_t copy = local / ns, j = local % ns;
+  const int64_t l = j / nu, b = j % nu;
+  const double l1 = (double)(l / ((int64_t)n2 * n3)), l2 = (double)((l / n3) % n2), l3 = (double)(l % n3);
+  const double* L = st.lat + 9 * s;
+  const double* rb = st.unit_pos + 3 * (st.unit_off[s] + b);
+  double x[3];
+  for (int c = 0; c < 3; ++c) {
+    double t = l1 * L[c];
+    t = t + l2 * L[3 + c];
+    t = t + l3 * L[6 + c];
+    x[c] = rb[c] + t;
+  }
+  if (copy > 0) {
+    const int64_t k = copy - 1, u = k / 6;
+    const int a = (int)((k % 6) / 2);
+    if (j == u) x[a] = (k % 2 == 0) ? x[a] + st.delta[0] : x[a] - st.delta[0];
+  }
+  for (int c = 0; c < 3; ++c) pos[3 * r + c] = x[c];
+}
+
+__global__ void __launch_bounds__(kFcThreads) k_ph_force_constants(PhView st, const float* __restrict__ forces, int asr,
+                                                                    double* __restrict__ phi, double* __restrict__ sums,
+                                                                    int32_t* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  __shared__ double sh[10][kFcThreads];
+  const int64_t g = blockIdx.x;   // global unit atom = (structure, home atom)
+  const int t = threadIdx.x;
+  const int s = st.unit_struct[g];
+  const int64_t u = g - st.unit_off[s];
+  const int64_t nu = st.unit_off[s + 1] - st.unit_off[s];
+  const int64_t ns = nu * st.dims[3 * s] * st.dims[3 * s + 1] * st.dims[3 * s + 2];
+  const int64_t r0 = st.row_off[s];
+  const double two_delta = 2.0 * st.delta[0];
+  // non-finite forces anywhere in the structure's 1 + 6 n_u copies (the same count in every workgroup of the structure)
+  double bad = 0.0;
+  const int64_t nvals = 3 * (st.row_off[s + 1] - r0);
+  for (int64_t i = t; i < nvals; i += kFcThreads) bad += std::isfinite(forces[3 * r0 + i]) ? 0.0 : 1.0;
+  const int64_t plus0 = r0 + (1 + 6 * u) * ns;   // first row of copy (u, a = 0, +)
+  double* out = phi + 9 * (st.pair_off[s] + u * ns);
+  double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int64_t j = t; j < ns; j += kFcThreads) {
+    for (int a = 0; a < 3; ++a) {
+      const float* fp = forces + 3 * (plus0 + 2 * a * ns + j);
+      const float* fm = forces + 3 * (plus0 + (2 * a + 1) * ns + j);
+      for (int c = 0; c < 3; ++c) {
+        const double v = -((double)fp[c] - (double)fm[c]) / two_delta;
+        acc[3 * a + c] += v;
+        if (!(asr && j == u)) out[9 * j + 3 * a + c] = v;
+      }
+    }
+  }
+  for (int k = 0; k < 9; ++k) sh[k][t] = acc[k];
+  sh[9][t] = bad;
+  __syncthreads();
+  for (int w = kFcThreads / 2; w > 0; w >>= 1) {   // fixed tree: the order depends on the thread index only
+    if (t < w)
+      for (int k = 0; k < 10; ++k) sh[k][t] += sh[k][t + w];
+    __syncthreads();
+  }
+  const bool failed = sh[9][0] != 0.0;
+  if (t < 9) {
+    const int a = t / 3, c = t % 3;
+    sums[9 * g + t] = sh[t][0];
+    if (asr) {
+      const float* fp = forces + 3 * (plus0 + 2 * a * ns + u);
+      const float* fm = forces + 3 * (plus0 + (2 * a + 1) * ns + u);
+      const double self = -((double)fp[c] - (double)fm[c]) / two_delta;
+      out[9 * u + t] = self - sh[t][0];
+    }
+  }
+  if (t == 0 && u == 0) nonfinite[s] = (int32_t)sh[9][0];
+  if (failed) {
+    __syncthreads();   // (failed is uniform over the workgroup)
+    for (int64_t i = t; i < 9 * ns; i += kFcThreads) out[i] = NAN;
+    if (t < 9) sums[9 * g + t] = NAN;
+  }
+}
+
+// the 3x3 block sum_l sum_m w_m Phi[u, l n_u + v] exp(2 pi i q.d_m) of structure s (re, im)
+__device__ inline void dyn_block(const PhView& st, const double* __restrict__ phi, int64_t s, int64_t u, int64_t v, int64_t nu,
+                                 int64_t ns, const double q[3], double re[9], double im[9]) {
+  for (int k = 0; k < 9; ++k) re[k] = im[k] = 0.0;
+  const int64_t row = st.pair_off[s] + u * ns;
+  for (int64_t j = v; j < ns; j += nu) {
+    const int64_t p = row + j;
+    const int m = st.img_count[p];
+    const double* d = st.img_d + 3 * kMaxMult * p;
+    double wc = 0.0, ws = 0.0;
+    for (int i = 0; i < m; ++i) {
+      const double x = q[0] * d[3 * i] + q[1] * d[3 * i + 1] + q[2] * d[3 * i + 2];
+      const double y = x - rint(x);   // q.d mod 1, in [-1/2, 1/2]
+      double sn, cs;
+      sincospi(2.0 * y, &sn, &cs);
+      wc += cs;
+      ws += sn;
+    }
+    const double w = 1.0 / (double)m;
+    wc *= w;
+    ws *= w;
+    const double* f = phi + 9 * p;
+    for (int k = 0; k < 9; ++k) {
+      re[k] += f[k] * wc;
+      im[k] += f[k] * ws;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kDynThreads) k_ph_dynmat(PhView st, int64_t n_q, int64_t blocks_per_q, const double* __restrict__ qs,
+                                                           const int32_t* __restrict__ q_struct, int32_t max_nu,
+                                                           const double* __restrict__ phi, double* __restrict__ out) {
+  const int64_t q_i = blockIdx.x / blocks_per_q;
+  const int64_t p = (blockIdx.x % blocks_per_q) * kDynThreads + threadIdx.x;
+  if (q_i >= n_q) return;
+  const int64_t s = q_struct[q_i];
+  if (s < 0 || s >= st.S) return;
+  const int64_t nu = st.unit_off[s + 1] - st.unit_off[s];
+  if (nu > max_nu || p >= nu * (nu + 1) / 2) return;
+  int64_t u = 0, rem = p;   // p -> (u, v), u <= v, row-major over the upper triangle
+  while (rem >= nu - u) { rem -= nu - u; ++u; }
+  const int64_t v = u + rem;
+  const int64_t ns = nu * st.dims[3 * s] * st.dims[3 * s + 1] * st.dims[3 * s + 2];
+  const double q[3] = {qs[3 * q_i], qs[3 * q_i + 1], qs[3 * q_i + 2]};
+  const double* m = st.mass + st.unit_off[s];
+  const double inv = 1.0 / sqrt(m[u] * m[v]);
+  double are[9], aim[9], bre[9], bim[9];
+  dyn_block(st, phi, s, u, v, nu, ns, q, are, aim);
+  if (u != v) {
+    dyn_block(st, phi, s, v, u, nu, ns, q, bre, bim);
+  } else {
+    for (int k = 0; k < 9; ++k) { bre[k] = are[k]; bim[k] = aim[k]; }
+  }
+  // H(u,v)[a][b] = (A[a][b] + conj(B[b][a])) / 2; H(v,u) = H(u,v)^H
+  const int64_t dim = 3 * (int64_t)max_nu;
+  double* o = out + 2 * dim * dim * q_i;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      const double hr = 0.5 * (are[3 * a + b] + bre[3 * b + a]) * inv;
+      const double hi = 0.5 * (aim[3 * a + b] - bim[3 * b + a]) * inv;
+      const int64_t ia = 3 * u + a, jb = 3 * v + b;
+      o[2 * (ia * dim + jb)] = hr;
+      o[2 * (ia * dim + jb) + 1] = hi;
+      o[2 * (jb * dim + ia)] = hr;
+      o[2 * (jb * dim + ia) + 1] = -hi;
+    }
+}
+
+bool ph_sizes_ok(const m3g_ph_sizes* z) {
+  return z && z->n_structs >= 1 && z->n_unit_atoms >= z->n_structs && z->n_super_atoms >= z->n_unit_atoms &&
+         z->n_pairs >= z->n_super_atoms && z->n_unit_atoms <= INT32_MAX && z->n_structs <= INT32_MAX &&
+         6 * z->n_pairs + z->n_super_atoms <= (int64_t)INT32_MAX * 256;
+}
+
+// the shortest images of supercell atom j seen from home atom u, in unit-cell fractional coordinates; false if more than kMaxMult tie
+bool shortest_images(const double L[9], const int n[3], const double* ru, const double* rv, const int l[3], std::vector<double>& d) {
+  // fractional difference in unit-cell coordinates: frac(r_v) - frac(r_u) + l
+  double inv[9];
+  const double det = L[0] * (L[4] * L[8] - L[5] * L[7]) - L[1] * (L[3] * L[8] - L[5] * L[6]) + L[2] * (L[3] * L[7] - L[4] * L[6]);
+  inv[0] = (L[4] * L[8] - L[5] * L[7]) / det; inv[1] = (L[2] * L[7] - L[1] * L[8]) / det; inv[2] = (L[1] * L[5] - L[2] * L[4]) / det;
+  inv[3] = (L[5] * L[6] - L[3] * L[8]) / det; inv[4] = (L[0] * L[8] - L[2] * L[6]) / det; inv[5] = (L[2] * L[3] - L[0] * L[5]) / det;
+  inv[6] = (L[3] * L[7] - L[4] * L[6]) / det; inv[7] = (L[1] * L[6] - L[0] * L[7]) / det; inv[8] = (L[0] * L[4] - L[1] * L[3]) / det;
+  double f0[3];   // (r_v - r_u) inv(L): row vector times the inverse of the row-vector lattice
+  for (int c = 0; c < 3; ++c) f0[c] = (rv[0] - ru[0]) * inv[c] + (rv[1] - ru[1]) * inv[3 + c] + (rv[2] - ru[2]) * inv[6 + c] + l[c];
+  double best = INFINITY;
+  double cand[125][4];
+  int k = 0;
+  for (int t0 = -2; t0 <= 2; ++t0)
+    for (int t1 = -2; t1 <= 2; ++t1)
+      for (int t2 = -2; t2 <= 2; ++t2) {
+        const double f[3] = {f0[0] + t0 * n[0], f0[1] + t1 * n[1], f0[2] + t2 * n[2]};
+        double x[3];
+        for (int c = 0; c < 3; ++c) x[c] = f[0] * L[c] + f[1] * L[3 + c] + f[2] * L[6 + c];
+        const double r = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+        cand[k][0] = f[0]; cand[k][1] = f[1]; cand[k][2] = f[2]; cand[k][3] = r;
+        best = std::fmin(best, r);
+        ++k;
+      }
+  d.clear();
+  for (int i = 0; i < 125; ++i)
+    if (cand[i][3] <= best + 1e-5) d.insert(d.end(), cand[i], cand[i] + 3);
+  return (int)d.size() / 3 <= kMaxMult;
+}
+}  // namespace
+}  // namespace m3g
+
+using namespace m3g;
+
+extern "C" int m3g_ph_state_bytes(const m3g_ph_sizes* sizes, size_t* bytes) {
+  if (!bytes || !ph_sizes_ok(sizes)) {
+    set_error("m3g_ph_state_bytes: bad sizes (need 1 <= n_structs <= n_unit_atoms <= n_super_atoms <= n_pairs)");
+    return M3G_ERR_VALUE;
+  }
+  *bytes = ph_layout(*sizes).total;
+  return M3G_OK;
+}
+
+extern "C" int m3g_ph_init(const m3g_ph_sizes* sizes, const int64_t* host_unit_offsets, const int32_t* host_supercells,
+                           const double* host_lattices, const double* host_positions, const double* host_masses, double delta, void* state,
+                           size_t state_bytes, void* stream_) {
+  if (!ph_sizes_ok(sizes) || !host_unit_offsets || !host_supercells || !host_lattices || !host_positions || !host_masses || !state) {
+    set_error("m3g_ph_init: null argument or bad sizes (need 1 <= n_structs <= n_unit_atoms <= n_super_atoms <= n_pairs)");
+    return M3G_ERR_VALUE;
+  }
+  const m3g_ph_sizes z = *sizes;
+  const int64_t S = z.n_structs, U = z.n_unit_atoms;
+  if (host_unit_offsets[0] != 0 || host_unit_offsets[S] != U) { set_error("m3g_ph_init: unit offsets must run from 0 to n_unit_atoms"); return M3G_ERR_VALUE; }
+  for (int64_t s = 0; s < S; ++s)
+    if (host_unit_offsets[s + 1] <= host_unit_offsets[s]) { set_error("m3g_ph_init: unit offsets must increase strictly (every structure holds an atom)"); return M3G_ERR_VALUE; }
+  if (!(std::isfinite(delta) && delta > 0.0)) { set_error("m3g_ph_init: delta must be finite and > 0"); return M3G_ERR_VALUE; }
+  std::vector<int64_t> row_off(S + 1, 0), pair_off(S + 1, 0);
+  std::vector<int32_t> unit_struct(U);
+  int64_t n_super = 0;
+  for (int64_t s = 0; s < S; ++s) {
+    const int32_t* n = host_supercells + 3 * s;
+    if (n[0] < 1 || n[1] < 1 || n[2] < 1 || (int64_t)n[0] * n[1] * n[2] > (1 << 20)) {
+      set_error("m3g_ph_init: supercell of structure %lld must have dims >= 1 (and at most 2^20 cells)", (long long)s);
+      return M3G_ERR_VALUE;
+    }
+    const double* L = host_lattices + 9 * s;
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(L[k])) { set_error("m3g_ph_init: lattice of structure %lld is not finite", (long long)s); return M3G_ERR_VALUE; }
+    const double det = L[0] * (L[4] * L[8] - L[5] * L[7]) - L[1] * (L[3] * L[8] - L[5] * L[6]) + L[2] * (L[3] * L[7] - L[4] * L[6]);
+    if (!(std::fabs(det) >= 1e-12)) { set_error("m3g_ph_init: singular cell of structure %lld", (long long)s); return M3G_ERR_VALUE; }
+    const int64_t nu = host_unit_offsets[s + 1] - host_unit_offsets[s];
+    const int64_t ns = nu * n[0] * n[1] * n[2];
+    for (int64_t g = host_unit_offsets[s]; g < host_unit_offsets[s + 1]; ++g) {
+      unit_struct[g] = (int32_t)s;
+      if (!(std::isfinite(host_masses[g]) && host_masses[g] > 0.0)) { set_error("m3g_ph_init: mass of unit atom %lld must be finite and > 0", (long long)g); return M3G_ERR_VALUE; }
+      for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(host_positions[3 * g + c])) { set_error("m3g_ph_init: position of unit atom %lld is not finite", (long long)g); return M3G_ERR_VALUE; }
+    }
+    row_off[s + 1] = row_off[s] + (1 + 6 * nu) * ns;
+    pair_off[s + 1] = pair_off[s] + nu * ns;
+    n_super += ns;
+  }
+  if (n_super != z.n_super_atoms || pair_off[S] != z.n_pairs) {
+    set_error("m3g_ph_init: sizes do not match the offsets and supercells (n_super_atoms %lld, n_pairs %lld expected)", (long long)n_super,
+              (long long)pair_off[S]);
+    return M3G_ERR_VALUE;
+  }
+  // the image table, fp64 on the host
+  std::vector<int32_t> img_count(z.n_pairs);
+  std::vector<double> img_d((size_t)3 * kMaxMult * z.n_pairs, 0.0), d;
+  for (int64_t s = 0; s < S; ++s) {
+    const int32_t* n = host_supercells + 3 * s;
+    const int64_t o = host_unit_offsets[s], nu = host_unit_offsets[s + 1] - o;
+    const int64_t ns = nu * n[0] * n[1] * n[2];
+    for (int64_t u = 0; u < nu; ++u)
+      for (int64_t j = 0; j < ns; ++j) {
+        const int64_t lc = j / nu, v = j % nu;
+        const int l[3] = {(int)(lc / ((int64_t)n[1] * n[2])), (int)((lc / n[2]) % n[1]), (int)(lc % n[2])};
+        const int nn[3] = {n[0], n[1], n[2]};
+        if (!shortest_images(host_lattices + 9 * s, nn, host_positions + 3 * (o + u), host_positions + 3 * (o + v), l, d)) {
+          set_error("m3g_ph_init: structure %lld: %zu shortest images tie for pair (%lld, %lld), above the image table capacity %d",
+                    (long long)s, d.size() / 3, (long long)u, (long long)j, kMaxMult);
+          return M3G_ERR_VALUE;
+        }
+        const int64_t p = pair_off[s] + u * ns + j;
+        img_count[p] = (int32_t)(d.size() / 3);
+        std::copy(d.begin(), d.end(), img_d.begin() + 3 * kMaxMult * p);
+      }
+  }
+  const PhLayout L = ph_layout(z);
+  if (state_bytes < L.total) { set_error("m3g_ph_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
+  hipStream_t s = (hipStream_t)stream_;
+  char* st = (char*)state;
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.row_off, row_off.data(), 8 * (S + 1), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.unit_off, host_unit_offsets, 8 * (S + 1), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.pair_off, pair_off.data(), 8 * (S + 1), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.dims, host_supercells, 4 * 3 * S, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.lat, host_lattices, 8 * 9 * S, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.unit_pos, host_positions, 8 * 3 * U, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.mass, host_masses, 8 * U, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.unit_struct, unit_struct.data(), 4 * U, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.delta, &delta, 8, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.img_count, img_count.data(), 4 * z.n_pairs, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st + L.img_d, img_d.data(), 8 * img_d.size(), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
+  return M3G_OK;
+}
+
+extern "C" int m3g_ph_displace(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, double* pos, void* stream_) {
+  if (!ph_sizes_ok(sizes) || !state || !pos) { set_error("m3g_ph_displace: null argument or bad sizes"); return M3G_ERR_VALUE; }
+  if (state_bytes < ph_layout(*sizes).total) { set_error("m3g_ph_displace: state buffer too small"); return M3G_ERR_SIZE; }
+  const PhView st = ph_view(*sizes, state);
+  hipLaunchKernelGGL(k_ph_displace, dim3((unsigned)((st.rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, st, pos);
+  M3G_HIP_CHECK(hipGetLastError());
+  return M3G_OK;
+}
+
+extern "C" int m3g_ph_force_constants(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const float* forces, int32_t asr,
+                                      double* phi, double* sums, int32_t* nonfinite, void* stream_) {
+  if (!ph_sizes_ok(sizes) || !state || !forces || !phi || !sums || !nonfinite || (asr != 0 && asr != 1)) {
+    set_error("m3g_ph_force_constants: null argument, bad sizes or asr not 0 / 1");
+    return M3G_ERR_VALUE;
+  }
+  if (state_bytes < ph_layout(*sizes).total) { set_error("m3g_ph_force_constants: state buffer too small"); return M3G_ERR_SIZE; }
+  const PhView st = ph_view(*sizes, state);
+  hipLaunchKernelGGL(k_ph_force_constants, dim3((unsigned)st.U), dim3(kFcThreads), 0, (hipStream_t)stream_, st, forces, (int)asr, phi, sums,
+                     nonfinite);
+  M3G_HIP_CHECK(hipGetLastError());
+  return M3G_OK;
+}
+
+extern "C" int m3g_ph_dynmat(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const double* phi, int64_t n_q, const double* q,
+                             const int32_t* q_struct, int32_t max_unit_atoms, double* dynmat, void* stream_) {
+  if (!ph_sizes_ok(sizes) || !state || !phi || n_q < 0 || (n_q > 0 && (!q || !q_struct || !dynmat)) || max_unit_atoms < 1 ||
+      max_unit_atoms > sizes->n_unit_atoms) {
+    set_error("m3g_ph_dynmat: null argument, bad sizes, n_q < 0 or max_unit_atoms outside [1, n_unit_atoms]");
+    return M3G_ERR_VALUE;
+  }
+  if (state_bytes < ph_layout(*sizes).total) { set_error("m3g_ph_dynmat: state buffer too small"); return M3G_ERR_SIZE; }
+  if (n_q == 0) return M3G_OK;
+  const int64_t pairs = (int64_t)max_unit_atoms * (max_unit_atoms + 1) / 2;
+  const int64_t per_q = (pairs + kDynThreads - 1) / kDynThreads;
+  if (n_q * per_q > (int64_t(1) << 26)) { set_error("m3g_ph_dynmat: too many q-points for one launch"); return M3G_ERR_VALUE; }
+  const PhView st = ph_view(*sizes, state);
+  hipLaunchKernelGGL(k_ph_dynmat, dim3((unsigned)(n_q * per_q)), dim3(kDynThreads), 0, (hipStream_t)stream_, st, n_q, per_q, q, q_struct,
+                     max_unit_atoms, phi, dynmat);
+  M3G_HIP_CHECK(hipGetLastError());
+  return M3G_OK;
+}

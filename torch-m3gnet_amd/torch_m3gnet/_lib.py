@@ -10,7 +10,7 @@ _PKG_ROOT = Path(__file__).resolve().parent.parent  # .../torch-m3gnet_amd
 LIB_PATH = _PKG_ROOT / "lib" / "libm3gnet_hip.so"
 
 M3G_OK, M3G_ERR_VALUE, M3G_ERR_STATE, M3G_ERR_SIZE, M3G_ERR_HIP, M3G_ERR_UNSUPPORTED = range(6)
-ABI_VERSION = 9
+ABI_VERSION = 10
 VERLET_FILL_LISTS_MAX_ROW = 1024   # M3G_VERLET_FILL_LISTS_MAX_ROW (include/m3gnet_hip.h)
 
 
@@ -76,6 +76,12 @@ class M3GDynParams(C.Structure):   # m3g_dyn_params
 DYN_NVE, DYN_NVT_BERENDSEN, DYN_NVT_LANGEVIN, DYN_NPT_BERENDSEN = range(4)   # M3G_DYN_* ensembles
 DYN_STARTED, DYN_ERROR = 1, 2                                               # M3G_DYN_* flag bits
 NEB_ROWS = 5                                                                 # M3G_NEB_ROWS
+PH_MAX_MULTIPLICITY = 27                                                     # M3G_PH_MAX_MULTIPLICITY
+
+
+class M3GPhSizes(C.Structure):   # m3g_ph_sizes
+    _fields_ = [("n_structs", C.c_int64), ("n_unit_atoms", C.c_int64), ("n_super_atoms", C.c_int64), ("n_pairs", C.c_int64)]
+
 
 # name -> (restype, argtypes); every symbol include/m3gnet_hip.h declares
 SYMBOLS = {
@@ -176,6 +182,14 @@ SYMBOLS = {
                                C.c_void_p, C.c_size_t, C.c_void_p]),
     "m3g_neb_forces": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
+    "m3g_ph_state_bytes": (C.c_int, [C.POINTER(M3GPhSizes), C.POINTER(C.c_size_t)]),
+    "m3g_ph_init": (C.c_int, [C.POINTER(M3GPhSizes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                              C.c_size_t, C.c_void_p]),
+    "m3g_ph_displace": (C.c_int, [C.POINTER(M3GPhSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "m3g_ph_force_constants": (C.c_int, [C.POINTER(M3GPhSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "m3g_ph_dynmat": (C.c_int, [C.POINTER(M3GPhSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_void_p, C.c_void_p]),
     "m3g_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "m3g_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_float),
                                    C.POINTER(C.c_int32)]),
