@@ -615,6 +615,87 @@ int m3g_ph_force_constants(const m3g_ph_sizes* sizes, const void* state, size_t 
 int m3g_ph_dynmat(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const double* phi, int64_t n_q, const double* q,
                   const int32_t* q_struct, int32_t max_unit_atoms, double* dynmat, void* stream);
 
+/* ---- batched finite-strain elastic constants and equation of state (csrc/m3g_elastic.hip) ------------------------------------------
+ * Replaces the host loop of pymatgen's DeformedStructureSet / matcalc's ElasticityCalc and EOSCalc over an ASE calculator (deform a
+ * cell, evaluate, copy the stress back, 25 times per structure, fit in numpy) for a whole batch of structures.
+ * Conventions: rows of a lattice are lattice vectors and a deformation acts on the right, L' = L D, r' = r D, D = I + eps symmetric.
+ * Voigt order xx, yy, zz, yz, zx, xy.  The engine's pair-virial `stresses` are -(1/V) dE/d eps; the Cauchy stress (tension positive)
+ * is sigma = -stresses, and every quantity below is stated in sigma.
+ *   deformed batch: structure s (n_s atoms, cell L, positions r) has 1 + M copies of its n_s rows: copy 0 undeformed, copy m = 1..M
+ *          deformed by D_m, which component[m-1] and magnitude[m-1] define: component j in 0..5 -- eps holds that one Voigt
+ *          component, eps_jj = d for j < 3, the two off-diagonal entries d / 2 for j >= 3 (d is the engineering shear) -- or
+ *          M3G_EL_VOLUMETRIC -- eps = d I (d the linear strain).  Structures one after another: row = (1 + M) o_s + c n_s + b.
+ *          r'_c = (r_0 D_0c + r_1 D_1c) + r_2 D_2c in exactly this order with no fused multiply-add, cells likewise;
+ *   elastic fit (mode M3G_EL_MODE_ELASTIC; fp64 from the fp32 stresses [copies, 6]): for every strained component j and stress
+ *          component i the slope of the least-squares straight line with intercept through (0, sigma_i of copy 0) and (d, sigma_i)
+ *          of the copies of component j, in copy order: C_raw[i][j] (eV/A^3).  C = (C_raw + C_raw^T) / 2, S = C^-1 (Gauss-Jordan
+ *          with partial pivoting), Voigt / Reuss / Hill bulk and shear moduli, E = 9 K G / (3 K + G) and nu = (3 K - 2 G) /
+ *          (2 (3 K + G)) from the Hill values, the universal anisotropy 5 G_V / G_R + K_V / K_R - 6, the eigenvalues of C (cyclic
+ *          Jacobi, row-major sweeps, ascending) and stable = smallest eigenvalue > 0.  This is the stress-strain tensor at the given
+ *          cell (what pymatgen / matcalc report); it is the second strain derivative of the energy only at zero residual stress.
+ *          A structure with a non-finite stress gets NaN in its whole row and a non-zero count; the others are unaffected;
+ *   EOS fit (mode M3G_EL_MODE_EOS; fp64 from the fp32 energies [copies]): third-order Birch-Murnaghan, which is exactly a cubic in
+ *          t = (V / V_ref)^(-2/3) - 1 = (1 + d)^-2 - 1 (V_ref = |det L|): least squares by Householder QR over the 1 + M points in
+ *          u = t / max |t| with the energy of copy 0 subtracted; t0 = the root of dE/dt that is a minimum; V0 = V_ref (1 + t0)^(-3/2),
+ *          E0 = E(t0), and with a2 = E''(t0) (1 + t0)^2 / 2, a3 = E'''(t0) (1 + t0)^3 / 6: B0 = 8 a2 / (9 V0), B0' = 4 + 2 a3 / a2.
+ *          Error bits: M3G_EL_EOS_NONFINITE (an energy is not finite: the row is NaN), M3G_EL_EOS_NO_MINIMUM (no minimum of the fitted
+ *          cubic inside the sampled range of t: the row holds NaN but for v_ref, rms and the point count).
+ * No atomics: a structure's results are bitwise the same alone or in any batch. */
+#define M3G_EL_VOLUMETRIC 6       /* component value of an isotropic deformation */
+#define M3G_EL_MODE_ELASTIC 0
+#define M3G_EL_MODE_EOS 1
+#define M3G_EL_MAX_DEFORM 64      /* deformations per structure */
+#define M3G_EL_MAX_STRAIN 0.2     /* |magnitude| below this */
+/* result row of m3g_el_fit_elastic (doubles): C_raw [36] row-major, C [36], S [36], residual sigma [6], eigenvalues [6], then */
+#define M3G_EL_ROW_CRAW 0
+#define M3G_EL_ROW_C 36
+#define M3G_EL_ROW_S 72
+#define M3G_EL_ROW_SIGMA0 108
+#define M3G_EL_ROW_EIG 114
+#define M3G_EL_ROW_ASYMMETRY 120
+#define M3G_EL_ROW_FIT_RESIDUAL 121
+#define M3G_EL_ROW_KV 122
+#define M3G_EL_ROW_KR 123
+#define M3G_EL_ROW_KH 124
+#define M3G_EL_ROW_GV 125
+#define M3G_EL_ROW_GR 126
+#define M3G_EL_ROW_GH 127
+#define M3G_EL_ROW_YOUNG 128
+#define M3G_EL_ROW_POISSON 129
+#define M3G_EL_ROW_ANISOTROPY 130
+#define M3G_EL_ROW_STABLE 131     /* 1.0 or 0.0 */
+#define M3G_EL_ROW 132
+/* result row of m3g_el_fit_eos (doubles): v0, e0, b0, b0', rms residual, v_ref, t0, number of points */
+#define M3G_EL_EOS_ROW 8
+#define M3G_EL_EOS_NONFINITE 1
+#define M3G_EL_EOS_NO_MINIMUM 2
+typedef struct {
+  int64_t n_structs;   /* S */
+  int64_t n_atoms;     /* U = sum_s n_s; the deformed batch has (1 + M) U rows and (1 + M) S copies */
+  int32_t n_deform;    /* M, 1 .. M3G_EL_MAX_DEFORM */
+  int32_t mode;        /* M3G_EL_MODE_* */
+} m3g_el_sizes;
+/* 1 <= n_structs <= n_atoms, 1 <= n_deform <= M3G_EL_MAX_DEFORM, mode 0 / 1, else M3G_ERR_VALUE. */
+int m3g_el_state_bytes(const m3g_el_sizes* sizes, size_t* bytes);
+/* HOST host_offsets [S+1] (int64, 0 = o_0 < ... < o_S = U), host_lattices [S,3,3] fp64, host_positions [U,3] fp64 (Cartesian),
+ * host_components [M] int32, host_magnitudes [M] fp64.  Everything is checked on the host before any HIP call: bad offsets, a singular
+ * or non-finite cell, non-finite positions, a magnitude that is not finite, zero or with |d| >= M3G_EL_MAX_STRAIN; elastic mode: a
+ * component outside 0..5, a component with fewer than two distinct magnitudes; EOS mode: a component other than M3G_EL_VOLUMETRIC,
+ * fewer than 5 distinct volumes (copy 0 counted) -> M3G_ERR_VALUE.  Waits for the stream. */
+int m3g_el_init(const m3g_el_sizes* sizes, const int64_t* host_offsets, const double* host_lattices, const double* host_positions,
+                const int32_t* host_components, const double* host_magnitudes, void* state, size_t state_bytes, void* stream);
+/* The deformed batch: pos [(1 + M) U, 3] fp64 and lattices [(1 + M) S, 3, 3] fp64 (copy c of structure s at (1 + M) s + c) DEVICE,
+ * written.  One launch, no allocation, copy or wait: capture-safe. */
+int m3g_el_deform(const m3g_el_sizes* sizes, const void* state, size_t state_bytes, double* pos, double* lattices, void* stream);
+/* stresses [(1 + M) S, 6] f32 DEVICE (the engine's pair-virial stresses of the copies); rows [S, M3G_EL_ROW] fp64, nonfinite [S] int32
+ * DEVICE, written.  Elastic mode only.  One launch, capture-safe. */
+int m3g_el_fit_elastic(const m3g_el_sizes* sizes, const void* state, size_t state_bytes, const float* stresses, double* rows,
+                       int32_t* nonfinite, void* stream);
+/* energies [(1 + M) S] f32 DEVICE (total energies of the copies); rows [S, M3G_EL_EOS_ROW] fp64, error [S] int32 (M3G_EL_EOS_* bits)
+ * DEVICE, written.  EOS mode only.  One launch, capture-safe. */
+int m3g_el_fit_eos(const m3g_el_sizes* sizes, const void* state, size_t state_bytes, const float* energies, double* rows, int32_t* error,
+                   void* stream);
+
 /* ---- measurement: per-stage device time from HIP events recorded on the call's own stream ---------
  * m3g_profile_enable(plan, 1) makes every following m3g_energy_forces record an event pair around each
  * stage launch; m3g_profile_read synchronises those events, returns per-stage totals since the last
@@ -646,7 +727,7 @@ int m3g_debug_radix_sort(int32_t key_bytes, int64_t n, void* keys, int32_t* vals
 int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes, int32_t* kernel_launches,
                        int32_t* other_operations);
 
-#define M3G_ABI_VERSION 10  /* 2: m3g_io.topo_hints, m3g_topology_hints; 3: m3g_verlet_*, m3g_topology_status, hints word certified on the buffer,
+#define M3G_ABI_VERSION 11  /* 2: m3g_io.topo_hints, m3g_topology_hints; 3: m3g_verlet_*, m3g_topology_status, hints word certified on the buffer,
                              * canonical edge order by the shift relative to the given coordinates, default precision fp32;
                              * 4: m3g_verlet_fill_lists, m3g_topology_build_canonical, M3G_TOPO_ERR_SYNC, options small_tiles / small_launches / fuse_node_tb;
                              * 5: m3g_topology_build_canonical_begin / _end, m3g_topology_data_bytes, option legendre_backward, m3g_md_*;
@@ -655,7 +736,8 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              * 7: m3g_fire_* (batched FIRE relaxation, fixed or variable cell);
                              * 8: m3g_dyn_* (batched molecular dynamics: NVE, NVT Berendsen / Langevin, NPT Berendsen);
                              * 9: m3g_neb_* (batched climbing-image NEB force projection, improved tangent; replaces ASE's NEB.get_forces);
-                             * 10: m3g_ph_* (batched finite-displacement phonons: displaced supercells, force constants, dynamical matrices) */
+                             * 10: m3g_ph_* (batched finite-displacement phonons: displaced supercells, force constants, dynamical matrices);
+                             * 11: m3g_el_* (batched finite-strain elastic constants and Birch-Murnaghan equation of state: deformed copies, both fits) */
 
 #ifdef __cplusplus
 }

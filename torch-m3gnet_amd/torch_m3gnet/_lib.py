@@ -10,7 +10,7 @@ _PKG_ROOT = Path(__file__).resolve().parent.parent  # .../torch-m3gnet_amd
 LIB_PATH = _PKG_ROOT / "lib" / "libm3gnet_hip.so"
 
 M3G_OK, M3G_ERR_VALUE, M3G_ERR_STATE, M3G_ERR_SIZE, M3G_ERR_HIP, M3G_ERR_UNSUPPORTED = range(6)
-ABI_VERSION = 10
+ABI_VERSION = 11
 VERLET_FILL_LISTS_MAX_ROW = 1024   # M3G_VERLET_FILL_LISTS_MAX_ROW (include/m3gnet_hip.h)
 
 
@@ -82,6 +82,14 @@ PH_MAX_MULTIPLICITY = 27                                                     # M
 class M3GPhSizes(C.Structure):   # m3g_ph_sizes
     _fields_ = [("n_structs", C.c_int64), ("n_unit_atoms", C.c_int64), ("n_super_atoms", C.c_int64), ("n_pairs", C.c_int64)]
 
+
+class M3GElSizes(C.Structure):   # m3g_el_sizes
+    _fields_ = [("n_structs", C.c_int64), ("n_atoms", C.c_int64), ("n_deform", C.c_int32), ("mode", C.c_int32)]
+
+
+EL_VOLUMETRIC, EL_MODE_ELASTIC, EL_MODE_EOS, EL_MAX_DEFORM, EL_MAX_STRAIN = 6, 0, 1, 64, 0.2   # M3G_EL_*
+EL_ROW, EL_EOS_ROW = 132, 8                                                  # M3G_EL_ROW, M3G_EL_EOS_ROW
+EL_EOS_NONFINITE, EL_EOS_NO_MINIMUM = 1, 2                                   # M3G_EL_EOS_* error bits
 
 # name -> (restype, argtypes); every symbol include/m3gnet_hip.h declares
 SYMBOLS = {
@@ -190,6 +198,12 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p]),
     "m3g_ph_dynmat": (C.c_int, [C.POINTER(M3GPhSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                 C.c_void_p, C.c_void_p]),
+    "m3g_el_state_bytes": (C.c_int, [C.POINTER(M3GElSizes), C.POINTER(C.c_size_t)]),
+    "m3g_el_init": (C.c_int, [C.POINTER(M3GElSizes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                              C.c_void_p]),
+    "m3g_el_deform": (C.c_int, [C.POINTER(M3GElSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_el_fit_elastic": (C.c_int, [C.POINTER(M3GElSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_el_fit_eos": (C.c_int, [C.POINTER(M3GElSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "m3g_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_float),
                                    C.POINTER(C.c_int32)]),
