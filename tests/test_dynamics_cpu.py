@@ -231,6 +231,8 @@ def test_molecular_dynamics_argument_validation():
     model = build_model(5.0, 4.0, 3, 3, 95, 16, 1)
     with pytest.raises(TypeError):
         MolecularDynamics(model.model)
+    with pytest.raises(TypeError, match="MolecularDynamics"):   # names the driver that was constructed
+        MolecularDynamics(model.model)
     for kw in (dict(ensemble="nvt"), dict(ensemble="npt_berendsen"), dict(ensemble="npt_berendsen", compressibility=0.0),
                dict(timestep=0.0), dict(timestep=float("nan")), dict(taut=-1.0), dict(taup=0.0), dict(friction=-0.01),
                dict(pressure=float("inf")), dict(fix_com=True), dict(skin=0.0), dict(temperature=-5.0), dict(temperature=[[300.0]]),

@@ -389,6 +389,8 @@ def test_elasticity_argument_validation():
     for cls in (Elasticity, EquationOfState):
         with pytest.raises(TypeError):
             cls(model.model)
+        with pytest.raises(TypeError, match=cls.__name__):   # names the driver that was constructed
+            cls(model.model)
         for kw in (dict(relax_atoms=2), dict(fmax=0.0), dict(fmax=float("nan")), dict(steps=-1), dict(steps=1.5), dict(max_atoms=0),
                    dict(max_atoms=2.5), dict(skin=0.0)):
             with pytest.raises(ValueError):

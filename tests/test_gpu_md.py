@@ -540,3 +540,34 @@ def test_trajectory_step_reports_sticky_error_bits_of_the_previous_step():
     want = model(ref.update(pos), extras=False)
     for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES):
         assert torch.equal(again[key], want[key]), key
+
+
+def test_raise_on_step_errors_reads_the_sticky_error_bits_of_the_last_step():
+    """`VerletGraph.raise_on_step_errors` is what the batched drivers call after their LAST `step`, whose error word no later
+    m3g_md_step reads: silent after a clean step, RuntimeError with the bits (M3G_TOPO_ERR_SYNC, forced as in the test above) and
+    the caller's leading word after a step that left some, silent again once `update` owns the lists (the fallback path of `step`:
+    the C side's topology was not the one evaluated)."""
+    from torch_m3gnet.data.md import VerletGraph
+
+    K = _K()
+    model = _model()
+    lat, p0, z = random_cell_arrays(40, 8.0, seed=11)
+    vg = VerletGraph([lat], [z], 5.0, 4.0, skin=0.6, device=DEV)
+    pos = torch.tensor(p0, device=DEV)
+    vg.raise_on_step_errors("relaxation")              # no step yet: nothing to read
+    good = vg.step(model, pos)
+    assert torch.isfinite(good[K.FORCES]).all()
+    vg.raise_on_step_errors("relaxation")              # clean
+    model.engine.set_option("debug_node_tb_polls", -64)
+    try:
+        bad = vg.step(model, pos)
+        assert torch.isnan(bad[K.FORCES]).any()
+    finally:
+        model.engine.set_option("debug_node_tb_polls", 0)
+    with pytest.raises(RuntimeError, match="error bits") as err:
+        vg.raise_on_step_errors("phonons")
+    message = str(err.value)
+    assert message.startswith("phonons: ") and "M3G_TOPO_ERR_*" in message
+    assert int(message.split("error bits ")[1].split()[0], 16) & 2   # M3G_TOPO_ERR_SYNC
+    vg.update(pos)                                     # the lists are `update`'s now, as after a step served by the fallback
+    vg.raise_on_step_errors("phonons")

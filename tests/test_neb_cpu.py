@@ -251,6 +251,8 @@ def test_neb_argument_validation():
     model = build_model(5.0, 4.0, 3, 3, 95, 16, 1)
     with pytest.raises(TypeError):
         NEB(model.model)
+    with pytest.raises(TypeError, match="NEB"):   # names the driver that was constructed
+        NEB(model.model)
     for kw in (dict(k=0.0), dict(k=-1.0), dict(k=float("nan")), dict(climb=2), dict(skin=0.0)):
         with pytest.raises(ValueError):
             NEB(model, **kw)

@@ -266,12 +266,35 @@ def test_c_abi_phonon_sizes():
     assert lib.m3g_ph_dynmat(C.byref(sz), dummy, 1 << 30, dummy, 0, None, None, 4, None, None) == _lib.M3G_OK   # nothing to do
 
 
+def test_sub_batches_against_a_brute_force_restatement():
+    """The engine sub-batches of one structure's copies (Phonons.run, the strain drivers): in order, no overlap, at most max_atoms
+    atoms each but never less than one copy -- the split decides the engine's batch composition, so it is pinned."""
+    from torch_m3gnet._driver import sub_batches
+
+    cases = ((25, 32, 200), (25, 32, 31), (25, 32, 32), (25, 32, 800), (25, 32, 10**6), (1, 4, 3), (13, 8, 24), (7, 5, 11))
+    for n_copies, n, max_atoms in cases:
+        want, first = [], 0
+        while first < n_copies:
+            count = 1
+            while (count + 1) * n <= max_atoms and first + count < n_copies:
+                count += 1
+            want.append((first, count))
+            first += count
+        got = list(sub_batches(n_copies, n, max_atoms))
+        assert got == want, (n_copies, n, max_atoms)
+        assert [f for f, _ in got] == np.cumsum([0] + [c for _, c in got])[:-1].tolist() and sum(c for _, c in got) == n_copies
+    assert [c for _, c in sub_batches(25, 32, 200)] == [6, 6, 6, 6, 1]
+    assert [c for _, c in sub_batches(25, 32, 31)] == [1] * 25
+
+
 def test_phonons_argument_validation():
     from torch_m3gnet.model.build import build_model
     from torch_m3gnet.phonons import Phonons
 
     model = build_model(5.0, 4.0, 3, 3, 95, 16, 1)
     with pytest.raises(TypeError):
+        Phonons(model.model)
+    with pytest.raises(TypeError, match="Phonons"):   # names the driver that was constructed
         Phonons(model.model)
     for kw in (dict(delta=0.0), dict(delta=-0.01), dict(delta=float("nan")), dict(asr=2), dict(max_atoms=0), dict(max_atoms=1.5),
                dict(max_qpoints=0), dict(cutoff_frequency=-1.0), dict(skin=0.0)):

@@ -378,6 +378,19 @@ class VerletGraph:
             out[K.FORCES], out[K.STRESSES] = f, st
         return out
 
+    def raise_on_step_errors(self, what: str) -> None:
+        """Raise if the last `step` left sticky error bits on its topology (m3g_md_step checks those of the EARLIER steps only).
+        `what` starts the message.  After a step served by the fallback (`model(self.update(pos))`: the lists are `update`'s, the
+        topology is the graph's own, which the engine checks) there is nothing to read here."""
+        if self._md_buffers is None or self._lists_owner != "c":
+            return
+        n_e, n_t = self._step_sizes
+        status = C.c_int32()
+        with _cuda.on_device(self.device):
+            _lib.check(self.lib.m3g_topology_status(self.N, n_e, n_t, self.S, _ptr(self._md_buffers["topo"]), C.byref(status), _stream()))
+        if status.value:
+            raise RuntimeError(f"{what}: the last evaluation left error bits {status.value:#x} on its topology (M3G_TOPO_ERR_*)")
+
     def step_lists(self) -> dict:
         """The lists `step` ran on last, as views of its capacity buffers (valid until the next `step`)."""
         n_e, n_t = self._step_sizes

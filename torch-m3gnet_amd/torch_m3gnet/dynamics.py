@@ -21,25 +21,18 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
+from ._driver import (EV_A3_TO_GPA, Driver, batch_layout, check_tensor, integer, positive, state_tensor, structure_arrays,
+                      structure_masses)
 from .data import MaterialGraphKey as K
-from .data.atomic_masses import masses_of
 from .data.graph_gpu import _ptr, _stream
 from .data.md import VerletGraph
 from .nn.modules import Gradient
-from .relax import Relaxer
 
 KAPPA = 9.648533215665e-3    # A/fs^2 per eV/(A amu)
 KB = 8.617333262e-5          # eV/K
-EV_PER_A3_IN_GPA = 160.21766208
+EV_PER_A3_IN_GPA = EV_A3_TO_GPA
 ENSEMBLES = {"nve": _lib.DYN_NVE, "nvt_berendsen": _lib.DYN_NVT_BERENDSEN, "nvt_langevin": _lib.DYN_NVT_LANGEVIN,
              "npt_berendsen": _lib.DYN_NPT_BERENDSEN}
-
-
-def _positive(name, x) -> float:
-    x = float(x)
-    if not (math.isfinite(x) and x > 0.0):
-        raise ValueError(f"{name} must be a finite number > 0; got {x}")
-    return x
 
 
 def maxwell_boltzmann(masses, temperature: float, seed: int = 0) -> np.ndarray:
@@ -84,14 +77,7 @@ class DynState:
         self.ensemble = ensemble
         self.params = _lib.M3GDynParams(ensemble=ENSEMBLES[ensemble], fix_com=1 if fix_com else 0, dt=dt, taut=taut, friction=friction,
                                         pressure=pressure, taup=taup, compressibility=compressibility)
-        if pos.dtype != torch.float64 or pos.dim() != 2 or pos.size(1) != 3 or not pos.is_contiguous():
-            raise ValueError("pos must be a contiguous [N, 3] float64 tensor")
-        self.offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-        self.N, self.S = int(pos.size(0)), int(len(self.offsets) - 1)
-        if self.S < 1:
-            raise ValueError("offsets must hold S + 1 >= 2 entries")
-        if lattice is not None and (lattice.dtype != torch.float64 or tuple(lattice.shape) != (self.S, 3, 3) or not lattice.is_contiguous()):
-            raise ValueError(f"lattice must be a contiguous [{self.S}, 3, 3] float64 tensor")
+        self.offsets, self.N, self.S = batch_layout(pos, lattice, offsets)
         if ensemble == "npt_berendsen" and lattice is None:
             raise ValueError("NPT needs the lattice")
         if velocities.dtype != torch.float64 or tuple(velocities.shape) != (self.N, 3) or velocities.device != pos.device:
@@ -105,9 +91,7 @@ class DynState:
         self.lattice32 = lattice.to(torch.float32) if lattice is not None else None
         self.device = pos.device
         self.lib = _lib.load_library()
-        nbytes = C.c_size_t()
-        _lib.check(self.lib.m3g_dyn_state_bytes(self.N, self.S, C.byref(nbytes)))
-        self.state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self.state = state_tensor(self.lib.m3g_dyn_state_bytes, self.N, self.S, device=self.device)
         self.obs = torch.full((self.S, 4), float("nan"), dtype=torch.float64, device=self.device)
         vel = velocities.contiguous()
         with _cuda.on_device(self.device):
@@ -128,17 +112,16 @@ def dyn_step(state: DynState, forces: torch.Tensor, stresses: torch.Tensor | Non
     """One MD call of the batch (m3g_dyn_step) at `forces` [N,3] and `stresses` [S,6] (float32, pair-virial convention; required in
     NPT) evaluated at `state.pos`: finish the step that ends here, write `state.obs`, start the next one (not with `finish_only`).
     Queued on the current stream; no wait, capture-safe."""
-    if forces.dtype != torch.float32 or tuple(forces.shape) != (state.N, 3) or not forces.is_contiguous():
-        raise ValueError(f"forces must be a contiguous [{state.N}, 3] float32 tensor")
-    if stresses is not None and (stresses.dtype != torch.float32 or tuple(stresses.shape) != (state.S, 6) or not stresses.is_contiguous()):
-        raise ValueError(f"stresses must be a contiguous [{state.S}, 6] float32 tensor")
+    check_tensor("forces", forces, (state.N, 3), torch.float32)
+    if stresses is not None:
+        check_tensor("stresses", stresses, (state.S, 6), torch.float32)
     with _cuda.on_device(state.device):
         _lib.check(state.lib.m3g_dyn_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
                                           _ptr(stresses), _ptr(state.pos), _ptr(state.lattice), _ptr(state.lattice32), 1 if finish_only else 0,
                                           _ptr(state.obs), _stream()))
 
 
-class MolecularDynamics:
+class MolecularDynamics(Driver):
     """Batched counterpart of m3gnet's `MolecularDynamics`.
 
     `model`: the `Gradient` returned by `build_model`; the run evaluates a `pair_virial=True` engine made from its `Sequential` (the
@@ -150,14 +133,13 @@ class MolecularDynamics:
     def __init__(self, model: Gradient, ensemble: str = "nvt_langevin", timestep: float = 1.0, temperature=300.0, taut: float | None = None,
                  friction: float = 0.01, pressure: float = 0.0, taup: float | None = None, compressibility: float | None = None,
                  fix_com: bool | None = None, skin: float = 0.5, seed=0, device="cuda"):
-        if not isinstance(model, Gradient):
-            raise TypeError("MolecularDynamics needs the Gradient model returned by build_model")
+        super().__init__(model, skin, device)
         if not isinstance(ensemble, str) or ensemble not in ENSEMBLES:
             raise ValueError(f"unknown ensemble {ensemble!r}; expected one of {sorted(ENSEMBLES)}")
         self.ensemble = ensemble
-        self.timestep = _positive("timestep", timestep)
-        self.taut = _positive("taut", 100.0 * self.timestep if taut is None else taut)
-        self.taup = _positive("taup", 1000.0 * self.timestep if taup is None else taup)
+        self.timestep = positive("timestep", timestep)
+        self.taut = positive("taut", 100.0 * self.timestep if taut is None else taut)
+        self.taup = positive("taup", 1000.0 * self.timestep if taup is None else taup)
         friction = float(friction)
         if not (math.isfinite(friction) and friction >= 0.0):
             raise ValueError(f"friction must be a finite number >= 0; got {friction}")
@@ -168,7 +150,7 @@ class MolecularDynamics:
         if ensemble == "npt_berendsen":
             if compressibility is None:
                 raise ValueError("npt_berendsen needs the compressibility (1/GPa)")
-            compressibility = _positive("compressibility", compressibility)
+            compressibility = positive("compressibility", compressibility)
         self.compressibility = compressibility
         if fix_com is None:
             fix_com = ensemble != "nvt_langevin"
@@ -179,12 +161,7 @@ class MolecularDynamics:
         if t.ndim > 1 or not (np.isfinite(t).all() and (t >= 0).all()):
             raise ValueError("temperature must be one finite value >= 0 (K) or one per structure")
         self.temperature = t
-        self.skin = _positive("skin", skin)
         self.seed = seed
-        self.model = Gradient(model.model, pair_virial=True, legendre_backward=model.legendre_backward)
-        if model._engine is not None:
-            self.model.engine.set_precision(model._engine.precision)
-        self.device = torch.device(device)
 
     def _params(self) -> dict:
         beta = 1.0 if self.compressibility is None else self.compressibility * EV_PER_A3_IN_GPA   # 1/GPa -> A^3/eV
@@ -199,26 +176,14 @@ class MolecularDynamics:
         velocities, lattice, total_energy, forces, stresses (pair virial) at the final step, n_steps, error (its forces became
         non-finite: it was stopped where it stood), and `log`: arrays step, e_pot, ke (eV), t (K), p (GPa), v (A^3) every
         `loginterval` steps and at the last one."""
-        if isinstance(steps, bool) or int(steps) != steps or steps < 0:
-            raise ValueError(f"steps must be an integer >= 0; got {steps}")
-        if isinstance(loginterval, bool) or int(loginterval) != loginterval or loginterval < 1:
-            raise ValueError(f"loginterval must be an integer >= 1; got {loginterval}")
-        steps, loginterval = int(steps), int(loginterval)
-        lat, pos, z = Relaxer._arrays(lattices, positions, atomic_numbers)
+        steps, loginterval = integer("steps", steps, 0), integer("loginterval", loginterval, 1)
+        lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
         S = len(z)
         temps = np.broadcast_to(self.temperature, (S,)) if self.temperature.ndim == 0 or len(self.temperature) == S else None
         if temps is None:
             raise ValueError(f"temperature: expected one value or one per structure ({S}); got {len(self.temperature)}")
         seeds = structure_seeds(self.seed, S)
-        if masses is None:
-            m = [masses_of(a) for a in z]
-        else:
-            if len(masses) != S:
-                raise ValueError("masses: expected one array per structure")
-            m = [np.asarray(x, dtype=np.float64).reshape(-1) for x in masses]
-            for s, (ms, a) in enumerate(zip(m, z)):
-                if len(ms) != len(a) or not (np.isfinite(ms).all() and (ms > 0).all()):
-                    raise ValueError(f"structure {s}: masses must be {len(a)} finite values > 0")
+        m = structure_masses(masses, z)
         if velocities is None:
             vel = [maxwell_boltzmann(ms, t, int(sd)) for ms, t, sd in zip(m, temps, seeds)]
         else:
@@ -250,14 +215,7 @@ class MolecularDynamics:
                     log[key].append(obs[:, j] * (EV_PER_A3_IN_GPA if key == "p" else 1.0))
             if npt and k < steps:
                 vg.set_lattice(list(lat64.cpu().numpy()))   # (waits: the candidate search in the new cells needs them on the host)
-        # the sticky error bits of the last step's topology (m3g_md_step checks those of the EARLIER steps only)
-        if vg._md_buffers is not None and vg._lists_owner == "c":
-            n_e, n_t = vg._step_sizes
-            status = C.c_int32()
-            with _cuda.on_device(vg.device):
-                _lib.check(vg.lib.m3g_topology_status(vg.N, n_e, n_t, vg.S, _ptr(vg._md_buffers["topo"]), C.byref(status), _stream()))
-            if status.value:
-                raise RuntimeError(f"molecular dynamics: the last evaluation left error bits {status.value:#x} on its topology (M3G_TOPO_ERR_*)")
+        vg.raise_on_step_errors("molecular dynamics")
         st = dyn.read()
         e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
         p_host, l_host = pos_t.cpu().numpy(), lat64.cpu().numpy()

@@ -17,20 +17,20 @@ strains, third-order Birch-Murnaghan as a linear least-squares cubic in (V / V_r
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Sequence
 
 import numpy as np
 import torch
 
 from . import _cuda, _lib
+from ._driver import (EV_A3_TO_GPA, Driver, boolean, check_tensor, gpu_device, integer, positive, state_tensor, structure_arrays,
+                      sub_batches)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
 from .data.md import VerletGraph
 from .nn.modules import Gradient
-from .relax import FireState, Relaxer, _check_fmax, fire_step
+from .relax import FireState, fire_loop
 
-EV_A3_TO_GPA = 160.21766208
 NORM_STRAINS = (-0.01, -0.005, 0.005, 0.01)    # matcalc's ElasticityCalc defaults
 SHEAR_STRAINS = (-0.06, -0.03, 0.03, 0.06)
 EOS_STRAINS = tuple(np.linspace(-0.05, 0.05, 11).tolist())
@@ -90,15 +90,9 @@ class ElasticState:
         self.row_offsets = (1 + self.M) * self.offsets
         self.sizes = _lib.M3GElSizes(self.S, int(self.offsets[-1]), self.M, self.mode)
         self.rows, self.copies = int(self.row_offsets[-1]), (1 + self.M) * self.S
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError(f"ElasticState runs on a GPU device; got {self.device}")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = gpu_device(device, "ElasticState")
         self.lib = _lib.load_library()
-        nbytes = C.c_size_t()
-        _lib.check(self.lib.m3g_el_state_bytes(C.byref(self.sizes), C.byref(nbytes)))
-        self.state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self.state = state_tensor(self.lib.m3g_el_state_bytes, C.byref(self.sizes), device=self.device)
         self.pos = torch.zeros(self.rows, 3, dtype=torch.float64, device=self.device)
         self.lat = torch.zeros(self.copies, 3, 3, dtype=torch.float64, device=self.device)
         self.rows_elastic = torch.full((self.S, _lib.EL_ROW), float("nan"), dtype=torch.float64, device=self.device)
@@ -139,16 +133,11 @@ def el_deform(state: ElasticState):
     return state.pos, state.lat
 
 
-def _check_input(state: ElasticState, name: str, x: torch.Tensor, shape: tuple) -> None:
-    if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != state.pos.device:
-        raise ValueError(f"{name} must be a contiguous {list(shape)} float32 tensor on {state.pos.device}")
-
-
 def el_fit_elastic(state: ElasticState, stresses: torch.Tensor) -> torch.Tensor:
     """Elastic tensors and moduli of every structure (m3g_el_fit_elastic) from the engine's pair-virial `stresses` [copies, 6] float32
     of the deformed batch: written to and returned as `state.rows_elastic` (layout: M3G_EL_ROW_*); `state.nonfinite` too.  Queued on
     the current stream; no wait, capture-safe."""
-    _check_input(state, "stresses", stresses, (state.copies, 6))
+    check_tensor("stresses", stresses, (state.copies, 6), torch.float32, state.pos.device)
     with _cuda.on_device(state.device):
         _lib.check(state.lib.m3g_el_fit_elastic(C.byref(state.sizes), _ptr(state.state), state.state.numel(), _ptr(stresses),
                                                 _ptr(state.rows_elastic), _ptr(state.nonfinite), _stream()))
@@ -159,7 +148,7 @@ def el_fit_eos(state: ElasticState, energies: torch.Tensor) -> torch.Tensor:
     """Birch-Murnaghan fits of every structure (m3g_el_fit_eos) from the total `energies` [copies] float32 of the deformed batch:
     written to and returned as `state.rows_eos` (v0, e0, b0, b0', rms residual, v_ref, t0, points); `state.error` too.  Queued on the
     current stream; no wait, capture-safe."""
-    _check_input(state, "energies", energies, (state.copies,))
+    check_tensor("energies", energies, (state.copies,), torch.float32, state.pos.device)
     with _cuda.on_device(state.device):
         _lib.check(state.lib.m3g_el_fit_eos(C.byref(state.sizes), _ptr(state.state), state.state.numel(), _ptr(energies),
                                             _ptr(state.rows_eos), _ptr(state.error), _stream()))
@@ -209,28 +198,13 @@ class EosResult:
         self.error = bool(error != 0 or fire_error)
 
 
-class _StrainDriver:
+class _StrainDriver(Driver):
     """What `Elasticity` and `EquationOfState` share: the arguments and the evaluation of the deformed batch."""
 
     def __init__(self, model: Gradient, relax_atoms: bool, fmax: float, steps: int, max_atoms: int, skin: float, device):
-        self.relaxer = Relaxer(model, relax_cell=False, skin=skin, device=device)   # (type and skin checks)
-        if not isinstance(relax_atoms, (bool, np.bool_)):
-            raise ValueError(f"relax_atoms must be True or False; got {relax_atoms!r}")
-        self.fmax = _check_fmax(fmax)
-        for name, v, least in (("steps", steps, 0), ("max_atoms", max_atoms, 1)):
-            if isinstance(v, bool) or int(v) != v or v < least:
-                raise ValueError(f"{name} must be an integer >= {least}; got {v}")
-        self.relax_atoms, self.steps, self.max_atoms = bool(relax_atoms), int(steps), int(max_atoms)
-        self.model, self.skin, self.device = self.relaxer.model, self.relaxer.skin, self.relaxer.device
-
-    def _topology_status(self, vg: VerletGraph) -> None:
-        if vg._md_buffers is not None and vg._lists_owner == "c":   # the sticky error bits of this step's topology
-            n_e, n_t = vg._step_sizes
-            status = C.c_int32()
-            with _cuda.on_device(vg.device):
-                _lib.check(vg.lib.m3g_topology_status(vg.N, n_e, n_t, vg.S, _ptr(vg._md_buffers["topo"]), C.byref(status), _stream()))
-            if status.value:
-                raise RuntimeError(f"elasticity: the evaluation left error bits {status.value:#x} on its topology (M3G_TOPO_ERR_*)")
+        super().__init__(model, skin, device)
+        self.relax_atoms, self.fmax = boolean("relax_atoms", relax_atoms), positive("fmax", fmax)
+        self.steps, self.max_atoms = integer("steps", steps, 0), integer("max_atoms", max_atoms, 1)
 
     def _evaluate(self, st: ElasticState, z: Sequence[np.ndarray]):
         """Energies [copies], pair-virial stresses [copies, 6] (float32, device) and FIRE flags [copies] (host) of the deformed batch
@@ -241,15 +215,10 @@ class _StrainDriver:
         energies = torch.empty(st.copies, dtype=torch.float32, device=st.pos.device)
         stresses = torch.empty(st.copies, 6, dtype=torch.float32, device=st.pos.device)
         flags = np.full(st.copies, _lib.FIRE_CONVERGED, dtype=np.int32)
-        # the copies in row order, in sub-batches of one structure's copies only, at most max_atoms atoms (at least one copy): the
-        # engine's rounding depends on the composition of its batch, so a structure's sub-batches -- and with them its stresses and
-        # energies -- are the same alone or in any batch (as Phonons.run)
         n_copies = 1 + st.M
-        for s in range(st.S):
+        for s in range(st.S):   # the copies in row order, structure by structure (`sub_batches`, as Phonons.run)
             n = int(st.n_atoms[s])
-            per = max(1, self.max_atoms // n)
-            for c0 in range(0, n_copies, per):
-                nc = min(per, n_copies - c0)
+            for c0, nc in sub_batches(n_copies, n, self.max_atoms):
                 k0 = n_copies * s + c0
                 r0 = int(st.row_offsets[s]) + c0 * n
                 pos = st.pos[r0:r0 + nc * n]
@@ -258,19 +227,15 @@ class _StrainDriver:
                     out = vg.step(model, pos)
                 else:   # the fixed-cell loop of Relaxer.relax over the copies of this sub-batch
                     fire = FireState(pos, vg.lattice.clone(), np.arange(nc + 1) * n, relax_cell=False, fmax=self.fmax)
-                    for k in range(self.steps + 1):
-                        out = vg.step(model, pos)   # waits for the skin test, hence for the previous FIRE launch and its count
-                        if k > 0 and fire.n_unconverged == 0:
-                            break
-                        fire_step(fire, out[K.FORCES], out[K.STRESSES], check_only=(k == self.steps))
+                    out = fire_loop(vg, model, fire, self.steps)
                     flags[k0:k0 + nc] = fire.read()["flags"]
-                self._topology_status(vg)
+                vg.raise_on_step_errors("elasticity")
                 energies[k0:k0 + nc] = out[K.TOTAL_ENERGY].reshape(-1)
                 stresses[k0:k0 + nc] = out[K.STRESSES]
         return energies, stresses, flags
 
     def _prepare(self, lattices, positions, atomic_numbers, components, magnitudes):
-        lat, pos, z = Relaxer._arrays(lattices, positions, atomic_numbers)
+        lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
         st = ElasticState(lat, pos, components, magnitudes, device=self.device)
         el_deform(st)
         energies, stresses, flags = self._evaluate(st, z)

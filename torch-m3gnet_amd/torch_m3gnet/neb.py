@@ -16,27 +16,25 @@ last entry of an argsort).  Positions are never wrapped during a run: build the 
 (`interpolate(..., mic=True)` does), so plain differences are minimum-image differences."""
 from __future__ import annotations
 
-import ctypes as C
-import math
 from typing import Sequence
 
 import numpy as np
 import torch
 
 from . import _cuda, _lib
+from ._driver import Driver, boolean, check_tensor, integer, positive, state_tensor, structure_arrays
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
 from .data.md import VerletGraph
 from .nn.modules import Gradient
-from .relax import FireState, Relaxer, _check_fmax, fire_step
+from .relax import FireState, _relax, fire_loop
 
 
 def interpolate(lattice, initial_pos, final_pos, n_images: int, mic: bool = True) -> list:
     """`n_images` (M >= 3, endpoints included) position arrays [n, 3] on the straight line from `initial_pos` to `final_pos`.  mic:
     every atom of the final image is first moved to its periodic image nearest to the atom's initial position (fractional
     differences rounded to the nearest integer), so that the path never crosses the cell."""
-    if isinstance(n_images, bool) or int(n_images) != n_images or n_images < 3:
-        raise ValueError(f"n_images must be an integer >= 3 (endpoints included); got {n_images}")
+    m = integer("n_images (endpoints included)", n_images, 3)
     L = np.asarray(lattice, dtype=np.float64).reshape(3, 3)
     p0 = np.asarray(initial_pos, dtype=np.float64)
     p1 = np.asarray(final_pos, dtype=np.float64)
@@ -46,7 +44,6 @@ def interpolate(lattice, initial_pos, final_pos, n_images: int, mic: bool = True
     if mic:
         frac = np.linalg.solve(L.T, d.T).T
         d = (frac - np.round(frac)) @ L
-    m = int(n_images)
     return [p0 + (j / (m - 1)) * d for j in range(m)]
 
 
@@ -70,16 +67,13 @@ class NEBState:
         self.endpoint_energies = np.ascontiguousarray(np.asarray(endpoint_energies, dtype=np.float64).reshape(-1))
         if len(self.endpoint_energies) != 2 * self.B:
             raise ValueError(f"expected {2 * self.B} endpoint energies (initial, final per band)")
-        if endpoint_pos.dtype != torch.float64 or endpoint_pos.dim() != 2 or endpoint_pos.size(1) != 3 or not endpoint_pos.is_contiguous():
-            raise ValueError("endpoint_pos must be a contiguous [rows, 3] float64 tensor")
+        check_tensor("endpoint_pos", endpoint_pos, ("rows", 3), torch.float64)
         sizes = np.diff(self.image_offsets)[np.clip(self.band_images[:-1], 0, self.I - 1)]
         if endpoint_pos.size(0) != 2 * int(sizes.sum()):
             raise ValueError(f"endpoint_pos must hold {2 * int(sizes.sum())} rows (initial and final image of every band)")
         self.device = endpoint_pos.device
         self.lib = _lib.load_library()
-        nbytes = C.c_size_t()
-        _lib.check(self.lib.m3g_neb_state_bytes(self.N, self.I, self.B, C.byref(nbytes)))
-        self.state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self.state = state_tensor(self.lib.m3g_neb_state_bytes, self.N, self.I, self.B, device=self.device)
         self.forces = torch.zeros(self.N, 3, dtype=torch.float32, device=self.device)
         self.rows = torch.full((self.I, _lib.NEB_ROWS), float("nan"), dtype=torch.float64, device=self.device)
         with _cuda.on_device(self.device):
@@ -97,33 +91,24 @@ def neb_forces(state: NEBState, pos: torch.Tensor, energies: torch.Tensor, force
     """NEB forces of every interior image (m3g_neb_forces) at `pos` [N,3] float64 from `energies` [I] and `forces` [N,3] (float32,
     evaluated at `pos`): written to and returned as `state.forces`; `state.rows` gets the per-image observables.  Queued on the
     current stream; no wait, capture-safe."""
-    if pos.dtype != torch.float64 or tuple(pos.shape) != (state.N, 3) or not pos.is_contiguous():
-        raise ValueError(f"pos must be a contiguous [{state.N}, 3] float64 tensor")
-    if energies.dtype != torch.float32 or tuple(energies.shape) != (state.I,) or not energies.is_contiguous():
-        raise ValueError(f"energies must be a contiguous [{state.I}] float32 tensor")
-    if forces.dtype != torch.float32 or tuple(forces.shape) != (state.N, 3) or not forces.is_contiguous():
-        raise ValueError(f"forces must be a contiguous [{state.N}, 3] float32 tensor")
+    check_tensor("pos", pos, (state.N, 3), torch.float64)
+    check_tensor("energies", energies, (state.I,), torch.float32)
+    check_tensor("forces", forces, (state.N, 3), torch.float32)
     with _cuda.on_device(state.device):
         _lib.check(state.lib.m3g_neb_forces(state.N, state.I, state.B, _ptr(state.state), state.state.numel(), _ptr(pos), _ptr(energies),
                                             _ptr(forces), _ptr(state.forces), _ptr(state.rows), _stream()))
     return state.forces
 
 
-class NEB:
+class NEB(Driver):
     """Batched climbing-image NEB (improved tangent) under device FIRE.
 
     `model`: the `Gradient` returned by `build_model` (evaluated, like `Relaxer`'s, through a pair-virial engine made from its
     `Sequential`).  `k`: spring constant in eV/A^2 (ASE's default 0.1); `climb`: climbing image on (default) or off."""
 
     def __init__(self, model: Gradient, k: float = 0.1, climb: bool = True, skin: float = 0.5, device="cuda"):
-        self.relaxer = Relaxer(model, relax_cell=False, skin=skin, device=device)   # (type and skin checks)
-        k = float(k)
-        if not (math.isfinite(k) and k > 0.0):
-            raise ValueError(f"k must be a finite number > 0; got {k}")
-        if not isinstance(climb, (bool, np.bool_)):
-            raise ValueError(f"climb must be True or False; got {climb!r}")
-        self.k, self.climb = k, bool(climb)
-        self.model, self.skin, self.device = self.relaxer.model, self.relaxer.skin, self.relaxer.device
+        super().__init__(model, skin, device)
+        self.k, self.climb = positive("k", k), boolean("climb", climb)
 
     @staticmethod
     def _bands(bands):
@@ -136,7 +121,7 @@ class NEB:
             lattice, z, images = band
             if len(images) < 3:
                 raise ValueError(f"band {b}: a band needs at least 3 images (both endpoints and one interior image); got {len(images)}")
-            lat, pos, zs = Relaxer._arrays([lattice] * len(images), list(images), [z] * len(images))
+            lat, pos, zs = structure_arrays([lattice] * len(images), list(images), [z] * len(images))
             out.append((lat[0], zs[0], pos))
         return out
 
@@ -144,18 +129,15 @@ class NEB:
             endpoint_steps: int = 500) -> list:
         """Optimise every band (lattice [3,3] rows = lattice vectors, atomic_numbers [n], images: M >= 3 position arrays [n,3] in path
         order, endpoints included) until the largest NEB-force row of its interior images is below `fmax` or `steps` FIRE steps.
-        The endpoints are evaluated once; with `relax_endpoints` they are first relaxed (`Relaxer(relax_cell=False)`, to
+        The endpoints are evaluated once; with `relax_endpoints` they are first relaxed (as `Relaxer(relax_cell=False)` does, to
         `endpoint_fmax`, default `fmax`) and every interior image j of M is shifted by (1 - t) dR_0 + t dR_M-1, t = j / (M-1), with
         dR the endpoints' displacements (a straight band stays the straight band between the relaxed endpoints).
         Returns one dict per band: positions [M,n,3], energies [M], forces and neb_forces [M-2,n,3] (true and NEB forces of the
         interior images at the final positions), climbing_image (index in 0..M-1, None without climb), barrier_forward (E_max - E_0),
         barrier_backward (E_max - E_M-1), n_steps, converged, error (its projection met a non-finite value: stopped where it stood)."""
-        fmax = _check_fmax(fmax)
-        for name, n in (("steps", steps), ("endpoint_steps", endpoint_steps)):
-            if isinstance(n, bool) or int(n) != n or n < 0:
-                raise ValueError(f"{name} must be an integer >= 0; got {n}")
-        steps = int(steps)
-        efmax = fmax if endpoint_fmax is None else _check_fmax(endpoint_fmax)
+        fmax = positive("fmax", fmax)
+        steps, endpoint_steps = integer("steps", steps, 0), integer("endpoint_steps", endpoint_steps, 0)
+        efmax = fmax if endpoint_fmax is None else positive("endpoint_fmax", endpoint_fmax)
         bands = self._bands(bands)
         B = len(bands)
         model, dev = self.model, self.device
@@ -164,7 +146,7 @@ class NEB:
         ep_z = [z for _, z, _ in bands for _ in range(2)]
         ep_pos = [p for _, _, imgs in bands for p in (imgs[0], imgs[-1])]
         if relax_endpoints:
-            res = self.relaxer.relax(ep_lat, ep_pos, ep_z, fmax=efmax, steps=int(endpoint_steps))
+            res = _relax(model, ep_lat, ep_pos, ep_z, relax_cell=False, fmax=efmax, steps=endpoint_steps, skin=self.skin, device=dev)
             new_pos = [r["positions"] for r in res]
             ep_e = np.array([r["total_energy"] for r in res])
             for b, (_, _, imgs) in enumerate(bands):
@@ -187,21 +169,9 @@ class NEB:
         ep_t = torch.tensor(np.concatenate([p for _, _, imgs in bands for p in (imgs[0], imgs[-1])]), dtype=torch.float64, device=vg.device)
         neb = NEBState(image_offsets, band_images, self.k, self.climb, ep_t, ep_e.reshape(B, 2))
         fire = FireState(pos_t, None, neb.band_offsets, relax_cell=False, fmax=fmax)
-        out = None
-        for it in range(steps + 1):
-            out = vg.step(model, pos_t)   # waits for the skin test, hence for the previous FIRE launch and its count
-            if it > 0 and fire.n_unconverged == 0:
-                break                     # (nothing moved at that launch: `out` and the NEB forces belong to the final positions)
-            neb_forces(neb, pos_t, out[K.TOTAL_ENERGY], out[K.FORCES])
-            fire_step(fire, neb.forces, None, check_only=(it == steps))
-        # the sticky error bits of the last step's topology (m3g_md_step checks those of the EARLIER steps only)
-        if vg._md_buffers is not None and vg._lists_owner == "c":
-            n_e, n_t = vg._step_sizes
-            status = C.c_int32()
-            with _cuda.on_device(vg.device):
-                _lib.check(vg.lib.m3g_topology_status(vg.N, n_e, n_t, vg.S, _ptr(vg._md_buffers["topo"]), C.byref(status), _stream()))
-            if status.value:
-                raise RuntimeError(f"NEB: the last evaluation left error bits {status.value:#x} on its topology (M3G_TOPO_ERR_*)")
+        # (when the loop leaves early nothing moved at the last launch: `out` and the NEB forces belong to the final positions)
+        out = fire_loop(vg, model, fire, steps, project=lambda out: neb_forces(neb, pos_t, out[K.TOTAL_ENERGY], out[K.FORCES]))
+        vg.raise_on_step_errors("NEB")
         st = fire.read()
         e, f = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES))
         p_host, nf, rows = pos_t.cpu().numpy(), neb.forces.double().cpu().numpy(), neb.rows.cpu().numpy()

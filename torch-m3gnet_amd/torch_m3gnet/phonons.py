@@ -22,12 +22,12 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
+from ._driver import (Driver, boolean, check_tensor, gpu_device, integer, positive, state_tensor, structure_arrays, structure_masses,
+                      sub_batches)
 from .data import MaterialGraphKey as K
-from .data.atomic_masses import masses_of
 from .data.graph_gpu import _ptr, _stream
 from .data.md import VerletGraph
 from .nn.modules import Gradient
-from .relax import Relaxer
 
 # CODATA (SI 2019 exact values; the atomic mass constant from CODATA 2018)
 _EV = 1.602176634e-19          # J
@@ -85,15 +85,9 @@ class PhononState:
         self.pair_offsets = np.concatenate([[0], np.cumsum(self.n_unit * self.super_sizes)]).astype(np.int64)
         self.sizes = _sizes(self.n_unit, self.supercells)
         self.rows = int(self.row_offsets[-1])
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError(f"PhononState runs on a GPU device; got {self.device}")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = gpu_device(device, "PhononState")
         self.lib = _lib.load_library()
-        nbytes = C.c_size_t()
-        _lib.check(self.lib.m3g_ph_state_bytes(C.byref(self.sizes), C.byref(nbytes)))
-        self.state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self.state = state_tensor(self.lib.m3g_ph_state_bytes, C.byref(self.sizes), device=self.device)
         self.pos = torch.zeros(self.rows, 3, dtype=torch.float64, device=self.device)
         self.phi = torch.full((self.sizes.n_pairs, 3, 3), float("nan"), dtype=torch.float64, device=self.device)
         self.sums = torch.full((self.sizes.n_unit_atoms, 9), float("nan"), dtype=torch.float64, device=self.device)
@@ -122,8 +116,7 @@ def ph_displace(state: PhononState) -> torch.Tensor:
 def ph_force_constants(state: PhononState, forces: torch.Tensor, asr: bool = True) -> torch.Tensor:
     """Force constants of every structure (m3g_ph_force_constants) from `forces` [rows, 3] float32 of the displaced batch: written to
     and returned as `state.phi`; `state.sums` and `state.nonfinite` too.  Queued on the current stream; no wait, capture-safe."""
-    if forces.dtype != torch.float32 or tuple(forces.shape) != (state.rows, 3) or not forces.is_contiguous() or forces.device != state.pos.device:
-        raise ValueError(f"forces must be a contiguous [{state.rows}, 3] float32 tensor on {state.pos.device}")
+    check_tensor("forces", forces, (state.rows, 3), torch.float32, state.pos.device)
     with _cuda.on_device(state.device):
         _lib.check(state.lib.m3g_ph_force_constants(C.byref(state.sizes), _ptr(state.state), state.state.numel(), _ptr(forces),
                                                     1 if asr else 0, _ptr(state.phi), _ptr(state.sums), _ptr(state.nonfinite), _stream()))
@@ -241,14 +234,13 @@ class PhononResult:
         path = np.asarray(path, dtype=np.float64)
         if path.ndim != 2 or path.shape[1] != 3 or len(path) < 2:
             raise ValueError("path must be [>= 2, 3] fractional q-points")
-        if isinstance(npts, bool) or int(npts) != npts or npts < 2:
-            raise ValueError(f"npts must be an integer >= 2; got {npts}")
-        t = np.linspace(0.0, 1.0, int(npts))[:, None]
+        npts = integer("npts", npts, 2)
+        t = np.linspace(0.0, 1.0, npts)[:, None]
         q = np.concatenate([a + t * (b - a) for a, b in zip(path[:-1], path[1:])])
         recip = np.linalg.inv(self.lattice).T   # rows: reciprocal vectors (no 2 pi)
         steps = np.linalg.norm(np.diff(q, axis=0) @ recip, axis=1)
         dist = np.concatenate([[0.0], np.cumsum(steps)])
-        return {"q": q, "distance": dist, "vertices": dist[::int(npts)].tolist() + [float(dist[-1])], "frequencies": self.frequencies(q)}
+        return {"q": q, "distance": dist, "vertices": dist[::npts].tolist() + [float(dist[-1])], "frequencies": self.frequencies(q)}
 
     def mesh(self, n, gamma_centered: bool = True) -> dict:
         """Frequencies on an n1 x n2 x n3 mesh (Gamma-centred, or Monkhorst-Pack) with uniform weights."""
@@ -281,7 +273,7 @@ class PhononResult:
         return {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in out.items()}
 
 
-class Phonons:
+class Phonons(Driver):
     """Batched finite-displacement phonons under an M3GNet potential.
 
     `model`: the `Gradient` returned by `build_model` (evaluated, like `Relaxer`'s, through a pair-virial engine made from its
@@ -292,35 +284,17 @@ class Phonons:
 
     def __init__(self, model: Gradient, delta: float = 0.01, asr: bool = True, max_atoms: int = 200_000, max_qpoints: int = 4096,
                  cutoff_frequency: float = 1e-3, skin: float = 0.5, device="cuda"):
-        self.relaxer = Relaxer(model, relax_cell=False, skin=skin, device=device)   # (type and skin checks)
-        delta = float(delta)
-        if not (math.isfinite(delta) and delta > 0.0):
-            raise ValueError(f"delta must be a finite number > 0; got {delta}")
-        if not isinstance(asr, (bool, np.bool_)):
-            raise ValueError(f"asr must be True or False; got {asr!r}")
-        for name, v in (("max_atoms", max_atoms), ("max_qpoints", max_qpoints)):
-            if isinstance(v, bool) or int(v) != v or v < 1:
-                raise ValueError(f"{name} must be an integer >= 1; got {v}")
+        super().__init__(model, skin, device)
+        self.delta, self.asr = positive("delta", delta), boolean("asr", asr)
+        self.max_atoms, self.max_qpoints = integer("max_atoms", max_atoms, 1), integer("max_qpoints", max_qpoints, 1)
         cutoff_frequency = float(cutoff_frequency)
         if not (math.isfinite(cutoff_frequency) and cutoff_frequency >= 0.0):
             raise ValueError(f"cutoff_frequency must be finite and >= 0; got {cutoff_frequency}")
-        self.delta, self.asr, self.max_atoms, self.max_qpoints = delta, bool(asr), int(max_atoms), int(max_qpoints)
         self.cutoff_frequency = cutoff_frequency
-        self.model, self.skin, self.device = self.relaxer.model, self.relaxer.skin, self.relaxer.device
 
     def _check(self, lattices, positions, atomic_numbers, supercells, masses):
-        lat, pos, z = Relaxer._arrays(lattices, positions, atomic_numbers)
-        sc = _check_supercells(supercells, len(lat))
-        if masses is None:
-            m = [masses_of(a) for a in z]
-        else:
-            if len(masses) != len(z):
-                raise ValueError("masses must hold one entry per structure")
-            m = [np.asarray(x, dtype=np.float64).reshape(-1) for x in masses]
-            for s, (x, a) in enumerate(zip(m, z)):
-                if len(x) != len(a) or not (np.isfinite(x).all() and (x > 0).all()):
-                    raise ValueError(f"structure {s}: masses must be [n] finite values > 0")
-        return lat, pos, z, sc, m
+        lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
+        return lat, pos, z, _check_supercells(supercells, len(lat)), structure_masses(masses, z)
 
     def run(self, lattices: Sequence, positions: Sequence, atomic_numbers: Sequence, supercells, masses=None) -> list:
         """Phonons of every structure (lattices [3,3] rows = lattice vectors, positions [n_s,3] Cartesian, atomic_numbers [n_s],
@@ -332,29 +306,17 @@ class Phonons:
         st = PhononState(lat, pos, m, sc, self.delta, device=dev)
         ph_displace(st)
         forces = torch.empty(st.rows, 3, dtype=torch.float32, device=st.pos.device)
-        # the displaced supercells in row order, in sub-batches of one structure's copies only, at most max_atoms atoms (at least one
-        # copy): the engine's rounding depends on the composition of its batch, so a structure's sub-batches -- and with them its
-        # forces -- are the same alone or in any batch
-        batches = []
+        row = 0   # the displaced supercells in row order, structure by structure (`sub_batches`)
         for s in range(st.S):
-            ns, n_copies = int(st.super_sizes[s]), 1 + 6 * int(st.n_unit[s])
-            per = max(1, self.max_atoms // ns)
-            batches += [[s] * min(per, n_copies - c) for c in range(0, n_copies, per)]
-        row = 0
-        for b in batches:
-            n_rows = sum(int(st.super_sizes[s]) for s in b)
-            vg = VerletGraph([st.supercell_lattice(s) for s in b], [st.supercell_numbers(s, z[s]) for s in b], cfg.cutoff,
-                             cfg.threebody_cutoff, skin=self.skin, device=dev)
-            out = vg.step(model, st.pos[row:row + n_rows])
-            if vg._md_buffers is not None and vg._lists_owner == "c":   # the sticky error bits of this step's topology
-                n_e, n_t = vg._step_sizes
-                status = C.c_int32()
-                with _cuda.on_device(vg.device):
-                    _lib.check(vg.lib.m3g_topology_status(vg.N, n_e, n_t, vg.S, _ptr(vg._md_buffers["topo"]), C.byref(status), _stream()))
-                if status.value:
-                    raise RuntimeError(f"phonons: the evaluation left error bits {status.value:#x} on its topology (M3G_TOPO_ERR_*)")
-            forces[row:row + n_rows] = out[K.FORCES]
-            row += n_rows
+            ns = int(st.super_sizes[s])
+            for _, nc in sub_batches(1 + 6 * int(st.n_unit[s]), ns, self.max_atoms):
+                n_rows = nc * ns
+                vg = VerletGraph([st.supercell_lattice(s)] * nc, [st.supercell_numbers(s, z[s])] * nc, cfg.cutoff, cfg.threebody_cutoff,
+                                 skin=self.skin, device=dev)
+                out = vg.step(model, st.pos[row:row + n_rows])
+                vg.raise_on_step_errors("phonons")
+                forces[row:row + n_rows] = out[K.FORCES]
+                row += n_rows
         ph_force_constants(st, forces, self.asr)
         # residual forces: the undisplaced supercell of every structure
         norms = forces.double().norm(dim=1)

@@ -12,13 +12,13 @@ so the candidates are searched again at every step (`VerletGraph.set_lattice`).
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Sequence
 
 import numpy as np
 import torch
 
 from . import _cuda, _lib
+from ._driver import Driver, batch_layout, check_tensor, integer, positive, state_tensor, structure_arrays
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
 from .data.md import VerletGraph
@@ -26,13 +26,6 @@ from .nn.modules import Gradient
 
 # ASE's FIRE defaults (ase/optimize/fire.py), as m3gnet's Relaxer uses them
 FIRE_DEFAULTS = dict(dt=0.1, maxstep=0.2, dtmax=1.0, nmin=5, finc=1.1, fdec=0.5, astart=0.1, fa=0.99)
-
-
-def _check_fmax(fmax) -> float:
-    fmax = float(fmax)
-    if not (math.isfinite(fmax) and fmax > 0.0):
-        raise ValueError(f"fmax must be a finite number > 0; got {fmax}")
-    return fmax
 
 
 class FireState:
@@ -47,16 +40,9 @@ class FireState:
             raise TypeError(f"unknown FIRE parameters {sorted(unknown)}")
         p = dict(FIRE_DEFAULTS, **fire_params)
         self.params = _lib.M3GFireParams(dt=p["dt"], maxstep=p["maxstep"], dtmax=p["dtmax"], finc=p["finc"], fdec=p["fdec"],
-                                         astart=p["astart"], fa=p["fa"], fmax=_check_fmax(fmax), nmin=int(p["nmin"]),
+                                         astart=p["astart"], fa=p["fa"], fmax=positive("fmax", fmax), nmin=int(p["nmin"]),
                                          relax_cell=1 if relax_cell else 0)
-        if pos.dtype != torch.float64 or pos.dim() != 2 or pos.size(1) != 3 or not pos.is_contiguous():
-            raise ValueError("pos must be a contiguous [N, 3] float64 tensor")
-        self.offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-        self.N, self.S = int(pos.size(0)), int(len(self.offsets) - 1)
-        if self.S < 1:
-            raise ValueError("offsets must hold S + 1 >= 2 entries")
-        if lattice is not None and (lattice.dtype != torch.float64 or tuple(lattice.shape) != (self.S, 3, 3) or not lattice.is_contiguous()):
-            raise ValueError(f"lattice must be a contiguous [{self.S}, 3, 3] float64 tensor")
+        self.offsets, self.N, self.S = batch_layout(pos, lattice, offsets)
         if relax_cell and lattice is None:
             raise ValueError("a cell relaxation needs the lattice")
         self.relax_cell = bool(relax_cell)
@@ -64,9 +50,7 @@ class FireState:
         self.lattice32 = lattice.to(torch.float32) if lattice is not None else None
         self.device = pos.device
         self.lib = _lib.load_library()
-        nbytes = C.c_size_t()
-        _lib.check(self.lib.m3g_fire_state_bytes(self.N, self.S, C.byref(nbytes)))
-        self.state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self.state = state_tensor(self.lib.m3g_fire_state_bytes, self.N, self.S, device=self.device)
         self.unconverged = torch.full((1,), self.S, dtype=torch.int32).pin_memory()   # written by every m3g_fire_step
         self._unconverged = self.unconverged.numpy()
         with _cuda.on_device(self.device):
@@ -95,10 +79,9 @@ def fire_step(state: FireState, forces: torch.Tensor, stresses: torch.Tensor | N
     """One FIRE iteration of the batch (m3g_fire_step) at `forces` [N,3] and `stresses` [S,6] (float32, pair-virial convention: the
     virial is W = V * stresses) evaluated at `state.pos`: converged / failed structures are flagged and frozen, every other one takes
     a step.  Queued on the current stream; no wait."""
-    if forces.dtype != torch.float32 or tuple(forces.shape) != (state.N, 3) or not forces.is_contiguous():
-        raise ValueError(f"forces must be a contiguous [{state.N}, 3] float32 tensor")
-    if stresses is not None and (stresses.dtype != torch.float32 or tuple(stresses.shape) != (state.S, 6) or not stresses.is_contiguous()):
-        raise ValueError(f"stresses must be a contiguous [{state.S}, 6] float32 tensor")
+    check_tensor("forces", forces, (state.N, 3), torch.float32)
+    if stresses is not None:
+        check_tensor("stresses", stresses, (state.S, 6), torch.float32)
     with _cuda.on_device(state.device):
         _lib.check(state.lib.m3g_fire_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
                                            _ptr(stresses), _ptr(state.pos), _ptr(state.lattice) if state.relax_cell else None,
@@ -106,84 +89,63 @@ def fire_step(state: FireState, forces: torch.Tensor, stresses: torch.Tensor | N
                                            C.c_void_p(state.unconverged.data_ptr()), _stream()))
 
 
-class Relaxer:
+def fire_loop(vg: VerletGraph, model: Gradient, fire: FireState, steps: int, project=None) -> dict:
+    """Up to `steps` FIRE iterations of `fire` over `vg.step(model, fire.pos)`; returns the evaluation at the final positions.
+    `project(out)`: the forces FIRE takes instead of `out`'s own (NEB).  With a relaxed cell every iteration copies the cells to the
+    host and searches the candidates again (`vg.set_lattice`).  `fire.n_unconverged` is pinned memory written by the FIRE launch:
+    it is read only behind a wait that follows that launch (the next `vg.step`'s skin test, or the lattice copy)."""
+    out = None
+    for k in range(steps + 1):
+        out = vg.step(model, fire.pos)   # waits for the skin test, hence for the previous FIRE launch and its count
+        if k > 0 and not fire.relax_cell and fire.n_unconverged == 0:
+            break                        # (nothing moved at that launch: `out` holds the final positions' results)
+        forces, stresses = (out[K.FORCES], out[K.STRESSES]) if project is None else (project(out), None)
+        fire_step(fire, forces, stresses, check_only=(k == steps))
+        if fire.relax_cell:
+            host_lat = fire.lattice.cpu().numpy()   # (waits: the candidate search in the new cells needs them on the host)
+            if fire.n_unconverged == 0 or k == steps:
+                break
+            vg.set_lattice(list(host_lat))
+    return out
+
+
+def _relax(model: Gradient, lat: list, pos: list, z: list, *, relax_cell: bool, fmax: float, steps: int, skin: float, device) -> list:
+    """`Relaxer.relax` on checked arguments, with the pair-virial `model` of the driver that calls it."""
+    cfg = model.engine.cfg
+    vg = VerletGraph(lat, z, cfg.cutoff, cfg.threebody_cutoff, skin=skin, device=device)
+    pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=vg.device)
+    offsets = np.concatenate([[0], np.cumsum([len(a) for a in z])])
+    lat64 = vg.lattice.clone()   # the FIRE launch writes the relaxed cells here
+    fire = FireState(pos_t, lat64, offsets, relax_cell=relax_cell, fmax=fmax)
+    out = fire_loop(vg, model, fire, steps)
+    vg.raise_on_step_errors("relaxation")
+    st = fire.read()
+    e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
+    p_host, l_host = pos_t.cpu().numpy(), lat64.cpu().numpy()
+    res = []
+    for s in range(len(z)):
+        a, b = int(offsets[s]), int(offsets[s + 1])
+        res.append({"positions": p_host[a:b].copy(), "lattice": l_host[s].copy(), "total_energy": float(e[s]), "forces": f[a:b].copy(),
+                    "stresses": sv[s].copy(), "n_steps": int(st["n_steps"][s]),
+                    "converged": bool(st["flags"][s] & _lib.FIRE_CONVERGED), "error": bool(st["flags"][s] & _lib.FIRE_ERROR)})
+    return res
+
+
+class Relaxer(Driver):
     """Batched counterpart of m3g's `Relaxer` (scripts/relax_org.py): FIRE, the cell relaxed by default (ASE's UnitCellFilter).
 
     `model`: the `Gradient` returned by `build_model`; the relaxation evaluates a `pair_virial=True` engine made from its
     `Sequential` (the cell forces need the strain derivative, which the reference's stress formula is not)."""
 
     def __init__(self, model: Gradient, relax_cell: bool = True, skin: float = 0.5, device="cuda"):
-        if not isinstance(model, Gradient):
-            raise TypeError("Relaxer needs the Gradient model returned by build_model")
-        skin = float(skin)
-        if not (math.isfinite(skin) and skin > 0.0):
-            raise ValueError(f"skin must be a finite number > 0; got {skin}")
-        self.model = Gradient(model.model, pair_virial=True, legendre_backward=model.legendre_backward)
-        if model._engine is not None:
-            self.model.engine.set_precision(model._engine.precision)
-        self.relax_cell, self.skin, self.device = bool(relax_cell), skin, torch.device(device)
-
-    @staticmethod
-    def _arrays(lattices, positions, atomic_numbers):
-        if not (len(lattices) == len(positions) == len(atomic_numbers)) or len(lattices) == 0:
-            raise ValueError("lattices, positions and atomic_numbers must hold one entry per structure (at least one)")
-        lat = [np.asarray(L, dtype=np.float64) for L in lattices]
-        pos = [np.asarray(p, dtype=np.float64) for p in positions]
-        z = [np.asarray(a).reshape(-1) for a in atomic_numbers]
-        for s, (L, p, a) in enumerate(zip(lat, pos, z)):
-            if L.shape != (3, 3):
-                raise ValueError(f"structure {s}: lattice must be [3, 3]; got {L.shape}")
-            if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] != len(a) or len(a) == 0:
-                raise ValueError(f"structure {s}: positions must be [n, 3] with n = len(atomic_numbers) >= 1; got {p.shape} for {len(a)} atoms")
-            if not (np.isfinite(L).all() and np.isfinite(p).all()):
-                raise ValueError(f"structure {s}: non-finite lattice or positions")
-            if abs(np.linalg.det(L)) < 1e-12:
-                raise ValueError(f"structure {s}: singular lattice")
-        return lat, pos, z
+        super().__init__(model, skin, device)
+        self.relax_cell = bool(relax_cell)
 
     def relax(self, lattices: Sequence, positions: Sequence, atomic_numbers: Sequence, fmax: float = 0.1, steps: int = 500) -> list:
         """Relax every structure (lattices: [3,3] rows = lattice vectors, positions: [n_s,3] Cartesian, atomic_numbers: [n_s]) until
         max_i |g_i| < fmax (cell rows included when the cell is relaxed) or `steps` FIRE steps.  Returns one dict per structure:
         positions [n_s,3], lattice [3,3], total_energy, forces [n_s,3], stresses [6] (pair virial) at the final positions, n_steps,
         converged, error (its forces became non-finite: it was stopped where it stood)."""
-        fmax = _check_fmax(fmax)
-        if isinstance(steps, bool) or int(steps) != steps or steps < 0:
-            raise ValueError(f"steps must be an integer >= 0; got {steps}")
-        steps = int(steps)
-        lat, pos, z = self._arrays(lattices, positions, atomic_numbers)
-        model, dev = self.model, self.device
-        cfg = model.engine.cfg
-        vg = VerletGraph(lat, z, cfg.cutoff, cfg.threebody_cutoff, skin=self.skin, device=dev)
-        pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=vg.device)
-        offsets = np.concatenate([[0], np.cumsum([len(a) for a in z])])
-        lat64 = vg.lattice.clone()   # the FIRE launch writes the relaxed cells here
-        fire = FireState(pos_t, lat64, offsets, relax_cell=self.relax_cell, fmax=fmax)
-        out = None
-        for k in range(steps + 1):
-            out = vg.step(model, pos_t)   # waits for the skin test, hence for the previous FIRE launch and its count
-            if k > 0 and not self.relax_cell and fire.n_unconverged == 0:
-                break                     # (nothing moved at that launch: `out` holds the final positions' results)
-            fire_step(fire, out[K.FORCES], out[K.STRESSES], check_only=(k == steps))
-            if self.relax_cell:
-                host_lat = lat64.cpu().numpy()   # (waits: the candidate search in the new cells needs them on the host)
-                if fire.n_unconverged == 0 or k == steps:
-                    break
-                vg.set_lattice(list(host_lat))
-        # the sticky error bits of the last step's topology (m3g_md_step checks those of the EARLIER steps only)
-        if vg._md_buffers is not None and vg._lists_owner == "c":
-            n_e, n_t = vg._step_sizes
-            status = C.c_int32()
-            with _cuda.on_device(vg.device):
-                _lib.check(vg.lib.m3g_topology_status(vg.N, n_e, n_t, vg.S, _ptr(vg._md_buffers["topo"]), C.byref(status), _stream()))
-            if status.value:
-                raise RuntimeError(f"relaxation: the last evaluation left error bits {status.value:#x} on its topology (M3G_TOPO_ERR_*)")
-        st = fire.read()
-        e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
-        p_host, l_host = pos_t.cpu().numpy(), lat64.cpu().numpy()
-        res = []
-        for s in range(len(z)):
-            a, b = int(offsets[s]), int(offsets[s + 1])
-            res.append({"positions": p_host[a:b].copy(), "lattice": l_host[s].copy(), "total_energy": float(e[s]), "forces": f[a:b].copy(),
-                        "stresses": sv[s].copy(), "n_steps": int(st["n_steps"][s]),
-                        "converged": bool(st["flags"][s] & _lib.FIRE_CONVERGED), "error": bool(st["flags"][s] & _lib.FIRE_ERROR)})
-        return res
+        fmax, steps = positive("fmax", fmax), integer("steps", steps, 0)
+        lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
+        return _relax(self.model, lat, pos, z, relax_cell=self.relax_cell, fmax=fmax, steps=steps, skin=self.skin, device=self.device)
