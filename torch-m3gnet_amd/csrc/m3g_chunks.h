@@ -1,9 +1,13 @@
-// The per-structure chunk table of the batched integrators (FIRE in m3g_relax.hip, MD in m3g_dynamics.hip): the N atoms of S
-// structures cut into chunks of <= kChunkRows atoms that never straddle a structure, so a reduction over a chunk's rows followed by
-// one over a structure's chunks in chunk order depends on that structure's own rows only -- bitwise the same alone or in any batch.
-// Device side: the offsets [S+1] (int64), the structure of every chunk and its first atom, and every structure's first chunk
-// ([S] = the number of chunks), built on the host from the caller's offsets and copied into the state buffer by the init call.
+// The device and C-ABI layer the five batched drivers share (m3g_relax.hip, m3g_dynamics.hip, m3g_neb.hip, m3g_phonons.hip,
+// m3g_elastic.hip).  The chunk table: the N atoms of S structures cut into chunks of <= kChunkRows atoms that never straddle a
+// structure, so a reduction over a chunk's rows (chunk_tree_reduce) followed by one over a structure's chunks in chunk order
+// (wave_chunk_sum, or a serial walk) depends on that structure's own rows only -- bitwise the same alone or in any batch.  Device
+// side: the offsets [S+1] (int64), the structure of every chunk and its first atom, and every structure's first chunk ([S] = the
+// number of chunks), built on the host from the caller's offsets and copied into the state buffer by the init call.
+// No device function here multiplies: a kernel's own floating-point contraction mode (some switch it off, lexically) must keep
+// deciding every rounding, and a helper would bring its own.  det3 / inv3 are host code.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -11,33 +15,121 @@
 #include "m3g_internal.h"
 
 namespace m3g {
-constexpr int kChunkRows = 256;   // atoms per chunk == threads per workgroup of the row kernels
+constexpr int kChunkRows = 256;       // atoms per chunk == threads per workgroup of the row kernels
+constexpr int kWave = 64;
+constexpr int kFinalizeWaves = 4;     // structures (one wave each) per workgroup of the wave-per-structure kernels
 
 // chunks of a batch, at most (a bound that needs no offsets, so launch grids and buffer sizes follow from N and S alone)
 inline int64_t chunk_bound(int64_t N, int64_t S) { return (N + kChunkRows - 1) / kChunkRows + S; }
 
+// hands out the 256-byte-aligned regions of a caller's state buffer, one after the other; `total` is the size so far
+struct StateArena {
+  size_t total = 0;
+  size_t take(size_t bytes) { const size_t at = total; total += (bytes + 255) & ~size_t(255); return at; }
+};
+
 struct ChunkLayout {
+  int64_t S;
   size_t offsets, chunk_struct, chunk_begin, first_chunk;
 };
-// `take(bytes)` returns the offset of the next region of the caller's state buffer
-template <class Take>
-ChunkLayout chunk_layout(int64_t N, int64_t S, Take&& take) {
+inline ChunkLayout chunk_layout(int64_t N, int64_t S, StateArena& arena) {
   const int64_t C = chunk_bound(N, S);
   ChunkLayout L{};
-  L.offsets = take(8 * (S + 1));
-  L.chunk_struct = take(4 * C);
-  L.chunk_begin = take(8 * C);
-  L.first_chunk = take(4 * (S + 1));   // [S] = number of chunks
+  L.S = S;
+  L.offsets = arena.take(8 * (S + 1));
+  L.chunk_struct = arena.take(4 * C);
+  L.chunk_begin = arena.take(8 * C);
+  L.first_chunk = arena.take(4 * (S + 1));   // [S] = number of chunks
   return L;
 }
 
-// 0 = o_0 < o_1 < ... < o_S = N; otherwise sets the library error ("<fn>: offsets ...") and returns false
-inline bool chunk_offsets_ok(const char* fn, const int64_t* host_offsets, int64_t N, int64_t S) {
-  if (host_offsets[0] != 0 || host_offsets[S] != N) { set_error("%s: offsets must run from 0 to n_atoms", fn); return false; }
+// The device side of the table.  Row kernels run one workgroup per chunk (a grid of chunk_bound() workgroups: those beyond the
+// table's chunk count return at once), thread t on row t of the chunk.
+struct ChunkView {
+  int64_t S;
+  const int64_t* offsets;
+  const int32_t* chunk_struct;
+  const int64_t* chunk_begin;
+  const int32_t* first_chunk;
+  __device__ int n_chunks() const { return first_chunk[S]; }
+  __device__ int structure(int c) const { return chunk_struct[c]; }   // c < n_chunks()
+  __device__ int64_t row(int c, int t) const { return chunk_begin[c] + t; }
+  __device__ bool holds(int s, int64_t row) const { return row < offsets[s + 1]; }   // (a structure's last chunk may be part-filled)
+  __device__ int chunks_begin(int64_t s) const { return first_chunk[s]; }
+  __device__ int chunks_end(int64_t s) const { return first_chunk[s + 1]; }
+};
+inline ChunkView chunk_view(const ChunkLayout& L, const void* state) {
+  const char* b = (const char*)state;
+  return ChunkView{L.S, (const int64_t*)(b + L.offsets), (const int32_t*)(b + L.chunk_struct), (const int64_t*)(b + L.chunk_begin),
+                   (const int32_t*)(b + L.first_chunk)};
+}
+
+__device__ inline double max_nan(double m, double x) { return (x > m || x != x) ? x : m; }   // a NaN row stays visible
+
+// K columns over the kChunkRows threads of a workgroup, thread t contributing val[]: the result of column j is sh[j][0].  A fixed
+// tree, so the order depends on the row's place in its chunk only.  The first K - KMax columns are sums, the last KMax max_nan.
+template <int K, int KMax = 0, class T>
+__device__ inline void chunk_tree_reduce(T (&sh)[K][kChunkRows], const T (&val)[K], int t) {
+  for (int j = 0; j < K; ++j) sh[j][t] = val[j];
+  __syncthreads();
+  for (int w = kChunkRows / 2; w > 0; w >>= 1) {
+    if (t < w) {
+      for (int j = 0; j < K - KMax; ++j) sh[j][t] += sh[j][t + w];
+      if constexpr (KMax > 0)
+        for (int j = K - KMax; j < K; ++j) sh[j][t] = max_nan(sh[j][t], sh[j][t + w]);
+    }
+    __syncthreads();
+  }
+}
+
+// The sums of structure s's chunk partials ([chunk][K]) by one wave: lane-strided in chunk order, then a butterfly (a + b on both
+// partners, so every lane ends with the same bits).
+template <int K>
+__device__ inline void wave_chunk_sum(const ChunkView& ch, int64_t s, const double* partial, int lane, double (&acc)[K]) {
+  for (int j = 0; j < K; ++j) acc[j] = 0.0;
+  for (int c = ch.chunks_begin(s) + lane; c < ch.chunks_end(s); c += kWave)
+    for (int j = 0; j < K; ++j) acc[j] += partial[K * c + j];
+#pragma unroll   // (as the compiler did of its own accord while this loop stood in the kernels)
+  for (int w = kWave / 2; w > 0; w >>= 1)
+    for (int j = 0; j < K; ++j) acc[j] += __shfl_xor(acc[j], w, kWave);
+}
+
+// Host checks; the _ok ones set the library error ("<fn>: ...") and return false.
+inline bool finite_positive(double x) { return std::isfinite(x) && x > 0.0; }
+inline bool batch_sizes_ok(int64_t N, int64_t S) { return N >= 1 && S >= 1 && S <= N; }   // every structure holds an atom
+
+// 0 = o_0 < o_1 < ... < o_S = N; `what` names the offsets and `upto` their end in the message
+inline bool offsets_ok(const char* fn, const int64_t* host_offsets, int64_t N, int64_t S, const char* what = "offsets",
+                       const char* upto = "n_atoms") {
+  if (host_offsets[0] != 0 || host_offsets[S] != N) { set_error("%s: %s must run from 0 to %s", fn, what, upto); return false; }
   for (int64_t s = 0; s < S; ++s)
-    if (host_offsets[s + 1] <= host_offsets[s]) { set_error("%s: offsets must increase strictly (every structure holds an atom)", fn); return false; }
+    if (host_offsets[s + 1] <= host_offsets[s]) { set_error("%s: %s must increase strictly (every structure holds an atom)", fn, what); return false; }
   return true;
 }
+
+// rows = lattice vectors (host arithmetic: the kernels spell their own determinants out)
+inline double det3(const double* L) {
+  return L[0] * (L[4] * L[8] - L[5] * L[7]) - L[1] * (L[3] * L[8] - L[5] * L[6]) + L[2] * (L[3] * L[7] - L[4] * L[6]);
+}
+inline void inv3(const double* L, double inv[9]) {   // from the adjugate
+  const double det = det3(L);
+  inv[0] = (L[4] * L[8] - L[5] * L[7]) / det; inv[1] = (L[2] * L[7] - L[1] * L[8]) / det; inv[2] = (L[1] * L[5] - L[2] * L[4]) / det;
+  inv[3] = (L[5] * L[6] - L[3] * L[8]) / det; inv[4] = (L[0] * L[8] - L[2] * L[6]) / det; inv[5] = (L[2] * L[3] - L[0] * L[5]) / det;
+  inv[6] = (L[3] * L[7] - L[4] * L[6]) / det; inv[7] = (L[1] * L[6] - L[0] * L[7]) / det; inv[8] = (L[0] * L[4] - L[1] * L[3]) / det;
+}
+
+// the lattice of structure s: finite, |det| >= 1e-12 (one structure per call, so a driver can keep it in its per-structure order)
+inline bool lattice_ok(const char* fn, const double* L, int64_t s) {
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(L[k])) { set_error("%s: lattice of structure %lld is not finite", fn, (long long)s); return false; }
+  if (!(std::fabs(det3(L)) >= 1e-12)) { set_error("%s: singular cell of structure %lld", fn, (long long)s); return false; }
+  return true;
+}
+
+inline dim3 blocks_for(int64_t n, int threads) { return dim3((unsigned)((n + threads - 1) / threads)); }
+
+// the tail of a call that launched (a macro, as M3G_HIP_CHECK: the error names the caller's file and line)
+#define M3G_RETURN_LAUNCH_STATUS() do { M3G_HIP_CHECK(hipGetLastError()); return M3G_OK; } while (0)
 
 // The host side of the table.  upload() queues asynchronous copies from these vectors: keep the object alive until the stream has
 // been synchronised.
@@ -56,11 +148,11 @@ struct ChunkTable {
     first_chunk[S] = (int32_t)chunk_struct.size();
   }
 
-  int upload(const ChunkLayout& L, char* state, const int64_t* host_offsets, int64_t S, hipStream_t s) const {
-    M3G_HIP_CHECK(hipMemcpyAsync(state + L.offsets, host_offsets, 8 * (S + 1), hipMemcpyHostToDevice, s));
+  int upload(const ChunkLayout& L, char* state, const int64_t* host_offsets, hipStream_t s) const {
+    M3G_HIP_CHECK(hipMemcpyAsync(state + L.offsets, host_offsets, 8 * (L.S + 1), hipMemcpyHostToDevice, s));
     M3G_HIP_CHECK(hipMemcpyAsync(state + L.chunk_struct, chunk_struct.data(), 4 * chunk_struct.size(), hipMemcpyHostToDevice, s));
     M3G_HIP_CHECK(hipMemcpyAsync(state + L.chunk_begin, chunk_begin.data(), 8 * chunk_begin.size(), hipMemcpyHostToDevice, s));
-    M3G_HIP_CHECK(hipMemcpyAsync(state + L.first_chunk, first_chunk.data(), 4 * (S + 1), hipMemcpyHostToDevice, s));
+    M3G_HIP_CHECK(hipMemcpyAsync(state + L.first_chunk, first_chunk.data(), 4 * (L.S + 1), hipMemcpyHostToDevice, s));
     return M3G_OK;
   }
 };

@@ -21,8 +21,6 @@ constexpr double kKappa = 9.648533215665e-3;   // A/fs^2 per eV/(A amu)
 constexpr double kBoltzmann = 8.617333262e-5;  // eV/K
 constexpr int kPart = 8;    // per chunk: sum m|v|^2, sum m v [3], sum F [3], non-finite forces
 constexpr int kCoef = 8;    // per structure: action (0 none, 1 finish only, 2 finish + start), finish?, lambda, mu, pbar [3], noise^2
-constexpr int kWave = 64;
-constexpr int kFinalizeWaves = 4;
 
 struct DynLayout {
   ChunkLayout chunks;
@@ -30,27 +28,23 @@ struct DynLayout {
 };
 DynLayout dyn_layout(int64_t N, int64_t S) {
   DynLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
-  L.chunks = chunk_layout(N, S, take);
-  L.partial = take(8 * kPart * chunk_bound(N, S));
-  L.mass = take(8 * N);
-  L.v = take(8 * 3 * N);
-  L.t0 = take(8 * S);
-  L.seed = take(8 * S);
-  L.flags = take(4 * S);
-  L.steps = take(8 * S);
-  L.coef = take(8 * kCoef * S);
-  L.total = o;
+  StateArena arena;
+  L.chunks = chunk_layout(N, S, arena);
+  L.partial = arena.take(8 * kPart * chunk_bound(N, S));
+  L.mass = arena.take(8 * N);
+  L.v = arena.take(8 * 3 * N);
+  L.t0 = arena.take(8 * S);
+  L.seed = arena.take(8 * S);
+  L.flags = arena.take(4 * S);
+  L.steps = arena.take(8 * S);
+  L.coef = arena.take(8 * kCoef * S);
+  L.total = arena.total;
   return L;
 }
 
 struct DynView {
-  int64_t N, S;
-  const int64_t* offsets;
-  const int32_t* chunk_struct;
-  const int64_t* chunk_begin;
-  const int32_t* first_chunk;
+  int64_t N;
+  ChunkView ch;
   double *partial, *mass, *v, *t0, *coef;
   uint64_t* seed;
   int32_t* flags;
@@ -59,10 +53,8 @@ struct DynView {
 DynView dyn_view(int64_t N, int64_t S, void* state) {
   const DynLayout L = dyn_layout(N, S);
   char* b = (char*)state;
-  return DynView{N, S, (const int64_t*)(b + L.chunks.offsets), (const int32_t*)(b + L.chunks.chunk_struct),
-                 (const int64_t*)(b + L.chunks.chunk_begin), (const int32_t*)(b + L.chunks.first_chunk), (double*)(b + L.partial),
-                 (double*)(b + L.mass), (double*)(b + L.v), (double*)(b + L.t0), (double*)(b + L.coef), (uint64_t*)(b + L.seed),
-                 (int32_t*)(b + L.flags), (int64_t*)(b + L.steps)};
+  return DynView{N, chunk_view(L.chunks, state), (double*)(b + L.partial), (double*)(b + L.mass), (double*)(b + L.v), (double*)(b + L.t0),
+                 (double*)(b + L.coef), (uint64_t*)(b + L.seed), (int32_t*)(b + L.flags), (int64_t*)(b + L.steps)};
 }
 
 // Philox4x64-10 (Salmon et al., SC'11; the generator of numpy.random.Philox)
@@ -92,7 +84,7 @@ __device__ inline void gaussian3(uint64_t seed, uint64_t k, uint64_t local, doub
 __global__ void __launch_bounds__(kChunkRows) k_dyn_init(DynView st, const double* __restrict__ vel) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < 3 * st.N) st.v[i] = vel[i];
-  if (i < st.S) {
+  if (i < st.ch.S) {
     st.flags[i] = 0;
     st.steps[i] = 0;
     st.coef[kCoef * i] = 0.0;
@@ -102,13 +94,13 @@ __global__ void __launch_bounds__(kChunkRows) k_dyn_init(DynView st, const doubl
 __global__ void __launch_bounds__(kChunkRows) k_dyn_partials(DynView st, double half_dt, const float* __restrict__ forces) {
   __shared__ double sh[kPart][kChunkRows];
   const int c = blockIdx.x, t = threadIdx.x;
-  if (c >= st.first_chunk[st.S]) return;
-  const int s = st.chunk_struct[c];
+  if (c >= st.ch.n_chunks()) return;
+  const int s = st.ch.structure(c);
   const int fl = st.flags[s];
   if (fl & M3G_DYN_ERROR) return;   // frozen: finalize reads nothing of it
-  const int64_t i = st.chunk_begin[c] + t;
+  const int64_t i = st.ch.row(c, t);
   double val[kPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (i < st.offsets[s + 1]) {
+  if (st.ch.holds(s, i)) {
     const double m = st.mass[i];
     double f[3], v[3];
     for (int k = 0; k < 3; ++k) {
@@ -123,13 +115,7 @@ __global__ void __launch_bounds__(kChunkRows) k_dyn_partials(DynView st, double 
     }
     val[7] = (std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2])) ? 0.0 : 1.0;
   }
-  for (int j = 0; j < kPart; ++j) sh[j][t] = val[j];
-  __syncthreads();
-  for (int w = kChunkRows / 2; w > 0; w >>= 1) {   // fixed tree: the order depends on the row's place in its chunk only
-    if (t < w)
-      for (int j = 0; j < kPart; ++j) sh[j][t] += sh[j][t + w];
-    __syncthreads();
-  }
+  chunk_tree_reduce<kPart>(sh, val, t);
   if (t < kPart) st.partial[kPart * c + t] = sh[t][0];
 }
 
@@ -138,18 +124,15 @@ __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_dyn_finalize(DynView
                                                                          float* __restrict__ lattice32, double* __restrict__ obs) {
   const int lane = threadIdx.x % kWave;
   const int64_t s = (int64_t)blockIdx.x * kFinalizeWaves + threadIdx.x / kWave;
-  if (s >= st.S) return;   // (whole waves: s is uniform across a wave)
+  if (s >= st.ch.S) return;   // (whole waves: s is uniform across a wave)
   const int fl = st.flags[s];
   double* coef = st.coef + kCoef * s;
   if (fl & M3G_DYN_ERROR) {
     if (lane == 0) coef[0] = 0.0;
     return;
   }
-  double acc[kPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int c = st.first_chunk[s] + lane; c < st.first_chunk[s + 1]; c += kWave)
-    for (int j = 0; j < kPart; ++j) acc[j] += st.partial[kPart * c + j];
-  for (int w = kWave / 2; w > 0; w >>= 1)   // butterfly: a + b on both partners, so every lane ends with the same bits
-    for (int j = 0; j < kPart; ++j) acc[j] += __shfl_xor(acc[j], w, kWave);
+  double acc[kPart];
+  wave_chunk_sum<kPart>(st.ch, s, st.partial, lane, acc);
   if (lane != 0) return;
   const bool npt = p.ensemble == M3G_DYN_NPT_BERENDSEN;
   bool bad = acc[7] != 0.0;
@@ -161,7 +144,7 @@ __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_dyn_finalize(DynView
     coef[0] = 0.0;
     return;
   }
-  const double n = (double)(st.offsets[s + 1] - st.offsets[s]);
+  const double n = (double)(st.ch.offsets[s + 1] - st.ch.offsets[s]);
   const double ke = acc[0] / (2.0 * kKappa);
   const double two_ke = 2.0 * ke;
   const double temp = two_ke / (3.0 * n * kBoltzmann);
@@ -212,13 +195,13 @@ __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_dyn_finalize(DynView
 __global__ void __launch_bounds__(kChunkRows) k_dyn_apply(DynView st, m3g_dyn_params p, double c1, const float* __restrict__ forces,
                                                           double* __restrict__ pos) {
   const int c = blockIdx.x;
-  if (c >= st.first_chunk[st.S]) return;
-  const int s = st.chunk_struct[c];
+  if (c >= st.ch.n_chunks()) return;
+  const int s = st.ch.structure(c);
   const double* coef = st.coef + kCoef * s;
   const double act = coef[0];
   if (act == 0.0) return;   // failed: bitwise untouched
-  const int64_t i = st.chunk_begin[c] + threadIdx.x;
-  if (i >= st.offsets[s + 1]) return;
+  const int64_t i = st.ch.row(c, threadIdx.x);
+  if (!st.ch.holds(s, i)) return;
   const double m = st.mass[i], h = 0.5 * p.dt;
   double a[3], v[3], x[3];
   for (int k = 0; k < 3; ++k) {
@@ -233,7 +216,7 @@ __global__ void __launch_bounds__(kChunkRows) k_dyn_apply(DynView st, m3g_dyn_pa
   for (int k = 0; k < 3; ++k) x[k] = pos[3 * i + k];
   if (p.ensemble == M3G_DYN_NVT_LANGEVIN) {   // B A O A
     double xi[3];
-    gaussian3(st.seed[s], (uint64_t)(st.steps[s] - 1), (uint64_t)(i - st.offsets[s]), xi);
+    gaussian3(st.seed[s], (uint64_t)(st.steps[s] - 1), (uint64_t)(i - st.ch.offsets[s]), xi);
     const double sigma = sqrt(coef[7] / m);
     for (int k = 0; k < 3; ++k) {
       v[k] += h * a[k];
@@ -259,17 +242,16 @@ __global__ void __launch_bounds__(kChunkRows) k_dyn_apply(DynView st, m3g_dyn_pa
 
 // nullptr when the parameters are valid, else what is wrong with them
 const char* dyn_params_error(const m3g_dyn_params* p) {
-  auto pos_finite = [](double x) { return std::isfinite(x) && x > 0.0; };
   if (!p) return "null parameters";
   if (p->ensemble < M3G_DYN_NVE || p->ensemble > M3G_DYN_NPT_BERENDSEN) return "unknown ensemble";
   if (p->fix_com != 0 && p->fix_com != 1) return "fix_com must be 0 or 1";
-  if (!pos_finite(p->dt)) return "dt must be finite and > 0";
+  if (!finite_positive(p->dt)) return "dt must be finite and > 0";
   if (!(std::isfinite(p->friction) && p->friction >= 0.0)) return "friction must be finite and >= 0";
   const bool berendsen = p->ensemble == M3G_DYN_NVT_BERENDSEN || p->ensemble == M3G_DYN_NPT_BERENDSEN;
-  if (berendsen && !pos_finite(p->taut)) return "taut must be finite and > 0";
+  if (berendsen && !finite_positive(p->taut)) return "taut must be finite and > 0";
   if (p->ensemble == M3G_DYN_NPT_BERENDSEN) {
-    if (!pos_finite(p->taup)) return "taup must be finite and > 0";
-    if (!pos_finite(p->compressibility)) return "compressibility must be finite and > 0";
+    if (!finite_positive(p->taup)) return "taup must be finite and > 0";
+    if (!finite_positive(p->compressibility)) return "compressibility must be finite and > 0";
     if (!std::isfinite(p->pressure)) return "pressure must be finite";
   }
   if (p->ensemble == M3G_DYN_NVT_LANGEVIN && p->fix_com) return "fix_com is not supported with the Langevin thermostat";
@@ -283,7 +265,7 @@ double langevin_c1(const m3g_dyn_params* p) { return p->ensemble == M3G_DYN_NVT_
 using namespace m3g;
 
 extern "C" int m3g_dyn_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* bytes) {
-  if (!bytes || n_atoms < 1 || n_structs < 1 || n_structs > n_atoms) { set_error("m3g_dyn_state_bytes: bad sizes"); return M3G_ERR_VALUE; }
+  if (!bytes || !batch_sizes_ok(n_atoms, n_structs)) { set_error("m3g_dyn_state_bytes: bad sizes"); return M3G_ERR_VALUE; }
   *bytes = dyn_layout(n_atoms, n_structs).total;
   return M3G_OK;
 }
@@ -292,14 +274,14 @@ extern "C" int m3g_dyn_init(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_
                             const double* host_temperatures, const uint64_t* host_seeds, const double* vel, void* state, size_t state_bytes,
                             void* stream_) {
   if (const char* why = dyn_params_error(p)) { set_error("m3g_dyn_init: invalid parameters: %s", why); return M3G_ERR_VALUE; }
-  if (n_atoms < 1 || n_structs < 1 || n_structs > n_atoms || !host_offsets || !host_masses || !host_temperatures || !host_seeds || !vel || !state) {
+  if (!batch_sizes_ok(n_atoms, n_structs) || !host_offsets || !host_masses || !host_temperatures || !host_seeds || !vel || !state) {
     set_error("m3g_dyn_init: null argument or bad sizes");
     return M3G_ERR_VALUE;
   }
   const int64_t N = n_atoms, S = n_structs;
-  if (!chunk_offsets_ok("m3g_dyn_init", host_offsets, N, S)) return M3G_ERR_VALUE;
+  if (!offsets_ok("m3g_dyn_init", host_offsets, N, S)) return M3G_ERR_VALUE;
   for (int64_t i = 0; i < N; ++i)
-    if (!(std::isfinite(host_masses[i]) && host_masses[i] > 0.0)) { set_error("m3g_dyn_init: mass of atom %lld is not finite and > 0", (long long)i); return M3G_ERR_VALUE; }
+    if (!finite_positive(host_masses[i])) { set_error("m3g_dyn_init: mass of atom %lld is not finite and > 0", (long long)i); return M3G_ERR_VALUE; }
   for (int64_t s = 0; s < S; ++s)
     if (!(std::isfinite(host_temperatures[s]) && host_temperatures[s] >= 0.0)) {
       set_error("m3g_dyn_init: temperature of structure %lld is not finite and >= 0", (long long)s);
@@ -310,12 +292,12 @@ extern "C" int m3g_dyn_init(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
   char* b = (char*)state;
-  if (int rc = table.upload(L.chunks, b, host_offsets, S, s)) return rc;
+  if (int rc = table.upload(L.chunks, b, host_offsets, s)) return rc;
   M3G_HIP_CHECK(hipMemcpyAsync(b + L.mass, host_masses, 8 * N, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync(b + L.t0, host_temperatures, 8 * S, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync(b + L.seed, host_seeds, 8 * S, hipMemcpyHostToDevice, s));
   const int64_t work = 3 * N > S ? 3 * N : S;
-  hipLaunchKernelGGL(k_dyn_init, dim3((unsigned)((work + kChunkRows - 1) / kChunkRows)), dim3(kChunkRows), 0, s, dyn_view(N, S, state), vel);
+  hipLaunchKernelGGL(k_dyn_init, blocks_for(work, kChunkRows), dim3(kChunkRows), 0, s, dyn_view(N, S, state), vel);
   M3G_HIP_CHECK(hipGetLastError());
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;
@@ -324,26 +306,25 @@ extern "C" int m3g_dyn_init(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_
 extern "C" int m3g_dyn_step(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
                             const float* stresses, double* pos, double* lattice, float* lattice32, int32_t finish_only, double* obs, void* stream_) {
   if (const char* why = dyn_params_error(p)) { set_error("m3g_dyn_step: invalid parameters: %s", why); return M3G_ERR_VALUE; }
-  if (n_atoms < 1 || n_structs < 1 || n_structs > n_atoms || !state || !forces || !pos) { set_error("m3g_dyn_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  if (p->ensemble == M3G_DYN_NPT_BERENDSEN && (!stresses || !lattice)) { set_error("m3g_dyn_step: NPT needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
   const int64_t N = n_atoms, S = n_structs;
+  if (!batch_sizes_ok(N, S) || !state || !forces || !pos) { set_error("m3g_dyn_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
+  if (p->ensemble == M3G_DYN_NPT_BERENDSEN && (!stresses || !lattice)) { set_error("m3g_dyn_step: NPT needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
   if (state_bytes < dyn_layout(N, S).total) { set_error("m3g_dyn_step: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
   const DynView st = dyn_view(N, S, state);
   const double c1 = langevin_c1(p);
   const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_dyn_partials, grid, dim3(kChunkRows), 0, s, st, 0.5 * p->dt, forces);
-  hipLaunchKernelGGL(k_dyn_finalize, dim3((unsigned)((S + kFinalizeWaves - 1) / kFinalizeWaves)), dim3(kWave * kFinalizeWaves), 0, s, st, *p,
+  hipLaunchKernelGGL(k_dyn_finalize, blocks_for(S, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, *p,
                      finish_only, c1, stresses, lattice, lattice32, obs);
   hipLaunchKernelGGL(k_dyn_apply, grid, dim3(kChunkRows), 0, s, st, *p, c1, forces, pos);
-  M3G_HIP_CHECK(hipGetLastError());
-  return M3G_OK;
+  M3G_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int m3g_dyn_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes, int32_t* host_flags, int64_t* host_steps,
                             double* host_vel, void* stream_) {
-  if (n_atoms < 1 || n_structs < 1 || n_structs > n_atoms || !state) { set_error("m3g_dyn_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const int64_t N = n_atoms, S = n_structs;
+  if (!batch_sizes_ok(N, S) || !state) { set_error("m3g_dyn_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const DynLayout L = dyn_layout(N, S);
   if (state_bytes < L.total) { set_error("m3g_dyn_read: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;

@@ -14,12 +14,12 @@
 #include <cmath>
 #include <vector>
 
+#include "m3g_chunks.h"
 #include "m3g_internal.h"
 
 namespace m3g {
 namespace {
 constexpr int kMaxDeform = M3G_EL_MAX_DEFORM;
-constexpr int kWave = 64;
 constexpr int kJacobiSweeps = 30;
 
 struct ElLayout {
@@ -27,17 +27,16 @@ struct ElLayout {
 };
 ElLayout el_layout(const m3g_el_sizes& z) {
   ElLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
+  StateArena arena;
   const int64_t S = z.n_structs, U = z.n_atoms, M = z.n_deform;
-  L.row_off = take(8 * (S + 1));
-  L.unit_off = take(8 * (S + 1));
-  L.lat = take(8 * 9 * S);
-  L.unit_pos = take(8 * 3 * U);
-  L.dmat = take(8 * 9 * (M + 1));
-  L.comp = take(4 * M);
-  L.mag = take(8 * M);
-  L.total = o;
+  L.row_off = arena.take(8 * (S + 1));
+  L.unit_off = arena.take(8 * (S + 1));
+  L.lat = arena.take(8 * 9 * S);
+  L.unit_pos = arena.take(8 * 3 * U);
+  L.dmat = arena.take(8 * 9 * (M + 1));
+  L.comp = arena.take(4 * M);
+  L.mag = arena.take(8 * M);
+  L.total = arena.total;
   return L;
 }
 
@@ -355,16 +354,9 @@ extern "C" int m3g_el_init(const m3g_el_sizes* sizes, const int64_t* host_offset
   const m3g_el_sizes z = *sizes;
   const int64_t S = z.n_structs, U = z.n_atoms;
   const int M = z.n_deform;
-  if (host_offsets[0] != 0 || host_offsets[S] != U) { set_error("m3g_el_init: offsets must run from 0 to n_atoms"); return M3G_ERR_VALUE; }
+  if (!offsets_ok("m3g_el_init", host_offsets, U, S)) return M3G_ERR_VALUE;
   for (int64_t s = 0; s < S; ++s)
-    if (host_offsets[s + 1] <= host_offsets[s]) { set_error("m3g_el_init: offsets must increase strictly (every structure holds an atom)"); return M3G_ERR_VALUE; }
-  for (int64_t s = 0; s < S; ++s) {
-    const double* L = host_lattices + 9 * s;
-    for (int k = 0; k < 9; ++k)
-      if (!std::isfinite(L[k])) { set_error("m3g_el_init: lattice of structure %lld is not finite", (long long)s); return M3G_ERR_VALUE; }
-    const double det = L[0] * (L[4] * L[8] - L[5] * L[7]) - L[1] * (L[3] * L[8] - L[5] * L[6]) + L[2] * (L[3] * L[7] - L[4] * L[6]);
-    if (!(std::fabs(det) >= 1e-12)) { set_error("m3g_el_init: singular cell of structure %lld", (long long)s); return M3G_ERR_VALUE; }
-  }
+    if (!lattice_ok("m3g_el_init", host_lattices + 9 * s, s)) return M3G_ERR_VALUE;
   for (int64_t i = 0; i < 3 * U; ++i)
     if (!std::isfinite(host_positions[i])) { set_error("m3g_el_init: position of atom %lld is not finite", (long long)(i / 3)); return M3G_ERR_VALUE; }
   for (int m = 0; m < M; ++m) {
@@ -428,9 +420,8 @@ extern "C" int m3g_el_deform(const m3g_el_sizes* sizes, const void* state, size_
   if (const int rc = el_call_ok("m3g_el_deform", sizes, state, state_bytes, pos && lattices, -1)) return rc;
   const ElView st = el_view(*sizes, state);
   const int64_t threads = st.rows > 3 * st.copies ? st.rows : 3 * st.copies;
-  hipLaunchKernelGGL(k_el_deform, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, st, pos, lattices);
-  M3G_HIP_CHECK(hipGetLastError());
-  return M3G_OK;
+  hipLaunchKernelGGL(k_el_deform, blocks_for(threads, 256), dim3(256), 0, (hipStream_t)stream_, st, pos, lattices);
+  M3G_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int m3g_el_fit_elastic(const m3g_el_sizes* sizes, const void* state, size_t state_bytes, const float* stresses, double* rows,
@@ -438,15 +429,13 @@ extern "C" int m3g_el_fit_elastic(const m3g_el_sizes* sizes, const void* state, 
   if (const int rc = el_call_ok("m3g_el_fit_elastic", sizes, state, state_bytes, stresses && rows && nonfinite, M3G_EL_MODE_ELASTIC)) return rc;
   const ElView st = el_view(*sizes, state);
   hipLaunchKernelGGL(k_el_fit_elastic, dim3((unsigned)st.S), dim3(kWave), 0, (hipStream_t)stream_, st, stresses, rows, nonfinite);
-  M3G_HIP_CHECK(hipGetLastError());
-  return M3G_OK;
+  M3G_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int m3g_el_fit_eos(const m3g_el_sizes* sizes, const void* state, size_t state_bytes, const float* energies, double* rows,
                               int32_t* error, void* stream_) {
   if (const int rc = el_call_ok("m3g_el_fit_eos", sizes, state, state_bytes, energies && rows && error, M3G_EL_MODE_EOS)) return rc;
   const ElView st = el_view(*sizes, state);
-  hipLaunchKernelGGL(k_el_fit_eos, dim3((unsigned)((st.S + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream_, st, energies, rows, error);
-  M3G_HIP_CHECK(hipGetLastError());
-  return M3G_OK;
+  hipLaunchKernelGGL(k_el_fit_eos, blocks_for(st.S, kWave), dim3(kWave), 0, (hipStream_t)stream_, st, energies, rows, error);
+  M3G_RETURN_LAUNCH_STATUS();
 }

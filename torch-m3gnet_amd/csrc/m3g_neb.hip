@@ -21,8 +21,6 @@ namespace m3g {
 namespace {
 constexpr int kPart = 6;    // per chunk: |tau+|^2, |tau-|^2, tau+.tau-, F.tau+, F.tau-, non-finite inputs
 constexpr int kRows = 5;    // observables per image: |tau+|, |tau-|, F.tau_hat, spring term, climbing flag
-constexpr int kWave = 64;
-constexpr int kFinalizeWaves = 4;
 
 struct NebLayout {
   ChunkLayout chunks;
@@ -31,28 +29,24 @@ struct NebLayout {
 // the endpoint rows (2 n_b per band) never exceed 2N: every band holds an interior image of n_b atoms
 NebLayout neb_layout(int64_t N, int64_t I, int64_t B) {
   NebLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
-  L.chunks = chunk_layout(N, I, take);
-  L.partial = take(8 * kPart * chunk_bound(N, I));
-  L.img_prev = take(8 * I);
-  L.img_next = take(8 * I);
-  L.band_images = take(4 * (B + 1));
-  L.k = take(8 * B);
-  L.climb = take(4 * B);
-  L.ep_pos = take(8 * 3 * 2 * N);
-  L.ep_energy = take(8 * 2 * B);
-  L.coef = take(8 * 2 * I);
-  L.total = o;
+  StateArena arena;
+  L.chunks = chunk_layout(N, I, arena);
+  L.partial = arena.take(8 * kPart * chunk_bound(N, I));
+  L.img_prev = arena.take(8 * I);
+  L.img_next = arena.take(8 * I);
+  L.band_images = arena.take(4 * (B + 1));
+  L.k = arena.take(8 * B);
+  L.climb = arena.take(4 * B);
+  L.ep_pos = arena.take(8 * 3 * 2 * N);
+  L.ep_energy = arena.take(8 * 2 * B);
+  L.coef = arena.take(8 * 2 * I);
+  L.total = arena.total;
   return L;
 }
 
 struct NebView {
-  int64_t N, I, B;
-  const int64_t* offsets;   // image atom offsets [I+1]
-  const int32_t* chunk_struct;
-  const int64_t* chunk_begin;
-  const int32_t* first_chunk;
+  int64_t N, B;
+  ChunkView ch;   // the interior images are its structures (ch.S of them)
   double* partial;
   const int64_t *img_prev, *img_next;   // first row of the neighbour image: >= 0 in pos, -1 - r for row r of the endpoint rows
   const int32_t* band_images;           // [B+1]
@@ -64,10 +58,8 @@ struct NebView {
 NebView neb_view(int64_t N, int64_t I, int64_t B, void* state) {
   const NebLayout L = neb_layout(N, I, B);
   char* b = (char*)state;
-  return NebView{N, I, B, (const int64_t*)(b + L.chunks.offsets), (const int32_t*)(b + L.chunks.chunk_struct),
-                 (const int64_t*)(b + L.chunks.chunk_begin), (const int32_t*)(b + L.chunks.first_chunk), (double*)(b + L.partial),
-                 (const int64_t*)(b + L.img_prev), (const int64_t*)(b + L.img_next),
-                 (const int32_t*)(b + L.band_images), (const double*)(b + L.k), (const int32_t*)(b + L.climb),
+  return NebView{N, B, chunk_view(L.chunks, state), (double*)(b + L.partial), (const int64_t*)(b + L.img_prev),
+                 (const int64_t*)(b + L.img_next), (const int32_t*)(b + L.band_images), (const double*)(b + L.k), (const int32_t*)(b + L.climb),
                  (const double*)(b + L.ep_pos), (const double*)(b + L.ep_energy), (double*)(b + L.coef)};
 }
 
@@ -78,7 +70,7 @@ __device__ inline const double* neighbour_row(int64_t enc, int64_t local, const 
 // tau+ and tau- of row r (of image i) and whether all twelve inputs of the row are finite
 __device__ inline bool row_taus(const NebView& st, int i, int64_t r, const double* __restrict__ pos, const float* __restrict__ forces,
                                 double tp[3], double tm[3], double f[3]) {
-  const int64_t local = r - st.offsets[i];
+  const int64_t local = r - st.ch.offsets[i];
   const double* x = pos + 3 * r;
   const double* xp = neighbour_row(st.img_prev[i], local, pos, st.ep_pos);
   const double* xn = neighbour_row(st.img_next[i], local, pos, st.ep_pos);
@@ -95,11 +87,11 @@ __device__ inline bool row_taus(const NebView& st, int i, int64_t r, const doubl
 __global__ void __launch_bounds__(kChunkRows) k_neb_partials(NebView st, const double* __restrict__ pos, const float* __restrict__ forces) {
   __shared__ double sh[kPart][kChunkRows];
   const int c = blockIdx.x, t = threadIdx.x;
-  if (c >= st.first_chunk[st.I]) return;
-  const int i = st.chunk_struct[c];
-  const int64_t r = st.chunk_begin[c] + t;
+  if (c >= st.ch.n_chunks()) return;
+  const int i = st.ch.structure(c);
+  const int64_t r = st.ch.row(c, t);
   double val[kPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (r < st.offsets[i + 1]) {
+  if (st.ch.holds(i, r)) {
     double tp[3], tm[3], f[3];
     val[5] = row_taus(st, i, r, pos, forces, tp, tm, f) ? 0.0 : 1.0;
     val[0] = tp[0] * tp[0] + tp[1] * tp[1] + tp[2] * tp[2];
@@ -108,13 +100,7 @@ __global__ void __launch_bounds__(kChunkRows) k_neb_partials(NebView st, const d
     val[3] = f[0] * tp[0] + f[1] * tp[1] + f[2] * tp[2];
     val[4] = f[0] * tm[0] + f[1] * tm[1] + f[2] * tm[2];
   }
-  for (int j = 0; j < kPart; ++j) sh[j][t] = val[j];
-  __syncthreads();
-  for (int w = kChunkRows / 2; w > 0; w >>= 1) {   // fixed tree: the order depends on the row's place in its chunk only
-    if (t < w)
-      for (int j = 0; j < kPart; ++j) sh[j][t] += sh[j][t + w];
-    __syncthreads();
-  }
+  chunk_tree_reduce<kPart>(sh, val, t);
   if (t < kPart) st.partial[kPart * c + t] = sh[t][0];
 }
 
@@ -134,11 +120,8 @@ __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_neb_finalize(NebView
   }
   const double kb = st.k[b];
   for (int i = i0; i < i1; ++i) {
-    double acc[kPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int c = st.first_chunk[i] + lane; c < st.first_chunk[i + 1]; c += kWave)
-      for (int j = 0; j < kPart; ++j) acc[j] += st.partial[kPart * c + j];
-    for (int w = kWave / 2; w > 0; w >>= 1)   // butterfly: a + b on both partners, so every lane ends with the same bits
-      for (int j = 0; j < kPart; ++j) acc[j] += __shfl_xor(acc[j], w, kWave);
+    double acc[kPart];
+    wave_chunk_sum<kPart>(st.ch, i, st.partial, lane, acc);
     if (lane != 0) continue;
     const double vi = energies[i];
     const double vp = i == i0 ? st.ep_energy[2 * b] : (double)energies[i - 1];
@@ -180,10 +163,10 @@ __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_neb_finalize(NebView
 __global__ void __launch_bounds__(kChunkRows) k_neb_apply(NebView st, const double* __restrict__ pos, const float* __restrict__ forces,
                                                           float* __restrict__ neb_forces) {
   const int c = blockIdx.x;
-  if (c >= st.first_chunk[st.I]) return;
-  const int i = st.chunk_struct[c];
-  const int64_t r = st.chunk_begin[c] + threadIdx.x;
-  if (r >= st.offsets[i + 1]) return;
+  if (c >= st.ch.n_chunks()) return;
+  const int i = st.ch.structure(c);
+  const int64_t r = st.ch.row(c, threadIdx.x);
+  if (!st.ch.holds(i, r)) return;
   const double alpha = st.coef[2 * i], beta = st.coef[2 * i + 1];
   double tp[3], tm[3], f[3];
   row_taus(st, i, r, pos, forces, tp, tm, f);
@@ -211,7 +194,7 @@ extern "C" int m3g_neb_init(int64_t n_atoms, int64_t n_images, int64_t n_bands, 
     set_error("m3g_neb_init: null argument or bad sizes (need 1 <= n_bands <= n_images <= n_atoms)");
     return M3G_ERR_VALUE;
   }
-  if (!chunk_offsets_ok("m3g_neb_init", host_image_offsets, N, I)) return M3G_ERR_VALUE;
+  if (!offsets_ok("m3g_neb_init", host_image_offsets, N, I)) return M3G_ERR_VALUE;
   if (host_band_images[0] != 0 || host_band_images[B] != I) { set_error("m3g_neb_init: band image offsets must run from 0 to n_images"); return M3G_ERR_VALUE; }
   std::vector<int64_t> img_prev(I), img_next(I);
   int64_t ep_rows = 0;
@@ -225,7 +208,7 @@ extern "C" int m3g_neb_init(int64_t n_atoms, int64_t n_images, int64_t n_bands, 
         set_error("m3g_neb_init: the images of band %lld have different atom counts", (long long)b);
         return M3G_ERR_VALUE;
       }
-    if (!(std::isfinite(host_k[b]) && host_k[b] > 0.0)) { set_error("m3g_neb_init: spring constant k of band %lld must be finite and > 0", (long long)b); return M3G_ERR_VALUE; }
+    if (!finite_positive(host_k[b])) { set_error("m3g_neb_init: spring constant k of band %lld must be finite and > 0", (long long)b); return M3G_ERR_VALUE; }
     if (host_climb[b] != 0 && host_climb[b] != 1) { set_error("m3g_neb_init: climb of band %lld must be 0 or 1", (long long)b); return M3G_ERR_VALUE; }
     if (!(std::isfinite(host_endpoint_energies[2 * b]) && std::isfinite(host_endpoint_energies[2 * b + 1]))) {
       set_error("m3g_neb_init: endpoint energies of band %lld are not finite", (long long)b);
@@ -242,7 +225,7 @@ extern "C" int m3g_neb_init(int64_t n_atoms, int64_t n_images, int64_t n_bands, 
   const ChunkTable table(host_image_offsets, I);
   hipStream_t s = (hipStream_t)stream_;
   char* st = (char*)state;
-  if (int rc = table.upload(L.chunks, st, host_image_offsets, I, s)) return rc;
+  if (int rc = table.upload(L.chunks, st, host_image_offsets, s)) return rc;
   M3G_HIP_CHECK(hipMemcpyAsync(st + L.img_prev, img_prev.data(), 8 * I, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync(st + L.img_next, img_next.data(), 8 * I, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync(st + L.band_images, host_band_images, 4 * (B + 1), hipMemcpyHostToDevice, s));
@@ -266,9 +249,7 @@ extern "C" int m3g_neb_forces(int64_t n_atoms, int64_t n_images, int64_t n_bands
   const NebView st = neb_view(N, I, B, state);
   const dim3 grid((unsigned)chunk_bound(N, I));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_neb_partials, grid, dim3(kChunkRows), 0, s, st, pos, forces);
-  hipLaunchKernelGGL(k_neb_finalize, dim3((unsigned)((B + kFinalizeWaves - 1) / kFinalizeWaves)), dim3(kWave * kFinalizeWaves), 0, s, st,
-                     energies, rows);
+  hipLaunchKernelGGL(k_neb_finalize, blocks_for(B, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, energies, rows);
   hipLaunchKernelGGL(k_neb_apply, grid, dim3(kChunkRows), 0, s, st, pos, forces, neb_forces);
-  M3G_HIP_CHECK(hipGetLastError());
-  return M3G_OK;
+  M3G_RETURN_LAUNCH_STATUS();
 }

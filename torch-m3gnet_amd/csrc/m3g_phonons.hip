@@ -20,12 +20,13 @@
 #include <cmath>
 #include <vector>
 
+#include "m3g_chunks.h"
 #include "m3g_internal.h"
 
 namespace m3g {
 namespace {
 constexpr int kMaxMult = M3G_PH_MAX_MULTIPLICITY;   // shortest images per (u, j) pair kept in the table
-constexpr int kFcThreads = 256;
+constexpr int kFcThreads = kChunkRows;   // the workgroup of chunk_tree_reduce (m3g_chunks.h)
 constexpr int kDynThreads = 64;
 
 struct PhLayout {
@@ -33,21 +34,20 @@ struct PhLayout {
 };
 PhLayout ph_layout(const m3g_ph_sizes& z) {
   PhLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
+  StateArena arena;
   const int64_t S = z.n_structs, U = z.n_unit_atoms, P = z.n_pairs;
-  L.row_off = take(8 * (S + 1));
-  L.unit_off = take(8 * (S + 1));
-  L.pair_off = take(8 * (S + 1));
-  L.dims = take(4 * 3 * S);
-  L.lat = take(8 * 9 * S);
-  L.unit_pos = take(8 * 3 * U);
-  L.mass = take(8 * U);
-  L.unit_struct = take(4 * U);
-  L.delta = take(8);
-  L.img_count = take(4 * P);
-  L.img_d = take(8 * 3 * kMaxMult * P);
-  L.total = o;
+  L.row_off = arena.take(8 * (S + 1));
+  L.unit_off = arena.take(8 * (S + 1));
+  L.pair_off = arena.take(8 * (S + 1));
+  L.dims = arena.take(4 * 3 * S);
+  L.lat = arena.take(8 * 9 * S);
+  L.unit_pos = arena.take(8 * 3 * U);
+  L.mass = arena.take(8 * U);
+  L.unit_struct = arena.take(4 * U);
+  L.delta = arena.take(8);
+  L.img_count = arena.take(4 * P);
+  L.img_d = arena.take(8 * 3 * kMaxMult * P);
+  L.total = arena.total;
   return L;
 }
 
@@ -120,13 +120,12 @@ __global__ void __launch_bounds__(kFcThreads) k_ph_force_constants(PhView st, co
   const int64_t ns = nu * st.dims[3 * s] * st.dims[3 * s + 1] * st.dims[3 * s + 2];
   const int64_t r0 = st.row_off[s];
   const double two_delta = 2.0 * st.delta[0];
+  double acc[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // the nine row sums, then the non-finite count
   // non-finite forces anywhere in the structure's 1 + 6 n_u copies (the same count in every workgroup of the structure)
-  double bad = 0.0;
   const int64_t nvals = 3 * (st.row_off[s + 1] - r0);
-  for (int64_t i = t; i < nvals; i += kFcThreads) bad += std::isfinite(forces[3 * r0 + i]) ? 0.0 : 1.0;
+  for (int64_t i = t; i < nvals; i += kFcThreads) acc[9] += std::isfinite(forces[3 * r0 + i]) ? 0.0 : 1.0;
   const int64_t plus0 = r0 + (1 + 6 * u) * ns;   // first row of copy (u, a = 0, +)
   double* out = phi + 9 * (st.pair_off[s] + u * ns);
-  double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int64_t j = t; j < ns; j += kFcThreads) {
     for (int a = 0; a < 3; ++a) {
       const float* fp = forces + 3 * (plus0 + 2 * a * ns + j);
@@ -138,14 +137,7 @@ __global__ void __launch_bounds__(kFcThreads) k_ph_force_constants(PhView st, co
       }
     }
   }
-  for (int k = 0; k < 9; ++k) sh[k][t] = acc[k];
-  sh[9][t] = bad;
-  __syncthreads();
-  for (int w = kFcThreads / 2; w > 0; w >>= 1) {   // fixed tree: the order depends on the thread index only
-    if (t < w)
-      for (int k = 0; k < 10; ++k) sh[k][t] += sh[k][t + w];
-    __syncthreads();
-  }
+  chunk_tree_reduce<10>(sh, acc, t);   // (the order depends on the thread index only)
   const bool failed = sh[9][0] != 0.0;
   if (t < 9) {
     const int a = t / 3, c = t % 3;
@@ -243,10 +235,7 @@ bool ph_sizes_ok(const m3g_ph_sizes* z) {
 bool shortest_images(const double L[9], const int n[3], const double* ru, const double* rv, const int l[3], std::vector<double>& d) {
   // fractional difference in unit-cell coordinates: frac(r_v) - frac(r_u) + l
   double inv[9];
-  const double det = L[0] * (L[4] * L[8] - L[5] * L[7]) - L[1] * (L[3] * L[8] - L[5] * L[6]) + L[2] * (L[3] * L[7] - L[4] * L[6]);
-  inv[0] = (L[4] * L[8] - L[5] * L[7]) / det; inv[1] = (L[2] * L[7] - L[1] * L[8]) / det; inv[2] = (L[1] * L[5] - L[2] * L[4]) / det;
-  inv[3] = (L[5] * L[6] - L[3] * L[8]) / det; inv[4] = (L[0] * L[8] - L[2] * L[6]) / det; inv[5] = (L[2] * L[3] - L[0] * L[5]) / det;
-  inv[6] = (L[3] * L[7] - L[4] * L[6]) / det; inv[7] = (L[1] * L[6] - L[0] * L[7]) / det; inv[8] = (L[0] * L[4] - L[1] * L[3]) / det;
+  inv3(L, inv);
   double f0[3];   // (r_v - r_u) inv(L): row vector times the inverse of the row-vector lattice
   for (int c = 0; c < 3; ++c) f0[c] = (rv[0] - ru[0]) * inv[c] + (rv[1] - ru[1]) * inv[3 + c] + (rv[2] - ru[2]) * inv[6 + c] + l[c];
   double best = INFINITY;
@@ -291,10 +280,8 @@ extern "C" int m3g_ph_init(const m3g_ph_sizes* sizes, const int64_t* host_unit_o
   }
   const m3g_ph_sizes z = *sizes;
   const int64_t S = z.n_structs, U = z.n_unit_atoms;
-  if (host_unit_offsets[0] != 0 || host_unit_offsets[S] != U) { set_error("m3g_ph_init: unit offsets must run from 0 to n_unit_atoms"); return M3G_ERR_VALUE; }
-  for (int64_t s = 0; s < S; ++s)
-    if (host_unit_offsets[s + 1] <= host_unit_offsets[s]) { set_error("m3g_ph_init: unit offsets must increase strictly (every structure holds an atom)"); return M3G_ERR_VALUE; }
-  if (!(std::isfinite(delta) && delta > 0.0)) { set_error("m3g_ph_init: delta must be finite and > 0"); return M3G_ERR_VALUE; }
+  if (!offsets_ok("m3g_ph_init", host_unit_offsets, U, S, "unit offsets", "n_unit_atoms")) return M3G_ERR_VALUE;
+  if (!finite_positive(delta)) { set_error("m3g_ph_init: delta must be finite and > 0"); return M3G_ERR_VALUE; }
   std::vector<int64_t> row_off(S + 1, 0), pair_off(S + 1, 0);
   std::vector<int32_t> unit_struct(U);
   int64_t n_super = 0;
@@ -304,16 +291,12 @@ extern "C" int m3g_ph_init(const m3g_ph_sizes* sizes, const int64_t* host_unit_o
       set_error("m3g_ph_init: supercell of structure %lld must have dims >= 1 (and at most 2^20 cells)", (long long)s);
       return M3G_ERR_VALUE;
     }
-    const double* L = host_lattices + 9 * s;
-    for (int k = 0; k < 9; ++k)
-      if (!std::isfinite(L[k])) { set_error("m3g_ph_init: lattice of structure %lld is not finite", (long long)s); return M3G_ERR_VALUE; }
-    const double det = L[0] * (L[4] * L[8] - L[5] * L[7]) - L[1] * (L[3] * L[8] - L[5] * L[6]) + L[2] * (L[3] * L[7] - L[4] * L[6]);
-    if (!(std::fabs(det) >= 1e-12)) { set_error("m3g_ph_init: singular cell of structure %lld", (long long)s); return M3G_ERR_VALUE; }
+    if (!lattice_ok("m3g_ph_init", host_lattices + 9 * s, s)) return M3G_ERR_VALUE;
     const int64_t nu = host_unit_offsets[s + 1] - host_unit_offsets[s];
     const int64_t ns = nu * n[0] * n[1] * n[2];
     for (int64_t g = host_unit_offsets[s]; g < host_unit_offsets[s + 1]; ++g) {
       unit_struct[g] = (int32_t)s;
-      if (!(std::isfinite(host_masses[g]) && host_masses[g] > 0.0)) { set_error("m3g_ph_init: mass of unit atom %lld must be finite and > 0", (long long)g); return M3G_ERR_VALUE; }
+      if (!finite_positive(host_masses[g])) { set_error("m3g_ph_init: mass of unit atom %lld must be finite and > 0", (long long)g); return M3G_ERR_VALUE; }
       for (int c = 0; c < 3; ++c)
         if (!std::isfinite(host_positions[3 * g + c])) { set_error("m3g_ph_init: position of unit atom %lld is not finite", (long long)g); return M3G_ERR_VALUE; }
     }
@@ -371,9 +354,8 @@ extern "C" int m3g_ph_displace(const m3g_ph_sizes* sizes, const void* state, siz
   if (!ph_sizes_ok(sizes) || !state || !pos) { set_error("m3g_ph_displace: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (state_bytes < ph_layout(*sizes).total) { set_error("m3g_ph_displace: state buffer too small"); return M3G_ERR_SIZE; }
   const PhView st = ph_view(*sizes, state);
-  hipLaunchKernelGGL(k_ph_displace, dim3((unsigned)((st.rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, st, pos);
-  M3G_HIP_CHECK(hipGetLastError());
-  return M3G_OK;
+  hipLaunchKernelGGL(k_ph_displace, blocks_for(st.rows, 256), dim3(256), 0, (hipStream_t)stream_, st, pos);
+  M3G_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int m3g_ph_force_constants(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const float* forces, int32_t asr,
@@ -386,8 +368,7 @@ extern "C" int m3g_ph_force_constants(const m3g_ph_sizes* sizes, const void* sta
   const PhView st = ph_view(*sizes, state);
   hipLaunchKernelGGL(k_ph_force_constants, dim3((unsigned)st.U), dim3(kFcThreads), 0, (hipStream_t)stream_, st, forces, (int)asr, phi, sums,
                      nonfinite);
-  M3G_HIP_CHECK(hipGetLastError());
-  return M3G_OK;
+  M3G_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int m3g_ph_dynmat(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const double* phi, int64_t n_q, const double* q,
@@ -405,6 +386,5 @@ extern "C" int m3g_ph_dynmat(const m3g_ph_sizes* sizes, const void* state, size_
   const PhView st = ph_view(*sizes, state);
   hipLaunchKernelGGL(k_ph_dynmat, dim3((unsigned)(n_q * per_q)), dim3(kDynThreads), 0, (hipStream_t)stream_, st, n_q, per_q, q, q_struct,
                      max_unit_atoms, phi, dynmat);
-  M3G_HIP_CHECK(hipGetLastError());
-  return M3G_OK;
+  M3G_RETURN_LAUNCH_STATUS();
 }

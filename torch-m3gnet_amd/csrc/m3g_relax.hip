@@ -1,7 +1,7 @@
 // Batched FIRE structure relaxation, fixed or variable cell (linear deformation gradient, as ASE's UnitCellFilter).  The reference's
 // relaxation script (scripts/relax_org.py) hands one structure at a time to m3gnet's Relaxer: ASE's FIRE on the host, one optimiser per
 // structure, several small array operations and host reductions per step.  Here one iteration of the whole batch is three launches:
-//   k_fire_partials   one workgroup per chunk (<= kFireRows atoms of ONE structure): generalized forces g of its rows and the partial
+//   k_fire_partials   one workgroup per chunk (<= kChunkRows atoms of ONE structure): generalized forces g of its rows and the partial
 //                     sums g.v, g.g, v.v, max_i |g_i|^2, in a fixed tree order;
 //   k_fire_finalize   one workgroup: per structure, the chunk partials in chunk order (+ the three cell rows), convergence / error
 //                     verdict, the FIRE scalars (dt, a, n), the mixing coefficients of v' = c_v v + c_g g and the step scale -- |v'|^2
@@ -17,7 +17,6 @@
 
 namespace m3g {
 namespace {
-constexpr int kFireRows = kChunkRows;   // atoms per chunk == threads per workgroup of the row kernels (m3g_chunks.h)
 constexpr int kCoef = 24;        // per structure: move, c_v, c_g, step scale, F before [9], F after [9], (pad)
 
 struct FireLayout {
@@ -26,44 +25,37 @@ struct FireLayout {
 };
 FireLayout fire_layout(int64_t N, int64_t S) {
   FireLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~size_t(255); return at; };
+  StateArena arena;
   const int64_t C = chunk_bound(N, S), R = N + 3 * S;
-  L.chunks = chunk_layout(N, S, take);
-  L.partial = take(8 * 4 * C);
-  L.x = take(8 * 3 * R);                // rows: the N atoms, then 3 cell rows per structure
-  L.v = take(8 * 3 * R);
-  L.l0 = take(8 * 9 * S);
-  L.f = take(8 * 9 * S);
-  L.dt = take(8 * S);
-  L.a = take(8 * S);
-  L.n = take(4 * S);
-  L.flags = take(4 * S);
-  L.steps = take(4 * S);
-  L.coef = take(8 * kCoef * S);
-  L.total = o;
+  L.chunks = chunk_layout(N, S, arena);
+  L.partial = arena.take(8 * 4 * C);
+  L.x = arena.take(8 * 3 * R);                // rows: the N atoms, then 3 cell rows per structure
+  L.v = arena.take(8 * 3 * R);
+  L.l0 = arena.take(8 * 9 * S);
+  L.f = arena.take(8 * 9 * S);
+  L.dt = arena.take(8 * S);
+  L.a = arena.take(8 * S);
+  L.n = arena.take(4 * S);
+  L.flags = arena.take(4 * S);
+  L.steps = arena.take(4 * S);
+  L.coef = arena.take(8 * kCoef * S);
+  L.total = arena.total;
   return L;
 }
 
 struct FireView {
-  int64_t N, S;
-  const int64_t* offsets;
-  const int32_t* chunk_struct;
-  const int64_t* chunk_begin;
-  const int32_t* first_chunk;
+  int64_t N;
+  ChunkView ch;
   double *partial, *x, *v, *l0, *f, *dt, *a, *coef;
   int32_t *n, *flags, *steps;
 };
 FireView fire_view(int64_t N, int64_t S, void* state) {
   const FireLayout L = fire_layout(N, S);
   char* b = (char*)state;
-  return FireView{N, S, (const int64_t*)(b + L.chunks.offsets), (const int32_t*)(b + L.chunks.chunk_struct),
-                  (const int64_t*)(b + L.chunks.chunk_begin), (const int32_t*)(b + L.chunks.first_chunk), (double*)(b + L.partial),
-                  (double*)(b + L.x), (double*)(b + L.v), (double*)(b + L.l0), (double*)(b + L.f), (double*)(b + L.dt), (double*)(b + L.a), (double*)(b + L.coef),
-                  (int32_t*)(b + L.n), (int32_t*)(b + L.flags), (int32_t*)(b + L.steps)};
+  return FireView{N, chunk_view(L.chunks, state), (double*)(b + L.partial), (double*)(b + L.x), (double*)(b + L.v), (double*)(b + L.l0),
+                  (double*)(b + L.f), (double*)(b + L.dt), (double*)(b + L.a), (double*)(b + L.coef), (int32_t*)(b + L.n), (int32_t*)(b + L.flags),
+                  (int32_t*)(b + L.steps)};
 }
-
-__device__ inline double max_nan(double m, double x) { return (x > m || x != x) ? x : m; }   // a NaN row stays visible
 
 // g = f F (row vector times the deformation gradient), or f itself with the cell fixed
 __device__ inline void gen_force(const float* __restrict__ forces, int64_t i, const double* F, bool cell, double g[3]) {
@@ -75,12 +67,12 @@ __device__ inline void gen_force(const float* __restrict__ forces, int64_t i, co
   }
 }
 
-__global__ void __launch_bounds__(kFireRows) k_fire_init(FireView st, const double* __restrict__ pos, const double* __restrict__ lattice,
+__global__ void __launch_bounds__(kChunkRows) k_fire_init(FireView st, const double* __restrict__ pos, const double* __restrict__ lattice,
                                                          double dt0, double astart) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < 3 * st.N) { st.x[i] = pos[i]; st.v[i] = 0.0; }
-  if (i < st.S) {
-    const double cf = (double)(st.offsets[i + 1] - st.offsets[i]);
+  if (i < st.ch.S) {
+    const double cf = (double)(st.ch.offsets[i + 1] - st.ch.offsets[i]);
     for (int k = 0; k < 9; ++k) {
       const double id = (k % 4 == 0) ? 1.0 : 0.0;
       st.l0[9 * i + k] = lattice ? lattice[9 * i + k] : 0.0;
@@ -97,55 +89,45 @@ __global__ void __launch_bounds__(kFireRows) k_fire_init(FireView st, const doub
   }
 }
 
-__global__ void __launch_bounds__(kFireRows) k_fire_partials(FireView st, int32_t relax_cell, const float* __restrict__ forces) {
-  __shared__ double sh[4][kFireRows];
+__global__ void __launch_bounds__(kChunkRows) k_fire_partials(FireView st, int32_t relax_cell, const float* __restrict__ forces) {
+  __shared__ double sh[4][kChunkRows];
   const int c = blockIdx.x, t = threadIdx.x;
-  if (c >= st.first_chunk[st.S]) return;
-  const int s = st.chunk_struct[c];
+  if (c >= st.ch.n_chunks()) return;
+  const int s = st.ch.structure(c);
   if (st.flags[s] & (M3G_FIRE_CONVERGED | M3G_FIRE_ERROR)) return;   // frozen: finalize reads nothing of it
-  const int64_t i = st.chunk_begin[c] + t, end = st.offsets[s + 1];
-  double gv = 0.0, gg = 0.0, vv = 0.0, g2 = 0.0;
-  if (i < end) {
+  const int64_t i = st.ch.row(c, t);
+  double val[4] = {0.0, 0.0, 0.0, 0.0};   // g.v, g.g, v.v, max |g_i|^2
+  if (st.ch.holds(s, i)) {
     double g[3];
     gen_force(forces, i, st.f + 9 * s, relax_cell != 0, g);
     const double* v = st.v + 3 * i;
-    gv = g[0] * v[0] + g[1] * v[1] + g[2] * v[2];
-    gg = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
-    vv = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-    g2 = gg;
+    val[0] = g[0] * v[0] + g[1] * v[1] + g[2] * v[2];
+    val[1] = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
+    val[2] = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+    val[3] = val[1];
   }
-  sh[0][t] = gv; sh[1][t] = gg; sh[2][t] = vv; sh[3][t] = g2;
-  __syncthreads();
-  for (int w = kFireRows / 2; w > 0; w >>= 1) {   // fixed tree: the order depends on the row's place in its chunk only
-    if (t < w) {
-      sh[0][t] += sh[0][t + w];
-      sh[1][t] += sh[1][t + w];
-      sh[2][t] += sh[2][t + w];
-      sh[3][t] = max_nan(sh[3][t], sh[3][t + w]);
-    }
-    __syncthreads();
-  }
+  chunk_tree_reduce<4, 1>(sh, val, t);   // three sums and a maximum
   if (t < 4) st.partial[4 * c + t] = sh[t][0];
 }
 
-__global__ void __launch_bounds__(kFireRows) k_fire_finalize(FireView st, m3g_fire_params p, int32_t check_only, const float* __restrict__ stresses,
+__global__ void __launch_bounds__(kChunkRows) k_fire_finalize(FireView st, m3g_fire_params p, int32_t check_only, const float* __restrict__ stresses,
                                                              double* __restrict__ lattice, float* __restrict__ lattice32, int32_t* host_unconverged) {
-  __shared__ int cnt_sh[kFireRows];
+  __shared__ int cnt_sh[1][kChunkRows];
   const int t = threadIdx.x;
   int cnt = 0;
-  for (int64_t s = t; s < st.S; s += kFireRows) {
+  for (int64_t s = t; s < st.ch.S; s += kChunkRows) {
     double* coef = st.coef + kCoef * s;
     int fl = st.flags[s];
     coef[0] = 0.0;
     if (fl & (M3G_FIRE_CONVERGED | M3G_FIRE_ERROR)) continue;
     double gv = 0.0, gg = 0.0, vv = 0.0, g2 = 0.0;
-    for (int c = st.first_chunk[s]; c < st.first_chunk[s + 1]; ++c) {
+    for (int c = st.ch.chunks_begin(s); c < st.ch.chunks_end(s); ++c) {   // serial, in chunk order
       gv += st.partial[4 * c];
       gg += st.partial[4 * c + 1];
       vv += st.partial[4 * c + 2];
       g2 = max_nan(g2, st.partial[4 * c + 3]);
     }
-    const double cf = (double)(st.offsets[s + 1] - st.offsets[s]);   // ASE's cell_factor: the structure's atom count
+    const double cf = (double)(st.ch.offsets[s + 1] - st.ch.offsets[s]);   // ASE's cell_factor: the structure's atom count
     double Fo[9], gc[9], vc[9], xc[9];
     const bool cell = p.relax_cell != 0;
     if (cell) {
@@ -242,23 +224,19 @@ __global__ void __launch_bounds__(kFireRows) k_fire_finalize(FireView st, m3g_fi
         }
     }
   }
-  cnt_sh[t] = cnt;
-  __syncthreads();
-  for (int w = kFireRows / 2; w > 0; w >>= 1) {
-    if (t < w) cnt_sh[t] += cnt_sh[t + w];
-    __syncthreads();
-  }
-  if (t == 0 && host_unconverged) *host_unconverged = cnt_sh[0];
+  const int val[1] = {cnt};
+  chunk_tree_reduce<1>(cnt_sh, val, t);
+  if (t == 0 && host_unconverged) *host_unconverged = cnt_sh[0][0];
 }
 
-__global__ void __launch_bounds__(kFireRows) k_fire_apply(FireView st, int32_t relax_cell, const float* __restrict__ forces, double* __restrict__ pos) {
+__global__ void __launch_bounds__(kChunkRows) k_fire_apply(FireView st, int32_t relax_cell, const float* __restrict__ forces, double* __restrict__ pos) {
   const int c = blockIdx.x;
-  if (c >= st.first_chunk[st.S]) return;
-  const int s = st.chunk_struct[c];
+  if (c >= st.ch.n_chunks()) return;
+  const int s = st.ch.structure(c);
   const double* coef = st.coef + kCoef * s;
   if (coef[0] == 0.0) return;   // converged, failed or checked only: bitwise untouched
-  const int64_t i = st.chunk_begin[c] + threadIdx.x;
-  if (i >= st.offsets[s + 1]) return;
+  const int64_t i = st.ch.row(c, threadIdx.x);
+  if (!st.ch.holds(s, i)) return;
   const double cv = coef[1], cg = coef[2], sdt = coef[3];
   double g[3], xn[3];
   gen_force(forces, i, coef + 4, relax_cell != 0, g);
@@ -277,10 +255,9 @@ __global__ void __launch_bounds__(kFireRows) k_fire_apply(FireView st, int32_t r
 }
 
 bool fire_params_ok(const m3g_fire_params* p) {
-  auto pos_finite = [](double x) { return std::isfinite(x) && x > 0.0; };
-  return p && pos_finite(p->dt) && pos_finite(p->maxstep) && pos_finite(p->dtmax) && pos_finite(p->finc) && pos_finite(p->fdec) &&
-         pos_finite(p->fmax) && std::isfinite(p->astart) && p->astart >= 0.0 && p->astart <= 1.0 && std::isfinite(p->fa) && p->fa >= 0.0 &&
-         p->fa <= 1.0 && p->nmin >= 0 && (p->relax_cell == 0 || p->relax_cell == 1);
+  return p && finite_positive(p->dt) && finite_positive(p->maxstep) && finite_positive(p->dtmax) && finite_positive(p->finc) &&
+         finite_positive(p->fdec) && finite_positive(p->fmax) && std::isfinite(p->astart) && p->astart >= 0.0 && p->astart <= 1.0 &&
+         std::isfinite(p->fa) && p->fa >= 0.0 && p->fa <= 1.0 && p->nmin >= 0 && (p->relax_cell == 0 || p->relax_cell == 1);
 }
 }  // namespace
 }  // namespace m3g
@@ -288,7 +265,7 @@ bool fire_params_ok(const m3g_fire_params* p) {
 using namespace m3g;
 
 extern "C" int m3g_fire_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* bytes) {
-  if (!bytes || n_atoms < 1 || n_structs < 1 || n_structs > n_atoms) { set_error("m3g_fire_state_bytes: bad sizes"); return M3G_ERR_VALUE; }
+  if (!bytes || !batch_sizes_ok(n_atoms, n_structs)) { set_error("m3g_fire_state_bytes: bad sizes"); return M3G_ERR_VALUE; }
   *bytes = fire_layout(n_atoms, n_structs).total;
   return M3G_OK;
 }
@@ -296,20 +273,19 @@ extern "C" int m3g_fire_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* 
 extern "C" int m3g_fire_init(const m3g_fire_params* p, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* pos,
                              const double* lattice, void* state, size_t state_bytes, void* stream_) {
   if (!fire_params_ok(p)) { set_error("m3g_fire_init: invalid FIRE parameters (fmax, dt, maxstep, dtmax, finc, fdec > 0; astart, fa in [0, 1])"); return M3G_ERR_VALUE; }
-  if (n_atoms < 1 || n_structs < 1 || n_structs > n_atoms || !host_offsets || !pos || !state || (p->relax_cell && !lattice)) {
+  if (!batch_sizes_ok(n_atoms, n_structs) || !host_offsets || !pos || !state || (p->relax_cell && !lattice)) {
     set_error("m3g_fire_init: null argument or bad sizes");
     return M3G_ERR_VALUE;
   }
   const int64_t N = n_atoms, S = n_structs;
-  if (!chunk_offsets_ok("m3g_fire_init", host_offsets, N, S)) return M3G_ERR_VALUE;
+  if (!offsets_ok("m3g_fire_init", host_offsets, N, S)) return M3G_ERR_VALUE;
   const FireLayout L = fire_layout(N, S);
   if (state_bytes < L.total) { set_error("m3g_fire_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(L.chunks, (char*)state, host_offsets, S, s)) return rc;
+  if (int rc = table.upload(L.chunks, (char*)state, host_offsets, s)) return rc;
   const int64_t work = 3 * N > S ? 3 * N : S;
-  hipLaunchKernelGGL(k_fire_init, dim3((unsigned)((work + kFireRows - 1) / kFireRows)), dim3(kFireRows), 0, s, fire_view(N, S, state), pos,
-                     lattice, p->dt, p->astart);
+  hipLaunchKernelGGL(k_fire_init, blocks_for(work, kChunkRows), dim3(kChunkRows), 0, s, fire_view(N, S, state), pos, lattice, p->dt, p->astart);
   M3G_HIP_CHECK(hipGetLastError());
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;
@@ -319,24 +295,23 @@ extern "C" int m3g_fire_step(const m3g_fire_params* p, int64_t n_atoms, int64_t 
                              const float* stresses, double* pos, double* lattice, float* lattice32, int32_t check_only, int32_t* unconverged,
                              void* stream_) {
   if (!fire_params_ok(p)) { set_error("m3g_fire_step: invalid FIRE parameters (fmax, dt, maxstep, dtmax, finc, fdec > 0; astart, fa in [0, 1])"); return M3G_ERR_VALUE; }
-  if (n_atoms < 1 || n_structs < 1 || n_structs > n_atoms || !state || !forces || !pos) { set_error("m3g_fire_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  if (p->relax_cell && (!stresses || !lattice)) { set_error("m3g_fire_step: a cell relaxation needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
   const int64_t N = n_atoms, S = n_structs;
+  if (!batch_sizes_ok(N, S) || !state || !forces || !pos) { set_error("m3g_fire_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
+  if (p->relax_cell && (!stresses || !lattice)) { set_error("m3g_fire_step: a cell relaxation needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
   if (state_bytes < fire_layout(N, S).total) { set_error("m3g_fire_step: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
   const FireView st = fire_view(N, S, state);
   const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
-  hipLaunchKernelGGL(k_fire_partials, grid, dim3(kFireRows), 0, s, st, p->relax_cell, forces);
-  hipLaunchKernelGGL(k_fire_finalize, dim3(1), dim3(kFireRows), 0, s, st, *p, check_only, stresses, lattice, lattice32, unconverged);
-  if (!check_only) hipLaunchKernelGGL(k_fire_apply, grid, dim3(kFireRows), 0, s, st, p->relax_cell, forces, pos);
-  M3G_HIP_CHECK(hipGetLastError());
-  return M3G_OK;
+  hipLaunchKernelGGL(k_fire_partials, grid, dim3(kChunkRows), 0, s, st, p->relax_cell, forces);
+  hipLaunchKernelGGL(k_fire_finalize, dim3(1), dim3(kChunkRows), 0, s, st, *p, check_only, stresses, lattice, lattice32, unconverged);
+  if (!check_only) hipLaunchKernelGGL(k_fire_apply, grid, dim3(kChunkRows), 0, s, st, p->relax_cell, forces, pos);
+  M3G_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int m3g_fire_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes, int32_t* host_flags, int32_t* host_steps,
                              double* host_dt, double* host_a, int32_t* host_n, double* host_x, double* host_v, void* stream_) {
-  if (n_atoms < 1 || n_structs < 1 || n_structs > n_atoms || !state) { set_error("m3g_fire_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const int64_t N = n_atoms, S = n_structs;
+  if (!batch_sizes_ok(N, S) || !state) { set_error("m3g_fire_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const FireLayout L = fire_layout(N, S);
   if (state_bytes < L.total) { set_error("m3g_fire_read: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
