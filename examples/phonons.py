@@ -7,7 +7,7 @@ The model is the default M3GNet architecture with the LJ-fitted fixture weights 
 reference's own code to Lennard-Jones Cu).  The 32-atom cubic cell is relaxed with its cell first (Relaxer); the 4-atom conventional
 cell at the relaxed lattice constant then goes through Phonons with an n x n x n supercell (default 3).  Prints the residual force,
 the acoustic sum rule violation, the frequencies at the special points of Gamma-X-W-K-Gamma-L (conventional-cell coordinates: the
-primitive bands folded), a coarse DOS and F(T)."""
+primitive bands folded), the sound velocities along [100] (group velocities at a small q), a coarse DOS and F(T)."""
 import sys
 import time
 from pathlib import Path
@@ -43,6 +43,8 @@ f = bands["frequencies"]
 for k, i in zip("GXWKGL", range(0, len(f) + 1, 41)):
     i = min(i, len(f) - 1)
     print(f"  {k}  " + " ".join(f"{x:6.3f}" for x in f[i]) + "  THz")
+v = res.group_velocities(np.array([[0.01, 0.0, 0.0]]) @ res.lattice.T)[0, :3, 0]   # q = 0.01 1/A along x (Cartesian, no 2 pi)
+print(f"sound velocities along [100]: TA {100 * v[0]:.0f}, {100 * v[1]:.0f} m/s  LA {100 * v[2]:.0f} m/s")
 print(f"band range {f.min():.3f} .. {f.max():.3f} THz  (imaginary modes: {(f < -0.05).sum()})")
 g, fp = dos["dos"], dos["frequency_points"]
 print("DOS (states/THz per cell):")

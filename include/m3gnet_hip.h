@@ -615,6 +615,53 @@ int m3g_ph_force_constants(const m3g_ph_sizes* sizes, const void* state, size_t 
 int m3g_ph_dynmat(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const double* phi, int64_t n_q, const double* q,
                   const int32_t* q_struct, int32_t max_unit_atoms, double* dynmat, void* stream);
 
+/* ---- batched Hermitian eigensolver for small matrices (csrc/m3g_eigh.h, csrc/m3g_eigh.hip) ------------------------------------------
+ * Replaces numpy.linalg.eigh (UPLO = 'U') over a batch of small complex Hermitian matrices.  Cyclic Jacobi with complex rotations in
+ * fp64, matrix and eigenvectors in LDS, one workgroup per matrix.  The rotation order is the round-robin (circle) pairing, which
+ * depends on n only; a rotation is skipped when |a_pq| <= DBL_EPSILON ||H||_F / n (the norm taken once, over the entries read); the
+ * solver stops after a sweep without a rotation, at most M3G_EIGH_MAX_SWEEPS sweeps.  No atomics: a matrix's outputs have the same
+ * bits alone, at any position of a batch and for any batch size.
+ *   a [M, n, n] complex128 (interleaved re, im; row-major) DEVICE: only the upper triangle and the real part of the diagonal are read;
+ *   eigenvalues [M, n] fp64 ascending (ties in index order); eigenvectors [M, n, n] complex128, column k belonging to eigenvalue k,
+ *   orthonormal (NULL allowed with want_vectors = 0: the eigenvalues have the same bits either way); info [M] int32: the sweeps run
+ *   (the last of them found nothing to rotate) in the bits M3G_EIGH_SWEEPS_MASK, M3G_EIGH_NONFINITE (an entry read, or the norm, is
+ *   not finite) and M3G_EIGH_NOT_CONVERGED (the last allowed sweep still rotated) above them.  A flagged matrix gets NaN eigenvalues
+ *   and eigenvectors; the others are unaffected.
+ * n < 1, n > M3G_EIGH_MAX_N, n_matrices < 0 or a null pointer -> M3G_ERR_VALUE; n_matrices == 0 does nothing.  One launch, no
+ * allocation, copy or wait: capture-safe. */
+#define M3G_EIGH_MAX_N 64
+#define M3G_EIGH_MAX_SWEEPS 30
+#define M3G_EIGH_SWEEPS_MASK 0xff
+#define M3G_EIGH_NONFINITE 0x100
+#define M3G_EIGH_NOT_CONVERGED 0x200
+int m3g_eigh_batched(int64_t n_matrices, int32_t n, const double* a, int32_t want_vectors, double* eigenvalues, double* eigenvectors,
+                     int32_t* info, void* stream);
+
+/* ---- phonon group velocities (csrc/m3g_phonons.hip) ------------------------------------------------------------------------------
+ * Replaces phonopy's DerivativeOfDynamicalMatrix (the analytic derivative) and GroupVelocity.
+ * m3g_ph_dynmat_gradient: the arguments, checks and launch shape of m3g_ph_dynmat; gradient [n_q, 3, 3 max_unit_atoms,
+ * 3 max_unit_atoms] complex128: dD / dq_alpha for the CARTESIAN q in 1/A without 2 pi (q_cart = q_frac L^-T), that is every image term
+ * of D times 2 pi i r_alpha with r = d L; eV / (A amu).  3 n_q blocks-per-q must fit one launch, else M3G_ERR_VALUE. */
+int m3g_ph_dynmat_gradient(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const double* phi, int64_t n_q,
+                           const double* q, const int32_t* q_struct, int32_t max_unit_atoms, double* gradient, void* stream);
+/* Group velocities v = d f / d q_cart (THz A; 1 THz A = 100 m/s) of n_q q-points, one workgroup each.  DEVICE: eigenvalues [n_q, n]
+ * (of D, eV / (A^2 amu), ascending), eigenvectors [n_q, n, n] complex128 (columns), gradient [n_q, 3, n, n] complex128 as above;
+ * velocities [n_q, n, 3] fp64 written.  HOST: direction [3], a Cartesian unit vector (| |d| - 1 | <= 1e-12).
+ * f_i = sign(lambda_i) sqrt(|lambda_i|) M3G_PH_THZ.  A degenerate set is a maximal run of consecutive f whose neighbouring gaps are
+ * below degeneracy_tolerance (THz, finite, >= 0).  In a set of more than one mode, W = E_S^H (sum_alpha direction_alpha dD_alpha) E_S
+ * is diagonalised by the solver above and E_S U stands for E_S (in LDS only: the caller's eigenvectors are not modified).  Then
+ * v[i, alpha] = Re(e_i^H dD_alpha e_i) M3G_PH_THZ^2 / (2 f_i); a mode with f_i < cutoff_frequency (THz, finite, >= 0; imaginary ones
+ * included) gets exactly 0.  A q with a non-finite eigenvalue (a matrix the solver flagged) gets NaN, and so do the modes of a set of
+ * more than M3G_PH_GV_MAX_SET modes or whose W the solver flags.  Sums: lane-strided, then a fixed tree; a q's result has the same
+ * bits alone or in any batch.  n < 1 or n > M3G_PH_GV_MAX_N, n_q < 0, a null pointer or a bad scalar -> M3G_ERR_VALUE; n_q == 0 does
+ * nothing.  One launch, capture-safe. */
+#define M3G_PH_THZ 15.63330423985619   /* sqrt(eV / (A^2 amu)) / (2 pi) in THz (CODATA 2018) */
+#define M3G_PH_GV_MAX_N 256
+#define M3G_PH_GV_MAX_SET 16
+int m3g_ph_group_velocities(int64_t n_q, int32_t n, const double* eigenvalues, const double* eigenvectors, const double* gradient,
+                            double degeneracy_tolerance, double cutoff_frequency, const double* direction, double* velocities,
+                            void* stream);
+
 /* ---- batched finite-strain elastic constants and equation of state (csrc/m3g_elastic.hip) ------------------------------------------
  * Replaces the host loop of pymatgen's DeformedStructureSet / matcalc's ElasticityCalc and EOSCalc over an ASE calculator (deform a
  * cell, evaluate, copy the stress back, 25 times per structure, fit in numpy) for a whole batch of structures.
@@ -737,7 +784,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              * 8: m3g_dyn_* (batched molecular dynamics: NVE, NVT Berendsen / Langevin, NPT Berendsen);
                              * 9: m3g_neb_* (batched climbing-image NEB force projection, improved tangent; replaces ASE's NEB.get_forces);
                              * 10: m3g_ph_* (batched finite-displacement phonons: displaced supercells, force constants, dynamical matrices);
-                             * 11: m3g_el_* (batched finite-strain elastic constants and Birch-Murnaghan equation of state: deformed copies, both fits) */
+                             * 11: m3g_el_* (batched finite-strain elastic constants and Birch-Murnaghan equation of state: deformed copies, both fits);
+                             *     additive, same version: m3g_eigh_batched (batched Hermitian Jacobi eigensolver), m3g_ph_dynmat_gradient,
+                             *     m3g_ph_group_velocities (phonon eigenvectors and group velocities) */
 
 #ifdef __cplusplus
 }

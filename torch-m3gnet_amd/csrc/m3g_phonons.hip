@@ -10,8 +10,14 @@
 //                          order; a structure with one gets NaN force constants);
 //   k_ph_dynmat            a thread per (q, u <= v): the two 3x3 blocks D(u,v), D(v,u) over the image table (one sincospi per image for
 //                          all nine entries, q.d reduced mod 1 first), mass weighting, Hermitisation, blocks (u,v) and (v,u) written.
+// On top of the dynamical matrices, for eigenvectors from the library's Hermitian solver (m3g_eigh.h; phonopy's GroupVelocity over
+// DerivativeOfDynamicalMatrix):
+//   k_ph_dynmat<true>      the thread map of k_ph_dynmat, three workgroups (alpha) for each of its own: dD / dq_alpha for the Cartesian
+//                          q (1/A, no 2 pi) -- every image term times 2 pi i r_alpha -- through the same dyn_block;
+//   k_ph_group_velocities  one workgroup per q-point: degenerate sets rotated to the eigenvectors of their block of the derivative
+//                          along `direction`, v = Re(e^H dD_alpha e) THZ^2 / (2 f), lane-strided sums and the fixed tree.
 // No atomics: every result depends on its structure's own inputs only, so it is bitwise the same alone or in any batch.  No allocation,
-// copy or wait in the three compute calls (capture-safe).
+// copy or wait in the compute calls (capture-safe).
 //
 // Layouts (structure s: n_u unit atoms, supercell n1 x n2 x n3, N_s = n_u n1 n2 n3 supercell atoms).  Supercell atom j = l n_u + b with
 // l = (l1 n2 + l2) n3 + l3, at r_b + l1 L_0 + l2 L_1 + l3 L_2.  The displaced batch holds per structure 1 + 6 n_u copies of N_s rows:
@@ -21,6 +27,7 @@
 #include <vector>
 
 #include "m3g_chunks.h"
+#include "m3g_eigh.h"
 #include "m3g_internal.h"
 
 namespace m3g {
@@ -157,9 +164,11 @@ __global__ void __launch_bounds__(kFcThreads) k_ph_force_constants(PhView st, co
   }
 }
 
-// the 3x3 block sum_l sum_m w_m Phi[u, l n_u + v] exp(2 pi i q.d_m) of structure s (re, im)
+// the 3x3 block sum_l sum_m w_m Phi[u, l n_u + v] exp(2 pi i q.d_m) of structure s (re, im); kGrad: every image term times
+// 2 pi i r_alpha, r = d L the Cartesian image vector -- the derivative with respect to the Cartesian q_alpha (1/A, no 2 pi)
+template <bool kGrad = false>
 __device__ inline void dyn_block(const PhView& st, const double* __restrict__ phi, int64_t s, int64_t u, int64_t v, int64_t nu,
-                                 int64_t ns, const double q[3], double re[9], double im[9]) {
+                                 int64_t ns, const double q[3], double re[9], double im[9], int alpha = 0) {
   for (int k = 0; k < 9; ++k) re[k] = im[k] = 0.0;
   const int64_t row = st.pair_off[s] + u * ns;
   for (int64_t j = v; j < ns; j += nu) {
@@ -172,8 +181,15 @@ __device__ inline void dyn_block(const PhView& st, const double* __restrict__ ph
       const double y = x - rint(x);   // q.d mod 1, in [-1/2, 1/2]
       double sn, cs;
       sincospi(2.0 * y, &sn, &cs);
-      wc += cs;
-      ws += sn;
+      if constexpr (kGrad) {   // 2 pi i r (cs + i sn)
+        const double* L = st.lat + 9 * s;
+        const double r = 2.0 * M_PI * (d[3 * i] * L[alpha] + d[3 * i + 1] * L[3 + alpha] + d[3 * i + 2] * L[6 + alpha]);
+        wc -= r * sn;
+        ws += r * cs;
+      } else {
+        wc += cs;
+        ws += sn;
+      }
     }
     const double w = 1.0 / (double)m;
     wc *= w;
@@ -186,11 +202,15 @@ __device__ inline void dyn_block(const PhView& st, const double* __restrict__ ph
   }
 }
 
+// kGrad: the grid holds three workgroups (alpha = 0, 1, 2) for each one of the plain kernel, out is [Q, 3, dim, dim]
+template <bool kGrad>
 __global__ void __launch_bounds__(kDynThreads) k_ph_dynmat(PhView st, int64_t n_q, int64_t blocks_per_q, const double* __restrict__ qs,
                                                            const int32_t* __restrict__ q_struct, int32_t max_nu,
                                                            const double* __restrict__ phi, double* __restrict__ out) {
-  const int64_t q_i = blockIdx.x / blocks_per_q;
-  const int64_t p = (blockIdx.x % blocks_per_q) * kDynThreads + threadIdx.x;
+  const int64_t slot = kGrad ? blockIdx.x / 3 : blockIdx.x;
+  const int alpha = kGrad ? (int)(blockIdx.x % 3) : 0;
+  const int64_t q_i = slot / blocks_per_q;
+  const int64_t p = (slot % blocks_per_q) * kDynThreads + threadIdx.x;
   if (q_i >= n_q) return;
   const int64_t s = q_struct[q_i];
   if (s < 0 || s >= st.S) return;
@@ -204,15 +224,15 @@ __global__ void __launch_bounds__(kDynThreads) k_ph_dynmat(PhView st, int64_t n_
   const double* m = st.mass + st.unit_off[s];
   const double inv = 1.0 / sqrt(m[u] * m[v]);
   double are[9], aim[9], bre[9], bim[9];
-  dyn_block(st, phi, s, u, v, nu, ns, q, are, aim);
+  dyn_block<kGrad>(st, phi, s, u, v, nu, ns, q, are, aim, alpha);
   if (u != v) {
-    dyn_block(st, phi, s, v, u, nu, ns, q, bre, bim);
+    dyn_block<kGrad>(st, phi, s, v, u, nu, ns, q, bre, bim, alpha);
   } else {
     for (int k = 0; k < 9; ++k) { bre[k] = are[k]; bim[k] = aim[k]; }
   }
   // H(u,v)[a][b] = (A[a][b] + conj(B[b][a])) / 2; H(v,u) = H(u,v)^H
   const int64_t dim = 3 * (int64_t)max_nu;
-  double* o = out + 2 * dim * dim * q_i;
+  double* o = out + 2 * dim * dim * (kGrad ? 3 * q_i + alpha : q_i);
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) {
       const double hr = 0.5 * (are[3 * a + b] + bre[3 * b + a]) * inv;
@@ -223,6 +243,137 @@ __global__ void __launch_bounds__(kDynThreads) k_ph_dynmat(PhView st, int64_t n_
       o[2 * (jb * dim + ia)] = hr;
       o[2 * (jb * dim + ia) + 1] = -hi;
     }
+}
+
+// Group velocities of one q-point per workgroup (include/m3gnet_hip.h, "phonon group velocities").  Degenerate sets one after the
+// other, in LDS only the set's eigenvectors X [m][n], a second block Y [m][n] (G_dir X first, then the rotated X U) and the
+// m x m blocks W and U: 512 n bytes of dynamic LDS for kGvSet = 16, whatever the width of the matrix.
+constexpr int kGvSet = M3G_PH_GV_MAX_SET;
+constexpr int kGvThreads = kChunkRows;
+inline size_t gv_lds_bytes(int n) { return sizeof(double) * ((size_t)4 * n * kGvSet + n); }
+
+__global__ void __launch_bounds__(kGvThreads) k_ph_group_velocities(int n, const double* __restrict__ lam, const double* __restrict__ E,
+                                                                    const double* __restrict__ G, double tol, double cutoff, double d0,
+                                                                    double d1, double d2, double* __restrict__ vout) {
+#pragma clang fp contract(off)
+  extern __shared__ double gv_lds[];
+  __shared__ double W[2 * kGvSet * kGvSet];
+  __shared__ double U[2 * kGvSet * kGvSet];
+  __shared__ EighScratch<kGvSet> sc;
+  __shared__ double sh[3][kGvThreads];
+  __shared__ int bad;
+  double* X = gv_lds;
+  double* Y = X + 2 * (size_t)n * kGvSet;
+  double* f = Y + 2 * (size_t)n * kGvSet;
+  const int64_t q = blockIdx.x;
+  const int t = threadIdx.x;
+  const int64_t nn = (int64_t)n * n;
+  const double* lq = lam + (int64_t)n * q;
+  const double* Eq = E + 2 * nn * q;
+  const double* Gq = G + 6 * nn * q;
+  double* out = vout + 3 * (int64_t)n * q;
+  constexpr double thz = M3G_PH_THZ;
+  if (t == 0) bad = 0;
+  __syncthreads();
+  for (int i = t; i < n; i += kGvThreads) {
+    const double l = lq[i];
+    if (!std::isfinite(l)) bad = 1;   // (every writer writes the same value)
+    f[i] = (l < 0.0 ? -1.0 : (l > 0.0 ? 1.0 : 0.0)) * sqrt(fabs(l)) * thz;
+  }
+  __syncthreads();
+  if (bad) {   // (uniform over the workgroup)
+    for (int i = t; i < 3 * n; i += kGvThreads) out[i] = NAN;
+    return;
+  }
+  for (int begin = 0; begin < n;) {   // (every thread walks the same sets)
+    int end = begin + 1;
+    while (end < n && f[end] - f[end - 1] < tol) ++end;
+    const int m = end - begin;
+    if (m > kGvSet || f[end - 1] < cutoff) {   // too large a set: NaN; every mode of it below the cutoff: exactly 0
+      const double fill = m > kGvSet ? (double)NAN : 0.0;
+      for (int i = 3 * begin + t; i < 3 * end; i += kGvThreads) out[i] = fill;
+      begin = end;
+      continue;
+    }
+    for (int e = t; e < n * m; e += kGvThreads) {
+      const int k = e / n, a = e % n;
+      X[2 * e] = Eq[2 * ((int64_t)a * n + begin + k)];
+      X[2 * e + 1] = Eq[2 * ((int64_t)a * n + begin + k) + 1];
+    }
+    __syncthreads();
+    const double* Z = X;
+    bool failed = false;
+    if (m > 1) {
+      for (int e = t; e < n * m; e += kGvThreads) {   // Y[k][a] = sum_b (sum_alpha d_alpha dD_alpha)[a, b] X[k][b]
+        const int k = e / n, a = e % n;
+        const double* g0 = Gq + 2 * (int64_t)a * n;
+        const double* g1 = g0 + 2 * nn;
+        const double* g2 = g1 + 2 * nn;
+        const double* x = X + 2 * (size_t)k * n;
+        double yr = 0.0, yi = 0.0;
+        for (int b = 0; b < n; ++b) {
+          const double gr = (d0 * g0[2 * b] + d1 * g1[2 * b]) + d2 * g2[2 * b];
+          const double gi = (d0 * g0[2 * b + 1] + d1 * g1[2 * b + 1]) + d2 * g2[2 * b + 1];
+          yr += gr * x[2 * b] - gi * x[2 * b + 1];
+          yi += gr * x[2 * b + 1] + gi * x[2 * b];
+        }
+        Y[2 * e] = yr;
+        Y[2 * e + 1] = yi;
+      }
+      __syncthreads();
+      for (int e = t; e < m * m; e += kGvThreads) {   // W[j, k] = sum_a conj(X[j][a]) Y[k][a]
+        const int j = e / m, k = e % m;
+        const double* x = X + 2 * (size_t)j * n;
+        const double* y = Y + 2 * (size_t)k * n;
+        double wr = 0.0, wi = 0.0;
+        for (int a = 0; a < n; ++a) {
+          wr += x[2 * a] * y[2 * a] + x[2 * a + 1] * y[2 * a + 1];
+          wi += x[2 * a] * y[2 * a + 1] - x[2 * a + 1] * y[2 * a];
+        }
+        W[2 * e] = wr;
+        W[2 * e + 1] = wi;
+      }
+      __syncthreads();
+      const int status = eigh_jacobi_lds<kGvSet>(W, U, m, sc, t, kGvThreads);
+      failed = (status & ~M3G_EIGH_SWEEPS_MASK) != 0;
+      for (int e = t; e < n * m; e += kGvThreads) {   // Y[k][a] = sum_j X[j][a] U[j, order[k]]
+        const int k = e / n, a = e % n;
+        const int col = sc.order[k];
+        double yr = 0.0, yi = 0.0;
+        for (int j = 0; j < m; ++j) {
+          const double xr = X[2 * ((size_t)j * n + a)], xi = X[2 * ((size_t)j * n + a) + 1];
+          const double ur = U[2 * (j * m + col)], ui = U[2 * (j * m + col) + 1];
+          yr += xr * ur - xi * ui;
+          yi += xr * ui + xi * ur;
+        }
+        Y[2 * e] = yr;
+        Y[2 * e + 1] = yi;
+      }
+      __syncthreads();
+      Z = Y;
+    }
+    for (int k = 0; k < m; ++k) {   // v[i, alpha] = Re(z^H dD_alpha z) thz^2 / (2 f_i): lane-strided over the rows, then the fixed tree
+      const double* z = Z + 2 * (size_t)k * n;
+      double acc[3] = {0.0, 0.0, 0.0};
+      for (int a = t; a < n; a += kGvThreads)
+        for (int c = 0; c < 3; ++c) {
+          const double* g = Gq + 2 * (c * nn + (int64_t)a * n);
+          double tr = 0.0, ti = 0.0;
+          for (int b = 0; b < n; ++b) {
+            tr += g[2 * b] * z[2 * b] - g[2 * b + 1] * z[2 * b + 1];
+            ti += g[2 * b] * z[2 * b + 1] + g[2 * b + 1] * z[2 * b];
+          }
+          acc[c] += z[2 * a] * tr + z[2 * a + 1] * ti;
+        }
+      chunk_tree_reduce<3>(sh, acc, t);
+      if (t < 3) {
+        const double fi = f[begin + k];
+        out[3 * (begin + k) + t] = failed ? (double)NAN : (fi < cutoff ? 0.0 : sh[t][0] * (thz * thz) / (2.0 * fi));
+      }
+      __syncthreads();
+    }
+    begin = end;
+  }
 }
 
 bool ph_sizes_ok(const m3g_ph_sizes* z) {
@@ -371,20 +522,64 @@ extern "C" int m3g_ph_force_constants(const m3g_ph_sizes* sizes, const void* sta
   M3G_RETURN_LAUNCH_STATUS();
 }
 
-extern "C" int m3g_ph_dynmat(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const double* phi, int64_t n_q, const double* q,
-                             const int32_t* q_struct, int32_t max_unit_atoms, double* dynmat, void* stream_) {
-  if (!ph_sizes_ok(sizes) || !state || !phi || n_q < 0 || (n_q > 0 && (!q || !q_struct || !dynmat)) || max_unit_atoms < 1 ||
+namespace {
+// the checks and the launch of m3g_ph_dynmat and m3g_ph_dynmat_gradient (three workgroups per one of the plain kernel)
+template <bool kGrad>
+int dynmat_call(const char* fn, const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const double* phi, int64_t n_q,
+                const double* q, const int32_t* q_struct, int32_t max_unit_atoms, double* out, void* stream_) {
+  if (!ph_sizes_ok(sizes) || !state || !phi || n_q < 0 || (n_q > 0 && (!q || !q_struct || !out)) || max_unit_atoms < 1 ||
       max_unit_atoms > sizes->n_unit_atoms) {
-    set_error("m3g_ph_dynmat: null argument, bad sizes, n_q < 0 or max_unit_atoms outside [1, n_unit_atoms]");
+    set_error("%s: null argument, bad sizes, n_q < 0 or max_unit_atoms outside [1, n_unit_atoms]", fn);
     return M3G_ERR_VALUE;
   }
-  if (state_bytes < ph_layout(*sizes).total) { set_error("m3g_ph_dynmat: state buffer too small"); return M3G_ERR_SIZE; }
+  if (state_bytes < ph_layout(*sizes).total) { set_error("%s: state buffer too small", fn); return M3G_ERR_SIZE; }
   if (n_q == 0) return M3G_OK;
   const int64_t pairs = (int64_t)max_unit_atoms * (max_unit_atoms + 1) / 2;
   const int64_t per_q = (pairs + kDynThreads - 1) / kDynThreads;
-  if (n_q * per_q > (int64_t(1) << 26)) { set_error("m3g_ph_dynmat: too many q-points for one launch"); return M3G_ERR_VALUE; }
+  const int64_t blocks = n_q * per_q * (kGrad ? 3 : 1);
+  if (blocks > (int64_t(1) << 26)) { set_error("%s: too many q-points for one launch", fn); return M3G_ERR_VALUE; }
   const PhView st = ph_view(*sizes, state);
-  hipLaunchKernelGGL(k_ph_dynmat, dim3((unsigned)(n_q * per_q)), dim3(kDynThreads), 0, (hipStream_t)stream_, st, n_q, per_q, q, q_struct,
-                     max_unit_atoms, phi, dynmat);
+  hipLaunchKernelGGL(k_ph_dynmat<kGrad>, dim3((unsigned)blocks), dim3(kDynThreads), 0, (hipStream_t)stream_, st, n_q, per_q, q, q_struct,
+                     max_unit_atoms, phi, out);
+  M3G_RETURN_LAUNCH_STATUS();
+}
+}  // namespace
+
+extern "C" int m3g_ph_dynmat(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const double* phi, int64_t n_q, const double* q,
+                             const int32_t* q_struct, int32_t max_unit_atoms, double* dynmat, void* stream_) {
+  return dynmat_call<false>("m3g_ph_dynmat", sizes, state, state_bytes, phi, n_q, q, q_struct, max_unit_atoms, dynmat, stream_);
+}
+
+extern "C" int m3g_ph_dynmat_gradient(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, const double* phi, int64_t n_q,
+                                      const double* q, const int32_t* q_struct, int32_t max_unit_atoms, double* gradient, void* stream_) {
+  return dynmat_call<true>("m3g_ph_dynmat_gradient", sizes, state, state_bytes, phi, n_q, q, q_struct, max_unit_atoms, gradient, stream_);
+}
+
+extern "C" int m3g_ph_group_velocities(int64_t n_q, int32_t n, const double* eigenvalues, const double* eigenvectors, const double* gradient,
+                                       double degeneracy_tolerance, double cutoff_frequency, const double* direction, double* velocities,
+                                       void* stream_) {
+  if (n_q < 0 || n_q > INT32_MAX || n < 1 || n > M3G_PH_GV_MAX_N) {
+    set_error("m3g_ph_group_velocities: need 0 <= n_q < 2^31 and 1 <= n <= %d (M3G_PH_GV_MAX_N); got n_q %lld, n %d", M3G_PH_GV_MAX_N,
+              (long long)n_q, (int)n);
+    return M3G_ERR_VALUE;
+  }
+  if (!direction || (n_q > 0 && (!eigenvalues || !eigenvectors || !gradient || !velocities))) {
+    set_error("m3g_ph_group_velocities: null argument");
+    return M3G_ERR_VALUE;
+  }
+  if (!(std::isfinite(degeneracy_tolerance) && degeneracy_tolerance >= 0.0 && std::isfinite(cutoff_frequency) && cutoff_frequency >= 0.0)) {
+    set_error("m3g_ph_group_velocities: degeneracy_tolerance and cutoff_frequency must be finite and >= 0");
+    return M3G_ERR_VALUE;
+  }
+  const double norm = std::sqrt(direction[0] * direction[0] + direction[1] * direction[1] + direction[2] * direction[2]);
+  if (!(std::fabs(norm - 1.0) <= 1e-12)) {   // (a NaN or an infinity fails the comparison too)
+    set_error("m3g_ph_group_velocities: direction must be a finite unit vector");
+    return M3G_ERR_VALUE;
+  }
+  if (n_q == 0) return M3G_OK;
+  const size_t lds = gv_lds_bytes(n);
+  if (lds > 48 * 1024) M3G_HIP_CHECK(hipFuncSetAttribute((const void*)k_ph_group_velocities, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_ph_group_velocities, dim3((unsigned)n_q), dim3(kGvThreads), lds, (hipStream_t)stream_, (int)n, eigenvalues, eigenvectors,
+                     gradient, degeneracy_tolerance, cutoff_frequency, direction[0], direction[1], direction[2], velocities);
   M3G_RETURN_LAUNCH_STATUS();
 }

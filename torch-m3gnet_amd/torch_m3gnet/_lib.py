@@ -77,6 +77,9 @@ DYN_NVE, DYN_NVT_BERENDSEN, DYN_NVT_LANGEVIN, DYN_NPT_BERENDSEN = range(4)   # M
 DYN_STARTED, DYN_ERROR = 1, 2                                               # M3G_DYN_* flag bits
 NEB_ROWS = 5                                                                 # M3G_NEB_ROWS
 PH_MAX_MULTIPLICITY = 27                                                     # M3G_PH_MAX_MULTIPLICITY
+EIGH_MAX_N, EIGH_MAX_SWEEPS = 64, 30                                         # M3G_EIGH_MAX_N, M3G_EIGH_MAX_SWEEPS
+EIGH_SWEEPS_MASK, EIGH_NONFINITE, EIGH_NOT_CONVERGED = 0xff, 0x100, 0x200    # M3G_EIGH_* info bits
+PH_THZ, PH_GV_MAX_N, PH_GV_MAX_SET = 15.63330423985619, 256, 16              # M3G_PH_THZ, M3G_PH_GV_MAX_N, M3G_PH_GV_MAX_SET
 
 
 class M3GPhSizes(C.Structure):   # m3g_ph_sizes
@@ -198,6 +201,11 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p]),
     "m3g_ph_dynmat": (C.c_int, [C.POINTER(M3GPhSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                 C.c_void_p, C.c_void_p]),
+    "m3g_ph_dynmat_gradient": (C.c_int, [C.POINTER(M3GPhSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_void_p, C.c_void_p]),
+    "m3g_ph_group_velocities": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "m3g_eigh_batched": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_el_state_bytes": (C.c_int, [C.POINTER(M3GElSizes), C.POINTER(C.c_size_t)]),
     "m3g_el_init": (C.c_int, [C.POINTER(M3GElSizes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                               C.c_void_p]),

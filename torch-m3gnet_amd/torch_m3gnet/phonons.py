@@ -6,7 +6,9 @@ evaluated one at a time.  `Phonons.run` takes a batch of structures instead.  Ev
 block of a single fp64 `pos` written by one launch (`ph_displace`); the displaced batch is evaluated through the path `Relaxer` uses
 (`VerletGraph.step`), in sub-batches of whole displaced supercells of one structure, at most `max_atoms` atoms; the force constants of the whole batch
 are one launch (`ph_force_constants`) and the dynamical matrices of any number of q-points one launch (`ph_dynamical_matrices`).
-Eigenvalues come from `torch.linalg.eigvalsh` on the device; DOS and thermal properties are fp64 torch ops on top.
+Eigenvalues come from `torch.linalg.eigvalsh` on the device (the default) or from the library's own batched Hermitian Jacobi solver
+(`eigensolver="jacobi"`, `linalg.eigh_batched`); eigenvectors, group velocities (`ph_group_velocities`, one launch) and the projected
+DOS always from the latter.  DOS and thermal properties are fp64 torch ops on top.
 
 Semantics (include/m3gnet_hip.h, "batched finite-displacement phonons"): phonopy's method with a diagonal supercell and no symmetry
 reduction; +-delta along x, y, z for every atom of the home cell; central differences; the acoustic sum rule imposed on the self term
@@ -22,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
+from .linalg import EIGH_MAX_N, eigh_batched
 from ._driver import (Driver, boolean, check_tensor, gpu_device, integer, positive, state_tensor, structure_arrays, structure_masses,
                       sub_batches)
 from .data import MaterialGraphKey as K
@@ -42,6 +45,13 @@ KB_EV = _BOLTZMANN / _EV               # eV / K
 # The eigen-solver path.  complex128 `eigvalsh` works on the device but took 1.9 s for 8,000 12 x 12 matrices on the MI355X, against
 # 6.7 ms for the real symmetric embedding [[A, -B], [B, A]] of H = A + iB, which holds every eigenvalue of H twice (profiles/phonons.txt).
 EIGH_PATH = "real_embedding"
+EIGENSOLVERS = ("embedding", "jacobi")   # Phonons(eigensolver=...): today's path (the default), or m3g_eigh_batched for 3n <= EIGH_MAX_N
+
+
+def _check_eigensolver(name) -> str:
+    if name not in EIGENSOLVERS:
+        raise ValueError(f"eigensolver must be one of {EIGENSOLVERS}; got {name!r}")
+    return name
 
 
 def _sizes(n_unit: Sequence[int], supercells: np.ndarray) -> _lib.M3GPhSizes:
@@ -141,6 +151,77 @@ def ph_dynamical_matrices(state: PhononState, structure: int, q) -> torch.Tensor
     return out
 
 
+def ph_dynamical_matrix_gradients(state: PhononState, structure: int, q) -> torch.Tensor:
+    """dD / dq_alpha [Q, 3, 3n, 3n] complex128 (eV / (A amu)) of structure `structure` at the fractional q-points `q` [Q, 3], with
+    respect to the CARTESIAN q in 1/A without 2 pi -- the convention of `band_structure`'s `distance` (m3g_ph_dynmat_gradient over
+    `state.phi`: every image term of D times 2 pi i r_alpha).  One launch."""
+    s = int(structure)
+    if not 0 <= s < state.S:
+        raise ValueError(f"structure must lie in [0, {state.S})")
+    q = torch.as_tensor(q, dtype=torch.float64, device=state.device).reshape(-1, 3).contiguous()
+    n = int(state.n_unit[s])
+    out = torch.zeros(len(q), 3, 3 * n, 3 * n, dtype=torch.complex128, device=state.device)
+    if len(q) == 0:
+        return out
+    q_struct = torch.full((len(q),), s, dtype=torch.int32, device=state.device)
+    with _cuda.on_device(state.device):
+        _lib.check(state.lib.m3g_ph_dynmat_gradient(C.byref(state.sizes), _ptr(state.state), state.state.numel(), _ptr(state.phi), len(q),
+                                                    _ptr(q), _ptr(q_struct), n, _ptr(out), _stream()))
+    return out
+
+
+def unit_direction(direction) -> np.ndarray:
+    """`direction` [3] (finite, not zero) scaled to unit length."""
+    d = np.asarray(direction, dtype=np.float64)
+    if d.shape != (3,) or not np.isfinite(d).all() or not np.linalg.norm(d) > 0.0:
+        raise ValueError(f"direction must be three finite numbers, not all zero; got {np.asarray(direction).tolist()}")
+    return np.ascontiguousarray(d / np.linalg.norm(d))
+
+
+def ph_group_velocities(eigenvalues: torch.Tensor, eigenvectors: torch.Tensor, gradient: torch.Tensor, direction=(1.0, 2.0, 3.0),
+                        degeneracy_tolerance: float = 1e-4, cutoff_frequency: float = 1e-3) -> torch.Tensor:
+    """Group velocities [Q, n, 3] float64 (THz A; 1 THz A = 100 m/s), v = d f / d q_cart (m3g_ph_group_velocities, one launch, one
+    workgroup per q): `eigenvalues` [Q, n] of D (ascending), `eigenvectors` [Q, n, n] (columns), `gradient` [Q, 3, n, n]
+    (`ph_dynamical_matrix_gradients`).  Modes closer than `degeneracy_tolerance` (THz) form a set; a set of several modes is rotated to
+    the eigenvectors of its block of sum_alpha direction_alpha dD_alpha first (phonopy's rule, `direction` normalised here).  A mode
+    below `cutoff_frequency` (THz) gets exactly 0; a q with a non-finite eigenvalue NaN.  n <= _lib.PH_GV_MAX_N."""
+    if not (torch.is_tensor(eigenvalues) and eigenvalues.dim() == 2):
+        raise ValueError("eigenvalues must be a [Q, n] float64 tensor")
+    nq, n = (int(k) for k in eigenvalues.shape)
+    d = unit_direction(direction)
+    tol, cut = float(degeneracy_tolerance), float(cutoff_frequency)
+    if not (math.isfinite(tol) and tol >= 0.0):
+        raise ValueError(f"degeneracy_tolerance must be finite and >= 0; got {degeneracy_tolerance}")
+    if not (math.isfinite(cut) and cut >= 0.0):
+        raise ValueError(f"cutoff_frequency must be finite and >= 0; got {cutoff_frequency}")
+    if not 1 <= n <= _lib.PH_GV_MAX_N:
+        raise ValueError(f"ph_group_velocities: n = {n} is outside [1, {_lib.PH_GV_MAX_N}] (the LDS of one workgroup holds two n x "
+                         f"{_lib.PH_GV_MAX_SET} blocks of a degenerate set)")
+    dev = eigenvalues.device
+    if dev.type != "cuda":
+        raise ValueError(f"ph_group_velocities runs on a GPU device; got {dev}")
+    check_tensor("eigenvalues", eigenvalues, (nq, n), torch.float64, dev)
+    check_tensor("eigenvectors", eigenvectors, (nq, n, n), torch.complex128, dev)
+    check_tensor("gradient", gradient, (nq, 3, n, n), torch.complex128, dev)
+    v = torch.empty(nq, n, 3, dtype=torch.float64, device=dev)
+    if nq:
+        with _cuda.on_device(dev):
+            _lib.check(_lib.load_library().m3g_ph_group_velocities(nq, n, _ptr(eigenvalues), _ptr(eigenvectors), _ptr(gradient), tol, cut,
+                                                                   d.ctypes.data, _ptr(v), _stream()))
+    return v
+
+
+def _eigh(d: torch.Tensor):
+    """(eigenvalues [Q, n] ascending, eigenvectors [Q, n, n] as columns) of Hermitian [Q, n, n] complex128 on the device: the
+    library's Jacobi solver up to EIGH_MAX_N, `torch.linalg.eigh` beyond (slow: 1.8 - 2.5 s for 8,000 12 x 12 matrices,
+    profiles/phonons.txt -- but still on the device)."""
+    if d.shape[-1] <= EIGH_MAX_N:
+        w, v, _ = eigh_batched(d, eigenvectors=True)   # (a flagged matrix is NaN already)
+        return w, v
+    w, v = torch.linalg.eigh(d)
+    return w.contiguous(), v.contiguous()
+
+
 def _eigvalsh(d: torch.Tensor) -> torch.Tensor:
     """Ascending eigenvalues [..., n] of Hermitian matrices [..., n, n] (complex128): every other eigenvalue of the real embedding."""
     a, b = d.real, d.imag
@@ -159,6 +240,15 @@ def gaussian_dos(frequencies: torch.Tensor, weights: torch.Tensor, grid: torch.T
     x = (grid[:, None, None] - f[None]) / sigma
     g = torch.exp(-0.5 * x * x) / (math.sqrt(2.0 * math.pi) * sigma)
     return (g.sum(dim=2) * weights[None]).sum(dim=1)
+
+
+def projected_gaussian_dos(frequencies: torch.Tensor, projections: torch.Tensor, weights: torch.Tensor, grid: torch.Tensor,
+                           sigma: float) -> torch.Tensor:
+    """`gaussian_dos` per atom [n_atoms, G]: the Gaussian of mode (q, i) weighted by `projections` [Q, n_atoms, modes]."""
+    f = frequencies.reshape(len(weights), -1)
+    x = (grid[:, None, None] - f[None]) / sigma
+    g = torch.exp(-0.5 * x * x) / (math.sqrt(2.0 * math.pi) * sigma)   # [G, Q, modes]
+    return torch.einsum("gqm,qam,q->ag", g, projections, weights)
 
 
 def harmonic_thermal(frequencies: torch.Tensor, weights: torch.Tensor, temperatures: torch.Tensor, cutoff_frequency: float = 1e-3) -> dict:
@@ -199,11 +289,13 @@ class PhononResult:
     """Phonons of one structure: `force_constants` [n, N_s, 3, 3] (eV/A^2, phonopy's compact layout), `residual_fmax` (largest force
     of the undisplaced supercell, eV/A), `asr_violation` (raw max |sum_j Phi|), `asr_correction` [n, 3, 3] (what the sum rule added to
     each self term; zeros with asr=False), `error` (a non-finite force: everything is NaN).  Frequencies (THz) come from the device
-    on demand: `frequencies(q)`, `band_structure`, `mesh`, `dos`, `thermal_properties`."""
+    on demand: `frequencies(q)`, `band_structure`, `mesh`, `dos`, `thermal_properties`, and with eigenvectors `modes(q)`,
+    `group_velocities`, `projected_dos`."""
 
     def __init__(self, state: PhononState, s: int, asr: bool, max_qpoints: int, cutoff_frequency: float, residual_fmax: float,
-                 phi: np.ndarray, sums: np.ndarray, nonfinite: int):
+                 phi: np.ndarray, sums: np.ndarray, nonfinite: int, eigensolver: str = "embedding"):
         self._state, self._s, self._max_q, self.cutoff_frequency = state, s, max_qpoints, cutoff_frequency
+        self.eigensolver = _check_eigensolver(eigensolver)
         n, ns = int(state.n_unit[s]), int(state.super_sizes[s])
         self.n_atoms, self.supercell = n, tuple(int(k) for k in state.supercells[s])
         self.lattice = state.lattices[s].copy()
@@ -224,8 +316,45 @@ class PhononResult:
         out = []
         for a in range(0, len(q), self._max_q):   # q batches of at most max_qpoints: each matrix is independent of the others
             d = ph_dynamical_matrices(self._state, self._s, q[a:a + self._max_q])
-            out.append(to_frequencies(_eigvalsh(d)).cpu().numpy())
+            lam = eigh_batched(d, eigenvectors=False)[0] if self.eigensolver == "jacobi" and n3 <= EIGH_MAX_N else _eigvalsh(d)
+            out.append(to_frequencies(lam).cpu().numpy())
         return np.concatenate(out) if out else np.zeros((0, n3))
+
+    def modes(self, q) -> dict:
+        """`frequencies` [Q, 3n] (THz, ascending, imaginary modes negative) and `eigenvectors` [Q, 3n, 3n] complex128 (column k
+        belongs to frequency k, orthonormal; the polarisation of atom u in rows 3u .. 3u + 2) at fractional q-points [Q, 3].  The
+        library's Jacobi solver for 3n <= EIGH_MAX_N, `torch.linalg.eigh` on the device beyond (slow)."""
+        q = np.asarray(q, dtype=np.float64).reshape(-1, 3)
+        n3 = 3 * self.n_atoms
+        if self.error:
+            return {"frequencies": np.full((len(q), n3), np.nan), "eigenvectors": np.full((len(q), n3, n3), np.nan, dtype=np.complex128)}
+        f, e = [np.zeros((0, n3))], [np.zeros((0, n3, n3), dtype=np.complex128)]
+        for a in range(0, len(q), self._max_q):
+            w, v = _eigh(ph_dynamical_matrices(self._state, self._s, q[a:a + self._max_q]))
+            f.append(to_frequencies(w).cpu().numpy())
+            e.append(v.cpu().numpy())
+        return {"frequencies": np.concatenate(f), "eigenvectors": np.concatenate(e)}
+
+    def group_velocities(self, q, direction=(1, 2, 3), degeneracy_tolerance: float = 1e-4) -> np.ndarray:
+        """[Q, 3n, 3] group velocities d f / d q_cart (THz A; 1 THz A = 100 m/s; q_cart in 1/A without 2 pi, as `band_structure`'s
+        `distance`) at fractional q-points [Q, 3], in the order of `frequencies`.  Phonopy's rules: modes closer than
+        `degeneracy_tolerance` (THz) are rotated within their set to the eigenvectors of the derivative along `direction` (Cartesian,
+        normalised here) first; a mode below `cutoff_frequency` gets exactly 0."""
+        q = np.asarray(q, dtype=np.float64).reshape(-1, 3)
+        n3 = 3 * self.n_atoms
+        unit_direction(direction)   # (refused before any work)
+        if not (math.isfinite(float(degeneracy_tolerance)) and float(degeneracy_tolerance) >= 0.0):
+            raise ValueError(f"degeneracy_tolerance must be finite and >= 0; got {degeneracy_tolerance}")
+        if n3 > _lib.PH_GV_MAX_N:
+            raise ValueError(f"group_velocities: 3n = {n3} is above {_lib.PH_GV_MAX_N} (_lib.PH_GV_MAX_N)")
+        if self.error:
+            return np.full((len(q), n3, 3), np.nan)
+        out = [np.zeros((0, n3, 3))]
+        for a in range(0, len(q), self._max_q):
+            w, v = _eigh(ph_dynamical_matrices(self._state, self._s, q[a:a + self._max_q]))
+            g = ph_dynamical_matrix_gradients(self._state, self._s, q[a:a + self._max_q])
+            out.append(ph_group_velocities(w, v, g, direction, degeneracy_tolerance, self.cutoff_frequency).cpu().numpy())
+        return np.concatenate(out)
 
     def band_structure(self, path, npts: int = 51) -> dict:
         """Frequencies along the straight segments between consecutive fractional q-points of `path` (npts points per segment, both
@@ -261,6 +390,26 @@ class PhononResult:
         g = gaussian_dos(torch.tensor(f, device=dev), torch.tensor(m["weights"], device=dev), grid, float(sigma))
         return {"frequency_points": grid.cpu().numpy(), "dos": g.cpu().numpy()}
 
+    def projected_dos(self, mesh=(10, 10, 10), sigma: float = 0.1, npts: int = 201, fmin: float | None = None, fmax: float | None = None,
+                      gamma_centered: bool = True) -> dict:
+        """Gaussian-smeared density of states per atom [n_atoms, npts] (states / THz per unit cell) on a mesh: each mode's Gaussian
+        weighted by sum_a |e_ua|^2, which sums to 1 over the atoms -- so the rows sum to the total DOS of the same frequencies (`dos`
+        of a result with eigensolver="jacobi" where 3n <= EIGH_MAX_N: the eigenvalues have the same bits with and without vectors)."""
+        if not (math.isfinite(sigma) and sigma > 0):
+            raise ValueError(f"sigma must be finite and > 0; got {sigma}")
+        q = monkhorst_pack(mesh, gamma_centered)
+        m = self.modes(q)
+        f = m["frequencies"]
+        lo = float(np.nanmin(f)) - 5 * sigma if fmin is None else float(fmin)
+        hi = float(np.nanmax(f)) + 5 * sigma if fmax is None else float(fmax)
+        dev = self._state.device
+        grid = torch.linspace(lo, hi, int(npts), dtype=torch.float64, device=dev)
+        e = torch.tensor(m["eigenvectors"], device=dev)
+        p = (e.real ** 2 + e.imag ** 2).reshape(len(q), self.n_atoms, 3, -1).sum(dim=2)   # [Q, atom, mode]
+        g = projected_gaussian_dos(torch.tensor(f, device=dev), p, torch.full((len(q),), 1.0 / len(q), dtype=torch.float64, device=dev),
+                                   grid, float(sigma))
+        return {"frequency_points": grid.cpu().numpy(), "projected_dos": g.cpu().numpy()}
+
     def thermal_properties(self, temperatures, mesh=(10, 10, 10), gamma_centered: bool = True) -> dict:
         """Harmonic F, S, Cv, E per unit cell (eV, eV/K) at `temperatures` (K) over a mesh; `n_excluded` modes below cutoff_frequency."""
         T = np.asarray(temperatures, dtype=np.float64).reshape(-1)
@@ -279,12 +428,14 @@ class Phonons(Driver):
     `model`: the `Gradient` returned by `build_model` (evaluated, like `Relaxer`'s, through a pair-virial engine made from its
     `Sequential`).  `delta`: displacement (A); `asr`: impose the acoustic sum rule; `max_atoms`: atoms per engine sub-batch (whole
     displaced supercells of one structure; a supercell larger than it is evaluated alone); `max_qpoints`: q-points per
-    dynamical-matrix launch.  A structure's results are bitwise the same alone or in any batch for a given `max_atoms`; a different
+    dynamical-matrix launch; `eigensolver`: "embedding" (the default: `torch.linalg.eigvalsh` on the real embedding) or "jacobi"
+    (`frequencies` through the library's batched Hermitian solver where 3n <= EIGH_MAX_N, the embedding beyond).  A structure's results are bitwise the same alone or in any batch for a given `max_atoms`; a different
     `max_atoms` can change the engine's sub-batches and so the last bits of its forces."""
 
     def __init__(self, model: Gradient, delta: float = 0.01, asr: bool = True, max_atoms: int = 200_000, max_qpoints: int = 4096,
-                 cutoff_frequency: float = 1e-3, skin: float = 0.5, device="cuda"):
+                 cutoff_frequency: float = 1e-3, skin: float = 0.5, device="cuda", eigensolver: str = "embedding"):
         super().__init__(model, skin, device)
+        self.eigensolver = _check_eigensolver(eigensolver)
         self.delta, self.asr = positive("delta", delta), boolean("asr", asr)
         self.max_atoms, self.max_qpoints = integer("max_atoms", max_atoms, 1), integer("max_qpoints", max_qpoints, 1)
         cutoff_frequency = float(cutoff_frequency)
@@ -325,4 +476,4 @@ class Phonons(Driver):
         self.forces = forces   # (the displaced batch's forces, kept for inspection)
         return [PhononResult(st, s, self.asr, self.max_qpoints, self.cutoff_frequency, res_f[s],
                              phi[int(st.pair_offsets[s]):int(st.pair_offsets[s + 1])], sums[int(st.unit_offsets[s]):int(st.unit_offsets[s + 1])],
-                             int(bad[s])) for s in range(st.S)]
+                             int(bad[s]), self.eigensolver) for s in range(st.S)]
