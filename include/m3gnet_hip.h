@@ -528,6 +528,64 @@ int m3g_dyn_step(const m3g_dyn_params* params, int64_t n_atoms, int64_t n_struct
  * NULL.  Waits for the stream. */
 int m3g_dyn_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes, int32_t* host_flags, int64_t* host_steps,
                  double* host_vel, void* stream);
+/* Byte offsets, inside a state buffer of these sizes, of the masses [N] and the velocities [N,3] (fp64): a device-side reader (the
+ * trajectory sampler below) takes the integrator's velocities without a copy.  Between two m3g_dyn_step calls they are the
+ * half-step velocities of the step under way; after a finish_only call the full-step ones. */
+int m3g_dyn_state_view(int64_t n_atoms, int64_t n_structs, size_t* mass_offset, size_t* velocity_offset);
+
+/* ---- trajectory observables: RDF, MSD and VACF accumulated on the device (csrc/m3g_trajectory.hip) ---------------------------------
+ * Fed one frame per m3g_traj_sample (from the MD loop, or any frames): per structure and species pair (a <= b) the INTEGER histogram
+ * of minimum-image pair distances below r_max in rdf_bins bins (unordered pairs i < j; bin = (int)(r rdf_bins / r_max) taken only
+ * where r < r_max, so a non-finite distance is counted nowhere), the sum of the cell volumes, and over a ring of the last n_lags
+ * sampled frames the sums, per species a and lag l, of |r_i(now) - r_i(now - l)|^2 and v_i(now) . v_i(now - l) over the atoms of
+ * species a, with the number of samples that contributed to lag l.  Division by atom counts and by lag_count is the caller's.
+ * The minimum image comes from rounding the fractional difference (fp64): exact for every pair closer than half the smallest
+ * perpendicular width w_min = V / max |a_j x a_k| of the cell; a sample taken with r_max > w_min / 2 in the CURRENT cell of a
+ * structure sets M3G_TRAJ_RDF_RANGE in its flags (compared with a relative slack of 1e-12, for the rounding of w_min itself).
+ * With remove_com the mass-weighted centre-of-mass position and velocity of the atom's own structure are subtracted from every
+ * stored frame.  Velocities: with `forces` the sampler stores v + kick kappa F / m
+ * (the finish kick of m3g_dyn_step: give the state's velocities -- m3g_dyn_state_view -- and the forces BEFORE the m3g_dyn_step
+ * call of the same positions, with kick = dt / 2, or 0 before the first step); without forces, `vel` as given.
+ * No float atomics: integer counts, fixed-order sums; every number is bitwise the same alone or in any batch. */
+typedef struct {
+  int64_t n_atoms;       /* N */
+  int64_t n_structs;     /* S */
+  int32_t max_species;   /* 1 .. 8: species indices are local, 0 .. max_species - 1 */
+  int32_t rdf_bins;      /* 0 (no RDF) .. 4096 */
+  int32_t n_lags;        /* 0 (no correlations) .. 4096: ring of n_lags frames, n_lags * N * 48 bytes */
+} m3g_traj_sizes;
+typedef struct {
+  double r_max;          /* A, finite and > 0 when rdf_bins > 0 */
+  int32_t remove_com;    /* 0 / 1 */
+} m3g_traj_params;
+#define M3G_TRAJ_RDF_RANGE 1   /* a sample saw r_max above half the smallest perpendicular width of the structure's cell */
+/* Sizes outside their limits, or rdf_bins == n_lags == 0 -> M3G_ERR_VALUE.  The size follows from `sizes` alone (no offsets), so the
+ * table of tile pairs (24 B each) and the grid of the RDF launch take the most pairs any batch of these sizes can have: t (t + 1) / 2
+ * + S - 1 with t = ceil(N / 256) + 1, reached when one structure holds nearly every atom.  Batches of many small structures launch
+ * workgroups that return at once; one structure of 10^6 atoms has 7.6e6 pairs, 183 MB of table (beside a ring of 48 MB per lag). */
+int m3g_traj_state_bytes(const m3g_traj_sizes* sizes, size_t* bytes);
+/* HOST host_offsets [S+1] (int64, as m3g_dyn_init), host_species [N] (int32, 0 .. max_species - 1), host_masses [N] (amu, > 0).
+ * Uploads the tables (the chunk table and the table of 256-atom tile pairs the RDF launch runs over) and zeroes the accumulators.
+ * Everything is checked on the host before any HIP call -> M3G_ERR_VALUE; a short state buffer -> M3G_ERR_SIZE.  Waits for the
+ * stream. */
+int m3g_traj_init(const m3g_traj_sizes* sizes, const m3g_traj_params* params, const int64_t* host_offsets, const int32_t* host_species,
+                  const double* host_masses, void* state, size_t state_bytes, void* stream);
+/* One sample: pos [N,3] fp64, lattice [S,3,3] fp64 (may be NULL when rdf_bins == 0), vel [N,3] fp64 (may be NULL when n_lags == 0),
+ * forces [N,3] f32 or NULL, all DEVICE.  One launch for the RDF and three (four with remove_com) for the correlations, whatever S;
+ * the ring position and the sample counts live in the state buffer: no allocation, copy or wait, capture-safe. */
+int m3g_traj_sample(const m3g_traj_sizes* sizes, const m3g_traj_params* params, void* state, size_t state_bytes, const double* pos,
+                    const double* lattice, const double* vel, const float* forces, double kick, void* stream);
+/* The accumulators to HOST memory; every output may be NULL: hist [S, P, rdf_bins] uint64 with P = max_species (max_species + 1) / 2,
+ * pair (a <= b) in row-major upper-triangle order; msd, vacf [S, max_species, n_lags] fp64; lag_count [S, n_lags] int64; n_samples [S]
+ * int64; volume_sum [S] fp64; flags [S] int32 (M3G_TRAJ_*).  Waits for the stream. */
+int m3g_traj_read(const m3g_traj_sizes* sizes, const void* state, size_t state_bytes, uint64_t* host_hist, double* host_msd,
+                  double* host_vacf, int64_t* host_lag_count, int64_t* host_n_samples, double* host_volume_sum, int32_t* host_flags,
+                  void* stream);
+/* The stored frame `lag` samples back (0: the last sample; < n_lags and < the samples taken, else M3G_ERR_VALUE) to HOST memory:
+ * host_pos, host_vel [N,3] fp64 -- what the correlations are formed from: the full-step velocities, centre of mass removed where
+ * asked for.  Waits for the stream. */
+int m3g_traj_frame(const m3g_traj_sizes* sizes, const void* state, size_t state_bytes, int32_t lag, double* host_pos, double* host_vel,
+                   void* stream);
 
 /* ---- batched nudged elastic band: climbing-image NEB force projection (csrc/m3g_neb.hip) ----------------------------------------
  * Replaces ASE's NEB.get_forces (NEB(images, k, climb, method="improvedtangent"), the forces an ASE optimiser drives on the host, one
@@ -786,7 +844,10 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              * 10: m3g_ph_* (batched finite-displacement phonons: displaced supercells, force constants, dynamical matrices);
                              * 11: m3g_el_* (batched finite-strain elastic constants and Birch-Murnaghan equation of state: deformed copies, both fits);
                              *     additive, same version: m3g_eigh_batched (batched Hermitian Jacobi eigensolver), m3g_ph_dynmat_gradient,
-                             *     m3g_ph_group_velocities (phonon eigenvectors and group velocities) */
+                             *     m3g_ph_group_velocities (phonon eigenvectors and group velocities);
+                             *     additive, same version: m3g_traj_state_bytes / _init / _sample / _read / _frame (trajectory observables) and
+                             *     m3g_dyn_state_view -- new exports only: no existing struct, constant or call changes, so a caller built
+                             *     against 11 runs unchanged */
 
 #ifdef __cplusplus
 }

@@ -270,6 +270,14 @@ extern "C" int m3g_dyn_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* b
   return M3G_OK;
 }
 
+extern "C" int m3g_dyn_state_view(int64_t n_atoms, int64_t n_structs, size_t* mass_offset, size_t* velocity_offset) {
+  if (!mass_offset || !velocity_offset || !batch_sizes_ok(n_atoms, n_structs)) { set_error("m3g_dyn_state_view: null argument or bad sizes"); return M3G_ERR_VALUE; }
+  const DynLayout L = dyn_layout(n_atoms, n_structs);
+  *mass_offset = L.mass;
+  *velocity_offset = L.v;
+  return M3G_OK;
+}
+
 extern "C" int m3g_dyn_init(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
                             const double* host_temperatures, const uint64_t* host_seeds, const double* vel, void* state, size_t state_bytes,
                             void* stream_) {

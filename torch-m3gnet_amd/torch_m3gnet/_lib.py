@@ -82,6 +82,18 @@ EIGH_SWEEPS_MASK, EIGH_NONFINITE, EIGH_NOT_CONVERGED = 0xff, 0x100, 0x200    # M
 PH_THZ, PH_GV_MAX_N, PH_GV_MAX_SET = 15.63330423985619, 256, 16              # M3G_PH_THZ, M3G_PH_GV_MAX_N, M3G_PH_GV_MAX_SET
 
 
+class M3GTrajSizes(C.Structure):   # m3g_traj_sizes
+    _fields_ = [("n_atoms", C.c_int64), ("n_structs", C.c_int64), ("max_species", C.c_int32), ("rdf_bins", C.c_int32),
+                ("n_lags", C.c_int32)]
+
+
+class M3GTrajParams(C.Structure):   # m3g_traj_params
+    _fields_ = [("r_max", C.c_double), ("remove_com", C.c_int32)]
+
+
+TRAJ_RDF_RANGE, TRAJ_MAX_SPECIES, TRAJ_MAX_BINS, TRAJ_MAX_LAGS = 1, 8, 4096, 4096   # M3G_TRAJ_RDF_RANGE and the limits of m3g_traj_sizes
+
+
 class M3GPhSizes(C.Structure):   # m3g_ph_sizes
     _fields_ = [("n_structs", C.c_int64), ("n_unit_atoms", C.c_int64), ("n_super_atoms", C.c_int64), ("n_pairs", C.c_int64)]
 
@@ -188,6 +200,15 @@ SYMBOLS = {
     "m3g_dyn_step": (C.c_int, [C.POINTER(M3GDynParams), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "m3g_dyn_read": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_dyn_state_view": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "m3g_traj_state_bytes": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(C.c_size_t)]),
+    "m3g_traj_init": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(M3GTrajParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_size_t, C.c_void_p]),
+    "m3g_traj_sample": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(M3GTrajParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "m3g_traj_read": (C.c_int, [C.POINTER(M3GTrajSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_traj_frame": (C.c_int, [C.POINTER(M3GTrajSizes), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_neb_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     "m3g_neb_init": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -27,6 +27,7 @@ from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
 from .data.md import VerletGraph
 from .nn.modules import Gradient
+from .trajectory import TrajectoryObservables, traj_sample
 
 KAPPA = 9.648533215665e-3    # A/fs^2 per eV/(A amu)
 KB = 8.617333262e-5          # eV/K
@@ -65,9 +66,11 @@ def structure_seeds(seed, n_structs: int) -> np.ndarray:
 class DynState:
     """MD state of a batch on the device (m3g_dyn_init): masses, velocities (fp64), target temperatures, seeds, flags and step counts.
     `pos` ([N,3] fp64, unwrapped) and `lattice` ([S,3,3] fp64, may be None except in NPT) are the caller's tensors: `dyn_step` moves
-    them IN PLACE (and `lattice32`, their fp32 copy).  `velocities` [N,3] fp64 device: copied.  `offsets`: S + 1 atom offsets, strictly
+    them IN PLACE (and `lattice32`, their fp32 copy).  The `velocities` ARGUMENT [N,3] fp64 device holds the starting velocities: copied.  `offsets`: S + 1 atom offsets, strictly
     increasing.  Parameters in the C ABI's units: dt, taut, taup in fs, friction in 1/fs, pressure in eV/A^3, compressibility in
-    A^3/eV.  `obs` [S,4] (KE eV, T K, P eV/A^3, V A^3) is written by every `dyn_step`."""
+    A^3/eV.  `obs` [S,4] (KE eV, T K, P eV/A^3, V A^3) is written by every `dyn_step`.  The `velocities` ATTRIBUTE is not the
+    argument: it is a live [N,3] fp64 view into the state buffer, the integrator's own velocities on the device (between two
+    `dyn_step` calls the half-step velocities of the step under way), which every `dyn_step` changes."""
 
     def __init__(self, pos: torch.Tensor, lattice: torch.Tensor | None, offsets: Sequence[int], masses, velocities: torch.Tensor,
                  temperatures, seeds, ensemble: str = "nve", dt: float = 1.0, taut: float = 100.0, friction: float = 0.01,
@@ -93,6 +96,9 @@ class DynState:
         self.lib = _lib.load_library()
         self.state = state_tensor(self.lib.m3g_dyn_state_bytes, self.N, self.S, device=self.device)
         self.obs = torch.full((self.S, 4), float("nan"), dtype=torch.float64, device=self.device)
+        mass_at, vel_at = C.c_size_t(), C.c_size_t()
+        _lib.check(self.lib.m3g_dyn_state_view(self.N, self.S, C.byref(mass_at), C.byref(vel_at)))
+        self.velocities = self.state[vel_at.value:vel_at.value + 24 * self.N].view(torch.float64).view(self.N, 3)
         vel = velocities.contiguous()
         with _cuda.on_device(self.device):
             _lib.check(self.lib.m3g_dyn_init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, self.masses.ctypes.data,
@@ -169,13 +175,17 @@ class MolecularDynamics(Driver):
                     pressure=self.pressure / EV_PER_A3_IN_GPA, taup=self.taup, compressibility=beta, fix_com=self.fix_com)
 
     def run(self, lattices: Sequence, positions: Sequence, atomic_numbers: Sequence, steps: int, velocities: Sequence | None = None,
-            masses: Sequence | None = None, loginterval: int = 10) -> list:
+            masses: Sequence | None = None, loginterval: int = 10, observables: TrajectoryObservables | None = None) -> list:
         """Integrate every structure (lattices: [3,3] rows = lattice vectors, positions: [n_s,3] Cartesian, atomic_numbers: [n_s])
         for `steps` steps.  velocities: [n_s,3] A/fs per structure (default: Maxwell-Boltzmann at the temperature, zero momentum);
         masses: [n_s] amu per structure (default: standard atomic weights).  Returns one dict per structure: positions (unwrapped),
         velocities, lattice, total_energy, forces, stresses (pair virial) at the final step, n_steps, error (its forces became
         non-finite: it was stopped where it stood), and `log`: arrays step, e_pot, ke (eV), t (K), p (GPa), v (A^3) every
-        `loginterval` steps and at the last one."""
+        `loginterval` steps and at the last one.  observables: a `TrajectoryObservables`; the trajectory is then sampled on the
+        device before the integrator call of every `sample_interval`-th step (positions, forces and velocities are synchronous only
+        there: the sampler completes the half-step velocities with the finish kick itself) and every dict gains "observables"."""
+        if observables is not None and not isinstance(observables, TrajectoryObservables):
+            raise TypeError(f"observables must be a TrajectoryObservables; got {type(observables).__name__}")
         steps, loginterval = integer("steps", steps, 0), integer("loginterval", loginterval, 1)
         lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
         S = len(z)
@@ -202,10 +212,13 @@ class MolecularDynamics(Driver):
         npt = self.ensemble == "npt_berendsen"
         dyn = DynState(pos_t, lat64, offsets, np.concatenate(m), torch.tensor(np.concatenate(vel), device=vg.device), temps, seeds,
                        **self._params())
+        traj = observables.begin(lat, z, m, vg.device) if observables is not None else None
         log = {key: [] for key in ("step", "e_pot", "ke", "t", "p", "v")}
         out = None
         for k in range(steps + 1):
             out = vg.step(model, pos_t)   # waits for the skin test (the previous dyn_step has been queued before it)
+            if traj is not None and k % observables.sample_interval == 0:
+                traj_sample(traj, pos_t, lat64, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
             dyn_step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=(k == steps))
             if k % loginterval == 0 or k == steps:   # (host copies on log steps only)
                 obs = dyn.obs.cpu().numpy()
@@ -226,4 +239,7 @@ class MolecularDynamics(Driver):
             res.append({"positions": p_host[a:b].copy(), "velocities": st["v"][a:b].copy(), "lattice": l_host[s].copy(),
                         "total_energy": float(e[s]), "forces": f[a:b].copy(), "stresses": sv[s].copy(), "n_steps": int(st["n_steps"][s]),
                         "error": bool(st["flags"][s] & _lib.DYN_ERROR), "log": {key: val[s].copy() for key, val in logs.items()}})
+        if traj is not None:
+            for r, obs in zip(res, observables.results(traj, self.timestep)):
+                r["observables"] = obs
         return res
