@@ -41,6 +41,34 @@ def test_stamped_fused_reverse_is_bit_identical_and_writes_stamps():
         assert torch.equal(out[k], v), k
 
 
+def test_stamps_switched_on_under_graph_replay_are_not_served_the_unstamped_graph():
+    """Every option is part of the key of a captured launch sequence.  With graph_replay on, switching "stamps" on between two calls on
+    identical buffers must capture anew: the first call's graph holds the unstamped kernel and no stamp buffer, and replaying it leaves
+    the buffer at zero.  The stamped kernel is the shipped kernel plus s_memtime reads: same forces, bit for bit."""
+    from torch_m3gnet import _lib
+    from torch_m3gnet.data import MaterialGraphKey as K
+    from torch_m3gnet.model.build import build_model
+
+    torch.manual_seed(0)
+    model = build_model(5.0, 4.0, 3, 3, 95, 64, 3).cuda()
+    eng = model.engine
+    g = fcc_cu_graph(2, 2, 2).to("cuda")
+    eng.set_option("graph_replay", 1)
+    try:
+        eng.set_precision("f16x3")
+        f0 = model(g)[K.FORCES].clone()
+        eng.set_option("stamps", 3)
+        f1 = model(g)[K.FORCES].clone()   # (same graph object, engine-owned outputs: the buffers of the first call)
+        torch.cuda.synchronize()
+        buf = np.zeros(256 * 16 * 12, dtype=np.uint64)
+        _lib.check(eng.lib.m3g_debug_read_stamps(eng.plan, buf.ctypes.data))
+        assert buf.any()
+        assert torch.equal(f1, f0)
+    finally:
+        eng.set_option("stamps", 0)
+        eng.set_option("graph_replay", 0)
+
+
 def test_readout_f16_option_agrees_with_the_exact_readout():
     """f16x3 mode: the readout layers run on exact-fp32 chains by default; option readout_f16 = 1 moves them to scaled two-part fp16
     chains (22-24 bits per product).  On a well-conditioned cell both give the same energies and forces to fp32 rounding."""

@@ -1,10 +1,12 @@
 // C-ABI entry points of libm3gnet_hip.so: plan (weights + constants), workspace carving and the
 // orchestration of the energy/force pipeline.  See include/m3gnet_hip.h for the contract.
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 
 #include "m3g_internal.h"
 
@@ -139,8 +141,7 @@ static void pack_mlp(std::vector<float>& blob, const MlpW& m, const m3g_plan& p,
   put_n(blob, m.wl, kRP, wl, D, R, 0, R);
 }
 
-Work work_carve(const Consts& c, bool mfma, int save_acts, int64_t N, int64_t E, int64_t T, int64_t S, void* base) {
-  (void)T;
+Work work_carve(int B, const StepPath& path, int64_t N, int64_t E, int64_t S, void* base) {
   Work w{};
   char* p = (char*)base;
   size_t off = 0;
@@ -148,22 +149,22 @@ Work work_carve(const Consts& c, bool mfma, int save_acts, int64_t N, int64_t E,
   size_t e = (size_t)E, n = (size_t)N;
   w.u = take(e * 3); w.d = take(e); w.h = take(e * kRP); w.hp = take(e * kRP);
   w.q = take(e * kCP); w.qp = take(e * kCP); w.fc3 = take(e); w.fc3p = take(e);
-  for (int b = 0; b <= c.B; ++b) w.x[b] = take(n * kDP);
-  for (int b = 0; b < c.B; ++b) w.v[b] = take(n * kCP);
-  for (int b = 0; b < c.B; ++b) w.m[b] = take(e * kCP);
+  for (int b = 0; b <= B; ++b) w.x[b] = take(n * kDP);
+  for (int b = 0; b < B; ++b) w.v[b] = take(n * kCP);
+  for (int b = 0; b < B; ++b) w.m[b] = take(e * kCP);
   w.dx = take(n * kDP); w.dx2 = take(n * kDP);
   w.dm = take(e * kCP); w.g = take(e * kCP); w.dg = take(e * kCP);
   w.dh = take(e * kRP); w.dd = take(e); w.du = take(e * 3); w.dp1 = take(e * 4 * kDP); w.dr = take(e * 3);
   const size_t tiles16 = (e + 15) / 16;
-  if (mfma) {
+  if (path.pipeline == kPipeMfma) {
     // fused MFMA path: per-block edge-feature images and node tables; the reverse pass recomputes every activation
-    for (int b = 0; b <= c.B; ++b) w.e_blk[b] = take(tiles16 * 1024);
-    if (save_acts >= 1) for (int b = 0; b < c.B; ++b) w.p1_blk[b] = take(tiles16 * 2 * 2048);
-    if (save_acts >= 2) for (int b = 0; b < c.B; ++b) w.p2_blk[b] = take(tiles16 * 2 * 2048);
-    for (int b = 0; b < c.B; ++b) { w.TAb[b] = take(n * 4 * kDP); w.TBb[b] = take(n * 4 * kDP); }
+    for (int b = 0; b <= B; ++b) w.e_blk[b] = take(tiles16 * 1024);
+    if (path.saved_acts >= 1) for (int b = 0; b < B; ++b) w.p1_blk[b] = take(tiles16 * 2 * 2048);
+    if (path.saved_acts >= 2) for (int b = 0; b < B; ++b) w.p2_blk[b] = take(tiles16 * 2 * 2048);
+    for (int b = 0; b < B; ++b) { w.TAb[b] = take(n * 4 * kDP); w.TBb[b] = take(n * 4 * kDP); }
     w.de_soa = take(tiles16 * 1024);
     w.dcn = take(tiles16 * 1024);
-    w.dh_parts = take((size_t)(2 * c.B + 1) * e * kRP);
+    w.dh_parts = take((size_t)(2 * B + 1) * e * kRP);
     w.seg_head = take((tiles16 + 1) * 4 * kDP);
     w.seg_first = take((n + 1) * 4 * kDP);
   } else {
@@ -171,9 +172,10 @@ Work work_carve(const Consts& c, bool mfma, int save_acts, int64_t N, int64_t E,
     w.TA = take(n * 4 * kDP); w.TB = take(n * 4 * kDP);
     w.e = take(e * kDP);
     w.de = take(e * kDP);
-    for (int b = 0; b < c.B; ++b) w.act[b] = take(e * 8 * kDP);
+    for (int b = 0; b < B; ++b) w.act[b] = take(e * 8 * kDP);
   }
   // tail scratch for optional outputs the caller did not ask for ([N] per-atom energies, [2 S] sums), then the step's sync words
+  w.tail = p ? (float*)(p + off) : nullptr;
   w.sync = p ? (int32_t*)(p + off + (n + (size_t)S * 2) * sizeof(float)) : nullptr;
   static_assert(kSyncWords <= 64, "the tail scratch reserves 64 words");
   off += align_up((n + (size_t)S * 2 + 64) * sizeof(float));
@@ -198,8 +200,8 @@ struct StageTimer {
   const m3g_plan* p;
   hipStream_t s;
   size_t pair = (size_t)-1;
-  StageTimer(const m3g_plan* plan, int stage, hipStream_t stream) : p(plan), s(stream) {
-    if (!p->profile) return;
+  StageTimer(const m3g_plan* plan, bool profile, int stage, hipStream_t stream) : p(plan), s(stream) {
+    if (!profile) return;
     if (p->ev_used * 2 + 2 > p->ev_pool.size()) {
       hipEvent_t a, b;
       if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
@@ -215,7 +217,7 @@ struct StageTimer {
     if (pair != (size_t)-1) (void)hipEventRecord(p->ev_pool[2 * pair + 1], s);
   }
 };
-#define M3G_STAGE(id) StageTimer _st_##id(plan, id, s)
+#define M3G_STAGE(id) StageTimer _st_##id(plan, mode.profile, id, s)
 
 extern "C" int m3g_profile_enable(m3g_plan* plan, int32_t enable) {
   if (!plan) { set_error("m3g_profile_enable: null plan"); return M3G_ERR_VALUE; }
@@ -279,7 +281,7 @@ extern "C" int m3g_plan_create(const m3g_config* cfg, m3g_plan** out) {
   p->cfg = *cfg;
   // sizes beyond the tiles of the MFMA kernels run on the any-size path (m3g_generic.hip)
   p->generic = cfg->l_max > kLCap || cfg->n_max > kRCap || cfg->embedding_dim > kDP || cfg->num_blocks > kMaxBlocks;
-  if (const char* env = getenv("M3G_EDGE_KERNEL")) p->edge_kernel = atoi(env) != 0 ? 1 : 0;
+  if (const char* env = getenv("M3G_EDGE_KERNEL")) p->opt.edge_kernel = atoi(env) != 0 ? 1 : 0;
   if (!p->generic) p->wl = make_layout(*cfg);
   *out = p;
   return M3G_OK;
@@ -337,122 +339,66 @@ extern "C" int m3g_plan_set_const(m3g_plan* plan, const char* name, const float*
   return M3G_OK;
 }
 
+// ---- options: one table (name, member of Options, accepted range, error text) + a hook for the few with side effects ----
+static int hook_stamps(m3g_plan* plan, int32_t* value) {   // diagnostic: an edge kernel with s_memtime phase stamps
+  if (*value && !plan->d_stamps) {
+    M3G_HIP_CHECK(hipMalloc((void**)&plan->d_stamps, 256 * 16 * 12 * sizeof(unsigned long long)));
+    M3G_HIP_CHECK(hipMemset(plan->d_stamps, 0, 256 * 16 * 12 * sizeof(unsigned long long)));
+  } else if (!*value && plan->d_stamps) {
+    (void)hipFree(plan->d_stamps);
+    plan->d_stamps = nullptr;
+  }
+  *value = *value == 0 ? 0 : *value == 3 ? 3 : *value == 2 ? 2 : 1;   // Options::stamp_target
+  return M3G_OK;
+}
+struct OptionRow {
+  const char* name;
+  int Options::*member;   // nullptr: the hook does everything
+  int lo, hi;             // accepted values ...
+  const char* error;      // ... and what a value outside them answers; nullptr: stored as value != 0 instead
+  int (*hook)(m3g_plan*, int32_t* value);   // runs before the store, may change the value or refuse it
+};
+#define M3G_HOOK(...) [](m3g_plan* plan, int32_t* value) -> int { __VA_ARGS__; return M3G_OK; }
+static const OptionRow kOptions[] = {
+    {"edge_kernel", &Options::edge_kernel, 0, 2, "edge_kernel must be 0 (VALU baseline), 1 (MFMA) or 2 (any-size path)",
+     M3G_HOOK(if (plan->generic && *value != 2) { set_error("this model size only runs on the any-size path (edge_kernel = 2)"); return M3G_ERR_UNSUPPORTED; })},
+    {"precision", &Options::precision, 0, 2,   // both image sets are resident: no recommit needed
+     "precision must be 0 (fp32: exact fp32 MFMA products), 1 (bf16x3 split products) or 2 (f16x3: scaled fp16 split products)", nullptr},
+    {"save_p1", &Options::save_p1, 0, 1, nullptr, nullptr},
+    {"save_p2", &Options::save_p2, 0, 1, nullptr, nullptr},
+    {"rev_kernel", &Options::rev_kernel, 0, 1, "rev_kernel must be 0 (node-MLP + edge-MLP kernel pair) or 1 (fused)", nullptr},
+    // graphs of at most this many 16-edge tiles take the split-tile edge kernels (m3g_edge_small.hip); 0: never.  (small_tiles_fwd, set afterwards, moves the forward threshold alone)
+    {"small_tiles", &Options::small_tiles, 0, INT_MAX, "small_tiles must be >= 0", M3G_HOOK(plan->opt.small_tiles_fwd = *value)},
+    {"small_tiles_fwd", &Options::small_tiles_fwd, 0, INT_MAX, "small_tiles_fwd must be >= 0", nullptr},   // the forward kernel's threshold alone (set after small_tiles)
+    {"dp1_by_dst", &Options::dp1_by_dst, 0, 1, nullptr, nullptr},   // 0: dp1 rows of the exact-fp32 fused path in edge order (A/B tests; bit-identical either way)
+    {"split_node_tiles", &Options::split_node_tiles, 0, INT_MAX, "split_node_tiles must be >= 0", nullptr},
+    {"fuse_node_tb", &Options::fuse_node_tb, 0, 1, nullptr, nullptr},   // 0: three-body reverse and node reverse as two launches (A/B tests; bit-identical either way)
+    {"debug_node_tb_polls", &Options::debug_node_tb_polls, INT_MIN, INT_MAX, nullptr, nullptr},   // test hook: bound (k > 0) or force (k < 0) the time-out of k_node_tb_reverse's wait
+    {"split_tail", &Options::split_tail, 0, 2, "split_tail must be 0 (never), 1 (a single left-over tile) or 2 (one or two)", nullptr},   // 0: every tile whole (A/B tests)
+    {"small_launches", &Options::small_launches, 0, 1, nullptr, nullptr},   // 0: never fuse the small-system launches (A/B tests; results are bit-identical either way)
+    {"graph_replay", &Options::graph_replay, 0, 1, nullptr, M3G_HOOK(if (!*value) drop_graphs(plan))},
+    {"overlap", &Options::overlap, 0, 1, nullptr, nullptr},
+    {"threebody_moments", &Options::tb_moments, 0, 1, nullptr, nullptr},
+    {"legendre_backward", &Options::legendre_ref, 0, 1, "legendre_backward: 0 (exact derivative) or 1 (the reference's backward)", nullptr},
+    {"readout_f16", &Options::readout_f16, 0, 1, nullptr, nullptr},
+    {"stress_mode", &Options::stress_mode, 0, 1, "stress_mode must be 0 (reference: sum pos (x) F / V) or 1 (pair virial)", nullptr},
+    // test hook: the next commit takes the device-move path although the device is the same
+    {"debug_force_move", nullptr, INT_MIN, INT_MAX, nullptr, M3G_HOOK(plan->debug_force_move = *value != 0; plan->committed = false)},
+    {"stamps", &Options::stamp_target, INT_MIN, INT_MAX, nullptr, hook_stamps},
+};
+#undef M3G_HOOK
+
+// (captured graphs need no dropping here: the bytes of Options are part of their key)
 extern "C" int m3g_plan_set_option(m3g_plan* plan, const char* name, int32_t value) {
   if (!plan || !name) { set_error("m3g_plan_set_option: null argument"); return M3G_ERR_VALUE; }
-  if (strcmp(name, "edge_kernel") == 0) {
-    if (value < 0 || value > 2) { set_error("edge_kernel must be 0 (VALU baseline), 1 (MFMA) or 2 (any-size path)"); return M3G_ERR_VALUE; }
-    if (plan->generic && value != 2) { set_error("this model size only runs on the any-size path (edge_kernel = 2)"); return M3G_ERR_UNSUPPORTED; }
-    plan->edge_kernel = value;
-    return M3G_OK;
-  }
-  if (strcmp(name, "precision") == 0) {
-    if (value != kPrecF32 && value != kPrecBf16x3 && value != kPrecF16x3) {
-      set_error("precision must be 0 (fp32: exact fp32 MFMA products), 1 (bf16x3 split products) or 2 (f16x3: scaled fp16 split products)");
-      return M3G_ERR_VALUE;
+  for (const OptionRow& row : kOptions) {
+    if (strcmp(name, row.name) != 0) continue;
+    if (value < row.lo || value > row.hi) {
+      if (row.error) { set_error("%s", row.error); return M3G_ERR_VALUE; }
+      value = 1;   // (any non-zero value switches an on/off option on)
     }
-    plan->precision = value;   // both image sets are resident: no recommit needed
-    return M3G_OK;
-  }
-  if (strcmp(name, "save_p1") == 0) {
-    plan->save_p1 = value != 0;
-    return M3G_OK;
-  }
-  if (strcmp(name, "save_p2") == 0) {
-    plan->save_p2 = value != 0;
-    return M3G_OK;
-  }
-  if (strcmp(name, "rev_kernel") == 0) {
-    if (value != 0 && value != 1) { set_error("rev_kernel must be 0 (node-MLP + edge-MLP kernel pair) or 1 (fused)"); return M3G_ERR_VALUE; }
-    plan->rev_kernel = value;
-    return M3G_OK;
-  }
-  if (strcmp(name, "small_tiles") == 0) {   // graphs of at most this many 16-edge tiles take the split-tile edge kernels (m3g_edge_small.hip); 0: never
-    if (value < 0) { set_error("small_tiles must be >= 0"); return M3G_ERR_VALUE; }
-    plan->small_tiles = value;
-    plan->small_tiles_fwd = value;   // (small_tiles_fwd, set afterwards, moves the forward kernel's threshold alone)
-    drop_graphs(plan);
-    return M3G_OK;
-  }
-  if (strcmp(name, "small_tiles_fwd") == 0) {   // the forward kernel's threshold alone (set after small_tiles)
-    if (value < 0) { set_error("small_tiles_fwd must be >= 0"); return M3G_ERR_VALUE; }
-    plan->small_tiles_fwd = value;
-    drop_graphs(plan);
-    return M3G_OK;
-  }
-  if (strcmp(name, "dp1_by_dst") == 0) {   // 0: dp1 rows of the exact-fp32 fused path in edge order (A/B tests; bit-identical either way)
-    plan->dp1_by_dst = value != 0;
-    drop_graphs(plan);
-    return M3G_OK;
-  }
-  if (strcmp(name, "split_node_tiles") == 0) {
-    if (value < 0) { set_error("split_node_tiles must be >= 0"); return M3G_ERR_VALUE; }
-    plan->split_node_tiles = value;
-    drop_graphs(plan);
-    return M3G_OK;
-  }
-  if (strcmp(name, "fuse_node_tb") == 0) {   // 0: three-body reverse and node reverse as two launches (A/B tests; bit-identical either way)
-    plan->fuse_node_tb = value != 0;
-    drop_graphs(plan);
-    return M3G_OK;
-  }
-  if (strcmp(name, "debug_node_tb_polls") == 0) {   // test hook: bound (k > 0) or force (k < 0) the time-out of k_node_tb_reverse's in-launch wait
-    plan->debug_node_tb_polls = value;
-    drop_graphs(plan);
-    return M3G_OK;
-  }
-  if (strcmp(name, "split_tail") == 0) {   // 0: the persistent reverse kernel runs every tile whole (A/B tests; forward outputs bit-identical either way)
-    if (value < 0 || value > 2) { set_error("split_tail must be 0 (never), 1 (a single left-over tile) or 2 (one or two)"); return M3G_ERR_VALUE; }
-    plan->split_tail = value;
-    drop_graphs(plan);
-    return M3G_OK;
-  }
-  if (strcmp(name, "small_launches") == 0) {   // 0: never fuse the small-system launches (A/B tests; results are bit-identical either way)
-    plan->small_launches = value != 0;
-    drop_graphs(plan);
-    return M3G_OK;
-  }
-  if (strcmp(name, "graph_replay") == 0) {
-    plan->graph_replay = value != 0;
-    if (!plan->graph_replay) drop_graphs(plan);
-    return M3G_OK;
-  }
-  if (strcmp(name, "overlap") == 0) {
-    plan->overlap = value != 0;
-    return M3G_OK;
-  }
-  if (strcmp(name, "threebody_moments") == 0) {
-    plan->tb_moments = value != 0;
-    return M3G_OK;
-  }
-  if (strcmp(name, "legendre_backward") == 0) {
-    if (value != 0 && value != 1) { set_error("legendre_backward: 0 (exact derivative) or 1 (the reference's backward)"); return M3G_ERR_VALUE; }
-    plan->legendre_ref = value != 0;
-    drop_graphs(plan);
-    return M3G_OK;
-  }
-  if (strcmp(name, "readout_f16") == 0) {
-    plan->readout_f16 = value != 0;
-    return M3G_OK;
-  }
-  if (strcmp(name, "stress_mode") == 0) {
-    if (value != 0 && value != 1) { set_error("stress_mode must be 0 (reference: sum pos (x) F / V) or 1 (pair virial)"); return M3G_ERR_VALUE; }
-    plan->stress_mode = value;
-    return M3G_OK;
-  }
-  if (strcmp(name, "debug_force_move") == 0) {   // test hook: the next commit takes the device-move path although the device is the same
-    plan->debug_force_move = value != 0;
-    plan->committed = false;
-    return M3G_OK;
-  }
-  if (strcmp(name, "stamps") == 0) {  // diagnostic: forward edge kernel with s_memtime phase stamps
-    plan->stamp_target = value == 3 ? 2 : value == 2 ? 1 : 0;   // 1: forward edge kernel, 2: reverse edge-MLP kernel, 3: fused reverse kernel (f16x3)
-    if (value && !plan->d_stamps) {
-      M3G_HIP_CHECK(hipMalloc((void**)&plan->d_stamps, 256 * 16 * 12 * sizeof(unsigned long long)));
-      M3G_HIP_CHECK(hipMemset(plan->d_stamps, 0, 256 * 16 * 12 * sizeof(unsigned long long)));
-    } else if (!value && plan->d_stamps) {
-      (void)hipFree(plan->d_stamps);
-      plan->d_stamps = nullptr;
-    }
+    if (row.hook) { int rc = row.hook(plan, &value); if (rc) return rc; }
+    if (row.member) plan->opt.*row.member = value;
     return M3G_OK;
   }
   set_error("unknown option '%s'", name);
@@ -483,7 +429,7 @@ extern "C" int m3g_plan_commit(m3g_plan* plan) {
       if (plan->d_weights) { (void)hipFree(plan->d_weights); plan->d_weights = nullptr; }
       free_mfma_images(plan);
       generic_free(plan);
-      if (plan->d_stamps) { (void)hipFree(plan->d_stamps); plan->d_stamps = nullptr; }
+      if (plan->d_stamps) { (void)hipFree(plan->d_stamps); plan->d_stamps = nullptr; plan->opt.stamp_target = 0; }
       release_device_handles(plan);   // the side stream, its events and the profiler's events belong to the old device too
       M3G_HIP_CHECK(hipSetDevice(dev));
       plan->debug_force_move = false;
@@ -493,7 +439,7 @@ extern "C" int m3g_plan_commit(m3g_plan* plan) {
   }
   { int rc = generic_commit(plan); if (rc) return rc; }
   if (plan->generic) {   // no padded blob, no MFMA images: the any-size path reads the raw tensors
-    plan->edge_kernel = 2;
+    plan->opt.edge_kernel = 2;
     plan->committed = true;
     return M3G_OK;
   }
@@ -578,12 +524,15 @@ extern "C" int m3g_plan_commit(m3g_plan* plan) {
   return M3G_OK;
 }
 
+static StepPath plan_step_path(const m3g_plan* plan, int64_t N, int64_t E, int64_t T, int64_t S, int topo_hints, bool forces, bool stresses, bool profile) {
+  const m3g_config& cfg = plan->cfg;
+  return resolve_step_path(plan->opt, ModelDims{cfg.l_max, cfg.n_max, cfg.l_max * cfg.n_max, cfg.num_blocks}, N, E, T, S, topo_hints, forces, stresses, profile);
+}
+
 extern "C" int m3g_workspace_bytes(const m3g_plan* plan, int64_t N, int64_t E, int64_t T, int64_t S, size_t* bytes) {
   if (!plan || !bytes || N < 0 || E < 0 || T < 0 || S < 0) { set_error("m3g_workspace_bytes: bad argument"); return M3G_ERR_VALUE; }
-  if (plan->edge_kernel == 2) { *bytes = generic_workspace_bytes(plan, N, E, T, S); return M3G_OK; }
-  Consts c{};
-  c.B = plan->cfg.num_blocks;
-  *bytes = work_carve(c, plan->edge_kernel == 1, saved_activations(plan), N, E, T, S, nullptr).total_bytes;
+  const StepPath p = plan_step_path(plan, N, E, T, S, 0, true, true, false);   // (the sizes do not depend on the call's outputs)
+  *bytes = p.pipeline == kPipeAnySize ? generic_workspace_bytes(plan, N, E, T, S) : work_carve(plan->cfg.num_blocks, p, N, E, S, nullptr).total_bytes;
   return M3G_OK;
 }
 
@@ -602,6 +551,195 @@ static void drop_graphs(const m3g_plan* plan) {
     if (g.graph) (void)hipGraphDestroy(g.graph);
   }
   plan->graphs.clear();
+}
+
+// ---- one step: checks, resolve_step_path, one work_carve, then the launches the StepPath names ------------------------
+// how a step is enqueued (an argument, not plan state: m3g_count_launches counts the un-profiled sequence of a profiled plan)
+struct RunMode { bool profile; };
+
+struct Step {   // what the enqueue_* pieces share
+  const m3g_plan* plan;
+  const m3g_io* io;
+  const StepPath p;
+  const bool mfma;
+  const Consts& c;
+  const WeightLayout& wl;
+  const float* W;
+  hipStream_t s;
+  RunMode mode;
+  Topo t;
+  Work w;
+  float *ea, *st;   // scaled per-atom energies and per-structure sums: the caller's buffers or the workspace's tail scratch
+  int enqueue_forward() const, enqueue_optional_outputs() const, enqueue_reverse() const;
+};
+
+static int check_call(const m3g_plan* plan, const m3g_io* io) {
+  if (!plan || !io) { set_error("m3g_energy_forces: null argument"); return M3G_ERR_VALUE; }
+  if (!plan->committed) { set_error("m3g_energy_forces: plan parameters not committed"); return M3G_ERR_STATE; }
+  int dev = -1;
+  M3G_HIP_CHECK(hipGetDevice(&dev));
+  if (dev == plan->device) return M3G_OK;
+  set_error("m3g_energy_forces: the plan was committed on device %d but the current device is %d (commit again on this device)", plan->device, dev);
+  return M3G_ERR_STATE;
+}
+
+int Step::enqueue_forward() const {
+  const bool want_f = io->forces != nullptr;
+  {
+    M3G_STAGE(ST_GEOM);
+    // small systems: the geometry stage and block 0's node tables (independent of each other) as two roles of one launch
+    if (p.geom_with_node_pre) launch_geometry_node_pre(plan, c, t, w, io->pos, io->lattice, io->edge_cell_shift, io->atom_types, W + wl.emb, s);
+    else launch_geometry(c, t, io->pos, io->lattice, io->edge_cell_shift, w, s);
+  }
+  {
+    M3G_STAGE(ST_EMBED);
+    if (mfma) {
+      if (c.B == 0) launch_embed_nodes_only(c, W, wl, t, io->atom_types, w, s);   // otherwise block 0's node kernel forms x^0
+      if (!p.fused_rev || c.B == 0) launch_embed_edges_soa(c, W + wl.adj_t, w.h, w.e_blk[0], t.E, s);   // fused path: block 0 forms e0 in its kernels
+    } else {
+      launch_embed(c, W, wl, t, io->atom_types, w, s);
+    }
+  }
+  for (int b = 0; b < c.B; ++b) {
+    {
+      M3G_STAGE(ST_NODE_PRE);
+      // MFMA path: block b > 0 forms x^b = x^(b-1) + per-centre message sums of block b-1 while loading it
+      if (mfma && b == 0 && p.geom_with_node_pre) { /* formed beside the geometry stage */ }
+      else if (mfma) launch_node_pre_mfma(plan, p.node_split, c, t, w, b, b > 0 ? w.x[b - 1] : nullptr, w.x[b], w.v[b], w.TAb[b], w.TBb[b],
+                                          b == 0 ? io->atom_types : nullptr, W + wl.emb, s);
+      else launch_node_pre(c, W, wl.blk[b], t, w, nullptr, w.x[b], w.v[b], w.TA, w.TB, s);
+    }
+    { M3G_STAGE(ST_THREEBODY); launch_threebody(p, c, t, w, w.v[b], w.m[b], s); }
+    M3G_STAGE(ST_EDGE_FWD);
+    if (mfma) {
+      if (p.fwd_split) launch_edge_fwd_split(plan, p, c, t, w, b, s);
+      else launch_edge_block_mfma(plan, p, c, t, w, b, s);
+      (void)ST_NODE_SUM;   // the per-centre sums are consumed by the next node_pre / the readout
+    } else {
+      if (t.N > 0) M3G_HIP_CHECK(hipMemcpyAsync(w.x[b + 1], w.x[b], sizeof(float) * t.N * kDP, hipMemcpyDeviceToDevice, s));
+      launch_edge_block(c, W, wl.blk[b], t, w, b, w.x[b + 1], s);
+    }
+  }
+  M3G_STAGE(ST_READOUT);
+  if (mfma) launch_readout_mfma(plan, p, c, wl, t, io->atom_types, c.B > 0 ? w.x[c.B - 1] : nullptr, w.x[c.B], w, ea, st, io->total_energy, want_f, s);
+  else launch_readout(c, W, wl, t, io->atom_types, nullptr, w.x[c.B], w, ea, st, io->total_energy, want_f, s);
+  return M3G_OK;
+}
+
+int Step::enqueue_optional_outputs() const {
+  M3G_STAGE(ST_OUTPUTS);
+  if (io->node_features) launch_copy_strided(w.x[c.B], kDP, io->node_features, c.D, c.D, t.N, s);
+  if (io->edge_attr) {
+    if (mfma) launch_soa_to_rows(w.e_blk[c.B], io->edge_attr, c.D, c.D, t.E, s);
+    else launch_copy_strided(w.e, kDP, io->edge_attr, c.D, c.D, t.E, s);
+  }
+  if (io->edge_distances && t.E > 0) M3G_HIP_CHECK(hipMemcpyAsync(io->edge_distances, w.d, sizeof(float) * t.E, hipMemcpyDeviceToDevice, s));
+  if (io->edge_weights) launch_copy_strided(w.h, kRP, io->edge_weights, c.R, c.R, t.E, s);
+  if (io->triplet_angles) launch_triplet_angles(t, io->triplet_edge_index, w.u, io->triplet_angles, s);
+  if (io->mid_edge_features)
+    for (int b = 0; b < c.B; ++b)   // the aggregate is kept per active edge: expand to the reference's [E, l_max*n_max]
+      launch_copy_expand_rows(t.act_id, w.m[b], kCP, io->mid_edge_features + (size_t)b * t.E * c.C, c.C, c.C, t.E, s);
+  return M3G_OK;
+}
+
+int Step::enqueue_reverse() const {
+  float *dx_cur = w.dx, *dx_alt = w.dx2;
+  bool dr_done = false;
+  if (!mfma && c.B > 0 && t.E > 0) {
+    M3G_HIP_CHECK(hipMemsetAsync(w.de, 0, sizeof(float) * t.E * kDP, s));
+    M3G_HIP_CHECK(hipMemsetAsync(w.dh, 0, sizeof(float) * t.E * kRP, s));
+  }
+  // dd / du need no clearing: the first three-body reverse of the step writes its (active) rows, and the geometry
+  // reverse reads active rows only
+  for (int b = c.B - 1; b >= 0; --b) {
+    const bool first = b == c.B - 1;
+    switch (p.rev_edge) {
+      case kRevSplit: { M3G_STAGE(ST_EDGE_REV_FUSED); launch_edge_rev_split(plan, p, c, t, w, b, dx_cur, /*de_is_zero=*/first, s); } break;
+      case kRevF32: { M3G_STAGE(ST_EDGE_REV_FUSED); launch_edge_rev_f32(plan, p, c, t, w, b, dx_cur, /*de_is_zero=*/first, s); } break;
+      case kRevFused: { M3G_STAGE(ST_EDGE_REV_FUSED); launch_edge_rev_fused(plan, c, t, w, b, dx_cur, /*de_is_zero=*/first, s); } break;
+      case kRevPair: {
+        { M3G_STAGE(ST_EDGE_REV_NODE); launch_edge_rev_node_mlp(plan, p, c, t, w, b, dx_cur, s); }
+        M3G_STAGE(ST_EDGE_REV);
+        launch_edge_rev_edge_mlp(plan, p, c, t, w, b, dx_cur, /*de_is_zero=*/first, s);
+      } break;
+      default: { M3G_STAGE(ST_EDGE_REV); launch_edge_block_reverse(c, W, wl.blk[b], t, w, b, dx_cur, s); }
+    }
+    bool node_done = false;   // dx_alt holds this block's dL/dx
+    if (p.tail[b] == kTailOverlap) {
+      // the node reverse's dp1 gather needs nothing from the three-body reverse: run that short latency-bound kernel on a
+      // side stream beside it, then add the v-gradient share (which needs its dL/dg) once both are done
+      if (!ensure_side_stream(plan)) { set_error("overlap: could not create the internal stream"); return M3G_ERR_HIP; }
+      M3G_HIP_CHECK(hipEventRecord(plan->ev_fork, s));
+      M3G_HIP_CHECK(hipStreamWaitEvent(plan->side_stream, plan->ev_fork, 0));
+      launch_threebody_reverse(p, c, t, w, w.v[b], first, plan->side_stream, plan->opt.legendre_ref);
+      M3G_HIP_CHECK(hipEventRecord(plan->ev_join, plan->side_stream));
+      launch_node_reverse(c, W, wl.blk[b], t, w, w.v[b], dx_cur, dx_alt, true, p.dp1, /*with_v_term=*/false, s);
+      M3G_HIP_CHECK(hipStreamWaitEvent(s, plan->ev_join, 0));
+      launch_node_reverse_v_term(c, W, wl.blk[b], t, w, w.v[b], dx_alt, s);
+      node_done = true;
+    } else if (p.tail[b] == kTailNodeTb) {
+      // (moment path) three-body reverse and node reverse of the block as two workgroup roles of ONE launch, if they are all resident
+      node_done = launch_node_tb_reverse(c, W, wl.blk[b], t, w, w.v[b], first, dx_cur, dx_alt, p.dp1, b, s, p.tb_hints, plan->opt.debug_node_tb_polls);
+    } else if (p.tail[b] == kTailFinalTb) {
+      launch_threebody_reverse_final(c, t, w, w.v[b], first, w.dh_parts, c.B, s, p.tb_hints);
+      dr_done = true;   // (moment path) the step's last three-body reverse formed dE/dr of every edge as well
+    }
+    if (!node_done && p.tail[b] != kTailFinalTb) {
+      { M3G_STAGE(ST_THREEBODY_REV); launch_threebody_reverse(p, c, t, w, w.v[b], first, s, plan->opt.legendre_ref); }
+      if (b > 0) {  // x^0 is the species embedding: no position dependence, its gradient is never needed
+        M3G_STAGE(ST_NODE_REV);
+        launch_node_reverse(c, W, wl.blk[b], t, w, w.v[b], dx_cur, dx_alt, p.fused_rev, p.dp1, /*with_v_term=*/true, s, p.node_rev_small);
+        node_done = true;
+      }
+    }
+    if (node_done) std::swap(dx_cur, dx_alt);
+  }
+  {
+    M3G_STAGE(ST_EMBED_REV);
+    if (p.fused_rev) { /* block 0's fused reverse kernel already added the embedding's dL/dh share */ }
+    else if (mfma) launch_embed_edges_reverse_soa(W + wl.adj, w.h, w.de_soa, w.dh_parts + (size_t)2 * c.B * t.E * kRP, t.E, s);
+    else launch_embed_reverse(c, W, wl, t, w, s);
+  }
+  M3G_STAGE(ST_GEOM_REV);
+  if (mfma) launch_geometry_reverse(c, t, w, w.dh_parts, p.fused_rev ? c.B : 2 * c.B + 1, io->forces, io->stresses, s, p.gather_virial, io->pos, io->lattice, dr_done);
+  else launch_geometry_reverse(c, t, w, w.dh, 1, io->forces, io->stresses, s);
+  if (p.stress == kStressPair) launch_stress_pair(t, w, io->lattice, io->stresses, s);
+  else if (p.stress == kStressRef) launch_stress(c, t, io->pos, io->lattice, io->forces, io->stresses, s, p.energy_deferred ? ea : nullptr, st, io->total_energy);
+  return M3G_OK;
+}
+
+// the launches of one call on stream `s` (after check_call): never a graph replay, never a look at plan->profile
+static int enqueue_step(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes, hipStream_t s, RunMode mode) {
+  const int64_t N = io->n_atoms, E = io->n_edges, T = io->n_triplets, S = io->n_structs;
+  if (N < 0 || E < 0 || T < 0 || S < 0) { set_error("negative size"); return M3G_ERR_VALUE; }
+  if (!io->total_energy || !io->topo || (N > 0 && (!io->pos || !io->atom_types)) || (S > 0 && !io->lattice) || (E > 0 && !io->edge_cell_shift)) {
+    set_error("m3g_energy_forces: missing required pointer");
+    return M3G_ERR_VALUE;
+  }
+  if (io->triplet_angles && T > 0 && !io->triplet_edge_index) { set_error("triplet_angles requires triplet_edge_index"); return M3G_ERR_VALUE; }
+  const StepPath p = plan_step_path(plan, N, E, T, S, io->topo_hints, io->forces != nullptr, io->stresses != nullptr, mode.profile);
+  if (p.pipeline == kPipeAnySize) return generic_energy_forces(plan, io, workspace, workspace_bytes, s);
+  Step k{plan, io, p, p.pipeline == kPipeMfma, plan->consts, plan->wl, plan->d_weights, s, mode, topo_carve(N, E, T, S, const_cast<void*>(io->topo)),
+         work_carve(plan->cfg.num_blocks, p, N, E, S, workspace)};
+  if (!workspace || workspace_bytes < k.w.total_bytes) { set_error("workspace too small: %zu < %zu", workspace_bytes, k.w.total_bytes); return M3G_ERR_SIZE; }
+  k.ea = io->scaled_atomic_energies ? io->scaled_atomic_energies : k.w.tail;
+  k.st = io->scaled_total_energy ? io->scaled_total_energy : k.w.tail + N;
+  { int rc = k.enqueue_forward(); if (rc) return rc; }
+  { int rc = k.enqueue_optional_outputs(); if (rc) return rc; }
+  if (io->forces) { int rc = k.enqueue_reverse(); if (rc) return rc; }
+  else if (io->stresses) { set_error("stresses require forces"); return M3G_ERR_VALUE; }
+  M3G_HIP_CHECK(hipGetLastError());
+  return M3G_OK;
+}
+
+// the launch sequence of one un-profiled call captured (not executed) on `s`
+static int capture_step(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes, hipStream_t s, hipGraph_t* graph) {
+  M3G_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  const int rc = enqueue_step(plan, io, workspace, workspace_bytes, s, RunMode{false});
+  const hipError_t e = hipStreamEndCapture(s, graph);
+  if (rc != M3G_OK) { if (*graph) (void)hipGraphDestroy(*graph); return rc; }
+  if (e != hipSuccess || !*graph) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return M3G_ERR_HIP; }
+  return M3G_OK;
 }
 
 // replay path of m3g_energy_forces: launches a cached graph, or captures one around the normal enqueue code.
@@ -623,55 +761,48 @@ static int energy_forces_graph(const m3g_plan* plan, const m3g_io* io, void* wor
     }
     return M3G_OK;
   };
-  std::vector<unsigned char> key(sizeof(m3g_io) + sizeof(void*) * 2 + sizeof(size_t) + 4 * sizeof(int));
+  // one key for a captured sequence: everything the launches depend on (every option included: the bytes of Options)
+  std::vector<unsigned char> key(sizeof(m3g_io) + sizeof(void*) * 2 + sizeof(size_t) + sizeof(Options));
   unsigned char* k = key.data();
   memcpy(k, io, sizeof(m3g_io)); k += sizeof(m3g_io);
   memcpy(k, &workspace, sizeof(void*)); k += sizeof(void*);
   memcpy(k, &s, sizeof(void*)); k += sizeof(void*);
   memcpy(k, &workspace_bytes, sizeof(size_t)); k += sizeof(size_t);
-  const int opts[4] = {plan->edge_kernel, plan->rev_kernel + 2 * plan->save_p1 + 4 * plan->save_p2 + 8 * plan->tb_moments + 16 * plan->precision + 64 * plan->readout_f16, plan->stress_mode, plan->overlap};
-  memcpy(k, opts, sizeof(opts));
+  memcpy(k, &plan->opt, sizeof(Options));
   for (auto& g : plan->graphs)
     if (g.key == key) { M3G_HIP_CHECK(hipGraphLaunch(g.exec, s)); return join(); }
   if (plan->graphs.size() >= 8) drop_graphs(plan);   // bounded cache
   m3g_plan::GraphEntry ge;
   ge.key = key;
-  M3G_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  plan->capturing = true;
-  const int rc = m3g_energy_forces(plan, io, workspace, workspace_bytes, (void*)s);
-  plan->capturing = false;
-  hipError_t e = hipStreamEndCapture(s, &ge.graph);
-  if (rc != M3G_OK) { if (ge.graph) (void)hipGraphDestroy(ge.graph); return rc; }
-  if (e != hipSuccess || !ge.graph) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return M3G_ERR_HIP; }
-  e = hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0);
+  { int rc = capture_step(plan, io, workspace, workspace_bytes, s, &ge.graph); if (rc) return rc; }
+  const hipError_t e = hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0);
   if (e != hipSuccess) { (void)hipGraphDestroy(ge.graph); set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e)); return M3G_ERR_HIP; }
   plan->graphs.push_back(ge);
   M3G_HIP_CHECK(hipGraphLaunch(ge.exec, s));
   return join();
 }
 
+extern "C" int m3g_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes,
+                                 void* stream_) {
+  { int rc = check_call(plan, io); if (rc) return rc; }
+  if (plan->opt.graph_replay && !plan->profile && !plan->opt.overlap)
+    return energy_forces_graph(plan, io, workspace, workspace_bytes, (hipStream_t)stream_);
+  return enqueue_step(plan, io, workspace, workspace_bytes, (hipStream_t)stream_, RunMode{plan->profile});
+}
+
 // m3g_count_launches: the call's launch sequence captured (not executed) on a stream of its own, nodes counted by type
 extern "C" int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes, int32_t* kernel_launches,
                                   int32_t* other_operations) {
   if (!plan || !io || !kernel_launches) { set_error("m3g_count_launches: null argument"); return M3G_ERR_VALUE; }
-  if (plan->capturing) { set_error("m3g_count_launches: a capture is in progress"); return M3G_ERR_STATE; }
+  { int rc = check_call(plan, io); if (rc) return rc; }
   hipStream_t s = nullptr;
   M3G_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   hipGraph_t graph = nullptr;
-  hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-  if (e != hipSuccess) { (void)hipStreamDestroy(s); set_error("hipStreamBeginCapture failed: %s", hipGetErrorString(e)); return M3G_ERR_HIP; }
-  const bool profile = plan->profile;
-  plan->capturing = true;
-  plan->profile = false;
-  const int rc = m3g_energy_forces(plan, io, workspace, workspace_bytes, (void*)s);
-  plan->capturing = false;
-  plan->profile = profile;
-  e = hipStreamEndCapture(s, &graph);
+  const int rc = capture_step(plan, io, workspace, workspace_bytes, s, &graph);
   (void)hipStreamDestroy(s);
-  if (rc != M3G_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-  if (e != hipSuccess || !graph) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return M3G_ERR_HIP; }
+  if (rc != M3G_OK) return rc;
   size_t n = 0;
-  e = hipGraphGetNodes(graph, nullptr, &n);
+  hipError_t e = hipGraphGetNodes(graph, nullptr, &n);
   std::vector<hipGraphNode_t> nodes(n);
   if (e == hipSuccess && n) e = hipGraphGetNodes(graph, nodes.data(), &n);
   int kernels = 0, other = 0;
@@ -686,197 +817,6 @@ extern "C" int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* 
   if (e != hipSuccess) { set_error("m3g_count_launches: reading the captured graph failed: %s", hipGetErrorString(e)); return M3G_ERR_HIP; }
   *kernel_launches = kernels;
   if (other_operations) *other_operations = other;
-  return M3G_OK;
-}
-
-// what the reverse edge kernels of this plan hand to k_node_reverse: the fused kernels write 24-bit rows (floating in the bf16x3 mode,
-// fixed point + scales in the f16x3 mode), everything else fp32 rows
-static int dp1_format(const m3g_plan* plan) {
-  if (!fused_reverse(plan)) return kDp1F32;
-  if (dp1_rows_by_dst(plan)) return kDp1F32ByDst;
-  return plan->precision == kPrecBf16x3 ? kDp1Packed : plan->precision == kPrecF16x3 ? kDp1Fixed : kDp1F32;
-}
-
-extern "C" int m3g_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes,
-                                 void* stream_) {
-  if (!plan || !io) { set_error("m3g_energy_forces: null argument"); return M3G_ERR_VALUE; }
-  if (!plan->committed) { set_error("m3g_energy_forces: plan parameters not committed"); return M3G_ERR_STATE; }
-  {
-    int dev = -1;
-    M3G_HIP_CHECK(hipGetDevice(&dev));
-    if (dev != plan->device) {
-      set_error("m3g_energy_forces: the plan was committed on device %d but the current device is %d (commit again on this device)", plan->device, dev);
-      return M3G_ERR_STATE;
-    }
-  }
-  if (plan->graph_replay && !plan->capturing && !plan->profile && !plan->overlap)
-    return energy_forces_graph(plan, io, workspace, workspace_bytes, (hipStream_t)stream_);
-  const int64_t N = io->n_atoms, E = io->n_edges, T = io->n_triplets, S = io->n_structs;
-  if (N < 0 || E < 0 || T < 0 || S < 0) { set_error("negative size"); return M3G_ERR_VALUE; }
-  if (!io->total_energy || !io->topo || (N > 0 && (!io->pos || !io->atom_types)) || (S > 0 && !io->lattice) ||
-      (E > 0 && !io->edge_cell_shift)) {
-    set_error("m3g_energy_forces: missing required pointer");
-    return M3G_ERR_VALUE;
-  }
-  if (io->triplet_angles && T > 0 && !io->triplet_edge_index) { set_error("triplet_angles requires triplet_edge_index"); return M3G_ERR_VALUE; }
-  hipStream_t s = (hipStream_t)stream_;
-  if (plan->edge_kernel == 2) return generic_energy_forces(plan, io, workspace, workspace_bytes, s);
-  const Consts& c = plan->consts;
-  const WeightLayout& wl = plan->wl;
-  const float* W = plan->d_weights;
-  Topo t = topo_carve(N, E, T, S, const_cast<void*>(io->topo));
-  // (0: the list kernels, always valid; the reference's Legendre backward is not linear in the incoming gradient of a triplet,
-  // so the moment sums cannot carry it)
-  const int tb_hints = plan->tb_moments && !plan->legendre_ref ? io->topo_hints : 0;
-  const bool mfma = plan->edge_kernel == 1;
-  const bool fused_rev = fused_reverse(plan);
-  Work w = work_carve(c, mfma, saved_activations(plan), N, E, T, S, nullptr);
-  if (!workspace || workspace_bytes < w.total_bytes) { set_error("workspace too small: %zu < %zu", workspace_bytes, w.total_bytes); return M3G_ERR_SIZE; }
-  w = work_carve(c, mfma, saved_activations(plan), N, E, T, S, workspace);
-  // tail scratch: per-atom energies + per-structure sums when the caller does not want them
-  float* tail = (float*)((char*)workspace + w.total_bytes - align_up(((size_t)N + (size_t)S * 2 + 64) * sizeof(float)));
-  float* ea = io->scaled_atomic_energies ? io->scaled_atomic_energies : tail;
-  float* st = io->scaled_total_energy ? io->scaled_total_energy : tail + N;
-
-  // ---------------- forward ----------------
-  // small systems: the geometry stage and block 0's node tables (independent of each other) as two roles of one launch
-  bool np0_done = false;
-  {
-    M3G_STAGE(ST_GEOM);
-    np0_done = mfma && !plan->profile && launch_geometry_node_pre(plan, c, t, w, io->pos, io->lattice, io->edge_cell_shift, io->atom_types, W + wl.emb, s);
-    if (!np0_done) launch_geometry(c, t, io->pos, io->lattice, io->edge_cell_shift, w, s);
-  }
-  {
-    M3G_STAGE(ST_EMBED);
-    if (mfma) {
-      if (c.B == 0) launch_embed_nodes_only(c, W, wl, t, io->atom_types, w, s);   // otherwise block 0's node kernel forms x^0
-      if (!fused_rev || c.B == 0) launch_embed_edges_soa(c, W + wl.adj_t, w.h, w.e_blk[0], E, s);   // fused path: block 0 forms e0 in its kernels
-    } else {
-      launch_embed(c, W, wl, t, io->atom_types, w, s);
-    }
-  }
-  for (int b = 0; b < c.B; ++b) {
-    {
-      M3G_STAGE(ST_NODE_PRE);
-      // MFMA path: block b > 0 forms x^b = x^(b-1) + per-centre message sums of block b-1 while loading it
-      if (mfma && b == 0 && np0_done) { /* formed beside the geometry stage */ }
-      else if (mfma) launch_node_pre_mfma(plan, c, t, w, b, b > 0 ? w.x[b - 1] : nullptr, w.x[b], w.v[b], w.TAb[b], w.TBb[b],
-                                          b == 0 ? io->atom_types : nullptr, W + wl.emb, s);
-      else launch_node_pre(c, W, wl.blk[b], t, w, nullptr, w.x[b], w.v[b], w.TA, w.TB, s);
-    }
-    { M3G_STAGE(ST_THREEBODY); launch_threebody(c, t, w, w.v[b], w.m[b], s, tb_hints); }
-    if (mfma) {
-      { M3G_STAGE(ST_EDGE_FWD); launch_edge_block_mfma(plan, c, t, w, b, /*for_reverse=*/io->forces != nullptr, s); }
-      (void)ST_NODE_SUM;   // the per-centre sums are consumed by the next node_pre / the readout
-    } else {
-      M3G_STAGE(ST_EDGE_FWD);
-      if (N > 0) M3G_HIP_CHECK(hipMemcpyAsync(w.x[b + 1], w.x[b], sizeof(float) * N * kDP, hipMemcpyDeviceToDevice, s));
-      launch_edge_block(c, W, wl.blk[b], t, w, b, w.x[b + 1], s);
-    }
-  }
-  const bool want_f = io->forces != nullptr;
-  bool energy_deferred = false;
-  {
-    M3G_STAGE(ST_READOUT);
-    // a step that ends with the reference virial forms the per-structure energy sums in that launch (nothing in between reads them)
-    energy_deferred = mfma && plan->small_launches && want_f && io->stresses && plan->stress_mode == 0 && !plan->profile;
-    if (mfma) launch_readout_mfma(plan, c, wl, t, io->atom_types, c.B > 0 ? w.x[c.B - 1] : nullptr, w.x[c.B], w, ea, st, io->total_energy, want_f, s,
-                                  &energy_deferred);
-    else launch_readout(c, W, wl, t, io->atom_types, nullptr, w.x[c.B], w, ea, st, io->total_energy, want_f, s);
-  }
-  StageTimer* st_out = new StageTimer(plan, ST_OUTPUTS, s);
-
-  if (io->node_features) launch_copy_strided(w.x[c.B], kDP, io->node_features, c.D, c.D, N, s);
-  if (io->edge_attr) {
-    if (mfma) launch_soa_to_rows(w.e_blk[c.B], io->edge_attr, c.D, c.D, E, s);
-    else launch_copy_strided(w.e, kDP, io->edge_attr, c.D, c.D, E, s);
-  }
-  if (io->edge_distances && E > 0) M3G_HIP_CHECK(hipMemcpyAsync(io->edge_distances, w.d, sizeof(float) * E, hipMemcpyDeviceToDevice, s));
-  if (io->edge_weights) launch_copy_strided(w.h, kRP, io->edge_weights, c.R, c.R, E, s);
-  if (io->triplet_angles) launch_triplet_angles(t, io->triplet_edge_index, w.u, io->triplet_angles, s);
-  if (io->mid_edge_features)
-    for (int b = 0; b < c.B; ++b)   // the aggregate is kept per active edge: expand to the reference's [E, l_max*n_max]
-      launch_copy_expand_rows(t.act_id, w.m[b], kCP, io->mid_edge_features + (size_t)b * E * c.C, c.C, c.C, E, s);
-  delete st_out;
-
-  // ---------------- reverse ----------------
-  if (want_f) {
-    float* dx_cur = w.dx;
-    float* dx_alt = w.dx2;
-    bool dr_done = false;
-    for (int b = c.B - 1; b >= 0; --b) {
-      if (b == c.B - 1 && E > 0) {
-          if (!mfma) {
-            M3G_HIP_CHECK(hipMemsetAsync(w.de, 0, sizeof(float) * E * kDP, s));
-            M3G_HIP_CHECK(hipMemsetAsync(w.dh, 0, sizeof(float) * E * kRP, s));
-          }
-          // dd / du need no clearing: the first three-body reverse of the step writes its (active) rows, and the geometry
-          // reverse reads active rows only
-      }
-      if (mfma && fused_rev) {
-        M3G_STAGE(ST_EDGE_REV_FUSED);
-        if (plan->precision == kPrecF32) launch_edge_rev_f32(plan, c, t, w, b, dx_cur, /*de_is_zero=*/b == c.B - 1, s);
-        else launch_edge_rev_fused(plan, c, t, w, b, dx_cur, /*de_is_zero=*/b == c.B - 1, s);
-      } else if (mfma) {
-        { M3G_STAGE(ST_EDGE_REV_NODE); launch_edge_rev_node_mlp(plan, c, t, w, b, dx_cur, s); }
-        M3G_STAGE(ST_EDGE_REV);
-        launch_edge_rev_edge_mlp(plan, c, t, w, b, dx_cur, /*de_is_zero=*/b == c.B - 1, s);
-      } else {
-        M3G_STAGE(ST_EDGE_REV);
-        launch_edge_block_reverse(c, W, wl.blk[b], t, w, b, dx_cur, s);
-      }
-      if (b > 0 && fused_rev && plan->overlap && !plan->profile && ensure_side_stream(plan)) {
-        // the node reverse's dp1 gather needs nothing from the three-body reverse: run that short latency-bound kernel on a
-        // side stream beside it, then add the v-gradient share (which needs its dL/dg) once both are done
-        M3G_HIP_CHECK(hipEventRecord(plan->ev_fork, s));
-        M3G_HIP_CHECK(hipStreamWaitEvent(plan->side_stream, plan->ev_fork, 0));
-        launch_threebody_reverse(c, t, w, w.v[b], /*first=*/b == c.B - 1, plan->side_stream, tb_hints, plan->legendre_ref);
-        M3G_HIP_CHECK(hipEventRecord(plan->ev_join, plan->side_stream));
-        launch_node_reverse(c, W, wl.blk[b], t, w, w.v[b], dx_cur, dx_alt, true, /*dp1 format=*/dp1_format(plan), /*with_v_term=*/false, s);
-        M3G_HIP_CHECK(hipStreamWaitEvent(s, plan->ev_join, 0));
-        launch_node_reverse_v_term(c, W, wl.blk[b], t, w, w.v[b], dx_alt, s);
-        float* tmp = dx_cur; dx_cur = dx_alt; dx_alt = tmp;
-      } else if (b > 0 && fused_rev && plan->fuse_node_tb && !plan->profile &&
-                 launch_node_tb_reverse(c, W, wl.blk[b], t, w, w.v[b], /*first=*/b == c.B - 1, dx_cur, dx_alt, dp1_format(plan), b, s, tb_hints, plan->debug_node_tb_polls)) {
-        // (moment path) three-body reverse and node reverse of the block as two workgroup roles of ONE launch
-        float* tmp = dx_cur; dx_cur = dx_alt; dx_alt = tmp;
-      } else if (b == 0 && mfma && fused_rev && plan->small_launches && !plan->profile &&
-                 launch_threebody_reverse_final(c, t, w, w.v[b], /*first=*/b == c.B - 1, w.dh_parts, c.B, s, tb_hints)) {
-        dr_done = true;   // (moment path) the step's last three-body reverse formed dE/dr of every edge as well
-      } else {
-        { M3G_STAGE(ST_THREEBODY_REV); launch_threebody_reverse(c, t, w, w.v[b], /*first=*/b == c.B - 1, s, tb_hints, plan->legendre_ref); }
-        if (b > 0) {  // x^0 is the species embedding: no position dependence, its gradient is never needed
-          M3G_STAGE(ST_NODE_REV);
-          launch_node_reverse(c, W, wl.blk[b], t, w, w.v[b], dx_cur, dx_alt, fused_rev, /*dp1 format=*/dp1_format(plan), /*with_v_term=*/true, s,
-                              /*small=*/plan->small_launches && N <= kFusedSumsMaxAtoms);
-          float* tmp = dx_cur; dx_cur = dx_alt; dx_alt = tmp;
-        }
-      }
-    }
-    {
-      M3G_STAGE(ST_EMBED_REV);
-      if (fused_rev) { /* block 0's fused reverse kernel already added the embedding's dL/dh share */ }
-      else if (mfma) launch_embed_edges_reverse_soa(W + wl.adj, w.h, w.de_soa, w.dh_parts + (size_t)2 * c.B * E * kRP, E, s);
-      else launch_embed_reverse(c, W, wl, t, w, s);
-    }
-    M3G_STAGE(ST_GEOM_REV);
-    // few structures: the force-gather launch ends with the reference virial (one launch less, bit-identical)
-    const bool fuse = mfma && plan->small_launches && plan->stress_mode == 0;
-    bool tail_fused = false;
-    if (mfma) tail_fused = launch_geometry_reverse(c, t, w, w.dh_parts, fused_rev ? c.B : 2 * c.B + 1, io->forces, io->stresses, s, fuse, io->pos, io->lattice,
-                                                   dr_done);
-    else launch_geometry_reverse(c, t, w, w.dh, 1, io->forces, io->stresses, s);
-    if (io->stresses && !tail_fused) {
-      if (plan->stress_mode == 1) launch_stress_pair(t, w, io->lattice, io->stresses, s);
-      else launch_stress(c, t, io->pos, io->lattice, io->forces, io->stresses, s, energy_deferred ? ea : nullptr, st, io->total_energy);
-    } else if (energy_deferred) {
-      launch_energy_sums(c, t, ea, st, io->total_energy, s);   // (the virial was formed by the force gather's last workgroup after all)
-    }
-  } else if (io->stresses) {
-    set_error("stresses require forces");
-    return M3G_ERR_VALUE;
-  }
-  M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }
 

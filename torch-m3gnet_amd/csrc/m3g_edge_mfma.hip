@@ -848,26 +848,27 @@ void launch_embed_edges_reverse_soa(const float* adj, const float* h, const floa
     hipLaunchKernelGGL(k_embed_edges_reverse_soa, dim3((unsigned)((tiles * 64 + 255) / 256)), dim3(256), 0, s, E, tiles, adj, h, de_soa, dh);
 }
 
-// for_reverse = false (energy-only call): nothing is saved for a reverse pass that will not run (2 KB per edge and block of stores)
-void launch_edge_block_mfma(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, bool for_reverse, hipStream_t s) {
+// the persistent forward kernel.  p.fwd_save = 0 in an energy-only call: nothing is saved for a reverse pass that will not run (2 KB
+// per edge and block of stores)
+void launch_edge_block_mfma(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, hipStream_t s) {
   const int64_t tiles = tiles_for(t.E);
   const MfmaFwdLayout L = mfma_fwd_layout();
-  if (tiles > 0 && tiles <= plan->small_tiles_fwd && launch_edge_fwd_split(plan, c, t, w, b, for_reverse, s)) return;
+  const int prec = plan->opt.precision;
   if (tiles > 0) {
-    FwdArgs a{t.E, tiles, plan->d_mfma_fwd[plan->precision] + (size_t)b * L.total, t.src, t.dst, w.h, w.m[b], w.TAb[b], w.TBb[b], t.act_id,
-              w.e_blk[b], w.e_blk[b + 1], w.seg_head, w.seg_first, plan->d_stamps, saves_p1(plan) ? w.p1_blk[b] : nullptr,
-              saves_p2(plan) ? w.p2_blk[b] : nullptr, plan->precision == kPrecF16x3 ? plan->w_scale_inv : 1.f};
+    FwdArgs a{t.E, tiles, plan->d_mfma_fwd[prec] + (size_t)b * L.total, t.src, t.dst, w.h, w.m[b], w.TAb[b], w.TBb[b], t.act_id,
+              w.e_blk[b], w.e_blk[b + 1], w.seg_head, w.seg_first, plan->d_stamps, p.saved_acts >= 1 ? w.p1_blk[b] : nullptr,
+              p.saved_acts == 2 ? w.p2_blk[b] : nullptr, prec == kPrecF16x3 ? plan->w_scale_inv : 1.f};
     dim3 grid(grid_for_tiles(tiles));
-    const bool first = b == 0 && fused_reverse(plan);   // the fused reverse kernel recomputes e0 as well: no embedded-edge image at all
-    const int save = for_reverse ? saved_activations(plan) : 0;   // fp32 mode only (saves_p1 / saves_p2)
+    const bool first = b == 0 && p.fused_rev;   // the fused reverse kernel recomputes e0 as well: no embedded-edge image at all
+    const int save = p.fwd_save;   // fp32 mode only
 #define M3G_FWD_LAUNCH(ST_, FIRST_, PREC_, SAVE_) hipLaunchKernelGGL((k_edge_block_mfma<TBS, ST_, FIRST_, PREC_, SAVE_>), grid, dim3(64 * fwd_waves<PREC_>()), 0, s, a, L)
 #define M3G_FWD_BY_MODE(ST_, FIRST_)                                                               \
-  if (plan->precision == kPrecBf16x3) { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecBf16x3, 0); }             \
-  else if (plan->precision == kPrecF16x3) { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecF16x3, 0); }          \
+  if (prec == kPrecBf16x3) { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecBf16x3, 0); }                        \
+  else if (prec == kPrecF16x3) { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecF16x3, 0); }                     \
   else if (save == 2) { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecF32, 2); }                                \
   else if (save == 1) { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecF32, 1); }                                \
   else { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecF32, 0); }
-    if (plan->d_stamps && plan->stamp_target == 0 && tb_steps_for(c.C) == 3) {
+    if (plan->d_stamps && plan->opt.stamp_target == 1 && tb_steps_for(c.C) == 3) {
       // diagnostic build of the default configuration (same code path as the shipped kernel, block 0 included)
       constexpr int TBS = 3;
       if (first) { M3G_FWD_BY_MODE(true, true); } else { M3G_FWD_BY_MODE(true, false); }
@@ -881,37 +882,40 @@ void launch_edge_block_mfma(const m3g_plan* plan, const Consts& c, const Topo& t
   }
 }
 
-void launch_edge_rev_node_mlp(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
+void launch_edge_rev_node_mlp(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
                               hipStream_t s) {
   (void)c;
   const int64_t tiles = tiles_for(t.E);
   if (tiles == 0) return;
   const MfmaRevLayout L = mfma_rev_layout();
-  const float* img_n = plan->d_mfma_rev[plan->precision] + (size_t)b * L.per_block + L.total_e;
-  const bool saved = saves_p1(plan);
+  const int prec = plan->opt.precision;
+  const float* img_n = plan->d_mfma_rev[prec] + (size_t)b * L.per_block + L.total_e;
+  const bool saved = p.saved_acts >= 1;
   RevArgs an{t.E, tiles, img_n, t.src, t.dst, w.h, w.m[b], dx_new, t.act_id, w.TAb[b], w.TBb[b], w.e_blk[b + 1], nullptr, w.de_soa, w.dcn, 0, w.dm,
              w.dh_parts + (size_t)(2 * b + 1) * t.E * kRP, w.dp1, nullptr, nullptr, nullptr, saved ? w.p1_blk[b] : nullptr, nullptr,
-             plan->precision == kPrecF16x3 ? plan->w_scale_inv : 1.f};
-  if (saved) { M3G_PREC_SWITCH(plan->precision, hipLaunchKernelGGL((k_edge_rev_node_mlp<PREC, true>), dim3(grid_for_tiles(tiles)), dim3(64 * kWavesRev), 0, s, an, L)); }
-  else { M3G_PREC_SWITCH(plan->precision, hipLaunchKernelGGL((k_edge_rev_node_mlp<PREC, false>), dim3(grid_for_tiles(tiles)), dim3(64 * kWavesRev), 0, s, an, L)); }
+             prec == kPrecF16x3 ? plan->w_scale_inv : 1.f};
+  if (saved) { M3G_PREC_SWITCH(prec, hipLaunchKernelGGL((k_edge_rev_node_mlp<PREC, true>), dim3(grid_for_tiles(tiles)), dim3(64 * kWavesRev), 0, s, an, L)); }
+  else { M3G_PREC_SWITCH(prec, hipLaunchKernelGGL((k_edge_rev_node_mlp<PREC, false>), dim3(grid_for_tiles(tiles)), dim3(64 * kWavesRev), 0, s, an, L)); }
 }
 
-void launch_edge_rev_edge_mlp(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
+void launch_edge_rev_edge_mlp(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
                               bool de_is_zero, hipStream_t s) {
   const int64_t tiles = tiles_for(t.E);
   if (tiles == 0) return;
   const MfmaRevLayout L = mfma_rev_layout();
-  const float* img_e = plan->d_mfma_rev[plan->precision] + (size_t)b * L.per_block;
+  const int prec = plan->opt.precision;
+  const bool saved = p.saved_acts >= 1;
+  const float* img_e = plan->d_mfma_rev[prec] + (size_t)b * L.per_block;
   RevArgs ae{t.E, tiles, img_e, t.src, t.dst, w.h, w.m[b], dx_new, t.act_id, w.TAb[b], w.TBb[b], w.e_blk[b], nullptr, w.de_soa, w.dcn,
              de_is_zero ? 1 : 0, w.dm, w.dh_parts + (size_t)(2 * b) * t.E * kRP, w.dp1, plan->d_stamps, nullptr, nullptr,
-             saves_p1(plan) ? w.p1_blk[b] : nullptr, nullptr, plan->precision == kPrecF16x3 ? plan->w_scale_inv : 1.f};
+             saved ? w.p1_blk[b] : nullptr, nullptr, prec == kPrecF16x3 ? plan->w_scale_inv : 1.f};
   dim3 grid(grid_for_tiles(tiles)), block(64 * kWavesRev);
-  if (plan->d_stamps && plan->stamp_target == 1 && tb_steps_for(c.C) == 3 && plan->precision == kPrecBf16x3) {  // diagnostic build
+  if (plan->d_stamps && plan->opt.stamp_target == 2 && tb_steps_for(c.C) == 3 && prec == kPrecBf16x3) {  // diagnostic build
     hipLaunchKernelGGL((k_edge_rev_edge_mlp<3, true>), grid, block, 0, s, ae, L);
     return;
   }
-  if (saves_p1(plan)) { M3G_PREC_SWITCH(plan->precision, M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_rev_edge_mlp<TBS, false, PREC, true>), grid, block, 0, s, ae, L))); }
-  else { M3G_PREC_SWITCH(plan->precision, M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_rev_edge_mlp<TBS, false, PREC, false>), grid, block, 0, s, ae, L))); }
+  if (saved) { M3G_PREC_SWITCH(prec, M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_rev_edge_mlp<TBS, false, PREC, true>), grid, block, 0, s, ae, L))); }
+  else { M3G_PREC_SWITCH(prec, M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_rev_edge_mlp<TBS, false, PREC, false>), grid, block, 0, s, ae, L))); }
 }
 
 void launch_edge_rev_fused(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
@@ -919,14 +923,14 @@ void launch_edge_rev_fused(const m3g_plan* plan, const Consts& c, const Topo& t,
   const int64_t tiles = tiles_for(t.E);
   if (tiles == 0) return;
   const MfmaRevFusedLayout L = mfma_rev_fused_layout();
-  const bool f16 = plan->precision == kPrecF16x3;
+  const bool f16 = plan->opt.precision == kPrecF16x3;
   const float* img = (f16 ? plan->d_mfma_revf_h : plan->d_mfma_revf) + (size_t)b * L.total;
   RevArgs ar{t.E, tiles, img, t.src, t.dst, w.h, w.m[b], dx_new, t.act_id, w.TAb[b], w.TBb[b], w.e_blk[b], w.e_blk[b + 1], w.de_soa, nullptr,
              de_is_zero ? 1 : 0, w.dm, w.dh_parts + (size_t)b * t.E * kRP, w.dp1, plan->d_stamps, w.seg_head, w.seg_first, nullptr, nullptr,
              f16 ? plan->w_scale_inv : 1.f, dp1_scale_of(w.dp1, t.E)};
   constexpr int WV = kWavesRevFused;
   dim3 grid(grid_for_tiles(tiles)), block(64 * WV);
-  if (plan->d_stamps && plan->stamp_target == 2 && f16 && tb_steps_for(c.C) == 3) {   // diagnostic build (tools/stamp_report_fused.py)
+  if (plan->d_stamps && plan->opt.stamp_target == 3 && f16 && tb_steps_for(c.C) == 3) {   // diagnostic build (tools/stamp_report_fused.py)
     if (b > 0) hipLaunchKernelGGL((k_edge_rev_fused<3, true, WV, kPrecF16x3, true>), grid, block, 0, s, ar, L);
     else hipLaunchKernelGGL((k_edge_rev_fused<3, false, WV, kPrecF16x3, true>), grid, block, 0, s, ar, L);
     return;

@@ -281,21 +281,20 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_f32(RevArgs a, MfmaRevF
   }
 }
 
-void launch_edge_rev_f32(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
+void launch_edge_rev_f32(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
                          bool de_is_zero, hipStream_t s) {
   const int64_t tiles = tiles_for(t.E);
   if (tiles == 0) return;
-  if (tiles <= plan->small_tiles && launch_edge_rev_split(plan, c, t, w, b, dx_new, de_is_zero, s)) return;
   const MfmaRevF32Layout L = mfma_rev_f32_layout();
   static_assert(kRevF32Floats * 4 + 16 <= 160 * 1024, "fused fp32 reverse image exceeds the LDS");
   const float* img = plan->d_mfma_revf32 + (size_t)b * L.total;
   RevArgs ar{t.E, tiles, img, t.src, t.dst, w.h, w.m[b], dx_new, t.act_id, nullptr, nullptr, nullptr, nullptr, w.de_soa, nullptr,
              de_is_zero ? 1 : 0, w.dm, w.dh_parts + (size_t)b * t.E * kRP, w.dp1, nullptr, w.seg_head, w.seg_first, w.p1_blk[b],
-             saves_p2(plan) ? w.p2_blk[b] : nullptr, 1.f, nullptr, dp1_rows_by_dst(plan) ? t.in_pos : nullptr, plan->split_tail};
+             p.saved_acts == 2 ? w.p2_blk[b] : nullptr, 1.f, nullptr, p.dp1_by_dst ? t.in_pos : nullptr, p.split_tail};
   static_assert(2 * kRevSplitGroupFloats + kRevSplitTabFloats <= kRevF32Floats, "the split tail's exchange buffers must fit in the image's LDS");
   constexpr int WV = kWavesRevF32;
   dim3 grid(grid_for_tiles(tiles, WV)), block(64 * WV);
-  const bool p2 = saves_p2(plan);
+  const bool p2 = p.saved_acts == 2;
   // (block 0: x^0 has no position dependence, nobody reads its dp1 rows)
 #define M3G_REV_F32_LAUNCH(NEED, P2) M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_rev_f32<TBS, NEED, WV, P2>), grid, block, 0, s, ar, L))
   if (b > 0) { if (p2) { M3G_REV_F32_LAUNCH(true, true); } else { M3G_REV_F32_LAUNCH(true, false); } }

@@ -202,37 +202,34 @@ __global__ void __launch_bounds__(64 * kSplitWaves) __attribute__((amdgpu_waves_
 
 }  // namespace
 
-bool launch_edge_fwd_split(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, bool for_reverse, hipStream_t s) {
+// (exact-fp32 mode, nothing or both layers saved, no stamps: StepPath::fwd_split / kRevSplit)
+void launch_edge_fwd_split(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, hipStream_t s) {
   const int64_t tiles = tiles_for(t.E);
-  if (tiles == 0) return true;
-  const int save = for_reverse ? saved_activations(plan) : 0;
-  if (plan->precision != kPrecF32 || save == 1 || plan->d_stamps) return false;   // (save == 1: an A/B option of the persistent kernels)
+  if (tiles == 0) return;
+  const int save = p.fwd_save;
   const MfmaFwdLayout L = mfma_fwd_layout();
   FwdArgs a{t.E, tiles, plan->d_mfma_fwd[kPrecF32] + (size_t)b * L.total, t.src, t.dst, w.h, w.m[b], w.TAb[b], w.TBb[b], t.act_id,
             w.e_blk[b], w.e_blk[b + 1], w.seg_head, w.seg_first, nullptr, save == 2 ? w.p1_blk[b] : nullptr, save == 2 ? w.p2_blk[b] : nullptr, 1.f};
   const dim3 grid(grid_for_split(tiles)), block(64 * kSplitWaves);
-  const bool first = b == 0 && fused_reverse(plan);
+  const bool first = b == 0 && p.fused_rev;
 #define M3G_FWDS(FIRST_) \
   if (save == 2) { M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_fwd_split<TBS, FIRST_, 2>), grid, block, 0, s, a, L)); } \
   else { M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_fwd_split<TBS, FIRST_, 0>), grid, block, 0, s, a, L)); }
   if (first) { M3G_FWDS(true); } else { M3G_FWDS(false); }
 #undef M3G_FWDS
-  return true;
 }
 
-bool launch_edge_rev_split(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new, bool de_is_zero,
+void launch_edge_rev_split(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new, bool de_is_zero,
                            hipStream_t s) {
   const int64_t tiles = tiles_for(t.E);
-  if (tiles == 0) return true;
-  if (plan->precision != kPrecF32 || !saves_p2(plan) || plan->d_stamps) return false;
+  if (tiles == 0) return;
   const MfmaRevF32Layout L = mfma_rev_f32_layout();
   RevArgs ar{t.E, tiles, plan->d_mfma_revf32 + (size_t)b * L.total, t.src, t.dst, w.h, w.m[b], dx_new, t.act_id, nullptr, nullptr, nullptr, nullptr,
              w.de_soa, nullptr, de_is_zero ? 1 : 0, w.dm, w.dh_parts + (size_t)b * t.E * kRP, w.dp1, nullptr, w.seg_head, w.seg_first, w.p1_blk[b],
-             w.p2_blk[b], 1.f, nullptr, dp1_rows_by_dst(plan) ? t.in_pos : nullptr};
+             w.p2_blk[b], 1.f, nullptr, p.dp1_by_dst ? t.in_pos : nullptr};
   const dim3 grid(grid_for_split(tiles)), block(64 * kSplitWaves);
   if (b > 0) { M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_rev_split<TBS, true>), grid, block, 0, s, ar, L)); }
   else { M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_rev_split<TBS, false>), grid, block, 0, s, ar, L)); }
-  return true;
 }
 
 }  // namespace m3g

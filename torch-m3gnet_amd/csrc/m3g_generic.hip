@@ -501,7 +501,7 @@ static GenConsts gen_consts(const m3g_plan* plan) {
   c.length_scale = (float)cfg.length_scale; c.energy_scale = (float)cfg.energy_scale;
   const double rc = cfg.cutoff / cfg.length_scale, rc3 = cfg.threebody_cutoff / cfg.length_scale;   // model/build.py:34-35
   c.rc = (float)rc; c.rc3 = (float)rc3;
-  c.ref_legendre = plan->legendre_ref ? 1 : 0;
+  c.ref_legendre = plan->opt.legendre_ref ? 1 : 0;
   const float pi_f = (float)M_PI;
   const auto& em = plan->cvals.at("em");
   const auto& dm = plan->cvals.at("dm");
@@ -734,7 +734,7 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
   if (E > 0) hipLaunchKernelGGL(g_geometry_rev, grid1(E), dim3(256), 0, s, E, R, w.u, w.d, w.hp, w.dh, w.dd, w.du, w.dr);
   launch_force_gather(c.length_scale, t, w.dr, io->forces, io->stresses, s);
   if (io->stresses) {
-    if (plan->stress_mode == 1) {
+    if (plan->opt.stress_mode == 1) {
       Work ww{};
       ww.u = w.u; ww.d = w.d; ww.dr = w.dr;
       launch_stress_pair(t, ww, io->lattice, io->stresses, s);

@@ -154,7 +154,8 @@ __global__ void __launch_bounds__(kStructThreads) k_struct_energy(const int32_t*
   __shared__ float part[kStructThreads];
   struct_energy<kStructThreads>(blockIdx.x, struct_ptr, flags, n_atoms, batch, ea, energy_scale, scaled_total, total, part);
 }
-void launch_struct_energy(const Consts& c, const Topo& t, const float* ea, float* scaled_total, float* total, hipStream_t s) {
+// per-structure sums of the scaled atomic energies and total = energy_scale * sum: one launch (fixed order)
+void launch_energy_sums(const Consts& c, const Topo& t, const float* ea, float* scaled_total, float* total, hipStream_t s) {
   if (t.S > 0)
     hipLaunchKernelGGL(k_struct_energy, dim3((unsigned)t.S), dim3(kStructThreads), 0, s, t.struct_ptr, t.flags, t.N, t.batch, ea, c.energy_scale,
                        scaled_total, total);
@@ -213,22 +214,19 @@ void launch_distance_only(float length_scale, const Topo& t, const float* pos, c
   hipLaunchKernelGGL((k_geometry<false, 1, 1>), grid_for(t.E), dim3(256), 0, s, c, a);
 }
 
-// Geometry reverse + force gather.  `fuse_stress`: the force-gather launch also forms the reference virial (its last workgroup,
-// bit-identical to k_struct_stress) when the batch has few structures; returns whether it did (else the caller launches
-// launch_stress / launch_stress_pair).
-bool launch_geometry_reverse(const Consts& c, const Topo& t, const Work& w, const float* dh, int dh_parts, float* forces,
-                             float* stresses, hipStream_t s, bool fuse_stress, const float* pos, const float* lattice, bool dr_done) {
+// Geometry reverse + force gather.  `gather_virial` (StepPath, few structures): the force-gather launch also forms the reference virial
+// (its last workgroup, bit-identical to k_struct_stress); else the caller launches launch_stress / launch_stress_pair.
+void launch_geometry_reverse(const Consts& c, const Topo& t, const Work& w, const float* dh, int dh_parts, float* forces,
+                             float* stresses, hipStream_t s, bool gather_virial, const float* pos, const float* lattice, bool dr_done) {
   const GeomRev g{t.E, w.u, w.d, w.hp, dh, dh_parts, w.dd, w.du, (t.T > 0 && c.B > 0) ? t.act_id : nullptr};
   if (t.E > 0 && !dr_done) hipLaunchKernelGGL(k_geometry_reverse, grid_for(t.E), dim3(256), 0, s, g, w.dr);   // (dr_done: formed by the last three-body reverse)
-  const bool fused = fuse_stress && stresses && w.sync && t.N > 0 && t.N <= kFusedSumsMaxAtoms && t.S > 0 && t.S <= kForceTailMaxStructs;
   if (t.N > 0) {
-    StressTail st{t.S, t.struct_ptr, t.flags, t.batch, pos, lattice, stresses, fused ? w.sync + kSyncForceTail : nullptr};
+    StressTail st{t.S, t.struct_ptr, t.flags, t.batch, pos, lattice, stresses, gather_virial ? w.sync + kSyncForceTail : nullptr};
     hipLaunchKernelGGL(k_force_gather, grid_for(t.N * 16), dim3(256), 0, s, c.length_scale, t.N, t.row_ptr, t.in_ptr, t.in_edge,
-                       w.dr, forces, stresses, (stresses && !fused) ? 6 * t.S : 0, st);
+                       w.dr, forces, stresses, (stresses && !gather_virial) ? 6 * t.S : 0, st);
   } else if (stresses) {
     (void)hipMemsetAsync(stresses, 0, sizeof(float) * 6 * t.S, s);
   }
-  return fused;
 }
 
 // force gather on its own (generic path, m3g_generic.hip): F = -(d E / d r) summed through both CSR lists, / length_scale

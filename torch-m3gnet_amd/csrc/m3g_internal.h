@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/m3gnet_hip.h"
+#include "m3g_step_path.h"
 
 namespace m3g {
 
@@ -17,13 +18,6 @@ constexpr int kLCap = 4;     // l_max <= kLCap
 constexpr int kRCap = 4;     // n_max <= kRCap
 constexpr int kCP = 16;      // padded l_max*n_max
 constexpr int kRP = 4;       // padded n_max
-constexpr int kMaxBlocks = 8;
-// arithmetic of the dense chains (plan option "precision"; m3g_edge_mfma.hip: chain_p)
-constexpr int kPrecF32 = 0;      // v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulate -- the reference's arithmetic (default)
-constexpr int kPrecBf16x3 = 1;   // 3 v_mfma_f32_16x16x32_bf16 products of 2-way bf16 splits per fp32 product, fp32 accumulate
-constexpr int kPrecF16x3 = 2;    // 3 v_mfma_f32_16x16x32_f16 products of 2-way fp16 splits of power-of-two SCALED operands: both parts of
-                                 // an operand together carry 22-24 significant bits (an fp32 value to within its own rounding), fp32 accumulate
-constexpr int kNumPrec = 3;
 
 void set_error(const char* fmt, ...);
 #define M3G_HIP_CHECK(expr)                                                               \
@@ -202,10 +196,8 @@ struct m3g_plan {
   float* d_mfma_revf_h = nullptr;  // the same layout holding fp16 parts of the scaled weights (f16x3 mode)
   float* d_mfma_revf32 = nullptr;  // [num_blocks][MfmaRevF32Layout.total] (fused fp32 reverse kernel)
   float* d_node_img[m3g::kNumPrec] = {nullptr, nullptr, nullptr};   // [num_blocks][kNodeImgFloats]: node-table weights as MFMA A-operand images (k_node_pre_mfma)
-  int precision = m3g::kPrecF32;   // option "precision" (default: exact fp32 MFMA products = the reference's arithmetic; 1 / 2 = the split modes, opt-in)
+  m3g::Options opt;           // every option of m3g_plan_set_option that shapes the step (m3g_step_path.h)
   float w_scale_inv = 1.f;       // f16x3 mode: 1 / (the power of two all chain-image weights were multiplied by), set by pack_mfma_images
-  int save_p1 = 1;               // option "save_p1" (fp32 mode only): 0 = recompute layer 1 in the reverse kernels (A/B tests)
-  int save_p2 = 1;               // option "save_p2" (fp32 mode, fused reverse): 0 = recompute layer 2 in the reverse kernel
   int device = -1;               // HIP device the plan's buffers live on (set by m3g_plan_commit)
   // generic path (m3g_generic.hip): raw state_dict tensors, unpadded, in one device blob; offsets by key
   bool generic = false;          // sizes beyond the MFMA kernels' tiles (or option "edge_kernel" = 2)
@@ -214,28 +206,7 @@ struct m3g_plan {
   float* d_readout_img = nullptr;   // [ReadoutImg::total]: readout MLP weights as exact-fp32 chain images (k_readout_mfma; fp32 and bf16x3 modes)
   float* d_readout_img_h = nullptr; // the same layout as scaled two-part fp16 chain images (f16x3 mode), weights scaled by 1 / ro_w_scale_inv
   float ro_w_scale_inv = 1.f;
-  int small_tiles_fwd = 3072;    // option "small_tiles_fwd": the same threshold for the forward kernel alone (measured: a gain up to ~900 atoms, equal at 1,372)
-  int small_tiles = 1536;        // option "small_tiles": graphs of at most this many 16-edge tiles run the split-tile edge kernels
-                                 // (m3g_edge_small.hip: a tile over the four SIMDs of a CU, operands in registers); 0 = never
-  int dp1_by_dst = 0;            // option "dp1_by_dst": see dp1_rows_by_dst().  Measured on the 10k-atom cell: node reverse 205 -> 207 us, reverse edge kernels
-                                 // 1.012 -> 1.017 ms per step -- the gather of whole 1-KB rows is not what bounds the node reverse; off by default
-  int split_node_tiles = 128;    // option "split_node_tiles": 16-atom tiles (2,048 atoms) up to which the node tables and the readout take their split forms
-                                 // (m3g_node_mfma.hip; measured at 625 tiles: node tables 58 -> 85 us, readout 28 -> 36 us per step -- not beyond)
-  int fuse_node_tb = 1;          // option "fuse_node_tb": three-body reverse (moment path) + node reverse of a block as two workgroup roles of
-                                 // one launch (k_node_tb_reverse, m3g_threebody.hip)
-  int debug_node_tb_polls = 0;   // option "debug_node_tb_polls" (tests): see launch_node_tb_reverse
-  int split_tail = 1;            // option "split_tail": see k_edge_rev_f32 (the tiles of a workgroup's last, part-filled round through the four-way split)
-  int small_launches = 1;        // option "small_launches": small systems take fused launches (force tail, readout + energy sums, ...)
-  int rev_kernel = 1;            // MFMA path: 1 = fused reverse kernel per block, 0 = node-MLP + edge-MLP kernel pair
-  bool readout_f16 = false; // option "readout_f16": the readout layers on scaled two-part fp16 chains in the f16x3 mode (5 us faster at 10,000
-                            // atoms); default: exact-fp32 chains in every mode -- the per-atom energy can be the ill-conditioned remainder of its
-                            // last layer's terms, where 22 against 24 bits per product show (fuzz case 84)
-  bool legendre_ref = false;   // option "legendre_backward" = 1: the reference's own (inexact) backward of P_l, list kernels only
-  bool tb_moments = true;   // option "threebody_moments": per-atom moment sums where the partner lists are complete (m3g_threebody.hip)
-  int stress_mode = 0;   // 0: reference formula sum pos (x) F / V; 1: pair virial (PBC consistent)
-  int edge_kernel = 1;           // 0 = VALU baseline (m3g_edge_simple.hip), 1 = MFMA (m3g_edge_mfma.hip)
-  int stamp_target = 0;          // which kernel runs its stamped variant: 0 forward edge block, 1 reverse edge-MLP kernel, 2 fused reverse (f16x3)
-  unsigned long long* d_stamps = nullptr;  // option "stamps": diagnostic phase-cycle sums [256][16][12] of the fwd edge kernel
+  unsigned long long* d_stamps = nullptr;  // option "stamps": diagnostic phase-cycle sums [256][16][12]; non-null exactly while opt.stamp_target != 0
   bool committed = false;
   // opt-in stage profiler (m3g_profile_*): event pairs recorded around stage launches
   // side stream: the three-body reverse of a block (short, latency-bound, does not fill the chip) runs beside the node
@@ -243,16 +214,10 @@ struct m3g_plan {
   bool debug_force_move = false;        // option debug_force_move (tests): the next commit runs the device-move path
   mutable hipStream_t side_stream = nullptr;
   mutable hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int overlap = 0;               // option "overlap": 1 = use the side stream (measured 2 % SLOWER on the 10k-atom step: two fork/join
-                                 // pairs of cross-stream event waits cost more than the ~40 us of kernel time they hide), default off
-  // hipGraph replay (option "graph_replay"): the launch sequence of one m3g_energy_forces call is captured once per
-  // distinct (io, workspace, stream, options) and replayed while those stay identical -- for small systems the ~36
-  // launches of a step are launch-bound.  The caller must then keep every buffer of the call alive and at the same address.
-  int graph_replay = 0;
+  // captured launch sequences (option "graph_replay"), keyed by (io, workspace, stream, opt)
   struct GraphEntry { std::vector<unsigned char> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
   mutable std::vector<GraphEntry> graphs;
-  mutable bool capturing = false;
-  mutable bool profile = false;
+  bool profile = false;                 // written by m3g_profile_enable only
   mutable std::vector<hipEvent_t> ev_pool;
   mutable std::vector<int> ev_stage;   // stage id of pair k (events 2k, 2k+1)
   mutable size_t ev_used = 0;          // pairs used since the last read
@@ -262,26 +227,13 @@ namespace m3g {
 
 // ---- topology view (device arrays carved from the caller's topo buffer) -----------------------------
 // compile-time dispatch on (l_max, n_max) <= (4, 4): BODY sees constexpr int L, R
-#define M3G_DISPATCH_LR(L_, R_, BODY)                         \
-  switch ((L_) * 8 + (R_)) {                                  \
-    case 1 * 8 + 1: { constexpr int L = 1, R = 1; BODY; } break; \
-    case 1 * 8 + 2: { constexpr int L = 1, R = 2; BODY; } break; \
-    case 1 * 8 + 3: { constexpr int L = 1, R = 3; BODY; } break; \
-    case 1 * 8 + 4: { constexpr int L = 1, R = 4; BODY; } break; \
-    case 2 * 8 + 1: { constexpr int L = 2, R = 1; BODY; } break; \
-    case 2 * 8 + 2: { constexpr int L = 2, R = 2; BODY; } break; \
-    case 2 * 8 + 3: { constexpr int L = 2, R = 3; BODY; } break; \
-    case 2 * 8 + 4: { constexpr int L = 2, R = 4; BODY; } break; \
-    case 3 * 8 + 1: { constexpr int L = 3, R = 1; BODY; } break; \
-    case 3 * 8 + 2: { constexpr int L = 3, R = 2; BODY; } break; \
-    case 3 * 8 + 3: { constexpr int L = 3, R = 3; BODY; } break; \
-    case 3 * 8 + 4: { constexpr int L = 3, R = 4; BODY; } break; \
-    case 4 * 8 + 1: { constexpr int L = 4, R = 1; BODY; } break; \
-    case 4 * 8 + 2: { constexpr int L = 4, R = 2; BODY; } break; \
-    case 4 * 8 + 3: { constexpr int L = 4, R = 3; BODY; } break; \
-    case 4 * 8 + 4: { constexpr int L = 4, R = 4; BODY; } break; \
-    default: break;                                           \
-  }
+#define M3G_LR_CASE(l, r, ...) case l * 8 + r: { constexpr int L = l, R = r; __VA_ARGS__; } break;
+#define M3G_LR_ROW(l, ...) M3G_LR_CASE(l, 1, __VA_ARGS__) M3G_LR_CASE(l, 2, __VA_ARGS__) M3G_LR_CASE(l, 3, __VA_ARGS__) M3G_LR_CASE(l, 4, __VA_ARGS__)
+#define M3G_DISPATCH_LR(L_, R_, BODY) \
+  switch ((L_) * 8 + (R_)) { M3G_LR_ROW(1, BODY) M3G_LR_ROW(2, BODY) M3G_LR_ROW(3, BODY) M3G_LR_ROW(4, BODY) default: break; }
+// ... on l_max <= 3 only (the three-body moment kernels; an `if constexpr (L <= 3)` body would still instantiate their L = 4 forms)
+#define M3G_DISPATCH_LR3(L_, R_, BODY) \
+  switch ((L_) * 8 + (R_)) { M3G_LR_ROW(1, BODY) M3G_LR_ROW(2, BODY) M3G_LR_ROW(3, BODY) default: break; }
 
 #ifndef M3G_TB_ROWS
 #define M3G_TB_ROWS 128
@@ -353,10 +305,6 @@ size_t topo_sort_tmp_bytes(int64_t E, int64_t T);
 // 24-bit dp1 rows (768 B per edge) leave the last quarter of the [E,4*kDP] fp32 buffer free: the f16x3 mode's per-row inverse
 // scales ([E][4] floats) live at its start
 inline float* dp1_scale_of(float* dp1, int64_t E) { return dp1 ? dp1 + (size_t)E * 192 : nullptr; }
-// dp1 hand-over formats of k_node_reverse: fp32 rows, 24-bit floating rows (bf16x3 fused kernel), 24-bit fixed-point rows + scales
-// (f16x3 fused kernel)
-enum { kDp1F32 = 0, kDp1Packed = 1, kDp1Fixed = 2, kDp1F32ByDst = 3 /* fp32 rows stored by position in the by-neighbour list */ };
-
 struct Work {
   // per-edge geometry / bases
   float *u, *d, *h, *hp, *q, *qp, *fc3, *fc3p;  // [E,3] [E] [E,kRP] [E,kRP] [E,kCP] [E,kCP] [E] [E]
@@ -380,9 +328,9 @@ struct Work {
   // MFMA path: tile-SoA images ([tile of 16 edges][4 blk][64 lanes][4]) of the edge features BEFORE each block
   // (e_blk[b]; e_blk[B] = final) and of dL/de, per-block node tables, row-major messages.  No activations saved.
   float* e_blk[kMaxBlocks + 1];
-  float* p2_blk[kMaxBlocks];  // fp32 mode, saves_p2(): layer-2 pre-activations, same shape; p1_blk then holds SiLU'(p1)
+  float* p2_blk[kMaxBlocks];  // fp32 mode, StepPath::saved_acts == 2: layer-2 pre-activations, same shape; p1_blk then holds SiLU'(p1)
   float* p1_blk[kMaxBlocks];  // fp32 mode: layer-1 pre-activations of both conv MLPs saved by the forward kernel,
-                              // [tiles][2 mlp][8 blk][64 lanes][4] (the reverse kernels start from them: saves_p1())
+                              // [tiles][2 mlp][8 blk][64 lanes][4] (the reverse kernels start from them: StepPath::saved_acts >= 1)
   float* TAb[kMaxBlocks];     // [N,4*kDP] per block (the reverse pass recomputes layer 1 from them)
   float* TBb[kMaxBlocks];
   float* de_soa;
@@ -392,33 +340,23 @@ struct Work {
   // tile's first run (the centre owning column 0), seg_first[i] = sum of the run in which centre i's row starts mid-tile
   float* seg_head;            // [tiles][4*kDP]
   float* seg_first;           // [N][4*kDP]
+  float* tail;                // [N + 2 S] scratch for the optional outputs the caller did not ask for (per-atom energies, per-structure sums)
   int32_t* sync;              // [kSyncWords] "last workgroup" counters of the step's fused launches: cleared by k_geometry, the first
                               // kernel of every step (nullptr when carved without a base)
   size_t total_bytes;
 };
-constexpr int kSyncWords = 16;
-constexpr int kSyncForceTail = 0, kSyncReadout = 1, kSyncNodeRev = 2;   // (+ block index for the per-block ones)
-// fused launches: the per-structure sums (energies after the readout, virial after the force gather) are formed by the LAST
-// workgroup of the producing launch when the batch has at most this many structures (it walks them one after the other)
-constexpr int64_t kForceTailMaxStructs = 8;
-// ... and at most this many atoms: the last workgroup's 256 threads then read <= 4 atoms each (measured on the 10,000-atom cell: 40
-// dependent reads per thread of values other XCDs have just written cost 24 us after the readout and 65 us after the force gather,
-// against 6 and 10 us for the stand-alone sum kernels)
-constexpr int64_t kFusedSumsMaxAtoms = 1024;   // (2,000 atoms: readout + sums 23 us against ~20 separately, gather + virial 19 against 17: no gain any more)
-constexpr int64_t kNodeTbFusedMaxAtoms = 128;   // k_node_tb_reverse (two roles in one launch): see launch_node_tb_reverse
-Work work_carve(const Consts& c, bool mfma, int save_acts /* 0 none, 1 p1, 2 p1 + p2 */, int64_t N, int64_t E, int64_t T, int64_t S, void* base);
+Work work_carve(int B, const StepPath& path /* pipeline, saved_acts */, int64_t N, int64_t E, int64_t S, void* base);
 
 // ---- kernel launchers (each in its own .hip) -----------------------------------------------------------
 // geometry.hip
 void launch_geometry(const Consts& c, const Topo& t, const float* pos, const float* lattice, const int32_t* shift,
                      const Work& w, hipStream_t s);
-bool launch_geometry_reverse(const Consts& c, const Topo& t, const Work& w, const float* dh, int dh_parts, float* forces,
-                             float* stresses, hipStream_t s, bool fuse_stress = false, const float* pos = nullptr, const float* lattice = nullptr,
+void launch_geometry_reverse(const Consts& c, const Topo& t, const Work& w, const float* dh, int dh_parts, float* forces,
+                             float* stresses, hipStream_t s, bool gather_virial = false, const float* pos = nullptr, const float* lattice = nullptr,
                              bool dr_done = false);
 void launch_stress(const Consts& c, const Topo& t, const float* pos, const float* lattice, const float* forces,
                    float* stresses, hipStream_t s, const float* ea = nullptr, float* scaled_total = nullptr, float* total = nullptr);
 void launch_stress_pair(const Topo& t, const Work& w, const float* lattice, float* stresses, hipStream_t s);
-void launch_struct_energy(const Consts& c, const Topo& t, const float* ea, float* scaled_total, float* total, hipStream_t s);
 void launch_force_gather(float length_scale, const Topo& t, const float* dr, float* forces, float* stresses, hipStream_t s);
 // generic.hip: any-size path (embedding_dim, l_max, n_max beyond the MFMA kernels' tiles)
 size_t generic_workspace_bytes(const m3g_plan* plan, int64_t N, int64_t E, int64_t T, int64_t S);
@@ -436,16 +374,15 @@ void launch_embed_reverse(const Consts& c, const float* W, const WeightLayout& w
                           hipStream_t s);
 void launch_node_pre(const Consts& c, const float* W, const BlockW& bw, const Topo& t, const Work& w, const float* x_prev, float* x,
                      float* v, float* TA, float* TB, hipStream_t s);
-void launch_node_pre_mfma(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* x_prev, float* x,
+void launch_node_pre_mfma(const m3g_plan* plan, bool split, const Consts& c, const Topo& t, const Work& w, int b, const float* x_prev, float* x,
                           float* v, float* TA, float* TB, const int64_t* types, const float* emb, hipStream_t s);
-bool launch_geometry_node_pre(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, const float* pos, const float* lattice,
+void launch_geometry_node_pre(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, const float* pos, const float* lattice,
                               const int32_t* shift, const int64_t* types, const float* emb, hipStream_t s);
 void launch_energy_sums(const Consts& c, const Topo& t, const float* scaled_atomic, float* scaled_total, float* total, hipStream_t s);
-// energy_sums_deferred (in/out): in true = the caller can form the per-structure energy sums later (k_struct_stress); out true =
-// they are still to be formed (neither this launch's last workgroup nor k_struct_energy did)
-void launch_readout_mfma(const m3g_plan* plan, const Consts& c, const WeightLayout& wl, const Topo& t, const int64_t* types,
+// (p.readout, p.readout_sums; without the latter the caller forms the energy sums: launch_energy_sums or, deferred, k_struct_stress)
+void launch_readout_mfma(const m3g_plan* plan, const StepPath& p, const Consts& c, const WeightLayout& wl, const Topo& t, const int64_t* types,
                          const float* x_prev, float* x, const Work& w, float* scaled_atomic, float* scaled_total, float* total,
-                         bool want_grad, hipStream_t s, bool* energy_sums_deferred = nullptr);
+                         bool want_grad, hipStream_t s);
 void launch_node_reverse(const Consts& c, const float* W, const BlockW& bw, const Topo& t, const Work& w,
                          const float* v, const float* dx_new, float* dx_out, bool row_sums_in_seg, int dp1_packed, bool with_v_term,
                          hipStream_t s, bool small = false);
@@ -461,45 +398,30 @@ void launch_copy_expand_rows(const int32_t* row_id, const float* in, int in_stri
 void launch_copy_strided(const float* in, int in_stride, float* out, int out_stride, int width, int64_t rows,
                          hipStream_t s);
 // threebody.hip
-void launch_threebody(const Consts& c, const Topo& t, const Work& w, const float* v, float* m, hipStream_t s, int topo_hints = 0);
-void launch_threebody_reverse(const Consts& c, const Topo& t, const Work& w, const float* v, bool first, hipStream_t s, int topo_hints = 0,
+// (p.moments with p.tb_hints, else the list kernels by p.long_lists)
+void launch_threebody(const StepPath& p, const Consts& c, const Topo& t, const Work& w, const float* v, float* m, hipStream_t s);
+void launch_threebody_reverse(const StepPath& p, const Consts& c, const Topo& t, const Work& w, const float* v, bool first, hipStream_t s,
                               bool ref_legendre = false);
-bool launch_threebody_reverse_final(const Consts& c, const Topo& t, const Work& w, const float* v, bool first, const float* dh, int dh_parts,
+void launch_threebody_reverse_final(const Consts& c, const Topo& t, const Work& w, const float* v, bool first, const float* dh, int dh_parts,
                                     hipStream_t s, int topo_hints);
+// the one launcher that may decline (false: the runtime cannot hold all its workgroups at once -- the caller launches the two kernels)
 bool launch_node_tb_reverse(const Consts& c, const float* W, const BlockW& bw, const Topo& t, const Work& w, const float* v, bool first,
                             const float* dx_new, float* dx_out, int dp1_packed, int block, hipStream_t s, int topo_hints, int debug_polls = 0);
 // pack_mfma.hip / edge_mfma.hip
 int pack_mfma_images(m3g_plan* plan);
 void free_mfma_images(m3g_plan* plan);
-// one fused reverse kernel per block: k_edge_rev_fused (bf16x3, dual-use bf16 images) or k_edge_rev_f32 (fp32, needs the saved
-// layer-1 pre-activations); otherwise the node-MLP + edge-MLP kernel pair
-// fp32 mode is bound by the matrix pipe: its forward kernel saves the layer-1 pre-activations of both MLPs (1 KB per edge and
-// block) and the reverse kernels start from them instead of recomputing that layer (a quarter of their MFMAs)
-inline bool saves_p1(const m3g_plan* plan) { return plan->edge_kernel == 1 && plan->precision == kPrecF32 && plan->save_p1 != 0; }
-// ... and, with the fused fp32 reverse kernel, the layer-2 pre-activations as well (another 1 KB per edge and block): the
-// reverse kernel then issues no recompute MFMA at all (576 instead of 832 per tile)
-inline bool saves_p2(const m3g_plan* plan) { return saves_p1(plan) && plan->rev_kernel == 1 && plan->save_p2 != 0; }
-inline int saved_activations(const m3g_plan* plan) { return saves_p2(plan) ? 2 : saves_p1(plan) ? 1 : 0; }
-// exact-fp32 fused reverse kernels: dp1 rows stored by the edge's position in the by-neighbour list (option "dp1_by_dst")
-inline bool dp1_rows_by_dst(const m3g_plan* plan) {
-  return plan->dp1_by_dst && plan->edge_kernel == 1 && plan->rev_kernel == 1 && plan->precision == kPrecF32 && saves_p1(plan);
-}
-inline bool fused_reverse(const m3g_plan* plan) {
-  return plan->edge_kernel == 1 && plan->rev_kernel == 1 && (plan->precision != kPrecF32 || saves_p1(plan));
-}
-void launch_edge_block_mfma(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, bool for_reverse, hipStream_t s);
-void launch_edge_rev_node_mlp(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
+void launch_edge_block_mfma(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, hipStream_t s);
+void launch_edge_rev_node_mlp(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
                               hipStream_t s);
-void launch_edge_rev_edge_mlp(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
+void launch_edge_rev_edge_mlp(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
                               bool de_is_zero, hipStream_t s);
 void launch_edge_rev_fused(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
                            bool de_is_zero, hipStream_t s);
-void launch_edge_rev_f32(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
+void launch_edge_rev_f32(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
                          bool de_is_zero, hipStream_t s);
-// edge_small.hip: the exact-fp32 edge kernels with one tile split over the four waves of a workgroup (small systems); false: the
-// configuration is not one they cover (another precision / A-B option / stamps) -- the caller then launches the persistent kernel
-bool launch_edge_fwd_split(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, bool for_reverse, hipStream_t s);
-bool launch_edge_rev_split(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new, bool de_is_zero,
+// edge_small.hip: the exact-fp32 edge kernels with one tile split over the four waves of a workgroup (small systems)
+void launch_edge_fwd_split(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, hipStream_t s);
+void launch_edge_rev_split(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new, bool de_is_zero,
                            hipStream_t s);
 void launch_embed_edges_soa(const Consts& c, const float* adj_t, const float* h, float* soa, int64_t E, hipStream_t s);
 void launch_embed_edges_reverse_soa(const float* adj, const float* h, const float* de_soa, float* dh_slice, int64_t E, hipStream_t s);

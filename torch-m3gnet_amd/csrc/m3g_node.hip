@@ -335,11 +335,6 @@ void launch_node_reverse_v_term(const Consts& c, const float* W, const BlockW& b
                        dx_out, reinterpret_cast<const int2*>(t.in_pair));
 }
 
-// per-structure sums of the scaled atomic energies and total = energy_scale * sum: one launch (k_struct_energy, fixed order)
-void launch_energy_sums(const Consts& c, const Topo& t, const float* scaled_atomic, float* scaled_total, float* total, hipStream_t s) {
-  launch_struct_energy(c, t, scaled_atomic, scaled_total, total, s);
-}
-
 void launch_readout(const Consts& c, const float* W, const WeightLayout& wl, const Topo& t, const int64_t* types,
                     const float* x_prev, float* x, const Work& w, float* scaled_atomic, float* scaled_total, float* total,
                     bool want_grad, hipStream_t s) {

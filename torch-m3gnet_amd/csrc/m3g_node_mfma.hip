@@ -489,20 +489,15 @@ __global__ void __launch_bounds__(256) k_readout_split(Consts c, int64_t N, cons
     struct_energy<256>(sidx, rs.struct_ptr, rs.flags, N, rs.batch, scaled_atomic, c.energy_scale, scaled_total, rs.total, xs);
 }
 
-void launch_readout_mfma(const m3g_plan* plan, const Consts& c, const WeightLayout& wl, const Topo& t, const int64_t* types,
+void launch_readout_mfma(const m3g_plan* plan, const StepPath& p, const Consts& c, const WeightLayout& wl, const Topo& t, const int64_t* types,
                          const float* x_prev, float* x, const Work& w, float* scaled_atomic, float* scaled_total, float* total,
-                         bool want_grad, hipStream_t s, bool* energy_sums_deferred) {
-  const bool may_defer = energy_sums_deferred && *energy_sums_deferred;
-  if (energy_sums_deferred) *energy_sums_deferred = false;
+                         bool want_grad, hipStream_t s) {
   if (t.N == 0) (void)hipMemsetAsync(scaled_total, 0, sizeof(float) * t.S, s);
-  bool sums_fused = false;
   if (t.N > 0) {
     const int64_t tiles = (t.N + 15) / 16;
     const int wgs = (int)std::min<int64_t>((tiles + 3) / 4, 256);
-    sums_fused = plan->small_launches && w.sync && t.N <= kFusedSumsMaxAtoms && t.S > 0 && t.S <= kForceTailMaxStructs;
-    const ReadoutSums rs{t.struct_ptr, t.flags, t.batch, total, sums_fused ? w.sync + kSyncReadout : nullptr};
-    const bool f16_readout = plan->precision == kPrecF16x3 && plan->readout_f16;
-    if (!f16_readout && plan->small_launches && tiles <= plan->split_node_tiles) {   // small systems: a tile over the four waves of a workgroup
+    const ReadoutSums rs{t.struct_ptr, t.flags, t.batch, total, p.readout_sums ? w.sync + kSyncReadout : nullptr};
+    if (p.readout == kReadoutSplit) {   // small systems: a tile over the four waves of a workgroup
       if (want_grad)
         hipLaunchKernelGGL(k_readout_split<true>, dim3((unsigned)tiles), dim3(256), 0, s, c, t.N, plan->d_readout_img, plan->d_weights + wl.elemental,
                            types, x_prev, w.seg_head, w.seg_first, t.row_ptr, x, scaled_atomic, w.dx, scaled_total, t.S, rs);
@@ -510,7 +505,7 @@ void launch_readout_mfma(const m3g_plan* plan, const Consts& c, const WeightLayo
         hipLaunchKernelGGL(k_readout_split<false>, dim3((unsigned)tiles), dim3(256), 0, s, c, t.N, plan->d_readout_img, plan->d_weights + wl.elemental,
                            types, x_prev, w.seg_head, w.seg_first, t.row_ptr, x, scaled_atomic, nullptr, scaled_total, t.S, rs);
     } else
-    if (plan->precision == kPrecF16x3 && plan->readout_f16)   // (option; default: exact-fp32 readout in every mode)
+    if (p.readout == kReadoutF16)   // (option; default: exact-fp32 readout in every mode)
       hipLaunchKernelGGL(k_readout_mfma<kPrecF16x3>, dim3(wgs), dim3(256), 0, s, c, t.N, plan->d_readout_img_h, plan->ro_w_scale_inv,
                          plan->d_weights + wl.elemental, types, x_prev, w.seg_head, w.seg_first, t.row_ptr, x, scaled_atomic,
                          want_grad ? w.dx : nullptr, scaled_total, t.S, rs);
@@ -520,40 +515,39 @@ void launch_readout_mfma(const m3g_plan* plan, const Consts& c, const WeightLayo
                          plan->d_weights + wl.elemental, types, x_prev, w.seg_head, w.seg_first, t.row_ptr, x, scaled_atomic,
                          want_grad ? w.dx : nullptr, scaled_total, t.S, rs);
   }
-  if (!sums_fused && may_defer && t.N > 0) *energy_sums_deferred = true;   // formed by the step's last launch (k_struct_stress)
-  else if (!sums_fused) launch_energy_sums(c, t, scaled_atomic, scaled_total, total, s);
+  // (p.energy_deferred: formed by the step's last launch, k_struct_stress)
+  if (!p.readout_sums && !p.energy_deferred) launch_energy_sums(c, t, scaled_atomic, scaled_total, total, s);
 }
 
 // types != nullptr (block 0): x is formed from the atom embedding `emb` ([num_types][kDP]) instead of being read
-void launch_node_pre_mfma(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, int b, const float* x_prev, float* x,
+void launch_node_pre_mfma(const m3g_plan* plan, bool split, const Consts& c, const Topo& t, const Work& w, int b, const float* x_prev, float* x,
                           float* v, float* TA, float* TB, const int64_t* types, const float* emb, hipStream_t s) {
   if (t.N == 0) return;
   const int64_t tiles = (t.N + 15) / 16;
-  if (plan->precision == kPrecF32 && plan->small_launches && tiles <= plan->split_node_tiles) {   // small systems: a tile and pass per workgroup
+  const int prec = plan->opt.precision;
+  if (split) {   // small systems (exact-fp32 mode): a tile and pass per workgroup
     const NodePreArgs a{c.C, t.N, plan->d_node_img[kPrecF32] + (size_t)b * kNodeImgFloats, x_prev, w.seg_head, w.seg_first, t.row_ptr, x, v, TA, TB,
                         types, emb, c.num_types};
     hipLaunchKernelGGL(k_node_pre_split, dim3((unsigned)(3 * tiles)), dim3(256), 0, s, a);
     return;
   }
   const int wgs = 3 * (int)std::min<int64_t>((tiles + 3) / 4, 256);   // (pass, group of four tiles); groups beyond 256 loop
-  M3G_PREC_SWITCH(plan->precision,
+  M3G_PREC_SWITCH(prec,
                   hipLaunchKernelGGL((k_node_pre_mfma<PREC>), dim3(wgs), dim3(256), 0, s, c.C, t.N,
-                                     plan->d_node_img[plan->precision] + (size_t)b * kNodeImgFloats, x_prev, w.seg_head, w.seg_first,
+                                     plan->d_node_img[prec] + (size_t)b * kNodeImgFloats, x_prev, w.seg_head, w.seg_first,
                                      t.row_ptr, x, v, TA, TB, types, emb, c.num_types,
-                                     plan->precision == kPrecF16x3 ? plan->w_scale_inv : 1.f));
+                                     prec == kPrecF16x3 ? plan->w_scale_inv : 1.f));
 }
 
-// geometry stage + block 0's node tables in one launch (small systems, exact-fp32 mode); false: not a case it covers
-bool launch_geometry_node_pre(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, const float* pos, const float* lattice,
+// geometry stage + block 0's node tables in one launch (small systems, exact-fp32 mode: StepPath::geom_with_node_pre)
+void launch_geometry_node_pre(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, const float* pos, const float* lattice,
                               const int32_t* shift, const int64_t* types, const float* emb, hipStream_t s) {
   const int64_t tiles = (t.N + 15) / 16;
-  if (plan->precision != kPrecF32 || !plan->small_launches || c.B == 0 || t.E == 0 || t.N == 0 || tiles > plan->split_node_tiles) return false;
   const int n_geo = (int)((t.E + 255) / 256);
   const GeomArgs ga = geometry_args(t, pos, lattice, shift, w);
   const NodePreArgs na{c.C, t.N, plan->d_node_img[kPrecF32], nullptr, w.seg_head, w.seg_first, t.row_ptr, w.x[0], w.v[0], w.TAb[0], w.TBb[0], types, emb,
                        c.num_types};
   M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_geometry_node_pre<L, R>), dim3((unsigned)(n_geo + 3 * tiles)), dim3(256), 0, s, c, ga, n_geo, na));
-  return true;
 }
 
 }  // namespace m3g

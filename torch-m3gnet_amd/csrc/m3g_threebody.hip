@@ -672,45 +672,25 @@ static inline dim3 grid_rows(int64_t n) {
   const int64_t blocks = (n + kTbRows - 1) / kTbRows;
   return dim3((unsigned)(blocks < M3G_TB_GRID_CAP ? blocks : M3G_TB_GRID_CAP));
 }
-// Long partner lists?  Triplets per edge is a host-side lower bound of triplets per ACTIVE edge (the number of active edges
-// lives on the device); either choice is correct, the wrong one only costs time (global-memory fallback or LDS footprint).
-static inline bool long_lists(const Topo& t) { return t.T > 24 * t.E; }
-
-// the moment kernels apply when the topology build found every window complete (hint bit, read back by the caller once per
-// topology: m3g_topology_hints) and l_max <= 3
-static inline bool use_moments(const Consts& c, int topo_hints) {
-  // (L, R outside M3G_DISPATCH_LR3's cases take the list kernels)
-  return (topo_hints & M3G_TOPO_TB_COMPLETE) && c.L >= 1 && c.L <= 3 && c.R >= 1 && c.R <= 4 && ((topo_hints >> 8) & 0xff) > 0 &&
-         ((topo_hints >> 16) & 0xff) > 0;
+// (StepPath::moments: L, R outside M3G_DISPATCH_LR3's cases take the list kernels)
+// arguments of the moment kernels: forward (m = the aggregate to form) or reverse (m = nullptr: the gradient arrays of the workspace)
+static TbMomArgs tb_mom_args(const Topo& t, const Work& w, const float* v, int topo_hints, float* m, bool first) {
+  if (m) return TbMomArgs{(int)(t.E / kTbRows + 1), t.src, t.arow_ptr, t.tb_fast, t.act_list, t.act_dst, t.tb_win, t.n_act, t.flags, topo_hints, w.u, w.fc3, nullptr, w.q, nullptr, v, nullptr, m, nullptr, nullptr, nullptr, 0};
+  return TbMomArgs{(int)(t.E / kTbRows + 1), t.src, t.arow_ptr, t.tb_fast, t.act_list, t.act_dst, t.tb_win, t.n_act, t.flags, topo_hints, w.u, w.fc3, w.fc3p, w.q, w.qp, v, w.dm, nullptr, w.dd, w.du, w.dg, first ? 1 : 0};
 }
-#define M3G_DISPATCH_LR3(Lv, Rv, BODY)                          \
-  switch ((Lv) * 8 + (Rv)) {                                    \
-    case 1 * 8 + 1: { constexpr int L = 1, R = 1; BODY; } break; \
-    case 1 * 8 + 2: { constexpr int L = 1, R = 2; BODY; } break; \
-    case 1 * 8 + 3: { constexpr int L = 1, R = 3; BODY; } break; \
-    case 1 * 8 + 4: { constexpr int L = 1, R = 4; BODY; } break; \
-    case 2 * 8 + 1: { constexpr int L = 2, R = 1; BODY; } break; \
-    case 2 * 8 + 2: { constexpr int L = 2, R = 2; BODY; } break; \
-    case 2 * 8 + 3: { constexpr int L = 2, R = 3; BODY; } break; \
-    case 2 * 8 + 4: { constexpr int L = 2, R = 4; BODY; } break; \
-    case 3 * 8 + 1: { constexpr int L = 3, R = 1; BODY; } break; \
-    case 3 * 8 + 2: { constexpr int L = 3, R = 2; BODY; } break; \
-    case 3 * 8 + 3: { constexpr int L = 3, R = 3; BODY; } break; \
-    case 3 * 8 + 4: { constexpr int L = 3, R = 4; BODY; } break; \
-    default: break;                                             \
-  }
 
-void launch_threebody(const Consts& c, const Topo& t, const Work& w, const float* v, float* m, hipStream_t s, int topo_hints) {
+void launch_threebody(const StepPath& p, const Consts& c, const Topo& t, const Work& w, const float* v, float* m, hipStream_t s) {
   if (t.E == 0) return;
   if (t.T == 0) return;   // no active edge: every consumer reads zeros through act_id < 0
-  if (use_moments(c, topo_hints)) {
-    TbMomArgs a{(int)(t.E / kTbRows + 1), t.src, t.arow_ptr, t.tb_fast, t.act_list, t.act_dst, t.tb_win, t.n_act, t.flags, topo_hints, w.u, w.fc3, nullptr, w.q, nullptr, v, nullptr, m, nullptr, nullptr, nullptr, 0};
+  const int topo_hints = p.tb_hints;
+  if (p.moments) {
+    const TbMomArgs a = tb_mom_args(t, w, v, topo_hints, m, false);
     const int rows = (topo_hints >> 8) & 0xff, atoms = (topo_hints >> 16) & 0xff;
     M3G_DISPATCH_LR3(c.L, c.R, hipLaunchKernelGGL((k_threebody_moments<L, R, false>), grid_rows(t.E), dim3(kTbMomThreads), (mom_lds_bytes<L, R, false>(rows, atoms)), s, c, a, rows, atoms));
     return;
   }
   TbArgs a{t.E, t.act_list, t.act_dst, t.tb_win, t.n_act, t.t1_ptr, t.t1_e2c, t.t1_b, w.u, w.fc3, w.q, v, m};
-  if (long_lists(t)) { M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_threebody_fwd<L, R, kTbListLong, kTbCap, kTbLprLong>), grid_rows(t.E), dim3(kTbRows * kTbLprLong), 0, s, c, a)); }
+  if (p.long_lists) { M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_threebody_fwd<L, R, kTbListLong, kTbCap, kTbLprLong>), grid_rows(t.E), dim3(kTbRows * kTbLprLong), 0, s, c, a)); }
   else { M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_threebody_fwd<L, R, kTbListShort, kTbCapShort, kTbLprShort>), grid_rows(t.E), dim3(kTbRows * kTbLprShort), 0, s, c, a)); }
 }
 
@@ -744,16 +724,11 @@ static bool node_tb_launch(const Consts& c, const TbMomArgs& a, int rows, int at
   return true;
 }
 
-// three-body reverse + node reverse of a block in one launch (k_node_tb_reverse); false: not applicable (list kernels, no atoms, no
-// sync words) -- the caller then launches the two kernels
+// three-body reverse + node reverse of a block in one launch (k_node_tb_reverse, StepPath's kTailNodeTb candidate); false: its
+// workgroups are not all resident at once -- the caller then launches the two kernels
 bool launch_node_tb_reverse(const Consts& c, const float* W, const BlockW& bw, const Topo& t, const Work& w, const float* v, bool first,
                             const float* dx_new, float* dx_out, int dp1_packed, int block, hipStream_t s, int topo_hints, int debug_polls) {
-  // Small cells only.  Measured: 32 atoms 20.7 -> 15.8 us for the pair, 108 atoms a gain, 256 atoms a small loss, 864 atoms 24 -> 47 us,
-  // 10,000 atoms 2.40 -> 2.62 ms per step: publishing costs an L2 write-back per three-body workgroup and an L2 invalidate per
-  // waiting wave (the XCDs' L2s are not coherent with each other), which a launch boundary does once for everybody.
-  if (t.N > kNodeTbFusedMaxAtoms) return false;
-  if (t.E == 0 || t.T == 0 || t.N == 0 || !w.sync || !use_moments(c, topo_hints) || kSyncNodeRev + block >= kSyncWords) return false;
-  TbMomArgs a{(int)(t.E / kTbRows + 1), t.src, t.arow_ptr, t.tb_fast, t.act_list, t.act_dst, t.tb_win, t.n_act, t.flags, topo_hints, w.u, w.fc3, w.fc3p, w.q, w.qp, v, w.dm, nullptr, w.dd, w.du, w.dg, first ? 1 : 0};
+  const TbMomArgs a = tb_mom_args(t, w, v, topo_hints, nullptr, first);
   const int rows = (topo_hints >> 8) & 0xff, atoms = (topo_hints >> 16) & 0xff;
   const NodeRevArgs na = node_rev_args(c, W, bw, t, w, v, dx_new, dx_out, /*row_sums_in_seg=*/true, dp1_packed, /*with_v_term=*/true);
   // the three-body role walks its row blocks with at most 128 workgroups: each publishes once, and a publish is a write-back of
@@ -765,24 +740,23 @@ bool launch_node_tb_reverse(const Consts& c, const float* W, const BlockW& bw, c
   return launched;
 }
 
-// the step's last three-body reverse + the geometry reverse (dE/dr of every edge) in one launch; false: not the moment path / no
-// triplets -- the caller then launches launch_threebody_reverse and k_geometry_reverse
-bool launch_threebody_reverse_final(const Consts& c, const Topo& t, const Work& w, const float* v, bool first, const float* dh, int dh_parts,
+// the step's last three-body reverse + the geometry reverse (dE/dr of every edge) in one launch (moment path: kTailFinalTb)
+void launch_threebody_reverse_final(const Consts& c, const Topo& t, const Work& w, const float* v, bool first, const float* dh, int dh_parts,
                                     hipStream_t s, int topo_hints) {
-  if (t.E == 0 || t.T == 0 || c.B == 0 || !use_moments(c, topo_hints)) return false;
-  TbMomArgs a{(int)(t.E / kTbRows + 1), t.src, t.arow_ptr, t.tb_fast, t.act_list, t.act_dst, t.tb_win, t.n_act, t.flags, topo_hints, w.u, w.fc3, w.fc3p, w.q, w.qp, v, w.dm, nullptr, w.dd, w.du, w.dg, first ? 1 : 0,
-              GeomRev{t.E, w.u, w.d, w.hp, dh, dh_parts, w.dd, w.du, t.act_id}, w.dr};
+  TbMomArgs a = tb_mom_args(t, w, v, topo_hints, nullptr, first);
+  a.geom = GeomRev{t.E, w.u, w.d, w.hp, dh, dh_parts, w.dd, w.du, t.act_id};
+  a.dr = w.dr;
   const int rows = (topo_hints >> 8) & 0xff, atoms = (topo_hints >> 16) & 0xff;
   M3G_DISPATCH_LR3(c.L, c.R, hipLaunchKernelGGL((k_threebody_moments_final<L, R>), grid_rows(t.E), dim3(kTbMomThreads), (mom_lds_bytes<L, R, true>(rows, atoms)), s, c, a, rows, atoms));
-  return true;
 }
 
-void launch_threebody_reverse(const Consts& c, const Topo& t, const Work& w, const float* v, bool first, hipStream_t s, int topo_hints,
+void launch_threebody_reverse(const StepPath& p, const Consts& c, const Topo& t, const Work& w, const float* v, bool first, hipStream_t s,
                               bool ref_legendre) {
   if (t.E == 0) return;
   if (t.T == 0) return;
-  if (use_moments(c, topo_hints)) {
-    TbMomArgs a{(int)(t.E / kTbRows + 1), t.src, t.arow_ptr, t.tb_fast, t.act_list, t.act_dst, t.tb_win, t.n_act, t.flags, topo_hints, w.u, w.fc3, w.fc3p, w.q, w.qp, v, w.dm, nullptr, w.dd, w.du, w.dg, first ? 1 : 0};
+  const int topo_hints = p.tb_hints;
+  if (p.moments) {
+    const TbMomArgs a = tb_mom_args(t, w, v, topo_hints, nullptr, first);
     const int rows = (topo_hints >> 8) & 0xff, atoms = (topo_hints >> 16) & 0xff;
     M3G_DISPATCH_LR3(c.L, c.R, hipLaunchKernelGGL((k_threebody_moments<L, R, true>), grid_rows(t.E), dim3(kTbMomThreads), (mom_lds_bytes<L, R, true>(rows, atoms)), s, c, a, rows, atoms));
     return;
@@ -790,7 +764,7 @@ void launch_threebody_reverse(const Consts& c, const Topo& t, const Work& w, con
   TbRevArgs a{t.E, t.act_list, t.act_dst, t.tb_win, t.n_act, t.t1_ptr, t.t1_e2c, t.t2_ptr, t.t2_e1c, t.t1_b, t.t2_b, w.u, w.fc3, w.fc3p, w.q,
               w.qp, v,
               w.dm, w.dd, w.du, w.dg, first ? 1 : 0, ref_legendre ? 1 : 0};
-  if (long_lists(t)) { M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_threebody_rev<L, R, kTbListLong, kTbCap, kTbLprLong>), grid_rows(t.E), dim3(kTbRows * kTbLprLong), 0, s, c, a)); }
+  if (p.long_lists) { M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_threebody_rev<L, R, kTbListLong, kTbCap, kTbLprLong>), grid_rows(t.E), dim3(kTbRows * kTbLprLong), 0, s, c, a)); }
   else { M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_threebody_rev<L, R, kTbListShort, kTbCapShort, kTbLprShort>), grid_rows(t.E), dim3(kTbRows * kTbLprShort), 0, s, c, a)); }
 }
 
