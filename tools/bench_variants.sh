@@ -1,5 +1,7 @@
 #!/bin/bash
-# usage: [PREC=f16x3] [STEPS=30] [BENCH_ARGS="--engine-option threebody_moments=0"] tools/bench_variants.sh name1 name2 ...   (runs bench.py with lib/variants/<name>.so swapped in; "base" = the built library)
+# usage: [PREC=f16x3] [STEPS=30] [BENCH_ARGS="--engine-option threebody_moments=0"] tools/bench_variants.sh name1 name2 ...
+# Runs bench.py once per name with lib/variants/<name>.so (tools/build_variant.sh: the kernels of another checkout, usually the
+# parent commit) swapped in for the library; "base" = the built library.  Same box, same session: the comparison a change needs.
 cd "$(dirname "$0")/.."
 L=torch-m3gnet_amd/lib
 cp $L/libm3gnet_hip.so /tmp/base.so

@@ -1,9 +1,10 @@
 #!/bin/bash
-# usage: tools/build_variant.sh <name> <extra hipcc flags...>   -> torch-m3gnet_amd/lib/variants/<name>.so
-# SRC=<dir with the csrc/*.hip,*.h to compile> (default: csrc) builds the variant from another copy of the sources, e.g. a
-# `git worktree` of an earlier commit, for same-box A/B timing.
-# (FILES="m3g_node ..." names the sources rebuilt with the flags -- default: the MFMA edge kernels m3g_edge_mfma.hip and
-# m3g_edge_rev_f32.hip --, everything else comes from build/)
+# usage: SRC=<dir> [FILES="m3g_node ..."] tools/build_variant.sh <name> [extra hipcc flags...]   -> torch-m3gnet_amd/lib/variants/<name>.so
+# Builds the kernels of ANOTHER checkout into a library that tools/bench_variants.sh can time next to the built one on the same
+# box -- how a change is compared with its parent commit.  SRC = the directory with that checkout's csrc/*.hip,*.h, e.g. a
+# `git worktree` of the parent (default: csrc, this tree's own).  FILES names the sources taken from SRC (default: the MFMA edge
+# kernels m3g_edge_mfma.hip and m3g_edge_rev_f32.hip); every other object comes from this tree's build/.  Prints the register
+# and spill use of the three main edge kernels.
 set -e
 cd "$(dirname "$0")/../torch-m3gnet_amd"
 name=$1; shift

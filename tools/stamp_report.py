@@ -26,7 +26,7 @@ for _ in range(3):
     model(g, extras=False)
 torch.cuda.synchronize()
 import os
-W = int(os.environ.get("STAMP_WAVES", "16"))   # waves per workgroup of the build under test (M3G_WAVES_FWD)
+W = int(os.environ.get("STAMP_WAVES", "16"))   # waves per workgroup of the build under test (kWaves, m3g_edge_common.h)
 buf = np.zeros(256 * 16 * 12, dtype=np.uint64)
 _lib.check(eng.lib.m3g_debug_read_stamps(eng.plan, buf.ctypes.data))
 s = buf.reshape(256, 16, 12)[:, :W].astype(np.float64)   # [workgroup][16 wave slots][12]: the first W slots are written

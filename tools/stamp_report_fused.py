@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phase cycle sums of the fused reverse kernel (f16x3) from its stamped diagnostic variant (GPU box).
-STAMP_WAVES = waves per workgroup of the build under test (M3G_WAVES_REV_FUSED, default 8)."""
+STAMP_WAVES = waves per workgroup of the build under test (kWavesRevFused in m3g_edge_common.h: 8)."""
 import os
 import sys
 from pathlib import Path

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """BASELINE config 5 (high triplet density): 2,000 atoms uniform in L = 31.1 A (1.6 A rejection, seed 0), cutoff 6 A, with
 three-body cutoff 4 A and 6 A.  Prints the step time and the three-body kernels' time, algorithmic HBM bytes/s and LDS read
-rate per launch (HIP-event stage timers of the library).  Run once per build of the rows-per-workgroup sweep
-(tools/sweep_config5.sh); one JSON line per three-body cutoff."""
+rate per launch (HIP-event stage timers of the library).  One JSON line per three-body cutoff
+(run once per build when comparing builds, e.g. of kTbRows in m3g_internal.h)."""
 import json
 import sys
 import time

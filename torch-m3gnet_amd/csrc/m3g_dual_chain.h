@@ -8,14 +8,9 @@
 #include "m3g_dual_image.h"
 #include "m3g_mfma_common.h"
 
-// Wave priority around the MFMA chains: with two waves per SIMD the arbiter otherwise lets the other wave's VALU stream
-// delay the chain's MFMA issue; raised priority keeps the matrix pipe fed while that VALU work fills the gaps
+// Wave priority around the MFMA chains (s_setprio 1 on entry, 0 on exit): with two waves per SIMD the arbiter otherwise lets
+// the other wave's VALU stream delay the chain's MFMA issue; raised priority keeps the matrix pipe fed while that VALU work fills the gaps
 // (measured on the fused reverse kernel: 0.973 -> 0.925 ms per step).
-#ifndef M3G_NO_CHAIN_PRIO
-#define M3G_CHAIN_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#else
-#define M3G_CHAIN_PRIO(p) ((void)0)
-#endif
 
 namespace m3g {
 
@@ -35,7 +30,7 @@ __device__ __forceinline__ void chain_dual(const float* img, const f32x4 (&x)[NX
   static_assert(XOFF + 2 * KS <= NX && AOFF + OB <= NA && (RB0 + OB) * 16 <= ROWS, "chain_dual operand out of range");
   const int m = lane & 15, q = lane >> 4, sw = dual_swz(m);
   const char* base = reinterpret_cast<const char*>(img) + (m >> 3) * 1024 + (m & 7) * 64;
-  M3G_CHAIN_PRIO(1);
+  __builtin_amdgcn_s_setprio(1);
   static_for<KS>([&]<int s>() {
     bf16x8 bh, bl;
     split8(x[XOFF + 2 * s], x[XOFF + 2 * s + 1], bh, bl);
@@ -57,7 +52,7 @@ __device__ __forceinline__ void chain_dual(const float* img, const f32x4 (&x)[NX
       });
     }
   });
-  M3G_CHAIN_PRIO(0);
+  __builtin_amdgcn_s_setprio(0);
 }
 
 // transposed: d holds ROWS/16 blocks of output-feature gradients starting at block DOFF (KS = ROWS/32 k-steps);
@@ -69,7 +64,7 @@ __device__ __forceinline__ void chain_dual_t(const float* img, const f32x4 (&d)[
   const int q = lane >> 4, qp = (lane & 15) >> 2, p = lane & 3;
   const int row_lo = 4 * q + qp, sw = dual_swz(row_lo);
   const char* base = reinterpret_cast<const char*>(img) + (row_lo >> 3) * 1024 + (row_lo & 7) * 64;
-  M3G_CHAIN_PRIO(1);
+  __builtin_amdgcn_s_setprio(1);
   static_for<KS>([&]<int s>() {
     bf16x8 bh, bl;
     split8(d[DOFF + 2 * s], d[DOFF + 2 * s + 1], bh, bl);
@@ -92,7 +87,7 @@ __device__ __forceinline__ void chain_dual_t(const float* img, const f32x4 (&d)[
       });
     }
   });
-  M3G_CHAIN_PRIO(0);
+  __builtin_amdgcn_s_setprio(0);
 }
 
 // ---- f16x3 mode: the same dual-use image holding fp16 parts of the SCALED weights (m3g_mfma_common.h); acc[AOFF + ob] += (W x)
@@ -104,14 +99,46 @@ __device__ __forceinline__ f16x8 join_halves_h(s16x4 a, s16x4 b) {
 }
 // A operands of one 16-row block (both parts, KS k-steps) -- requested one block AHEAD of the MFMAs that consume them: the LDS
 // round trip (64+ cycles, more with eight waves reading) is longer than the two or three MFMAs the compiler's own schedule puts
-// between a ds_read and its use, and with two waves per SIMD those waits are exposed (M3G_CHAIN_PREFETCH).
+// between a ds_read and its use, and with two waves per SIMD those waits are exposed.
 template <int KS>
 struct DualA { f16x8 h[KS], l[KS]; };
-#ifndef M3G_NO_CHAIN_PREFETCH
-#define M3G_CHAIN_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define M3G_CHAIN_FENCE() ((void)0)
-#endif
+// The loop of every f16x3 chain (this file and chain_h, m3g_edge_common.h): fetch<ob + 1>() requests the next row block's
+// operands, then the three products per k-step of row block ob -- whose operands `cur` holds -- go to out<ob>(scaled sum).  The
+// fences keep the requests ahead of the MFMAs and the consumer behind them.
+template <int OB, int KS, class FETCH, class OUT>
+__device__ __forceinline__ void chain_h_blocks(DualA<KS> cur, const HalfB<KS>& b, FETCH&& fetch, OUT&& out) {
+  static_for<OB>([&]<int ob>() {
+    DualA<KS> nxt = cur;
+    if constexpr (ob + 1 < OB) nxt = fetch.template operator()<ob + 1>();
+    sched_fence();
+    f32x4 t = {0.f, 0.f, 0.f, 0.f};
+    static_for<KS>([&]<int s>() {
+      t = mfma_f16(cur.h[s], b.hi[s], t);
+      t = mfma_f16(cur.h[s], b.lo[s], t);
+      t = mfma_f16(cur.l[s], b.hi[s], t);
+    });
+    out.template operator()<ob>(t);
+    sched_fence();
+    cur = nxt;
+  });
+}
+// acc[AOFF + ob] += (W x)[ob-th block of the image as `fetch` reads it] in true units; `used` (optional) receives x's per-edge scale
+template <int OB, int KS, int XOFF, int AOFF, class FETCH, int NX, int NA>
+__device__ __forceinline__ void chain_dual_h_acc(FETCH&& fetch, const f32x4 (&x)[NX], f32x4 (&acc)[NA], float w_inv,
+                                                 EdgeScale* used) {
+  // the first block's operands travel while the vector ALU finds the scale and splits x
+  DualA<KS> cur = fetch.template operator()<0>();
+  sched_fence();
+  const EdgeScale sc = edge_scale<2 * KS, XOFF>(x);
+  if (used) *used = sc;
+  const HalfB<KS> b = split_h<KS, XOFF>(x, sc.s);
+  const float inv = sc.inv * w_inv;
+  __builtin_amdgcn_s_setprio(1);
+  chain_h_blocks<OB, KS>(cur, b, fetch, [&]<int ob>(const f32x4& t) {
+    acc[AOFF + ob] = t * inv + acc[AOFF + ob];   // (vector form: the compiler emits two v_pk_fma_f32)
+  });
+  __builtin_amdgcn_s_setprio(0);
+}
 template <int OB, int KS, int ROWS, int XOFF = 0, int AOFF = 0, int RB0 = 0, int NX, int NA>
 __device__ __forceinline__ void chain_dual_h(const float* img, const f32x4 (&x)[NX], f32x4 (&acc)[NA], int lane, float w_inv) {
   static_assert(KS == 2, "the image holds 64 input features");
@@ -125,40 +152,11 @@ __device__ __forceinline__ void chain_dual_h(const float* img, const f32x4 (&x)[
     static_for<KS>([&]<int s>() {
       const char* u = base + (((s * 4 + q) ^ sw) << 3);
       a.h[s] = join_halves_h(*(const s16x4*)(u + roff), *(const s16x4*)(u + roff + plane));
-#ifdef M3G_DIAG_NO_AL   // timing diagnostic only (wrong results): no LDS reads of the low-part image
-      a.l[s] = a.h[s];
-#else
       a.l[s] = join_halves_h(*(const s16x4*)(u + roff + lo), *(const s16x4*)(u + roff + lo + plane));
-#endif
     });
     return a;
   };
-  // the first block's operands travel while the vector ALU finds the scale and splits x
-  DualA<KS> cur = fetch.template operator()<0>();
-  M3G_CHAIN_FENCE();
-  const EdgeScale sc = edge_scale<2 * KS, XOFF>(x);
-  const HalfB<KS> b = split_h<KS, XOFF>(x, sc.s);
-  const float inv = sc.inv * w_inv;
-  M3G_CHAIN_PRIO(1);
-  static_for<OB>([&]<int ob>() {
-    DualA<KS> nxt = cur;
-    if constexpr (ob + 1 < OB) nxt = fetch.template operator()<ob + 1>();
-    M3G_CHAIN_FENCE();
-    f32x4 t = {0.f, 0.f, 0.f, 0.f};
-    static_for<KS>([&]<int s>() {
-      t = mfma_f16(cur.h[s], b.hi[s], t);
-#ifndef M3G_DIAG_H1
-      t = mfma_f16(cur.h[s], b.lo[s], t);
-      t = mfma_f16(cur.l[s], b.hi[s], t);
-#elif defined(M3G_DIAG_H1_KEEP)   // ... with the low-part reads and splits kept alive: the MFMAs alone
-      asm volatile("" ::"v"(cur.l[s]), "v"(b.lo[s]));
-#endif
-    });
-    acc[AOFF + ob] = t * inv + acc[AOFF + ob];   // (vector form: the compiler emits two v_pk_fma_f32)
-    M3G_CHAIN_FENCE();
-    cur = nxt;
-  });
-  M3G_CHAIN_PRIO(0);
+  chain_dual_h_acc<OB, KS, XOFF, AOFF>(fetch, x, acc, w_inv, nullptr);
 }
 // `used` (optional): receives the per-edge scale the chain found for d, for a caller that stores d on the same scale (pack24_fixed)
 template <int OB, int KS, int ROWS, int DOFF = 0, int AOFF = 0, int KB0 = 0, int ND, int NA>
@@ -177,42 +175,12 @@ __device__ __forceinline__ void chain_dual_t_h(const float* img, const f32x4 (&d
       constexpr int r0 = (KB0 + 2 * s) * 2048, r1 = (KB0 + 2 * s + 1) * 2048;
       a.h[s] = join_halves_h(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(u + r0)),
                              __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(u + r1)));
-#ifdef M3G_DIAG_NO_AL   // timing diagnostic only (wrong results): no LDS reads of the low-part image
-      a.l[s] = a.h[s];
-#else
       a.l[s] = join_halves_h(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(u + r0 + lo)),
                              __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(u + r1 + lo)));
-#endif
     });
     return a;
   };
-  // the first block's operands travel while the vector ALU finds the scale and splits d
-  DualA<KS> cur = fetch.template operator()<0>();
-  M3G_CHAIN_FENCE();
-  const EdgeScale sc = edge_scale<2 * KS, DOFF>(d);
-  if (used) *used = sc;
-  const HalfB<KS> b = split_h<KS, DOFF>(d, sc.s);
-  const float inv = sc.inv * w_inv;
-  M3G_CHAIN_PRIO(1);
-  static_for<OB>([&]<int ob>() {
-    DualA<KS> nxt = cur;
-    if constexpr (ob + 1 < OB) nxt = fetch.template operator()<ob + 1>();
-    M3G_CHAIN_FENCE();
-    f32x4 t = {0.f, 0.f, 0.f, 0.f};
-    static_for<KS>([&]<int s>() {
-      t = mfma_f16(cur.h[s], b.hi[s], t);
-#ifndef M3G_DIAG_H1
-      t = mfma_f16(cur.h[s], b.lo[s], t);
-      t = mfma_f16(cur.l[s], b.hi[s], t);
-#elif defined(M3G_DIAG_H1_KEEP)   // ... with the low-part reads and splits kept alive: the MFMAs alone
-      asm volatile("" ::"v"(cur.l[s]), "v"(b.lo[s]));
-#endif
-    });
-    acc[AOFF + ob] = t * inv + acc[AOFF + ob];   // (vector form: the compiler emits two v_pk_fma_f32)
-    M3G_CHAIN_FENCE();
-    cur = nxt;
-  });
-  M3G_CHAIN_PRIO(0);
+  chain_dual_h_acc<OB, KS, DOFF, AOFF>(fetch, d, acc, w_inv, used);
 }
 
 // host: img receives ROWS*64 floats (hi part, then lo part); get(row, col) with col < 64

@@ -14,21 +14,13 @@ namespace m3g {
 __host__ __device__ inline int dual32_f(int m) { return (m & 3) | (((m >> 2) & 1) << 4) | (((m >> 3) & 1) << 3); }
 __host__ __device__ inline int dual32_index(int row, int col) { return row * 64 + (col ^ dual32_f(row & 15)); }
 
-#if defined(M3G_F32_STAGGER_PRIO)
-#define M3G_DUAL32_PRIO(p) do { if (p) { const int cls = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)); if (cls == 0) __builtin_amdgcn_s_setprio(3); else if (cls == 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); } else __builtin_amdgcn_s_setprio(0); } while (0)
-#elif !defined(M3G_NO_F32_CHAIN_PRIO)
-#define M3G_DUAL32_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#else
-#define M3G_DUAL32_PRIO(p) ((void)0)
-#endif
-
 // acc[AOFF + ob] += W[(RB0 + ob)*16 .. +16][0..64) . x[XOFF .. XOFF + 4)     (x: 64 input features in accumulator layout)
 template <int OB, int XOFF = 0, int AOFF = 0, int RB0 = 0, int NX, int NA>
 __device__ __forceinline__ void chain_dual32(const float* img, const f32x4 (&x)[NX], f32x4 (&acc)[NA], int lane) {
   static_assert(XOFF + 4 <= NX && AOFF + OB <= NA, "chain_dual32 operand out of range");
   const int m = lane & 15, q = lane >> 4;
   const int base = m * 64 + ((4 * q) ^ dual32_f(m));
-  M3G_DUAL32_PRIO(1);
+  __builtin_amdgcn_s_setprio(1);
   static_for<4>([&]<int blk>() {
     static_for<4>([&]<int r>() {
       const float b = x[XOFF + blk][r];
@@ -36,7 +28,7 @@ __device__ __forceinline__ void chain_dual32(const float* img, const f32x4 (&x)[
       static_for<OB>([&]<int ob>() { acc[AOFF + ob] = mfma16(p[(RB0 + ob) * 1024], b, acc[AOFF + ob]); });
     });
   });
-  M3G_DUAL32_PRIO(0);
+  __builtin_amdgcn_s_setprio(0);
 }
 
 // transposed: acc[AOFF + ob] (64 input-feature gradients, ob = 0..3) += sum_o W[o][ob*16 ..] d[o]; d holds NB 16-row blocks of
@@ -46,7 +38,7 @@ __device__ __forceinline__ void chain_dual32_t(const float* img, const f32x4 (&d
   static_assert(DOFF + NB <= ND && AOFF + 4 <= NA, "chain_dual32_t operand out of range");
   const int m = lane & 15, q = lane >> 4;
   const int base = q * 256 + (m ^ (((q & 1) << 4) | ((q >> 1) << 3)));
-  M3G_DUAL32_PRIO(1);
+  __builtin_amdgcn_s_setprio(1);
   static_for<NB>([&]<int blk>() {
     static_for<4>([&]<int r>() {
       const float b = d[DOFF + blk][r];
@@ -56,7 +48,7 @@ __device__ __forceinline__ void chain_dual32_t(const float* img, const f32x4 (&d
       });
     });
   });
-  M3G_DUAL32_PRIO(0);
+  __builtin_amdgcn_s_setprio(0);
 }
 
 // host: img receives rows*64 floats; get(row, col) with col < 64

@@ -15,27 +15,14 @@ namespace m3g {
 constexpr int kFwdLdsFloats = 8 * kTbSteps * 64 + 2 * (8 * 4 * 4 * 64 + 2 * (4 * 4 * 4 * 64) + 2 * 4 * 64 + 4 * 64) + 4 * 64;
 constexpr int kRevMlpFloats = 8 * 4 * 4 * 64 + 4 * (4 * 4 * 4 * 64) + 2 * 4 * 64 + 4 * 8 * 4 * 64 + 64 * 4;   // node-MLP reverse image
 constexpr int kRevEdgeFloats = kRevMlpFloats + 8 * kTbSteps * 64 + 8 * 4 * 64;                // + three-body images
-#ifndef M3G_WAVES_FWD
-#define M3G_WAVES_FWD 16        // forward kernel: 16 waves = 4 per SIMD (<= 128 VGPRs)
-#endif
-constexpr int kWaves = M3G_WAVES_FWD;
-#ifndef M3G_WAVES_FWD_H
-#define M3G_WAVES_FWD_H 12      // f16x3 forward: 3 per SIMD (<= 168 VGPRs), which pays for the A operands requested a row block ahead (chain_h)
-#endif
+constexpr int kWaves = 16;        // forward kernel: 16 waves = 4 per SIMD (<= 128 VGPRs)
+constexpr int kWavesFwdH = 12;    // f16x3 forward: 3 per SIMD (<= 168 VGPRs), which pays for the A operands requested a row block ahead (chain_h)
+constexpr int kWavesFwdBf = 12;   // bf16x3 forward: as the f16x3 kernel
 // waves per workgroup of the forward kernel by precision mode (kPrecF16x3 = 2, m3g_internal.h)
 template <int PREC>
-#ifndef M3G_WAVES_FWD_BF
-#define M3G_WAVES_FWD_BF 12     // bf16x3 forward: as the f16x3 kernel
-#endif
-constexpr int fwd_waves() { return PREC == kPrecF16x3 ? M3G_WAVES_FWD_H : PREC == kPrecBf16x3 ? M3G_WAVES_FWD_BF : kWaves; }
-#ifndef M3G_WAVES_REV_FUSED
-#define M3G_WAVES_REV_FUSED 8   // 2 waves per SIMD, 256 VGPRs, no spills (12 waves: 168 VGPRs and ~120 spilled, slower)
-#endif
-constexpr int kWavesRevFused = M3G_WAVES_REV_FUSED;
-#ifndef M3G_WAVES_REV
-#define M3G_WAVES_REV 12
-#endif
-constexpr int kWavesRev = M3G_WAVES_REV;   // reverse kernels hold layer-1 pre-activations across the recompute: 3 per SIMD (<= 168 VGPRs)
+constexpr int fwd_waves() { return PREC == kPrecF16x3 ? kWavesFwdH : PREC == kPrecBf16x3 ? kWavesFwdBf : kWaves; }
+constexpr int kWavesRevFused = 8;   // 2 waves per SIMD, 256 VGPRs, no spills (12 waves: 168 VGPRs and ~120 spilled, slower)
+constexpr int kWavesRev = 12;   // reverse kernels hold layer-1 pre-activations across the recompute: 3 per SIMD (<= 168 VGPRs)
 constexpr int kTileEdges = 16;
 constexpr int kTileFloats = 4 * 64 * 4;     // one 64-feature tile image: [4 blk][64 lanes][4]
 constexpr int kP1TileFloats = 8 * 64 * 4;   // layer-1 pre-activations of one MLP and tile: [8 blk][64 lanes][4]
@@ -43,19 +30,12 @@ constexpr int kP1TileFloats = 8 * 64 * 4;   // layer-1 pre-activations of one ML
 // chains on bf16x3 the matrix work is cheap, and recomputing both layers of both MLPs in the reverse kernels costs less
 // than streaming 2 KB of pre-activations per edge and block through HBM (measured history: DESIGN.md section 4).
 
-#ifdef M3G_USE_FWD_CHAIN_PRIO
-#define M3G_FWD_CHAIN_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#else
-#define M3G_FWD_CHAIN_PRIO(p) ((void)0)
-#endif
 // acc[AOFF + ob] += W(ob-th 16-row block, :) . x[XOFF .. XOFF + 2*KS)   (chain image: m3g_pack_mfma.hip)
 template <int OB, int KS, int XOFF = 0, int AOFF = 0, int NX, int NA>
 __device__ __forceinline__ void chain(const float* img, const f32x4 (&x)[NX], f32x4 (&acc)[NA], int lane) {
   static_assert(XOFF + 2 * KS <= NX && AOFF + OB <= NA, "chain operand out of range");
   const bf16x8* hi_img = reinterpret_cast<const bf16x8*>(img) + lane;
   const bf16x8* lo_img = hi_img + OB * KS * 64;
-  M3G_FWD_CHAIN_PRIO(1);
-#ifndef M3G_NO_BF16_CHAIN_PREFETCH
   // A operands of item (s, ob + 1) requested before the MFMAs of item (s, ob), as chain_h does in the f16x3 mode (bf16x3 forward
   // kernel with 12 waves: 0.426 -> 0.416 ms per step; 12 waves without it spill and are slower, 0.451)
   bf16x8 bh[KS], bl[KS];
@@ -69,26 +49,13 @@ __device__ __forceinline__ void chain(const float* img, const f32x4 (&x)[NX], f3
       nh = hi_img[(ob1 * KS + s1) * 64];
       nl = lo_img[(ob1 * KS + s1) * 64];
     }
-    __builtin_amdgcn_sched_barrier(0);
+    sched_fence();
     acc[AOFF + ob] = mfma_bf16(ah, bh[s], acc[AOFF + ob]);
     acc[AOFF + ob] = mfma_bf16(ah, bl[s], acc[AOFF + ob]);
     acc[AOFF + ob] = mfma_bf16(al, bh[s], acc[AOFF + ob]);
-    __builtin_amdgcn_sched_barrier(0);
+    sched_fence();
     ah = nh; al = nl;
   });
-#else
-  static_for<KS>([&]<int s>() {
-    bf16x8 bh, bl;
-    split8(x[XOFF + 2 * s], x[XOFF + 2 * s + 1], bh, bl);
-    static_for<OB>([&]<int ob>() {
-      const bf16x8 ah = hi_img[(ob * KS + s) * 64], al = lo_img[(ob * KS + s) * 64];
-      acc[AOFF + ob] = mfma_bf16(ah, bh, acc[AOFF + ob]);
-      acc[AOFF + ob] = mfma_bf16(ah, bl, acc[AOFF + ob]);
-      acc[AOFF + ob] = mfma_bf16(al, bh, acc[AOFF + ob]);
-    });
-  });
-#endif
-  M3G_FWD_CHAIN_PRIO(0);
 }
 
 // exact-fp32 chain on v_mfma_f32_16x16x4_f32: acc[AOFF + ob] += W(ob-th row block, :) . x[XOFF .. XOFF + NB) with the
@@ -98,36 +65,18 @@ __device__ __forceinline__ void chain(const float* img, const f32x4 (&x)[NX], f3
 // vector instruction of an older wave that is ready when the matrix pipe frees delays the next MFMA by its 4 issue cycles
 // (tools/mfma_f32_dep_probe.hip: 36 instead of 32 cycles per MFMA with one v_fma per MFMA in the stream, at 1, 2 and 4 waves
 // per SIMD).  Raised priority inside the chains lets the wave that feeds the matrix pipe win that arbitration.
-#if defined(M3G_F32_STAGGER_PRIO)
-// experiment: the waves that share a SIMD (wave ids w, w+4, w+8, ...) enter their chains at different priorities, so two
-// co-running chains do not split the matrix pipe evenly and leave it at the same moment
-__device__ __forceinline__ void f32_chain_prio_on() {
-  const int cls = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-  if (cls == 0) __builtin_amdgcn_s_setprio(3);
-  else if (cls == 1) __builtin_amdgcn_s_setprio(2);
-  else __builtin_amdgcn_s_setprio(1);
-}
-#define M3G_F32_CHAIN_PRIO(p) do { if (p) f32_chain_prio_on(); else __builtin_amdgcn_s_setprio(0); } while (0)
-#elif defined(M3G_F32_INVERSE_PRIO)
-// experiment: the vector phases run at raised priority, the chains at 0
-#define M3G_F32_CHAIN_PRIO(p) __builtin_amdgcn_s_setprio((p) ? 0 : M3G_F32_INVERSE_PRIO)
-#elif !defined(M3G_NO_F32_CHAIN_PRIO)
-#define M3G_F32_CHAIN_PRIO(p) __builtin_amdgcn_s_setprio(p)
-#else
-#define M3G_F32_CHAIN_PRIO(p) ((void)0)
-#endif
 // NBT / KB0: the image holds NBT k-blocks per row block, this call consumes blocks KB0 .. KB0 + NB of it (a slice of the k range)
 template <int OB, int NB, int XOFF = 0, int AOFF = 0, int NBT = NB, int KB0 = 0, int NX, int NA>
 __device__ __forceinline__ void chain_f32(const float* img, const f32x4 (&x)[NX], f32x4 (&acc)[NA], int lane) {
   static_assert(XOFF + NB <= NX && AOFF + OB <= NA && KB0 + NB <= NBT, "chain_f32 operand out of range");
-  M3G_F32_CHAIN_PRIO(1);
+  __builtin_amdgcn_s_setprio(1);
   static_for<NB>([&]<int blk>() {
     static_for<4>([&]<int r>() {
       const float b = x[XOFF + blk][r];
       static_for<OB>([&]<int ob>() { acc[AOFF + ob] = mfma16(img[(ob * (4 * NBT) + (KB0 + blk) * 4 + r) * 64 + lane], b, acc[AOFF + ob]); });
     });
   });
-  M3G_F32_CHAIN_PRIO(0);
+  __builtin_amdgcn_s_setprio(0);
 }
 
 // Precision modes of the dense chains (plan option "precision"):
@@ -147,7 +96,6 @@ template <int OB, int KS, class OUT>
 __device__ __forceinline__ void chain_h(const float* img, const HalfB<KS>& b, int lane, OUT&& out) {
   const f16x8* hi_img = reinterpret_cast<const f16x8*>(img) + lane;
   const f16x8* lo_img = hi_img + OB * KS * 64;
-#ifndef M3G_NO_FWD_CHAIN_PREFETCH
   // A operands of row block ob + 1 requested before the MFMAs of row block ob (as the dual-image chains, m3g_dual_chain.h:
   // the compiler's own order leaves two or three MFMAs between a ds_read and its use, a third of the LDS round trip; forward kernel
   // with 12 waves 0.460 -> 0.427 ms per step -- at 16 waves = 128 VGPRs the extra 16 registers spill and it is slower, 0.480)
@@ -156,42 +104,7 @@ __device__ __forceinline__ void chain_h(const float* img, const HalfB<KS>& b, in
     static_for<KS>([&]<int s>() { a.h[s] = hi_img[(ob * KS + s) * 64]; a.l[s] = lo_img[(ob * KS + s) * 64]; });
     return a;
   };
-  DualA<KS> cur = fetch.template operator()<0>();
-  static_for<OB>([&]<int ob>() {
-    DualA<KS> nxt = cur;
-    if constexpr (ob + 1 < OB) nxt = fetch.template operator()<ob + 1>();
-    __builtin_amdgcn_sched_barrier(0);
-    f32x4 t = {0.f, 0.f, 0.f, 0.f};
-    static_for<KS>([&]<int s>() {
-      t = mfma_f16(cur.h[s], b.hi[s], t);
-      t = mfma_f16(cur.h[s], b.lo[s], t);
-      t = mfma_f16(cur.l[s], b.hi[s], t);
-    });
-    out.template operator()<ob>(t);
-    __builtin_amdgcn_sched_barrier(0);
-    cur = nxt;
-  });
-#else
-  static_for<OB>([&]<int ob>() {
-    f32x4 t = {0.f, 0.f, 0.f, 0.f};
-    static_for<KS>([&]<int s>() {
-      const f16x8 ah = hi_img[(ob * KS + s) * 64], al = lo_img[(ob * KS + s) * 64];
-#ifdef M3G_DIAG_NO_AL   // timing diagnostic only (wrong results): no LDS reads of the low-part image
-      const f16x8& al_ = ah;
-#else
-      const f16x8& al_ = al;
-#endif
-      t = mfma_f16(ah, b.hi[s], t);
-#ifndef M3G_DIAG_H1   // timing diagnostic only (wrong results): one product per k-step instead of three
-      t = mfma_f16(ah, b.lo[s], t);
-      t = mfma_f16(al_, b.hi[s], t);
-#elif defined(M3G_DIAG_H1_KEEP)   // ... with the low-part reads and splits kept alive: the MFMAs alone
-      asm volatile("" ::"v"(al_), "v"(b.lo[s]));
-#endif
-    });
-    out.template operator()<ob>(t);
-  });
-#endif
+  chain_h_blocks<OB, KS>(fetch.template operator()<0>(), b, fetch, out);
 }
 // acc[AOFF + ob] += (W x)[ob-th row block] in true units: the f16x3 counterpart of chain_p (scale of x taken over its 2 KS blocks)
 template <int OB, int KS, int XOFF = 0, int AOFF = 0, int NX, int NA>
@@ -215,19 +128,11 @@ __device__ __forceinline__ void chain_p(const float* img, const f32x4 (&x)[NX], 
 // bias image: lanes < 16 of block ob carry b[ob*16 + lane] (built as the A operand of a k-step against a constant one).
 // The accumulator registers of lane (m, q) are rows 4q .. 4q+3 of the block, so the same image read as one 16-byte LDS
 // broadcast per block initialises the accumulators directly -- identical values, no MFMA.
-#ifdef M3G_BIAS_MFMA
-template <int OB, int AOFF, int NA>
-__device__ __forceinline__ void bias_step(const float* img, f32x4 (&acc)[NA], int lane) {
-  const float one = lane < 16 ? 1.f : 0.f;
-  static_for<OB>([&]<int ob>() { acc[AOFF + ob] = mfma16(img[ob * 64 + lane], one, f32x4{0.f, 0.f, 0.f, 0.f}); });
-}
-#else
 template <int OB, int AOFF, int NA>
 __device__ __forceinline__ void bias_step(const float* img, f32x4 (&acc)[NA], int lane) {
   const int q = lane >> 4;
   static_for<OB>([&]<int ob>() { acc[AOFF + ob] = *(const f32x4*)(img + ob * 64 + 4 * q); });
 }
-#endif
 
 // Persistent tile queue.  Static over workgroups, dynamic inside one:
 //   * workgroups with the same blockIdx % 8 share an XCD (speed only, never correctness); that label owns one
@@ -331,7 +236,6 @@ __device__ __forceinline__ SegMasks seg_masks(int ci, int lane) {
                : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]),  \
                  "+v"(x[9]), "+v"(x[10]), "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]), "+v"(x[15])                     \
                : "v"(m))
-#ifndef M3G_NO_ASM_SCAN
 __device__ __forceinline__ void seg_scan(f32x4 (&v)[4], const SegMasks& k) {
   float x[16];
   static_for<16>([&]<int i>() { x[i] = v[i >> 2][i & 3]; });
@@ -341,7 +245,6 @@ __device__ __forceinline__ void seg_scan(f32x4 (&v)[4], const SegMasks& k) {
   M3G_SCAN_STEP16(8, k.m8);
   static_for<16>([&]<int i>() { v[i >> 2][i & 3] = x[i]; });
 }
-#endif
 template <int N>
 __device__ __forceinline__ void seg_scan(f32x4 (&v)[N], const SegMasks& k) {
   static_for<N>([&]<int b>() {
@@ -473,17 +376,13 @@ __device__ __forceinline__ void tb_preact_p(const float* tbimg, const TbIn<PREC,
     static_for<8>([&]<int ob>() {
       f16x8 nh = ah, nl = al;
       if constexpr (ob + 1 < 8) { nh = hi[(ob + 1) * 32]; nl = lo[(ob + 1) * 32]; }
-#ifndef M3G_NO_FWD_CHAIN_PREFETCH
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      sched_fence();
       f32x4 t = {0.f, 0.f, 0.f, 0.f};
       t = mfma_f16(ah, in.hi, t);
       t = mfma_f16(ah, in.lo, t);
       t = mfma_f16(al, in.hi, t);
       p[ob] = t * in.inv;
-#ifndef M3G_NO_FWD_CHAIN_PREFETCH
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      sched_fence();
       ah = nh; al = nl;
     });
   } else {
@@ -494,10 +393,6 @@ __device__ __forceinline__ void tb_preact_p(const float* tbimg, const TbIn<PREC,
 // layer-1 accumulators start from the gathered per-node tables TA[i] + TB[j] (x_i / x_j parts, bias folded)
 __device__ __forceinline__ void gather_tables(const float* __restrict__ TA, const float* __restrict__ TB, int mlp, int64_t ci,
                                               int64_t cj, int qd, f32x4 (&p1)[8]) {
-#ifdef M3G_DIAG_NO_GATHER   // timing diagnostic only (wrong results): what the table gathers cost
-  static_for<8>([&]<int ob>() { p1[ob] = f32x4{0.1f, 0.2f, 0.3f, 0.4f}; });
-  return;
-#endif
   const float* ta = TA + ci * (4 * kDP) + mlp * (2 * kDP) + 4 * qd;
   const float* tb = TB + cj * (4 * kDP) + mlp * (2 * kDP) + 4 * qd;
   static_for<8>([&]<int ob>() { p1[ob] = *(const f32x4*)(ta + ob * 16) + *(const f32x4*)(tb + ob * 16); });
@@ -551,11 +446,7 @@ __device__ __forceinline__ void store_dh(float* dh, int64_t edge, int64_t E, f32
 // instead of filling the 16 wave slots of a few CUs: a wave alone on its SIMD finishes a tile about three times sooner than
 // four waves sharing the SIMD finish theirs, and a small system's step is the serial latency of its kernels.
 inline int grid_for_tiles(int64_t tiles, int /*waves*/ = kWaves) {
-#ifdef M3G_GRID_PACKED   // round-1 rule: fill the wave slots of ceil(tiles / waves) CUs
-  int64_t wgs = (tiles + kWaves - 1) / kWaves;
-#else
   int64_t wgs = tiles;
-#endif
   wgs = (wgs + 7) / 8 * 8;
   if (wgs < 8) wgs = 8;
   if (wgs > 256) wgs = 256;

@@ -12,7 +12,7 @@
 //     weight images (m3g_pack_mfma.hip, m3g_dual_image.h), which a workgroup copies into LDS once and every wave
 //     re-reads as the A operand;
 //   * layer-1 accumulators start from the gathered per-node tables TA[i] + TB[j] (x_i / x_j parts, bias folded);
-//     layer-2 biases enter as one extra k-step against a constant-one operand;
+//     layer-2 accumulators start from the bias image, one 16-byte LDS broadcast per block (bias_step);
 //   * a lane's 4 accumulator registers are 4 consecutive features, so every tile load/store is a 16-byte access
 //     (1 KiB per wave instruction);
 //   * the 16 edge lanes are a DPP row and a centre's edges are consecutive, so sums over a centre's edges (messages in
@@ -26,25 +26,13 @@
 
 namespace m3g {
 
-// the fp32 forward kernel evaluates its activations on value PAIRS too (packed fp32 instructions; round 4: 1,218 -> 1,038 vector
-// instructions per tile, no spills at its 128-register budget any more, forward -2 % same-box; -DM3G_F32_SCALAR_ACT for A/B)
-#ifndef M3G_F32_SCALAR_ACT
-constexpr bool kF32Pairs = true;
-#else
-constexpr bool kF32Pairs = false;
-#endif
-
 // ---------------------------------------------------------------------------------------------- forward
 // both layers of one conv GatedMLP from the edge-feature tile x: p1 = layer-1 pre-activations (dense 0..3, gate 4..7),
 // p2 = layer-2 pre-activations.  `w1c/w2d/w2g/b2` are offsets of the forward images inside `lds`.
 // p1_out != nullptr: the layer-1 pre-activations (table rows + bias + W1c e) are stored for the reverse pass, which then
 // starts from them instead of gathering the tables and recomputing the layer ([8 blk][64 lanes][4] per tile and MLP)
 // saved activations are written once and read once, a whole reverse pass later: streaming stores keep them out of L2
-#ifndef M3G_SAVE_PLAIN_STORE
-#define M3G_SAVE_STORE(ptr, val) __builtin_nontemporal_store((val), (f32x4*)(ptr))
-#else
-#define M3G_SAVE_STORE(ptr, val) (*(f32x4*)(ptr) = (val))
-#endif
+__device__ __forceinline__ void save_store(float* ptr, const f32x4& val) { __builtin_nontemporal_store(val, (f32x4*)ptr); }
 // SAVE (compile time: a run-time choice doubles the code paths and spills): 0 nothing saved, 1 p1 -> p1_out, 2 SiLU'(p1) ->
 // p1_out and p2 -> p2_out
 template <bool KEEP_P1, int PREC, int SAVE = 0>
@@ -59,25 +47,17 @@ __device__ __forceinline__ void mlp_preacts(const float* lds, int w1c, int w2d, 
     // pre-activations -- SiLU' costs three more vector instructions here, next to the sigmoid SiLU evaluates anyway
     static_for<8>([&]<int ob>() {
       f32x4 ds;
-#ifndef M3G_F32_SCALAR_ACT
       static_for<2>([&]<int k>() {   // value pairs on packed fp32 instructions (silu_pair: SiLU and SiLU' from one sigmoid)
         f32x2 act, der;
         silu_pair(f32x2{p1[ob][2 * k], p1[ob][2 * k + 1]}, act, der);
         p1[ob][2 * k] = act[0]; p1[ob][2 * k + 1] = act[1];
         ds[2 * k] = der[0]; ds[2 * k + 1] = der[1];
       });
-#else
-      static_for<4>([&]<int r>() {
-        const float p = p1[ob][r], sg = fsigmoid(p);
-        p1[ob][r] = p * sg;
-        ds[r] = sg * (1.f + p * (1.f - sg));
-      });
-#endif
-      M3G_SAVE_STORE(p1_out + ob * 256, ds);
+      save_store(p1_out + ob * 256, ds);
     });
     chain_p<PREC, 4, 2, 0, 0>(lds + w2d, p1, p2, lane, w_inv);
     chain_p<PREC, 4, 2, 4, 4>(lds + w2g, p1, p2, lane, w_inv);
-    static_for<8>([&]<int ob>() { M3G_SAVE_STORE(p2_out + ob * 256, p2[ob]); });
+    static_for<8>([&]<int ob>() { save_store(p2_out + ob * 256, p2[ob]); });
     return;
   }
   if (KEEP_P1) {
@@ -120,7 +100,9 @@ __device__ __forceinline__ void mlp_forward_mfma(const float* lds, const MfmaMlp
   st.template mark<S0 + 1>();  // both layers
   static_for<4>([&]<int ob>() {
     out[ob] = mfma16(lds[L.wl + ob * 64 + lane], hb, f32x4{0.f, 0.f, 0.f, 0.f});
-    if constexpr (PREC == kPrecF16x3 || (kF32Pairs && PREC == kPrecF32)) {
+    // the f16x3 and fp32 kernels evaluate the gate on value PAIRS (packed fp32 instructions; fp32 forward, round 4: 1,218 -> 1,038
+    // vector instructions per tile, no spills at its 128-register budget any more, -2 % same-box)
+    if constexpr (PREC == kPrecF16x3 || PREC == kPrecF32) {
       static_for<2>([&]<int k>() {
         const f32x2 v = gated_pair(f32x2{p2[ob][2 * k], p2[ob][2 * k + 1]}, f32x2{p2[4 + ob][2 * k], p2[4 + ob][2 * k + 1]}) *
                         f32x2{out[ob][2 * k], out[ob][2 * k + 1]};
@@ -143,9 +125,6 @@ __global__ void __launch_bounds__(64 * fwd_waves<PREC>()) k_edge_block_mfma(FwdA
   const int lane = threadIdx.x & 63, qd = lane >> 4;
   TileQueue queue(a.tiles, q_head);
   Stamps<ST> st;
-#ifdef M3G_FWD_STATIC_PRIO
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= M3G_FWD_STATIC_PRIO) __builtin_amdgcn_s_setprio(1);
-#endif
   int ticket = queue.fetch(lane);
   if (ticket >= queue.count) return;
   int ci_i, cj_i;
@@ -193,7 +172,7 @@ __global__ void __launch_bounds__(64 * fwd_waves<PREC>()) k_edge_block_mfma(FwdA
     {  // three-body gated update (nn/interaction.py:220-221)
       f32x4 p[8];
       tb_preact_p<PREC, TBS>(lds + L.tb, tbin, p, lv);
-      if constexpr (PREC == kPrecF16x3 || (kF32Pairs && PREC == kPrecF32)) {
+      if constexpr (PREC == kPrecF16x3 || PREC == kPrecF32) {
         static_for<4>([&]<int blk>() {
           static_for<2>([&]<int k>() {
             const f32x2 v = gated_pair(f32x2{p[blk][2 * k], p[blk][2 * k + 1]}, f32x2{p[4 + blk][2 * k], p[4 + blk][2 * k + 1]});
@@ -481,12 +460,7 @@ __device__ __forceinline__ void mlp_preacts_dual(const float* lds, const MfmaMlp
 
 // Scheduling fence between the phases of the fused reverse kernel: the machine scheduler otherwise interleaves
 // neighbouring phases to hide latency inside ONE wave, which inflates live ranges past the 168 registers that allow a
-// third wave per SIMD -- and a third wave hides more latency than the interleaving does.
-#ifndef M3G_NO_SCHED_FENCE
-#define M3G_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define M3G_SCHED_FENCE() ((void)0)
-#endif
+// third wave per SIMD -- and a third wave hides more latency than the interleaving does (the sched_fence() calls below).
 
 // reverse of one conv GatedMLP at input tile x (recomputing both layers), dual-image version of mlp_reverse_mfma.
 // The dense and the gate branch are independent between layer 1 and the final product, so each is carried through
@@ -503,14 +477,13 @@ __device__ __forceinline__ void mlp_reverse_dual(const float* lds, const MfmaMlp
   f32x4 p1[8], d2[8];
   gather_tables(a.TA, a.TB, mlp, ci, cj, qd, p1);
   cdual<PREC, 8, 2, 128>(lds + L.w1c, x, p1, lane, a.w_inv);
-  M3G_SCHED_FENCE();
+  sched_fence();
   st.template mark<S0>();       // inputs arrived, table gather, layer 1
   bias_step<4, 0>(lds + L.b2, d2, lane);
   bias_step<4, 4>(lds + L.b2 + 4 * 64, d2, lane);
   static_for<2>([&]<int half>() {   // 0: dense branch (p1[0..3] -> d2[0..3]), 1: gate branch
     f32x4 hid[4];
     static_for<4>([&]<int ob>() {
-#ifndef M3G_NO_PAIR_ACT
       static_for<2>([&]<int k>() {
         f32x4& pv = p1[4 * half + ob];
         f32x2 act, der;
@@ -518,16 +491,9 @@ __device__ __forceinline__ void mlp_reverse_dual(const float* lds, const MfmaMlp
         hid[ob][2 * k] = act[0]; hid[ob][2 * k + 1] = act[1];
         pv[2 * k] = der[0]; pv[2 * k + 1] = der[1];   // p1 is only needed again as SiLU'(p1)
       });
-#else
-      static_for<4>([&]<int r>() {
-        const float p = p1[4 * half + ob][r], sg = fsigmoid(p);
-        hid[ob][r] = p * sg;
-        p1[4 * half + ob][r] = sg * (1.f + p * (1.f - sg));   // p1 is only needed again as SiLU'(p1)
-      });
-#endif
     });
     cdual<PREC, 4, 2, 64, 0, 4 * half>(lds + (half == 0 ? L.w2d : L.w2g), hid, d2, lane, a.w_inv);
-    M3G_SCHED_FENCE();
+    sched_fence();
   });
   st.template mark<S0 + 1>();   // activations, layer 2
   // W_l h on the matrix pipe (4 small MFMAs, as the forward kernel) instead of a 4-term dot per element on the vector ALU
@@ -535,20 +501,13 @@ __device__ __forceinline__ void mlp_reverse_dual(const float* lds, const MfmaMlp
   const float hb_sel = qd == 0 ? hv[0] : qd == 1 ? hv[1] : qd == 2 ? hv[2] : hv[3];
   static_for<4>([&]<int ob>() {
     const f32x4 sl = mfma16(lds[L.wld + ob * 64 + lane], hb_sel, f32x4{0.f, 0.f, 0.f, 0.f});
-#ifndef M3G_NO_PAIR_ACT
     // value pairs on packed fp32 instructions (silu_pair): out = SiLU(p2d) sg(p2g) s_lin
     static_for<2>([&]<int k>() {
       const f32x2 p2d = {d2[ob][2 * k], d2[ob][2 * k + 1]}, p2g = {d2[4 + ob][2 * k], d2[4 + ob][2 * k + 1]};
       const f32x2 du = {d_upd[ob][2 * k], d_upd[ob][2 * k + 1]}, s_lin = {sl[2 * k], sl[2 * k + 1]};
       f32x2 sd, dsd;
       silu_pair(p2d, sd, dsd);
-#ifdef M3G_DIAG_CHEAP_ACT
-      const f32x2 sg = p2g * 0.25f + 0.5f;
-#else
-      const f32x2 tg = p2g * -1.4426950408889634f;
-      const f32x2 dg = f32x2{__builtin_amdgcn_exp2f(tg[0]), __builtin_amdgcn_exp2f(tg[1])} + 1.f;
-      const f32x2 sg = {__builtin_amdgcn_rcpf(dg[0]), __builtin_amdgcn_rcpf(dg[1])};
-#endif
+      const f32x2 sg = sigmoid_pair(p2g);
       const f32x2 a_g = du * sg;            // dL/d(out) sg(p2g)
       const f32x2 d_s = a_g * sd;           // dL/d(s_lin)
       const f32x2 d_o = a_g * s_lin;
@@ -563,23 +522,10 @@ __device__ __forceinline__ void mlp_reverse_dual(const float* lds, const MfmaMlp
       d2[ob][2 * k] = dd[0]; d2[ob][2 * k + 1] = dd[1];
       d2[4 + ob][2 * k] = dgt[0]; d2[4 + ob][2 * k + 1] = dgt[1];
     });
-#else
-    static_for<4>([&]<int r>() {
-      const float p2d = d2[ob][r], p2g = d2[4 + ob][r];
-      const f32x4 w = *(const f32x4*)(lds + L.wl + (ob * 16 + 4 * qd + r) * 4);
-      const float s_lin = sl[r];
-      const float sg = fsigmoid(p2g), sgd = fsigmoid(p2d), sd = p2d * sgd;
-      const float du = d_upd[ob][r];
-      const float d_out = du * s_lin, d_s = du * sd * sg;
-      dhv[0] += d_s * w[0]; dhv[1] += d_s * w[1]; dhv[2] += d_s * w[2]; dhv[3] += d_s * w[3];
-      d2[ob][r] = d_out * sg * (sgd * (1.f + p2d * (1.f - sgd)));
-      d2[4 + ob][r] = d_out * sd * sg * (1.f - sg);
-    });
-#endif
     asm volatile("" : "+v"(dhv[0]), "+v"(dhv[1]), "+v"(dhv[2]), "+v"(dhv[3]));   // see mlp_reverse_mfma
   });
   zero(contrib);
-  M3G_SCHED_FENCE();
+  sched_fence();
   st.template mark<S0 + 2>();   // gating derivatives
   static_for<2>([&]<int half>() {
     f32x4 dp1[4];
@@ -617,7 +563,7 @@ __device__ __forceinline__ void mlp_reverse_dual(const float* lds, const MfmaMlp
       seg_scan(dp1, sk);
       seg_store<MLP * 8 + 4 * half>(dp1, sk, a.seg_head, a.seg_first, tile, ci, qd);
     }
-    M3G_SCHED_FENCE();
+    sched_fence();
     st.template mark<S0 + 3 + half>();   // transposed chains, dp1 stores, per-centre scan of one half
   });
 }
@@ -630,9 +576,6 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_fused(RevArgs a, MfmaRe
   load_image(lds, a.img, kRevFusedFloats, q_head);
   const int lane = threadIdx.x & 63, qd = lane >> 4;
   TileQueue queue(a.tiles, q_head);
-#ifdef M3G_REV_STATIC_PRIO
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= M3G_REV_STATIC_PRIO) __builtin_amdgcn_s_setprio(1);
-#endif
   int ticket = queue.fetch(lane);
   if (ticket >= queue.count) return;
   int ci_i, cj_i;
@@ -683,7 +626,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_fused(RevArgs a, MfmaRe
     }
     // the opaque copy also pins the order: without it the scheduler hoists the e1 computation above the node phase
     asm volatile("" : "+v"(lv));
-    M3G_SCHED_FENCE();
+    sched_fence();
     if (FIRST) {
       const float hb = a.h[ec * kRP + qd];
       static_for<4>([&]<int blk>() {

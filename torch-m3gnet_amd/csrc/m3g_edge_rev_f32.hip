@@ -40,16 +40,7 @@ MfmaRevF32Layout mfma_rev_f32_layout() {
 }
 
 constexpr int kRevF32Floats = 8 * kTbSteps * 64 + 32 * 64 + 2 * (2 * 64 * 64 + 4 * 32 * 64 + 2 * 4 * 64 + 64 * 4 + 4 * 64) + 4 * 64 + 64 * 4;
-#ifndef M3G_WAVES_REV_F32
-#define M3G_WAVES_REV_F32 8
-#endif
-constexpr int kWavesRevF32 = M3G_WAVES_REV_F32;
-
-#ifndef M3G_NO_SCHED_FENCE
-#define M3G_F32_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define M3G_F32_FENCE() ((void)0)
-#endif
+constexpr int kWavesRevF32 = 8;
 
 // reverse of one conv GatedMLP from its saved layer-1 pre-activations: d_upd = dL/d(output) is pulled back; returns
 // contrib = W1c^T dL/dp1 and accumulates dL/dh into dhv; NEED_DP1: stores the dL/dp1 rows (x_j half of the node reverse) and
@@ -79,15 +70,16 @@ __device__ __forceinline__ void mlp_reverse_f32(const float* lds, const MfmaMlpR
         });
       });
       chain_dual32<4, 0, 4 * half>(lds + (half == 0 ? L.w2d : L.w2g), hid, d2, lane);
-      M3G_F32_FENCE();
+      sched_fence();
     });
   }
   // gating derivatives; W_l h on the matrix pipe (4 small MFMAs), dL/dh on the vector ALU
   const float hb_sel = qd == 0 ? hv[0] : qd == 1 ? hv[1] : qd == 2 ? hv[2] : hv[3];
   static_for<4>([&]<int ob>() {
     const f32x4 sl = mfma16(lds[L.wld + ob * 64 + lane], hb_sel, f32x4{0.f, 0.f, 0.f, 0.f});
-#ifndef M3G_F32_SCALAR_ACT   // (round 4: 1,885 -> 1,457 vector instructions per tile, 211 -> 200 VGPRs, reverse -0.9 % same-box; -DM3G_F32_SCALAR_ACT for A/B)
-    static_for<2>([&]<int k>() {   // value pairs on packed fp32 instructions (as the f16x3 fused kernel evaluates them)
+    // value pairs on packed fp32 instructions, as the f16x3 fused kernel evaluates them (round 4, against one value at a time:
+    // 1,885 -> 1,457 vector instructions per tile, 211 -> 200 VGPRs, reverse -0.9 % same-box)
+    static_for<2>([&]<int k>() {
       const f32x2 p2d = {d2[ob][2 * k], d2[ob][2 * k + 1]}, p2g = {d2[4 + ob][2 * k], d2[4 + ob][2 * k + 1]};
       const f32x2 du = {d_upd[ob][2 * k], d_upd[ob][2 * k + 1]}, s_lin = {sl[2 * k], sl[2 * k + 1]};
       f32x2 sd, dsd;
@@ -107,25 +99,12 @@ __device__ __forceinline__ void mlp_reverse_f32(const float* lds, const MfmaMlpR
       d2[ob][2 * k] = dd[0]; d2[ob][2 * k + 1] = dd[1];
       d2[4 + ob][2 * k] = dgt[0]; d2[4 + ob][2 * k + 1] = dgt[1];
     });
-#else
-    static_for<4>([&]<int r>() {
-      const float p2d = d2[ob][r], p2g = d2[4 + ob][r];
-      const f32x4 w = *(const f32x4*)(lds + L.wl + (ob * 16 + 4 * qd + r) * 4);
-      const float s_lin = sl[r];
-      const float sg = fsigmoid(p2g), sgd = fsigmoid(p2d), sd = p2d * sgd;
-      const float du = d_upd[ob][r];
-      const float d_out = du * s_lin, d_s = du * sd * sg;
-      dhv[0] += d_s * w[0]; dhv[1] += d_s * w[1]; dhv[2] += d_s * w[2]; dhv[3] += d_s * w[3];
-      d2[ob][r] = d_out * sg * (sgd * (1.f + p2d * (1.f - sgd)));
-      d2[4 + ob][r] = d_out * sd * sg * (1.f - sg);
-    });
-#endif
     // pin the running dL/dh sums: otherwise LLVM sinks the accumulation chain to its only use at the end of the kernel and
     // keeps every w / sd / sg temporary alive
     asm volatile("" : "+v"(dhv[0]), "+v"(dhv[1]), "+v"(dhv[2]), "+v"(dhv[3]));
   });
   zero(contrib);
-  M3G_F32_FENCE();
+  sched_fence();
   static_for<2>([&]<int half>() {
     f32x4 dp1[4];
     zero(dp1);
@@ -144,7 +123,7 @@ __device__ __forceinline__ void mlp_reverse_f32(const float* lds, const MfmaMlpR
       seg_scan(dp1, sk);
       seg_store<MLP * 8 + 4 * half>(dp1, sk, a.seg_head, a.seg_first, tile, ci, qd);
     }
-    M3G_F32_FENCE();
+    sched_fence();
   });
 }
 
@@ -205,10 +184,6 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_f32(RevArgs a, MfmaRevF
       static_for<4>([&]<int blk>() { dmsg[blk] = *(const f32x4*)(xrow + blk * 16); });
       f32x4 d2n[8];
       if constexpr (SAVED_P2) load_p2(a, tile, 1, d2n);
-#ifdef M3G_P2_PREFETCH   // measured: no effect (1.011 vs 1.003 ms per step), the SIMD's other wave already covers that latency
-      // the edge MLP's saved rows are requested now, a whole MLP reverse ahead of their use (32 registers; the kernel has them)
-      if constexpr (SAVED_P2) load_p2(a, tile, 0, d2e);
-#endif
       mlp_reverse_f32<NEED_DP1, 1, SAVED_P2>(lds, L.mlp[1], a, edge, drow, tile, ci, sk, hv, dmsg, contrib, dhv, lv, d2n);
     }
     // dL/d e2 = what flows in from later blocks + the node MLP's contribution
@@ -218,11 +193,11 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_f32(RevArgs a, MfmaRevF
       static_for<4>([&]<int blk>() { de[blk] = load_tile4(de_tile + blk * 256) + contrib[blk]; });
     }
     asm volatile("" : "+v"(lv));
-    M3G_F32_FENCE();
+    sched_fence();
     // edge-update MLP (nn/conv.py:68-75)
-#ifndef M3G_P2_PREFETCH
+    // (requesting the edge MLP's saved rows a whole MLP reverse ahead: no effect, 1.011 vs 1.003 ms per step -- the SIMD's other
+    // wave already covers that latency)
     if constexpr (SAVED_P2) load_p2(a, tile, 0, d2e);
-#endif
     mlp_reverse_f32<NEED_DP1, 0, SAVED_P2>(lds, L.mlp[0], a, edge, drow, tile, ci, sk, hv, de, contrib, dhv, lv, d2e);
     static_for<4>([&]<int blk>() {  // dL/d e1 = dL/d e2 + contribution
       de[blk] += contrib[blk];
@@ -244,7 +219,6 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_f32(RevArgs a, MfmaRevF
     // three-body gated update, reverse (nn/interaction.py:220-221)
     f32x4 d8[8];
     tb_preact<TBS>(lds + L.tb, mb, d8, lv);
-#ifndef M3G_F32_SCALAR_ACT
     static_for<4>([&]<int blk>() {
       static_for<2>([&]<int k>() {
         f32x2 sd, dsd;
@@ -256,15 +230,6 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_f32(RevArgs a, MfmaRevF
         d8[4 + blk][2 * k] = dgt[0]; d8[4 + blk][2 * k + 1] = dgt[1];
       });
     });
-#else
-    static_for<4>([&]<int blk>() {
-      static_for<4>([&]<int r>() {
-        const float p = d8[blk][r], sgd = fsigmoid(p), sg = fsigmoid(d8[4 + blk][r]);
-        d8[blk][r] = de[blk][r] * sg * (sgd * (1.f + p * (1.f - sgd)));
-        d8[4 + blk][r] = de[blk][r] * (p * sgd) * sg * (1.f - sg);
-      });
-    });
-#endif
     f32x4 dmv[1];
     zero(dmv);
     chain_f32<1, 8>(lds + L.tbT, d8, dmv, lv);

@@ -67,7 +67,7 @@ template <int SAVE>
 __device__ __forceinline__ f32x4 mlp_forward_split(const FwdMlpA& A, const f32x4 (&t1)[2], const f32x4 (&x)[4], float hb, float* hs, int w,
                                                    int lane, float* p1_out, float* p2_out) {
   f32x4 p1d = t1[0], p1g = t1[1];
-  M3G_F32_CHAIN_PRIO(1);
+  __builtin_amdgcn_s_setprio(1);
   static_for<4>([&]<int blk>() {
     static_for<4>([&]<int r>() {
       const float b = x[blk][r];
@@ -75,7 +75,7 @@ __device__ __forceinline__ f32x4 mlp_forward_split(const FwdMlpA& A, const f32x4
       p1g = mfma16(A.w1[1][blk * 4 + r], b, p1g);
     });
   });
-  M3G_F32_CHAIN_PRIO(0);
+  __builtin_amdgcn_s_setprio(0);
   if constexpr (SAVE == 2) {
     f32x4 dsd, dsg;
     static_for<2>([&]<int k>() {
@@ -99,10 +99,10 @@ __device__ __forceinline__ f32x4 mlp_forward_split(const FwdMlpA& A, const f32x4
   f32x4 hid[8];
   static_for<8>([&]<int ob>() { hid[ob] = *(const f32x4*)(hs + ob * 256 + lane * 4); });
   f32x4 p2d = A.b2[0], p2g = A.b2[1];
-  M3G_F32_CHAIN_PRIO(1);
+  __builtin_amdgcn_s_setprio(1);
   chain_reg16<0>(A.w2[0], hid, p2d);
   chain_reg16<4>(A.w2[1], hid, p2g);
-  M3G_F32_CHAIN_PRIO(0);
+  __builtin_amdgcn_s_setprio(0);
   if constexpr (SAVE == 2) {
     __builtin_nontemporal_store(p2d, (f32x4*)(p2_out + w * 256));
     __builtin_nontemporal_store(p2g, (f32x4*)(p2_out + (4 + w) * 256));

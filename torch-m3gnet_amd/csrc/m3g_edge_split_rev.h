@@ -94,12 +94,12 @@ __device__ __forceinline__ f32x4 mlp_reverse_split(const RevMlpA& A, const RevAr
   static_for<2>([&]<int hf>() {
     f32x4 dp1 = zero4();
     const f32x4 ds1 = load_tile4(p1_src + (4 * hf + w) * 256);   // saved SiLU'(p1), this wave's block of this half (requested ahead of its chain)
-    M3G_F32_CHAIN_PRIO(1);
+    __builtin_amdgcn_s_setprio(1);
     static_for<4>([&]<int blk>() {   // (B operands block by block from LDS: all eight blocks at once are 32 live registers)
       const f32x4 d2b = *(const f32x4*)(hs1 + (4 * hf + blk) * 256 + lane * 4);
       static_for<4>([&]<int r>() { dp1 = mfma16(A.w2t[hf][blk * 4 + r], d2b[r], dp1); });
     });
-    M3G_F32_CHAIN_PRIO(0);
+    __builtin_amdgcn_s_setprio(0);
     dp1 *= ds1;
     if (NEED_DP1 && edge < a.E) *(f32x4*)(a.dp1 + drow * (4 * kDP) + MLP * (2 * kDP) + hf * kDP + 4 * qd + w * 16) = dp1;
     dp1h[hf] = dp1;
@@ -114,12 +114,12 @@ __device__ __forceinline__ f32x4 mlp_reverse_split(const RevMlpA& A, const RevAr
   *(f32x4*)(hs2 + (4 + w) * 256 + lane * 4) = dp1h[1];
   __syncthreads();
   f32x4 contrib = zero4();
-  M3G_F32_CHAIN_PRIO(1);
+  __builtin_amdgcn_s_setprio(1);
   static_for<8>([&]<int blk>() {
     const f32x4 db = *(const f32x4*)(hs2 + blk * 256 + lane * 4);
     static_for<4>([&]<int r>() { contrib = mfma16(A.w1ct[blk * 4 + r], db[r], contrib); });
   });
-  M3G_F32_CHAIN_PRIO(0);
+  __builtin_amdgcn_s_setprio(0);
   return contrib;
 }
 

@@ -235,14 +235,8 @@ namespace m3g {
 #define M3G_DISPATCH_LR3(L_, R_, BODY) \
   switch ((L_) * 8 + (R_)) { M3G_LR_ROW(1, BODY) M3G_LR_ROW(2, BODY) M3G_LR_ROW(3, BODY) default: break; }
 
-#ifndef M3G_TB_ROWS
-#define M3G_TB_ROWS 128
-#endif
-constexpr int kTbRows = M3G_TB_ROWS;
-#ifndef M3G_TB_CAP
-#define M3G_TB_CAP 255
-#endif
-constexpr int kTbCap = M3G_TB_CAP;   // staged three-body window: the rows of the workgroup + the other rows of the centres they belong to;
+constexpr int kTbRows = 128;
+constexpr int kTbCap = 255;   // staged three-body window: the rows of the workgroup + the other rows of the centres they belong to;
                                      // < 256 so a window-relative partner id fits a byte (rows beyond it are read from global memory)
 // staged partner ids per row and list (one byte each; longer lists continue from global memory).  Two instantiations of the
 // three-body kernels: the short lists of the usual 3-body cutoff (r_3 = 4 A: ~17 partners per active edge) and the long ones of

@@ -20,21 +20,15 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+// the machine scheduler moves no instruction across this point
+__device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 
-#ifdef M3G_DIAG_CHEAP_ACT   // timing diagnostic only (wrong results): activations without transcendentals
-__device__ __forceinline__ float fsigmoid(float p) { return p * 0.25f + 0.5f; }
-#else
 __device__ __forceinline__ float fsigmoid(float p) { return __builtin_amdgcn_rcpf(1.f + __expf(-p)); }
-#endif
 __device__ __forceinline__ float fsilu(float p) { return p * fsigmoid(p); }
 // SiLU(p) * sigmoid(g) = p / ((1 + e^-p)(1 + e^-g)): one reciprocal for the gated product instead of two sigmoids
 // (each factor is >= 1, an overflowing exponential gives inf -> rcp 0, the correct limit)
 __device__ __forceinline__ float fgated(float p, float g) {
-#ifdef M3G_DIAG_CHEAP_ACT
-  return p * (g * 0.25f + 0.5f);
-#else
   return p * __builtin_amdgcn_rcpf((1.f + __expf(-p)) * (1.f + __expf(-g)));
-#endif
 }
 __device__ __forceinline__ float fdsilu(float p) {
   float s = fsigmoid(p);
@@ -46,46 +40,24 @@ __device__ __forceinline__ float fdsilu(float p) {
 // four transcendentals per pair instead of nine and four.  1 - sg is formed as 1 + (-sg), not as e^-p sg: the latter is inf * 0
 // for p < -88.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void silu_pair(f32x2 p, f32x2& act, f32x2& der) {
-#ifdef M3G_DIAG_CHEAP_ACT
-  const f32x2 sg = p * 0.25f + 0.5f;
-#else
-  const f32x2 t = p * -1.4426950408889634f;
-  const f32x2 d = f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + 1.f;
-  const f32x2 sg = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-#endif
-  act = p * sg;
-  der = act * (1.f - sg) + sg;
-}
-
-__device__ __forceinline__ f32x2 sigmoid_pair(f32x2 g) {
-#ifdef M3G_DIAG_CHEAP_ACT
-  return g * 0.25f + 0.5f;
-#else
+__device__ __forceinline__ f32x2 sigmoid_pair(f32x2 g) {   // 1 / (1 + 2^(-g log2 e))
   const f32x2 t = g * -1.4426950408889634f;
   const f32x2 d = f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + 1.f;
   return f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-#endif
 }
-// SiLU of a value pair / SiLU(p) * sigmoid(g) of two value pairs, the same way (fsilu, fgated)
-__device__ __forceinline__ f32x2 silu_pair(f32x2 p) {
-#ifdef M3G_DIAG_CHEAP_ACT
-  return p * (p * 0.25f + 0.5f);
-#else
-  const f32x2 t = p * -1.4426950408889634f;
-  const f32x2 d = f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + 1.f;
-  return p * f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-#endif
+__device__ __forceinline__ void silu_pair(f32x2 p, f32x2& act, f32x2& der) {
+  const f32x2 sg = sigmoid_pair(p);
+  act = p * sg;
+  der = act * (1.f - sg) + sg;
 }
+// SiLU of a value pair / SiLU(p) * sigmoid(g) of two value pairs, the same way (fsilu, fgated); the gated product takes ONE
+// reciprocal of the product of both denominators, so it is not built on sigmoid_pair
+__device__ __forceinline__ f32x2 silu_pair(f32x2 p) { return p * sigmoid_pair(p); }
 __device__ __forceinline__ f32x2 gated_pair(f32x2 p, f32x2 g) {
-#ifdef M3G_DIAG_CHEAP_ACT
-  return p * (g * 0.25f + 0.5f);
-#else
   const f32x2 tp = p * -1.4426950408889634f, tg = g * -1.4426950408889634f;
   const f32x2 d = (f32x2{__builtin_amdgcn_exp2f(tp[0]), __builtin_amdgcn_exp2f(tp[1])} + 1.f) *
                   (f32x2{__builtin_amdgcn_exp2f(tg[0]), __builtin_amdgcn_exp2f(tg[1])} + 1.f);
   return p * f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-#endif
 }
 
 // ---- the dense chains run on v_mfma_f32_16x16x32_bf16 with split operands ("bf16x3") ----------------------------
@@ -137,10 +109,9 @@ __device__ __forceinline__ f32x4 mfma_f16(f16x8 a, f16x8 b, f32x4 c) { return __
 // Hazards inside the block (the recogniser does not look into inline assembly): a half-register write (v_fma_mixlo/hi) needs one
 // wait state before a vector instruction reads that register (dst_sel / op_sel forwarding, gfx940+): the reader of the low half
 // comes two instructions after its writer, the reader of the high half two after its.
-#if !defined(M3G_SPLIT_H_MIX) && !defined(M3G_SPLIT_H_PLAIN)
-// default form: the scaling as one packed multiply, the high parts by v_cvt_pk_f16_f32 -- no half-register writers at all, five
+// This form: the scaling as one packed multiply, the high parts by v_cvt_pk_f16_f32 -- no half-register writers at all, five
 // plain-rate instructions per pair, bit-identical parts (the power-of-two product is exact); same-box A/B against the mix form
-// below: forward 0.452 -> 0.447, fused reverse 0.955 -> 0.943 ms per step
+// (v_fma_mixlo/hi_f16 for the high parts): forward 0.452 -> 0.447, fused reverse 0.955 -> 0.943 ms per step
 typedef float f32x2_split __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split_pair_h(float a, float b, float s, f16x2& hi, f16x2& lo) {
   const f32x2_split t = f32x2_split{a, b} * s;
@@ -159,27 +130,6 @@ __device__ __forceinline__ void split_pair_h(float a, float b, float s, f16x2& h
   hi = __builtin_bit_cast(f16x2, h);
   lo = __builtin_bit_cast(f16x2, l);
 }
-#elif defined(M3G_SPLIT_H_MIX)
-__device__ __forceinline__ void split_pair_h(float a, float b, float s, f16x2& hi, f16x2& lo) {
-  unsigned h;
-  float ra, rb;
-  asm("v_fma_mixlo_f16 %0, %3, %4, 0\n\t"
-      "v_fma_mixhi_f16 %0, %3, %5, 0\n\t"
-      "v_fma_mix_f32 %1, %3, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-      "v_fma_mix_f32 %2, %3, %5, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-      : "=&v"(h), "=&v"(ra), "=v"(rb)
-      : "v"(s), "v"(a), "v"(b));
-  hi = __builtin_bit_cast(f16x2, h);
-  lo = f16x2{(_Float16)ra, (_Float16)rb};   // v_cvt_pk_f16_f32: round to nearest, like the high part
-}
-#else
-__device__ __forceinline__ void split_pair_h(float a, float b, float s, f16x2& hi, f16x2& lo) {
-  const float as = a * s, bs = b * s;
-  hi = f16x2{(_Float16)as, (_Float16)bs};
-  const float ra = __builtin_fmaf((float)hi[0], -1.0f, as), rb = __builtin_fmaf((float)hi[1], -1.0f, bs);
-  lo = f16x2{(_Float16)ra, (_Float16)rb};
-}
-#endif
 // B operand of one k-step (accumulator blocks a, b scaled by s): element j < 4 from a, j >= 4 from b (as split8)
 __device__ __forceinline__ void split8h(const f32x4& a, const f32x4& b, float s, f16x8& hi, f16x8& lo) {
   f16x2 h[4], l[4];
@@ -207,9 +157,6 @@ struct EdgeScale { float s, inv; };
 template <int NB, int XOFF = 0, int NX>
 __device__ __forceinline__ EdgeScale edge_scale(const f32x4 (&x)[NX]) {
   static_assert(XOFF + NB <= NX, "edge_scale operand out of range");
-#ifdef M3G_DIAG_NO_SCALE   // timing diagnostic only (wrong results): what finding the per-edge scales costs
-  return EdgeScale{1024.f, 1.f / 1024.f};
-#endif
   float m = 0.f;
   static_for<NB>([&]<int b>() { static_for<4>([&]<int r>() { m = fmaxf(m, fabsf(x[XOFF + b][r])); }); });
   unsigned u = max_lane_quarters_bits(__builtin_bit_cast(unsigned, m));

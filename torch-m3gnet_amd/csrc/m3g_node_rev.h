@@ -11,18 +11,11 @@ namespace m3g {
 // kNodesRev atoms per workgroup: phase 1 streams the dp1 rows (HBM-bound gather: a wave reads a whole 1-KB row per
 // instruction, 16 B per lane), phase 2 applies the transposed first-layer weights once for all atoms of the group
 // (the 128 KB of W1a/W1b would otherwise be re-read from L2 for every atom).
-#ifndef M3G_NODES_REV
-#define M3G_NODES_REV 4   // measured: 4 -> 0.259, 8 -> 0.288, 16 -> 0.293 ms per step (one atom per wave keeps more independent gathers in flight)
-#endif
-constexpr int kNodesRev = M3G_NODES_REV;
-#ifndef M3G_NR_BATCH
-#define M3G_NR_BATCH 8   // 768-byte nontemporal rows, index pairs handed out by v_readlane: 4 -> 0.172, 8 -> 0.166, 12 -> 0.171 ms per step
-#endif
-constexpr int kNrBatch = M3G_NR_BATCH;   // rows in flight per wave in the dp1 gather (multiple of 4)
-#ifndef M3G_NR_BATCH_SMALL
-#define M3G_NR_BATCH_SMALL 16   // ... of the small-system instantiation (PRELOAD): the launch is a chain of round trips there, not bandwidth
-#endif
-constexpr int kNrBatchSmall = M3G_NR_BATCH_SMALL;
+constexpr int kNodesRev = 4;   // measured: 4 -> 0.259, 8 -> 0.288, 16 -> 0.293 ms per step (one atom per wave keeps more independent gathers in flight)
+// rows in flight per wave in the dp1 gather (multiple of 4); 768-byte nontemporal rows, index pairs handed out by v_readlane:
+// 4 -> 0.172, 8 -> 0.166, 12 -> 0.171 ms per step
+constexpr int kNrBatch = 8;
+constexpr int kNrBatchSmall = 16;   // ... of the small-system instantiation (PRELOAD): the launch is a chain of round trips there, not bandwidth
 struct NodeRevArgs {
   int C;
   int64_t N;
@@ -134,93 +127,79 @@ __device__ __forceinline__ void node_reverse_body(const NodeRevArgs& args, int64
       const int cq = ln & 15;
       // NB whole 1-KB rows in flight per wave, the remainder in one guarded batch as well (a row-at-a-time tail
       // is a dependent round trip per row)
-#ifndef M3G_NR_NO_CHUNK
       // the (edge, three-body row) pairs of up to 64 in-edges arrive in ONE coalesced load, a lane each, and are handed
       // out by v_readlane: a pair load per batch would put a dependent round trip in front of every batch of row loads
       const int ks = __builtin_amdgcn_readfirstlane(k), k1s = __builtin_amdgcn_readfirstlane(k1);
       for (int kc = ks; kc < k1s; kc += 64) {
         const int cnt = k1s - kc < 64 ? k1s - kc : 64;
         const int2 mine = (PRELOAD && kc == ks) ? mine_first : (ln < cnt ? in_pair[kc + ln] : make_int2(-1, -1));
-      for (int b = 0; b < cnt; b += NB) {
-        int2 f[NB];   // (edge id, compact three-body row or -1)
-        float4 u[NB];
-        float g[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          const int src = b + j < 64 ? b + j : 63;   // lanes >= cnt hold (-1, -1)
-          f[j].x = b + j < 64 ? __builtin_amdgcn_readlane(mine.x, src) : -1;
-          f[j].y = b + j < 64 ? __builtin_amdgcn_readlane(mine.y, src) : -1;
-          if (args.dp1_by_dst && f[j].x >= 0) f[j].x = kc + b + j;   // rows stored in list order: a stream, not a gather
-        }
-#else
-      for (; k < k1; k += NB) {
-        int2 f[NB];   // (edge id, compact three-body row or -1)
-        float4 u[NB];
-        float g[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) f[j] = k + j < k1 ? in_pair[k + j] : make_int2(-1, -1);
-#endif
-#ifndef M3G_DP1_F32
-        if (dp1_packed == kDp1Fixed) {   // rows of the fused f16x3 reverse kernel: 24-bit fixed point + a scale per 64 columns (pack24_fixed)
-          u32x3 pk[NB];
-          float sc[NB];
+        for (int b = 0; b < cnt; b += NB) {
+          int2 f[NB];   // (edge id, compact three-body row or -1)
+          float4 u[NB];
+          float g[NB];
 #pragma unroll
           for (int j = 0; j < NB; ++j) {
-            pk[j] = f[j].x >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4*>(reinterpret_cast<const unsigned*>(dp1) +
-                                                                   (int64_t)f[j].x * kDp1PackedDwords + 3 * ln))
-                                : u32x3{0u, 0u, 0u};   // (any bytes decode to finite numbers; the zero scale makes them 0)
-            sc[j] = f[j].x >= 0 ? dp1_scale[(int64_t)f[j].x * 4 + (ln >> 4)] : 0.f;
+            const int src = b + j < 64 ? b + j : 63;   // lanes >= cnt hold (-1, -1)
+            f[j].x = b + j < 64 ? __builtin_amdgcn_readlane(mine.x, src) : -1;
+            f[j].y = b + j < 64 ? __builtin_amdgcn_readlane(mine.y, src) : -1;
+            if (args.dp1_by_dst && f[j].x >= 0) f[j].x = kc + b + j;   // rows stored in list order: a stream, not a gather
           }
+          if (dp1_packed == kDp1Fixed) {   // rows of the fused f16x3 reverse kernel: 24-bit fixed point + a scale per 64 columns (pack24_fixed)
+            u32x3 pk[NB];
+            float sc[NB];
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+              pk[j] = f[j].x >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4*>(reinterpret_cast<const unsigned*>(dp1) +
+                                                                     (int64_t)f[j].x * kDp1PackedDwords + 3 * ln))
+                                  : u32x3{0u, 0u, 0u};   // (any bytes decode to finite numbers; the zero scale makes them 0)
+              sc[j] = f[j].x >= 0 ? dp1_scale[(int64_t)f[j].x * 4 + (ln >> 4)] : 0.f;
+            }
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+              const f32x4 t = unpack24_fixed(pk[j], sc[j]);
+              u[j] = make_float4(t[0], t[1], t[2], t[3]);
+              g[j] = (with_v_term && f[j].y >= 0) ? dgq[(int64_t)f[j].y * kCP + cq] : 0.f;
+            }
+          } else if (dp1_packed) {   // rows written by the fused bf16x3 reverse kernel: 24-bit values, 12 B per lane (m3g_mfma_common.h: pack24)
+            u32x3 pk[NB];
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+              // nontemporal: every row is read exactly once, and keeping it out of L2 leaves the cache to the weights and
+              // partial rows (node reverse 0.218 -> 0.187 ms per step)
+              pk[j] = f[j].x >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4*>(reinterpret_cast<const unsigned*>(dp1) +
+                                                                     (int64_t)f[j].x * kDp1PackedDwords + 3 * ln))
+                                  : u32x3{0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+              const f32x4 t = unpack24(pk[j]);
+              u[j] = make_float4(t[0], t[1], t[2], t[3]);
+              g[j] = (with_v_term && f[j].y >= 0) ? dgq[(int64_t)f[j].y * kCP + cq] : 0.f;
+            }
+          } else
 #pragma unroll
           for (int j = 0; j < NB; ++j) {
-            const f32x4 t = unpack24_fixed(pk[j], sc[j]);
-            u[j] = make_float4(t[0], t[1], t[2], t[3]);
+            // fp32 rows (fp32 mode, split reverse kernels): read once -> nontemporal, like the packed rows
+            if (f[j].x >= 0) {
+              const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(dp1) + (int64_t)f[j].x * 64 + ln);
+              u[j] = make_float4(t[0], t[1], t[2], t[3]);
+            } else {
+              u[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            // dL/dg holds one row per ACTIVE edge; other edges contribute nothing
             g[j] = (with_v_term && f[j].y >= 0) ? dgq[(int64_t)f[j].y * kCP + cq] : 0.f;
           }
-        } else if (dp1_packed) {   // rows written by the fused bf16x3 reverse kernel: 24-bit values, 12 B per lane (m3g_mfma_common.h: pack24)
-          u32x3 pk[NB];
 #pragma unroll
-          for (int j = 0; j < NB; ++j)
-            // nontemporal: every row is read exactly once, and keeping it out of L2 leaves the cache to the weights and
-            // partial rows (node reverse 0.218 -> 0.187 ms per step)
-            pk[j] = f[j].x >= 0 ? __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4*>(reinterpret_cast<const unsigned*>(dp1) +
-                                                                   (int64_t)f[j].x * kDp1PackedDwords + 3 * ln))
-                                : u32x3{0u, 0u, 0u};
-#pragma unroll
-          for (int j = 0; j < NB; ++j) {
-            const f32x4 t = unpack24(pk[j]);
-            u[j] = make_float4(t[0], t[1], t[2], t[3]);
-            g[j] = (with_v_term && f[j].y >= 0) ? dgq[(int64_t)f[j].y * kCP + cq] : 0.f;
+          for (int j = 0; j < NB; j += 4) {
+            b0.x += u[j].x; b0.y += u[j].y; b0.z += u[j].z; b0.w += u[j].w;
+            b1.x += u[j + 1].x; b1.y += u[j + 1].y; b1.z += u[j + 1].z; b1.w += u[j + 1].w;
+            b2.x += u[j + 2].x; b2.y += u[j + 2].y; b2.z += u[j + 2].z; b2.w += u[j + 2].w;
+            b3.x += u[j + 3].x; b3.y += u[j + 3].y; b3.z += u[j + 3].z; b3.w += u[j + 3].w;
+            dv += (g[j] + g[j + 1]) + (g[j + 2] + g[j + 3]);
           }
-        } else
-#endif
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          // fp32 rows (fp32 mode, split reverse kernels): read once -> nontemporal, like the packed rows
-          if (f[j].x >= 0) {
-            const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(dp1) + (int64_t)f[j].x * 64 + ln);
-            u[j] = make_float4(t[0], t[1], t[2], t[3]);
-          } else {
-            u[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-          }
-          // dL/dg holds one row per ACTIVE edge; other edges contribute nothing
-          g[j] = (with_v_term && f[j].y >= 0) ? dgq[(int64_t)f[j].y * kCP + cq] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < NB; j += 4) {
-          b0.x += u[j].x; b0.y += u[j].y; b0.z += u[j].z; b0.w += u[j].w;
-          b1.x += u[j + 1].x; b1.y += u[j + 1].y; b1.z += u[j + 1].z; b1.w += u[j + 1].w;
-          b2.x += u[j + 2].x; b2.y += u[j + 2].y; b2.z += u[j + 2].z; b2.w += u[j + 2].w;
-          b3.x += u[j + 3].x; b3.y += u[j + 3].y; b3.z += u[j + 3].z; b3.w += u[j + 3].w;
-          dv += (g[j] + g[j + 1]) + (g[j + 2] + g[j + 3]);
         }
       }
-#ifndef M3G_NR_NO_CHUNK
-      }
-#endif
       b0.x += b2.x; b0.y += b2.y; b0.z += b2.z; b0.w += b2.w;
       b1.x += b3.x; b1.y += b3.y; b1.z += b3.z; b1.w += b3.w;
-#ifndef M3G_NR_NO_CHUNK
       if constexpr (DEFER_V) {
         if (args.with_v_term) {
           const bool never_came = wait_for_dgq();   // (bounded wait ran out: the rows below are stale -- NaN instead, M3G_TOPO_ERR_SYNC)
@@ -243,7 +222,6 @@ __device__ __forceinline__ void node_reverse_body(const NodeRevArgs& args, int64
           if (never_came) dv = __builtin_nanf("");
         }
       }
-#endif
       if (ln < kCP) {
         const float vv = v[i * kCP + ln];
         dvv = ln < C ? dv * vv * (1.f - vv) : 0.f;
@@ -277,11 +255,7 @@ __device__ __forceinline__ void node_reverse_body(const NodeRevArgs& args, int64
         }
       }
     } else
-#ifdef M3G_DIAG_NR_NO_PHASE2   // timing diagnostic only (wrong results): what re-reading W1a^T / W1b^T per 4-atom group costs
-    for (int o = 0; o < 4; o += 4) {
-#else
     for (int o = 0; o < kDP; o += 4) {
-#endif
       // four weight rows per trip: the row sums come from LDS as 16-byte broadcasts (a b32 read per term made this phase
       // LDS-issue-bound: 512 reads per thread), the eight weight loads of a trip are independent
       float a[4], b[4];

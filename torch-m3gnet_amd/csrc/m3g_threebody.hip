@@ -602,10 +602,9 @@ __device__ __forceinline__ void tb_moments_body(const Consts& c, const TbMomArgs
     }
   }
 }
-#ifndef M3G_TB_MOM_THREADS
-#define M3G_TB_MOM_THREADS 128   // (256 measured: forward -3.6 us, reverse +2 us per step on the 10k-atom cell -- no gain) threads per workgroup of the stand-alone moment kernels (kTbRows of them own a row; all stage and sum)
-#endif
-constexpr int kTbMomThreads = M3G_TB_MOM_THREADS;
+// threads per workgroup of the stand-alone moment kernels (kTbRows of them own a row; all stage and sum); 256 measured: forward
+// -3.6 us, reverse +2 us per step on the 10k-atom cell -- no gain
+constexpr int kTbMomThreads = 128;
 template <int L, int R, bool REV>
 __global__ void __launch_bounds__(kTbMomThreads) k_threebody_moments(Consts c, TbMomArgs a, int cap_rows, int cap_atoms) {
   extern __shared__ __attribute__((aligned(16))) float lds_mom[];
@@ -665,12 +664,10 @@ __global__ void __launch_bounds__(256) k_node_tb_reverse(Consts c, TbMomArgs ta,
 }
 
 // at most kTbGridCap workgroups (what 256 CUs hold at once at this LDS footprint and then some): they walk the row blocks
-#ifndef M3G_TB_GRID_CAP
-#define M3G_TB_GRID_CAP 2048
-#endif
+constexpr int kTbGridCap = 2048;
 static inline dim3 grid_rows(int64_t n) {
   const int64_t blocks = (n + kTbRows - 1) / kTbRows;
-  return dim3((unsigned)(blocks < M3G_TB_GRID_CAP ? blocks : M3G_TB_GRID_CAP));
+  return dim3((unsigned)(blocks < kTbGridCap ? blocks : kTbGridCap));
 }
 // (StepPath::moments: L, R outside M3G_DISPATCH_LR3's cases take the list kernels)
 // arguments of the moment kernels: forward (m = the aggregate to form) or reverse (m = nullptr: the gradient arrays of the workspace)
