@@ -344,3 +344,29 @@ def test_split_tail_of_the_persistent_reverse_kernel(cells, mode):
     if os.path.isdir("gpurun_out"):
         with open("gpurun_out/small_vs_large_margins.txt", "a") as fh:
             fh.write(f"split tail, {4 * cells[0] ** 3} atoms: forward bit-identical; F {f_err:.2e} of max|F|, stress {s_err:.2e}\n")
+
+
+@pytest.mark.parametrize("forces", [True, False])
+def test_split_node_and_readout_kernels_are_bit_identical(forces):
+    """Option split_node_tiles alone: 128 (default: split node tables, k_geometry_node_pre, split readout) against 0
+    (k_node_pre_mfma<fp32>, k_readout_mfma<fp32>), every other option at its default -- the split forms run the same k-ordered
+    chains, so energies, per-atom energies, node features, forces and stresses are equal bit for bit.  One part-filled 16-atom
+    tile, 108 atoms (six full tiles and a part-filled seventh) and a batch of three structures (the launch's last workgroup walks
+    more than one); forces=False is the GRAD = false instantiation of the split readout."""
+    from helpers import fcc_cu_graph, random_cell_graph
+    from torch_m3gnet.data import MaterialGraphKey as K
+    from torch_m3gnet.data.material_graph import Batch
+
+    graphs = [Batch.from_data_list([random_cell_graph(12, 6.0, 0)]).to("cuda"), fcc_cu_graph(3, 3, 3).to("cuda"),
+              Batch.from_data_list([random_cell_graph(12, 6.0, s) for s in range(3)]).to("cuda")]
+    keys = [K.TOTAL_ENERGY, K.SCALED_ATOMIC_ENERGIES, K.NODE_FEATURES] + ([K.FORCES, K.STRESSES] if forces else [])
+    for i, g0 in enumerate(graphs):
+        outs = []
+        for tiles in (128, 0):
+            model, _ = build_engine_model("cu32", "doc")
+            model.engine.set_option("split_node_tiles", tiles)
+            g = model(g0.clone(), forces=forces)
+            torch.cuda.synchronize()
+            outs.append({k: g[k].clone() for k in keys})
+        for k in keys:
+            assert torch.equal(outs[0][k], outs[1][k]), (i, k)

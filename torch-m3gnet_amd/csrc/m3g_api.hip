@@ -20,8 +20,6 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
 // ---- weight layout ---------------------------------------------------------------------------------
 static void layout_mlp(MlpW& m, size_t& off) {
   auto take = [&](size_t n) { size_t r = off; off += (n + 63) / 64 * 64; return r; };

@@ -126,8 +126,6 @@ inline bool lattice_ok(const char* fn, const double* L, int64_t s) {
   return true;
 }
 
-inline dim3 blocks_for(int64_t n, int threads) { return dim3((unsigned)((n + threads - 1) / threads)); }
-
 // the tail of a call that launched (a macro, as M3G_HIP_CHECK: the error names the caller's file and line)
 #define M3G_RETURN_LAUNCH_STATUS() do { M3G_HIP_CHECK(hipGetLastError()); return M3G_OK; } while (0)
 

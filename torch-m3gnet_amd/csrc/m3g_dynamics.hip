@@ -305,7 +305,7 @@ extern "C" int m3g_dyn_init(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_
   M3G_HIP_CHECK(hipMemcpyAsync(b + L.t0, host_temperatures, 8 * S, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync(b + L.seed, host_seeds, 8 * S, hipMemcpyHostToDevice, s));
   const int64_t work = 3 * N > S ? 3 * N : S;
-  hipLaunchKernelGGL(k_dyn_init, blocks_for(work, kChunkRows), dim3(kChunkRows), 0, s, dyn_view(N, S, state), vel);
+  hipLaunchKernelGGL(k_dyn_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, dyn_view(N, S, state), vel);
   M3G_HIP_CHECK(hipGetLastError());
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;
@@ -323,7 +323,7 @@ extern "C" int m3g_dyn_step(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_
   const double c1 = langevin_c1(p);
   const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_dyn_partials, grid, dim3(kChunkRows), 0, s, st, 0.5 * p->dt, forces);
-  hipLaunchKernelGGL(k_dyn_finalize, blocks_for(S, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, *p,
+  hipLaunchKernelGGL(k_dyn_finalize, grid_for(S, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, *p,
                      finish_only, c1, stresses, lattice, lattice32, obs);
   hipLaunchKernelGGL(k_dyn_apply, grid, dim3(kChunkRows), 0, s, st, *p, c1, forces, pos);
   M3G_RETURN_LAUNCH_STATUS();

@@ -245,6 +245,7 @@ __device__ __forceinline__ void seg_scan(f32x4 (&v)[4], const SegMasks& k) {
   M3G_SCAN_STEP16(8, k.m8);
   static_for<16>([&]<int i>() { v[i >> 2][i & 3] = x[i]; });
 }
+// any other number of blocks (the split-tile kernels scan one): x += dpp(x) * m is the same fused multiply-add the assembly block issues
 template <int N>
 __device__ __forceinline__ void seg_scan(f32x4 (&v)[N], const SegMasks& k) {
   static_for<N>([&]<int b>() {
@@ -259,13 +260,13 @@ __device__ __forceinline__ void seg_scan(f32x4 (&v)[N], const SegMasks& k) {
   });
 }
 // run-end lanes store their run's sum: the tile's first run into seg_head[tile], a run starting mid-tile into
-// seg_first[centre]; row = 4*kDP floats, this call covers blocks [B0, B0+N) of it
-template <int B0, int N>
+// seg_first[centre]; row = 4*kDP floats, this call covers blocks [b0, b0+N) of it
+template <int N>
 __device__ __forceinline__ void seg_store(const f32x4 (&v)[N], const SegMasks& k, float* seg_head, float* seg_first, int64_t tile,
-                                          int64_t ci, int qd) {
+                                          int64_t ci, int qd, int b0) {
   if (k.run_end) {
     float* row = (k.first_run ? seg_head + tile * (4 * kDP) : seg_first + ci * (4 * kDP)) + 4 * qd;
-    static_for<N>([&]<int b>() { *(f32x4*)(row + (B0 + b) * 16) = v[b]; });
+    static_for<N>([&]<int b>() { *(f32x4*)(row + (b0 + b) * 16) = v[b]; });
   }
 }
 
@@ -278,7 +279,7 @@ __device__ __forceinline__ void load_image(float* lds, const float* __restrict__
     f32x4 t[kBatch];
     static_for<kBatch>([&]<int j>() {
       const int i = base + j * nt + (int)threadIdx.x;
-      t[j] = i < n_vec ? *(const f32x4*)(src + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+      t[j] = i < n_vec ? *(const f32x4*)(src + 4 * i) : zero4();
     });
     static_for<kBatch>([&]<int j>() {
       const int i = base + j * nt + (int)threadIdx.x;
@@ -348,7 +349,7 @@ template <int PREC, int TBS>
 __device__ __forceinline__ TbIn<PREC, TBS> tb_load(const float* __restrict__ m, int arow, int q, float w_inv) {
   TbIn<PREC, TBS> r;
   if constexpr (PREC == kPrecF16x3) {
-    f32x4 v[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    f32x4 v[2] = {zero4(), zero4()};
     if (arow >= 0 && q < 2) {   // (< 0: the edge takes part in no triplet, its aggregate is zero)
       const float* row = m + (int64_t)arow * kCP + 8 * q;
       v[0] = *(const f32x4*)row;
@@ -377,7 +378,7 @@ __device__ __forceinline__ void tb_preact_p(const float* tbimg, const TbIn<PREC,
       f16x8 nh = ah, nl = al;
       if constexpr (ob + 1 < 8) { nh = hi[(ob + 1) * 32]; nl = lo[(ob + 1) * 32]; }
       sched_fence();
-      f32x4 t = {0.f, 0.f, 0.f, 0.f};
+      f32x4 t = zero4();
       t = mfma_f16(ah, in.hi, t);
       t = mfma_f16(ah, in.lo, t);
       t = mfma_f16(al, in.hi, t);

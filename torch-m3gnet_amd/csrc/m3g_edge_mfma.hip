@@ -99,7 +99,7 @@ __device__ __forceinline__ void mlp_forward_mfma(const float* lds, const MfmaMlp
   mlp_preacts<false, PREC, SAVE>(lds, L.w1c, L.w2d, L.w2g, L.b2, x, p1, p2, lane, p1_out, p2_out, a.w_inv);
   st.template mark<S0 + 1>();  // both layers
   static_for<4>([&]<int ob>() {
-    out[ob] = mfma16(lds[L.wl + ob * 64 + lane], hb, f32x4{0.f, 0.f, 0.f, 0.f});
+    out[ob] = mfma16(lds[L.wl + ob * 64 + lane], hb, zero4());
     // the f16x3 and fp32 kernels evaluate the gate on value PAIRS (packed fp32 instructions; fp32 forward, round 4: 1,218 -> 1,038
     // vector instructions per tile, no spills at its 128-register budget any more, -2 % same-box)
     if constexpr (PREC == kPrecF16x3 || PREC == kPrecF32) {
@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(64 * fwd_waves<PREC>()) k_edge_block_mfma(FwdA
     const float hb = a.h[ec * kRP + qv];
     if (FIRST) {
       static_for<4>([&]<int blk>() {
-        x[blk] = mfma16(lds[L.adj + blk * 64 + lv], hb, f32x4{0.f, 0.f, 0.f, 0.f});
+        x[blk] = mfma16(lds[L.adj + blk * 64 + lv], hb, zero4());
         static_for<4>([&]<int r>() { x[blk][r] = fsilu(x[blk][r]); });
       });
     }
@@ -196,10 +196,10 @@ __global__ void __launch_bounds__(64 * fwd_waves<PREC>()) k_edge_block_mfma(FwdA
     mlp_forward_mfma<ST, 7, PREC, SAVE>(lds, L.mlp[1], 1, a, ci, cj, hb, x, out, lv, st, SAVE >= 1 ? p1_tile + kP1TileFloats : nullptr,
                                         SAVE >= 2 ? p2_tile + kP1TileFloats : nullptr);  // node message (nn/conv.py:77-89)
     {  // sum of the messages per centre instead of a [E,64] message array + a node-side pass over it (nn/conv.py:82-88)
-      if (edge >= a.E) static_for<4>([&]<int blk>() { out[blk] = f32x4{0.f, 0.f, 0.f, 0.f}; });   // padding lanes of the last tile
+      if (edge >= a.E) static_for<4>([&]<int blk>() { out[blk] = zero4(); });   // padding lanes of the last tile
       const SegMasks sk = seg_masks((int)ci, lane);
       seg_scan(out, sk);
-      seg_store<0>(out, sk, a.seg_head, a.seg_first, tile, ci, qd);
+      seg_store(out, sk, a.seg_head, a.seg_first, tile, ci, qd, 0);
     }
     st.template mark<11>();  // message sums
     if (!has_next) break;
@@ -308,7 +308,7 @@ __global__ void __launch_bounds__(64 * kWavesRev) k_edge_rev_node_mlp(RevArgs a,
     float* dcn_tile = a.dcn + tile * kTileFloats + lane * 4;
     const float* e_tile = a.e_tile + tile * kTileFloats + lane * 4;
     const f32x4 hv = *(const f32x4*)(a.h + ec * kRP);
-    f32x4 dhv = {0.f, 0.f, 0.f, 0.f};
+    f32x4 dhv = zero4();
     f32x4 contrib[4];
     {
       f32x4 dmsg[4], x[4];
@@ -356,7 +356,7 @@ __global__ void __launch_bounds__(64 * kWavesRev) k_edge_rev_edge_mlp(RevArgs a,
     float* de_tile = a.de_soa + tile * kTileFloats + lane * 4;
     const float* e_tile = a.e_tile + tile * kTileFloats + lane * 4;
     const f32x4 hv = *(const f32x4*)(a.h + ec * kRP);
-    f32x4 dhv = {0.f, 0.f, 0.f, 0.f};
+    f32x4 dhv = zero4();
     float mb[TBS];
     const int arow = a.act_id[ec];   // < 0: the edge takes part in no triplet, its aggregate is zero
     static_for<TBS>([&]<int s>() { mb[s] = arow >= 0 ? a.m[(int64_t)arow * kCP + 4 * s + qd] : 0.f; });
@@ -500,7 +500,7 @@ __device__ __forceinline__ void mlp_reverse_dual(const float* lds, const MfmaMlp
   // (64 VALU instructions per MLP; fused reverse 0.904 -> 0.889 ms per step)
   const float hb_sel = qd == 0 ? hv[0] : qd == 1 ? hv[1] : qd == 2 ? hv[2] : hv[3];
   static_for<4>([&]<int ob>() {
-    const f32x4 sl = mfma16(lds[L.wld + ob * 64 + lane], hb_sel, f32x4{0.f, 0.f, 0.f, 0.f});
+    const f32x4 sl = mfma16(lds[L.wld + ob * 64 + lane], hb_sel, zero4());
     // value pairs on packed fp32 instructions (silu_pair): out = SiLU(p2d) sg(p2g) s_lin
     static_for<2>([&]<int k>() {
       const f32x2 p2d = {d2[ob][2 * k], d2[ob][2 * k + 1]}, p2g = {d2[4 + ob][2 * k], d2[4 + ob][2 * k + 1]};
@@ -561,7 +561,7 @@ __device__ __forceinline__ void mlp_reverse_dual(const float* lds, const MfmaMlp
       // x_j half, which is a gather by neighbour.
       if (edge >= a.E) zero(dp1);   // padding lanes of the last tile
       seg_scan(dp1, sk);
-      seg_store<MLP * 8 + 4 * half>(dp1, sk, a.seg_head, a.seg_first, tile, ci, qd);
+      seg_store(dp1, sk, a.seg_head, a.seg_first, tile, ci, qd, MLP * 8 + 4 * half);
     }
     sched_fence();
     st.template mark<S0 + 3 + half>();   // transposed chains, dp1 stores, per-centre scan of one half
@@ -600,7 +600,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_fused(RevArgs a, MfmaRe
     float* de_tile = a.de_soa + tile * kTileFloats + lane * 4;
     const float* e_tile = a.e_tile + tile * kTileFloats + lane * 4;
     const f32x4 hv = *(const f32x4*)(a.h + ec * kRP);
-    f32x4 dhv = {0.f, 0.f, 0.f, 0.f}, dp1_inv = {0.f, 0.f, 0.f, 0.f};
+    f32x4 dhv = zero4(), dp1_inv = zero4();
     const int arow = arow_i;   // < 0: the edge takes part in no triplet, its aggregate is zero
     const TbIn<PREC, TBS> tbin = tb_load<PREC, TBS>(a.m, arow, qd, a.w_inv);
     f32x4 x[4], de[4], contrib[4];
@@ -630,7 +630,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_fused(RevArgs a, MfmaRe
     if (FIRST) {
       const float hb = a.h[ec * kRP + qd];
       static_for<4>([&]<int blk>() {
-        x[blk] = mfma16(lds[L.adj + blk * 64 + lv], hb, f32x4{0.f, 0.f, 0.f, 0.f});
+        x[blk] = mfma16(lds[L.adj + blk * 64 + lv], hb, zero4());
         static_for<4>([&]<int r>() { x[blk][r] = fsilu(x[blk][r]); });
       });
     } else {
@@ -658,7 +658,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_fused(RevArgs a, MfmaRe
       // edge embedding, reverse (nothing upstream of e0 but the radial basis): dL/dh += W_adj^T (dL/de0 * SiLU'(W_adj h))
       const float hb = a.h[ec * kRP + qd];
       static_for<4>([&]<int blk>() {
-        const f32x4 pe = mfma16(lds[L.adj + blk * 64 + lv], hb, f32x4{0.f, 0.f, 0.f, 0.f});
+        const f32x4 pe = mfma16(lds[L.adj + blk * 64 + lv], hb, zero4());
         static_for<4>([&]<int r>() {
           const f32x4 w = *(const f32x4*)(lds + L.adjp + (blk * 16 + 4 * qd + r) * 4);
           const float t = de[blk][r] * fdsilu(pe[r]);

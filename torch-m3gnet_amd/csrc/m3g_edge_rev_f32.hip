@@ -76,7 +76,7 @@ __device__ __forceinline__ void mlp_reverse_f32(const float* lds, const MfmaMlpR
   // gating derivatives; W_l h on the matrix pipe (4 small MFMAs), dL/dh on the vector ALU
   const float hb_sel = qd == 0 ? hv[0] : qd == 1 ? hv[1] : qd == 2 ? hv[2] : hv[3];
   static_for<4>([&]<int ob>() {
-    const f32x4 sl = mfma16(lds[L.wld + ob * 64 + lane], hb_sel, f32x4{0.f, 0.f, 0.f, 0.f});
+    const f32x4 sl = mfma16(lds[L.wld + ob * 64 + lane], hb_sel, zero4());
     // value pairs on packed fp32 instructions, as the f16x3 fused kernel evaluates them (round 4, against one value at a time:
     // 1,885 -> 1,457 vector instructions per tile, 211 -> 200 VGPRs, reverse -0.9 % same-box)
     static_for<2>([&]<int k>() {
@@ -121,7 +121,7 @@ __device__ __forceinline__ void mlp_reverse_f32(const float* lds, const MfmaMlpR
     if (NEED_DP1) {
       if (edge >= a.E) zero(dp1);   // padding lanes of the last tile
       seg_scan(dp1, sk);
-      seg_store<MLP * 8 + 4 * half>(dp1, sk, a.seg_head, a.seg_first, tile, ci, qd);
+      seg_store(dp1, sk, a.seg_head, a.seg_first, tile, ci, qd, MLP * 8 + 4 * half);
     }
     sched_fence();
   });
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_f32(RevArgs a, MfmaRevF
     const SegMasks sk = seg_masks((int)ci, lane);
     float* de_tile = a.de_soa + tile * kTileFloats + lane * 4;
     const f32x4 hv = *(const f32x4*)(a.h + ec * kRP);
-    f32x4 dhv = {0.f, 0.f, 0.f, 0.f};
+    f32x4 dhv = zero4();
     float mb[TBS];
     const int arow = a.act_id[ec];   // < 0: the edge takes part in no triplet, its aggregate is zero
     static_for<TBS>([&]<int s>() { mb[s] = arow >= 0 ? a.m[(int64_t)arow * kCP + 4 * s + qd] : 0.f; });
@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_f32(RevArgs a, MfmaRevF
       // edge embedding, reverse (nothing upstream of e0 but the radial basis): dL/dh += W_adj^T (dL/de0 * SiLU'(W_adj h))
       const float hb = qd == 0 ? hv[0] : qd == 1 ? hv[1] : qd == 2 ? hv[2] : hv[3];
       static_for<4>([&]<int blk>() {
-        const f32x4 pe = mfma16(lds[L.adj + blk * 64 + lv], hb, f32x4{0.f, 0.f, 0.f, 0.f});
+        const f32x4 pe = mfma16(lds[L.adj + blk * 64 + lv], hb, zero4());
         static_for<4>([&]<int r>() {
           const f32x4 w = *(const f32x4*)(lds + L.adjp + (blk * 16 + 4 * qd + r) * 4);
           const float t = de[blk][r] * fdsilu(pe[r]);

@@ -289,8 +289,6 @@ __global__ void __launch_bounds__(256) k_edge_block_reverse(Consts c, int64_t E,
   }
 }
 
-static inline dim3 grid_for(int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
-
 void launch_edge_block(const Consts& c, const float* W, const BlockW& bw, const Topo& t, const Work& w, int b,
                        float* x_new, hipStream_t s) {
   if (t.E == 0) return;

@@ -33,13 +33,6 @@ inline int grid_for_split(int64_t tiles) {
   return (int)(wgs < 1 ? 1 : wgs);
 }
 
-// acc += sum_{blk < 4, r < 4} A[blk*4 + r] * x[XOFF + blk][r]   (chain_f32 restricted to one 16-row output block: same k order)
-template <int XOFF, int NX>
-__device__ __forceinline__ void chain_reg16(const float (&A)[16], const f32x4 (&x)[NX], f32x4& acc) {
-  static_assert(XOFF + 4 <= NX, "chain_reg16 operand out of range");
-  static_for<4>([&]<int blk>() { static_for<4>([&]<int r>() { acc = mfma16(A[blk * 4 + r], x[XOFF + blk][r], acc); }); });
-}
-
 // ------------------------------------------------------------------------------------------------------------- forward
 // register-resident A operands of one conv GatedMLP, forward: this wave's layer-1 rows (dense block w, gate block 4 + w),
 // layer-2 rows (dense out block w from the dense hidden half, gate out block w from the gate half), its bias quads and W_l rows
@@ -93,11 +86,9 @@ __device__ __forceinline__ f32x4 mlp_forward_split(const FwdMlpA& A, const f32x4
     static_for<4>([&]<int r>() { p1d[r] = fsilu(p1d[r]); p1g[r] = fsilu(p1g[r]); });
   }
   // hidden activations of all waves -> every wave (the B operand of layer 2 is the whole hidden vector of its branch)
-  *(f32x4*)(hs + w * 256 + lane * 4) = p1d;
-  *(f32x4*)(hs + (4 + w) * 256 + lane * 4) = p1g;
-  __syncthreads();
+  split_publish(hs, w, lane, p1d, p1g);
   f32x4 hid[8];
-  static_for<8>([&]<int ob>() { hid[ob] = *(const f32x4*)(hs + ob * 256 + lane * 4); });
+  split_collect(hs, lane, hid);
   f32x4 p2d = A.b2[0], p2g = A.b2[1];
   __builtin_amdgcn_s_setprio(1);
   chain_reg16<0>(A.w2[0], hid, p2d);
@@ -180,10 +171,10 @@ __global__ void __launch_bounds__(64 * kSplitWaves) k_edge_fwd_split(FwdArgs a, 
     // node message (nn/conv.py:77-89) and its sum per centre (82-88)
     out = mlp_forward_split<SAVE>(A1, t1[1], x, hb, hs, w, lane, SAVE == 2 ? p1_tile + kP1TileFloats : nullptr,
                                   SAVE == 2 ? p2_tile + kP1TileFloats : nullptr);
-    if (edge >= a.E) out = zero4();   // padding lanes of the last tile
+    f32x4 msg[1] = {edge < a.E ? out : zero4()};   // (padding lanes of the last tile)
     const SegMasks sk = seg_masks((int)ci, lane);
-    seg_scan1(out, sk);
-    seg_store1(out, sk, a.seg_head, a.seg_first, tile, ci, qd, w);
+    seg_scan(msg, sk);
+    seg_store(msg, sk, a.seg_head, a.seg_first, tile, ci, qd, w);
     // (xs / hs of the next tile: its first write of xs follows this tile's last barrier, which every wave reaches only after
     //  its reads of xs; its first write of hs follows the next tile's first barrier, which follows every wave's reads of hs)
   }

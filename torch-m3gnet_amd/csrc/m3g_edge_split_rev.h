@@ -12,28 +12,26 @@ constexpr int kSplitWaves = 4;
 constexpr int kRevSplitGroupFloats = 3 * 8 * 256;
 constexpr int kRevSplitTabFloats = 3 * 256;   // plain W_l of both MLPs, plain W_adj (block 0): shared by all groups
 
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+// acc += sum_{blk < 4, r < 4} A[blk*4 + r] * x[XOFF + blk][r]   (chain_f32 restricted to one 16-row output block: same k order)
+template <int XOFF, int NX>
+__device__ __forceinline__ void chain_reg16(const float (&A)[16], const f32x4 (&x)[NX], f32x4& acc) {
+  static_assert(XOFF + 4 <= NX, "chain_reg16 operand out of range");
+  static_for<4>([&]<int blk>() { static_for<4>([&]<int r>() { acc = mfma16(A[blk * 4 + r], x[XOFF + blk][r], acc); }); });
+}
 
-// segmented inclusive scan of one accumulator block along the DPP row (seg_scan of m3g_edge_common.h for a single block:
-// x += dpp(x) * m is the same fused multiply-add the 16-value assembly block issues)
-__device__ __forceinline__ void seg_scan1(f32x4& v, const SegMasks& k) {
-  static_for<4>([&]<int r>() {
-    float x = v[r];
-    x = fmaf(row_shr_f<1>(x), k.m1, x);
-    x = fmaf(row_shr_f<2>(x), k.m2, x);
-    x = fmaf(row_shr_f<4>(x), k.m4, x);
-    x = fmaf(row_shr_f<8>(x), k.m8, x);
-    v[r] = x;
-  });
+// The split-tile exchange: what the next layer needs of the other waves' rows (its B operand is the whole activation vector) crosses
+// through LDS.  Every wave stores its dense block w and its gate block 4 + w to `hs` (8 blocks x 256 floats), then a workgroup barrier ...
+__device__ __forceinline__ void split_publish(float* hs, int w, int lane, const f32x4& dense, const f32x4& gate) {
+  *(f32x4*)(hs + w * 256 + lane * 4) = dense;
+  *(f32x4*)(hs + (4 + w) * 256 + lane * 4) = gate;
+  __syncthreads();
 }
-// run-end lanes store their run's sum for row block `blk` of the 4*kDP-float row (seg_store with a run-time block)
-__device__ __forceinline__ void seg_store1(const f32x4& v, const SegMasks& k, float* seg_head, float* seg_first, int64_t tile, int64_t ci,
-                                           int qd, int blk) {
-  if (k.run_end) {
-    float* row = (k.first_run ? seg_head + tile * (4 * kDP) : seg_first + ci * (4 * kDP)) + 4 * qd;
-    *(f32x4*)(row + blk * 16) = v;
-  }
+// ... and every wave reads all eight blocks (or, short of registers, block by block inside its chain)
+__device__ __forceinline__ void split_collect(const float* hs, int lane, f32x4 (&all)[8]) {
+  static_for<8>([&]<int ob>() { all[ob] = *(const f32x4*)(hs + ob * 256 + lane * 4); });
 }
+// (k_readout_split and node_pre_split_body, m3g_node_mfma.hip, spell both out: through these helpers their compiled code changes by
+//  more than register names -- profiles/device_idioms.txt)
 
 // ------------------------------------------------------------------------------------------------------------- reverse
 struct RevMlpA {
@@ -87,9 +85,7 @@ __device__ __forceinline__ f32x4 mlp_reverse_split(const RevMlpA& A, const RevAr
     d2g[2 * k] = dgt[0]; d2g[2 * k + 1] = dgt[1];
   });
   // dL/dp2 of all waves -> every wave (B operand of the W2^T products)
-  *(f32x4*)(hs1 + w * 256 + lane * 4) = d2d;
-  *(f32x4*)(hs1 + (4 + w) * 256 + lane * 4) = d2g;
-  __syncthreads();
+  split_publish(hs1, w, lane, d2d, d2g);
   f32x4 dp1h[2];
   static_for<2>([&]<int hf>() {
     f32x4 dp1 = zero4();
@@ -104,15 +100,13 @@ __device__ __forceinline__ f32x4 mlp_reverse_split(const RevMlpA& A, const RevAr
     if (NEED_DP1 && edge < a.E) *(f32x4*)(a.dp1 + drow * (4 * kDP) + MLP * (2 * kDP) + hf * kDP + 4 * qd + w * 16) = dp1;
     dp1h[hf] = dp1;
     if (NEED_DP1) {   // per-centre sums of the dp1 rows (x_i half of the node reverse)
-      f32x4 t = edge < a.E ? dp1 : zero4();
-      seg_scan1(t, sk);
-      seg_store1(t, sk, a.seg_head, a.seg_first, tile, ci, qd, MLP * 8 + 4 * hf + w);
+      f32x4 t[1] = {edge < a.E ? dp1 : zero4()};
+      seg_scan(t, sk);
+      seg_store(t, sk, a.seg_head, a.seg_first, tile, ci, qd, MLP * 8 + 4 * hf + w);
     }
   });
   // dL/dp1 of all waves -> every wave (B operand of the W1c^T product)
-  *(f32x4*)(hs2 + w * 256 + lane * 4) = dp1h[0];
-  *(f32x4*)(hs2 + (4 + w) * 256 + lane * 4) = dp1h[1];
-  __syncthreads();
+  split_publish(hs2, w, lane, dp1h[0], dp1h[1]);
   f32x4 contrib = zero4();
   __builtin_amdgcn_s_setprio(1);
   static_for<8>([&]<int blk>() {

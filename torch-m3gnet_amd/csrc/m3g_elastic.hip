@@ -420,7 +420,7 @@ extern "C" int m3g_el_deform(const m3g_el_sizes* sizes, const void* state, size_
   if (const int rc = el_call_ok("m3g_el_deform", sizes, state, state_bytes, pos && lattices, -1)) return rc;
   const ElView st = el_view(*sizes, state);
   const int64_t threads = st.rows > 3 * st.copies ? st.rows : 3 * st.copies;
-  hipLaunchKernelGGL(k_el_deform, blocks_for(threads, 256), dim3(256), 0, (hipStream_t)stream_, st, pos, lattices);
+  hipLaunchKernelGGL(k_el_deform, grid_for(threads, 256), dim3(256), 0, (hipStream_t)stream_, st, pos, lattices);
   M3G_RETURN_LAUNCH_STATUS();
 }
 
@@ -436,6 +436,6 @@ extern "C" int m3g_el_fit_eos(const m3g_el_sizes* sizes, const void* state, size
                               int32_t* error, void* stream_) {
   if (const int rc = el_call_ok("m3g_el_fit_eos", sizes, state, state_bytes, energies && rows && error, M3G_EL_MODE_EOS)) return rc;
   const ElView st = el_view(*sizes, state);
-  hipLaunchKernelGGL(k_el_fit_eos, blocks_for(st.S, kWave), dim3(kWave), 0, (hipStream_t)stream_, st, energies, rows, error);
+  hipLaunchKernelGGL(k_el_fit_eos, grid_for(st.S, kWave), dim3(kWave), 0, (hipStream_t)stream_, st, energies, rows, error);
   M3G_RETURN_LAUNCH_STATUS();
 }

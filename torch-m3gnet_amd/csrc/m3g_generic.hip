@@ -27,7 +27,6 @@ struct GenConsts {
   int ref_legendre;   // option "legendre_backward" (m3g_threebody.hip: legendre_ref_k)
 };
 
-inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 #define GEN_IDX(n_total)                                              \
   const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; \
   if (gid >= (n_total)) return;
@@ -136,7 +135,7 @@ __global__ void __launch_bounds__(256) g_map(int64_t n, int op, const float* __r
   else Y[gid] *= x * (1.f - x);
 }
 static void map(hipStream_t s, int64_t n, int op, const float* X, float* Y) {
-  if (n > 0) hipLaunchKernelGGL(g_map, grid1(n), dim3(256), 0, s, n, op, X, Y);
+  if (n > 0) hipLaunchKernelGGL(g_map, grid_for(n), dim3(256), 0, s, n, op, X, Y);
 }
 
 // ---- S0 geometry and bases (nn/scale.py:24-29, nn/invariant.py:20-59, nn/featurizer.py:81-100, nn/interaction.py:268-350,389-400)
@@ -564,7 +563,7 @@ static void linear_t(hipStream_t s, int64_t n, int out, int in, const float* DY,
   gemm(s, n, in, out, DY, ldd, W, in, 1, nullptr, DX, ldx, beta);
 }
 static void gated(hipStream_t s, int64_t n, const float* pd, const float* pg, const float* lin, const float* base, float* y) {
-  if (n > 0) hipLaunchKernelGGL(g_gated, grid1(n), dim3(256), 0, s, n, pd, pg, lin, base, y);
+  if (n > 0) hipLaunchKernelGGL(g_gated, grid_for(n), dim3(256), 0, s, n, pd, pg, lin, base, y);
 }
 
 // one conv GatedMLP forward on the concat rows (nn/conv.py:68-97, nn/core.py:61-62): saves p1d, p1g, p2d, p2g, lin = W_l h (all [E,D]);
@@ -586,7 +585,7 @@ static void gen_mlp_forward(hipStream_t s, int64_t E, int D, int R, const GenBlo
 static void gen_mlp_reverse(hipStream_t s, int64_t E, int D, int R, const GenBlockW::Mlp& q, const GenWork& w, const GenWork::Blk& k, int m,
                             const float* d_upd, float* de_out) {
   // gating: d_p2d, d_p2g into t0 / t1, d_lin into msg
-  hipLaunchKernelGGL(g_gated_rev, grid1(E * D), dim3(256), 0, s, E * D, k.p2d[m], k.p2g[m], k.lin[m], d_upd, w.t0, w.t1, w.msg);
+  hipLaunchKernelGGL(g_gated_rev, grid_for(E * D), dim3(256), 0, s, E * D, k.p2d[m], k.p2g[m], k.lin[m], d_upd, w.t0, w.t1, w.msg);
   linear_t(s, E, D, R, w.msg, D, q.wl, w.dh, R, /*beta=*/true);            // dL/dh += d_lin W_l          (W_l [D,R])
   linear_t(s, E, D, D, w.t0, D, q.w2d, w.dp1d[m], D);                       // d hidden dense = d_p2d W2d
   linear_t(s, E, D, D, w.t1, D, q.w2g, w.dp1g[m], D);
@@ -614,9 +613,9 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
 
   // ---------------- forward ----------------
   if (E > 0)
-    hipLaunchKernelGGL(g_geometry, grid1(E), dim3(256), 0, s, c, E, t.src, t.dst, t.batch, io->pos, io->lattice, io->edge_cell_shift, w.u, w.d, w.h,
+    hipLaunchKernelGGL(g_geometry, grid_for(E), dim3(256), 0, s, c, E, t.src, t.dst, t.batch, io->pos, io->lattice, io->edge_cell_shift, w.u, w.d, w.h,
                        w.hp, w.fc3, w.fc3p, w.q, w.qp);
-  if (N > 0) hipLaunchKernelGGL(g_embed_x, grid1(N * D), dim3(256), 0, s, N, D, c.num_types, io->atom_types, W.emb, w.x[0]);
+  if (N > 0) hipLaunchKernelGGL(g_embed_x, grid_for(N * D), dim3(256), 0, s, N, D, c.num_types, io->atom_types, W.emb, w.x[0]);
   linear(s, E, D, R, w.h, R, W.adj, nullptr, w.pe0, D);                     // e0 = SiLU(W_adj h), nn/featurizer.py:128-132
   map(s, E * D, OP_SILU, w.pe0, w.e[0]);
   for (int b = 0; b < B; ++b) {
@@ -625,19 +624,19 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
     linear(s, N, C, D, w.x[b], D, kw.w1s, kw.b1s, k.v, C);                  // v = sigmoid(W1 x + b1), nn/interaction.py:204-205
     map(s, N * C, OP_SIGMOID, k.v, k.v);
     if (E > 0) {
-      hipLaunchKernelGGL(g_threebody_fwd, grid1(E * c.L), dim3(256), 0, s, c, E, t.t1_ptr, t.t1_e2, t.dst, w.u, w.q, k.v, k.Ssum);
-      hipLaunchKernelGGL(g_scale_rows, grid1(E * C), dim3(256), 0, s, E, C, w.fc3, k.Ssum, k.m);
+      hipLaunchKernelGGL(g_threebody_fwd, grid_for(E * c.L), dim3(256), 0, s, c, E, t.t1_ptr, t.t1_e2, t.dst, w.u, w.q, k.v, k.Ssum);
+      hipLaunchKernelGGL(g_scale_rows, grid_for(E * C), dim3(256), 0, s, E, C, w.fc3, k.Ssum, k.m);
     }
     linear(s, E, D, C, k.m, C, kw.wd, nullptr, k.pd, D);                    // three-body gated update, nn/interaction.py:220-221
     linear(s, E, D, C, k.m, C, kw.wg, nullptr, k.pg, D);
     gated(s, E * D, k.pd, k.pg, nullptr, w.e[b], k.e1);
-    if (E > 0) hipLaunchKernelGGL(g_concat, grid1(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, w.x[b], k.e1, w.cat);
+    if (E > 0) hipLaunchKernelGGL(g_concat, grid_for(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, w.x[b], k.e1, w.cat);
     gen_mlp_forward(s, E, D, R, kw.e, w, k, 0, k.e1, w.e[b + 1]);           // edge update
-    if (E > 0) hipLaunchKernelGGL(g_concat, grid1(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, w.x[b], w.e[b + 1], w.cat);
+    if (E > 0) hipLaunchKernelGGL(g_concat, grid_for(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, w.x[b], w.e[b + 1], w.cat);
     gen_mlp_forward(s, E, D, R, kw.n, w, k, 1, nullptr, w.msg);             // node message
     if (N > 0) {
       M3G_HIP_CHECK(hipMemcpyAsync(w.x[b + 1], w.x[b], sizeof(float) * N * D, hipMemcpyDeviceToDevice, s));
-      hipLaunchKernelGGL(g_segsum, grid1(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.msg, (int64_t)D, w.x[b + 1], (int64_t)D, 1);
+      hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.msg, (int64_t)D, w.x[b + 1], (int64_t)D, 1);
     }
   }
   // readout (nn/readout.py:39-58)
@@ -652,7 +651,7 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
   map(s, N * D, OP_SILU, w.rp2g, w.rh1);
   linear(s, N, 1, D, w.rh0, D, W.rw[0][2], W.rb[0][2], w.rod, 1);
   linear(s, N, 1, D, w.rh1, D, W.rw[1][2], W.rb[1][2], w.rog, 1);
-  if (N > 0) hipLaunchKernelGGL(g_atomic_energy, grid1(N), dim3(256), 0, s, N, c.num_types, c.energy_scale, io->atom_types, W.elemental, w.rod, w.rog, ea, t.flags);
+  if (N > 0) hipLaunchKernelGGL(g_atomic_energy, grid_for(N), dim3(256), 0, s, N, c.num_types, c.energy_scale, io->atom_types, W.elemental, w.rod, w.rog, ea, t.flags);
   M3G_HIP_CHECK(hipMemsetAsync(st, 0, sizeof(float) * S, s));
   launch_energy_sums(cc, t, ea, st, io->total_energy, s);
 
@@ -673,7 +672,7 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
     return M3G_OK;
   }
   // readout reverse: dL/d eps = energy_scale
-  if (N > 0) hipLaunchKernelGGL(g_readout_seed, grid1(N), dim3(256), 0, s, N, c.energy_scale, w.rod, w.rog, w.rod, w.rog);   // in place: d_od, d_og
+  if (N > 0) hipLaunchKernelGGL(g_readout_seed, grid_for(N), dim3(256), 0, s, N, c.energy_scale, w.rod, w.rog, w.rod, w.rog);   // in place: d_od, d_og
   linear_t(s, N, 1, D, w.rod, 1, W.rw[0][2], w.rh0, D);                    // d hidden-2 dense = d_od w3d
   linear_t(s, N, 1, D, w.rog, 1, W.rw[1][2], w.rh1, D);
   map(s, N * D, OP_MUL_DSILU, w.rp2d, w.rh0);                               // d p2
@@ -694,27 +693,27 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
     const GenBlockW& kw = W.blk[b];
     const GenWork::Blk& k = w.b[b];
     // node-message MLP: d msg[e] = dx[centre(e)]
-    if (E > 0) hipLaunchKernelGGL(g_gather, grid1(E * D), dim3(256), 0, s, E, D, t.src, dx_cur, (int64_t)D, w.hd, (int64_t)D, 0);
+    if (E > 0) hipLaunchKernelGGL(g_gather, grid_for(E * D), dim3(256), 0, s, E, D, t.src, dx_cur, (int64_t)D, w.hd, (int64_t)D, 0);
     gen_mlp_reverse(s, E, D, R, kw.n, w, k, 1, w.hd, w.de);                 // de (dL/de2) += node MLP's contribution
     // edge-update MLP with upstream dL/de2 (a copy: de itself receives the contribution)
     if (E > 0) M3G_HIP_CHECK(hipMemcpyAsync(w.hg, w.de, sizeof(float) * E * D, hipMemcpyDeviceToDevice, s));
     gen_mlp_reverse(s, E, D, R, kw.e, w, k, 0, w.hg, w.de);                 // de = dL/de1
     // three-body gated update reverse: d_pd, d_pg -> dm
-    if (E > 0) hipLaunchKernelGGL(g_gated_rev, grid1(E * D), dim3(256), 0, s, E * D, k.pd, k.pg, nullptr, w.de, w.t0, w.t1, nullptr);
+    if (E > 0) hipLaunchKernelGGL(g_gated_rev, grid_for(E * D), dim3(256), 0, s, E * D, k.pd, k.pg, nullptr, w.de, w.t0, w.t1, nullptr);
     linear_t(s, E, D, C, w.t0, D, kw.wd, w.dm, C);
     linear_t(s, E, D, C, w.t1, D, kw.wg, w.dm, C, /*beta=*/true);
     if (E > 0)
-      hipLaunchKernelGGL(g_threebody_rev, grid1(E), dim3(256), 0, s, c, E, t.t1_ptr, t.t1_e2, t.t2_ptr, t.t2_e1, t.dst, w.u, w.fc3, w.fc3p, w.q, w.qp,
+      hipLaunchKernelGGL(g_threebody_rev, grid_for(E), dim3(256), 0, s, c, E, t.t1_ptr, t.t1_e2, t.t2_ptr, t.t2_e1, t.dst, w.u, w.fc3, w.fc3p, w.q, w.qp,
                          k.v, k.Ssum, w.dm, w.dd, w.du, w.dgq);
     if (b > 0 && N > 0) {   // x^0 is the species embedding: its gradient is never needed
       // d_TA / d_TB = dp1 rows summed by centre / by neighbour, columns [edge dense | edge gate | node dense | node gate]
       for (int m = 0; m < 2; ++m) {
-        hipLaunchKernelGGL(g_segsum, grid1(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.dp1d[m], (int64_t)D, w.dTA + (2 * m) * D, (int64_t)4 * D, 0);
-        hipLaunchKernelGGL(g_segsum, grid1(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.dp1g[m], (int64_t)D, w.dTA + (2 * m + 1) * D, (int64_t)4 * D, 0);
-        hipLaunchKernelGGL(g_segsum, grid1(N * D), dim3(256), 0, s, N, D, t.in_ptr, t.in_edge, w.dp1d[m], (int64_t)D, w.dTB + (2 * m) * D, (int64_t)4 * D, 0);
-        hipLaunchKernelGGL(g_segsum, grid1(N * D), dim3(256), 0, s, N, D, t.in_ptr, t.in_edge, w.dp1g[m], (int64_t)D, w.dTB + (2 * m + 1) * D, (int64_t)4 * D, 0);
+        hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.dp1d[m], (int64_t)D, w.dTA + (2 * m) * D, (int64_t)4 * D, 0);
+        hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.dp1g[m], (int64_t)D, w.dTA + (2 * m + 1) * D, (int64_t)4 * D, 0);
+        hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.in_ptr, t.in_edge, w.dp1d[m], (int64_t)D, w.dTB + (2 * m) * D, (int64_t)4 * D, 0);
+        hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.in_ptr, t.in_edge, w.dp1g[m], (int64_t)D, w.dTB + (2 * m + 1) * D, (int64_t)4 * D, 0);
       }
-      hipLaunchKernelGGL(g_segsum, grid1(N * C), dim3(256), 0, s, N, C, t.in_ptr, t.in_edge, w.dgq, (int64_t)C, w.dv, (int64_t)C, 0);
+      hipLaunchKernelGGL(g_segsum, grid_for(N * C), dim3(256), 0, s, N, C, t.in_ptr, t.in_edge, w.dgq, (int64_t)C, w.dv, (int64_t)C, 0);
       map(s, N * C, OP_MUL_DSIGMOID_OF_V, k.v, w.dv);
       M3G_HIP_CHECK(hipMemcpyAsync(dx_alt, dx_cur, sizeof(float) * N * D, hipMemcpyDeviceToDevice, s));
       const GenBlockW::Mlp* mm[2] = {&kw.e, &kw.n};
@@ -731,7 +730,7 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
   // edge embedding reverse: dh += (de * SiLU'(pe0)) W_adj
   map(s, E * D, OP_MUL_DSILU, w.pe0, w.de);
   linear_t(s, E, D, R, w.de, D, W.adj, w.dh, R, true);
-  if (E > 0) hipLaunchKernelGGL(g_geometry_rev, grid1(E), dim3(256), 0, s, E, R, w.u, w.d, w.hp, w.dh, w.dd, w.du, w.dr);
+  if (E > 0) hipLaunchKernelGGL(g_geometry_rev, grid_for(E), dim3(256), 0, s, E, R, w.u, w.d, w.hp, w.dh, w.dd, w.du, w.dr);
   launch_force_gather(c.length_scale, t, w.dr, io->forces, io->stresses, s);
   if (io->stresses) {
     if (plan->opt.stress_mode == 1) {
@@ -834,7 +833,7 @@ extern "C" int m3g_linear(int64_t n, int32_t in, int32_t out, const float* X, co
 // y = a * b elementwise (the final dense(x) * gate(x) of GatedMLP.forward, nn/core.py:61-62)
 extern "C" int m3g_multiply(int64_t n, const float* a, const float* b, float* y, void* stream_) {
   if (n < 0 || (n > 0 && (!a || !b || !y))) { set_error("m3g_multiply: bad argument"); return M3G_ERR_VALUE; }
-  if (n > 0) hipLaunchKernelGGL(g_mul, grid1(n), dim3(256), 0, (hipStream_t)stream_, n, a, b, y);
+  if (n > 0) hipLaunchKernelGGL(g_mul, grid_for(n), dim3(256), 0, (hipStream_t)stream_, n, a, b, y);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }
@@ -846,7 +845,7 @@ extern "C" int m3g_bessel_basis(int32_t l_max, int32_t n_max, double cutoff, con
     return M3G_ERR_VALUE;
   }
   const GenConsts c = basis_consts(l_max, n_max, cutoff, cutoff, host_zeros, host_factors);
-  if (n > 0) hipLaunchKernelGGL(g_bessel_basis, grid1(n * c.C), dim3(256), 0, (hipStream_t)stream_, c, n, rs, out);
+  if (n > 0) hipLaunchKernelGGL(g_bessel_basis, grid_for(n * c.C), dim3(256), 0, (hipStream_t)stream_, c, n, rs, out);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }
@@ -871,7 +870,7 @@ extern "C" int m3g_three_body(int32_t l_max, int32_t n_max, int32_t D, double sc
   linear(s, N, C, D, x, D, w_sigmoid, b_sigmoid, v, C);
   map(s, N * C, OP_SIGMOID, v, v);
   M3G_HIP_CHECK(hipMemsetAsync(m, 0, sizeof(float) * E * C, s));
-  if (T > 0) hipLaunchKernelGGL(g_threebody_standalone, grid1(T * c.L), dim3(256), 0, s, c, T, E, edge_index, triplet_edge_index, edge_distances,
+  if (T > 0) hipLaunchKernelGGL(g_threebody_standalone, grid_for(T * c.L), dim3(256), 0, s, c, T, E, edge_index, triplet_edge_index, edge_distances,
                                 triplet_angles, v, m);
   linear(s, E, D, C, m, C, w_dense, nullptr, pd, D);
   linear(s, E, D, C, m, C, w_gate, nullptr, pg, D);
@@ -911,11 +910,11 @@ extern "C" int m3g_conv_block(int32_t D, int32_t R, int64_t N, int64_t E, int64_
     const float* const* a = host_params + 9 * m;
     q[m] = GenBlockW::Mlp{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]};
   }
-  if (E > 0) hipLaunchKernelGGL(g_concat, grid1(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, x, edge_attr, w.cat);
+  if (E > 0) hipLaunchKernelGGL(g_concat, grid_for(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, x, edge_attr, w.cat);
   gen_mlp_forward(s, E, D, R, q[0], w, k, 0, edge_attr, edge_attr);   // e += GatedMLP(concat) * (W_e h)
-  if (E > 0) hipLaunchKernelGGL(g_concat, grid1(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, x, edge_attr, w.cat);
+  if (E > 0) hipLaunchKernelGGL(g_concat, grid_for(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, x, edge_attr, w.cat);
   gen_mlp_forward(s, E, D, R, q[1], w, k, 1, nullptr, w.msg);
-  if (N > 0) hipLaunchKernelGGL(g_segsum, grid1(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.msg, (int64_t)D, x, (int64_t)D, 1);
+  if (N > 0) hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.msg, (int64_t)D, x, (int64_t)D, 1);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }
@@ -944,9 +943,9 @@ extern "C" int m3g_readout(int32_t D, int64_t N, int64_t S, const float* const* 
   linear(s, N, 1, D, t0, D, dp[4], dp[5], od, 1);
   linear(s, N, 1, D, t1, D, gp[4], gp[5], og, 1);
   M3G_HIP_CHECK(hipMemsetAsync(scaled_total, 0, sizeof(float) * S, s));
-  if (N > 0) hipLaunchKernelGGL(g_atomic_energy_standalone, grid1(N), dim3(256), 0, s, N, (float)energy_scale, elemental_per_atom, od, og, batch,
+  if (N > 0) hipLaunchKernelGGL(g_atomic_energy_standalone, grid_for(N), dim3(256), 0, s, N, (float)energy_scale, elemental_per_atom, od, og, batch,
                                 scaled_atomic, scaled_total);
-  if (S > 0) hipLaunchKernelGGL(g_scale, grid1(S), dim3(256), 0, s, S, (float)energy_scale, scaled_total, total);
+  if (S > 0) hipLaunchKernelGGL(g_scale, grid_for(S), dim3(256), 0, s, S, (float)energy_scale, scaled_total, total);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }

@@ -81,16 +81,8 @@ __global__ void __launch_bounds__(256) k_force_gather(float length_scale, int64_
     forces[i * 3 + 2] = fz / length_scale;
   }
   if (!st.counter) return;   // uniform
-  // publish this workgroup's forces, then count it: the workgroup that counts last sees all forces and forms the virial of
-  // every structure exactly as k_struct_stress does (no workgroup ever waits for another)
   __shared__ float part[kStructThreads * 6];
-  __shared__ int s_last;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(st.counter, 1) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (!last_workgroup(st.counter)) return;   // the virial of every structure, exactly as k_struct_stress forms it
   for (int s = 0; s < (int)st.S; ++s) struct_stress<256>(s, st.struct_ptr, st.flags, N, st.batch, st.pos, st.lattice, forces, st.stresses, part);
 }
 
@@ -192,8 +184,6 @@ __global__ void __launch_bounds__(256) k_edge_featurizer(Consts c, int64_t E, co
   radial_basis(c, d[e], h, hp);
   for (int m = 0; m < c.R; ++m) out[e * out_stride + m] = h[m];
 }
-
-static inline dim3 grid_for(int64_t n, int tpb = 256) { return dim3((unsigned)((n + tpb - 1) / tpb)); }
 
 void launch_geometry(const Consts& c, const Topo& t, const float* pos, const float* lattice, const int32_t* shift,
                      const Work& w, hipStream_t s) {

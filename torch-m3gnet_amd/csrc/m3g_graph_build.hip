@@ -24,8 +24,6 @@
 
 namespace m3g {
 
-static inline size_t align_up_g(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
 // Geometry shared by the search and by the skin-list update (m3g_verlet_*): the update must classify a pair exactly as a fresh
 // search would, so both go through these functions, compiled WITHOUT floating-point contraction (an fma formed in one caller and
 // not in the other would let the two disagree on a pair that sits on the cutoff sphere to within rounding).
@@ -103,7 +101,7 @@ static NbScratch nb_carve(int64_t N, int64_t S, int64_t M, void* base) {
   NbScratch w{};
   char* p = (char*)base;
   size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p ? (void*)(p + off) : nullptr; off += align_up_g(bytes); return r; };
+  auto take = [&](size_t bytes) { void* r = p ? (void*)(p + off) : nullptr; off += align_up(bytes); return r; };
   w.max_bins = 2 * N + 8 * S;   // k_struct_info keeps every structure within 2 count + 8 bins
   w.info = (StructInfo*)take(sizeof(StructInfo) * (size_t)(S + 1));
   w.bin_off = (int64_t*)take(sizeof(int64_t) * (size_t)(S + 2));
@@ -454,7 +452,7 @@ static VerletScratch verlet_carve(int64_t N, int64_t Ec, void* base) {
   VerletScratch w{};
   char* p = (char*)base;
   size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p ? (void*)(p + off) : nullptr; off += align_up_g(bytes); return r; };
+  auto take = [&](size_t bytes) { void* r = p ? (void*)(p + off) : nullptr; off += align_up(bytes); return r; };
   w.pos_w = (double*)take(sizeof(double) * 3 * (size_t)(N + 1));
   w.wrap = (int32_t*)take(sizeof(int32_t) * 3 * (size_t)(N + 1));
   w.state = (uint8_t*)take((size_t)Ec + 16);
@@ -831,7 +829,7 @@ static TbScratch tb_carve(int64_t N, int64_t E, void* base) {
   TbScratch w{};
   char* p = (char*)base;
   size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p ? (void*)(p + off) : nullptr; off += align_up_g(bytes); return r; };
+  auto take = [&](size_t bytes) { void* r = p ? (void*)(p + off) : nullptr; off += align_up(bytes); return r; };
   w.rank = (int32_t*)take(sizeof(int32_t) * (size_t)(E + 1));
   w.deg = (int32_t*)take(sizeof(int32_t) * (size_t)(N + 1));
   w.row_ptr = (int32_t*)take(sizeof(int32_t) * (size_t)(N + 2));
@@ -929,8 +927,6 @@ __global__ void __launch_bounds__(256) k_fill_triplets(int64_t N, int64_t E, int
 
 using namespace m3g;
 
-static inline dim3 g_for(int64_t n, int tpb = 256) { return dim3((unsigned)((n + tpb - 1) / tpb)); }
-
 extern "C" int m3g_neighbor_scratch_bytes(int64_t N, int64_t S, int64_t max_images, size_t* bytes) {
   if (!bytes || N < 0 || S < 0 || max_images < 1) { set_error("m3g_neighbor_scratch_bytes: bad argument"); return M3G_ERR_VALUE; }
   if (N * max_images >= (int64_t(1) << 31)) { set_error("neighbour search too large: atoms x images >= 2^31"); return M3G_ERR_UNSUPPORTED; }
@@ -956,17 +952,17 @@ extern "C" int m3g_neighbor_count_triplets(int64_t N, int64_t S, int64_t max_ima
   M3G_HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int), s));
   *host_n_edges = 0;
   if (N == 0 || S == 0) return M3G_OK;
-  hipLaunchKernelGGL(k_struct_info, g_for(S), dim3(256), 0, s, N, S, lattice, batch, cutoff, w.info, w.bin_off, flags, w.tri + N);
+  hipLaunchKernelGGL(k_struct_info, grid_for(S), dim3(256), 0, s, N, S, lattice, batch, cutoff, w.info, w.bin_off, flags, w.tri + N);
   M3G_HIP_CHECK(prims::exclusive_scan<int64_t>(w.bin_off, w.bin_off, S + 1, w.tmp, s));
   // atoms sorted by bin: a counting sort (bin ids are < max_bins) -- per-bin counters filled while the positions are wrapped, one
   // scan, one scatter
   M3G_HIP_CHECK(hipMemsetAsync(w.bin_start, 0, sizeof(int32_t) * (size_t)(w.max_bins + 2), s));
-  hipLaunchKernelGGL(k_wrap_positions, g_for(N), dim3(256), 0, s, N, S, pos, batch, w.info, w.bin_off, w.pos_w, w.wrap, w.binc, w.bin_key,
+  hipLaunchKernelGGL(k_wrap_positions, grid_for(N), dim3(256), 0, s, N, S, pos, batch, w.info, w.bin_off, w.pos_w, w.wrap, w.binc, w.bin_key,
                      w.bin_start, w.bin_rank, flags);
   M3G_HIP_CHECK(prims::exclusive_scan<int32_t>(w.bin_start, w.bin_start, w.max_bins + 2, w.tmp, s));
-  hipLaunchKernelGGL(k_bin_scatter, g_for(N), dim3(256), 0, s, N, w.bin_key, w.bin_rank, w.bin_start, w.pos_w, w.perm, w.pos_s);
+  hipLaunchKernelGGL(k_bin_scatter, grid_for(N), dim3(256), 0, s, N, w.bin_key, w.bin_rank, w.bin_start, w.pos_w, w.perm, w.pos_s);
   const int64_t NM = N * max_images;
-  hipLaunchKernelGGL((k_neighbors<false>), g_for(N * 64), dim3(256), 0, s, N, max_images, batch, w.info, w.bin_off, w.bin_start, w.perm, w.pos_s,
+  hipLaunchKernelGGL((k_neighbors<false>), grid_for(N * 64), dim3(256), 0, s, N, max_images, batch, w.info, w.bin_off, w.bin_start, w.perm, w.pos_s,
                      w.pos_w, w.binc, w.wrap, cutoff, w.counts, (int64_t)0, nullptr, nullptr, nullptr, threebody_cutoff, host_n_triplets ? w.tri : nullptr);
   M3G_HIP_CHECK(hipMemsetAsync(w.counts + NM, 0, sizeof(int64_t), s));
   M3G_HIP_CHECK(prims::exclusive_scan<int64_t>(w.counts, w.counts, NM + 1, w.tmp, s));
@@ -994,10 +990,10 @@ extern "C" int m3g_neighbor_fill(int64_t N, int64_t S, int64_t max_images, const
   if (n_edges == 0 || N == 0) return M3G_OK;
   if (!scratch || !edge_index || !edge_cell_shift || !distances) { set_error("m3g_neighbor_fill: null argument"); return M3G_ERR_VALUE; }
   NbScratch w = nb_carve(N, S, max_images, scratch);
-  hipLaunchKernelGGL((k_neighbors<true>), g_for(N * 64), dim3(256), 0, s, N, max_images, batch, w.info, w.bin_off, w.bin_start, w.perm,
+  hipLaunchKernelGGL((k_neighbors<true>), grid_for(N * 64), dim3(256), 0, s, N, max_images, batch, w.info, w.bin_off, w.bin_start, w.perm,
                      w.pos_s, w.pos_w, w.binc, w.wrap, cutoff, w.counts, n_edges, edge_index, edge_cell_shift, distances, 0.f, nullptr);
   // canonical order inside a centre: by the shift relative to the given coordinates (rows with a neighbour outside the home cell)
-  hipLaunchKernelGGL(k_rows_canonical, g_for(N * 64), dim3(256), 0, s, N, max_images, w.counts, w.wrap, n_edges, edge_index, edge_cell_shift, distances);
+  hipLaunchKernelGGL(k_rows_canonical, grid_for(N * 64), dim3(256), 0, s, N, max_images, w.counts, w.wrap, n_edges, edge_index, edge_cell_shift, distances);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }
@@ -1015,7 +1011,7 @@ extern "C" int m3g_verlet_rows(int64_t N, int64_t n_candidates, const int64_t* c
   if (!cand_row_ptr || (n_candidates > 0 && !cand_edge_index)) { set_error("m3g_verlet_rows: null argument"); return M3G_ERR_VALUE; }
   int* flags = (int*)(cand_row_ptr + N + 1);   // one spare word behind the row pointers (the caller allocates N + 2)
   M3G_HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int), s));
-  hipLaunchKernelGGL(k_rows_from_sorted, g_for(N + 1), dim3(256), 0, s, N, n_candidates, cand_edge_index, cand_row_ptr, flags);
+  hipLaunchKernelGGL(k_rows_from_sorted, grid_for(N + 1), dim3(256), 0, s, N, n_candidates, cand_edge_index, cand_row_ptr, flags);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }
@@ -1042,13 +1038,13 @@ extern "C" int m3g_verlet_update_async(int64_t N, int64_t S, int64_t Ec, const d
   // cand_state == NULL: fresh candidates, no lists built from them yet -- everything counts as changed (and no row has to say so)
   if (!cand_state) M3G_HIP_CHECK(hipMemsetAsync(w.acc + 1, 1, 1, s));
   if (N <= kVerletFusedMaxAtoms) {   // small cells: the whole pass in one launch
-    hipLaunchKernelGGL(k_verlet_update_small, g_for(N * 64), dim3(256), 0, s, N, S, Ec, pos, pos_ref, batch, lattice, cand_edge_index, cand_shift,
+    hipLaunchKernelGGL(k_verlet_update_small, grid_for(N * 64), dim3(256), 0, s, N, S, Ec, pos, pos_ref, batch, lattice, cand_edge_index, cand_shift,
                        cand_row_ptr, cutoff, threebody_cutoff, cand_state, w.state, w.dist, w.row_keep, w.row_tri, w.acc);
     M3G_HIP_CHECK(hipMemcpyAsync(host_out, w.acc, sizeof(uint64_t) * 6, hipMemcpyDeviceToHost, s));
     return M3G_OK;
   }
-  hipLaunchKernelGGL(k_verlet_prep, g_for(N), dim3(256), 0, s, N, S, pos, pos_ref, lattice, batch, w.pos_w, w.wrap, w.acc);
-  hipLaunchKernelGGL(k_verlet_rows, g_for(N * 64), dim3(256), 0, s, N, S, Ec, batch, lattice, cand_edge_index, cand_shift, cand_row_ptr, w.pos_w,
+  hipLaunchKernelGGL(k_verlet_prep, grid_for(N), dim3(256), 0, s, N, S, pos, pos_ref, lattice, batch, w.pos_w, w.wrap, w.acc);
+  hipLaunchKernelGGL(k_verlet_rows, grid_for(N * 64), dim3(256), 0, s, N, S, Ec, batch, lattice, cand_edge_index, cand_shift, cand_row_ptr, w.pos_w,
                      w.wrap, cutoff, threebody_cutoff, cand_state, w.state, w.dist, w.row_keep, w.row_tri, w.acc);
   hipLaunchKernelGGL(k_verlet_totals, dim3(1), dim3(1024), 0, s, N, w.row_keep, w.row_tri, cand_row_ptr, w.acc);
   M3G_HIP_CHECK(hipMemcpyAsync(host_out, w.acc, sizeof(uint64_t) * 6, hipMemcpyDeviceToHost, s));
@@ -1086,7 +1082,7 @@ extern "C" int m3g_verlet_fill(int64_t N, int64_t Ec, int64_t n_edges, void* scr
   VerletScratch w = verlet_carve(N, Ec, scratch);
   M3G_HIP_CHECK(hipMemsetAsync(w.row_keep + N, 0, sizeof(int32_t), s));
   M3G_HIP_CHECK(prims::exclusive_scan<int32_t>(w.row_keep, w.row_keep, N + 1, w.scan_tmp, s));
-  hipLaunchKernelGGL(k_verlet_fill, g_for(N * 64), dim3(256), 0, s, N, Ec, n_edges, cand_edge_index, cand_shift, cand_row_ptr, w.row_keep, w.state,
+  hipLaunchKernelGGL(k_verlet_fill, grid_for(N * 64), dim3(256), 0, s, N, Ec, n_edges, cand_edge_index, cand_shift, cand_row_ptr, w.row_keep, w.state,
                      w.dist, edge_index, edge_cell_shift, distances, cand_state);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
@@ -1109,7 +1105,7 @@ extern "C" int m3g_verlet_fill_lists(int64_t N, int64_t Ec, int64_t n_edges, int
   }
   VerletScratch w = verlet_carve(N, Ec, scratch);
   hipLaunchKernelGGL(k_verlet_offsets, dim3(1), dim3(kRefillScanThreads), 0, s, N, w.row_keep, w.row_tri, w.off_e, w.off_t);
-  hipLaunchKernelGGL(k_verlet_fill_lists, g_for(N * 64), dim3(256), 0, s, N, Ec, n_edges, n_triplets, cand_edge_index, cand_shift, cand_row_ptr, w.off_e,
+  hipLaunchKernelGGL(k_verlet_fill_lists, grid_for(N * 64), dim3(256), 0, s, N, Ec, n_edges, n_triplets, cand_edge_index, cand_shift, cand_row_ptr, w.off_e,
                      w.off_t, w.state, edge_index, edge_cell_shift, cand_state, triplet_edge_index, num_triplet_i, num_triplet_ij);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
@@ -1134,8 +1130,8 @@ extern "C" int m3g_threebody_count(int64_t N, int64_t E, const int64_t* edge_ind
   TbScratch w = tb_carve(N, E, scratch);
   int* flags = (int*)((char*)scratch + w.total);
   M3G_HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int), s));
-  hipLaunchKernelGGL(k_rows_from_sorted, g_for(N + 1), dim3(256), 0, s, N, E, edge_index, w.row_ptr, flags);
-  hipLaunchKernelGGL(k_rank_valid, g_for(N * 64), dim3(256), 0, s, N, w.row_ptr, distances, threebody_cutoff, w.rank, w.deg, w.counts);
+  hipLaunchKernelGGL(k_rows_from_sorted, grid_for(N + 1), dim3(256), 0, s, N, E, edge_index, w.row_ptr, flags);
+  hipLaunchKernelGGL(k_rank_valid, grid_for(N * 64), dim3(256), 0, s, N, w.row_ptr, distances, threebody_cutoff, w.rank, w.deg, w.counts);
   M3G_HIP_CHECK(hipMemsetAsync(w.counts + E, 0, sizeof(int64_t), s));
   M3G_HIP_CHECK(prims::exclusive_scan<int64_t>(w.counts, w.counts, E + 1, w.scan_tmp, s));
   int h_flags = 0;
@@ -1160,11 +1156,11 @@ extern "C" int m3g_threebody_build(int64_t N, int64_t E, const int64_t* edge_ind
   TbScratch w = tb_carve(N, E, scratch);
   int* flags = (int*)((char*)scratch + w.total);
   M3G_HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int), s));
-  hipLaunchKernelGGL(k_rows_from_sorted, g_for(N + 1), dim3(256), 0, s, N, E, edge_index, w.row_ptr, flags);
-  hipLaunchKernelGGL(k_rank_valid, g_for(N * 64), dim3(256), 0, s, N, w.row_ptr, distances, threebody_cutoff, w.rank, w.deg, w.counts);
+  hipLaunchKernelGGL(k_rows_from_sorted, grid_for(N + 1), dim3(256), 0, s, N, E, edge_index, w.row_ptr, flags);
+  hipLaunchKernelGGL(k_rank_valid, grid_for(N * 64), dim3(256), 0, s, N, w.row_ptr, distances, threebody_cutoff, w.rank, w.deg, w.counts);
   M3G_HIP_CHECK(hipMemsetAsync(w.counts + E, 0, sizeof(int64_t), s));
   M3G_HIP_CHECK(prims::exclusive_scan<int64_t>(w.counts, w.counts, E + 1, w.scan_tmp, s));
-  hipLaunchKernelGGL(k_fill_triplets, g_for(N * 64), dim3(256), 0, s, N, E, n_triplets, w.row_ptr, w.rank, w.deg, w.counts, triplet_edge_index,
+  hipLaunchKernelGGL(k_fill_triplets, grid_for(N * 64), dim3(256), 0, s, N, E, n_triplets, w.row_ptr, w.rank, w.deg, w.counts, triplet_edge_index,
                      num_triplet_i, num_triplet_ij);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
@@ -1176,7 +1172,7 @@ extern "C" int m3g_threebody_fill(int64_t N, int64_t E, const int64_t* edge_inde
   if (N == 0) return M3G_OK;
   if (!scratch || (n_triplets > 0 && !triplet_edge_index)) { set_error("m3g_threebody_fill: null argument"); return M3G_ERR_VALUE; }
   TbScratch w = tb_carve(N, E, scratch);
-  hipLaunchKernelGGL(k_fill_triplets, g_for(N * 64), dim3(256), 0, s, N, E, n_triplets, w.row_ptr, w.rank, w.deg, w.counts, triplet_edge_index,
+  hipLaunchKernelGGL(k_fill_triplets, grid_for(N * 64), dim3(256), 0, s, N, E, n_triplets, w.row_ptr, w.rank, w.deg, w.counts, triplet_edge_index,
                      num_triplet_i, num_triplet_ij);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;

@@ -225,6 +225,12 @@ struct m3g_plan {
 
 namespace m3g {
 
+// ---- host helpers shared by the launchers ----------------------------------------------------------------
+// sizes of carved sub-buffers: every array starts on a 256-byte boundary
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+// grid of a launch with one thread (or one group of `per`) per item
+inline dim3 grid_for(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
+
 // ---- topology view (device arrays carved from the caller's topo buffer) -----------------------------
 // compile-time dispatch on (l_max, n_max) <= (4, 4): BODY sees constexpr int L, R
 #define M3G_LR_CASE(l, r, ...) case l * 8 + r: { constexpr int L = l, R = r; __VA_ARGS__; } break;

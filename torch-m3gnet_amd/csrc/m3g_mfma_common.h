@@ -220,9 +220,10 @@ __device__ __forceinline__ f32x4 unpack24_fixed(const u32x3& w, float inv9) {
                (__builtin_bit_cast(float, c) - kFix24Magic) * inv9, (__builtin_bit_cast(float, d) - kFix24Magic) * inv9};
 }
 
+__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 template <int N>
 __device__ __forceinline__ void zero(f32x4 (&v)[N]) {
-  static_for<N>([&]<int i>() { v[i] = f32x4{0.f, 0.f, 0.f, 0.f}; });
+  static_for<N>([&]<int i>() { v[i] = zero4(); });
 }
 
 }  // namespace m3g

@@ -249,7 +249,7 @@ extern "C" int m3g_neb_forces(int64_t n_atoms, int64_t n_images, int64_t n_bands
   const NebView st = neb_view(N, I, B, state);
   const dim3 grid((unsigned)chunk_bound(N, I));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_neb_partials, grid, dim3(kChunkRows), 0, s, st, pos, forces);
-  hipLaunchKernelGGL(k_neb_finalize, blocks_for(B, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, energies, rows);
+  hipLaunchKernelGGL(k_neb_finalize, grid_for(B, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, energies, rows);
   hipLaunchKernelGGL(k_neb_apply, grid, dim3(kChunkRows), 0, s, st, pos, forces, neb_forces);
   M3G_RETURN_LAUNCH_STATUS();
 }

@@ -18,9 +18,8 @@ __global__ void __launch_bounds__(256) k_embed_nodes(int64_t N, int num_types, c
   if (idx >= N * kDP) return;
   int64_t a = idx / kDP;
   int o = (int)(idx % kDP);
-  int64_t ty = types[a];
-  ty = ty < 0 ? 0 : (ty >= num_types ? num_types - 1 : ty);
-  x[idx] = emb[ty * kDP + o];
+  bool bad;   // (reported by the readout kernels)
+  x[idx] = emb[species_index(types[a], num_types, bad) * kDP + o];
 }
 
 // e0[e,:] = SiLU(W_adj h[e,:])
@@ -290,8 +289,6 @@ __global__ void __launch_bounds__(256) k_copy_expand_rows(int64_t n, int width, 
   const int r = row_id[e];
   out[e * out_stride + o] = r >= 0 ? in[(int64_t)r * in_stride + o] : 0.f;
 }
-
-static inline dim3 grid_for(int64_t n, int tpb = 256) { return dim3((unsigned)((n + tpb - 1) / tpb)); }
 
 void launch_embed(const Consts& c, const float* W, const WeightLayout& wl, const Topo& t, const int64_t* types,
                   const Work& w, hipStream_t s) {

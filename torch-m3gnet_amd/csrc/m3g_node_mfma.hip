@@ -13,6 +13,39 @@ namespace m3g {
 // re-read 128 KB of weights from L2 for every 16 atoms.  x^b = x^(b-1) + the per-centre message sums of block b-1 is
 // formed while the tile is loaded (x_prev != nullptr) and written back for the later stages.
 constexpr int kNodeXPitch = 68;   // floats per staged x row: 64 + 4 keeps 16-byte alignment and spreads the 16 rows over the banks
+// Forming a tile's x rows, lane (m, q) holding features 16q .. 16q+15 of atom m: x^b = x^(b-1) + the per-centre message sums the
+// forward edge kernel of block b-1 left as partial rows (seg_first: a run starting mid-tile, seg_head: one row per 16-edge tile, see
+// seg_scan) -- folded into the consumers of x^b instead of a kernel of its own.
+__device__ __forceinline__ void add_message_sums(f32x4 (&xr)[4], int64_t atom, int q, const float* __restrict__ seg_head,
+                                                 const float* __restrict__ seg_first, const int32_t* __restrict__ row_ptr) {
+  const int r0 = row_ptr[atom], r1 = row_ptr[atom + 1];
+  if (r1 > r0) {
+    if (r0 & 15) static_for<4>([&]<int j>() { xr[j] += *(const f32x4*)(seg_first + atom * (4 * kDP) + 16 * q + 4 * j); });
+    for (int t = (r0 + 15) >> 4; t <= (r1 - 1) >> 4; ++t)
+      static_for<4>([&]<int j>() { xr[j] += *(const f32x4*)(seg_head + (int64_t)t * (4 * kDP) + 16 * q + 4 * j); });
+  }
+}
+// ... written back for the later stages by the one wave (or pass) its caller picks
+__device__ __forceinline__ void store_x_row(float* __restrict__ x, int64_t atom, int q, const f32x4 (&xr)[4]) {
+  static_for<4>([&]<int j>() { *(f32x4*)(x + atom * kDP + 16 * q + 4 * j) = xr[j]; });
+}
+// ... staged in the wave's own LDS area and read back as accumulator-layout blocks: lane (m, q) holds features blk*16 + 4q + {0..3}
+// of atom m (only this wave touches xs: LDS operations of a wave complete in order)
+__device__ __forceinline__ void x_rows_to_blocks(float* xs, int m, int q, const f32x4 (&xr)[4], f32x4 (&xb)[4]) {
+  static_for<4>([&]<int j>() { *(f32x4*)(xs + m * kNodeXPitch + 16 * q + 4 * j) = xr[j]; });
+  static_for<4>([&]<int blk>() { xb[blk] = *(const f32x4*)(xs + m * kNodeXPitch + blk * 16 + 4 * q); });
+}
+// One 16-row block of [TA | TB | v]^T goes out by its output block index: 0-15 -> TA, 16-31 -> TB, 32 -> v = sigmoid (channels >= C zero)
+__device__ __forceinline__ void store_node_block(int ob, const f32x4& acc, int64_t atom, int q, int C, float* __restrict__ TA, float* __restrict__ TB,
+                                                 float* __restrict__ v) {
+  if (ob < 16) *(f32x4*)(TA + atom * (4 * kDP) + ob * 16 + 4 * q) = acc;
+  else if (ob < 32) *(f32x4*)(TB + atom * (4 * kDP) + (ob - 16) * 16 + 4 * q) = acc;
+  else {
+    f32x4 o;
+    static_for<4>([&]<int r>() { o[r] = 4 * q + r < C ? fsigmoid(acc[r]) : 0.f; });
+    *(f32x4*)(v + atom * kCP + 4 * q) = o;
+  }
+}
 // One of the three 11-row-block passes per WORKGROUP (blockIdx.x % 3): its third of the weight image (45 KB + the biases) is all
 // the workgroup stages, two to three workgroups share a CU, and a small system's tiles spread over three times as many waves.
 // (Until round 3 every workgroup staged the whole 135-KB image and walked all three passes -- or, for small systems, gave its
@@ -28,15 +61,16 @@ __global__ void __launch_bounds__(256) k_node_pre_mfma(int C, int64_t N, const f
   constexpr int kBiasFloats = kNodeRowBlocks * 16;
   __shared__ __attribute__((aligned(16))) float lds[kNodePassFloats + kBiasFloats + 4 * 16 * kNodeXPitch];
   const int g = blockIdx.x % 3;   // this workgroup's pass (uniform)
-  {  // this pass's image chunk and the biases -> LDS, every 16-byte load of a thread in flight at once
+  {  // this pass's image chunk and the biases -> LDS, every 16-byte load of a thread in flight at once (not load_image
+     // of m3g_edge_common.h: folding either copy of this file into it changes the compiled kernels -- profiles/device_idioms.txt)
     constexpr int kVec = kNodePassFloats / 4, kPer = (kVec + 255) / 256;
     const float* src = img + (size_t)g * kNodePassFloats;
     f32x4 t[kPer];
     static_for<kPer>([&]<int j>() {
       const int i = j * 256 + (int)threadIdx.x;
-      t[j] = i < kVec ? *(const f32x4*)(src + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+      t[j] = i < kVec ? *(const f32x4*)(src + 4 * i) : zero4();
     });
-    const f32x4 tb = (int)threadIdx.x < kBiasFloats / 4 ? *(const f32x4*)(img + kNodeRowBlocks * 16 * 64 + 4 * threadIdx.x) : f32x4{0.f, 0.f, 0.f, 0.f};
+    const f32x4 tb = (int)threadIdx.x < kBiasFloats / 4 ? *(const f32x4*)(img + kNodeRowBlocks * 16 * 64 + 4 * threadIdx.x) : zero4();
     static_for<kPer>([&]<int j>() {
       const int i = j * 256 + (int)threadIdx.x;
       if (i < kVec) *(f32x4*)(lds + 4 * i) = t[j];
@@ -53,31 +87,22 @@ __global__ void __launch_bounds__(256) k_node_pre_mfma(int C, int64_t N, const f
     const int64_t atom = tile * 16 + m;
     const bool live = atom < N;
     f32x4 xr[4];
-    static_for<4>([&]<int j>() { xr[j] = f32x4{0.f, 0.f, 0.f, 0.f}; });
+    static_for<4>([&]<int j>() { xr[j] = zero4(); });
     if (live) {
       const float* src = (x_prev ? x_prev : x) + atom * kDP + 16 * q;
       if (types) {   // block 0: x^0 = atom embedding row (nn/featurizer.py:99-103), formed and stored here
-        int64_t ty = types[atom];
-        ty = ty < 0 ? 0 : (ty >= num_types ? num_types - 1 : ty);
-        src = emb + ty * kDP + 16 * q;
+        bool bad;    // (reported by the readout kernels)
+        src = emb + species_index(types[atom], num_types, bad) * kDP + 16 * q;
       }
       static_for<4>([&]<int j>() { xr[j] = *(const f32x4*)(src + 4 * j); });
-      if (types && g == 0) static_for<4>([&]<int j>() { *(f32x4*)(x + atom * kDP + 16 * q + 4 * j) = xr[j]; });
+      if (types && g == 0) store_x_row(x, atom, q, xr);
       if (x_prev) {
-        const int r0 = row_ptr[atom], r1 = row_ptr[atom + 1];
-        if (r1 > r0) {
-          if (r0 & 15) static_for<4>([&]<int j>() { xr[j] += *(const f32x4*)(seg_first + atom * (4 * kDP) + 16 * q + 4 * j); });
-          for (int t = (r0 + 15) >> 4; t <= (r1 - 1) >> 4; ++t)
-            static_for<4>([&]<int j>() { xr[j] += *(const f32x4*)(seg_head + (int64_t)t * (4 * kDP) + 16 * q + 4 * j); });
-        }
-        if (g == 0) static_for<4>([&]<int j>() { *(f32x4*)(x + atom * kDP + 16 * q + 4 * j) = xr[j]; });   // (the pass-0 workgroup writes x^b back)
+        add_message_sums(xr, atom, q, seg_head, seg_first, row_ptr);
+        if (g == 0) store_x_row(x, atom, q, xr);   // (the pass-0 workgroup writes x^b back)
       }
     }
-    static_for<4>([&]<int j>() { *(f32x4*)(xs + m * kNodeXPitch + 16 * q + 4 * j) = xr[j]; });
-    // (only this wave reads xs: LDS operations of a wave complete in order)
-    // x as accumulator-layout blocks: lane (m, q) holds features blk*16 + 4q + {0..3} of atom m
     f32x4 xb[4];
-    static_for<4>([&]<int blk>() { xb[blk] = *(const f32x4*)(xs + m * kNodeXPitch + blk * 16 + 4 * q); });
+    x_rows_to_blocks(xs, m, q, xr, xb);
     int lv = lane;
     asm volatile("" : "+v"(lv));   // keep the image reads inside the tile loop
     static_for<3>([&]<int G>() {   // 11 row blocks: split-precision chains like the edge kernels' (fp32 accumulate)
@@ -85,18 +110,7 @@ __global__ void __launch_bounds__(256) k_node_pre_mfma(int C, int64_t N, const f
       f32x4 acc[11];
       static_for<11>([&]<int j>() { acc[j] = *(const f32x4*)(bias + (11 * G + j) * 16 + 4 * q); });
       chain_p<PREC, 11, 2>(lds, xb, acc, lv, w_inv);
-      if (live) {
-        static_for<11>([&]<int j>() {
-          constexpr int ob = 11 * G + j;
-          if (ob < 16) *(f32x4*)(TA + atom * (4 * kDP) + ob * 16 + 4 * q) = acc[j];
-          else if (ob < 32) *(f32x4*)(TB + atom * (4 * kDP) + (ob - 16) * 16 + 4 * q) = acc[j];
-          else {
-            f32x4 o;
-            static_for<4>([&]<int r>() { o[r] = 4 * q + r < C ? fsigmoid(acc[j][r]) : 0.f; });
-            *(f32x4*)(v + atom * kCP + 4 * q) = o;
-          }
-        });
-      }
+      if (live) static_for<11>([&]<int j>() { store_node_block(11 * G + j, acc[j], atom, q, C, TA, TB, v); });
     });
   }
 }
@@ -148,29 +162,24 @@ __device__ __forceinline__ void node_pre_split_body(const NodePreArgs& args, int
   const int64_t atom = tile * 16 + m;
   const bool live = atom < N;
   f32x4 xr[4];
-  static_for<4>([&]<int j>() { xr[j] = f32x4{0.f, 0.f, 0.f, 0.f}; });
+  static_for<4>([&]<int j>() { xr[j] = zero4(); });
   if (live) {
     const float* src = (x_prev ? x_prev : x) + atom * kDP + 16 * q;
     if (types) {   // block 0: x^0 = atom embedding row (nn/featurizer.py:99-103), formed and stored here
-      int64_t ty = types[atom];
+      int64_t ty = types[atom];   // (species_index's clamp, spelled out: through it k_geometry_node_pre compiles to two v_mov_b32 less)
       ty = ty < 0 ? 0 : (ty >= num_types ? num_types - 1 : ty);
       src = emb + ty * kDP + 16 * q;
     }
     static_for<4>([&]<int j>() { xr[j] = *(const f32x4*)(src + 4 * j); });
-    if (types && g == 0 && w == 0) static_for<4>([&]<int j>() { *(f32x4*)(x + atom * kDP + 16 * q + 4 * j) = xr[j]; });
+    if (types && g == 0 && w == 0) store_x_row(x, atom, q, xr);
     if (x_prev) {
-      const int r0 = row_ptr[atom], r1 = row_ptr[atom + 1];
-      if (r1 > r0) {
-        if (r0 & 15) static_for<4>([&]<int j>() { xr[j] += *(const f32x4*)(seg_first + atom * (4 * kDP) + 16 * q + 4 * j); });
-        for (int t = (r0 + 15) >> 4; t <= (r1 - 1) >> 4; ++t)
-          static_for<4>([&]<int j>() { xr[j] += *(const f32x4*)(seg_head + (int64_t)t * (4 * kDP) + 16 * q + 4 * j); });
-      }
-      if (g == 0 && w == 0) static_for<4>([&]<int j>() { *(f32x4*)(x + atom * kDP + 16 * q + 4 * j) = xr[j]; });   // (one wave writes x^b back)
+      add_message_sums(xr, atom, q, seg_head, seg_first, row_ptr);
+      if (g == 0 && w == 0) store_x_row(x, atom, q, xr);   // (one wave writes x^b back)
     }
   }
-  static_for<4>([&]<int j>() { *(f32x4*)(xs + m * kNodeXPitch + 16 * q + 4 * j) = xr[j]; });
-  f32x4 xb[4];   // (only this wave reads its staging area)
-  static_for<4>([&]<int blk>() { xb[blk] = *(const f32x4*)(xs + m * kNodeXPitch + blk * 16 + 4 * q); });
+  f32x4 xb[4];
+  x_rows_to_blocks(xs, m, q, xr, xb);
+  // (chain_reg16 per row block would issue each block's 16 steps in a row: interleaved, a step waits only for its own weight loads)
   static_for<4>([&]<int blk>() {
     static_for<4>([&]<int r>() {
       const float b = xb[blk][r];
@@ -181,14 +190,7 @@ __device__ __forceinline__ void node_pre_split_body(const NodePreArgs& args, int
   static_for<3>([&]<int jj>() {
     const int j = w + 4 * jj;
     if (j >= 11) return;
-    const int ob = 11 * g + j;
-    if (ob < 16) *(f32x4*)(TA + atom * (4 * kDP) + ob * 16 + 4 * q) = acc[jj];
-    else if (ob < 32) *(f32x4*)(TB + atom * (4 * kDP) + (ob - 16) * 16 + 4 * q) = acc[jj];
-    else {
-      f32x4 o;
-      static_for<4>([&]<int r>() { o[r] = 4 * q + r < C ? fsigmoid(acc[jj][r]) : 0.f; });
-      *(f32x4*)(v + atom * kCP + 4 * q) = o;
-    }
+    store_node_block(11 * g + j, acc[jj], atom, q, C, TA, TB, v);
   });
 }
 
@@ -223,13 +225,13 @@ __global__ void __launch_bounds__(256) k_readout_mfma(Consts c, int64_t N, const
   __shared__ __attribute__((aligned(16))) float lds[ReadoutImg::total + 4 * 16 * kNodeXPitch];
   // the per-structure sums are accumulated with atomics by the next kernel: cleared here instead of a memset launch
   if (blockIdx.x == 0) for (int64_t i = threadIdx.x; i < S; i += blockDim.x) scaled_total[i] = 0.f;
-  {
+  {  // (load_image with a batch of 16 and 256 threads, spelled out: see k_node_pre_mfma)
     constexpr int kVec = ReadoutImg::total / 4, kBatch = 16;
     for (int base = 0; base < kVec; base += 256 * kBatch) {
       f32x4 t[kBatch];
       static_for<kBatch>([&]<int j>() {
         const int i = base + j * 256 + (int)threadIdx.x;
-        t[j] = i < kVec ? *(const f32x4*)(img + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+        t[j] = i < kVec ? *(const f32x4*)(img + 4 * i) : zero4();
       });
       static_for<kBatch>([&]<int j>() {
         const int i = base + j * 256 + (int)threadIdx.x;
@@ -245,23 +247,18 @@ __global__ void __launch_bounds__(256) k_readout_mfma(Consts c, int64_t N, const
     const int64_t atom = tile * 16 + m;
     const bool live = atom < N;
     f32x4 xr[4];
-    static_for<4>([&]<int j>() { xr[j] = f32x4{0.f, 0.f, 0.f, 0.f}; });
+    static_for<4>([&]<int j>() { xr[j] = zero4(); });
     if (live) {
       const float* src = (x_prev ? x_prev : x) + atom * kDP + 16 * q;
       static_for<4>([&]<int j>() { xr[j] = *(const f32x4*)(src + 4 * j); });
       if (x_prev) {
-        const int r0 = row_ptr[atom], r1 = row_ptr[atom + 1];
-        if (r1 > r0) {
-          if (r0 & 15) static_for<4>([&]<int j>() { xr[j] += *(const f32x4*)(seg_first + atom * (4 * kDP) + 16 * q + 4 * j); });
-          for (int t = (r0 + 15) >> 4; t <= (r1 - 1) >> 4; ++t)
-            static_for<4>([&]<int j>() { xr[j] += *(const f32x4*)(seg_head + (int64_t)t * (4 * kDP) + 16 * q + 4 * j); });
-        }
+        add_message_sums(xr, atom, q, seg_head, seg_first, row_ptr);
+        // (store_x_row, spelled out: through the helper this kernel compiles to one v_mov_b32 less -- profiles/device_idioms.txt)
         static_for<4>([&]<int j>() { *(f32x4*)(x + atom * kDP + 16 * q + 4 * j) = xr[j]; });
       }
     }
-    static_for<4>([&]<int j>() { *(f32x4*)(xs + m * kNodeXPitch + 16 * q + 4 * j) = xr[j]; });
     f32x4 xb[4];
-    static_for<4>([&]<int blk>() { xb[blk] = *(const f32x4*)(xs + m * kNodeXPitch + blk * 16 + 4 * q); });
+    x_rows_to_blocks(xs, m, q, xr, xb);
     int lv = lane;
     asm volatile("" : "+v"(lv));
     // layer 1 (dense blocks 0-3, gate 4-7): p1 -> hidden, p1 keeps SiLU'
@@ -320,15 +317,7 @@ __global__ void __launch_bounds__(256) k_readout_mfma(Consts c, int64_t N, const
     if (live) static_for<4>([&]<int blk>() { *(f32x4*)(dx + atom * kDP + blk * 16 + 4 * q) = dxb[blk]; });
   }
   if (!rs.counter) return;   // uniform
-  // per-structure energy sums by the LAST workgroup of this launch (few structures: one launch less than k_struct_energy, same
-  // fixed summation order -> bit-identical totals; no workgroup waits for another)
-  __shared__ int s_last;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(rs.counter, 1) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (!last_workgroup(rs.counter)) return;   // per-structure energy sums (few structures: one launch less than k_struct_energy)
   float* part = lds + ReadoutImg::total;   // the x staging area (4 x 16 x kNodeXPitch floats >= kStructThreads)
   static_assert(4 * 16 * kNodeXPitch >= kStructThreads, "staging area too small for the energy sums");
   for (int sidx = 0; sidx < (int)S; ++sidx)
@@ -374,23 +363,17 @@ __global__ void __launch_bounds__(256) k_readout_split(Consts c, int64_t N, cons
     const bool live = atom < N;
     // x^B = x^(B-1) + per-centre message sums, formed by every wave for itself (wave 0 stores it)
     f32x4 xr[4];
-    static_for<4>([&]<int j>() { xr[j] = f32x4{0.f, 0.f, 0.f, 0.f}; });
+    static_for<4>([&]<int j>() { xr[j] = zero4(); });
     if (live) {
       const float* src = (x_prev ? x_prev : x) + atom * kDP + 16 * q;
       static_for<4>([&]<int j>() { xr[j] = *(const f32x4*)(src + 4 * j); });
       if (x_prev) {
-        const int r0 = row_ptr[atom], r1 = row_ptr[atom + 1];
-        if (r1 > r0) {
-          if (r0 & 15) static_for<4>([&]<int j>() { xr[j] += *(const f32x4*)(seg_first + atom * (4 * kDP) + 16 * q + 4 * j); });
-          for (int t = (r0 + 15) >> 4; t <= (r1 - 1) >> 4; ++t)
-            static_for<4>([&]<int j>() { xr[j] += *(const f32x4*)(seg_head + (int64_t)t * (4 * kDP) + 16 * q + 4 * j); });
-        }
-        if (w == 0) static_for<4>([&]<int j>() { *(f32x4*)(x + atom * kDP + 16 * q + 4 * j) = xr[j]; });
+        add_message_sums(xr, atom, q, seg_head, seg_first, row_ptr);
+        if (w == 0) store_x_row(x, atom, q, xr);
       }
     }
-    static_for<4>([&]<int j>() { *(f32x4*)(xw + m * kNodeXPitch + 16 * q + 4 * j) = xr[j]; });
-    f32x4 xb[4];   // (only this wave reads its staging area: LDS operations of a wave complete in order)
-    static_for<4>([&]<int blk>() { xb[blk] = *(const f32x4*)(xw + m * kNodeXPitch + blk * 16 + 4 * q); });
+    f32x4 xb[4];
+    x_rows_to_blocks(xw, m, q, xr, xb);
     // layer 1, rows w (dense) and 4 + w (gate): p1 -> hidden, p1 keeps SiLU'
     f32x4 p1d = b1[0], p1g = b1[1];
     static_for<4>([&]<int blk>() {
@@ -456,7 +439,7 @@ __global__ void __launch_bounds__(256) k_readout_split(Consts c, int64_t N, cons
       __syncthreads();
       f32x4 d2[8];
       static_for<8>([&]<int ob>() { d2[ob] = *(const f32x4*)(hs + ob * 256 + lane * 4); });
-      f32x4 dp1d = {0.f, 0.f, 0.f, 0.f}, dp1g = {0.f, 0.f, 0.f, 0.f};
+      f32x4 dp1d = zero4(), dp1g = zero4();
       static_for<4>([&]<int blk>() {
         static_for<4>([&]<int r>() {
           dp1d = mfma16(a_w2t[0][blk * 4 + r], d2[blk][r], dp1d);
@@ -471,20 +454,14 @@ __global__ void __launch_bounds__(256) k_readout_split(Consts c, int64_t N, cons
       __syncthreads();
       f32x4 dp1[8];
       static_for<8>([&]<int ob>() { dp1[ob] = *(const f32x4*)(hs + ob * 256 + lane * 4); });
-      f32x4 dxb = {0.f, 0.f, 0.f, 0.f};
+      f32x4 dxb = zero4();
       static_for<8>([&]<int blk>() { static_for<4>([&]<int r>() { dxb = mfma16(a_w1t[blk * 4 + r], dp1[blk][r], dxb); }); });
       if (live) *(f32x4*)(dx + atom * kDP + w * 16 + 4 * q) = dxb;
     }
     __syncthreads();   // hs is rewritten by the next tile
   }
   if (!rs.counter) return;   // uniform
-  __shared__ int s_last;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(rs.counter, 1) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (!last_workgroup(rs.counter)) return;
   for (int sidx = 0; sidx < (int)S; ++sidx)
     struct_energy<256>(sidx, rs.struct_ptr, rs.flags, N, rs.batch, scaled_atomic, c.energy_scale, scaled_total, rs.total, xs);
 }
@@ -497,23 +474,20 @@ void launch_readout_mfma(const m3g_plan* plan, const StepPath& p, const Consts& 
     const int64_t tiles = (t.N + 15) / 16;
     const int wgs = (int)std::min<int64_t>((tiles + 3) / 4, 256);
     const ReadoutSums rs{t.struct_ptr, t.flags, t.batch, total, p.readout_sums ? w.sync + kSyncReadout : nullptr};
+    // one argument list for the four kernels: image, its inverse weight scale (k_readout_mfma only), dE/dx wanted or not
+    auto launch = [&](auto kernel, unsigned grid, const float* img, auto... w_inv) {
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, c, t.N, img, w_inv..., plan->d_weights + wl.elemental, types, x_prev, w.seg_head,
+                         w.seg_first, t.row_ptr, x, scaled_atomic, want_grad ? w.dx : nullptr, scaled_total, t.S, rs);
+    };
     if (p.readout == kReadoutSplit) {   // small systems: a tile over the four waves of a workgroup
-      if (want_grad)
-        hipLaunchKernelGGL(k_readout_split<true>, dim3((unsigned)tiles), dim3(256), 0, s, c, t.N, plan->d_readout_img, plan->d_weights + wl.elemental,
-                           types, x_prev, w.seg_head, w.seg_first, t.row_ptr, x, scaled_atomic, w.dx, scaled_total, t.S, rs);
-      else
-        hipLaunchKernelGGL(k_readout_split<false>, dim3((unsigned)tiles), dim3(256), 0, s, c, t.N, plan->d_readout_img, plan->d_weights + wl.elemental,
-                           types, x_prev, w.seg_head, w.seg_first, t.row_ptr, x, scaled_atomic, nullptr, scaled_total, t.S, rs);
-    } else
-    if (p.readout == kReadoutF16)   // (option; default: exact-fp32 readout in every mode)
-      hipLaunchKernelGGL(k_readout_mfma<kPrecF16x3>, dim3(wgs), dim3(256), 0, s, c, t.N, plan->d_readout_img_h, plan->ro_w_scale_inv,
-                         plan->d_weights + wl.elemental, types, x_prev, w.seg_head, w.seg_first, t.row_ptr, x, scaled_atomic,
-                         want_grad ? w.dx : nullptr, scaled_total, t.S, rs);
-    else   // every mode by default: this stage forms the energies and seeds the reverse pass (bf16x3 products here moved the Cu-32 virial from
-           // 4.5e-5 to 1.2e-4 of its fp64 value; f16x3 products put a six-atom structure's ill-conditioned energy 5.3e-5 off instead of 9e-6)
-      hipLaunchKernelGGL(k_readout_mfma<kPrecF32>, dim3(wgs), dim3(256), 0, s, c, t.N, plan->d_readout_img, 1.f,
-                         plan->d_weights + wl.elemental, types, x_prev, w.seg_head, w.seg_first, t.row_ptr, x, scaled_atomic,
-                         want_grad ? w.dx : nullptr, scaled_total, t.S, rs);
+      if (want_grad) launch(k_readout_split<true>, (unsigned)tiles, plan->d_readout_img);
+      else launch(k_readout_split<false>, (unsigned)tiles, plan->d_readout_img);
+    } else if (p.readout == kReadoutF16) {   // (option; default: exact-fp32 readout in every mode)
+      launch(k_readout_mfma<kPrecF16x3>, (unsigned)wgs, plan->d_readout_img_h, plan->ro_w_scale_inv);
+    } else {   // every mode by default: this stage forms the energies and seeds the reverse pass (bf16x3 products here moved the Cu-32 virial from
+               // 4.5e-5 to 1.2e-4 of its fp64 value; f16x3 products put a six-atom structure's ill-conditioned energy 5.3e-5 off instead of 9e-6)
+      launch(k_readout_mfma<kPrecF32>, (unsigned)wgs, plan->d_readout_img, 1.f);
+    }
   }
   // (p.energy_deferred: formed by the step's last launch, k_struct_stress)
   if (!p.readout_sums && !p.energy_deferred) launch_energy_sums(c, t, scaled_atomic, scaled_total, total, s);

@@ -505,7 +505,7 @@ extern "C" int m3g_ph_displace(const m3g_ph_sizes* sizes, const void* state, siz
   if (!ph_sizes_ok(sizes) || !state || !pos) { set_error("m3g_ph_displace: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (state_bytes < ph_layout(*sizes).total) { set_error("m3g_ph_displace: state buffer too small"); return M3G_ERR_SIZE; }
   const PhView st = ph_view(*sizes, state);
-  hipLaunchKernelGGL(k_ph_displace, blocks_for(st.rows, 256), dim3(256), 0, (hipStream_t)stream_, st, pos);
+  hipLaunchKernelGGL(k_ph_displace, grid_for(st.rows, 256), dim3(256), 0, (hipStream_t)stream_, st, pos);
   M3G_RETURN_LAUNCH_STATUS();
 }
 

@@ -285,7 +285,7 @@ extern "C" int m3g_fire_init(const m3g_fire_params* p, int64_t n_atoms, int64_t 
   hipStream_t s = (hipStream_t)stream_;
   if (int rc = table.upload(L.chunks, (char*)state, host_offsets, s)) return rc;
   const int64_t work = 3 * N > S ? 3 * N : S;
-  hipLaunchKernelGGL(k_fire_init, blocks_for(work, kChunkRows), dim3(kChunkRows), 0, s, fire_view(N, S, state), pos, lattice, p->dt, p->astart);
+  hipLaunchKernelGGL(k_fire_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, fire_view(N, S, state), pos, lattice, p->dt, p->astart);
   M3G_HIP_CHECK(hipGetLastError());
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;

@@ -15,8 +15,6 @@
 
 namespace m3g {
 
-static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
 size_t topo_sort_tmp_bytes(int64_t E, int64_t T) {
   size_t m = (size_t)std::max<int64_t>(std::max<int64_t>(E, T), 1);
   // scratch of the radix sorts (general lists only) and of the active-edge scan (m3g_prims.h); + E + 1: the certificate's per-row

@@ -386,7 +386,7 @@ extern "C" int m3g_traj_sample(const m3g_traj_sizes* sizes, const m3g_traj_param
     if (params->remove_com) hipLaunchKernelGGL(k_traj_com, grid, dim3(kChunkRows), 0, s, st, pos, vel, forces, kick);
     hipLaunchKernelGGL(k_traj_store, grid, dim3(kChunkRows), 0, s, st, params->remove_com, pos, vel, forces, kick);
     hipLaunchKernelGGL(k_traj_partials, dim3(grid.x, (unsigned)((sizes->n_lags + kLagBlock - 1) / kLagBlock)), dim3(kChunkRows), 0, s, st);
-    hipLaunchKernelGGL(k_traj_finalize, blocks_for(S * sizes->n_lags * sizes->max_species, kChunkRows), dim3(kChunkRows), 0, s, st,
+    hipLaunchKernelGGL(k_traj_finalize, grid_for(S * sizes->n_lags * sizes->max_species, kChunkRows), dim3(kChunkRows), 0, s, st,
                        rdf ? 0 : 1);
   }
   M3G_RETURN_LAUNCH_STATUS();
