@@ -1,6 +1,7 @@
 """Shared test plumbing: fixtures -> oracle inputs and -> engine (torch_m3gnet) inputs."""
 from __future__ import annotations
 
+from collections import Counter
 from pathlib import Path
 
 import numpy as np
@@ -79,6 +80,59 @@ def rel_err(a: torch.Tensor, b: torch.Tensor) -> float:
     """max|a-b| / max|b| (the metric SURVEY.md §8(d) prescribes for forces)."""
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-300))
+
+
+# ---- the persistent (large-system) kernel selection, forced on inputs the default selection sends down the small-system path
+# (resolve_step_path, csrc/m3g_step_path.h).  Order matters: setting small_tiles also moves small_tiles_fwd (option table of
+# csrc/m3g_api.hip), so both edge kernels become the persistent ones; split_node_tiles = 0 selects k_node_pre_mfma<fp32> and
+# k_readout_mfma<fp32>; split_tail = 0 keeps every tile in the whole-tile body of k_edge_rev_f32.
+PERSISTENT = dict(small_tiles=0, split_node_tiles=0, split_tail=0)
+PERSISTENT_TAIL = dict(PERSISTENT, split_tail=1)
+
+
+def persistent_tile_counts(n_edges: int) -> Counter:
+    """How many workgroups of a persistent edge kernel get how many 16-edge tiles: {tiles per workgroup: workgroups}.  A restatement
+    of tiles_for, grid_for_tiles and the TileQueue constructor of csrc/m3g_edge_common.h (tests/test_step_path_cpu.py pins it to a table
+    computed from that code)."""
+    tiles = (n_edges + 15) // 16                       # tiles_for
+    grid = min(max((tiles + 7) // 8 * 8, 8), 256)      # grid_for_tiles
+    per_xcd, wgs = (tiles + 7) // 8, grid >> 3         # TileQueue: an eighth of the tiles per blockIdx % 8, equal chunks inside it
+    chunk = (per_xcd + wgs - 1) // wgs
+    counts = Counter()
+    for block in range(grid):
+        xcd, q = block & 7, block >> 3
+        lo = xcd * per_xcd + q * chunk
+        hi = min(lo + chunk, (xcd + 1) * per_xcd, tiles)
+        counts[max(hi - lo, 0)] += 1
+    return counts
+
+
+def wave_takes_a_second_tile(counts: Counter) -> bool:
+    """k_edge_rev_f32 runs 8 waves per workgroup: a wave comes round its loop again once a workgroup has more than 8 tiles."""
+    return max(counts) > 8
+
+
+def split_tail_runs(counts: Counter, split_tail: int = 1) -> bool:
+    """Some workgroup's left-over tiles (count mod 4 in 1..split_tail) leave the queue for rev_split_run."""
+    return any(1 <= count % 4 <= split_tail for count, workgroups in counts.items() if workgroups > 0)
+
+
+def set_options(model, **options):
+    for name, value in options.items():
+        model.engine.set_option(name, value)
+    return model
+
+
+def record_line(name: str, line: str) -> None:
+    """Measured margins kept with the run: printed, and appended to the file `name` in the directory that the environment variable
+    M3G_MARGINS_DIR names, where it is set and exists (profiles/persistent_path_margins.txt is such a file)."""
+    import os
+
+    print(line)
+    out_dir = os.environ.get("M3G_MARGINS_DIR", "")
+    if out_dir and os.path.isdir(out_dir):
+        with open(os.path.join(out_dir, name), "a") as fh:
+            fh.write(line + "\n")
 
 
 # workload builders live in the package (bench.py uses them without importing this module, which imports the oracle)

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import random_cell_graph, rel_err
+from helpers import PERSISTENT, random_cell_graph, record_line, rel_err, set_options
 from oracle import m3gnet_oracle as orc
 from test_gpu_properties import _oracle_inputs
 
@@ -12,9 +12,18 @@ pytestmark = pytest.mark.gpu
 
 
 # cases 0-11 run on the MFMA kernels, whose arithmetic mode matters: the default exact-fp32 mode and the opt-in f16x3 mode are both
-# swept; 12-19 take the any-size path, which is plain fp32 whatever the option says
-@pytest.mark.parametrize("case,precision", [(c, "fp32") for c in range(20)] + [(c, "f16x3") for c in range(12)])
-def test_random_model_shape_and_batch_vs_oracle(case, precision):
+# swept; 12-19 take the any-size path, which is plain fp32 whatever the option says.  Batches this small take the small-system path on
+# the default selection, so cases 0-11 run once more in fp32 on the persistent kernels (helpers.PERSISTENT), and in the bf16x3 mode at
+# that mode's gates (tests/test_gpu_parity.py, test_saturated_activations_stress_case: E 1e-3, F 5e-4, stresses 2e-3)
+_GATES = {"fp32": (1e-5, 1e-4, 1e-4), "f16x3": (1e-5, 1e-4, 1e-4), "bf16x3": (1e-3, 5e-4, 2e-3)}
+
+
+@pytest.mark.parametrize("case,precision,options",
+                         [pytest.param(c, "fp32", {}, id=f"{c}-fp32") for c in range(20)] +
+                         [pytest.param(c, "f16x3", {}, id=f"{c}-f16x3") for c in range(12)] +
+                         [pytest.param(c, "fp32", PERSISTENT, id=f"{c}-fp32-persistent") for c in range(12)] +
+                         [pytest.param(c, "bf16x3", {}, id=f"{c}-bf16x3") for c in range(12)])
+def test_random_model_shape_and_batch_vs_oracle(case, precision, options):
     """cases 0-11: shapes of the fast (MFMA) kernels; 12-19: any shape the reference accepts (widths up to 160, l_max up to 9,
     n_max up to 10, up to 10 blocks) -- the any-size path.  Energies at the strict 1e-5, forces / stresses at 1e-4."""
     from torch_m3gnet.data import MaterialGraphKey as K
@@ -43,12 +52,18 @@ def test_random_model_shape_and_batch_vs_oracle(case, precision):
         n = int(rng.integers(1, max(2, min(40, int(box**3 / 14.0)))))   # keeps the random packing feasible
         graphs.append(random_cell_graph(n, box, seed=1000 * case + s, cutoff=cutoff, tb_cutoff=tb, dmin=1.4))
     model.engine.set_precision(precision)
+    set_options(model, **options)
     g = model(Batch.from_data_list(graphs).to("cuda"))
     p, cfg, c, og = _oracle_inputs(model, g)
     o = orc.energy_forces(p, cfg, c, og, legendre_backward="exact")
     e_err = float(((g[K.TOTAL_ENERGY].cpu() - o["total_energy"]).abs() / o["total_energy"].abs().clamp_min(1e-6)).max())
-    assert e_err < 1e-5
+    e_tol, f_tol, s_tol = _GATES[precision]
     fmax = float(o["forces"].abs().max())
-    assert float((g[K.FORCES].cpu() - o["forces"]).abs().max()) < 1e-4 * fmax + 1e-9
-    if float(o["stresses"].abs().max()) > 0:
-        assert rel_err(g[K.STRESSES], o["stresses"]) < 1e-4
+    f_abs = float((g[K.FORCES].cpu() - o["forces"]).abs().max())
+    s_err = rel_err(g[K.STRESSES], o["stresses"]) if float(o["stresses"].abs().max()) > 0 else 0.0
+    if options or precision == "bf16x3":
+        record_line("persistent_path_margins.txt", f"fuzz case {case} (l_max {l_max} n_max {n_max}, {len(graphs)} cells) {precision}"
+                    f"{' persistent' if options else ''}: E {e_err:.2e}  F {f_abs / max(fmax, 1e-300):.2e}  stress {s_err:.2e}")
+    assert e_err < e_tol
+    assert f_abs < f_tol * fmax + 1e-9
+    assert s_err < s_tol

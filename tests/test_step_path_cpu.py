@@ -86,3 +86,27 @@ def test_resolved_step_path_of_every_threshold_and_option(tmp_path):
         want = dict(BASE, **change)
         diff = {k: (got[name][k], want[k]) for k in want if got[name][k] != want[k]}
         assert not diff and got[name].keys() == want.keys(), f"{name}: (resolved, expected) {diff}"
+
+
+# tiles -> {tiles per workgroup: workgroups}, worked out from tiles_for, grid_for_tiles and the TileQueue constructor of
+# csrc/m3g_edge_common.h: 84 (32-atom cell: one tile per workgroup, 88 launched), 284 (108 atoms: two each on 142 of 256 workgroups),
+# 672 (256 atoms), 2,268 (864 atoms: 9 each, the last workgroup of an XCD's eighth 5, of the last eighth 1), 5,376 (2,048 atoms)
+TILE_COUNTS = {84: {1: 84, 0: 4}, 284: {2: 142, 0: 114}, 672: {3: 224, 0: 32}, 2268: {9: 248, 5: 7, 1: 1}, 5376: {21: 256}}
+
+
+def test_restated_tile_queue_gives_the_kernels_share_per_workgroup():
+    """helpers.persistent_tile_counts is what the GPU tests use to assert the regime their input puts k_edge_rev_f32 in (a wave's
+    second tile, the split tail): pinned here to the table above, and to the invariants of the queue for every size up to 6,000 tiles."""
+    from helpers import persistent_tile_counts, split_tail_runs, wave_takes_a_second_tile
+
+    for tiles, want in TILE_COUNTS.items():
+        for n_edges in (16 * tiles - 15, 16 * tiles):   # a part-filled last tile is a tile
+            assert dict(persistent_tile_counts(n_edges)) == want, (tiles, n_edges)
+    for tiles in list(range(0, 600)) + list(range(600, 6000, 37)):
+        counts = persistent_tile_counts(16 * tiles)
+        assert sum(c * n for c, n in counts.items()) == tiles            # every tile handed out once
+        assert sum(counts.values()) == min(max((tiles + 7) // 8 * 8, 8), 256)
+    assert not wave_takes_a_second_tile(persistent_tile_counts(16 * 672)) and wave_takes_a_second_tile(persistent_tile_counts(16 * 2268))
+    assert not split_tail_runs(persistent_tile_counts(16 * 284), 1) and split_tail_runs(persistent_tile_counts(16 * 284), 2)
+    assert split_tail_runs(persistent_tile_counts(16 * 84), 1) and split_tail_runs(persistent_tile_counts(16 * 2268), 1)
+    assert not split_tail_runs(persistent_tile_counts(16 * 672), 2)
