@@ -468,6 +468,46 @@ int m3g_fire_step(const m3g_fire_params* params, int64_t n_atoms, int64_t n_stru
 int m3g_fire_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes, int32_t* host_flags, int32_t* host_steps,
                   double* host_dt, double* host_a, int32_t* host_n, double* host_x, double* host_v, void* stream);
 
+/* ---- batched structure relaxation: L-BFGS beside FIRE, fixed or variable cell (csrc/m3g_lbfgs.hip) ------------------------------
+ * ASE's LBFGS without line search, applied to every structure of a batch on its own, over the generalized coordinates X and forces g
+ * of the FIRE calls above (the same cell filter, the same verdicts, the same freezing; grad = -g).  Per call and structure: the
+ * verdicts; then, once the structure has stepped, the pair s = X - X_prev, y = grad - grad_prev joins its history with rho = 1 / y.s
+ * (only the newest `memory` pairs are kept; a pair whose y.s is zero or not finite is NOT stored, where ASE would divide by zero --
+ * two equal fp32 force arrays give y = 0; a negative y.s is kept, as in ASE); the two-loop recursion with H0 = 1 / alpha gives the
+ * direction p; longest = max over rows |p_row| (cell rows included), p *= maxstep / longest when longest >= maxstep, dr = damping p;
+ * a non-finite dr flags the structure M3G_LBFGS_ERROR and does not move it; else X_prev = X, grad_prev = grad, X += dr.
+ * The state buffer is caller-owned device memory; with C = ceil(N / 256) + S, R = N + 3 S, M = memory + 1 it holds, each region rounded
+ * up to 256 bytes: the chunk table (8 (S+1) + 4 C + 8 C + 4 (S+1)), partial sums 8 * 5 * C * (M + 1) + 8 C, the vectors X, X_prev, grad,
+ * grad_prev, p (8 * 3R each), the rings of s and y (8 * 3R * M each: the dominant term, memory * 2 * 3(N+3S) * 8), L0 and F (8 * 9 * S
+ * each), per structure two Gram blocks s_i.y_j, y_i.y_j (8 * M * M each) and five coefficient vectors (8 * M each), four int32 words and
+ * 16 doubles. */
+typedef struct {
+  double maxstep, damping, alpha;   /* ASE defaults: 0.2, 1.0, 70.0 (H0 = 1 / alpha); all > 0 */
+  double fmax;                      /* > 0 */
+  int32_t memory;                   /* 100; 1 <= memory <= M3G_LBFGS_MAX_MEMORY */
+  int32_t relax_cell;               /* 0 positions only, 1 positions and cell */
+} m3g_lbfgs_params;
+#define M3G_LBFGS_STARTED 1     /* the structure has taken a step (X_prev and grad_prev are set); the bits of M3G_FIRE_* */
+#define M3G_LBFGS_CONVERGED 2   /* frozen: max_i |g_i| < fmax was seen */
+#define M3G_LBFGS_ERROR 4       /* frozen: its generalized forces or its step held a non-finite value */
+#define M3G_LBFGS_MAX_MEMORY 2047
+int m3g_lbfgs_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t memory, size_t* bytes);
+/* Arguments as the FIRE init call.  Invalid parameters (memory < 1, a non-finite or non-positive maxstep, damping, alpha or fmax,
+ * relax_cell not 0 or 1), bad offsets or a cell relaxation without lattice -> M3G_ERR_VALUE before any HIP call; a short state buffer
+ * -> M3G_ERR_SIZE.  Waits for the stream. */
+int m3g_lbfgs_init(const m3g_lbfgs_params* params, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* pos,
+                   const double* lattice, void* state, size_t state_bytes, void* stream);
+/* One L-BFGS iteration of the batch; arguments, units, check_only and `unconverged` as the FIRE step call.  FIVE launches whatever the
+ * memory, the history depth reached and the batch (three with check_only), no atomics, no allocation and no wait: capture-safe.  params:
+ * those of the init call. */
+int m3g_lbfgs_step(const m3g_lbfgs_params* params, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
+                   const float* stresses, double* pos, double* lattice, float* lattice32, int32_t check_only, int32_t* unconverged, void* stream);
+/* Per-structure flags (M3G_LBFGS_*), step counts, history depths (pairs stored, <= memory) [S] and the generalized coordinates
+ * [N + 3S, 3] (the N atom rows, then three cell rows per structure) to HOST memory; every output may be NULL.  `memory`: that of the
+ * init call.  Waits for the stream. */
+int m3g_lbfgs_read(int64_t n_atoms, int64_t n_structs, int32_t memory, const void* state, size_t state_bytes, int32_t* host_flags,
+                   int32_t* host_steps, int32_t* host_pairs, double* host_x, void* stream);
+
 /* ---- batched molecular dynamics: NVE, NVT (Berendsen, Langevin BAOAB), NPT Berendsen (csrc/m3g_dynamics.hip) -------------------
  * Replaces the m3gnet package's MolecularDynamics (m3gnet.models.MolecularDynamics, the interface the reference stands in for: ASE's
  * VelocityVerlet "nve", NVTBerendsen "nvt" and NPTBerendsen "npt_berendsen" on one structure, on the host) for a whole batch, each
@@ -846,7 +886,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     additive, same version: m3g_eigh_batched (batched Hermitian Jacobi eigensolver), m3g_ph_dynmat_gradient,
                              *     m3g_ph_group_velocities (phonon eigenvectors and group velocities);
                              *     additive, same version: m3g_traj_state_bytes / _init / _sample / _read / _frame (trajectory observables) and
-                             *     m3g_dyn_state_view -- new exports only: no existing struct, constant or call changes, so a caller built
+                             *     m3g_dyn_state_view;
+                             *     additive, same version: m3g_lbfgs_state_bytes / _init / _step / _read (batched L-BFGS relaxation beside
+                             *     FIRE) -- new exports only: no existing struct, constant or call changes, so a caller built
                              *     against 11 runs unchanged */
 
 #ifdef __cplusplus

@@ -68,6 +68,15 @@ class M3GFireParams(C.Structure):   # m3g_fire_params
 FIRE_STARTED, FIRE_CONVERGED, FIRE_ERROR = 1, 2, 4   # M3G_FIRE_* flag bits
 
 
+class M3GLbfgsParams(C.Structure):   # m3g_lbfgs_params
+    _fields_ = [("maxstep", C.c_double), ("damping", C.c_double), ("alpha", C.c_double), ("fmax", C.c_double), ("memory", C.c_int32),
+                ("relax_cell", C.c_int32)]
+
+
+LBFGS_STARTED, LBFGS_CONVERGED, LBFGS_ERROR = FIRE_STARTED, FIRE_CONVERGED, FIRE_ERROR   # M3G_LBFGS_*: the bits of M3G_FIRE_*
+LBFGS_MAX_MEMORY = 2047   # M3G_LBFGS_MAX_MEMORY
+
+
 class M3GDynParams(C.Structure):   # m3g_dyn_params
     _fields_ = [("ensemble", C.c_int32), ("fix_com", C.c_int32), ("dt", C.c_double), ("taut", C.c_double), ("friction", C.c_double),
                 ("pressure", C.c_double), ("taup", C.c_double), ("compressibility", C.c_double)]
@@ -194,6 +203,13 @@ SYMBOLS = {
                                 C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "m3g_fire_read": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_lbfgs_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "m3g_lbfgs_init": (C.c_int, [C.POINTER(M3GLbfgsParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
+    "m3g_lbfgs_step": (C.c_int, [C.POINTER(M3GLbfgsParams), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "m3g_lbfgs_read": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
     "m3g_dyn_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     "m3g_dyn_init": (C.c_int, [C.POINTER(M3GDynParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_size_t, C.c_void_p]),
