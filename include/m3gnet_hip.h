@@ -573,6 +573,47 @@ int m3g_dyn_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t s
  * half-step velocities of the step under way; after a finish_only call the full-step ones. */
 int m3g_dyn_state_view(int64_t n_atoms, int64_t n_structs, size_t* mass_offset, size_t* velocity_offset);
 
+/* ---- batched replica-exchange MD (parallel tempering) over an m3g_dyn_* batch (csrc/m3g_remd.hip) -----------------------------------
+ * The S structures of an NVT_LANGEVIN batch are cut into G ladders by ladder_offsets [G+1] (0 = o_0 < ... < o_G = S): ladder g is the
+ * contiguous run of R_g = o_{g+1} - o_g >= 2 replicas of one system, with strictly ascending temperatures T_g[0..R_g) > 0 and one
+ * 64-bit seed; replica o_g + k starts holding temperature index k (the caller gives m3g_dyn_init the same temperatures).  An exchange
+ * swaps TEMPERATURES, not configurations: positions never move between rows, so neighbour lists stay valid.
+ * One m3g_remd_exchange is attempt a = 0, 1, ... of every ladder (the count lives on the device), at the energies E [S]:
+ *   1. E of every replica without M3G_DYN_ERROR whose E is finite joins count / mean / M2 (Welford, fp64) of the index it holds,
+ *      before any swap;
+ *   2. the pairs (k, k+1) with k % 2 == a % 2: i holds k, j holds k+1, Delta = (1/(k_B T_k) - 1/(k_B T_{k+1})) (E_i - E_j) in fp64 (k_B
+ *      of m3g_dyn_*); accepted iff Delta >= 0 or u < exp(Delta), u = ((w_0 >> 11) + 0.5) 2^-53 of Philox4x64-10 with counter (a, k, 0, 0)
+ *      and key (ladder seed, 1) -- the Langevin draws use key word 0;
+ *   3. a pair with M3G_DYN_ERROR or M3G_DYN_STARTED on either replica, or a non-finite energy, is NOT attempted: not counted, nothing
+ *      of it written.  STARTED means half-step velocities: make the call after a finish_only m3g_dyn_step;
+ *   4. on accept the held indices and the holder map are swapped, the new targets are written into the dyn state's target
+ *      temperatures (read by the next m3g_dyn_step), and the velocities are scaled by sqrt(T_new / T_old); every other replica's
+ *      velocities stay bitwise untouched;
+ *   5. round trips: a replica that reaches index R-1 after last touching index 0, and then reaches 0 again, has completed one;
+ *   6. row a of `history` (the held index of every replica) is written if a < history_rows; the attempt counter becomes a + 1.
+ * No atomics: a ladder's results depend on its own replicas only, bitwise the same alone or beside any other ladders.
+ * Per-(ladder, index) and per-pair arrays are [S]: row o_g + k is index k (pair (k, k+1)) of ladder g; the row o_g + R_g - 1 of a pair
+ * array is unused. */
+int m3g_remd_state_bytes(int64_t n_structs, int64_t n_ladders, size_t* bytes);
+/* host_ladder_offsets [G+1] int64, host_temperatures [S] (K; replica order, ladder after ladder), host_seeds [G]: HOST.  Null pointers,
+ * offsets that do not run from 0 to S or do not increase strictly, a ladder of fewer than 2 replicas, a temperature that is not
+ * finite, <= 0 or not strictly ascending within its ladder -> M3G_ERR_VALUE, a short buffer -> M3G_ERR_SIZE, before any HIP call.
+ * Waits for the stream. */
+int m3g_remd_init(int64_t n_structs, int64_t n_ladders, const int64_t* host_ladder_offsets, const double* host_temperatures,
+                  const uint64_t* host_seeds, void* state, size_t state_bytes, void* stream);
+/* remd_state: of m3g_remd_init; dyn_state: of m3g_dyn_init over the same S structures (N atoms); energies [S] f32 DEVICE; history
+ * [history_rows, S] int32 DEVICE or NULL.  TWO launches whatever S and G, no atomics, no allocation, copy or wait: capture-safe. */
+int m3g_remd_exchange(int64_t n_atoms, int64_t n_structs, int64_t n_ladders, void* remd_state, size_t remd_bytes, void* dyn_state,
+                      size_t dyn_bytes, const float* energies, int32_t* history, int64_t history_rows, void* stream);
+/* To HOST memory, every output may be NULL: held index of every replica and the replica holding every index (int32 [S], replica
+ * numbers of the batch), attempts / accepts of every pair (int64 [S]), count (int64), mean and M2 (fp64) of the energy at every index
+ * [S], round trips of every replica (int64 [S]) and the attempt counters (int64 [G]).  Waits for the stream. */
+int m3g_remd_read(int64_t n_structs, int64_t n_ladders, const void* state, size_t state_bytes, int32_t* host_held, int32_t* host_holder,
+                  int64_t* host_attempts, int64_t* host_accepts, int64_t* host_count, double* host_mean, double* host_m2,
+                  int64_t* host_round_trips, int64_t* host_counters, void* stream);
+/* Byte offset, inside an m3g_dyn_* state buffer of these sizes, of the target temperatures [S] (fp64) the exchange writes. */
+int m3g_remd_target_view(int64_t n_atoms, int64_t n_structs, size_t* temperature_offset);
+
 /* ---- trajectory observables: RDF, MSD and VACF accumulated on the device (csrc/m3g_trajectory.hip) ---------------------------------
  * Fed one frame per m3g_traj_sample (from the MD loop, or any frames): per structure and species pair (a <= b) the INTEGER histogram
  * of minimum-image pair distances below r_max in rdf_bins bins (unordered pairs i < j; bin = (int)(r rdf_bins / r_max) taken only
@@ -889,7 +930,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     m3g_dyn_state_view;
                              *     additive, same version: m3g_lbfgs_state_bytes / _init / _step / _read (batched L-BFGS relaxation beside
                              *     FIRE) -- new exports only: no existing struct, constant or call changes, so a caller built
-                             *     against 11 runs unchanged */
+                             *     against 11 runs unchanged;
+                             *     additive, same version: m3g_remd_state_bytes / _init / _exchange / _read / _target_view (batched
+                             *     replica-exchange MD over an m3g_dyn_* batch) */
 
 #ifdef __cplusplus
 }

@@ -217,6 +217,13 @@ SYMBOLS = {
                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "m3g_dyn_read": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_dyn_state_view": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "m3g_remd_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "m3g_remd_init": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "m3g_remd_exchange": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                    C.c_int64, C.c_void_p]),
+    "m3g_remd_read": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_remd_target_view": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     "m3g_traj_state_bytes": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(C.c_size_t)]),
     "m3g_traj_init": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(M3GTrajParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p]),
