@@ -364,6 +364,10 @@ int m3g_verlet_fill(int64_t n_atoms, int64_t n_candidates, int64_t n_edges, void
  * M3G_ERR_UNSUPPORTED -- use the two calls above, which have no limits and return identical lists.  No wait.
  * Replaces, for a trajectory, the per-structure rebuild of data/material_graph.py:168-254. */
 #define M3G_VERLET_FILL_LISTS_MAX_ROW 1024
+/* m3g_verlet_update(_async) runs its whole pass in ONE launch up to this many atoms and in three launches (wrap, rows, totals) above
+ * it; both classify every pair through the same device functions and return the same verdict.  Not a limit of any call: it names
+ * the regime, so that a test can place itself on either side. */
+#define M3G_VERLET_ONE_LAUNCH_MAX_ATOMS 512
 int m3g_verlet_fill_lists(int64_t n_atoms, int64_t n_candidates, int64_t n_edges, int64_t n_triplets, int64_t max_cand_row, void* scratch,
                           const int64_t* cand_edge_index, const int32_t* cand_shift, const int32_t* cand_row_ptr,
                           int64_t* edge_index /* [2,E] */, int32_t* edge_cell_shift /* [E,3] */, uint8_t* cand_state /* [Ec] out */,

@@ -279,6 +279,55 @@ def test_two_launch_refill_writes_the_lists_of_the_general_calls():
     assert a.stats["refill"] >= 12 and b.stats["refill"] >= 12
 
 
+def test_one_launch_and_three_launch_skin_updates_agree_at_the_threshold():
+    """The skin update is one launch up to M3G_VERLET_ONE_LAUNCH_MAX_ATOMS atoms and three launches above.  Object A holds exactly
+    that many atoms (seven 64-atom cells, a 30- and a 28-atom cell and a 6-atom cell smaller than the cutoff: self-images, long
+    candidate rows); object B holds the same cells followed by one more 6-atom cell, which puts it on the three-launch side.  Both
+    walk the same trajectory (thermal moves, near-zero moves, a lattice-vector jump).  At every step each object's lists are the
+    fresh build's; B's lists restricted to A's atoms are A's (the extra cell is last, so edge and triplet ids agree); and on the
+    steps where only A's atoms moved both take the same path and report the same "changed" word."""
+    from torch_m3gnet import _lib
+    from torch_m3gnet.data.graph_gpu import batch_from_arrays
+    from torch_m3gnet.data.md import VerletGraph
+
+    K = _K()
+    limit = _lib.VERLET_ONE_LAUNCH_MAX_ATOMS
+    cells = [random_cell_arrays(64, 9.0, 40 + k) for k in range(7)]
+    cells += [random_cell_arrays(30, 7.0, 51), random_cell_arrays(28, 7.0, 52), random_cell_arrays(6, 4.2, 53, dmin=1.8)]
+    extra = random_cell_arrays(6, 4.2, 54, dmin=1.8)
+    lats, pos0, zs = zip(*cells)
+    lats_b, zs_b = lats + (extra[0],), zs + (extra[2],)
+    sizes = [len(p) for p in pos0]
+    a = VerletGraph(lats, zs, 5.0, 4.0, skin=0.4, device=DEV)
+    b = VerletGraph(lats_b, zs_b, 5.0, 4.0, skin=0.4, device=DEV)
+    assert a.N == limit and b.N > limit, (a.N, b.N, limit)   # the regimes this test is about
+    rng = np.random.default_rng(17)
+    pos, pos_x = np.concatenate(pos0), extra[1].copy()
+    for step in range(10):
+        pos = pos + rng.normal(0.0, 1e-9 if step in (3, 7) else 0.015, pos.shape)   # steps 3 and 7: nothing to speak of -> reuse
+        if step == 5:
+            pos[3] += lats[0][1]                                                     # a wrapped coordinate -> search
+        only_a_moved = step not in (0, 2, 6)
+        if step in (2, 6):
+            pos_x = pos_x + rng.normal(0.0, 0.004, pos_x.shape)
+        pos_b = np.concatenate([pos, pos_x])
+        before = dict(a.stats), dict(b.stats)
+        ga, gb = a.update(torch.tensor(pos, device=DEV)), b.update(torch.tensor(pos_b, device=DEV))
+        _same_graph(ga, batch_from_arrays(lats, np.split(pos, np.cumsum(sizes)[:-1]), zs, 5.0, 4.0, device=DEV))
+        _same_graph(gb, batch_from_arrays(lats_b, np.split(pos_b, np.cumsum(sizes)), zs_b, 5.0, 4.0, device=DEV))
+        n_e, n_t = int(ga[K.NUM_EDGES]), int(ga[K.NUM_TRIPLETS])
+        assert torch.equal(gb[K.EDGE_INDEX][:, :n_e], ga[K.EDGE_INDEX]) and bool((gb[K.EDGE_INDEX][0, n_e:] >= a.N).all()), step
+        assert torch.equal(gb[K.EDGE_CELL_SHIFT][:n_e], ga[K.EDGE_CELL_SHIFT]), step
+        assert torch.equal(gb[K.NUM_TRIPLET_I][:a.N], ga[K.NUM_TRIPLET_I]) and torch.equal(gb[K.NUM_TRIPLET_IJ][:n_e], ga[K.NUM_TRIPLET_IJ]), step
+        assert torch.equal(gb[K.TRIPLET_EDGE_INDEX][:, :n_t], ga[K.TRIPLET_EDGE_INDEX]) and bool((gb[K.TRIPLET_EDGE_INDEX][:, n_t:] >= n_e).all()), step
+        if only_a_moved:
+            path_a = {k: a.stats[k] - before[0][k] for k in a.stats}
+            path_b = {k: b.stats[k] - before[1][k] for k in b.stats}
+            assert path_a == path_b and bool(a._verdict_i64[1]) == bool(b._verdict_i64[1]), (step, path_a, path_b)
+    for vg in (a, b):
+        assert vg.stats["reuse"] >= 1 and vg.stats["refill"] >= 3 and vg.stats["search"] >= 2, vg.stats
+
+
 def test_canonical_topology_build_equals_the_checked_build():
     """A graph marked as written by the library's own builders takes m3g_topology_build_canonical (no mirror / completeness checks);
     the same tensors without the mark take the checked build: same certificate word, bit-identical results.  An in-place change of

@@ -141,9 +141,8 @@ static void pack_mlp(std::vector<float>& blob, const MlpW& m, const m3g_plan& p,
 
 Work work_carve(int B, const StepPath& path, int64_t N, int64_t E, int64_t S, void* base) {
   Work w{};
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t n_floats) { float* r = p ? (float*)(p + off) : nullptr; off += align_up(n_floats * sizeof(float)); return r; };
+  Carve c{(char*)base};
+  auto take = [&](size_t n_floats) { return (float*)c.take(n_floats * sizeof(float)); };
   size_t e = (size_t)E, n = (size_t)N;
   w.u = take(e * 3); w.d = take(e); w.h = take(e * kRP); w.hp = take(e * kRP);
   w.q = take(e * kCP); w.qp = take(e * kCP); w.fc3 = take(e); w.fc3p = take(e);
@@ -173,11 +172,10 @@ Work work_carve(int B, const StepPath& path, int64_t N, int64_t E, int64_t S, vo
     for (int b = 0; b < B; ++b) w.act[b] = take(e * 8 * kDP);
   }
   // tail scratch for optional outputs the caller did not ask for ([N] per-atom energies, [2 S] sums), then the step's sync words
-  w.tail = p ? (float*)(p + off) : nullptr;
-  w.sync = p ? (int32_t*)(p + off + (n + (size_t)S * 2) * sizeof(float)) : nullptr;
   static_assert(kSyncWords <= 64, "the tail scratch reserves 64 words");
-  off += align_up((n + (size_t)S * 2 + 64) * sizeof(float));
-  w.total_bytes = off;
+  w.tail = take(n + (size_t)S * 2 + 64);
+  w.sync = w.tail ? (int32_t*)(w.tail + n + (size_t)S * 2) : nullptr;
+  w.total_bytes = c.off;
   return w;
 }
 

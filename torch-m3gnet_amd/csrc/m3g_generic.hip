@@ -443,9 +443,8 @@ struct GenWork {
 
 static GenWork gen_carve(int D, int C, int R, int B, int64_t N, int64_t E, int64_t S, void* base) {
   GenWork w{};
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t n) { float* r = p ? (float*)(p + off) : nullptr; off += (n * sizeof(float) + 255) / 256 * 256; return r; };
+  Carve c{(char*)base};
+  auto take = [&](size_t n) { return (float*)c.take(n * sizeof(float)); };
   const size_t e = (size_t)E, n = (size_t)N;
   w.u = take(e * 3); w.d = take(e); w.h = take(e * R); w.hp = take(e * R); w.fc3 = take(e); w.fc3p = take(e); w.q = take(e * C); w.qp = take(e * C);
   for (int b = 0; b <= B; ++b) { w.x[b] = take(n * D); w.e[b] = take(e * D); }
@@ -462,8 +461,8 @@ static GenWork gen_carve(int D, int C, int R, int B, int64_t N, int64_t E, int64
   w.dm = take(e * C); w.dgq = take(e * C);
   for (int m = 0; m < 2; ++m) { w.dp1d[m] = take(e * D); w.dp1g[m] = take(e * D); }
   w.dTA = take(n * 4 * D); w.dTB = take(n * 4 * D); w.dv = take(n * C);
-  off += ((n + (size_t)S * 2 + 64) * sizeof(float) + 255) / 256 * 256;   // tail scratch for optional outputs
-  w.total = off;
+  take(n + (size_t)S * 2 + 64);   // tail scratch for optional outputs
+  w.total = c.off;
   return w;
 }
 

@@ -21,6 +21,7 @@
 
 #include "m3g_internal.h"
 #include "m3g_prims.h"
+#include "m3g_struct_sum.h"
 
 namespace m3g {
 
@@ -99,27 +100,25 @@ struct NbScratch {
 
 static NbScratch nb_carve(int64_t N, int64_t S, int64_t M, void* base) {
   NbScratch w{};
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p ? (void*)(p + off) : nullptr; off += align_up(bytes); return r; };
+  Carve c{(char*)base};
   w.max_bins = 2 * N + 8 * S;   // k_struct_info keeps every structure within 2 count + 8 bins
-  w.info = (StructInfo*)take(sizeof(StructInfo) * (size_t)(S + 1));
-  w.bin_off = (int64_t*)take(sizeof(int64_t) * (size_t)(S + 2));
-  w.pos_w = (double*)take(sizeof(double) * 3 * (size_t)(N + 1));
-  w.wrap = (int32_t*)take(sizeof(int32_t) * 3 * (size_t)(N + 1));
-  w.binc = (int32_t*)take(sizeof(int32_t) * 3 * (size_t)(N + 1));
-  w.bin_key = (int32_t*)take(sizeof(int32_t) * (size_t)(N + 1));
-  w.bin_rank = (int32_t*)take(sizeof(int32_t) * (size_t)(N + 1));
-  w.perm = (int32_t*)take(sizeof(int32_t) * (size_t)(N + 1));
-  w.bin_start = (int32_t*)take(sizeof(int32_t) * (size_t)(w.max_bins + 2));
-  w.pos_s = (double*)take(sizeof(double) * 3 * (size_t)(N + 1));
-  w.counts = (int64_t*)take(sizeof(int64_t) * (size_t)(N * M + 2));
-  w.tri = (int64_t*)take(sizeof(int64_t) * (size_t)(N + 2));
+  w.info = (StructInfo*)c.take(sizeof(StructInfo) * (size_t)(S + 1));
+  w.bin_off = (int64_t*)c.take(sizeof(int64_t) * (size_t)(S + 2));
+  w.pos_w = (double*)c.take(sizeof(double) * 3 * (size_t)(N + 1));
+  w.wrap = (int32_t*)c.take(sizeof(int32_t) * 3 * (size_t)(N + 1));
+  w.binc = (int32_t*)c.take(sizeof(int32_t) * 3 * (size_t)(N + 1));
+  w.bin_key = (int32_t*)c.take(sizeof(int32_t) * (size_t)(N + 1));
+  w.bin_rank = (int32_t*)c.take(sizeof(int32_t) * (size_t)(N + 1));
+  w.perm = (int32_t*)c.take(sizeof(int32_t) * (size_t)(N + 1));
+  w.bin_start = (int32_t*)c.take(sizeof(int32_t) * (size_t)(w.max_bins + 2));
+  w.pos_s = (double*)c.take(sizeof(double) * 3 * (size_t)(N + 1));
+  w.counts = (int64_t*)c.take(sizeof(int64_t) * (size_t)(N * M + 2));
+  w.tri = (int64_t*)c.take(sizeof(int64_t) * (size_t)(N + 2));
   // scratch of the three scans (counts per (atom, image); bins per structure; atoms per bin), m3g_prims.h
   w.tmp_bytes = std::max(std::max(prims::scan_tmp_bytes<int64_t>(N * M + 1), prims::scan_tmp_bytes<int64_t>(S + 1)),
                          prims::scan_tmp_bytes<int32_t>(w.max_bins + 2));
-  w.tmp = take(w.tmp_bytes);
-  w.total = off;
+  w.tmp = c.take(w.tmp_bytes);
+  w.total = c.off;
   return w;
 }
 
@@ -450,23 +449,84 @@ struct VerletScratch {
 };
 static VerletScratch verlet_carve(int64_t N, int64_t Ec, void* base) {
   VerletScratch w{};
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p ? (void*)(p + off) : nullptr; off += align_up(bytes); return r; };
-  w.pos_w = (double*)take(sizeof(double) * 3 * (size_t)(N + 1));
-  w.wrap = (int32_t*)take(sizeof(int32_t) * 3 * (size_t)(N + 1));
-  w.state = (uint8_t*)take((size_t)Ec + 16);
-  w.dist = (double*)take(sizeof(double) * (size_t)(Ec + 1));
-  w.row_keep = (int32_t*)take(sizeof(int32_t) * (size_t)(N + 2));
-  w.row_tri = (int64_t*)take(sizeof(int64_t) * (size_t)(N + 1));
+  Carve c{(char*)base};
+  w.pos_w = (double*)c.take(sizeof(double) * 3 * (size_t)(N + 1));
+  w.wrap = (int32_t*)c.take(sizeof(int32_t) * 3 * (size_t)(N + 1));
+  w.state = (uint8_t*)c.take((size_t)Ec + 16);
+  w.dist = (double*)c.take(sizeof(double) * (size_t)(Ec + 1));
+  w.row_keep = (int32_t*)c.take(sizeof(int32_t) * (size_t)(N + 2));
+  w.row_tri = (int64_t*)c.take(sizeof(int64_t) * (size_t)(N + 1));
   const size_t tmp = prims::scan_tmp_bytes<int32_t>(N + 1);
   w.scan_tmp_bytes = tmp;
-  w.scan_tmp = take(tmp);
-  w.acc = (unsigned long long*)take(sizeof(unsigned long long) * 8);   // [4]: workgroup counter of the one-launch update (small cells)
-  w.off_e = (int32_t*)take(sizeof(int32_t) * (size_t)(N + 2));
-  w.off_t = (int64_t*)take(sizeof(int64_t) * (size_t)(N + 2));
-  w.total = off;
+  w.scan_tmp = c.take(tmp);
+  w.acc = (unsigned long long*)c.take(sizeof(unsigned long long) * 8);   // [4]: workgroup counter of the one-launch update (small cells)
+  w.off_e = (int32_t*)c.take(sizeof(int32_t) * (size_t)(N + 2));
+  w.off_t = (int64_t*)c.take(sizeof(int64_t) * (size_t)(N + 2));
+  w.total = c.off;
   return w;
+}
+
+// ---- what the three-launch update and the one-launch update of a small cell share: a pair is classified, a row closed and the
+// totals formed by ONE body each, so the two paths agree by construction (tests/test_gpu_md.py walks both side by side) ----
+// squared displacement of an atom since the reference positions
+__device__ __forceinline__ double verlet_disp2(double x, double y, double z, const double* __restrict__ ref) {
+  const double dx = x - ref[0], dy = y - ref[1], dz = z - ref[2];
+  double m = dx * dx + dy * dy + dz * dz;
+  if (!(m >= 0.0)) m = 1e300;   // NaN positions: force the rebuild path (which reports them)
+  return m;
+}
+// candidate c of a centre at wrapped position pw_i, its neighbour at pw_j in image `sh` of the wrapped cell: membership byte and
+// distance at the current positions, compared with the membership the caller's lists were built with
+__device__ __forceinline__ void verlet_candidate(const double* lat, const int (&sh)[3], const double* pw_i, const double* pw_j, double c2,
+                                                 float tb_cutoff, int c, const uint8_t* __restrict__ old_state, uint8_t* state, double* dist,
+                                                 bool& in2, bool& in3, bool& changed) {
+  double ox, oy, oz;
+  image_offset(lat, sh, pw_i, ox, oy, oz);
+  const double d2 = pair_d2(pw_j, ox, oy, oz);
+  const double d = sqrt(d2);
+  in2 = pair_hit(d2, c2);
+  in3 = in2 && (float)d <= tb_cutoff;   // as the reference thresholds the narrowed lengths
+  const uint8_t st = (uint8_t)((in2 ? 1 : 0) | (in3 ? 2 : 0));
+  state[c] = st;
+  dist[c] = d;
+  changed = changed || (old_state && st != old_state[c]);
+}
+// the end of centre i's row: kept candidates, triplets, and the changed flag
+__device__ __forceinline__ void verlet_row_done(int64_t i, int lane, int n2, int n3, bool changed, int32_t* row_keep, int64_t* row_tri,
+                                                unsigned long long* acc) {
+  const bool any_changed = __any(changed);
+  if (lane == 0) {   // (no per-row atomics on shared totals: 10,000 waves on one address serialise -- verlet_totals adds the rows up)
+    row_keep[i] = n2;
+    row_tri[i] = (int64_t)n3 * (n3 > 0 ? n3 - 1 : 0);
+    // rare along a trajectory; right after a search EVERY row differs from the zeroed membership bytes, and 10,000 atomics on one
+    // address serialise (measured: 118 us) -- so look first, and only the first few waves write
+    if (any_changed && __atomic_load_n(acc + 1, __ATOMIC_RELAXED) == 0ull) atomicOr(acc + 1, 1ull);
+  }
+}
+// one workgroup of WAVES waves: E = sum of the rows' kept candidates, T = sum of their triplets (integers: any order gives the same
+// totals), acc[5] = the longest candidate row (the caller chooses the refill entry point by it without a read-back of its own)
+template <int WAVES>
+__device__ __forceinline__ void verlet_totals(int64_t N, const int32_t* __restrict__ row_keep, const int64_t* __restrict__ row_tri,
+                                              const int32_t* __restrict__ row_ptr, unsigned long long* acc) {
+  __shared__ unsigned long long se[WAVES], st[WAVES], sm[WAVES];
+  unsigned long long e = 0, t = 0, m = 0;
+  for (int64_t i = threadIdx.x; i < N; i += blockDim.x) {
+    e += (unsigned long long)row_keep[i]; t += (unsigned long long)row_tri[i];
+    const unsigned long long len = (unsigned long long)(row_ptr[i + 1] - row_ptr[i]);
+    m = len > m ? len : m;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    e += __shfl_xor(e, o); t += __shfl_xor(t, o);
+    const unsigned long long mo = __shfl_xor(m, o);
+    m = mo > m ? mo : m;
+  }
+  if ((threadIdx.x & 63) == 0) { se[threadIdx.x >> 6] = e; st[threadIdx.x >> 6] = t; sm[threadIdx.x >> 6] = m; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    e = 0; t = 0; m = 0;
+    for (int k = 0; k < WAVES; ++k) { e += se[k]; t += st[k]; m = sm[k] > m ? sm[k] : m; }
+    acc[2] = e; acc[3] = t; acc[5] = m;
+  }
 }
 
 // one thread per atom: wrapped position and wrap exactly as the search forms them; largest displacement since the reference
@@ -483,9 +543,7 @@ __global__ void k_verlet_prep(int64_t N, int64_t S, const double* __restrict__ p
     double f[3], w[3], pw[3];
     wrap_point(fr.lat, fr.inv, x, y, z, f, w, pw);
     for (int c = 0; c < 3; ++c) { pos_w[a * 3 + c] = pw[c]; wrap[a * 3 + c] = (int32_t)w[c]; }
-    const double dx = x - pos_ref[a * 3], dy = y - pos_ref[a * 3 + 1], dz = z - pos_ref[a * 3 + 2];
-    m = dx * dx + dy * dy + dz * dz;
-    if (!(m >= 0.0)) m = 1e300;   // NaN positions: force the rebuild path (which reports them)
+    m = verlet_disp2(x, y, z, pos_ref + a * 3);
   }
   // wave maximum first: one atomic per wave (non-negative doubles order like their bit patterns)
   for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
@@ -518,54 +576,65 @@ __global__ void __launch_bounds__(256) k_verlet_rows(int64_t N, int64_t S, int64
       // the image of the wrapped cell this edge belongs to: shift = image - wrap[j] + wrap[i]
       int sh[3];
       for (int p = 0; p < 3; ++p) sh[p] = cand_shift[(int64_t)c * 3 + p] + wrap[j * 3 + p] - wrap[i * 3 + p];
-      double ox, oy, oz;
-      image_offset(lat, sh, pos_w + i * 3, ox, oy, oz);
-      const double d2 = pair_d2(pos_w + j * 3, ox, oy, oz);
-      const double d = sqrt(d2);
-      in2 = pair_hit(d2, c2);
-      in3 = in2 && (float)d <= tb_cutoff;   // as the reference thresholds the narrowed lengths
-      const uint8_t st = (uint8_t)((in2 ? 1 : 0) | (in3 ? 2 : 0));
-      state[c] = st;
-      dist[c] = d;
-      changed = changed || (old_state && st != old_state[c]);
+      verlet_candidate(lat, sh, pos_w + i * 3, pos_w + j * 3, c2, tb_cutoff, c, old_state, state, dist, in2, in3, changed);
     }
     n2 += __popcll(__ballot(in2));
     n3 += __popcll(__ballot(in3));
   }
-  const bool any_changed = __any(changed);
-  if (lane == 0) {   // (no per-row atomics on shared totals: 10,000 waves on one address serialise -- k_verlet_totals adds the rows up)
-    row_keep[i] = n2;
-    row_tri[i] = (int64_t)n3 * (n3 > 0 ? n3 - 1 : 0);
-    // rare along a trajectory; right after a search EVERY row differs from the zeroed membership bytes, and 10,000 atomics on one
-    // address serialise (measured: 118 us) -- so look first, and only the first few waves write
-    if (any_changed && __atomic_load_n(acc + 1, __ATOMIC_RELAXED) == 0ull) atomicOr(acc + 1, 1ull);
-  }
+  verlet_row_done(i, lane, n2, n3, changed, row_keep, row_tri, acc);
 }
-// one workgroup: E = sum of the rows' kept candidates, T = sum of their triplets (fixed order: integers anyway)
-// (acc[5] = the longest candidate row: the caller chooses the refill entry point by it without a read-back of its own)
-__global__ void __launch_bounds__(1024) k_verlet_totals(int64_t N, const int32_t* __restrict__ row_keep, const int64_t* __restrict__ row_tri,
-                                                        const int32_t* __restrict__ row_ptr, unsigned long long* acc) {
-  __shared__ unsigned long long se[16], st[16], sm[16];
-  unsigned long long e = 0, t = 0, m = 0;
-  for (int64_t i = threadIdx.x; i < N; i += blockDim.x) {
-    e += (unsigned long long)row_keep[i]; t += (unsigned long long)row_tri[i];
-    const unsigned long long len = (unsigned long long)(row_ptr[i + 1] - row_ptr[i]);
-    m = len > m ? len : m;
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    e += __shfl_xor(e, o); t += __shfl_xor(t, o);
-    const unsigned long long mo = __shfl_xor(m, o);
-    m = mo > m ? mo : m;
-  }
-  if ((threadIdx.x & 63) == 0) { se[threadIdx.x >> 6] = e; st[threadIdx.x >> 6] = t; sm[threadIdx.x >> 6] = m; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    e = 0; t = 0; m = 0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) { e += se[k]; t += st[k]; m = sm[k] > m ? sm[k] : m; }
-    acc[2] = e; acc[3] = t; acc[5] = m;
-  }
+constexpr int kVerletTotalsWaves = 16;
+__global__ void __launch_bounds__(64 * kVerletTotalsWaves) k_verlet_totals(int64_t N, const int32_t* __restrict__ row_keep, const int64_t* __restrict__ row_tri,
+                                                                        const int32_t* __restrict__ row_ptr, unsigned long long* acc) {
+  verlet_totals<kVerletTotalsWaves>(N, row_keep, row_tri, row_ptr, acc);
 }
 
+constexpr int kRefillList = 1024;   // valid edges of a centre listed in LDS (the host checks the longest candidate row against it)
+// The d (d - 1) triplets of a centre from its valid edges listed by rank (d >= 2 of them in `vlist`), in the reference's order: slot q
+// holds the first edge of rank q / (d - 1) and the partner of rank k or k + 1, k = q % (d - 1) (itself skipped); the lanes write the
+// centre's contiguous range from out0 on side by side.  Shared by the three-body build and the two-launch refill.
+__device__ __forceinline__ void triplet_slots(int d, int lane, int64_t out0, int64_t T, const int32_t* vlist, int64_t* tei) {
+  const int n = d * (d - 1);
+  for (int q = lane; q < n; q += 64) {
+    const int a = q / (d - 1), k = q - a * (d - 1);
+    const int64_t o = out0 + q;
+    if (o < T) { tei[o] = vlist[a]; tei[T + o] = vlist[k < a ? k : k + 1]; }
+  }
+}
+// The kept candidates of centre i's row, in candidate order, to the edge slots from `out` on; the membership bytes become the
+// caller's.  DIST: also their distances.  LIST: the slots of the kept edges inside the three-body cutoff are listed by rank in
+// `vlist` (kRefillList entries); their number is returned (0 without LIST).
+template <bool DIST, bool LIST>
+__device__ __forceinline__ int verlet_fill_row(int64_t i, int lane, int r0, int r1, int64_t out, int64_t Ec, int64_t E, const int64_t* __restrict__ cand_ei,
+                                               const int32_t* __restrict__ cand_shift, const uint8_t* __restrict__ state, uint8_t* cand_state,
+                                               int64_t* __restrict__ edge_index, int32_t* __restrict__ shift, const double* __restrict__ dist_c,
+                                               double* __restrict__ dist, int32_t* vlist) {
+  int d = 0;   // edges of this centre inside the three-body cutoff so far
+  for (int base = r0; base < r1; base += 64) {
+    const int c = base + lane;
+    const uint8_t st = c < r1 ? state[c] : (uint8_t)0;
+    const bool keep = (st & 1) != 0, valid = LIST && (st & 2) != 0;
+    const unsigned long long m = __ballot(keep), mv = LIST ? __ballot(valid) : 0ull;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (c < r1) cand_state[c] = st;
+    if (keep) {
+      const int64_t a = out + __popcll(m & below);
+      if (a < E) {
+        edge_index[a] = i;
+        edge_index[E + a] = cand_ei[Ec + c];
+        for (int p = 0; p < 3; ++p) shift[a * 3 + p] = cand_shift[(int64_t)c * 3 + p];
+        if (DIST) dist[a] = dist_c[c];
+        if (valid) {
+          const int rk = d + __popcll(mv & below);
+          if (rk < kRefillList) vlist[rk] = (int32_t)a;
+        }
+      }
+    }
+    out += __popcll(m);
+    d += __popcll(mv);
+  }
+  return d;
+}
 // one wave per centre: its kept candidates, in candidate order, to the slots the scan assigned to the row
 __global__ void __launch_bounds__(256) k_verlet_fill(int64_t N, int64_t Ec, int64_t E, const int64_t* __restrict__ cand_ei,
                                                      const int32_t* __restrict__ cand_shift, const int32_t* __restrict__ row_ptr,
@@ -575,33 +644,16 @@ __global__ void __launch_bounds__(256) k_verlet_fill(int64_t N, int64_t Ec, int6
   const int lane = threadIdx.x & 63;
   const int64_t i = blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6);
   if (i >= N) return;
-  const int r0 = row_ptr[i], r1 = row_ptr[i + 1];
-  int64_t out = row_off[i];
-  for (int base = r0; base < r1; base += 64) {
-    const int c = base + lane;
-    const uint8_t st = c < r1 ? state[c] : (uint8_t)0;
-    const bool keep = (st & 1) != 0;
-    const unsigned long long m = __ballot(keep);
-    if (c < r1) cand_state[c] = st;
-    if (keep) {
-      const int64_t a = out + __popcll(m & ((1ull << lane) - 1ull));
-      if (a < E) {
-        edge_index[a] = i;
-        edge_index[E + a] = cand_ei[Ec + c];
-        for (int p = 0; p < 3; ++p) shift[a * 3 + p] = cand_shift[(int64_t)c * 3 + p];
-        dist[a] = dist_c[c];
-      }
-    }
-    out += __popcll(m);
-  }
+  verlet_fill_row<true, false>(i, lane, row_ptr[i], row_ptr[i + 1], row_off[i], Ec, E, cand_ei, cand_shift, state, cand_state, edge_index, shift, dist_c,
+                               dist, nullptr);
 }
 
 // Small cells: k_verlet_prep + k_verlet_rows + k_verlet_totals in ONE launch.  A wave per centre wraps its own position AND each
-// candidate's neighbour position on the fly (wrap_point on the raw coordinates: the very arithmetic k_verlet_prep applies per atom, so
-// every pair is classified exactly as before) instead of reading a wrapped copy another launch would have to write first; the
-// totals are formed by the launch's last workgroup (device-scope counter, nobody waits).  Three launch boundaries less per MD step
-// of a small cell (~10 us of the 0.19 ms a 32-atom iteration takes).
-constexpr int64_t kVerletFusedMaxAtoms = 512;
+// candidate's neighbour position on the fly (wrap_point on the raw coordinates: the very arithmetic k_verlet_prep applies per atom)
+// instead of reading a wrapped copy another launch would have to write first, and hands them to the same verlet_candidate /
+// verlet_row_done as k_verlet_rows; the totals are formed by the launch's last workgroup (last_workgroup: device-scope counter,
+// nobody waits).  Three launch boundaries less per MD step of a small cell (~10 us of the 0.19 ms a 32-atom iteration takes).
+constexpr int64_t kVerletFusedMaxAtoms = M3G_VERLET_ONE_LAUNCH_MAX_ATOMS;
 __global__ void __launch_bounds__(256) k_verlet_update_small(int64_t N, int64_t S, int64_t Ec, const double* __restrict__ pos,
                                                              const double* __restrict__ pos_ref, const int64_t* __restrict__ batch,
                                                              const double* __restrict__ lattice, const int64_t* __restrict__ cand_ei,
@@ -619,12 +671,7 @@ __global__ void __launch_bounds__(256) k_verlet_update_small(int64_t N, int64_t 
     double fi[3], wi[3], pwi[3];
     wrap_point(fr.lat, fr.inv, xi, yi, zi, fi, wi, pwi);
     const int wi0 = (int32_t)wi[0], wi1 = (int32_t)wi[1], wi2 = (int32_t)wi[2];
-    if (lane == 0) {   // largest displacement since the reference (k_verlet_prep)
-      const double dx = xi - pos_ref[i * 3], dy = yi - pos_ref[i * 3 + 1], dz = zi - pos_ref[i * 3 + 2];
-      double m = dx * dx + dy * dy + dz * dz;
-      if (!(m >= 0.0)) m = 1e300;
-      atomicMax(acc, (unsigned long long)__double_as_longlong(m));
-    }
+    if (lane == 0) atomicMax(acc, (unsigned long long)__double_as_longlong(verlet_disp2(xi, yi, zi, pos_ref + i * 3)));
     const double c2 = cutoff_sq(cutoff);
     const int r0 = row_ptr[i], r1 = row_ptr[i + 1];
     int n2 = 0, n3 = 0;
@@ -640,56 +687,15 @@ __global__ void __launch_bounds__(256) k_verlet_update_small(int64_t N, int64_t 
         sh[0] = cand_shift[(int64_t)c * 3] + (int32_t)wj[0] - wi0;
         sh[1] = cand_shift[(int64_t)c * 3 + 1] + (int32_t)wj[1] - wi1;
         sh[2] = cand_shift[(int64_t)c * 3 + 2] + (int32_t)wj[2] - wi2;
-        double ox, oy, oz;
-        image_offset(lat, sh, pwi, ox, oy, oz);
-        const double d2 = pair_d2(pwj, ox, oy, oz);
-        const double d = sqrt(d2);
-        in2 = pair_hit(d2, c2);
-        in3 = in2 && (float)d <= tb_cutoff;
-        const uint8_t st = (uint8_t)((in2 ? 1 : 0) | (in3 ? 2 : 0));
-        state[c] = st;
-        dist[c] = d;
-        changed = changed || (old_state && st != old_state[c]);
+        verlet_candidate(lat, sh, pwi, pwj, c2, tb_cutoff, c, old_state, state, dist, in2, in3, changed);
       }
       n2 += __popcll(__ballot(in2));
       n3 += __popcll(__ballot(in3));
     }
-    const bool any_changed = __any(changed);
-    if (lane == 0) {
-      row_keep[i] = n2;
-      row_tri[i] = (int64_t)n3 * (n3 > 0 ? n3 - 1 : 0);
-      if (any_changed && __atomic_load_n(acc + 1, __ATOMIC_RELAXED) == 0ull) atomicOr(acc + 1, 1ull);
-    }
+    verlet_row_done(i, lane, n2, n3, changed, row_keep, row_tri, acc);
   }
-  // totals by the last workgroup (k_verlet_totals' sums: integers, any order)
-  __shared__ int s_last;
-  __shared__ unsigned long long se[4], st4[4];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(acc + 4, 1ull) == (unsigned long long)gridDim.x - 1ull;
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  __shared__ unsigned long long sm4[4];
-  unsigned long long e = 0, t = 0, m = 0;
-  for (int64_t k = threadIdx.x; k < N; k += blockDim.x) {
-    e += (unsigned long long)row_keep[k]; t += (unsigned long long)row_tri[k];
-    const unsigned long long len = (unsigned long long)(row_ptr[k + 1] - row_ptr[k]);
-    m = len > m ? len : m;
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    e += __shfl_xor(e, o); t += __shfl_xor(t, o);
-    const unsigned long long mo = __shfl_xor(m, o);
-    m = mo > m ? mo : m;
-  }
-  if (lane == 0) { se[threadIdx.x >> 6] = e; st4[threadIdx.x >> 6] = t; sm4[threadIdx.x >> 6] = m; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    acc[2] = (se[0] + se[1]) + (se[2] + se[3]); acc[3] = (st4[0] + st4[1]) + (st4[2] + st4[3]);
-    m = sm4[0];
-    for (int k = 1; k < 4; ++k) m = sm4[k] > m ? sm4[k] : m;
-    acc[5] = m;
-  }
+  if (!last_workgroup(acc + 4)) return;
+  verlet_totals<4>(N, row_keep, row_tri, row_ptr, acc);
 }
 
 // ---- refill in two launches (m3g_verlet_fill_lists) ----------------------------------------------------------------------
@@ -753,7 +759,6 @@ __global__ void __launch_bounds__(kRefillScanThreads) k_verlet_offsets(int64_t N
   if (t == 0) { off_e[N] = (int32_t)carry_e; off_t[N] = carry_t; }
 }
 
-constexpr int kRefillList = 1024;   // valid edges of a centre listed in LDS (the host checks the longest candidate row against it)
 __global__ void __launch_bounds__(256) k_verlet_fill_lists(int64_t N, int64_t Ec, int64_t E, int64_t T, const int64_t* __restrict__ cand_ei,
                                                            const int32_t* __restrict__ cand_shift, const int32_t* __restrict__ row_ptr,
                                                            const int32_t* __restrict__ off_e, const int64_t* __restrict__ off_t,
@@ -766,30 +771,8 @@ __global__ void __launch_bounds__(256) k_verlet_fill_lists(int64_t N, int64_t Ec
   if (i >= N) return;
   int32_t* vlist = vlist_all + wave * kRefillList;
   const int r0 = row_ptr[i], r1 = row_ptr[i + 1];
-  int64_t out = off_e[i];
-  int d = 0;   // edges of this centre inside the three-body cutoff so far
-  for (int base = r0; base < r1; base += 64) {
-    const int c = base + lane;
-    const uint8_t st = c < r1 ? state[c] : (uint8_t)0;
-    const bool keep = (st & 1) != 0, valid = (st & 2) != 0;
-    const unsigned long long m = __ballot(keep), mv = __ballot(valid);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (c < r1) cand_state[c] = st;
-    if (keep) {
-      const int64_t a = out + __popcll(m & below);
-      if (a < E) {
-        edge_index[a] = i;
-        edge_index[E + a] = cand_ei[Ec + c];
-        for (int p = 0; p < 3; ++p) shift[a * 3 + p] = cand_shift[(int64_t)c * 3 + p];
-        if (valid) {
-          const int rk = d + __popcll(mv & below);
-          if (rk < kRefillList) vlist[rk] = (int32_t)a;
-        }
-      }
-    }
-    out += __popcll(m);
-    d += __popcll(mv);
-  }
+  const int d = verlet_fill_row<false, true>(i, lane, r0, r1, off_e[i], Ec, E, cand_ei, cand_shift, state, cand_state, edge_index, shift, nullptr, nullptr,
+                                             vlist);
   if (lane == 0 && num_triplet_i) num_triplet_i[i] = (int64_t)d * (d > 0 ? d - 1 : 0);
   if (num_triplet_ij) {   // per kept edge: d - 1 partners when it lies inside the three-body cutoff
     int64_t o2 = off_e[i];
@@ -806,13 +789,7 @@ __global__ void __launch_bounds__(256) k_verlet_fill_lists(int64_t N, int64_t Ec
   }
   if (d < 2) return;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // vlist entries written by other lanes of this wave
-  const int64_t out0 = off_t[i];
-  const int n = d * (d - 1);
-  for (int q = lane; q < n; q += 64) {   // slot q: first edge of rank q / (d - 1), partner of rank k or k + 1, k = q % (d - 1)
-    const int a = q / (d - 1), k = q - a * (d - 1);
-    const int64_t o = out0 + q;
-    if (o < T) { tei[o] = vlist[a]; tei[T + o] = vlist[k < a ? k : k + 1]; }
-  }
+  triplet_slots(d, lane, off_t[i], T, vlist, tei);
 }
 
 // ---- three-body ------------------------------------------------------------------------------------------------
@@ -827,25 +804,22 @@ struct TbScratch {
 };
 static TbScratch tb_carve(int64_t N, int64_t E, void* base) {
   TbScratch w{};
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p ? (void*)(p + off) : nullptr; off += align_up(bytes); return r; };
-  w.rank = (int32_t*)take(sizeof(int32_t) * (size_t)(E + 1));
-  w.deg = (int32_t*)take(sizeof(int32_t) * (size_t)(N + 1));
-  w.row_ptr = (int32_t*)take(sizeof(int32_t) * (size_t)(N + 2));
-  w.counts = (int64_t*)take(sizeof(int64_t) * (size_t)(E + 2));
+  Carve c{(char*)base};
+  w.rank = (int32_t*)c.take(sizeof(int32_t) * (size_t)(E + 1));
+  w.deg = (int32_t*)c.take(sizeof(int32_t) * (size_t)(N + 1));
+  w.row_ptr = (int32_t*)c.take(sizeof(int32_t) * (size_t)(N + 2));
+  w.counts = (int64_t*)c.take(sizeof(int64_t) * (size_t)(E + 2));
   const size_t tmp = prims::scan_tmp_bytes<int64_t>(E + 1);
   w.scan_tmp_bytes = tmp;
-  w.scan_tmp = take(tmp);
-  w.total = off;
+  w.scan_tmp = c.take(tmp);
+  w.total = c.off;
   return w;
 }
 
 __global__ void k_rows_from_sorted(int64_t N, int64_t E, const int64_t* __restrict__ src, int32_t* row_ptr, int* flags) {
   int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (r > N) return;
-  int64_t lo = 0, hi = E;
-  while (lo < hi) { int64_t mid = (lo + hi) >> 1; if (src[mid] < r) lo = mid + 1; else hi = mid; }
+  const int64_t lo = lower_bound(src, E, r);
   row_ptr[r] = (int32_t)lo;
   if (r < N && lo < E && lo > 0 && src[lo - 1] > src[lo]) atomicOr(flags, 1);
 }
@@ -903,12 +877,7 @@ __global__ void __launch_bounds__(256) k_fill_triplets(int64_t N, int64_t E, int
   const int64_t out0 = offsets[first];
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // vlist entries written by other lanes of this wave
   if (d <= kTripletList) {
-    const int n = d * (d - 1);
-    for (int q = lane; q < n; q += 64) {
-      const int a = q / (d - 1), k = q - a * (d - 1);
-      const int64_t o = out0 + q;
-      if (o < T) { tei[o] = vlist[a]; tei[T + o] = vlist[k < a ? k : k + 1]; }
-    }
+    triplet_slots(d, lane, out0, T, vlist, tei);
   } else {   // very long rows: one lane per first edge, partners found by walking the row
     for (int base = r0; base < r1; base += 64) {
       const int e = base + lane;
@@ -1046,7 +1015,7 @@ extern "C" int m3g_verlet_update_async(int64_t N, int64_t S, int64_t Ec, const d
   hipLaunchKernelGGL(k_verlet_prep, grid_for(N), dim3(256), 0, s, N, S, pos, pos_ref, lattice, batch, w.pos_w, w.wrap, w.acc);
   hipLaunchKernelGGL(k_verlet_rows, grid_for(N * 64), dim3(256), 0, s, N, S, Ec, batch, lattice, cand_edge_index, cand_shift, cand_row_ptr, w.pos_w,
                      w.wrap, cutoff, threebody_cutoff, cand_state, w.state, w.dist, w.row_keep, w.row_tri, w.acc);
-  hipLaunchKernelGGL(k_verlet_totals, dim3(1), dim3(1024), 0, s, N, w.row_keep, w.row_tri, cand_row_ptr, w.acc);
+  hipLaunchKernelGGL(k_verlet_totals, dim3(1), dim3(64 * kVerletTotalsWaves), 0, s, N, w.row_keep, w.row_tri, cand_row_ptr, w.acc);
   M3G_HIP_CHECK(hipMemcpyAsync(host_out, w.acc, sizeof(uint64_t) * 6, hipMemcpyDeviceToHost, s));
   return M3G_OK;
 }

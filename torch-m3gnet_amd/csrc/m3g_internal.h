@@ -230,6 +230,26 @@ namespace m3g {
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 // grid of a launch with one thread (or one group of `per`) per item
 inline dim3 grid_for(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
+// carving a caller's buffer into arrays, one after the other from `base`; a null base measures (`off` ends as the bytes needed)
+struct Carve {
+  char* base;
+  size_t off = 0;
+  void* take(size_t bytes) { void* r = base ? (void*)(base + off) : nullptr; off += align_up(bytes); return r; }
+};
+
+// ---- device helper shared by the graph-side units -----------------------------------------------------------
+// One thread's binary search: the first index of the sorted a[0..n) whose key is not below `key`, n when there is none.  `key_of`
+// projects an element onto what the array is sorted by (the high word of a 64-bit (row, partner) key, say).
+struct KeyItself { template <class T> __device__ T operator()(T v) const { return v; } };
+template <class T, class K, class KeyOf = KeyItself>
+__device__ __forceinline__ int64_t lower_bound(const T* a, int64_t n, K key, KeyOf key_of = {}) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (key_of(a[mid]) < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
 
 // ---- topology view (device arrays carved from the caller's topo buffer) -----------------------------
 // compile-time dispatch on (l_max, n_max) <= (4, 4): BODY sees constexpr int L, R

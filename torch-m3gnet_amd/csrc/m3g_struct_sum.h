@@ -153,12 +153,14 @@ __device__ __forceinline__ void struct_energy(int s, const int32_t* __restrict__
 // "The launch's last workgroup forms the per-structure sums": every workgroup publishes what it wrote (release fence), then counts
 // itself; the workgroup that counts last sees all of it (acquire fence) and forms the sums exactly as the stand-alone kernels do --
 // one launch less, the same fixed summation order, and no workgroup ever waits for another.  True in every thread of that
-// workgroup; every thread of the workgroup must call it (barriers).  `counter`: a zeroed word of Work::sync.
-__device__ __forceinline__ bool last_workgroup(int32_t* counter) {
+// workgroup; every thread of the workgroup must call it (barriers).  `counter`: a zeroed word (int32 of Work::sync, or the 64-bit
+// word 4 of the skin update's accumulators).
+template <class Word>
+__device__ __forceinline__ bool last_workgroup(Word* counter) {
   __shared__ int s_last;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
   __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(counter, 1) == (int)gridDim.x - 1;
+  if (threadIdx.x == 0) s_last = atomicAdd(counter, (Word)1) == (Word)gridDim.x - (Word)1;
   __syncthreads();
   if (!s_last) return false;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");

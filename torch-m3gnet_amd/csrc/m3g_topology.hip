@@ -6,10 +6,8 @@
 //   * triplets by first edge (t1) and by second edge (t2), each list in canonical (sorted) order so
 //     results do not depend on the order of triplet_edge_index (reference property test
 //     tests/test_model.py:21-38).
-// Index-only integer work: HBM-bound radix sorts (hipCUB) + binary searches; not on the per-step path
+// Index-only integer work: HBM-bound radix sorts and scans (m3g_prims.h) + binary searches; not on the per-step path
 // while the neighbour list is unchanged.
-#include <cstdlib>
-
 #include "m3g_internal.h"
 #include "m3g_prims.h"
 
@@ -26,53 +24,132 @@ size_t topo_sort_tmp_bytes(int64_t E, int64_t T) {
 Topo topo_carve(int64_t N, int64_t E, int64_t T, int64_t S, void* base) {
   Topo t{};
   t.N = N; t.E = E; t.T = T; t.S = S;
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p ? (void*)(p + off) : nullptr; off += align_up(bytes); return r; };
-  t.src = (int32_t*)take(sizeof(int32_t) * (E + 1));
-  t.dst = (int32_t*)take(sizeof(int32_t) * (E + 1));
-  t.row_ptr = (int32_t*)take(sizeof(int32_t) * (N + 1));
-  t.in_ptr = (int32_t*)take(sizeof(int32_t) * (N + 1));
-  t.in_edge = (int32_t*)take(sizeof(int32_t) * (E + 1));
-  t.in_pair = (int32_t*)take(sizeof(int32_t) * 2 * (E + 1));
-  t.in_pos = (int32_t*)take(sizeof(int32_t) * (E + 1));
-  t.t1_ptr = (int32_t*)take(sizeof(int32_t) * (E + 1));
-  t.t1_e2 = (int32_t*)take(sizeof(int32_t) * (T + 1));
-  t.t2_ptr = (int32_t*)take(sizeof(int32_t) * (E + 1));
-  t.t2_e1 = (int32_t*)take(sizeof(int32_t) * (T + 1));
-  t.act_list = (int32_t*)take(sizeof(int32_t) * (E + 1));
-  t.act_scan = (int32_t*)take(sizeof(int32_t) * (E + 2));
-  t.act_id = (int32_t*)take(sizeof(int32_t) * (E + 1));
-  t.arow_ptr = (int32_t*)take(sizeof(int32_t) * (N + 2));
-  t.act_dst = (int32_t*)take(sizeof(int32_t) * (E + 1));
-  t.tb_win = (int32_t*)take(sizeof(int32_t) * 6 * (E / kTbRows + 2));
-  t.tb_fast = (int32_t*)take(sizeof(int32_t) * 2 * (E / kTbRows + 2));
-  t.t1_e2c = (int32_t*)take(sizeof(int32_t) * (T + 1));
-  t.t2_e1c = (int32_t*)take(sizeof(int32_t) * (T + 1));
-  t.t1_b = (uint8_t*)take((size_t)T + 16);
-  t.t2_b = (uint8_t*)take((size_t)T + 16);
-  t.batch = (int32_t*)take(sizeof(int32_t) * (N + 1));
-  t.struct_ptr = (int32_t*)take(sizeof(int32_t) * (S + 2));
-  t.flags = (int32_t*)take(sizeof(int32_t) * kTopoFlags);
+  Carve c{(char*)base};
+  t.src = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
+  t.dst = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
+  t.row_ptr = (int32_t*)c.take(sizeof(int32_t) * (N + 1));
+  t.in_ptr = (int32_t*)c.take(sizeof(int32_t) * (N + 1));
+  t.in_edge = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
+  t.in_pair = (int32_t*)c.take(sizeof(int32_t) * 2 * (E + 1));
+  t.in_pos = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
+  t.t1_ptr = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
+  t.t1_e2 = (int32_t*)c.take(sizeof(int32_t) * (T + 1));
+  t.t2_ptr = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
+  t.t2_e1 = (int32_t*)c.take(sizeof(int32_t) * (T + 1));
+  t.act_list = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
+  t.act_scan = (int32_t*)c.take(sizeof(int32_t) * (E + 2));
+  t.act_id = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
+  t.arow_ptr = (int32_t*)c.take(sizeof(int32_t) * (N + 2));
+  t.act_dst = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
+  t.tb_win = (int32_t*)c.take(sizeof(int32_t) * 6 * (E / kTbRows + 2));
+  t.tb_fast = (int32_t*)c.take(sizeof(int32_t) * 2 * (E / kTbRows + 2));
+  t.t1_e2c = (int32_t*)c.take(sizeof(int32_t) * (T + 1));
+  t.t2_e1c = (int32_t*)c.take(sizeof(int32_t) * (T + 1));
+  t.t1_b = (uint8_t*)c.take((size_t)T + 16);
+  t.t2_b = (uint8_t*)c.take((size_t)T + 16);
+  t.batch = (int32_t*)c.take(sizeof(int32_t) * (N + 1));
+  t.struct_ptr = (int32_t*)c.take(sizeof(int32_t) * (S + 2));
+  t.flags = (int32_t*)c.take(sizeof(int32_t) * kTopoFlags);
   t.n_act = t.flags ? t.flags + 2 : nullptr;
   t.sort_tmp_bytes = topo_sort_tmp_bytes(E, T);
-  t.sort_tmp = take(t.sort_tmp_bytes);
-  t.total_bytes = off;
+  t.sort_tmp = c.take(t.sort_tmp_bytes);
+  t.total_bytes = c.off;
   return t;
 }
 
-__global__ void k_convert_edges(int64_t N, int64_t E, const int64_t* __restrict__ ei, int32_t* src, int32_t* dst,
-                                int32_t* edge_ids, int32_t* flags) {
-  int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (e >= E) return;
+// ---- one copy of every body that a stand-alone kernel of the general build shares with a role of the six-launch canonical build
+// (k_canon_*): the canonical build writes the general build's buffer bit for bit because both call these ----
+// edge e: int64 -> int32 with the range check (flags[0] bit 1) and the row-order check (bit 0)
+__device__ __forceinline__ void convert_edge(int64_t N, int64_t E, int64_t e, const int64_t* ei, int32_t* src, int32_t* dst, int32_t* flags) {
   int64_t i = ei[e], j = ei[E + e];
   int bad = 0;
   if (i < 0 || i >= N || j < 0 || j >= N) { bad |= 2; i = 0; j = 0; }
   if (e > 0 && ei[e - 1] > i) bad |= 1;
   src[e] = (int32_t)i;
   dst[e] = (int32_t)j;
-  edge_ids[e] = (int32_t)e;
   if (bad) atomicOr(flags, bad);
+}
+// atom a's structure id: range check (flags[0] bit 1) and order check (flags[3]: not sorted, per-structure sums fall back to atomics)
+__device__ __forceinline__ void convert_batch(int64_t S, int64_t a, const int64_t* batch, int32_t* out, int32_t* flags) {
+  int64_t b = batch[a];
+  if (b < 0 || b >= S) { atomicOr(flags, 2); b = 0; }
+  if (a > 0 && batch[a - 1] > batch[a]) atomicOr(flags + 3, 1);
+  out[a] = (int32_t)b;
+}
+// triplet t = (e1, e2): range check (flags[0] bit 1) and common-centre check (bit 2); an out-of-range pair comes back as (0, 0)
+__device__ __forceinline__ void checked_triplet(int64_t E, int64_t T, int64_t t, const int64_t* tei, const int32_t* src,
+                                                int32_t* flags, int64_t& e1, int64_t& e2) {
+  e1 = tei[t]; e2 = tei[T + t];
+  int bad = 0;
+  if (e1 < 0 || e1 >= E || e2 < 0 || e2 >= E) { bad |= 2; e1 = 0; e2 = 0; }
+  else if (src[e1] != src[e2]) bad |= 4;
+  if (bad) atomicOr(flags, bad);
+}
+// order[0] bit 0 when triplet t's key (e1, e2) is below its predecessor's: the list is not sorted
+__device__ __forceinline__ void triplet_order_check(int64_t T, int64_t t, const int64_t* tei, int64_t e1, int64_t e2, int32_t* order) {
+  if (t > 0) {
+    const int64_t p1 = tei[t - 1], p2 = tei[T + t - 1];
+    if (p1 > e1 || (p1 == e1 && p2 > e2)) atomicOr(order, 1);
+  }
+}
+// slot i of the by-neighbour list: (edge, table[edge]) and the inverse position.  (idx may hold anything while a build runs ahead of
+// its own verdict -- an edge list that turns out not to be symmetric leaves rows of in_edge unwritten until the sort replaces them --,
+// so the lookup is bounded: never an out-of-range read)
+__device__ __forceinline__ void pair_with_lookup(int64_t n, int64_t i, const int32_t* idx, const int32_t* table, int32_t* out,
+                                                 int32_t* pos) {
+  if (i >= n) return;
+  const int32_t e = idx[i];
+  const bool ok = e >= 0 && (int64_t)e < n;
+  out[2 * i] = ok ? e : 0;
+  out[2 * i + 1] = ok ? table[e] : -1;
+  if (ok) pos[e] = (int32_t)i;   // inverse of the by-neighbour list (a permutation of the edges once the build has passed its checks)
+}
+// byte-sized partner id of a triplet slot: compacted row r (-1: none) fixes the three-body workgroup and so the staged window
+// [lo, lo + n); the compacted partner is stored relative to lo, 255 when it falls outside
+__device__ __forceinline__ uint8_t partner_byte(int r, const int32_t* win, int partner_c) {
+  const int blk = (r < 0 ? 0 : r) / kTbRows;
+  const int wlo = win[6 * blk], whi = win[6 * blk + 1];
+  const int n = (whi - wlo) < kTbCap ? (whi - wlo) : kTbCap;
+  const int d = partner_c - wlo;
+  return (uint8_t)((r >= 0 && d >= 0 && d < n && d < 255) ? d : 255);
+}
+// Window b (b * kTbRows < A) of the A compacted rows: rows [lo, hi), na atoms from atom a0 on; true when it fits the moment path.
+// The test runs in the optimistic pass, BEFORE the malformed-graph flags are read back: an edge list not sorted by centre leaves
+// row_ptr / arow_ptr non-monotonic and the windows then come out with hi <= lo (or beyond A).  Such a window is never used (the build
+// raises), but it must not be dereferenced -- act_list[hi - 1] would index padding: it reads as empty, lo = hi = na = a0 = 0.
+__device__ __forceinline__ bool tb_window_fits(int A, int64_t b, const int32_t* win, const int32_t* act_list,
+                                               const int32_t* src, int& lo, int& hi, int& na, int& a0) {
+  lo = win[6 * b]; hi = win[6 * b + 1];
+  if (lo < 0 || hi <= lo || hi > A) { lo = 0; hi = 0; na = 0; a0 = 0; return false; }
+  a0 = src[act_list[lo]];
+  na = src[act_list[hi - 1]] - a0 + 1;
+  return na <= kTbFastAtoms && hi - lo <= kTbCap;
+}
+// the certificate's statistics over one workgroup of at most WAVES waves: windows that may not use the moment path (sum), largest
+// window in rows and in atoms (maxima); true in thread 0, which then holds the three totals
+template <int WAVES>
+__device__ __forceinline__ bool tb_stats_reduce(int& bad, int& rows, int& atoms) {
+  __shared__ int s_bad[WAVES], s_rows[WAVES], s_atoms[WAVES];
+  for (int o = 32; o > 0; o >>= 1) { bad += __shfl_xor(bad, o); rows = max(rows, __shfl_xor(rows, o)); atoms = max(atoms, __shfl_xor(atoms, o)); }
+  if ((threadIdx.x & 63) == 0) { s_bad[threadIdx.x >> 6] = bad; s_rows[threadIdx.x >> 6] = rows; s_atoms[threadIdx.x >> 6] = atoms; }
+  __syncthreads();
+  if (threadIdx.x != 0) return false;
+  bad = 0; rows = 0; atoms = 0;
+  for (int k = 0; k < (int)(blockDim.x >> 6); ++k) { bad += s_bad[k]; rows = max(rows, s_rows[k]); atoms = max(atoms, s_atoms[k]); }
+  return true;
+}
+// the certificate's word from its statistics; the window sizes travel in one byte each
+__host__ __device__ inline int32_t hints_word(int32_t bad, int32_t rows, int32_t atoms) {
+  static_assert(kTbCap <= 255 && kTbFastAtoms <= 255, "m3g_topology_hints packs the largest window (rows, atoms) in 8 bits each");
+  return (bad == 0 && rows > 0) ? (M3G_TOPO_TB_COMPLETE | ((rows & 0xff) << 8) | ((atoms & 0xff) << 16)) : 0;
+}
+
+__global__ void k_convert_edges(int64_t N, int64_t E, const int64_t* __restrict__ ei, int32_t* src, int32_t* dst,
+                                int32_t* edge_ids, int32_t* flags) {
+  int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  edge_ids[e] = (int32_t)e;
+  convert_edge(N, E, e, ei, src, dst, flags);
 }
 
 __global__ void k_iota32(int64_t n, int32_t* out) {
@@ -81,11 +158,7 @@ __global__ void k_iota32(int64_t n, int32_t* out) {
 }
 __global__ void k_convert_batch(int64_t N, int64_t S, const int64_t* __restrict__ batch, int32_t* out, int32_t* flags) {
   int64_t a = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (a >= N) return;
-  int64_t b = batch[a];
-  if (b < 0 || b >= S) { atomicOr(flags, 2); b = 0; }
-  if (a > 0 && batch[a - 1] > batch[a]) atomicOr(flags + 3, 1);   // not sorted: per-structure sums fall back to atomics
-  out[a] = (int32_t)b;
+  if (a < N) convert_batch(S, a, batch, out, flags);
 }
 
 // `order` (which == 0 only): order[0] != 0 when the (e1, e2) keys are not already in ascending order
@@ -94,17 +167,11 @@ __global__ void k_convert_triplets(int64_t E, int64_t T, const int64_t* __restri
                                    uint64_t* keys, int which, int32_t* flags, int32_t* order, int32_t* __restrict__ low_out = nullptr) {
   int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (t >= T) return;
-  int64_t e1 = tei[t], e2 = tei[T + t];
-  int bad = 0;
-  if (e1 < 0 || e1 >= E || e2 < 0 || e2 >= E) { bad |= 2; e1 = 0; e2 = 0; }
-  else if (src[e1] != src[e2]) bad |= 4;
+  int64_t e1, e2;
+  checked_triplet(E, T, t, tei, src, flags, e1, e2);
   keys[t] = which == 0 ? (((uint64_t)e1 << 32) | (uint64_t)e2) : (((uint64_t)e2 << 32) | (uint64_t)e1);
   if (low_out) low_out[t] = (int32_t)(which == 0 ? e2 : e1);
-  if (bad) atomicOr(flags, bad);
-  if (which == 0 && t > 0) {
-    const int64_t p1 = tei[t - 1], p2 = tei[T + t - 1];
-    if (p1 > e1 || (p1 == e1 && p2 > e2)) atomicOr(order, 1);
-  }
+  if (which == 0) triplet_order_check(T, t, tei, e1, e2, order);
 }
 // order[0] |= 2 when some triplet (e1, e2) has no mirror (e2, e1) in the SORTED key list: the list is one-sided.  The mirror can
 // only sit in the row of e2, rows[e2] .. rows[e2 + 1] (a handful of slots), so the search stays inside that row.
@@ -113,13 +180,9 @@ __global__ void k_check_symmetric(int64_t T, const uint64_t* __restrict__ sorted
   if (t >= T) return;
   const uint64_t k = sorted_keys[t], want = (k << 32) | (k >> 32);
   const int64_t e2 = (int64_t)(k & 0xffffffffu);
-  int64_t lo = rows[e2], hi = rows[e2 + 1];
-  const int64_t end = hi;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (sorted_keys[mid] < want) lo = mid + 1; else hi = mid;
-  }
-  if (lo >= end || sorted_keys[lo] != want) atomicOr(order, 2);
+  const int64_t begin = rows[e2], end = rows[e2 + 1];
+  const int64_t at = begin + lower_bound(sorted_keys + begin, end - begin, want);
+  if (at >= end || sorted_keys[at] != want) atomicOr(order, 2);
 }
 
 // Incoming-edge lists without a sort, for SYMMETRIC edge lists (every i -> j has its j -> i, with multiplicity: what any full
@@ -185,23 +248,11 @@ __global__ void __launch_bounds__(256) k_in_edges_symmetric(int64_t N, const int
 // ptr[r] = first position whose key (high word of keys64, or keys32[pos]) >= r, for r = 0..rows
 __global__ void k_lower_bound64(int64_t rows, int64_t n, const uint64_t* __restrict__ keys, int32_t* ptr) {
   int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (r > rows) return;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)(keys[mid] >> 32) < r) lo = mid + 1; else hi = mid;
-  }
-  ptr[r] = (int32_t)lo;
+  if (r <= rows) ptr[r] = (int32_t)lower_bound(keys, n, r, [](uint64_t k) { return (int64_t)(k >> 32); });
 }
 __global__ void k_lower_bound32(int64_t rows, int64_t n, const int32_t* __restrict__ keys, int32_t* ptr) {
   int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (r > rows) return;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)keys[mid] < r) lo = mid + 1; else hi = mid;
-  }
-  ptr[r] = (int32_t)lo;
+  if (r <= rows) ptr[r] = (int32_t)lower_bound(keys, n, r);
 }
 __global__ void k_low_word(int64_t n, const uint64_t* __restrict__ keys, int32_t* out) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -283,20 +334,11 @@ __global__ void __launch_bounds__(256) k_tb_fast(int64_t blocks, const int32_t* 
   int na = 0, a0 = 0;
   const int A = *n_act;
   if (b * kTbRows < A) {
-    const int lo = win[6 * b], hi = win[6 * b + 1];
-    // This kernel runs in the optimistic pass, BEFORE the malformed-graph flags are read back: an edge list not sorted by centre
-    // leaves row_ptr / arow_ptr non-monotonic and k_tb_windows then writes windows with hi <= lo (or beyond A).  Such a window
-    // is never used (the build raises), but it must not be dereferenced here: act_list[hi - 1] would index padding.
-    if (lo < 0 || hi <= lo || hi > A) {
-      if (lane == 0) { fast[2 * b] = 0; fast[2 * b + 1] = 0; }
-      return;
-    }
-    a0 = src[act_list[lo]];
-    na = src[act_list[hi - 1]] - a0 + 1;
+    int lo, hi;
+    const bool fits = tb_window_fits(A, b, win, act_list, src, lo, hi, na, a0);
     bool mine = true;
     if (ok) for (int r = lo + lane; r < hi; r += 64) mine = mine && ok[r] != 0;   // (ok == nullptr: lists complete by construction)
-    const bool all = na <= kTbFastAtoms && hi - lo <= kTbCap && __all(mine);
-    if (!all) na = 0;
+    if (!(fits && __all(mine))) na = 0;
   }
   if (lane == 0) {   // (the statistics of all windows are formed by k_tb_stats: thousands of atomics on three words serialise, 33 us)
     fast[2 * b] = na;
@@ -306,7 +348,6 @@ __global__ void __launch_bounds__(256) k_tb_fast(int64_t blocks, const int32_t* 
 // one workgroup: stats[0] = windows that hold rows but may not use the moment path, [1] = largest such window (rows), [2] = most atoms
 __global__ void __launch_bounds__(1024) k_tb_stats(int64_t blocks, const int32_t* __restrict__ n_act, const int32_t* __restrict__ win,
                                                    const int32_t* __restrict__ fast, int32_t* stats) {
-  __shared__ int s_bad[16], s_rows[16], s_atoms[16];
   const int A = *n_act;
   int bad = 0, rows = 0, atoms = 0;
   for (int64_t b = threadIdx.x; b < blocks; b += blockDim.x) {
@@ -315,30 +356,15 @@ __global__ void __launch_bounds__(1024) k_tb_stats(int64_t blocks, const int32_t
     if (na > 0) { rows = max(rows, win[6 * b + 1] - win[6 * b]); atoms = max(atoms, na); }
     else ++bad;
   }
-  for (int o = 32; o > 0; o >>= 1) { bad += __shfl_xor(bad, o); rows = max(rows, __shfl_xor(rows, o)); atoms = max(atoms, __shfl_xor(atoms, o)); }
-  if ((threadIdx.x & 63) == 0) { s_bad[threadIdx.x >> 6] = bad; s_rows[threadIdx.x >> 6] = rows; s_atoms[threadIdx.x >> 6] = atoms; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    bad = 0; rows = 0; atoms = 0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) { bad += s_bad[k]; rows = max(rows, s_rows[k]); atoms = max(atoms, s_atoms[k]); }
-    stats[0] = bad; stats[1] = rows; stats[2] = atoms;
-  }
+  if (tb_stats_reduce<16>(bad, rows, atoms)) { stats[0] = bad; stats[1] = rows; stats[2] = atoms; }
 }
 __global__ void k_set_word(int32_t* dst, int32_t v) { *dst = v; }
-// (idx may hold anything while a build runs ahead of its own verdict -- an edge list that turns out not to be symmetric leaves
-// rows of in_edge unwritten until the sort replaces them --, so the lookup is bounded: never an out-of-range read)
 __global__ void k_pair_with_lookup(int64_t n, const int32_t* __restrict__ idx, const int32_t* __restrict__ table, int32_t* out, int32_t* pos) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int32_t e = idx[i];
-  const bool ok = e >= 0 && (int64_t)e < n;
-  out[2 * i] = ok ? e : 0;
-  out[2 * i + 1] = ok ? table[e] : -1;
-  if (ok) pos[e] = (int32_t)i;   // inverse of the by-neighbour list (a permutation of the edges once the build has passed its checks)
+  pair_with_lookup(n, i, idx, table, out, pos);
 }
-// byte-sized partner ids: for triplet slot t of list (t_ptr, t_other_c), the row it belongs to fixes the workgroup and so the
-// staged window [lo, lo + n); the partner is stored relative to lo, 255 when it falls outside.  The row is the high word of the
-// slot's sorted key when the keys are still at hand (KEYS), otherwise a binary search in t_ptr.
+// partner_byte for triplet slot t of list (t_ptr, t_other_c).  The row the slot belongs to is the high word of the slot's sorted key
+// when the keys are still at hand (KEYS), otherwise a binary search in t_ptr.
 template <bool KEYS>
 __global__ void k_partner_bytes(int64_t E, int64_t T, const int32_t* __restrict__ t_ptr, const uint64_t* __restrict__ sorted_keys,
                                 const int32_t* __restrict__ act_id, const int32_t* __restrict__ win, const int32_t* __restrict__ t_other_c,
@@ -349,15 +375,10 @@ __global__ void k_partner_bytes(int64_t E, int64_t T, const int32_t* __restrict_
   if (KEYS) {
     lo = (int64_t)(sorted_keys[t] >> 32);
   } else {
-    int64_t hi = E;   // last e with t_ptr[e] <= t
+    int64_t hi = E;   // last e with t_ptr[e] <= t (an upper bound: not lower_bound's search)
     while (lo < hi) { int64_t mid = (lo + hi + 1) >> 1; if (t_ptr[mid] <= t) lo = mid; else hi = mid - 1; }
   }
-  const int r = act_id[lo];
-  const int blk = (r < 0 ? 0 : r) / kTbRows;
-  const int wlo = win[6 * blk], whi = win[6 * blk + 1];
-  const int n = (whi - wlo) < kTbCap ? (whi - wlo) : kTbCap;
-  const int d = t_other_c[t] - wlo;
-  out[t] = (uint8_t)((r >= 0 && d >= 0 && d < n && d < 255) ? d : 255);
+  out[t] = partner_byte(act_id[lo], win, t_other_c[t]);
 }
 __global__ void k_compact_partners(int64_t T, const int32_t* __restrict__ scan, const int32_t* __restrict__ a, const int32_t* __restrict__ b,
                                    int32_t* ac, int32_t* bc) {
@@ -378,15 +399,7 @@ __global__ void k_compact_partners(int64_t T, const int32_t* __restrict__ scan, 
 // whole build down the general path.  Every kernel after the first leaves at once when the first has flagged the edge list, so
 // none walks rows that are not rows; the triplet list is checked in the last kernel (its one pass over the triplets), and the kernels
 // before it only read it through bounded searches and a streamed pass that ignores what does not belong to the atom's row.
-__device__ __forceinline__ int64_t lower_bound_i64(const int64_t* __restrict__ a, int64_t n, int64_t key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-// the same by a whole wave: 64 probes per round, so ~log64(n) dependent loads instead of log2(n) (4 against 22 on the 10k-atom
+// lower_bound (m3g_internal.h) by a whole wave: 64 probes per round, so ~log64(n) dependent loads instead of log2(n) (4 against 22 on the 10k-atom
 // cell's triplet list; the per-lane search made k_canon_triplets a 47-us chain of round trips).  Wave-uniform result.
 __device__ __forceinline__ int64_t wave_lower_bound_i64(const int64_t* __restrict__ a, int64_t n, int64_t key, int lane) {
   int64_t lo = 0, hi = n;   // the answer lies in [lo, hi]
@@ -437,29 +450,16 @@ __device__ __forceinline__ void wave_lower_bound2_i64(const int64_t* __restrict_
   *out1 = lo1;
 }
 constexpr int kCanonStage = 512;   // edges per atom whose triplet rows are resolved in LDS (longer rows: one binary search per edge)
-// roles by thread index: edges (k_convert_edges), atoms (k_convert_batch), rows (lower bounds in the int64 lists themselves), zero
+// roles by thread index: edges (convert_edge), atoms (convert_batch), rows (lower bounds in the int64 lists themselves), zero
 // fill of the window tables
 __global__ void __launch_bounds__(256) k_canon_edges(int64_t N, int64_t E, int64_t S, const int64_t* __restrict__ ei, const int64_t* __restrict__ batch,
                                                      int32_t* src, int32_t* dst, int32_t* out_batch, int32_t* row_ptr, int32_t* struct_ptr, int32_t* tb_win,
                                                      int64_t n_win, int32_t* tb_fast, int64_t n_fast, int32_t* flags) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < E) {
-    int64_t a = ei[i], b = ei[E + i];
-    int bad = 0;
-    if (a < 0 || a >= N || b < 0 || b >= N) { bad |= 2; a = 0; b = 0; }
-    if (i > 0 && ei[i - 1] > a) bad |= 1;
-    src[i] = (int32_t)a;
-    dst[i] = (int32_t)b;
-    if (bad) atomicOr(flags, bad);
-  }
-  if (i < N) {
-    int64_t b = batch[i];
-    if (b < 0 || b >= S) { atomicOr(flags, 2); b = 0; }
-    if (i > 0 && batch[i - 1] > batch[i]) atomicOr(flags + 3, 1);
-    out_batch[i] = (int32_t)b;
-  }
-  if (i <= N) row_ptr[i] = (int32_t)lower_bound_i64(ei, E, i);
-  if (i <= S) struct_ptr[i] = (int32_t)lower_bound_i64(batch, N, i);
+  if (i < E) convert_edge(N, E, i, ei, src, dst, flags);
+  if (i < N) convert_batch(S, i, batch, out_batch, flags);
+  if (i <= N) row_ptr[i] = (int32_t)lower_bound(ei, E, i);
+  if (i <= S) struct_ptr[i] = (int32_t)lower_bound(batch, N, i);
   if (i < n_win) tb_win[i] = 0;
   if (i < n_fast) tb_fast[i] = 0;
 }
@@ -491,9 +491,9 @@ __global__ void __launch_bounds__(256) k_canon_rows(int64_t N, int64_t E, int64_
     for (int base = r0; base < r1; base += 64) {
       const int e = base + lane;
       const bool valid = e < r1;
-      int p = valid ? (int)lower_bound_i64(tei, T, e) : 0;
+      int p = valid ? (int)lower_bound(tei, T, (int64_t)e) : 0;
       int pn = __shfl_down(p, 1);
-      if (valid && (lane == 63 || e + 1 >= r1)) pn = (int)lower_bound_i64(tei, T, (int64_t)e + 1);
+      if (valid && (lane == 63 || e + 1 >= r1)) pn = (int)lower_bound(tei, T, (int64_t)e + 1);
       if (valid) { t1_ptr[e] = p; t2_ptr[e] = p; }
       n_active += __popcll(__ballot(valid && pn > p));
     }
@@ -590,9 +590,9 @@ __global__ void __launch_bounds__(256) k_canon_active(int64_t N, int64_t E, cons
     run += __popcll(mask);
   }
 }
-// roles by workgroup: [0, e_blocks) in-edge pairs (k_pair_with_lookup); [e_blocks, e_blocks + t_blocks) compacted partners and their
+// roles by workgroup: [0, e_blocks) in-edge pairs (pair_with_lookup); [e_blocks, e_blocks + t_blocks) compacted partners and their
 // window bytes in both roles (k_compact_partners, k_partner_bytes); the last workgroup: which windows may use the moment path, and the
-// statistics of the certificate (k_tb_fast for lists complete by construction, k_tb_stats)
+// statistics of the certificate (k_tb_fast's window test for lists complete by construction, k_tb_stats' reduction)
 __global__ void __launch_bounds__(256) k_canon_finish(int64_t E, int64_t T, int64_t e_blocks, int64_t t_blocks, int64_t windows,
                                                       const int64_t* __restrict__ tei, const int32_t* __restrict__ in_edge,
                                                       const int32_t* __restrict__ act_id, const int32_t* __restrict__ act_scan,
@@ -605,74 +605,45 @@ __global__ void __launch_bounds__(256) k_canon_finish(int64_t E, int64_t T, int6
   if (__builtin_nontemporal_load(flags) & 15) return;
   const int64_t blk = blockIdx.x;
   if (blk < e_blocks) {
-    const int64_t i = blk * blockDim.x + threadIdx.x;
-    if (i >= E) return;
-    const int32_t e = in_edge[i];
-    const bool ok = e >= 0 && (int64_t)e < E;
-    in_pair[2 * i] = ok ? e : 0;
-    in_pair[2 * i + 1] = ok ? act_id[e] : -1;
-    if (ok) in_pos[e] = (int32_t)i;
+    pair_with_lookup(E, blk * blockDim.x + threadIdx.x, in_edge, act_id, in_pair, in_pos);
     return;
   }
   if (blk < e_blocks + t_blocks) {
     const int64_t t = (blk - e_blocks) * blockDim.x + threadIdx.x;
     if (t >= T) return;
-    // the one pass over the triplet list: range / centre / order checks (k_convert_triplets), partner lists in both roles, then the
-    // compacted partners and their window bytes
-    int64_t e1 = tei[t], e2 = tei[T + t];
-    int bad = 0;
-    if (e1 < 0 || e1 >= E || e2 < 0 || e2 >= E) { bad |= 2; e1 = 0; e2 = 0; }
-    else if (src[e1] != src[e2]) bad |= 4;
-    if (bad) atomicOr(flags, bad);
-    if (t > 0) {
-      const int64_t p1 = tei[t - 1], p2 = tei[T + t - 1];
-      if (p1 > tei[t] || (p1 == tei[t] && p2 > tei[T + t])) atomicOr(flags + 1, 1);
-    }
+    // the one pass over the triplet list: range / centre / order checks (as k_convert_triplets), partner lists in both roles, then
+    // the compacted partners and their window bytes
+    int64_t e1, e2;
+    checked_triplet(E, T, t, tei, src, flags, e1, e2);
+    triplet_order_check(T, t, tei, e1, e2, flags + 1);
     t1_e2[t] = (int32_t)e2;
     t2_e1[t] = (int32_t)e2;
     const int c2 = act_scan[e2];
     t1_e2c[t] = c2;
     t2_e1c[t] = c2;
-    const int r = act_id[e1];
-    const int b = (r < 0 ? 0 : r) / kTbRows;
-    const int wlo = win[6 * b], whi = win[6 * b + 1];
-    const int n = (whi - wlo) < kTbCap ? (whi - wlo) : kTbCap;
-    const int d = c2 - wlo;
-    const uint8_t byte = (uint8_t)((r >= 0 && d >= 0 && d < n && d < 255) ? d : 255);
+    const uint8_t byte = partner_byte(act_id[e1], win, c2);
     t1_b[t] = byte;
     t2_b[t] = byte;
     return;
   }
-  __shared__ int s_bad[4], s_rows[4], s_atoms[4];
   const int A = flags[2];
   int bad = 0, rows = 0, atoms = 0;
   for (int64_t b = threadIdx.x; b < windows; b += blockDim.x) {
     int na = 0, a0 = 0;
     if (b * kTbRows < A) {
-      const int lo = win[6 * b], hi = win[6 * b + 1];
-      if (lo >= 0 && hi > lo && hi <= A) {
-        a0 = src[act_list[lo]];
-        na = src[act_list[hi - 1]] - a0 + 1;
-        if (!(na <= kTbFastAtoms && hi - lo <= kTbCap)) na = 0;
-        if (na > 0) { rows = max(rows, hi - lo); atoms = max(atoms, na); }
-        else ++bad;
-      } else {
-        a0 = 0; ++bad;
-      }
+      int lo, hi;
+      if (!tb_window_fits(A, b, win, act_list, src, lo, hi, na, a0)) na = 0;   // (rows complete by construction: no per-row test)
+      if (na > 0) { rows = max(rows, hi - lo); atoms = max(atoms, na); }
+      else ++bad;
     }
     fast[2 * b] = na;
     fast[2 * b + 1] = a0;
   }
-  for (int o = 32; o > 0; o >>= 1) { bad += __shfl_xor(bad, o); rows = max(rows, __shfl_xor(rows, o)); atoms = max(atoms, __shfl_xor(atoms, o)); }
-  if ((threadIdx.x & 63) == 0) { s_bad[threadIdx.x >> 6] = bad; s_rows[threadIdx.x >> 6] = rows; s_atoms[threadIdx.x >> 6] = atoms; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    bad = 0; rows = 0; atoms = 0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) { bad += s_bad[k]; rows = max(rows, s_rows[k]); atoms = max(atoms, s_atoms[k]); }
+  if (tb_stats_reduce<4>(bad, rows, atoms)) {
     stats[0] = bad; stats[1] = rows; stats[2] = atoms;
-    // the certificate's word stays with the buffer (flags[7] = stats[3]; hints_word() on the host forms the same word from the
-    // verdict): every check has passed when this line is reached, so no launch is needed after the host has read the verdict
-    stats[3] = (bad == 0 && rows > 0) ? (M3G_TOPO_TB_COMPLETE | ((rows & 0xff) << 8) | ((atoms & 0xff) << 16)) : 0;
+    // the certificate's word stays with the buffer (flags[7] = stats[3]; the host forms the same word from the verdict with the same
+    // function): every check has passed when this line is reached, so no launch is needed after the host has read the verdict
+    stats[3] = hints_word(bad, rows, atoms);
   }
 }
 
@@ -716,12 +687,6 @@ static bool launch_hint_kernels(const Topo& t, hipStream_t s, bool trusted = fal
   hipLaunchKernelGGL(k_tb_stats, dim3(1), dim3(1024), 0, s, E / kTbRows + 1, t.n_act, t.tb_win, t.tb_fast, t.flags + 4);
   return true;
 }
-static int32_t hints_word(const int32_t (&h)[3]) {
-  // the window sizes travel in one byte each
-  static_assert(kTbCap <= 255 && kTbFastAtoms <= 255, "m3g_topology_hints packs the largest window (rows, atoms) in 8 bits each");
-  return (h[0] == 0 && h[1] > 0) ? (M3G_TOPO_TB_COMPLETE | ((h[1] & 0xff) << 8) | ((h[2] & 0xff) << 16)) : 0;
-}
-
 // host_hints != NULL: also form the certificate of m3g_topology_hints and return its word.  For the lists the graph builders emit
 // (triplets sorted by (e1, e2) and symmetric, edge list symmetric) the WHOLE build -- rows, partner lists, active-edge compaction,
 // windows, certificate -- is queued on that assumption and ONE read-back (malformed-graph bits, order / symmetry verdicts, the
@@ -827,7 +792,7 @@ static int topology_build(int64_t N, int64_t E, int64_t T, int64_t S, const int6
     const bool assumed_ok = !(h[1] & 3) && !(try_mirrors && (h[0] & 8));
     if (assumed_ok) {
       if (hinted) {
-        *host_hints = hints_word(hs);
+        *host_hints = hints_word(hs[0], hs[1], hs[2]);
         // the same word stays with the buffer (flags[7]): the moment kernels run only when the word the caller hands to
         // m3g_energy_forces is the one certified for THIS topology buffer
         hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, s, t.flags + 7, *host_hints);
@@ -915,8 +880,7 @@ extern "C" int m3g_topology_build_hints(int64_t N, int64_t E, int64_t T, int64_t
 constexpr int64_t kCanonMaxAtoms = 131072;   // k_canon_scan is one workgroup
 static thread_local int32_t g_last_canonical_path = 0;
 static bool canonical_fast_applies(int64_t N, int64_t E, int64_t T, int64_t S, const void* ei, const void* tei, const void* batch) {
-  static const bool fast_off = [] { const char* v = getenv("M3G_CANON_FAST"); return v && v[0] == '0'; }();   // A/B measurements
-  return !fast_off && N > 0 && N <= kCanonMaxAtoms && E > 0 && T > 0 && S > 0 && ei && tei && batch;
+  return N > 0 && N <= kCanonMaxAtoms && E > 0 && T > 0 && S > 0 && ei && tei && batch;
 }
 static int canonical_fast_launch(int64_t N, int64_t E, int64_t T, int64_t S, const int64_t* edge_index, const int64_t* triplet_edge_index,
                                  const int64_t* batch, const Topo& t, int32_t* verdict, hipStream_t s) {
@@ -944,8 +908,7 @@ static int canonical_fast_launch(int64_t N, int64_t E, int64_t T, int64_t S, con
 static int canonical_fast_settle(const Topo& t, const int32_t* verdict, int32_t* host_flags, int32_t* host_hints, hipStream_t s, bool* done) {
   *done = false;
   if ((verdict[0] & 15) || (verdict[1] & 1)) return M3G_OK;   // malformed, not symmetric or not sorted: the general path decides what it is
-  const int32_t hs[3] = {verdict[4], verdict[5], verdict[6]};
-  *host_hints = hints_word(hs);   // (k_canon_finish has left the same word on the buffer, flags[7])
+  *host_hints = hints_word(verdict[4], verdict[5], verdict[6]);   // (k_canon_finish has left the same word on the buffer, flags[7])
   (void)s;
   if (host_flags) host_flags[0] = verdict[0];
   *done = true;
@@ -1037,7 +1000,7 @@ extern "C" int m3g_topology_hints(int64_t N, int64_t E, int64_t T, int64_t S, co
   int32_t h[3] = {0, 0, 0};
   M3G_HIP_CHECK(hipMemcpyAsync(h, t.flags + 4, sizeof(h), hipMemcpyDeviceToHost, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
-  *host_hints = hints_word(h);
+  *host_hints = hints_word(h[0], h[1], h[2]);
   // the same word stays with the buffer (flags[7]): the moment kernels run only when the word the caller hands to m3g_energy_forces
   // is the one certified for THIS topology buffer -- a stale word, or one copied from another buffer, flags an error instead
   hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, s, t.flags + 7, *host_hints);

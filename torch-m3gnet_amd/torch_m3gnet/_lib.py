@@ -12,6 +12,7 @@ LIB_PATH = _PKG_ROOT / "lib" / "libm3gnet_hip.so"
 M3G_OK, M3G_ERR_VALUE, M3G_ERR_STATE, M3G_ERR_SIZE, M3G_ERR_HIP, M3G_ERR_UNSUPPORTED = range(6)
 ABI_VERSION = 11
 VERLET_FILL_LISTS_MAX_ROW = 1024   # M3G_VERLET_FILL_LISTS_MAX_ROW (include/m3gnet_hip.h)
+VERLET_ONE_LAUNCH_MAX_ATOMS = 512   # M3G_VERLET_ONE_LAUNCH_MAX_ATOMS: m3g_verlet_update is one launch up to here, three above
 
 
 class M3GConfig(C.Structure):
