@@ -618,6 +618,63 @@ int m3g_remd_read(int64_t n_structs, int64_t n_ladders, const void* state, size_
 /* Byte offset, inside an m3g_dyn_* state buffer of these sizes, of the target temperatures [S] (fp64) the exchange writes. */
 int m3g_remd_target_view(int64_t n_atoms, int64_t n_structs, size_t* temperature_offset);
 
+/* ---- batched canonical atom-swap Monte Carlo, alone or interleaved with m3g_dyn_* MD (csrc/m3g_mc.hip) -------------------------------
+ * A batch of S structures with N atoms in all (offsets [S+1] as m3g_fire_init), each with a temperature T_s > 0 (K) and a 64-bit seed.
+ * `active` [N] (uint8) marks the rows that take part, fixed for the run (only the cation sublattice, say).  Rows are SITES: a trial
+ * exchanges the occupants of two rows of one structure -- two entries of atom_types and, with a dynamics state, their masses and
+ * velocities (the atoms trade places and each keeps its own velocity, so the kinetic energy is unchanged and the acceptance needs
+ * the potential energy only).  Positions never move: neighbour and triplet lists stay valid, and the multiset of species is
+ * preserved, so a range check of atom_types made once stays true.
+ * Draws: structure s keeps a proposal counter a_s = 0, 1, ... on the device; proposal a_s draws Philox4x64-10 with counter
+ * (a_s, 0, 0, 0) and key (seed_s, 2) -- key word 0 is the Langevin noise, word 1 replica exchange; u_k = ((w_k >> 11) + 0.5) 2^-53.
+ * m3g_mc_propose, per structure: n_p = its active rows; row i = the active row of rank min((int64)(u_0 n_p), n_p - 1) in row order;
+ *   m = the active rows whose species differs from that of i; row j = the one of rank min((int64)(u_1 m), m - 1) among those.  The
+ *   pair is drawn with probability (1/n_p) [1/(n_p - n_s(i)) + 1/(n_p - n_s(j))], which the swap leaves unchanged: the proposal is
+ *   symmetric for unequal compositions too.  The occupants of i and j are exchanged in place, (i, j) and u_2 of the SAME Philox
+ *   output are recorded, M3G_MC_PENDING is set.  a_s advances for every structure at every call, attempted or not, so a structure's
+ *   stream depends on its own history only; a_s - 1 is also the index of the call.
+ *   A structure is NOT attempted, nothing of it written but a_s (and the flag named), when it is already PENDING (sets the sticky
+ *   M3G_MC_ERR_ORDER), when a dynamics state is given and it has M3G_DYN_ERROR or M3G_DYN_STARTED (half-step velocities: call after a
+ *   finish_only m3g_dyn_step), when its current energy is not finite, or when its active rows hold fewer than two species (sets
+ *   M3G_MC_NO_PAIR; the init call sets it for fewer than two active rows).
+ * m3g_mc_decide, per PENDING structure, at the trial energies E' [S] (the engine's output for the swapped species) and the current
+ *   energies E [S] (caller-owned, updated in place): dE = (double)E' - (double)E; a non-finite E' is rejected explicitly (-inf too)
+ *   and counted in `nonfinite`; otherwise accepted iff dE <= 0 or u_2 < exp(-dE / (k_B T_s)), k_B of m3g_dyn_*.  Reject: rows i, j
+ *   are exchanged back -- species, masses and velocities bitwise what they were.  Accept: E[s] = E'[s], and the structure's rows of
+ *   the current forces [N,3] / stresses [S,6], when given, are overwritten with the trial ones (a rejected structure's stay bitwise
+ *   untouched).  Then attempts, accepts and count / mean / M2 (Welford, fp64) of the current energy after the verdict are updated
+ *   and PENDING is cleared.  Row a of history [rows, S, 3] (int32), a the index of the last propose call, gets (i - o_s, j - o_s,
+ *   1 | 0), or (-1, -1, -1) for a structure that call did not attempt, if a < rows; a second decide without a new proposal changes
+ *   nothing.
+ * No atomics: a structure's results are bitwise the same alone or in any batch. */
+#define M3G_MC_NO_PAIR 1     /* fewer than two active rows, or fewer than two species on them: never attempted */
+#define M3G_MC_PENDING 2     /* proposed, not yet decided: atom_types (masses, velocities) hold the trial configuration */
+#define M3G_MC_ERR_ORDER 4   /* sticky: a proposal was asked for while one was pending */
+int m3g_mc_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* bytes);
+/* host_offsets [S+1] int64, host_temperatures [S] (K), host_seeds [S], host_active [N] uint8: HOST.  Null pointers, bad offsets, a
+ * temperature that is not finite and > 0 -> M3G_ERR_VALUE, a short buffer -> M3G_ERR_SIZE, before any HIP call.  Waits for the
+ * stream. */
+int m3g_mc_init(int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_temperatures, const uint64_t* host_seeds,
+                const uint8_t* host_active, void* state, size_t state_bytes, void* stream);
+/* atom_types [N] int64 DEVICE (the array the engine reads), exchanged in place; dyn_state: of m3g_dyn_init over the same batch, or
+ * NULL (pure lattice Monte Carlo); energies [S] f32 DEVICE: the current ones.  ONE launch whatever S, no allocation, copy or wait:
+ * capture-safe. */
+int m3g_mc_propose(int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, int64_t* atom_types, void* dyn_state, size_t dyn_bytes,
+                   const float* energies, void* stream);
+/* trial_energies [S], trial_forces [N,3], trial_stresses [S,6] (f32 DEVICE): the evaluation of the trial; energies, forces, stresses:
+ * the current ones, updated in place.  forces and stresses are optional, each given together with its trial partner (else
+ * M3G_ERR_VALUE); history [history_rows, S, 3] int32 DEVICE or NULL.  TWO launches (the verdict with the revert, the row copy over the
+ * chunk table), ONE when forces and stresses are NULL; no allocation, copy or wait: capture-safe. */
+int m3g_mc_decide(int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, int64_t* atom_types, void* dyn_state, size_t dyn_bytes,
+                  const float* trial_energies, const float* trial_forces, const float* trial_stresses, float* energies, float* forces,
+                  float* stresses, int32_t* history, int64_t history_rows, void* stream);
+/* To HOST memory, every output may be NULL: flags (M3G_MC_*, int32), proposal counters, attempts, accepts, non-finite trials, count
+ * (int64), mean and M2 (fp64) of the current energy [S], and the last attempted pair [S,2] (int32, rows relative to the structure).
+ * Waits for the stream. */
+int m3g_mc_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes, int32_t* host_flags, int64_t* host_counters,
+                int64_t* host_attempts, int64_t* host_accepts, int64_t* host_nonfinite, int64_t* host_count, double* host_mean, double* host_m2,
+                int32_t* host_pairs, void* stream);
+
 /* ---- trajectory observables: RDF, MSD and VACF accumulated on the device (csrc/m3g_trajectory.hip) ---------------------------------
  * Fed one frame per m3g_traj_sample (from the MD loop, or any frames): per structure and species pair (a <= b) the INTEGER histogram
  * of minimum-image pair distances below r_max in rdf_bins bins (unordered pairs i < j; bin = (int)(r rdf_bins / r_max) taken only
@@ -936,7 +993,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     FIRE) -- new exports only: no existing struct, constant or call changes, so a caller built
                              *     against 11 runs unchanged;
                              *     additive, same version: m3g_remd_state_bytes / _init / _exchange / _read / _target_view (batched
-                             *     replica-exchange MD over an m3g_dyn_* batch) */
+                             *     replica-exchange MD over an m3g_dyn_* batch);
+                             *     additive, same version: m3g_mc_state_bytes / _init / _propose / _decide / _read (batched atom-swap
+                             *     Monte Carlo, alone or over an m3g_dyn_* batch) */
 
 #ifdef __cplusplus
 }

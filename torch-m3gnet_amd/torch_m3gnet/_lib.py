@@ -85,6 +85,7 @@ class M3GDynParams(C.Structure):   # m3g_dyn_params
 
 DYN_NVE, DYN_NVT_BERENDSEN, DYN_NVT_LANGEVIN, DYN_NPT_BERENDSEN = range(4)   # M3G_DYN_* ensembles
 DYN_STARTED, DYN_ERROR = 1, 2                                               # M3G_DYN_* flag bits
+MC_NO_PAIR, MC_PENDING, MC_ERR_ORDER = 1, 2, 4                              # M3G_MC_* flag bits
 NEB_ROWS = 5                                                                 # M3G_NEB_ROWS
 PH_MAX_MULTIPLICITY = 27                                                     # M3G_PH_MAX_MULTIPLICITY
 EIGH_MAX_N, EIGH_MAX_SWEEPS = 64, 30                                         # M3G_EIGH_MAX_N, M3G_EIGH_MAX_SWEEPS
@@ -225,6 +226,13 @@ SYMBOLS = {
     "m3g_remd_read": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_remd_target_view": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "m3g_mc_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "m3g_mc_init": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "m3g_mc_propose": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "m3g_mc_decide": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "m3g_mc_read": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_traj_state_bytes": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(C.c_size_t)]),
     "m3g_traj_init": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(M3GTrajParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p]),

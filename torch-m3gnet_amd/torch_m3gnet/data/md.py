@@ -96,6 +96,19 @@ class VerletGraph:
         self._graph_constants[K.LATTICE] = self.lattice32
         self._cand, self.graph, self._pending, self._state_valid = None, None, None, False
 
+    def use_atom_types(self, atom_types: torch.Tensor) -> None:
+        """Read the species from the caller's `atom_types` ([N] int64 on this device, e.g. a slice of a larger batch's array) from now
+        on, through its pointer at every evaluation: a caller that PERMUTES the species in place between evaluations (swap Monte
+        Carlo) changes what the engine sees without touching any list -- the lists depend on the positions only.  The values must stay
+        a permutation of the atomic numbers given at construction (the range check made there is kept).  Call before the first
+        `step` / `update`."""
+        if atom_types.shape != (self.N,) or atom_types.dtype != torch.long or atom_types.device != self.device or not atom_types.is_contiguous():
+            raise ValueError(f"atom_types must be a contiguous [{self.N}] int64 tensor on {self.device}")
+        if self._md is not None or self.graph is not None:
+            raise RuntimeError("use_atom_types must be called before the first evaluation")
+        self.atom_types = atom_types
+        self._graph_constants[K.ATOM_TYPES] = atom_types
+
     # ------------------------------------------------------------------------------------------------ candidates
     def _search(self, pos: torch.Tensor) -> None:
         ei, shift, dist = neighbor_list_gpu(self.lattice, pos, self.batch, self.cutoff + self.skin, host_lattice=self._host_lattice)
