@@ -1,6 +1,6 @@
-"""GPU: the stamped diagnostic variant of the fused reverse kernel (plan option "stamps" = 3, tools/stamp_report_fused.py) is the
-shipped kernel plus s_memtime reads: it must leave energies, forces and stresses bit-identical, and every wave that worked must have
-written non-zero phase sums."""
+"""GPU: the stamped diagnostic variants of the edge kernels (plan option "stamps": 1 forward kernel, 2 edge-MLP kernel of the reverse
+pair, 3 fused reverse kernel; tools/stamp_report*.py) are the shipped kernels plus s_memtime reads: they must leave energies, forces
+and stresses bit-identical, and every wave that worked must have written non-zero phase sums."""
 import numpy as np
 import pytest
 import torch
@@ -9,20 +9,32 @@ from helpers import fcc_cu_graph
 
 pytestmark = pytest.mark.gpu
 
+# target -> (precision, options under which the target's stamped kernel is the one that runs (resolve_step_path and the launchers:
+# 1 any precision, 2 bf16x3 and the kernel pair, 3 f16x3 and the fused kernel), waves per workgroup, phase marks the kernel passes)
+STAMPED = {
+    1: ("f16x3", {}, 12, (0, 1, 2, 3, 5, 6, 7, 8, 10, 11)),   # k_edge_block_mfma: marks 0, 1, 6, 11 + {0, 1, 3} past 2 and 7 per MLP
+    2: ("bf16x3", {"rev_kernel": 0}, 12, (1, 2, 3, 4, 5, 6, 7)),   # k_edge_rev_edge_mlp
+    3: ("f16x3", {}, 8, tuple(range(12))),   # k_edge_rev_fused
+}
 
-def test_stamped_fused_reverse_is_bit_identical_and_writes_stamps():
+
+@pytest.mark.parametrize("target", sorted(STAMPED))
+def test_stamped_fused_reverse_is_bit_identical_and_writes_stamps(target):
     from torch_m3gnet import _lib
     from torch_m3gnet.data import MaterialGraphKey as K
     from torch_m3gnet.model.build import build_model
 
+    precision, options, waves, marks = STAMPED[target]
     torch.manual_seed(0)
     model = build_model(5.0, 4.0, 3, 3, 95, 64, 3).cuda()
-    model.engine.set_precision("f16x3")
+    eng = model.engine
+    eng.set_precision(precision)
+    for name, value in options.items():
+        eng.set_option(name, value)
     g = fcc_cu_graph(4, 4, 6).to("cuda")
     out = model(g)
     ref = {k: out[k].clone() for k in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES)}
-    eng = model.engine
-    eng.set_option("stamps", 3)
+    eng.set_option("stamps", target)
     try:
         out = model(g)
         torch.cuda.synchronize()
@@ -31,9 +43,10 @@ def test_stamped_fused_reverse_is_bit_identical_and_writes_stamps():
         buf = np.zeros(256 * 16 * 12, dtype=np.uint64)
         _lib.check(eng.lib.m3g_debug_read_stamps(eng.plan, buf.ctypes.data))
         s = buf.reshape(256, 16, 12)
-        assert s[:, :8].sum() > 0 and s[:, 8:].sum() == 0   # eight waves per workgroup
-        busy = s[:, :8].sum(-1) > 0
-        assert busy.any() and (s[:, :8][busy] > 0).all()    # a wave that processed a tile passed every phase mark
+        unused = [i for i in range(12) if i not in marks]
+        assert s[:, :waves].sum() > 0 and s[:, waves:].sum() == 0 and s[:, :, unused].sum() == 0
+        busy = s[:, :waves].sum(-1) > 0
+        assert busy.any() and (s[:, :waves][busy][:, list(marks)] > 0).all()    # a wave that processed a tile passed every phase mark
     finally:
         eng.set_option("stamps", 0)
     out = model(g)

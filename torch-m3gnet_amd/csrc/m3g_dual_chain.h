@@ -111,7 +111,7 @@ __device__ __forceinline__ void chain_h_blocks(DualA<KS> cur, const HalfB<KS>& b
     DualA<KS> nxt = cur;
     if constexpr (ob + 1 < OB) nxt = fetch.template operator()<ob + 1>();
     sched_fence();
-    f32x4 t = {0.f, 0.f, 0.f, 0.f};
+    f32x4 t = zero4();
     static_for<KS>([&]<int s>() {
       t = mfma_f16(cur.h[s], b.hi[s], t);
       t = mfma_f16(cur.h[s], b.lo[s], t);

@@ -307,6 +307,16 @@ struct Stamps {
   __device__ __forceinline__ void mark() {
     if (ON) { unsigned long long t = stamp_now(); sum[I] += t - last; last = t; }
   }
+  // end of the kernel: every wave's sums to its slot of the debug buffer, [256 workgroups][16 wave slots][12]; ACCUMULATE: summed over
+  // the launches since the option was set
+  template <bool ACCUMULATE>
+  __device__ __forceinline__ void store(unsigned long long* stamps, int lane) const {
+    if (ON && lane == 0) {
+      const int wave = threadIdx.x >> 6;
+      unsigned long long* dst = stamps + ((size_t)blockIdx.x * 16 + wave) * 12;
+      for (int i = 0; i < 12; ++i) dst[i] = ACCUMULATE ? dst[i] + sum[i] : sum[i];
+    }
+  }
 };
 
 // ---- kernel argument blocks ----------------------------------------------------------------------------------------
@@ -399,6 +409,57 @@ __device__ __forceinline__ void gather_tables(const float* __restrict__ TA, cons
   static_for<8>([&]<int ob>() { p1[ob] = *(const f32x4*)(ta + ob * 16) + *(const f32x4*)(tb + ob * 16); });
 }
 
+// ---- reverse-side idioms shared by the fused (m3g_edge_mfma.hip), fp32 (m3g_edge_rev_f32.hip) and split-tile
+// (m3g_edge_split_rev.h) reverse kernels: one row block of a lane at a time, the loops over row blocks stay with the callers ----
+// Reverse of a conv GatedMLP's output  out = SiLU(p2d) sg(p2g) s_lin, s_lin = W_l h, for ONE row block: d2d / d2g arrive as the
+// layer-2 pre-activations and leave as dL/dp2d / dL/dp2g, du = dL/d(out), sl = the block's s_lin, wl4 = the block's four plain W_l
+// rows of this lane ([4][4]); dL/dh is accumulated into dhv.  Value pairs on packed fp32 instructions (silu_pair).  The caller pins dhv
+// after each row block (see mlp_reverse_mfma).  (mlp_reverse_f32 spells the same body out: through this function four of its kernels
+// pack one more pair of additions -- profiles/edge_idioms.txt.)
+__device__ __forceinline__ void gated_out_reverse(f32x4& d2d, f32x4& d2g, const f32x4& d_upd, const f32x4& sl, const float* wl4, f32x4& dhv) {
+  static_for<2>([&]<int k>() {
+    const f32x2 p2d = {d2d[2 * k], d2d[2 * k + 1]}, p2g = {d2g[2 * k], d2g[2 * k + 1]};
+    const f32x2 du = {d_upd[2 * k], d_upd[2 * k + 1]}, s_lin = {sl[2 * k], sl[2 * k + 1]};
+    f32x2 sd, dsd;
+    silu_pair(p2d, sd, dsd);
+    const f32x2 sg = sigmoid_pair(p2g);
+    const f32x2 a_g = du * sg;            // dL/d(out) sg(p2g)
+    const f32x2 d_s = a_g * sd;           // dL/d(s_lin)
+    const f32x2 d_o = a_g * s_lin;
+    const f32x2 dd = d_o * dsd;           // dL/d(p2d)
+    const f32x2 dgt = (d_s * s_lin) * (1.f - sg);   // dL/d(p2g)
+    const f32x4 w0 = *(const f32x4*)(wl4 + (2 * k) * 4), w1 = *(const f32x4*)(wl4 + (2 * k + 1) * 4);
+    f32x2 h01 = {dhv[0], dhv[1]}, h23 = {dhv[2], dhv[3]};
+    h01 += f32x2{w0[0], w0[1]} * d_s[0]; h23 += f32x2{w0[2], w0[3]} * d_s[0];
+    h01 += f32x2{w1[0], w1[1]} * d_s[1]; h23 += f32x2{w1[2], w1[3]} * d_s[1];
+    dhv[0] = h01[0]; dhv[1] = h01[1]; dhv[2] = h23[0]; dhv[3] = h23[1];
+    d2d[2 * k] = dd[0]; d2d[2 * k + 1] = dd[1];
+    d2g[2 * k] = dgt[0]; d2g[2 * k + 1] = dgt[1];
+  });
+}
+
+// d msg[e] = dx_new[centre(e)]: dL/d(output) of the node-message MLP (nn/conv.py:77-89), this lane's four row blocks
+__device__ __forceinline__ void load_dmsg(const float* __restrict__ dx_new, int64_t ci, int qd, f32x4 (&dmsg)[4]) {
+  const float* xrow = dx_new + ci * kDP + 4 * qd;
+  static_for<4>([&]<int blk>() { dmsg[blk] = *(const f32x4*)(xrow + blk * 16); });
+}
+// dL/d e2 = what flows in from later blocks (the tile image at de_tile, unless nothing does: the last block) + the node MLP's contribution
+__device__ __forceinline__ void de2_from(bool de_is_zero, const float* de_tile, const f32x4 (&contrib)[4], f32x4 (&de)[4]) {
+  if (de_is_zero) {
+    static_for<4>([&]<int blk>() { de[blk] = contrib[blk]; });
+  } else {
+    static_for<4>([&]<int blk>() { de[blk] = load_tile4(de_tile + blk * 256) + contrib[blk]; });
+  }
+}
+// dL/d e1 = dL/d e2 + the edge MLP's contribution, stored for the block before (STORE = false in block 0: e0 has no edge-feature input)
+template <bool STORE>
+__device__ __forceinline__ void de1_from(float* de_tile, const f32x4 (&contrib)[4], f32x4 (&de)[4]) {
+  static_for<4>([&]<int blk>() {
+    de[blk] += contrib[blk];
+    if (STORE) *(f32x4*)(de_tile + blk * 256) = de[blk];
+  });
+}
+
 struct RevArgs {
   int64_t E, tiles;
   const float* img;     // reverse image of this kernel's MLP (edge image also carries the three-body images)
@@ -456,6 +517,25 @@ inline int grid_for_tiles(int64_t tiles, int /*waves*/ = kWaves) {
 
 inline int tb_steps_for(int C) { return (C + 3) / 4; }
 inline int64_t tiles_for(int64_t E) { return (E + kTileEdges - 1) / kTileEdges; }
+
+// Kernel argument blocks as every edge launcher fills them for block b; a launcher then sets, by name, the few fields its kernel adds
+// (everything not listed here is zero / nullptr, w_inv = 1)
+inline FwdArgs fwd_args(const Topo& t, const Work& w, int b, const float* img) {
+  FwdArgs a{};
+  a.E = t.E; a.tiles = tiles_for(t.E); a.img = img;
+  a.src = t.src; a.dst = t.dst; a.h = w.h; a.m = w.m[b]; a.TA = w.TAb[b]; a.TB = w.TBb[b]; a.act_id = t.act_id;
+  a.e_in = w.e_blk[b]; a.e_out = w.e_blk[b + 1]; a.seg_head = w.seg_head; a.seg_first = w.seg_first; a.w_inv = 1.f;
+  return a;
+}
+// dh_slice: the launch's slice of Work::dh_parts
+inline RevArgs rev_args(const Topo& t, const Work& w, int b, const float* img, const float* dx_new, bool de_is_zero, int dh_slice) {
+  RevArgs a{};
+  a.E = t.E; a.tiles = tiles_for(t.E); a.img = img;
+  a.src = t.src; a.dst = t.dst; a.h = w.h; a.m = w.m[b]; a.dx_new = dx_new; a.act_id = t.act_id;
+  a.de_soa = w.de_soa; a.de_is_zero = de_is_zero ? 1 : 0; a.dm = w.dm; a.dh = w.dh_parts + (size_t)dh_slice * t.E * kRP; a.dp1 = w.dp1;
+  a.w_inv = 1.f;
+  return a;
+}
 
 #define M3G_TBS_SWITCH(C_, CALL)                     \
   switch (tb_steps_for(C_)) {                        \

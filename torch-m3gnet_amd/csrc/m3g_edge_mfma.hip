@@ -63,13 +63,7 @@ __device__ __forceinline__ void mlp_preacts(const float* lds, int w1c, int w2d, 
   if (KEEP_P1) {
     // reverse pass: p1 is only needed again as SiLU'(p1) -- leave that in p1 (one sigmoid evaluation for both)
     f32x4 hid[8];
-    static_for<8>([&]<int ob>() {
-      static_for<4>([&]<int r>() {
-        const float p = p1[ob][r], sg = fsigmoid(p);
-        hid[ob][r] = p * sg;
-        p1[ob][r] = sg * (1.f + p * (1.f - sg));
-      });
-    });
+    static_for<8>([&]<int ob>() { silu_keep_derivative(p1[ob], hid[ob]); });
     chain_p<PREC, 4, 2, 0, 0>(lds + w2d, hid, p2, lane, w_inv);
     chain_p<PREC, 4, 2, 4, 4>(lds + w2g, hid, p2, lane, w_inv);
   } else {
@@ -100,17 +94,7 @@ __device__ __forceinline__ void mlp_forward_mfma(const float* lds, const MfmaMlp
   st.template mark<S0 + 1>();  // both layers
   static_for<4>([&]<int ob>() {
     out[ob] = mfma16(lds[L.wl + ob * 64 + lane], hb, zero4());
-    // the f16x3 and fp32 kernels evaluate the gate on value PAIRS (packed fp32 instructions; fp32 forward, round 4: 1,218 -> 1,038
-    // vector instructions per tile, no spills at its 128-register budget any more, -2 % same-box)
-    if constexpr (PREC == kPrecF16x3 || PREC == kPrecF32) {
-      static_for<2>([&]<int k>() {
-        const f32x2 v = gated_pair(f32x2{p2[ob][2 * k], p2[ob][2 * k + 1]}, f32x2{p2[4 + ob][2 * k], p2[4 + ob][2 * k + 1]}) *
-                        f32x2{out[ob][2 * k], out[ob][2 * k + 1]};
-        out[ob][2 * k] = v[0]; out[ob][2 * k + 1] = v[1];
-      });
-    } else {
-      static_for<4>([&]<int r>() { out[ob][r] = fgated(p2[ob][r], p2[4 + ob][r]) * out[ob][r]; });
-    }
+    mul_gated<PREC == kPrecF16x3 || PREC == kPrecF32>(out[ob], p2[ob], p2[4 + ob]);   // (those two modes gate on value pairs)
   });
   st.template mark<S0 + 3>();  // gating
 }
@@ -172,16 +156,7 @@ __global__ void __launch_bounds__(64 * fwd_waves<PREC>()) k_edge_block_mfma(FwdA
     {  // three-body gated update (nn/interaction.py:220-221)
       f32x4 p[8];
       tb_preact_p<PREC, TBS>(lds + L.tb, tbin, p, lv);
-      if constexpr (PREC == kPrecF16x3 || PREC == kPrecF32) {
-        static_for<4>([&]<int blk>() {
-          static_for<2>([&]<int k>() {
-            const f32x2 v = gated_pair(f32x2{p[blk][2 * k], p[blk][2 * k + 1]}, f32x2{p[4 + blk][2 * k], p[4 + blk][2 * k + 1]});
-            x[blk][2 * k] += v[0]; x[blk][2 * k + 1] += v[1];
-          });
-        });
-      } else {
-        static_for<4>([&]<int blk>() { static_for<4>([&]<int r>() { x[blk][r] += fgated(p[blk][r], p[4 + blk][r]); }); });
-      }
+      static_for<4>([&]<int blk>() { add_gated<PREC == kPrecF16x3 || PREC == kPrecF32>(x[blk], p[blk], p[4 + blk]); });
     }
     st.template mark<1>();  // three-body MLP
     f32x4 out[4];
@@ -207,11 +182,7 @@ __global__ void __launch_bounds__(64 * fwd_waves<PREC>()) k_edge_block_mfma(FwdA
     cj_i = ncj;
     arow_i = narow;
   }
-  if (ST && lane == 0) {
-    const int wave = threadIdx.x >> 6;
-    unsigned long long* dst = a.stamps + ((size_t)blockIdx.x * 16 + wave) * 12;   // [256 workgroups][16 wave slots][12]
-    for (int i = 0; i < 12; ++i) dst[i] = st.sum[i];
-  }
+  st.template store<false>(a.stamps, lane);
 }
 
 // ---------------------------------------------------------------------------------------------- reverse
@@ -235,13 +206,7 @@ __device__ __forceinline__ void mlp_reverse_mfma(const float* lds, const MfmaMlp
     bias_step<4, 0>(lds + L.b2, d2, lane);
     bias_step<4, 4>(lds + L.b2 + 4 * 64, d2, lane);
     f32x4 hid[8];
-    static_for<8>([&]<int ob>() {
-      static_for<4>([&]<int r>() {
-        const float p = p1[ob][r], sg = fsigmoid(p);
-        hid[ob][r] = p * sg;
-        p1[ob][r] = sg * (1.f + p * (1.f - sg));
-      });
-    });
+    static_for<8>([&]<int ob>() { silu_keep_derivative(p1[ob], hid[ob]); });
     chain_p<PREC, 4, 2, 0, 0>(lds + L.w2d, hid, d2, lane, a.w_inv);
     chain_p<PREC, 4, 2, 4, 4>(lds + L.w2g, hid, d2, lane, a.w_inv);
   } else {
@@ -312,11 +277,8 @@ __global__ void __launch_bounds__(64 * kWavesRev) k_edge_rev_node_mlp(RevArgs a,
     f32x4 contrib[4];
     {
       f32x4 dmsg[4], x[4];
-      const float* xrow = a.dx_new + ci * kDP + 4 * qd;
-      static_for<4>([&]<int blk>() {
-        dmsg[blk] = *(const f32x4*)(xrow + blk * 16);
-        if (!SAVED) x[blk] = *(const f32x4*)(e_tile + blk * 256);     // e2: the node MLP's input
-      });
+      load_dmsg(a.dx_new, ci, qd, dmsg);
+      if (!SAVED) static_for<4>([&]<int blk>() { x[blk] = *(const f32x4*)(e_tile + blk * 256); });     // e2: the node MLP's input
       Stamps<false> st0;
       mlp_reverse_mfma<false, PREC, SAVED>(lds, L.mlp, 1, a, edge, tile, ci, cj, hv, x, dmsg, contrib, dhv, lv, st0);
     }
@@ -368,7 +330,7 @@ __global__ void __launch_bounds__(64 * kWavesRev) k_edge_rev_edge_mlp(RevArgs a,
         f32x4 p[8];
         static_for<4>([&]<int blk>() { x[blk] = *(const f32x4*)(e_tile + blk * 256); });
         tb_preact<TBS>(lds + L.tb, mb, p, lv);
-        static_for<4>([&]<int blk>() { static_for<4>([&]<int r>() { x[blk][r] += fgated(p[blk][r], p[4 + blk][r]); }); });
+        static_for<4>([&]<int blk>() { add_gated<false>(x[blk], p[blk], p[4 + blk]); });
       }
       st.template mark<1>();   // tile loads + three-body recompute
       // dL/d e2 = what flows in from later blocks + the node MLP's contribution (both loaded here, at the tile start)
@@ -404,11 +366,7 @@ __global__ void __launch_bounds__(64 * kWavesRev) k_edge_rev_edge_mlp(RevArgs a,
     ci_i = nci;
     cj_i = ncj;
   }
-  if (ST && lane == 0) {
-    const int wave = threadIdx.x >> 6;
-    unsigned long long* dst = a.stamps + ((size_t)blockIdx.x * 16 + wave) * 12;
-    for (int i = 0; i < 12; ++i) dst[i] = st.sum[i];
-  }
+  st.template store<false>(a.stamps, lane);
 }
 
 // ---------------------------------------------------------------------------------------------- fused reverse
@@ -442,13 +400,7 @@ __device__ __forceinline__ void mlp_preacts_dual(const float* lds, const MfmaMlp
   bias_step<4, 4>(lds + L.b2 + 4 * 64, p2, lane);
   if (KEEP_P1) {
     f32x4 hid[8];
-    static_for<8>([&]<int ob>() {
-      static_for<4>([&]<int r>() {
-        const float p = p1[ob][r], sg = fsigmoid(p);
-        hid[ob][r] = p * sg;
-        p1[ob][r] = sg * (1.f + p * (1.f - sg));
-      });
-    });
+    static_for<8>([&]<int ob>() { silu_keep_derivative(p1[ob], hid[ob]); });
     chain_dual<4, 2, 64, 0, 0>(lds + L.w2d, hid, p2, lane);
     chain_dual<4, 2, 64, 4, 4>(lds + L.w2g, hid, p2, lane);
   } else {
@@ -501,27 +453,7 @@ __device__ __forceinline__ void mlp_reverse_dual(const float* lds, const MfmaMlp
   const float hb_sel = qd == 0 ? hv[0] : qd == 1 ? hv[1] : qd == 2 ? hv[2] : hv[3];
   static_for<4>([&]<int ob>() {
     const f32x4 sl = mfma16(lds[L.wld + ob * 64 + lane], hb_sel, zero4());
-    // value pairs on packed fp32 instructions (silu_pair): out = SiLU(p2d) sg(p2g) s_lin
-    static_for<2>([&]<int k>() {
-      const f32x2 p2d = {d2[ob][2 * k], d2[ob][2 * k + 1]}, p2g = {d2[4 + ob][2 * k], d2[4 + ob][2 * k + 1]};
-      const f32x2 du = {d_upd[ob][2 * k], d_upd[ob][2 * k + 1]}, s_lin = {sl[2 * k], sl[2 * k + 1]};
-      f32x2 sd, dsd;
-      silu_pair(p2d, sd, dsd);
-      const f32x2 sg = sigmoid_pair(p2g);
-      const f32x2 a_g = du * sg;            // dL/d(out) sg(p2g)
-      const f32x2 d_s = a_g * sd;           // dL/d(s_lin)
-      const f32x2 d_o = a_g * s_lin;
-      const f32x2 dd = d_o * dsd;           // dL/d(p2d)
-      const f32x2 dgt = (d_s * s_lin) * (1.f - sg);   // dL/d(p2g)
-      const f32x4 w0 = *(const f32x4*)(lds + L.wl + (ob * 16 + 4 * qd + 2 * k) * 4);
-      const f32x4 w1 = *(const f32x4*)(lds + L.wl + (ob * 16 + 4 * qd + 2 * k + 1) * 4);
-      f32x2 h01 = {dhv[0], dhv[1]}, h23 = {dhv[2], dhv[3]};
-      h01 += f32x2{w0[0], w0[1]} * d_s[0]; h23 += f32x2{w0[2], w0[3]} * d_s[0];
-      h01 += f32x2{w1[0], w1[1]} * d_s[1]; h23 += f32x2{w1[2], w1[3]} * d_s[1];
-      dhv[0] = h01[0]; dhv[1] = h01[1]; dhv[2] = h23[0]; dhv[3] = h23[1];
-      d2[ob][2 * k] = dd[0]; d2[ob][2 * k + 1] = dd[1];
-      d2[4 + ob][2 * k] = dgt[0]; d2[4 + ob][2 * k + 1] = dgt[1];
-    });
+    gated_out_reverse(d2[ob], d2[4 + ob], d_upd[ob], sl, lds + L.wl + (ob * 16 + 4 * qd) * 4, dhv);
     asm volatile("" : "+v"(dhv[0]), "+v"(dhv[1]), "+v"(dhv[2]), "+v"(dhv[3]));   // see mlp_reverse_mfma
   });
   zero(contrib);
@@ -612,18 +544,12 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_fused(RevArgs a, MfmaRe
       f32x4 x2[4];
       const float* e2_tile = a.e2_tile + tile * kTileFloats + lane * 4;
       static_for<4>([&]<int blk>() { x2[blk] = load_tile4(e2_tile + blk * 256); });
-      // d msg[e] = dx_new[centre(e)]
       f32x4 dmsg[4];
-      const float* xrow = a.dx_new + ci * kDP + 4 * qd;
-      static_for<4>([&]<int blk>() { dmsg[blk] = *(const f32x4*)(xrow + blk * 16); });
+      load_dmsg(a.dx_new, ci, qd, dmsg);
       mlp_reverse_dual<NEED_DP1, 1, PREC, ST, 0>(lds, L.mlp[1], a, edge, tile, ci, cj, sk, hv, x2, dmsg, contrib, dhv, lv, st, dp1_inv);
     }
     // dL/d e2 = what flows in from later blocks + the node MLP's contribution
-    if (a.de_is_zero) {
-      static_for<4>([&]<int blk>() { de[blk] = contrib[blk]; });
-    } else {
-      static_for<4>([&]<int blk>() { de[blk] = load_tile4(de_tile + blk * 256) + contrib[blk]; });
-    }
+    de2_from(a.de_is_zero, de_tile, contrib, de);
     // the opaque copy also pins the order: without it the scheduler hoists the e1 computation above the node phase
     asm volatile("" : "+v"(lv));
     sched_fence();
@@ -639,21 +565,13 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_fused(RevArgs a, MfmaRe
     {  // e1 = e_in + three-body gated update (the edge MLP's input)
       f32x4 p[8];
       tb_preact_p<PREC, TBS>(lds + L.tb, tbin, p, lv);
-      static_for<4>([&]<int blk>() {
-        static_for<2>([&]<int k>() {   // value pairs on packed fp32 instructions (gated_pair)
-          const f32x2 v = gated_pair(f32x2{p[blk][2 * k], p[blk][2 * k + 1]}, f32x2{p[4 + blk][2 * k], p[4 + blk][2 * k + 1]});
-          x[blk][2 * k] += v[0]; x[blk][2 * k + 1] += v[1];
-        });
-      });
+      static_for<4>([&]<int blk>() { add_gated<true>(x[blk], p[blk], p[4 + blk]); });
     }
     st.template mark<5>();   // dL/de and e images arrived, e1 recomputed (three-body MLP)
     mlp_reverse_dual<NEED_DP1, 0, PREC, ST, 6>(lds, L.mlp[0], a, edge, tile, ci, cj, sk, hv, x, de, contrib, dhv, lv, st, dp1_inv);
     // the row's four inverse scales in one 16-byte store per edge (f16x3 mode; 256 contiguous bytes per tile)
     if (NEED_DP1 && PREC == kPrecF16x3 && qd == 0 && edge < a.E) *(f32x4*)(a.dp1_scale + edge * 4) = dp1_inv;
-    static_for<4>([&]<int blk>() {  // dL/d e1 = dL/d e2 + contribution
-      de[blk] += contrib[blk];
-      if (!FIRST) *(f32x4*)(de_tile + blk * 256) = de[blk];
-    });
+    de1_from<!FIRST>(de_tile, contrib, de);
     if (FIRST) {
       // edge embedding, reverse (nothing upstream of e0 but the radial basis): dL/dh += W_adj^T (dL/de0 * SiLU'(W_adj h))
       const float hb = a.h[ec * kRP + qd];
@@ -670,18 +588,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_fused(RevArgs a, MfmaRe
     // three-body gated update, reverse
     f32x4 d8[8];
     tb_preact_p<PREC, TBS>(lds + L.tb, tbin, d8, lv);
-    static_for<4>([&]<int blk>() {
-      static_for<2>([&]<int k>() {   // value pairs on packed fp32 instructions (silu_pair)
-        const f32x2 p = {d8[blk][2 * k], d8[blk][2 * k + 1]}, g = {d8[4 + blk][2 * k], d8[4 + blk][2 * k + 1]};
-        const f32x2 dv = {de[blk][2 * k], de[blk][2 * k + 1]};
-        f32x2 sd, dsd, sg;
-        silu_pair(p, sd, dsd);
-        sg = sigmoid_pair(g);
-        const f32x2 a_g = dv * sg, dd = a_g * dsd, dgt = (a_g * sd) * (1.f - sg);
-        d8[blk][2 * k] = dd[0]; d8[blk][2 * k + 1] = dd[1];
-        d8[4 + blk][2 * k] = dgt[0]; d8[4 + blk][2 * k + 1] = dgt[1];
-      });
-    });
+    static_for<4>([&]<int blk>() { gated_reverse(d8[blk], d8[4 + blk], de[blk]); });
     f32x4 dmv[1];
     zero(dmv);
     chain_p<PREC, 1, 4>(lds + L.tbT, d8, dmv, lv, a.w_inv);
@@ -693,11 +600,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_fused(RevArgs a, MfmaRe
     cj_i = ncj;
     arow_i = narow;
   }
-  if (ST && lane == 0) {
-    const int wave = threadIdx.x >> 6;
-    unsigned long long* dst = a.stamps + ((size_t)blockIdx.x * 16 + wave) * 12;
-    for (int i = 0; i < 12; ++i) dst[i] += st.sum[i];   // summed over the launches since the option was set (a slot per wave)
-  }
+  st.template store<true>(a.stamps, lane);   // (a slot per wave)
 }
 
 // ---------------------------------------------------------------------------------------------- helpers
@@ -798,9 +701,11 @@ void launch_edge_block_mfma(const m3g_plan* plan, const StepPath& p, const Const
   const MfmaFwdLayout L = mfma_fwd_layout();
   const int prec = plan->opt.precision;
   if (tiles > 0) {
-    FwdArgs a{t.E, tiles, plan->d_mfma_fwd[prec] + (size_t)b * L.total, t.src, t.dst, w.h, w.m[b], w.TAb[b], w.TBb[b], t.act_id,
-              w.e_blk[b], w.e_blk[b + 1], w.seg_head, w.seg_first, plan->d_stamps, p.saved_acts >= 1 ? w.p1_blk[b] : nullptr,
-              p.saved_acts == 2 ? w.p2_blk[b] : nullptr, prec == kPrecF16x3 ? plan->w_scale_inv : 1.f};
+    FwdArgs a = fwd_args(t, w, b, plan->d_mfma_fwd[prec] + (size_t)b * L.total);
+    a.stamps = plan->d_stamps;
+    if (p.saved_acts >= 1) a.p1_out = w.p1_blk[b];
+    if (p.saved_acts == 2) a.p2_out = w.p2_blk[b];
+    if (prec == kPrecF16x3) a.w_inv = plan->w_scale_inv;
     dim3 grid(grid_for_tiles(tiles));
     const bool first = b == 0 && p.fused_rev;   // the fused reverse kernel recomputes e0 as well: no embedded-edge image at all
     const int save = p.fwd_save;   // fp32 mode only
@@ -834,9 +739,10 @@ void launch_edge_rev_node_mlp(const m3g_plan* plan, const StepPath& p, const Con
   const int prec = plan->opt.precision;
   const float* img_n = plan->d_mfma_rev[prec] + (size_t)b * L.per_block + L.total_e;
   const bool saved = p.saved_acts >= 1;
-  RevArgs an{t.E, tiles, img_n, t.src, t.dst, w.h, w.m[b], dx_new, t.act_id, w.TAb[b], w.TBb[b], w.e_blk[b + 1], nullptr, w.de_soa, w.dcn, 0, w.dm,
-             w.dh_parts + (size_t)(2 * b + 1) * t.E * kRP, w.dp1, nullptr, nullptr, nullptr, saved ? w.p1_blk[b] : nullptr, nullptr,
-             prec == kPrecF16x3 ? plan->w_scale_inv : 1.f};
+  RevArgs an = rev_args(t, w, b, img_n, dx_new, false, 2 * b + 1);
+  an.TA = w.TAb[b]; an.TB = w.TBb[b]; an.e_tile = w.e_blk[b + 1]; an.dcn = w.dcn;
+  if (saved) an.p1 = w.p1_blk[b];
+  if (prec == kPrecF16x3) an.w_inv = plan->w_scale_inv;
   if (saved) { M3G_PREC_SWITCH(prec, hipLaunchKernelGGL((k_edge_rev_node_mlp<PREC, true>), dim3(grid_for_tiles(tiles)), dim3(64 * kWavesRev), 0, s, an, L)); }
   else { M3G_PREC_SWITCH(prec, hipLaunchKernelGGL((k_edge_rev_node_mlp<PREC, false>), dim3(grid_for_tiles(tiles)), dim3(64 * kWavesRev), 0, s, an, L)); }
 }
@@ -849,9 +755,10 @@ void launch_edge_rev_edge_mlp(const m3g_plan* plan, const StepPath& p, const Con
   const int prec = plan->opt.precision;
   const bool saved = p.saved_acts >= 1;
   const float* img_e = plan->d_mfma_rev[prec] + (size_t)b * L.per_block;
-  RevArgs ae{t.E, tiles, img_e, t.src, t.dst, w.h, w.m[b], dx_new, t.act_id, w.TAb[b], w.TBb[b], w.e_blk[b], nullptr, w.de_soa, w.dcn,
-             de_is_zero ? 1 : 0, w.dm, w.dh_parts + (size_t)(2 * b) * t.E * kRP, w.dp1, plan->d_stamps, nullptr, nullptr,
-             saved ? w.p1_blk[b] : nullptr, nullptr, prec == kPrecF16x3 ? plan->w_scale_inv : 1.f};
+  RevArgs ae = rev_args(t, w, b, img_e, dx_new, de_is_zero, 2 * b);
+  ae.TA = w.TAb[b]; ae.TB = w.TBb[b]; ae.e_tile = w.e_blk[b]; ae.dcn = w.dcn; ae.stamps = plan->d_stamps;
+  if (saved) ae.p1 = w.p1_blk[b];
+  if (prec == kPrecF16x3) ae.w_inv = plan->w_scale_inv;
   dim3 grid(grid_for_tiles(tiles)), block(64 * kWavesRev);
   if (plan->d_stamps && plan->opt.stamp_target == 2 && tb_steps_for(c.C) == 3 && prec == kPrecBf16x3) {  // diagnostic build
     hipLaunchKernelGGL((k_edge_rev_edge_mlp<3, true>), grid, block, 0, s, ae, L);
@@ -868,9 +775,10 @@ void launch_edge_rev_fused(const m3g_plan* plan, const Consts& c, const Topo& t,
   const MfmaRevFusedLayout L = mfma_rev_fused_layout();
   const bool f16 = plan->opt.precision == kPrecF16x3;
   const float* img = (f16 ? plan->d_mfma_revf_h : plan->d_mfma_revf) + (size_t)b * L.total;
-  RevArgs ar{t.E, tiles, img, t.src, t.dst, w.h, w.m[b], dx_new, t.act_id, w.TAb[b], w.TBb[b], w.e_blk[b], w.e_blk[b + 1], w.de_soa, nullptr,
-             de_is_zero ? 1 : 0, w.dm, w.dh_parts + (size_t)b * t.E * kRP, w.dp1, plan->d_stamps, w.seg_head, w.seg_first, nullptr, nullptr,
-             f16 ? plan->w_scale_inv : 1.f, dp1_scale_of(w.dp1, t.E)};
+  RevArgs ar = rev_args(t, w, b, img, dx_new, de_is_zero, b);
+  ar.TA = w.TAb[b]; ar.TB = w.TBb[b]; ar.e_tile = w.e_blk[b]; ar.e2_tile = w.e_blk[b + 1]; ar.stamps = plan->d_stamps;
+  ar.seg_head = w.seg_head; ar.seg_first = w.seg_first; ar.dp1_scale = dp1_scale_of(w.dp1, t.E);
+  if (f16) ar.w_inv = plan->w_scale_inv;
   constexpr int WV = kWavesRevFused;
   dim3 grid(grid_for_tiles(tiles)), block(64 * WV);
   if (plan->d_stamps && plan->opt.stamp_target == 3 && f16 && tb_steps_for(c.C) == 3) {   // diagnostic build (tools/stamp_report_fused.py)

@@ -62,13 +62,7 @@ __device__ __forceinline__ void mlp_reverse_f32(const float* lds, const MfmaMlpR
     bias_step<4, 4>(lds + L.b2 + 4 * 64, d2, lane);
     static_for<2>([&]<int half>() {   // 0: dense branch (p1[0..3] -> d2[0..3]), 1: gate branch
       f32x4 hid[4];
-      static_for<4>([&]<int ob>() {
-        static_for<4>([&]<int r>() {
-          const float p = p1[4 * half + ob][r], sg = fsigmoid(p);
-          hid[ob][r] = p * sg;
-          p1[4 * half + ob][r] = sg * (1.f + p * (1.f - sg));   // p1 is only needed again as SiLU'(p1)
-        });
-      });
+      static_for<4>([&]<int ob>() { silu_keep_derivative(p1[4 * half + ob], hid[ob]); });   // p1 is only needed again as SiLU'(p1)
       chain_dual32<4, 0, 4 * half>(lds + (half == 0 ? L.w2d : L.w2g), hid, d2, lane);
       sched_fence();
     });
@@ -178,20 +172,15 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_f32(RevArgs a, MfmaRevF
     static_for<TBS>([&]<int s>() { mb[s] = arow >= 0 ? a.m[(int64_t)arow * kCP + 4 * s + qd] : 0.f; });
     f32x4 de[4], contrib[4], d2e[8];
     {
-      // node-message MLP (nn/conv.py:77-89): d msg[e] = dx_new[centre(e)]
+      // node-message MLP (nn/conv.py:77-89)
       f32x4 dmsg[4];
-      const float* xrow = a.dx_new + ci * kDP + 4 * qd;
-      static_for<4>([&]<int blk>() { dmsg[blk] = *(const f32x4*)(xrow + blk * 16); });
+      load_dmsg(a.dx_new, ci, qd, dmsg);
       f32x4 d2n[8];
       if constexpr (SAVED_P2) load_p2(a, tile, 1, d2n);
       mlp_reverse_f32<NEED_DP1, 1, SAVED_P2>(lds, L.mlp[1], a, edge, drow, tile, ci, sk, hv, dmsg, contrib, dhv, lv, d2n);
     }
     // dL/d e2 = what flows in from later blocks + the node MLP's contribution
-    if (a.de_is_zero) {
-      static_for<4>([&]<int blk>() { de[blk] = contrib[blk]; });
-    } else {
-      static_for<4>([&]<int blk>() { de[blk] = load_tile4(de_tile + blk * 256) + contrib[blk]; });
-    }
+    de2_from(a.de_is_zero, de_tile, contrib, de);
     asm volatile("" : "+v"(lv));
     sched_fence();
     // edge-update MLP (nn/conv.py:68-75)
@@ -199,10 +188,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_f32(RevArgs a, MfmaRevF
     // wave already covers that latency)
     if constexpr (SAVED_P2) load_p2(a, tile, 0, d2e);
     mlp_reverse_f32<NEED_DP1, 0, SAVED_P2>(lds, L.mlp[0], a, edge, drow, tile, ci, sk, hv, de, contrib, dhv, lv, d2e);
-    static_for<4>([&]<int blk>() {  // dL/d e1 = dL/d e2 + contribution
-      de[blk] += contrib[blk];
-      if (!FIRST) *(f32x4*)(de_tile + blk * 256) = de[blk];
-    });
+    de1_from<!FIRST>(de_tile, contrib, de);
     if (FIRST) {
       // edge embedding, reverse (nothing upstream of e0 but the radial basis): dL/dh += W_adj^T (dL/de0 * SiLU'(W_adj h))
       const float hb = qd == 0 ? hv[0] : qd == 1 ? hv[1] : qd == 2 ? hv[2] : hv[3];
@@ -219,17 +205,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_edge_rev_f32(RevArgs a, MfmaRevF
     // three-body gated update, reverse (nn/interaction.py:220-221)
     f32x4 d8[8];
     tb_preact<TBS>(lds + L.tb, mb, d8, lv);
-    static_for<4>([&]<int blk>() {
-      static_for<2>([&]<int k>() {
-        f32x2 sd, dsd;
-        silu_pair(f32x2{d8[blk][2 * k], d8[blk][2 * k + 1]}, sd, dsd);
-        const f32x2 sg = sigmoid_pair(f32x2{d8[4 + blk][2 * k], d8[4 + blk][2 * k + 1]});
-        const f32x2 a_g = f32x2{de[blk][2 * k], de[blk][2 * k + 1]} * sg;
-        const f32x2 dd = a_g * dsd, dgt = (a_g * sd) * (1.f - sg);
-        d8[blk][2 * k] = dd[0]; d8[blk][2 * k + 1] = dd[1];
-        d8[4 + blk][2 * k] = dgt[0]; d8[4 + blk][2 * k + 1] = dgt[1];
-      });
-    });
+    static_for<4>([&]<int blk>() { gated_reverse(d8[blk], d8[4 + blk], de[blk]); });
     f32x4 dmv[1];
     zero(dmv);
     chain_f32<1, 8>(lds + L.tbT, d8, dmv, lv);
@@ -253,9 +229,10 @@ void launch_edge_rev_f32(const m3g_plan* plan, const StepPath& p, const Consts& 
   const MfmaRevF32Layout L = mfma_rev_f32_layout();
   static_assert(kRevF32Floats * 4 + 16 <= 160 * 1024, "fused fp32 reverse image exceeds the LDS");
   const float* img = plan->d_mfma_revf32 + (size_t)b * L.total;
-  RevArgs ar{t.E, tiles, img, t.src, t.dst, w.h, w.m[b], dx_new, t.act_id, nullptr, nullptr, nullptr, nullptr, w.de_soa, nullptr,
-             de_is_zero ? 1 : 0, w.dm, w.dh_parts + (size_t)b * t.E * kRP, w.dp1, nullptr, w.seg_head, w.seg_first, w.p1_blk[b],
-             p.saved_acts == 2 ? w.p2_blk[b] : nullptr, 1.f, nullptr, p.dp1_by_dst ? t.in_pos : nullptr, p.split_tail};
+  RevArgs ar = rev_args(t, w, b, img, dx_new, de_is_zero, b);
+  ar.seg_head = w.seg_head; ar.seg_first = w.seg_first; ar.p1 = w.p1_blk[b]; ar.split_tail = p.split_tail;
+  if (p.saved_acts == 2) ar.p2 = w.p2_blk[b];
+  if (p.dp1_by_dst) ar.in_pos = t.in_pos;
   static_assert(2 * kRevSplitGroupFloats + kRevSplitTabFloats <= kRevF32Floats, "the split tail's exchange buffers must fit in the image's LDS");
   constexpr int WV = kWavesRevF32;
   dim3 grid(grid_for_tiles(tiles, WV)), block(64 * WV);

@@ -99,10 +99,7 @@ __device__ __forceinline__ f32x4 mlp_forward_split(const FwdMlpA& A, const f32x4
     __builtin_nontemporal_store(p2g, (f32x4*)(p2_out + (4 + w) * 256));
   }
   f32x4 out = mfma16(A.wl, hb, zero4());
-  static_for<2>([&]<int k>() {
-    const f32x2 v = gated_pair(f32x2{p2d[2 * k], p2d[2 * k + 1]}, f32x2{p2g[2 * k], p2g[2 * k + 1]}) * f32x2{out[2 * k], out[2 * k + 1]};
-    out[2 * k] = v[0]; out[2 * k + 1] = v[1];
-  });
+  mul_gated<true>(out, p2d, p2g);
   return out;
 }
 
@@ -150,10 +147,7 @@ __global__ void __launch_bounds__(64 * kSplitWaves) k_edge_fwd_split(FwdArgs a, 
         pd = mfma16(a_tb[0][s], mb[s], pd);
         pg = mfma16(a_tb[1][s], mb[s], pg);
       });
-      static_for<2>([&]<int k>() {
-        const f32x2 v = gated_pair(f32x2{pd[2 * k], pd[2 * k + 1]}, f32x2{pg[2 * k], pg[2 * k + 1]});
-        xw[2 * k] += v[0]; xw[2 * k + 1] += v[1];
-      });
+      add_gated<true>(xw, pd, pg);
     }
     f32x4 x[4];
     *(f32x4*)(xs + w * 256 + lane * 4) = xw;
@@ -199,8 +193,8 @@ void launch_edge_fwd_split(const m3g_plan* plan, const StepPath& p, const Consts
   if (tiles == 0) return;
   const int save = p.fwd_save;
   const MfmaFwdLayout L = mfma_fwd_layout();
-  FwdArgs a{t.E, tiles, plan->d_mfma_fwd[kPrecF32] + (size_t)b * L.total, t.src, t.dst, w.h, w.m[b], w.TAb[b], w.TBb[b], t.act_id,
-            w.e_blk[b], w.e_blk[b + 1], w.seg_head, w.seg_first, nullptr, save == 2 ? w.p1_blk[b] : nullptr, save == 2 ? w.p2_blk[b] : nullptr, 1.f};
+  FwdArgs a = fwd_args(t, w, b, plan->d_mfma_fwd[kPrecF32] + (size_t)b * L.total);
+  if (save == 2) { a.p1_out = w.p1_blk[b]; a.p2_out = w.p2_blk[b]; }
   const dim3 grid(grid_for_split(tiles)), block(64 * kSplitWaves);
   const bool first = b == 0 && p.fused_rev;
 #define M3G_FWDS(FIRST_) \
@@ -215,9 +209,9 @@ void launch_edge_rev_split(const m3g_plan* plan, const StepPath& p, const Consts
   const int64_t tiles = tiles_for(t.E);
   if (tiles == 0) return;
   const MfmaRevF32Layout L = mfma_rev_f32_layout();
-  RevArgs ar{t.E, tiles, plan->d_mfma_revf32 + (size_t)b * L.total, t.src, t.dst, w.h, w.m[b], dx_new, t.act_id, nullptr, nullptr, nullptr, nullptr,
-             w.de_soa, nullptr, de_is_zero ? 1 : 0, w.dm, w.dh_parts + (size_t)b * t.E * kRP, w.dp1, nullptr, w.seg_head, w.seg_first, w.p1_blk[b],
-             w.p2_blk[b], 1.f, nullptr, p.dp1_by_dst ? t.in_pos : nullptr};
+  RevArgs ar = rev_args(t, w, b, plan->d_mfma_revf32 + (size_t)b * L.total, dx_new, de_is_zero, b);
+  ar.seg_head = w.seg_head; ar.seg_first = w.seg_first; ar.p1 = w.p1_blk[b]; ar.p2 = w.p2_blk[b];
+  if (p.dp1_by_dst) ar.in_pos = t.in_pos;
   const dim3 grid(grid_for_split(tiles)), block(64 * kSplitWaves);
   if (b > 0) { M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_rev_split<TBS, true>), grid, block, 0, s, ar, L)); }
   else { M3G_TBS_SWITCH(c.C, hipLaunchKernelGGL((k_edge_rev_split<TBS, false>), grid, block, 0, s, ar, L)); }

@@ -65,25 +65,7 @@ __device__ __forceinline__ f32x4 mlp_reverse_split(const RevMlpA& A, const RevAr
   f32x4 d2d = load_tile4(p2_src + w * 256), d2g = load_tile4(p2_src + (4 + w) * 256);   // saved layer-2 pre-activations
   // gating derivatives; W_l h on the matrix pipe, dL/dh on the vector ALU (as mlp_reverse_f32, for row block w)
   const f32x4 sl = mfma16(A.wld, hb_sel, zero4());
-  static_for<2>([&]<int k>() {
-    const f32x2 p2d = {d2d[2 * k], d2d[2 * k + 1]}, p2g = {d2g[2 * k], d2g[2 * k + 1]};
-    const f32x2 du = {d_upd[2 * k], d_upd[2 * k + 1]}, s_lin = {sl[2 * k], sl[2 * k + 1]};
-    f32x2 sd, dsd;
-    silu_pair(p2d, sd, dsd);
-    const f32x2 sg = sigmoid_pair(p2g);
-    const f32x2 a_g = du * sg;            // dL/d(out) sg(p2g)
-    const f32x2 d_s = a_g * sd;           // dL/d(s_lin)
-    const f32x2 d_o = a_g * s_lin;
-    const f32x2 dd = d_o * dsd;           // dL/d(p2d)
-    const f32x2 dgt = (d_s * s_lin) * (1.f - sg);   // dL/d(p2g)
-    const f32x4 w0 = *(const f32x4*)(A.wl + (2 * k) * 4), w1 = *(const f32x4*)(A.wl + (2 * k + 1) * 4);
-    f32x2 h01 = {dhv[0], dhv[1]}, h23 = {dhv[2], dhv[3]};
-    h01 += f32x2{w0[0], w0[1]} * d_s[0]; h23 += f32x2{w0[2], w0[3]} * d_s[0];
-    h01 += f32x2{w1[0], w1[1]} * d_s[1]; h23 += f32x2{w1[2], w1[3]} * d_s[1];
-    dhv[0] = h01[0]; dhv[1] = h01[1]; dhv[2] = h23[0]; dhv[3] = h23[1];
-    d2d[2 * k] = dd[0]; d2d[2 * k + 1] = dd[1];
-    d2g[2 * k] = dgt[0]; d2g[2 * k + 1] = dgt[1];
-  });
+  gated_out_reverse(d2d, d2g, d_upd, sl, A.wl, dhv);
   // dL/dp2 of all waves -> every wave (B operand of the W2^T products)
   split_publish(hs1, w, lane, d2d, d2g);
   f32x4 dp1h[2];
@@ -196,15 +178,7 @@ __device__ __forceinline__ void rev_split_run(const RevArgs& a, const MfmaRevF32
       pd = mfma16(a_tb[0][s], mb[s], pd);
       pg = mfma16(a_tb[1][s], mb[s], pg);
     });
-    static_for<2>([&]<int k>() {
-      f32x2 sd, dsd;
-      silu_pair(f32x2{pd[2 * k], pd[2 * k + 1]}, sd, dsd);
-      const f32x2 sg = sigmoid_pair(f32x2{pg[2 * k], pg[2 * k + 1]});
-      const f32x2 a_g = f32x2{de[2 * k], de[2 * k + 1]} * sg;
-      const f32x2 dd = a_g * dsd, dgt = (a_g * sd) * (1.f - sg);
-      pd[2 * k] = dd[0]; pd[2 * k + 1] = dd[1];
-      pg[2 * k] = dgt[0]; pg[2 * k + 1] = dgt[1];
-    });
+    gated_reverse(pd, pg, de);
     // dL/dm = W_tb^T d8 over the 128 rows: this wave's 32 rows (blocks w, 4 + w), partial results added in wave order below
     f32x4 dmv = zero4();
     static_for<4>([&]<int r>() { dmv = mfma16(a_tbt[0][r], pd[r], dmv); });

@@ -60,6 +60,54 @@ __device__ __forceinline__ f32x2 gated_pair(f32x2 p, f32x2 g) {
   return p * f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
 }
 
+// ---- the same activations over one accumulator block (the 4 values of a lane), the form the edge / node kernels use them in ----
+// x += SiLU(pd) sg(pg): the three-body gated update (nn/interaction.py:220-221).  PAIRS: value pairs on packed fp32 instructions
+// (the f16x3 and fp32 kernels; fp32 forward, round 4: 1,218 -> 1,038 vector instructions per tile, no spills at its 128-register
+// budget any more, -2 % same-box), else value by value
+template <bool PAIRS>
+__device__ __forceinline__ void add_gated(f32x4& x, const f32x4& pd, const f32x4& pg) {
+  if constexpr (PAIRS) {
+    static_for<2>([&]<int k>() {
+      const f32x2 v = gated_pair(f32x2{pd[2 * k], pd[2 * k + 1]}, f32x2{pg[2 * k], pg[2 * k + 1]});
+      x[2 * k] += v[0]; x[2 * k + 1] += v[1];
+    });
+  } else {
+    static_for<4>([&]<int r>() { x[r] += fgated(pd[r], pg[r]); });
+  }
+}
+// out <- SiLU(pd) sg(pg) out: a conv GatedMLP's output times W_l h (nn/conv.py:68-89)
+template <bool PAIRS>
+__device__ __forceinline__ void mul_gated(f32x4& out, const f32x4& pd, const f32x4& pg) {
+  if constexpr (PAIRS) {
+    static_for<2>([&]<int k>() {
+      const f32x2 v = gated_pair(f32x2{pd[2 * k], pd[2 * k + 1]}, f32x2{pg[2 * k], pg[2 * k + 1]}) * f32x2{out[2 * k], out[2 * k + 1]};
+      out[2 * k] = v[0]; out[2 * k + 1] = v[1];
+    });
+  } else {
+    static_for<4>([&]<int r>() { out[r] = fgated(pd[r], pg[r]) * out[r]; });
+  }
+}
+// reverse of x += SiLU(pd) sg(pg) on value pairs: pd / pg arrive as the pre-activations and leave as dL/dpd / dL/dpg, de = dL/dx
+__device__ __forceinline__ void gated_reverse(f32x4& pd, f32x4& pg, const f32x4& de) {
+  static_for<2>([&]<int k>() {
+    f32x2 sd, dsd;
+    silu_pair(f32x2{pd[2 * k], pd[2 * k + 1]}, sd, dsd);
+    const f32x2 sg = sigmoid_pair(f32x2{pg[2 * k], pg[2 * k + 1]});
+    const f32x2 a_g = f32x2{de[2 * k], de[2 * k + 1]} * sg;
+    const f32x2 dd = a_g * dsd, dgt = (a_g * sd) * (1.f - sg);
+    pd[2 * k] = dd[0]; pd[2 * k + 1] = dd[1];
+    pg[2 * k] = dgt[0]; pg[2 * k + 1] = dgt[1];
+  });
+}
+// hid = SiLU(p), p <- SiLU'(p) from one sigmoid, value by value: a layer whose pre-activations are only needed again as SiLU'
+__device__ __forceinline__ void silu_keep_derivative(f32x4& p, f32x4& hid) {
+  static_for<4>([&]<int r>() {
+    const float v = p[r], sg = fsigmoid(v);
+    hid[r] = v * sg;
+    p[r] = sg * (1.f + v * (1.f - sg));
+  });
+}
+
 // ---- the dense chains run on v_mfma_f32_16x16x32_bf16 with split operands ("bf16x3") ----------------------------
 // a = a_hi + a_lo (both bf16; the residual a - a_hi is formed exactly in fp32), a.b ~ a_hi b_hi + a_hi b_lo + a_lo b_hi,
 // accumulated in fp32: 3 MFMAs at 16x the fp32-MFMA rate.  bf16 keeps the fp32 exponent range, which the tiny gradient

@@ -265,13 +265,7 @@ __global__ void __launch_bounds__(256) k_readout_mfma(Consts c, int64_t N, const
     f32x4 p1[8], hid[8];
     static_for<8>([&]<int ob>() { p1[ob] = *(const f32x4*)(lds + ReadoutImg::b1 + ob * 16 + 4 * q); });
     chain_p<PREC, 8, 2>(lds + ReadoutImg::w1, xb, p1, lv, w_inv);
-    static_for<8>([&]<int ob>() {
-      static_for<4>([&]<int r>() {
-        const float p = p1[ob][r], sg = fsigmoid(p);
-        hid[ob][r] = p * sg;
-        p1[ob][r] = sg * (1.f + p * (1.f - sg));
-      });
-    });
+    static_for<8>([&]<int ob>() { silu_keep_derivative(p1[ob], hid[ob]); });
     // layer 2
     f32x4 p2[8];
     static_for<8>([&]<int ob>() { p2[ob] = *(const f32x4*)(lds + ReadoutImg::b2 + ob * 16 + 4 * q); });
