@@ -1,5 +1,6 @@
-// The device and C-ABI layer the five batched drivers share (m3g_relax.hip, m3g_dynamics.hip, m3g_neb.hip, m3g_phonons.hip,
-// m3g_elastic.hip).  The chunk table: the N atoms of S structures cut into chunks of <= kChunkRows atoms that never straddle a
+// The device and C-ABI layer the batched drivers share: m3g_relax.hip (FIRE), m3g_lbfgs.hip, m3g_dynamics.hip, m3g_remd.hip, m3g_mc.hip,
+// m3g_neb.hip, m3g_phonons.hip, m3g_elastic.hip and m3g_trajectory.hip.  Every state buffer is described once, by the function that
+// carves its view (chunk_view below, then the driver's own regions; see Carved), and read back through read_back.  The chunk table: the N atoms of S structures cut into chunks of <= kChunkRows atoms that never straddle a
 // structure, so a reduction over a chunk's rows (chunk_tree_reduce) followed by one over a structure's chunks in chunk order
 // (wave_chunk_sum, or a serial walk) depends on that structure's own rows only -- bitwise the same alone or in any batch.  Device
 // side: the offsets [S+1] (int64), the structure of every chunk and its first atom, and every structure's first chunk ([S] = the
@@ -22,27 +23,6 @@ constexpr int kFinalizeWaves = 4;     // structures (one wave each) per workgrou
 // chunks of a batch, at most (a bound that needs no offsets, so launch grids and buffer sizes follow from N and S alone)
 inline int64_t chunk_bound(int64_t N, int64_t S) { return (N + kChunkRows - 1) / kChunkRows + S; }
 
-// hands out the 256-byte-aligned regions of a caller's state buffer, one after the other; `total` is the size so far
-struct StateArena {
-  size_t total = 0;
-  size_t take(size_t bytes) { const size_t at = total; total += (bytes + 255) & ~size_t(255); return at; }
-};
-
-struct ChunkLayout {
-  int64_t S;
-  size_t offsets, chunk_struct, chunk_begin, first_chunk;
-};
-inline ChunkLayout chunk_layout(int64_t N, int64_t S, StateArena& arena) {
-  const int64_t C = chunk_bound(N, S);
-  ChunkLayout L{};
-  L.S = S;
-  L.offsets = arena.take(8 * (S + 1));
-  L.chunk_struct = arena.take(4 * C);
-  L.chunk_begin = arena.take(8 * C);
-  L.first_chunk = arena.take(4 * (S + 1));   // [S] = number of chunks
-  return L;
-}
-
 // The device side of the table.  Row kernels run one workgroup per chunk (a grid of chunk_bound() workgroups: those beyond the
 // table's chunk count return at once), thread t on row t of the chunk.
 struct ChunkView {
@@ -58,10 +38,28 @@ struct ChunkView {
   __device__ int chunks_begin(int64_t s) const { return first_chunk[s]; }
   __device__ int chunks_end(int64_t s) const { return first_chunk[s + 1]; }
 };
-inline ChunkView chunk_view(const ChunkLayout& L, const void* state) {
-  const char* b = (const char*)state;
-  return ChunkView{L.S, (const int64_t*)(b + L.offsets), (const int32_t*)(b + L.chunk_struct), (const int64_t*)(b + L.chunk_begin),
-                   (const int32_t*)(b + L.first_chunk)};
+// carves the table from a driver's state: the first four regions of every state buffer
+inline ChunkView chunk_view(int64_t N, int64_t S, Carve& c) {
+  const int64_t C = chunk_bound(N, S);
+  ChunkView v{S};
+  v.offsets = c.take<int64_t>(S + 1);
+  v.chunk_struct = c.take<int32_t>(C);
+  v.chunk_begin = c.take<int64_t>(C);
+  v.first_chunk = c.take<int32_t>(S + 1);   // [S] = number of chunks
+  return v;
+}
+
+// Every driver describes its state once, as `Carved<XView> x_view(sizes..., void* state)`: one Carve::take per region, in allocation
+// order.  Over a null state the same function measures: `bytes` is the size of the buffer, and each pointer of `view` the byte offset
+// of its region (carve_offset).
+template <class View>
+struct Carved { View view; size_t bytes; };
+
+// read-back: a null destination (or an empty region) is skipped, otherwise `count` elements are queued device-to-host on s (the
+// caller synchronises)
+template <class T>
+inline hipError_t read_back(T* host, const T* dev, size_t count, hipStream_t s) {
+  return host && count ? hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, s) : hipSuccess;
 }
 
 __device__ inline double max_nan(double m, double x) { return (x > m || x != x) ? x : m; }   // a NaN row stays visible
@@ -146,11 +144,11 @@ struct ChunkTable {
     first_chunk[S] = (int32_t)chunk_struct.size();
   }
 
-  int upload(const ChunkLayout& L, char* state, const int64_t* host_offsets, hipStream_t s) const {
-    M3G_HIP_CHECK(hipMemcpyAsync(state + L.offsets, host_offsets, 8 * (L.S + 1), hipMemcpyHostToDevice, s));
-    M3G_HIP_CHECK(hipMemcpyAsync(state + L.chunk_struct, chunk_struct.data(), 4 * chunk_struct.size(), hipMemcpyHostToDevice, s));
-    M3G_HIP_CHECK(hipMemcpyAsync(state + L.chunk_begin, chunk_begin.data(), 8 * chunk_begin.size(), hipMemcpyHostToDevice, s));
-    M3G_HIP_CHECK(hipMemcpyAsync(state + L.first_chunk, first_chunk.data(), 4 * (L.S + 1), hipMemcpyHostToDevice, s));
+  int upload(const ChunkView& v, const int64_t* host_offsets, hipStream_t s) const {
+    M3G_HIP_CHECK(hipMemcpyAsync((void*)v.offsets, host_offsets, 8 * (v.S + 1), hipMemcpyHostToDevice, s));
+    M3G_HIP_CHECK(hipMemcpyAsync((void*)v.chunk_struct, chunk_struct.data(), 4 * chunk_struct.size(), hipMemcpyHostToDevice, s));
+    M3G_HIP_CHECK(hipMemcpyAsync((void*)v.chunk_begin, chunk_begin.data(), 8 * chunk_begin.size(), hipMemcpyHostToDevice, s));
+    M3G_HIP_CHECK(hipMemcpyAsync((void*)v.first_chunk, first_chunk.data(), 4 * (v.S + 1), hipMemcpyHostToDevice, s));
     return M3G_OK;
   }
 };

@@ -1,5 +1,6 @@
 // The device state of m3g_dyn_* (m3g_dynamics.hip) and its random generator, shared with the callers that work on that state between
-// two m3g_dyn_step calls (m3g_remd.hip: the target temperatures, velocities, flags and chunk table of a replica-exchange batch).
+// two m3g_dyn_step calls: m3g_remd.hip (the target temperatures, velocities, flags and chunk table of a replica-exchange batch) and
+// m3g_mc.hip (the flags, masses and velocities of a hybrid Monte Carlo batch; its own draws use philox4x64_10 and uniform53 too).
 #pragma once
 #include "m3g_chunks.h"
 #include "m3g_internal.h"
@@ -10,26 +11,6 @@ constexpr double kBoltzmann = 8.617333262e-5;  // eV/K
 constexpr int kPart = 8;    // per chunk: sum m|v|^2, sum m v [3], sum F [3], non-finite forces
 constexpr int kCoef = 8;    // per structure: action (0 none, 1 finish only, 2 finish + start), finish?, lambda, mu, pbar [3], noise^2
 
-struct DynLayout {
-  ChunkLayout chunks;
-  size_t partial, mass, v, t0, seed, flags, steps, coef, total;
-};
-inline DynLayout dyn_layout(int64_t N, int64_t S) {
-  DynLayout L{};
-  StateArena arena;
-  L.chunks = chunk_layout(N, S, arena);
-  L.partial = arena.take(8 * kPart * chunk_bound(N, S));
-  L.mass = arena.take(8 * N);
-  L.v = arena.take(8 * 3 * N);
-  L.t0 = arena.take(8 * S);
-  L.seed = arena.take(8 * S);
-  L.flags = arena.take(4 * S);
-  L.steps = arena.take(8 * S);
-  L.coef = arena.take(8 * kCoef * S);
-  L.total = arena.total;
-  return L;
-}
-
 struct DynView {
   int64_t N;
   ChunkView ch;
@@ -38,11 +19,19 @@ struct DynView {
   int32_t* flags;
   int64_t* steps;
 };
-inline DynView dyn_view(int64_t N, int64_t S, void* state) {
-  const DynLayout L = dyn_layout(N, S);
-  char* b = (char*)state;
-  return DynView{N, chunk_view(L.chunks, state), (double*)(b + L.partial), (double*)(b + L.mass), (double*)(b + L.v), (double*)(b + L.t0),
-                 (double*)(b + L.coef), (uint64_t*)(b + L.seed), (int32_t*)(b + L.flags), (int64_t*)(b + L.steps)};
+inline Carved<DynView> dyn_view(int64_t N, int64_t S, void* state) {
+  Carve c{state};
+  DynView st{N};
+  st.ch = chunk_view(N, S, c);
+  st.partial = c.take<double>(kPart * chunk_bound(N, S));
+  st.mass = c.take<double>(N);
+  st.v = c.take<double>(3 * N);
+  st.t0 = c.take<double>(S);
+  st.seed = c.take<uint64_t>(S);
+  st.flags = c.take<int32_t>(S);
+  st.steps = c.take<int64_t>(S);
+  st.coef = c.take<double>(kCoef * S);
+  return {st, c.off};
 }
 
 // Philox4x64-10 (Salmon et al., SC'11; the generator of numpy.random.Philox)

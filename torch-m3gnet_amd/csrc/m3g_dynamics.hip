@@ -212,15 +212,15 @@ using namespace m3g;
 
 extern "C" int m3g_dyn_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* bytes) {
   if (!bytes || !batch_sizes_ok(n_atoms, n_structs)) { set_error("m3g_dyn_state_bytes: bad sizes"); return M3G_ERR_VALUE; }
-  *bytes = dyn_layout(n_atoms, n_structs).total;
+  *bytes = dyn_view(n_atoms, n_structs, nullptr).bytes;
   return M3G_OK;
 }
 
 extern "C" int m3g_dyn_state_view(int64_t n_atoms, int64_t n_structs, size_t* mass_offset, size_t* velocity_offset) {
   if (!mass_offset || !velocity_offset || !batch_sizes_ok(n_atoms, n_structs)) { set_error("m3g_dyn_state_view: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  const DynLayout L = dyn_layout(n_atoms, n_structs);
-  *mass_offset = L.mass;
-  *velocity_offset = L.v;
+  const DynView at = dyn_view(n_atoms, n_structs, nullptr).view;   // (over a null state: the offsets)
+  *mass_offset = carve_offset(at.mass);
+  *velocity_offset = carve_offset(at.v);
   return M3G_OK;
 }
 
@@ -241,17 +241,16 @@ extern "C" int m3g_dyn_init(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_
       set_error("m3g_dyn_init: temperature of structure %lld is not finite and >= 0", (long long)s);
       return M3G_ERR_VALUE;
     }
-  const DynLayout L = dyn_layout(N, S);
-  if (state_bytes < L.total) { set_error("m3g_dyn_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
+  const auto [st, total] = dyn_view(N, S, state);
+  if (state_bytes < total) { set_error("m3g_dyn_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  char* b = (char*)state;
-  if (int rc = table.upload(L.chunks, b, host_offsets, s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.mass, host_masses, 8 * N, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.t0, host_temperatures, 8 * S, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.seed, host_seeds, 8 * S, hipMemcpyHostToDevice, s));
+  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
+  M3G_HIP_CHECK(hipMemcpyAsync(st.mass, host_masses, 8 * N, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st.t0, host_temperatures, 8 * S, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st.seed, host_seeds, 8 * S, hipMemcpyHostToDevice, s));
   const int64_t work = 3 * N > S ? 3 * N : S;
-  hipLaunchKernelGGL(k_dyn_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, dyn_view(N, S, state), vel);
+  hipLaunchKernelGGL(k_dyn_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, st, vel);
   M3G_HIP_CHECK(hipGetLastError());
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;
@@ -263,9 +262,9 @@ extern "C" int m3g_dyn_step(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !state || !forces || !pos) { set_error("m3g_dyn_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (p->ensemble == M3G_DYN_NPT_BERENDSEN && (!stresses || !lattice)) { set_error("m3g_dyn_step: NPT needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
-  if (state_bytes < dyn_layout(N, S).total) { set_error("m3g_dyn_step: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = dyn_view(N, S, state);
+  if (state_bytes < total) { set_error("m3g_dyn_step: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const DynView st = dyn_view(N, S, state);
   const double c1 = langevin_c1(p);
   const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_dyn_partials, grid, dim3(kChunkRows), 0, s, st, 0.5 * p->dt, forces);
@@ -279,13 +278,12 @@ extern "C" int m3g_dyn_read(int64_t n_atoms, int64_t n_structs, const void* stat
                             double* host_vel, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !state) { set_error("m3g_dyn_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  const DynLayout L = dyn_layout(N, S);
-  if (state_bytes < L.total) { set_error("m3g_dyn_read: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = dyn_view(N, S, (void*)state);
+  if (state_bytes < total) { set_error("m3g_dyn_read: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const char* b = (const char*)state;
-  if (host_flags) M3G_HIP_CHECK(hipMemcpyAsync(host_flags, b + L.flags, 4 * S, hipMemcpyDeviceToHost, s));
-  if (host_steps) M3G_HIP_CHECK(hipMemcpyAsync(host_steps, b + L.steps, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_vel) M3G_HIP_CHECK(hipMemcpyAsync(host_vel, b + L.v, 8 * 3 * N, hipMemcpyDeviceToHost, s));
+  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
+  M3G_HIP_CHECK(read_back(host_steps, st.steps, S, s));
+  M3G_HIP_CHECK(read_back(host_vel, st.v, 3 * N, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;
 }

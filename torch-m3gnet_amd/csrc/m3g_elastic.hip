@@ -22,24 +22,6 @@ namespace {
 constexpr int kMaxDeform = M3G_EL_MAX_DEFORM;
 constexpr int kJacobiSweeps = 30;
 
-struct ElLayout {
-  size_t row_off, unit_off, lat, unit_pos, dmat, comp, mag, total;
-};
-ElLayout el_layout(const m3g_el_sizes& z) {
-  ElLayout L{};
-  StateArena arena;
-  const int64_t S = z.n_structs, U = z.n_atoms, M = z.n_deform;
-  L.row_off = arena.take(8 * (S + 1));
-  L.unit_off = arena.take(8 * (S + 1));
-  L.lat = arena.take(8 * 9 * S);
-  L.unit_pos = arena.take(8 * 3 * U);
-  L.dmat = arena.take(8 * 9 * (M + 1));
-  L.comp = arena.take(4 * M);
-  L.mag = arena.take(8 * M);
-  L.total = arena.total;
-  return L;
-}
-
 struct ElView {
   int64_t S, U, rows, copies;   // copies = (1 + M) S
   int32_t M;
@@ -50,12 +32,18 @@ struct ElView {
   const int32_t* comp;                 // [M]
   const double* mag;                   // [M]
 };
-ElView el_view(const m3g_el_sizes& z, const void* state) {
-  const ElLayout L = el_layout(z);
-  const char* b = (const char*)state;
-  return ElView{z.n_structs, z.n_atoms, (1 + (int64_t)z.n_deform) * z.n_atoms, (1 + (int64_t)z.n_deform) * z.n_structs, z.n_deform,
-                (const int64_t*)(b + L.row_off), (const int64_t*)(b + L.unit_off), (const double*)(b + L.lat),
-                (const double*)(b + L.unit_pos), (const double*)(b + L.dmat), (const int32_t*)(b + L.comp), (const double*)(b + L.mag)};
+Carved<ElView> el_view(const m3g_el_sizes& z, const void* state) {
+  Carve c{state};
+  const int64_t S = z.n_structs, U = z.n_atoms, M = z.n_deform;
+  ElView st{S, U, (1 + M) * U, (1 + M) * S, z.n_deform};
+  st.row_off = c.take<int64_t>(S + 1);
+  st.unit_off = c.take<int64_t>(S + 1);
+  st.lat = c.take<double>(9 * S);
+  st.unit_pos = c.take<double>(3 * U);
+  st.dmat = c.take<double>(9 * (M + 1));
+  st.comp = c.take<int32_t>(M);
+  st.mag = c.take<double>(M);
+  return {st, c.off};
 }
 
 __global__ void __launch_bounds__(256) k_el_deform(ElView st, double* __restrict__ pos, double* __restrict__ lattices) {
@@ -331,7 +319,7 @@ constexpr const char* kSizesMsg = "bad sizes (need 1 <= n_structs <= n_atoms, 1 
 int el_call_ok(const char* name, const m3g_el_sizes* sizes, const void* state, size_t state_bytes, bool pointers, int mode) {
   if (!el_sizes_ok(sizes) || !state || !pointers) { set_error("%s: null argument or %s", name, kSizesMsg); return M3G_ERR_VALUE; }
   if (mode >= 0 && sizes->mode != mode) { set_error("%s: the state was made for the other mode (M3G_EL_MODE_*)", name); return M3G_ERR_VALUE; }
-  if (state_bytes < el_layout(*sizes).total) { set_error("%s: state buffer too small", name); return M3G_ERR_SIZE; }
+  if (state_bytes < el_view(*sizes, nullptr).bytes) { set_error("%s: state buffer too small", name); return M3G_ERR_SIZE; }
   return M3G_OK;
 }
 }  // namespace
@@ -341,7 +329,7 @@ using namespace m3g;
 
 extern "C" int m3g_el_state_bytes(const m3g_el_sizes* sizes, size_t* bytes) {
   if (!bytes || !el_sizes_ok(sizes)) { set_error("m3g_el_state_bytes: %s", kSizesMsg); return M3G_ERR_VALUE; }
-  *bytes = el_layout(*sizes).total;
+  *bytes = el_view(*sizes, nullptr).bytes;
   return M3G_OK;
 }
 
@@ -401,24 +389,23 @@ extern "C" int m3g_el_init(const m3g_el_sizes* sizes, const int64_t* host_offset
     if (c < 3) D[4 * c] = 1.0 + d;
     else if (c < 6) D[3 * kVoigt[c][0] + kVoigt[c][1]] = D[3 * kVoigt[c][1] + kVoigt[c][0]] = 0.5 * d;
   }
-  const ElLayout L = el_layout(z);
-  if (state_bytes < L.total) { set_error("m3g_el_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
+  const auto [st, total] = el_view(z, state);
+  if (state_bytes < total) { set_error("m3g_el_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  char* st = (char*)state;
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.row_off, row_off.data(), 8 * (S + 1), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.unit_off, host_offsets, 8 * (S + 1), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.lat, host_lattices, 8 * 9 * S, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.unit_pos, host_positions, 8 * 3 * U, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.dmat, dmat.data(), 8 * dmat.size(), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.comp, host_components, 4 * (size_t)M, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.mag, host_magnitudes, 8 * (size_t)M, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.row_off, row_off.data(), 8 * (S + 1), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.unit_off, host_offsets, 8 * (S + 1), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.lat, host_lattices, 8 * 9 * S, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.unit_pos, host_positions, 8 * 3 * U, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.dmat, dmat.data(), 8 * dmat.size(), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.comp, host_components, 4 * (size_t)M, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.mag, host_magnitudes, 8 * (size_t)M, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;
 }
 
 extern "C" int m3g_el_deform(const m3g_el_sizes* sizes, const void* state, size_t state_bytes, double* pos, double* lattices, void* stream_) {
   if (const int rc = el_call_ok("m3g_el_deform", sizes, state, state_bytes, pos && lattices, -1)) return rc;
-  const ElView st = el_view(*sizes, state);
+  const ElView st = el_view(*sizes, state).view;
   const int64_t threads = st.rows > 3 * st.copies ? st.rows : 3 * st.copies;
   hipLaunchKernelGGL(k_el_deform, grid_for(threads, 256), dim3(256), 0, (hipStream_t)stream_, st, pos, lattices);
   M3G_RETURN_LAUNCH_STATUS();
@@ -427,7 +414,7 @@ extern "C" int m3g_el_deform(const m3g_el_sizes* sizes, const void* state, size_
 extern "C" int m3g_el_fit_elastic(const m3g_el_sizes* sizes, const void* state, size_t state_bytes, const float* stresses, double* rows,
                                   int32_t* nonfinite, void* stream_) {
   if (const int rc = el_call_ok("m3g_el_fit_elastic", sizes, state, state_bytes, stresses && rows && nonfinite, M3G_EL_MODE_ELASTIC)) return rc;
-  const ElView st = el_view(*sizes, state);
+  const ElView st = el_view(*sizes, state).view;
   hipLaunchKernelGGL(k_el_fit_elastic, dim3((unsigned)st.S), dim3(kWave), 0, (hipStream_t)stream_, st, stresses, rows, nonfinite);
   M3G_RETURN_LAUNCH_STATUS();
 }
@@ -435,7 +422,7 @@ extern "C" int m3g_el_fit_elastic(const m3g_el_sizes* sizes, const void* state, 
 extern "C" int m3g_el_fit_eos(const m3g_el_sizes* sizes, const void* state, size_t state_bytes, const float* energies, double* rows,
                               int32_t* error, void* stream_) {
   if (const int rc = el_call_ok("m3g_el_fit_eos", sizes, state, state_bytes, energies && rows && error, M3G_EL_MODE_EOS)) return rc;
-  const ElView st = el_view(*sizes, state);
+  const ElView st = el_view(*sizes, state).view;
   hipLaunchKernelGGL(k_el_fit_eos, grid_for(st.S, kWave), dim3(kWave), 0, (hipStream_t)stream_, st, energies, rows, error);
   M3G_RETURN_LAUNCH_STATUS();
 }

@@ -230,12 +230,17 @@ namespace m3g {
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 // grid of a launch with one thread (or one group of `per`) per item
 inline dim3 grid_for(int64_t n, int per = 256) { return dim3((unsigned)((n + per - 1) / per)); }
-// carving a caller's buffer into arrays, one after the other from `base`; a null base measures (`off` ends as the bytes needed)
+// carving a caller's buffer into arrays, one after the other from `base`.  A null base measures: `off` ends as the bytes needed,
+// and what take() returned are the byte offsets themselves (integer arithmetic, so no pointer is formed from null + n).
 struct Carve {
-  char* base;
+  uintptr_t base;
   size_t off = 0;
-  void* take(size_t bytes) { void* r = base ? (void*)(base + off) : nullptr; off += align_up(bytes); return r; }
+  explicit Carve(const void* b) : base((uintptr_t)b) {}
+  template <class T> T* take(size_t count) { T* r = (T*)(base + off); off += align_up(sizeof(T) * count); return r; }
+  void* take(size_t bytes) { return take<char>(bytes); }
 };
+// the byte offset of a pointer taken from a Carve over a null base
+inline size_t carve_offset(const void* p) { return (size_t)(uintptr_t)p; }
 
 // ---- device helper shared by the graph-side units -----------------------------------------------------------
 // One thread's binary search: the first index of the sorted a[0..n) whose key is not below `key`, n when there is none.  `key_of`

@@ -33,44 +33,6 @@ constexpr int kMaxMemory = 2047;     // the solve kernel keeps 2 (memory + 1) co
 //   X, X_prev, grad, grad_prev, p: 8*3R each;  the rings of s and y: 8*3R*M each  (the dominant term: memory * 2 * 3(N+3S) * 8);
 //   L0, F: 8*9*S each;  the Gram blocks s_i.y_j and y_i.y_j: 8*M*M*S each;  rho, s.grad, y.grad, c_s, c_y: 8*M*S each;
 //   ring head, pair count, flags, step count: 4*S each;  coefficients 8*16*S.
-struct LbfgsLayout {
-  ChunkLayout chunks;
-  size_t head_part, slot_part, pmax, x, xprev, grad, gprev, p, ring_s, ring_y, l0, f, sy, yy, rho, sg, yg, cs, cy, head, count, flags, steps,
-      coef, total;
-};
-LbfgsLayout lbfgs_layout(int64_t N, int64_t S, int64_t memory) {
-  LbfgsLayout L{};
-  StateArena arena;
-  const size_t C = (size_t)chunk_bound(N, S), R = (size_t)(N + 3 * S), M = (size_t)memory + 1, Ss = (size_t)S;
-  L.chunks = chunk_layout(N, S, arena);
-  L.head_part = arena.take(8 * kHeadDots * C);
-  L.slot_part = arena.take(8 * kSlotDots * M * C);
-  L.pmax = arena.take(8 * C);
-  L.x = arena.take(8 * 3 * R);                // rows: the N atoms, then 3 cell rows per structure
-  L.xprev = arena.take(8 * 3 * R);
-  L.grad = arena.take(8 * 3 * R);
-  L.gprev = arena.take(8 * 3 * R);
-  L.p = arena.take(8 * 3 * R);
-  L.ring_s = arena.take(8 * 3 * R * M);
-  L.ring_y = arena.take(8 * 3 * R * M);
-  L.l0 = arena.take(8 * 9 * Ss);
-  L.f = arena.take(8 * 9 * Ss);
-  L.sy = arena.take(8 * M * M * Ss);
-  L.yy = arena.take(8 * M * M * Ss);
-  L.rho = arena.take(8 * M * Ss);
-  L.sg = arena.take(8 * M * Ss);
-  L.yg = arena.take(8 * M * Ss);
-  L.cs = arena.take(8 * M * Ss);
-  L.cy = arena.take(8 * M * Ss);
-  L.head = arena.take(4 * Ss);
-  L.count = arena.take(4 * Ss);
-  L.flags = arena.take(4 * Ss);
-  L.steps = arena.take(4 * Ss);
-  L.coef = arena.take(8 * kCoef * Ss);
-  L.total = arena.total;
-  return L;
-}
-
 struct LbfgsView {
   int64_t N, R;     // atoms; rows of a vector (N + 3 S)
   int M;            // ring slots: memory + 1
@@ -82,14 +44,36 @@ struct LbfgsView {
   __device__ double* s_of(int slot) const { return ring_s + (size_t)slot * 3 * R; }
   __device__ double* y_of(int slot) const { return ring_y + (size_t)slot * 3 * R; }
 };
-LbfgsView lbfgs_view(int64_t N, int64_t S, int64_t memory, void* state) {
-  const LbfgsLayout L = lbfgs_layout(N, S, memory);
-  char* b = (char*)state;
-  auto d = [b](size_t at) { return (double*)(b + at); };
-  auto i = [b](size_t at) { return (int32_t*)(b + at); };
-  return LbfgsView{N, N + 3 * S, (int)memory + 1, chunk_view(L.chunks, state), d(L.head_part), d(L.slot_part), d(L.pmax), d(L.x), d(L.xprev),
-                   d(L.grad), d(L.gprev), d(L.p), d(L.ring_s), d(L.ring_y), d(L.l0), d(L.f), d(L.sy), d(L.yy), d(L.rho), d(L.sg), d(L.yg),
-                   d(L.cs), d(L.cy), d(L.coef), i(L.head), i(L.count), i(L.flags), i(L.steps)};
+Carved<LbfgsView> lbfgs_view(int64_t N, int64_t S, int64_t memory, void* state) {
+  Carve c{state};
+  const size_t C = (size_t)chunk_bound(N, S), R = (size_t)(N + 3 * S), M = (size_t)memory + 1, Ss = (size_t)S;
+  LbfgsView st{N, N + 3 * S, (int)memory + 1};
+  st.ch = chunk_view(N, S, c);
+  st.head_part = c.take<double>(kHeadDots * C);
+  st.slot_part = c.take<double>(kSlotDots * M * C);
+  st.pmax = c.take<double>(C);
+  st.x = c.take<double>(3 * R);                // rows: the N atoms, then 3 cell rows per structure
+  st.xprev = c.take<double>(3 * R);
+  st.grad = c.take<double>(3 * R);
+  st.gprev = c.take<double>(3 * R);
+  st.p = c.take<double>(3 * R);
+  st.ring_s = c.take<double>(3 * R * M);
+  st.ring_y = c.take<double>(3 * R * M);
+  st.l0 = c.take<double>(9 * Ss);
+  st.f = c.take<double>(9 * Ss);
+  st.sy = c.take<double>(M * M * Ss);
+  st.yy = c.take<double>(M * M * Ss);
+  st.rho = c.take<double>(M * Ss);
+  st.sg = c.take<double>(M * Ss);
+  st.yg = c.take<double>(M * Ss);
+  st.cs = c.take<double>(M * Ss);
+  st.cy = c.take<double>(M * Ss);
+  st.head = c.take<int32_t>(Ss);
+  st.count = c.take<int32_t>(Ss);
+  st.flags = c.take<int32_t>(Ss);
+  st.steps = c.take<int32_t>(Ss);
+  st.coef = c.take<double>(kCoef * Ss);
+  return {st, c.off};
 }
 
 __device__ inline double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -474,7 +458,7 @@ extern "C" int m3g_lbfgs_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t
     set_error("m3g_lbfgs_state_bytes: bad sizes (1 <= memory <= %d)", kMaxMemory);
     return M3G_ERR_VALUE;
   }
-  *bytes = lbfgs_layout(n_atoms, n_structs, memory).total;
+  *bytes = lbfgs_view(n_atoms, n_structs, memory, nullptr).bytes;
   return M3G_OK;
 }
 
@@ -487,13 +471,13 @@ extern "C" int m3g_lbfgs_init(const m3g_lbfgs_params* p, int64_t n_atoms, int64_
   }
   const int64_t N = n_atoms, S = n_structs;
   if (!offsets_ok("m3g_lbfgs_init", host_offsets, N, S)) return M3G_ERR_VALUE;
-  const LbfgsLayout L = lbfgs_layout(N, S, p->memory);
-  if (state_bytes < L.total) { set_error("m3g_lbfgs_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
+  const auto [st, total] = lbfgs_view(N, S, p->memory, state);
+  if (state_bytes < total) { set_error("m3g_lbfgs_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(L.chunks, (char*)state, host_offsets, s)) return rc;
+  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
   const int64_t work = 3 * N > S ? 3 * N : S;
-  hipLaunchKernelGGL(k_lbfgs_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, lbfgs_view(N, S, p->memory, state), pos, lattice);
+  hipLaunchKernelGGL(k_lbfgs_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, st, pos, lattice);
   M3G_HIP_CHECK(hipGetLastError());
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;
@@ -506,9 +490,9 @@ extern "C" int m3g_lbfgs_step(const m3g_lbfgs_params* p, int64_t n_atoms, int64_
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !state || !forces || !pos) { set_error("m3g_lbfgs_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (p->relax_cell && (!stresses || !lattice)) { set_error("m3g_lbfgs_step: a cell relaxation needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
-  if (state_bytes < lbfgs_layout(N, S, p->memory).total) { set_error("m3g_lbfgs_step: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = lbfgs_view(N, S, p->memory, state);
+  if (state_bytes < total) { set_error("m3g_lbfgs_step: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const LbfgsView st = lbfgs_view(N, S, p->memory, state);
   const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
   const size_t lds = 2 * sizeof(double) * (size_t)st.M;
   hipLaunchKernelGGL(k_lbfgs_gather, grid, dim3(kChunkRows), 0, s, st, p->relax_cell, forces);
@@ -523,15 +507,13 @@ extern "C" int m3g_lbfgs_read(int64_t n_atoms, int64_t n_structs, int32_t memory
                               int32_t* host_steps, int32_t* host_pairs, double* host_x, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !state || memory < 1 || memory > kMaxMemory) { set_error("m3g_lbfgs_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  const LbfgsLayout L = lbfgs_layout(N, S, memory);
-  if (state_bytes < L.total) { set_error("m3g_lbfgs_read: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = lbfgs_view(N, S, memory, (void*)state);
+  if (state_bytes < total) { set_error("m3g_lbfgs_read: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const char* b = (const char*)state;
-  const int64_t R = N + 3 * S;
-  if (host_flags) M3G_HIP_CHECK(hipMemcpyAsync(host_flags, b + L.flags, 4 * S, hipMemcpyDeviceToHost, s));
-  if (host_steps) M3G_HIP_CHECK(hipMemcpyAsync(host_steps, b + L.steps, 4 * S, hipMemcpyDeviceToHost, s));
-  if (host_pairs) M3G_HIP_CHECK(hipMemcpyAsync(host_pairs, b + L.count, 4 * S, hipMemcpyDeviceToHost, s));
-  if (host_x) M3G_HIP_CHECK(hipMemcpyAsync(host_x, b + L.x, 8 * 3 * R, hipMemcpyDeviceToHost, s));
+  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
+  M3G_HIP_CHECK(read_back(host_steps, st.steps, S, s));
+  M3G_HIP_CHECK(read_back(host_pairs, st.count, S, s));
+  M3G_HIP_CHECK(read_back(host_x, st.x, 3 * st.R, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;
 }

@@ -20,33 +20,6 @@
 
 namespace m3g {
 namespace {
-struct McLayout {
-  ChunkLayout chunks;
-  size_t active, temps, seed, flags, counter, decided, pair, u2, accepted, attempts, accepts, nonfinite, count, mean, m2, total;
-};
-McLayout mc_layout(int64_t N, int64_t S) {
-  McLayout L{};
-  StateArena arena;
-  L.chunks = chunk_layout(N, S, arena);
-  L.active = arena.take(N);          // uint8 per row
-  L.temps = arena.take(8 * S);
-  L.seed = arena.take(8 * S);
-  L.flags = arena.take(4 * S);       // M3G_MC_*
-  L.counter = arena.take(8 * S);     // proposals drawn = m3g_mc_propose calls
-  L.decided = arena.take(8 * S);     // calls whose history row has been written
-  L.pair = arena.take(4 * 2 * S);    // rows (i, j) of the last attempted trial, relative to the structure
-  L.u2 = arena.take(8 * S);          // the verdict's uniform of the pending trial
-  L.accepted = arena.take(4 * S);    // verdict of the last m3g_mc_decide (k_mc_commit reads it)
-  L.attempts = arena.take(8 * S);
-  L.accepts = arena.take(8 * S);
-  L.nonfinite = arena.take(8 * S);
-  L.count = arena.take(8 * S);
-  L.mean = arena.take(8 * S);
-  L.m2 = arena.take(8 * S);
-  L.total = arena.total;
-  return L;
-}
-
 struct McView {
   int64_t S;
   ChunkView ch;
@@ -57,13 +30,26 @@ struct McView {
   int64_t *counter, *decided, *attempts, *accepts, *nonfinite, *count;
   double *u2, *mean, *m2;
 };
-McView mc_view(int64_t N, int64_t S, void* state) {
-  const McLayout L = mc_layout(N, S);
-  char* b = (char*)state;
-  return McView{S, chunk_view(L.chunks, state), (const uint8_t*)(b + L.active), (const double*)(b + L.temps), (const uint64_t*)(b + L.seed),
-                (int32_t*)(b + L.flags), (int32_t*)(b + L.pair), (int32_t*)(b + L.accepted), (int64_t*)(b + L.counter),
-                (int64_t*)(b + L.decided), (int64_t*)(b + L.attempts), (int64_t*)(b + L.accepts), (int64_t*)(b + L.nonfinite),
-                (int64_t*)(b + L.count), (double*)(b + L.u2), (double*)(b + L.mean), (double*)(b + L.m2)};
+Carved<McView> mc_view(int64_t N, int64_t S, void* state) {
+  Carve c{state};
+  McView st{S};
+  st.ch = chunk_view(N, S, c);
+  st.active = c.take<uint8_t>(N);        // per row
+  st.temps = c.take<double>(S);
+  st.seed = c.take<uint64_t>(S);
+  st.flags = c.take<int32_t>(S);         // M3G_MC_*
+  st.counter = c.take<int64_t>(S);       // proposals drawn = m3g_mc_propose calls
+  st.decided = c.take<int64_t>(S);       // calls whose history row has been written
+  st.pair = c.take<int32_t>(2 * S);      // rows (i, j) of the last attempted trial, relative to the structure
+  st.u2 = c.take<double>(S);             // the verdict's uniform of the pending trial
+  st.accepted = c.take<int32_t>(S);      // verdict of the last m3g_mc_decide (k_mc_commit reads it)
+  st.attempts = c.take<int64_t>(S);
+  st.accepts = c.take<int64_t>(S);
+  st.nonfinite = c.take<int64_t>(S);
+  st.count = c.take<int64_t>(S);
+  st.mean = c.take<double>(S);
+  st.m2 = c.take<double>(S);
+  return {st, c.off};
 }
 
 // the rows lo .. hi of one structure, 64 at a time by one wave: row `row` takes part when it is active and (with `other` >= 0) holds
@@ -220,7 +206,7 @@ using namespace m3g;
 
 extern "C" int m3g_mc_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* bytes) {
   if (!bytes || !mc_sizes_ok(n_atoms, n_structs)) { set_error("m3g_mc_state_bytes: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  *bytes = mc_layout(n_atoms, n_structs).total;
+  *bytes = mc_view(n_atoms, n_structs, nullptr).bytes;
   return M3G_OK;
 }
 
@@ -239,23 +225,23 @@ extern "C" int m3g_mc_init(int64_t n_atoms, int64_t n_structs, const int64_t* ho
     }
     if (host_offsets[s + 1] - host_offsets[s] > INT32_MAX) { set_error("m3g_mc_init: structure %lld holds too many atoms", (long long)s); return M3G_ERR_VALUE; }
   }
-  const McLayout L = mc_layout(N, S);
-  if (state_bytes < L.total) { set_error("m3g_mc_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
-  const size_t tail = L.total - L.active;   // everything after the chunk table: counters, statistics and flags start at zero
-  std::vector<char> image(tail, 0);
-  const auto at = [&](size_t region) { return image.data() + (region - L.active); };
-  for (int64_t i = 0; i < N; ++i) at(L.active)[i] = host_active[i] ? 1 : 0;
-  std::memcpy(at(L.temps), host_temperatures, 8 * S);
-  std::memcpy(at(L.seed), host_seeds, 8 * S);
+  const auto [st, total] = mc_view(N, S, state);
+  if (state_bytes < total) { set_error("m3g_mc_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  std::vector<char> image(total, 0);   // counters, statistics and flags start at zero (the chunk table's part is not sent: upload() below)
+  const McView im = mc_view(N, S, image.data()).view;
+  for (int64_t i = 0; i < N; ++i) ((uint8_t*)im.active)[i] = host_active[i] ? 1 : 0;
+  std::memcpy((void*)im.temps, host_temperatures, 8 * S);
+  std::memcpy((void*)im.seed, host_seeds, 8 * S);
   for (int64_t s = 0; s < S; ++s) {
     int64_t n_p = 0;
     for (int64_t i = host_offsets[s]; i < host_offsets[s + 1]; ++i) n_p += host_active[i] ? 1 : 0;
-    if (n_p < 2) ((int32_t*)at(L.flags))[s] = M3G_MC_NO_PAIR;   // (the species are the device's to look at: k_mc_propose)
+    if (n_p < 2) im.flags[s] = M3G_MC_NO_PAIR;   // (the species are the device's to look at: k_mc_propose)
   }
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(L.chunks, (char*)state, host_offsets, s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync((char*)state + L.active, image.data(), tail, hipMemcpyHostToDevice, s));
+  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
+  const size_t table_bytes = (size_t)((const char*)im.active - image.data());   // everything after the chunk table goes in one copy
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.active, im.active, total - table_bytes, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host image and tables above go out of scope)
   return M3G_OK;
 }
@@ -264,11 +250,11 @@ extern "C" int m3g_mc_propose(int64_t n_atoms, int64_t n_structs, void* state, s
                               size_t dyn_bytes, const float* energies, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
   if (!mc_sizes_ok(N, S) || !state || !atom_types || !energies) { set_error("m3g_mc_propose: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  if (state_bytes < mc_layout(N, S).total) { set_error("m3g_mc_propose: Monte Carlo state buffer too small"); return M3G_ERR_SIZE; }
-  if (dyn_state && dyn_bytes < dyn_layout(N, S).total) { set_error("m3g_mc_propose: dynamics state buffer too small"); return M3G_ERR_SIZE; }
-  DynView dyn{};
-  if (dyn_state) dyn = dyn_view(N, S, dyn_state);
-  hipLaunchKernelGGL(k_mc_propose, dim3((unsigned)S), dim3(kWave), 0, (hipStream_t)stream_, mc_view(N, S, state), atom_types, dyn.flags, dyn.mass,
+  const auto [st, total] = mc_view(N, S, state);
+  const auto [dyn, dyn_total] = dyn_state ? dyn_view(N, S, dyn_state) : Carved<DynView>{};
+  if (state_bytes < total) { set_error("m3g_mc_propose: Monte Carlo state buffer too small"); return M3G_ERR_SIZE; }
+  if (dyn_bytes < dyn_total) { set_error("m3g_mc_propose: dynamics state buffer too small"); return M3G_ERR_SIZE; }
+  hipLaunchKernelGGL(k_mc_propose, dim3((unsigned)S), dim3(kWave), 0, (hipStream_t)stream_, st, atom_types, dyn.flags, dyn.mass,
                      dyn.v, energies);
   M3G_RETURN_LAUNCH_STATUS();
 }
@@ -285,12 +271,11 @@ extern "C" int m3g_mc_decide(int64_t n_atoms, int64_t n_structs, void* state, si
     set_error("m3g_mc_decide: trial and current forces (stresses) must be given together");
     return M3G_ERR_VALUE;
   }
-  if (state_bytes < mc_layout(N, S).total) { set_error("m3g_mc_decide: Monte Carlo state buffer too small"); return M3G_ERR_SIZE; }
-  if (dyn_state && dyn_bytes < dyn_layout(N, S).total) { set_error("m3g_mc_decide: dynamics state buffer too small"); return M3G_ERR_SIZE; }
-  DynView dyn{};
-  if (dyn_state) dyn = dyn_view(N, S, dyn_state);
+  const auto [st, total] = mc_view(N, S, state);
+  const auto [dyn, dyn_total] = dyn_state ? dyn_view(N, S, dyn_state) : Carved<DynView>{};
+  if (state_bytes < total) { set_error("m3g_mc_decide: Monte Carlo state buffer too small"); return M3G_ERR_SIZE; }
+  if (dyn_bytes < dyn_total) { set_error("m3g_mc_decide: dynamics state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const McView st = mc_view(N, S, state);
   hipLaunchKernelGGL(k_mc_verdict, dim3((unsigned)S), dim3(kWave), 0, s, st, atom_types, dyn.mass, dyn.v, trial_energies, energies, history,
                      history_rows);
   if (forces || stresses)
@@ -303,19 +288,18 @@ extern "C" int m3g_mc_read(int64_t n_atoms, int64_t n_structs, const void* state
                            double* host_m2, int32_t* host_pairs, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
   if (!mc_sizes_ok(N, S) || !state) { set_error("m3g_mc_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  const McLayout L = mc_layout(N, S);
-  if (state_bytes < L.total) { set_error("m3g_mc_read: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = mc_view(N, S, (void*)state);
+  if (state_bytes < total) { set_error("m3g_mc_read: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const char* b = (const char*)state;
-  if (host_flags) M3G_HIP_CHECK(hipMemcpyAsync(host_flags, b + L.flags, 4 * S, hipMemcpyDeviceToHost, s));
-  if (host_counters) M3G_HIP_CHECK(hipMemcpyAsync(host_counters, b + L.counter, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_attempts) M3G_HIP_CHECK(hipMemcpyAsync(host_attempts, b + L.attempts, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_accepts) M3G_HIP_CHECK(hipMemcpyAsync(host_accepts, b + L.accepts, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_nonfinite) M3G_HIP_CHECK(hipMemcpyAsync(host_nonfinite, b + L.nonfinite, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_count) M3G_HIP_CHECK(hipMemcpyAsync(host_count, b + L.count, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_mean) M3G_HIP_CHECK(hipMemcpyAsync(host_mean, b + L.mean, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_m2) M3G_HIP_CHECK(hipMemcpyAsync(host_m2, b + L.m2, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_pairs) M3G_HIP_CHECK(hipMemcpyAsync(host_pairs, b + L.pair, 8 * S, hipMemcpyDeviceToHost, s));
+  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
+  M3G_HIP_CHECK(read_back(host_counters, st.counter, S, s));
+  M3G_HIP_CHECK(read_back(host_attempts, st.attempts, S, s));
+  M3G_HIP_CHECK(read_back(host_accepts, st.accepts, S, s));
+  M3G_HIP_CHECK(read_back(host_nonfinite, st.nonfinite, S, s));
+  M3G_HIP_CHECK(read_back(host_count, st.count, S, s));
+  M3G_HIP_CHECK(read_back(host_mean, st.mean, S, s));
+  M3G_HIP_CHECK(read_back(host_m2, st.m2, S, s));
+  M3G_HIP_CHECK(read_back(host_pairs, st.pair, 2 * S, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;
 }

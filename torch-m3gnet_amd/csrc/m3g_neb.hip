@@ -22,28 +22,6 @@ namespace {
 constexpr int kPart = 6;    // per chunk: |tau+|^2, |tau-|^2, tau+.tau-, F.tau+, F.tau-, non-finite inputs
 constexpr int kRows = 5;    // observables per image: |tau+|, |tau-|, F.tau_hat, spring term, climbing flag
 
-struct NebLayout {
-  ChunkLayout chunks;
-  size_t partial, img_prev, img_next, band_images, k, climb, ep_pos, ep_energy, coef, total;
-};
-// the endpoint rows (2 n_b per band) never exceed 2N: every band holds an interior image of n_b atoms
-NebLayout neb_layout(int64_t N, int64_t I, int64_t B) {
-  NebLayout L{};
-  StateArena arena;
-  L.chunks = chunk_layout(N, I, arena);
-  L.partial = arena.take(8 * kPart * chunk_bound(N, I));
-  L.img_prev = arena.take(8 * I);
-  L.img_next = arena.take(8 * I);
-  L.band_images = arena.take(4 * (B + 1));
-  L.k = arena.take(8 * B);
-  L.climb = arena.take(4 * B);
-  L.ep_pos = arena.take(8 * 3 * 2 * N);
-  L.ep_energy = arena.take(8 * 2 * B);
-  L.coef = arena.take(8 * 2 * I);
-  L.total = arena.total;
-  return L;
-}
-
 struct NebView {
   int64_t N, B;
   ChunkView ch;   // the interior images are its structures (ch.S of them)
@@ -55,12 +33,21 @@ struct NebView {
   const double *ep_pos, *ep_energy;     // per band: initial rows, final rows; energies [2B] (initial, final)
   double* coef;                         // [I, 2]: alpha, beta
 };
-NebView neb_view(int64_t N, int64_t I, int64_t B, void* state) {
-  const NebLayout L = neb_layout(N, I, B);
-  char* b = (char*)state;
-  return NebView{N, B, chunk_view(L.chunks, state), (double*)(b + L.partial), (const int64_t*)(b + L.img_prev),
-                 (const int64_t*)(b + L.img_next), (const int32_t*)(b + L.band_images), (const double*)(b + L.k), (const int32_t*)(b + L.climb),
-                 (const double*)(b + L.ep_pos), (const double*)(b + L.ep_energy), (double*)(b + L.coef)};
+// the endpoint rows (2 n_b per band) never exceed 2N: every band holds an interior image of n_b atoms
+Carved<NebView> neb_view(int64_t N, int64_t I, int64_t B, void* state) {
+  Carve c{state};
+  NebView st{N, B};
+  st.ch = chunk_view(N, I, c);
+  st.partial = c.take<double>(kPart * chunk_bound(N, I));
+  st.img_prev = c.take<int64_t>(I);
+  st.img_next = c.take<int64_t>(I);
+  st.band_images = c.take<int32_t>(B + 1);
+  st.k = c.take<double>(B);
+  st.climb = c.take<int32_t>(B);
+  st.ep_pos = c.take<double>(3 * 2 * N);
+  st.ep_energy = c.take<double>(2 * B);
+  st.coef = c.take<double>(2 * I);
+  return {st, c.off};
 }
 
 __device__ inline const double* neighbour_row(int64_t enc, int64_t local, const double* pos, const double* ep) {
@@ -181,7 +168,7 @@ using namespace m3g;
 
 extern "C" int m3g_neb_state_bytes(int64_t n_atoms, int64_t n_images, int64_t n_bands, size_t* bytes) {
   if (!bytes || !neb_sizes_ok(n_atoms, n_images, n_bands)) { set_error("m3g_neb_state_bytes: bad sizes (need 1 <= n_bands <= n_images <= n_atoms)"); return M3G_ERR_VALUE; }
-  *bytes = neb_layout(n_atoms, n_images, n_bands).total;
+  *bytes = neb_view(n_atoms, n_images, n_bands, nullptr).bytes;
   return M3G_OK;
 }
 
@@ -220,19 +207,18 @@ extern "C" int m3g_neb_init(int64_t n_atoms, int64_t n_images, int64_t n_bands, 
     }
     ep_rows += 2 * n;
   }
-  const NebLayout L = neb_layout(N, I, B);
-  if (state_bytes < L.total) { set_error("m3g_neb_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
+  const auto [st, total] = neb_view(N, I, B, state);
+  if (state_bytes < total) { set_error("m3g_neb_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
   const ChunkTable table(host_image_offsets, I);
   hipStream_t s = (hipStream_t)stream_;
-  char* st = (char*)state;
-  if (int rc = table.upload(L.chunks, st, host_image_offsets, s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.img_prev, img_prev.data(), 8 * I, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.img_next, img_next.data(), 8 * I, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.band_images, host_band_images, 4 * (B + 1), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.k, host_k, 8 * B, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.climb, host_climb, 4 * B, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.ep_pos, endpoint_pos, 8 * 3 * ep_rows, hipMemcpyDeviceToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.ep_energy, host_endpoint_energies, 8 * 2 * B, hipMemcpyHostToDevice, s));
+  if (int rc = table.upload(st.ch, host_image_offsets, s)) return rc;
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.img_prev, img_prev.data(), 8 * I, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.img_next, img_next.data(), 8 * I, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.band_images, host_band_images, 4 * (B + 1), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.k, host_k, 8 * B, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.climb, host_climb, 4 * B, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.ep_pos, endpoint_pos, 8 * 3 * ep_rows, hipMemcpyDeviceToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.ep_energy, host_endpoint_energies, 8 * 2 * B, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;
 }
@@ -244,9 +230,9 @@ extern "C" int m3g_neb_forces(int64_t n_atoms, int64_t n_images, int64_t n_bands
     set_error("m3g_neb_forces: null argument or bad sizes");
     return M3G_ERR_VALUE;
   }
-  if (state_bytes < neb_layout(N, I, B).total) { set_error("m3g_neb_forces: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = neb_view(N, I, B, state);
+  if (state_bytes < total) { set_error("m3g_neb_forces: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const NebView st = neb_view(N, I, B, state);
   const dim3 grid((unsigned)chunk_bound(N, I));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_neb_partials, grid, dim3(kChunkRows), 0, s, st, pos, forces);
   hipLaunchKernelGGL(k_neb_finalize, grid_for(B, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, energies, rows);

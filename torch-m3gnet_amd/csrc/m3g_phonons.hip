@@ -36,28 +36,6 @@ constexpr int kMaxMult = M3G_PH_MAX_MULTIPLICITY;   // shortest images per (u, j
 constexpr int kFcThreads = kChunkRows;   // the workgroup of chunk_tree_reduce (m3g_chunks.h)
 constexpr int kDynThreads = 64;
 
-struct PhLayout {
-  size_t row_off, unit_off, pair_off, dims, lat, unit_pos, mass, unit_struct, delta, img_count, img_d, total;
-};
-PhLayout ph_layout(const m3g_ph_sizes& z) {
-  PhLayout L{};
-  StateArena arena;
-  const int64_t S = z.n_structs, U = z.n_unit_atoms, P = z.n_pairs;
-  L.row_off = arena.take(8 * (S + 1));
-  L.unit_off = arena.take(8 * (S + 1));
-  L.pair_off = arena.take(8 * (S + 1));
-  L.dims = arena.take(4 * 3 * S);
-  L.lat = arena.take(8 * 9 * S);
-  L.unit_pos = arena.take(8 * 3 * U);
-  L.mass = arena.take(8 * U);
-  L.unit_struct = arena.take(4 * U);
-  L.delta = arena.take(8);
-  L.img_count = arena.take(4 * P);
-  L.img_d = arena.take(8 * 3 * kMaxMult * P);
-  L.total = arena.total;
-  return L;
-}
-
 struct PhView {
   int64_t S, U, rows;
   const int64_t *row_off, *unit_off, *pair_off;   // [S+1]: displaced rows, unit atoms, (u, j) pairs
@@ -70,14 +48,22 @@ struct PhView {
   const int32_t* img_count;                       // [P]
   const double* img_d;                            // [P, kMaxMult, 3] unit-cell fractional
 };
-PhView ph_view(const m3g_ph_sizes& z, const void* state) {
-  const PhLayout L = ph_layout(z);
-  const char* b = (const char*)state;
-  return PhView{z.n_structs, z.n_unit_atoms, 6 * z.n_pairs + z.n_super_atoms,
-                (const int64_t*)(b + L.row_off), (const int64_t*)(b + L.unit_off), (const int64_t*)(b + L.pair_off),
-                (const int32_t*)(b + L.dims), (const double*)(b + L.lat), (const double*)(b + L.unit_pos), (const double*)(b + L.mass),
-                (const int32_t*)(b + L.unit_struct), (const double*)(b + L.delta), (const int32_t*)(b + L.img_count),
-                (const double*)(b + L.img_d)};
+Carved<PhView> ph_view(const m3g_ph_sizes& z, const void* state) {
+  Carve c{state};
+  const int64_t S = z.n_structs, U = z.n_unit_atoms, P = z.n_pairs;
+  PhView st{S, U, 6 * P + z.n_super_atoms};
+  st.row_off = c.take<int64_t>(S + 1);
+  st.unit_off = c.take<int64_t>(S + 1);
+  st.pair_off = c.take<int64_t>(S + 1);
+  st.dims = c.take<int32_t>(3 * S);
+  st.lat = c.take<double>(9 * S);
+  st.unit_pos = c.take<double>(3 * U);
+  st.mass = c.take<double>(U);
+  st.unit_struct = c.take<int32_t>(U);
+  st.delta = c.take<double>(1);
+  st.img_count = c.take<int32_t>(P);
+  st.img_d = c.take<double>(3 * kMaxMult * P);
+  return {st, c.off};
 }
 
 __global__ void __launch_bounds__(256) k_ph_displace(PhView st, double* __restrict__ pos) {
@@ -418,7 +404,7 @@ extern "C" int m3g_ph_state_bytes(const m3g_ph_sizes* sizes, size_t* bytes) {
     set_error("m3g_ph_state_bytes: bad sizes (need 1 <= n_structs <= n_unit_atoms <= n_super_atoms <= n_pairs)");
     return M3G_ERR_VALUE;
   }
-  *bytes = ph_layout(*sizes).total;
+  *bytes = ph_view(*sizes, nullptr).bytes;
   return M3G_OK;
 }
 
@@ -482,29 +468,28 @@ extern "C" int m3g_ph_init(const m3g_ph_sizes* sizes, const int64_t* host_unit_o
         std::copy(d.begin(), d.end(), img_d.begin() + 3 * kMaxMult * p);
       }
   }
-  const PhLayout L = ph_layout(z);
-  if (state_bytes < L.total) { set_error("m3g_ph_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
+  const auto [st, total] = ph_view(z, state);
+  if (state_bytes < total) { set_error("m3g_ph_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  char* st = (char*)state;
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.row_off, row_off.data(), 8 * (S + 1), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.unit_off, host_unit_offsets, 8 * (S + 1), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.pair_off, pair_off.data(), 8 * (S + 1), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.dims, host_supercells, 4 * 3 * S, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.lat, host_lattices, 8 * 9 * S, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.unit_pos, host_positions, 8 * 3 * U, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.mass, host_masses, 8 * U, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.unit_struct, unit_struct.data(), 4 * U, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.delta, &delta, 8, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.img_count, img_count.data(), 4 * z.n_pairs, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st + L.img_d, img_d.data(), 8 * img_d.size(), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.row_off, row_off.data(), 8 * (S + 1), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.unit_off, host_unit_offsets, 8 * (S + 1), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.pair_off, pair_off.data(), 8 * (S + 1), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.dims, host_supercells, 4 * 3 * S, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.lat, host_lattices, 8 * 9 * S, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.unit_pos, host_positions, 8 * 3 * U, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.mass, host_masses, 8 * U, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.unit_struct, unit_struct.data(), 4 * U, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.delta, &delta, 8, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.img_count, img_count.data(), 4 * z.n_pairs, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.img_d, img_d.data(), 8 * img_d.size(), hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;
 }
 
 extern "C" int m3g_ph_displace(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, double* pos, void* stream_) {
   if (!ph_sizes_ok(sizes) || !state || !pos) { set_error("m3g_ph_displace: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  if (state_bytes < ph_layout(*sizes).total) { set_error("m3g_ph_displace: state buffer too small"); return M3G_ERR_SIZE; }
-  const PhView st = ph_view(*sizes, state);
+  const auto [st, total] = ph_view(*sizes, state);
+  if (state_bytes < total) { set_error("m3g_ph_displace: state buffer too small"); return M3G_ERR_SIZE; }
   hipLaunchKernelGGL(k_ph_displace, grid_for(st.rows, 256), dim3(256), 0, (hipStream_t)stream_, st, pos);
   M3G_RETURN_LAUNCH_STATUS();
 }
@@ -515,8 +500,8 @@ extern "C" int m3g_ph_force_constants(const m3g_ph_sizes* sizes, const void* sta
     set_error("m3g_ph_force_constants: null argument, bad sizes or asr not 0 / 1");
     return M3G_ERR_VALUE;
   }
-  if (state_bytes < ph_layout(*sizes).total) { set_error("m3g_ph_force_constants: state buffer too small"); return M3G_ERR_SIZE; }
-  const PhView st = ph_view(*sizes, state);
+  const auto [st, total] = ph_view(*sizes, state);
+  if (state_bytes < total) { set_error("m3g_ph_force_constants: state buffer too small"); return M3G_ERR_SIZE; }
   hipLaunchKernelGGL(k_ph_force_constants, dim3((unsigned)st.U), dim3(kFcThreads), 0, (hipStream_t)stream_, st, forces, (int)asr, phi, sums,
                      nonfinite);
   M3G_RETURN_LAUNCH_STATUS();
@@ -532,13 +517,13 @@ int dynmat_call(const char* fn, const m3g_ph_sizes* sizes, const void* state, si
     set_error("%s: null argument, bad sizes, n_q < 0 or max_unit_atoms outside [1, n_unit_atoms]", fn);
     return M3G_ERR_VALUE;
   }
-  if (state_bytes < ph_layout(*sizes).total) { set_error("%s: state buffer too small", fn); return M3G_ERR_SIZE; }
+  const auto [st, total] = ph_view(*sizes, state);
+  if (state_bytes < total) { set_error("%s: state buffer too small", fn); return M3G_ERR_SIZE; }
   if (n_q == 0) return M3G_OK;
   const int64_t pairs = (int64_t)max_unit_atoms * (max_unit_atoms + 1) / 2;
   const int64_t per_q = (pairs + kDynThreads - 1) / kDynThreads;
   const int64_t blocks = n_q * per_q * (kGrad ? 3 : 1);
   if (blocks > (int64_t(1) << 26)) { set_error("%s: too many q-points for one launch", fn); return M3G_ERR_VALUE; }
-  const PhView st = ph_view(*sizes, state);
   hipLaunchKernelGGL(k_ph_dynmat<kGrad>, dim3((unsigned)blocks), dim3(kDynThreads), 0, (hipStream_t)stream_, st, n_q, per_q, q, q_struct,
                      max_unit_atoms, phi, out);
   M3G_RETURN_LAUNCH_STATUS();

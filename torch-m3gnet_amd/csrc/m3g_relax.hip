@@ -19,42 +19,29 @@ namespace m3g {
 namespace {
 constexpr int kCoef = 24;        // per structure: move, c_v, c_g, step scale, F before [9], F after [9], (pad)
 
-struct FireLayout {
-  ChunkLayout chunks;
-  size_t partial, x, v, l0, f, dt, a, n, flags, steps, coef, total;
-};
-FireLayout fire_layout(int64_t N, int64_t S) {
-  FireLayout L{};
-  StateArena arena;
-  const int64_t C = chunk_bound(N, S), R = N + 3 * S;
-  L.chunks = chunk_layout(N, S, arena);
-  L.partial = arena.take(8 * 4 * C);
-  L.x = arena.take(8 * 3 * R);                // rows: the N atoms, then 3 cell rows per structure
-  L.v = arena.take(8 * 3 * R);
-  L.l0 = arena.take(8 * 9 * S);
-  L.f = arena.take(8 * 9 * S);
-  L.dt = arena.take(8 * S);
-  L.a = arena.take(8 * S);
-  L.n = arena.take(4 * S);
-  L.flags = arena.take(4 * S);
-  L.steps = arena.take(4 * S);
-  L.coef = arena.take(8 * kCoef * S);
-  L.total = arena.total;
-  return L;
-}
-
 struct FireView {
   int64_t N;
   ChunkView ch;
   double *partial, *x, *v, *l0, *f, *dt, *a, *coef;
   int32_t *n, *flags, *steps;
 };
-FireView fire_view(int64_t N, int64_t S, void* state) {
-  const FireLayout L = fire_layout(N, S);
-  char* b = (char*)state;
-  return FireView{N, chunk_view(L.chunks, state), (double*)(b + L.partial), (double*)(b + L.x), (double*)(b + L.v), (double*)(b + L.l0),
-                  (double*)(b + L.f), (double*)(b + L.dt), (double*)(b + L.a), (double*)(b + L.coef), (int32_t*)(b + L.n), (int32_t*)(b + L.flags),
-                  (int32_t*)(b + L.steps)};
+Carved<FireView> fire_view(int64_t N, int64_t S, void* state) {
+  Carve c{state};
+  const int64_t C = chunk_bound(N, S), R = N + 3 * S;
+  FireView st{N};
+  st.ch = chunk_view(N, S, c);
+  st.partial = c.take<double>(4 * C);
+  st.x = c.take<double>(3 * R);                // rows: the N atoms, then 3 cell rows per structure
+  st.v = c.take<double>(3 * R);
+  st.l0 = c.take<double>(9 * S);
+  st.f = c.take<double>(9 * S);
+  st.dt = c.take<double>(S);
+  st.a = c.take<double>(S);
+  st.n = c.take<int32_t>(S);
+  st.flags = c.take<int32_t>(S);
+  st.steps = c.take<int32_t>(S);
+  st.coef = c.take<double>(kCoef * S);
+  return {st, c.off};
 }
 
 // g = f F (row vector times the deformation gradient), or f itself with the cell fixed
@@ -266,7 +253,7 @@ using namespace m3g;
 
 extern "C" int m3g_fire_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* bytes) {
   if (!bytes || !batch_sizes_ok(n_atoms, n_structs)) { set_error("m3g_fire_state_bytes: bad sizes"); return M3G_ERR_VALUE; }
-  *bytes = fire_layout(n_atoms, n_structs).total;
+  *bytes = fire_view(n_atoms, n_structs, nullptr).bytes;
   return M3G_OK;
 }
 
@@ -279,13 +266,13 @@ extern "C" int m3g_fire_init(const m3g_fire_params* p, int64_t n_atoms, int64_t 
   }
   const int64_t N = n_atoms, S = n_structs;
   if (!offsets_ok("m3g_fire_init", host_offsets, N, S)) return M3G_ERR_VALUE;
-  const FireLayout L = fire_layout(N, S);
-  if (state_bytes < L.total) { set_error("m3g_fire_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
+  const auto [st, total] = fire_view(N, S, state);
+  if (state_bytes < total) { set_error("m3g_fire_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(L.chunks, (char*)state, host_offsets, s)) return rc;
+  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
   const int64_t work = 3 * N > S ? 3 * N : S;
-  hipLaunchKernelGGL(k_fire_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, fire_view(N, S, state), pos, lattice, p->dt, p->astart);
+  hipLaunchKernelGGL(k_fire_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, st, pos, lattice, p->dt, p->astart);
   M3G_HIP_CHECK(hipGetLastError());
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;
@@ -298,9 +285,9 @@ extern "C" int m3g_fire_step(const m3g_fire_params* p, int64_t n_atoms, int64_t 
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !state || !forces || !pos) { set_error("m3g_fire_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (p->relax_cell && (!stresses || !lattice)) { set_error("m3g_fire_step: a cell relaxation needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
-  if (state_bytes < fire_layout(N, S).total) { set_error("m3g_fire_step: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = fire_view(N, S, state);
+  if (state_bytes < total) { set_error("m3g_fire_step: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const FireView st = fire_view(N, S, state);
   const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_fire_partials, grid, dim3(kChunkRows), 0, s, st, p->relax_cell, forces);
   hipLaunchKernelGGL(k_fire_finalize, dim3(1), dim3(kChunkRows), 0, s, st, *p, check_only, stresses, lattice, lattice32, unconverged);
@@ -312,18 +299,17 @@ extern "C" int m3g_fire_read(int64_t n_atoms, int64_t n_structs, const void* sta
                              double* host_dt, double* host_a, int32_t* host_n, double* host_x, double* host_v, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !state) { set_error("m3g_fire_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  const FireLayout L = fire_layout(N, S);
-  if (state_bytes < L.total) { set_error("m3g_fire_read: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = fire_view(N, S, (void*)state);
+  if (state_bytes < total) { set_error("m3g_fire_read: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const char* b = (const char*)state;
   const int64_t R = N + 3 * S;
-  if (host_flags) M3G_HIP_CHECK(hipMemcpyAsync(host_flags, b + L.flags, 4 * S, hipMemcpyDeviceToHost, s));
-  if (host_steps) M3G_HIP_CHECK(hipMemcpyAsync(host_steps, b + L.steps, 4 * S, hipMemcpyDeviceToHost, s));
-  if (host_dt) M3G_HIP_CHECK(hipMemcpyAsync(host_dt, b + L.dt, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_a) M3G_HIP_CHECK(hipMemcpyAsync(host_a, b + L.a, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_n) M3G_HIP_CHECK(hipMemcpyAsync(host_n, b + L.n, 4 * S, hipMemcpyDeviceToHost, s));
-  if (host_x) M3G_HIP_CHECK(hipMemcpyAsync(host_x, b + L.x, 8 * 3 * R, hipMemcpyDeviceToHost, s));
-  if (host_v) M3G_HIP_CHECK(hipMemcpyAsync(host_v, b + L.v, 8 * 3 * R, hipMemcpyDeviceToHost, s));
+  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
+  M3G_HIP_CHECK(read_back(host_steps, st.steps, S, s));
+  M3G_HIP_CHECK(read_back(host_dt, st.dt, S, s));
+  M3G_HIP_CHECK(read_back(host_a, st.a, S, s));
+  M3G_HIP_CHECK(read_back(host_n, st.n, S, s));
+  M3G_HIP_CHECK(read_back(host_x, st.x, 3 * R, s));
+  M3G_HIP_CHECK(read_back(host_v, st.v, 3 * R, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;
 }

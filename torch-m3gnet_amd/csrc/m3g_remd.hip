@@ -21,30 +21,6 @@ namespace m3g {
 namespace {
 constexpr int kUp = 1, kDown = 2;   // round-trip labels: last end of the ladder touched was index 0 / index R-1 (after index 0)
 
-struct RemdLayout {
-  size_t offsets, held, scale, label, trips, holder, count, mean, m2, attempts, accepts, counter, temps, seed, total;
-};
-RemdLayout remd_layout(int64_t S, int64_t G) {
-  RemdLayout L{};
-  StateArena arena;
-  L.offsets = arena.take(8 * (G + 1));
-  L.held = arena.take(4 * S);       // per replica
-  L.scale = arena.take(8 * S);
-  L.label = arena.take(4 * S);
-  L.trips = arena.take(8 * S);
-  L.holder = arena.take(4 * S);     // per (ladder, temperature index): row lo_g + k
-  L.count = arena.take(8 * S);
-  L.mean = arena.take(8 * S);
-  L.m2 = arena.take(8 * S);
-  L.attempts = arena.take(8 * S);   // per pair (k, k+1): row lo_g + k (row lo_g + R_g - 1 stays 0)
-  L.accepts = arena.take(8 * S);
-  L.counter = arena.take(8 * G);    // per ladder
-  L.temps = arena.take(8 * S);
-  L.seed = arena.take(8 * G);
-  L.total = arena.total;
-  return L;
-}
-
 struct RemdView {
   int64_t S, G;
   const int64_t* offsets;
@@ -54,13 +30,24 @@ struct RemdView {
   const double* temps;
   const uint64_t* seed;
 };
-RemdView remd_view(int64_t S, int64_t G, void* state) {
-  const RemdLayout L = remd_layout(S, G);
-  char* b = (char*)state;
-  return RemdView{S, G, (const int64_t*)(b + L.offsets), (int32_t*)(b + L.held), (int32_t*)(b + L.label), (int32_t*)(b + L.holder),
-                  (double*)(b + L.scale), (double*)(b + L.mean), (double*)(b + L.m2), (int64_t*)(b + L.trips), (int64_t*)(b + L.count),
-                  (int64_t*)(b + L.attempts), (int64_t*)(b + L.accepts), (int64_t*)(b + L.counter), (const double*)(b + L.temps),
-                  (const uint64_t*)(b + L.seed)};
+Carved<RemdView> remd_view(int64_t S, int64_t G, void* state) {
+  Carve c{state};
+  RemdView st{S, G};
+  st.offsets = c.take<int64_t>(G + 1);
+  st.held = c.take<int32_t>(S);       // per replica
+  st.scale = c.take<double>(S);
+  st.label = c.take<int32_t>(S);
+  st.trips = c.take<int64_t>(S);
+  st.holder = c.take<int32_t>(S);     // per (ladder, temperature index): row lo_g + k
+  st.count = c.take<int64_t>(S);
+  st.mean = c.take<double>(S);
+  st.m2 = c.take<double>(S);
+  st.attempts = c.take<int64_t>(S);   // per pair (k, k+1): row lo_g + k (row lo_g + R_g - 1 stays 0)
+  st.accepts = c.take<int64_t>(S);
+  st.counter = c.take<int64_t>(G);    // per ladder
+  st.temps = c.take<double>(S);
+  st.seed = c.take<uint64_t>(G);
+  return {st, c.off};
 }
 
 // One wave (= one workgroup, so __syncthreads is the wave's barrier and makes its writes visible to its other lanes) per ladder.
@@ -144,13 +131,13 @@ using namespace m3g;
 
 extern "C" int m3g_remd_state_bytes(int64_t n_structs, int64_t n_ladders, size_t* bytes) {
   if (!bytes || !remd_sizes_ok(n_structs, n_ladders)) { set_error("m3g_remd_state_bytes: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  *bytes = remd_layout(n_structs, n_ladders).total;
+  *bytes = remd_view(n_structs, n_ladders, nullptr).bytes;
   return M3G_OK;
 }
 
 extern "C" int m3g_remd_target_view(int64_t n_atoms, int64_t n_structs, size_t* temperature_offset) {
   if (!temperature_offset || !batch_sizes_ok(n_atoms, n_structs)) { set_error("m3g_remd_target_view: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  *temperature_offset = dyn_layout(n_atoms, n_structs).t0;
+  *temperature_offset = carve_offset(dyn_view(n_atoms, n_structs, nullptr).view.t0);   // (over a null state: the offset)
   return M3G_OK;
 }
 
@@ -171,22 +158,22 @@ extern "C" int m3g_remd_init(int64_t n_structs, int64_t n_ladders, const int64_t
         return M3G_ERR_VALUE;
       }
   }
-  const RemdLayout L = remd_layout(S, G);
-  if (state_bytes < L.total) { set_error("m3g_remd_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
-  std::vector<char> image(L.total, 0);   // counts, means, accepts and the attempt counters start at zero
-  char* b = image.data();
-  std::memcpy(b + L.offsets, host_ladder_offsets, 8 * (G + 1));
-  std::memcpy(b + L.temps, host_temperatures, 8 * S);
-  std::memcpy(b + L.seed, host_seeds, 8 * G);
+  const size_t total = remd_view(S, G, nullptr).bytes;
+  if (state_bytes < total) { set_error("m3g_remd_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  std::vector<char> image(total, 0);   // counts, means, accepts and the attempt counters start at zero
+  const RemdView im = remd_view(S, G, image.data()).view;
+  std::memcpy((void*)im.offsets, host_ladder_offsets, 8 * (G + 1));
+  std::memcpy((void*)im.temps, host_temperatures, 8 * S);
+  std::memcpy((void*)im.seed, host_seeds, 8 * G);
   for (int64_t g = 0; g < G; ++g)
     for (int64_t lo = host_ladder_offsets[g], r = lo; r < host_ladder_offsets[g + 1]; ++r) {
-      ((int32_t*)(b + L.held))[r] = (int32_t)(r - lo);
-      ((int32_t*)(b + L.holder))[r] = (int32_t)r;
-      ((int32_t*)(b + L.label))[r] = r == lo ? kUp : 0;
-      ((double*)(b + L.scale))[r] = 1.0;
+      im.held[r] = (int32_t)(r - lo);
+      im.holder[r] = (int32_t)r;
+      im.label[r] = r == lo ? kUp : 0;
+      im.scale[r] = 1.0;
     }
   hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(hipMemcpyAsync(state, b, L.total, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(state, image.data(), total, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host image above goes out of scope)
   return M3G_OK;
 }
@@ -198,11 +185,11 @@ extern "C" int m3g_remd_exchange(int64_t n_atoms, int64_t n_structs, int64_t n_l
     set_error("m3g_remd_exchange: null argument or bad sizes");
     return M3G_ERR_VALUE;
   }
-  if (remd_bytes < remd_layout(S, G).total) { set_error("m3g_remd_exchange: replica-exchange state buffer too small"); return M3G_ERR_SIZE; }
-  if (dyn_bytes < dyn_layout(N, S).total) { set_error("m3g_remd_exchange: dynamics state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, remd_total] = remd_view(S, G, remd_state);
+  const auto [dyn, dyn_total] = dyn_view(N, S, dyn_state);
+  if (remd_bytes < remd_total) { set_error("m3g_remd_exchange: replica-exchange state buffer too small"); return M3G_ERR_SIZE; }
+  if (dyn_bytes < dyn_total) { set_error("m3g_remd_exchange: dynamics state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const RemdView st = remd_view(S, G, remd_state);
-  const DynView dyn = dyn_view(N, S, dyn_state);
   hipLaunchKernelGGL(k_remd_decide, dim3((unsigned)G), dim3(kWave), 0, s, st, dyn.t0, dyn.flags, energies, history, history_rows);
   hipLaunchKernelGGL(k_remd_rescale, dim3((unsigned)chunk_bound(N, S)), dim3(kChunkRows), 0, s, dyn, st.scale);
   M3G_RETURN_LAUNCH_STATUS();
@@ -213,19 +200,18 @@ extern "C" int m3g_remd_read(int64_t n_structs, int64_t n_ladders, const void* s
                              double* host_m2, int64_t* host_round_trips, int64_t* host_counters, void* stream_) {
   const int64_t S = n_structs, G = n_ladders;
   if (!remd_sizes_ok(S, G) || !state) { set_error("m3g_remd_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  const RemdLayout L = remd_layout(S, G);
-  if (state_bytes < L.total) { set_error("m3g_remd_read: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = remd_view(S, G, (void*)state);
+  if (state_bytes < total) { set_error("m3g_remd_read: state buffer too small"); return M3G_ERR_SIZE; }
   hipStream_t s = (hipStream_t)stream_;
-  const char* b = (const char*)state;
-  if (host_held) M3G_HIP_CHECK(hipMemcpyAsync(host_held, b + L.held, 4 * S, hipMemcpyDeviceToHost, s));
-  if (host_holder) M3G_HIP_CHECK(hipMemcpyAsync(host_holder, b + L.holder, 4 * S, hipMemcpyDeviceToHost, s));
-  if (host_attempts) M3G_HIP_CHECK(hipMemcpyAsync(host_attempts, b + L.attempts, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_accepts) M3G_HIP_CHECK(hipMemcpyAsync(host_accepts, b + L.accepts, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_count) M3G_HIP_CHECK(hipMemcpyAsync(host_count, b + L.count, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_mean) M3G_HIP_CHECK(hipMemcpyAsync(host_mean, b + L.mean, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_m2) M3G_HIP_CHECK(hipMemcpyAsync(host_m2, b + L.m2, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_round_trips) M3G_HIP_CHECK(hipMemcpyAsync(host_round_trips, b + L.trips, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_counters) M3G_HIP_CHECK(hipMemcpyAsync(host_counters, b + L.counter, 8 * G, hipMemcpyDeviceToHost, s));
+  M3G_HIP_CHECK(read_back(host_held, st.held, S, s));
+  M3G_HIP_CHECK(read_back(host_holder, st.holder, S, s));
+  M3G_HIP_CHECK(read_back(host_attempts, st.attempts, S, s));
+  M3G_HIP_CHECK(read_back(host_accepts, st.accepts, S, s));
+  M3G_HIP_CHECK(read_back(host_count, st.count, S, s));
+  M3G_HIP_CHECK(read_back(host_mean, st.mean, S, s));
+  M3G_HIP_CHECK(read_back(host_m2, st.m2, S, s));
+  M3G_HIP_CHECK(read_back(host_round_trips, st.trips, S, s));
+  M3G_HIP_CHECK(read_back(host_counters, st.counter, G, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;
 }

@@ -44,35 +44,6 @@ inline int64_t pair_bound(int64_t N, int64_t S) {
   return t * (t + 1) / 2 + (S - 1);
 }
 
-struct TrajLayout {
-  ChunkLayout chunks;
-  size_t species, nspec, mass, pairs, ctr, flags, n_samples, volume, hist, msd, vacf, lag_count, zero_end, com, partial, ring, total;
-};
-TrajLayout traj_layout(const m3g_traj_sizes& z) {
-  const int64_t N = z.n_atoms, S = z.n_structs, M = z.max_species, B = z.rdf_bins, G = z.n_lags, C = chunk_bound(N, S);
-  TrajLayout L{};
-  StateArena arena;
-  L.chunks = chunk_layout(N, S, arena);
-  L.species = arena.take(4 * N);
-  L.nspec = arena.take(4 * S);
-  L.mass = arena.take(8 * N);
-  L.pairs = arena.take(B ? sizeof(TilePair) * pair_bound(N, S) : 0);
-  L.ctr = arena.take(8 * kCounters);   // the accumulators from here to zero_end are cleared by the init call
-  L.flags = arena.take(4 * S);
-  L.n_samples = arena.take(8 * S);
-  L.volume = arena.take(8 * S);
-  L.hist = arena.take(8 * S * species_pairs((int)M) * B);
-  L.msd = arena.take(8 * S * M * G);
-  L.vacf = arena.take(8 * S * M * G);
-  L.lag_count = arena.take(8 * S * G);
-  L.zero_end = arena.total;
-  L.com = arena.take(G ? 8 * kComPart * C : 0);
-  L.partial = arena.take(8 * 2 * M * G * C);
-  L.ring = arena.take(48 * G * N);
-  L.total = arena.total;
-  return L;
-}
-
 struct TrajView {
   int64_t N;
   int32_t M, B, G;
@@ -90,14 +61,27 @@ struct TrajView {
   double *com, *partial;
   double2* ring;   // [G][3][N]: (x, y), (z, vx), (vy, vz) of atom i at [slot][0..2][i]
 };
-TrajView traj_view(const m3g_traj_sizes& z, void* state) {
-  const TrajLayout L = traj_layout(z);
-  char* b = (char*)state;
-  return TrajView{z.n_atoms, z.max_species, z.rdf_bins, z.n_lags, chunk_view(L.chunks, state), (const int32_t*)(b + L.species),
-                  (const int32_t*)(b + L.nspec), (const double*)(b + L.mass), (const TilePair*)(b + L.pairs), (int64_t*)(b + L.ctr),
-                  (int32_t*)(b + L.flags), (int64_t*)(b + L.n_samples), (double*)(b + L.volume), (unsigned long long*)(b + L.hist),
-                  (double*)(b + L.msd), (double*)(b + L.vacf), (int64_t*)(b + L.lag_count), (double*)(b + L.com), (double*)(b + L.partial),
-                  (double2*)(b + L.ring)};
+Carved<TrajView> traj_view(const m3g_traj_sizes& z, void* state) {
+  const int64_t N = z.n_atoms, S = z.n_structs, M = z.max_species, B = z.rdf_bins, G = z.n_lags, C = chunk_bound(N, S);
+  Carve c{state};
+  TrajView st{N, z.max_species, z.rdf_bins, z.n_lags};
+  st.ch = chunk_view(N, S, c);
+  st.species = c.take<int32_t>(N);
+  st.nspec = c.take<int32_t>(S);
+  st.mass = c.take<double>(N);
+  st.pairs = c.take<TilePair>(B ? pair_bound(N, S) : 0);
+  st.ctr = c.take<int64_t>(kCounters);   // the accumulators from here up to `com` are cleared by the init call
+  st.flags = c.take<int32_t>(S);
+  st.n_samples = c.take<int64_t>(S);
+  st.volume = c.take<double>(S);
+  st.hist = c.take<unsigned long long>(S * species_pairs((int)M) * B);
+  st.msd = c.take<double>(S * M * G);
+  st.vacf = c.take<double>(S * M * G);
+  st.lag_count = c.take<int64_t>(S * G);
+  st.com = c.take<double>(G ? kComPart * C : 0);
+  st.partial = c.take<double>(2 * M * G * C);
+  st.ring = c.take<double2>(3 * G * N);
+  return {st, c.off};
 }
 
 template <bool kLds>
@@ -320,7 +304,7 @@ extern "C" int m3g_traj_state_bytes(const m3g_traj_sizes* sizes, size_t* bytes) 
   const m3g_traj_params* any = &kNoRdf;
   if (const char* why = traj_error(sizes, any)) { set_error("m3g_traj_state_bytes: %s", why); return M3G_ERR_VALUE; }
   if (!bytes) { set_error("m3g_traj_state_bytes: null argument"); return M3G_ERR_VALUE; }
-  *bytes = traj_layout(*sizes).total;
+  *bytes = traj_view(*sizes, nullptr).bytes;
   return M3G_OK;
 }
 
@@ -340,8 +324,8 @@ extern "C" int m3g_traj_init(const m3g_traj_sizes* sizes, const m3g_traj_params*
       if (!finite_positive(host_masses[i])) { set_error("m3g_traj_init: mass of atom %lld is not finite and > 0", (long long)i); return M3G_ERR_VALUE; }
       if (host_species[i] >= nspec[s]) nspec[s] = host_species[i] + 1;
     }
-  const TrajLayout L = traj_layout(*sizes);
-  if (state_bytes < L.total) { set_error("m3g_traj_init: state buffer too small (%zu < %zu)", state_bytes, L.total); return M3G_ERR_SIZE; }
+  const auto [st, total] = traj_view(*sizes, state);
+  if (state_bytes < total) { set_error("m3g_traj_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
   std::vector<TilePair> pairs;
   if (sizes->rdf_bins > 0)
     for (int64_t s = 0; s < S; ++s)
@@ -351,14 +335,13 @@ extern "C" int m3g_traj_init(const m3g_traj_sizes* sizes, const m3g_traj_params*
   const int64_t ctr[kCounters] = {0, 0, (int64_t)pairs.size(), 0};
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  char* b = (char*)state;
-  if (int rc = table.upload(L.chunks, b, host_offsets, s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.species, host_species, 4 * N, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.nspec, nspec.data(), 4 * S, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.mass, host_masses, 8 * N, hipMemcpyHostToDevice, s));
-  if (!pairs.empty()) M3G_HIP_CHECK(hipMemcpyAsync(b + L.pairs, pairs.data(), sizeof(TilePair) * pairs.size(), hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemsetAsync(b + L.ctr, 0, L.zero_end - L.ctr, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(b + L.ctr, ctr, sizeof(ctr), hipMemcpyHostToDevice, s));
+  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.species, host_species, 4 * N, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.nspec, nspec.data(), 4 * S, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.mass, host_masses, 8 * N, hipMemcpyHostToDevice, s));
+  if (!pairs.empty()) M3G_HIP_CHECK(hipMemcpyAsync((void*)st.pairs, pairs.data(), sizeof(TilePair) * pairs.size(), hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipMemsetAsync(st.ctr, 0, (size_t)((const char*)st.com - (const char*)st.ctr), s));
+  M3G_HIP_CHECK(hipMemcpyAsync(st.ctr, ctr, sizeof(ctr), hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
   return M3G_OK;
 }
@@ -369,10 +352,10 @@ extern "C" int m3g_traj_sample(const m3g_traj_sizes* sizes, const m3g_traj_param
   const bool rdf = sizes->rdf_bins > 0, lags = sizes->n_lags > 0;
   if (!state || !pos || (rdf && !lattice) || (lags && !vel)) { set_error("m3g_traj_sample: null argument"); return M3G_ERR_VALUE; }
   if (forces && !std::isfinite(kick)) { set_error("m3g_traj_sample: kick must be finite"); return M3G_ERR_VALUE; }
-  if (state_bytes < traj_layout(*sizes).total) { set_error("m3g_traj_sample: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = traj_view(*sizes, state);
+  if (state_bytes < total) { set_error("m3g_traj_sample: state buffer too small"); return M3G_ERR_SIZE; }
   const int64_t N = sizes->n_atoms, S = sizes->n_structs;
   hipStream_t s = (hipStream_t)stream_;
-  const TrajView st = traj_view(*sizes, state);
   if (rdf) {   // workgroups beyond the table's pair count return at once
     const dim3 grid((unsigned)pair_bound(N, S));
     const size_t lds = sizeof(unsigned int) * species_pairs(sizes->max_species) * sizes->rdf_bins;
@@ -397,18 +380,17 @@ extern "C" int m3g_traj_read(const m3g_traj_sizes* sizes, const void* state, siz
                              void* stream_) {
   if (const char* why = traj_error(sizes, &kNoRdf)) { set_error("m3g_traj_read: %s", why); return M3G_ERR_VALUE; }
   if (!state) { set_error("m3g_traj_read: null argument"); return M3G_ERR_VALUE; }
-  const TrajLayout L = traj_layout(*sizes);
-  if (state_bytes < L.total) { set_error("m3g_traj_read: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = traj_view(*sizes, (void*)state);
+  if (state_bytes < total) { set_error("m3g_traj_read: state buffer too small"); return M3G_ERR_SIZE; }
   const size_t S = sizes->n_structs, M = sizes->max_species, B = sizes->rdf_bins, G = sizes->n_lags;
   hipStream_t s = (hipStream_t)stream_;
-  const char* b = (const char*)state;
-  if (host_hist && B) M3G_HIP_CHECK(hipMemcpyAsync(host_hist, b + L.hist, 8 * S * species_pairs((int)M) * B, hipMemcpyDeviceToHost, s));
-  if (host_msd && G) M3G_HIP_CHECK(hipMemcpyAsync(host_msd, b + L.msd, 8 * S * M * G, hipMemcpyDeviceToHost, s));
-  if (host_vacf && G) M3G_HIP_CHECK(hipMemcpyAsync(host_vacf, b + L.vacf, 8 * S * M * G, hipMemcpyDeviceToHost, s));
-  if (host_lag_count && G) M3G_HIP_CHECK(hipMemcpyAsync(host_lag_count, b + L.lag_count, 8 * S * G, hipMemcpyDeviceToHost, s));
-  if (host_n_samples) M3G_HIP_CHECK(hipMemcpyAsync(host_n_samples, b + L.n_samples, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_volume_sum) M3G_HIP_CHECK(hipMemcpyAsync(host_volume_sum, b + L.volume, 8 * S, hipMemcpyDeviceToHost, s));
-  if (host_flags) M3G_HIP_CHECK(hipMemcpyAsync(host_flags, b + L.flags, 4 * S, hipMemcpyDeviceToHost, s));
+  M3G_HIP_CHECK(read_back((unsigned long long*)host_hist, st.hist, S * species_pairs((int)M) * B, s));
+  M3G_HIP_CHECK(read_back(host_msd, st.msd, S * M * G, s));
+  M3G_HIP_CHECK(read_back(host_vacf, st.vacf, S * M * G, s));
+  M3G_HIP_CHECK(read_back(host_lag_count, st.lag_count, S * G, s));
+  M3G_HIP_CHECK(read_back(host_n_samples, st.n_samples, S, s));
+  M3G_HIP_CHECK(read_back(host_volume_sum, st.volume, S, s));
+  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;
 }
@@ -417,17 +399,16 @@ extern "C" int m3g_traj_frame(const m3g_traj_sizes* sizes, const void* state, si
                               void* stream_) {
   if (const char* why = traj_error(sizes, &kNoRdf)) { set_error("m3g_traj_frame: %s", why); return M3G_ERR_VALUE; }
   if (!state || !host_pos || !host_vel || sizes->n_lags == 0) { set_error("m3g_traj_frame: null argument or no ring (n_lags == 0)"); return M3G_ERR_VALUE; }
-  const TrajLayout L = traj_layout(*sizes);
-  if (state_bytes < L.total) { set_error("m3g_traj_frame: state buffer too small"); return M3G_ERR_SIZE; }
+  const auto [st, total] = traj_view(*sizes, (void*)state);
+  if (state_bytes < total) { set_error("m3g_traj_frame: state buffer too small"); return M3G_ERR_SIZE; }
   const int64_t N = sizes->n_atoms, G = sizes->n_lags;
   hipStream_t s = (hipStream_t)stream_;
-  const char* b = (const char*)state;
   int64_t ctr[kCounters];
-  M3G_HIP_CHECK(hipMemcpyAsync(ctr, b + L.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(ctr, st.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   if (lag < 0 || lag >= G || lag >= ctr[kDone]) { set_error("m3g_traj_frame: no frame %d samples back", (int)lag); return M3G_ERR_VALUE; }
   std::vector<double2> slot(3 * N);
-  M3G_HIP_CHECK(hipMemcpyAsync(slot.data(), b + L.ring + 48 * N * (size_t)((ctr[kDone] - 1 - lag) % G), 48 * N, hipMemcpyDeviceToHost, s));
+  M3G_HIP_CHECK(hipMemcpyAsync(slot.data(), st.ring + 3 * N * ((ctr[kDone] - 1 - lag) % G), 48 * N, hipMemcpyDeviceToHost, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   for (int64_t i = 0; i < N; ++i) {
     host_pos[3 * i] = slot[i].x; host_pos[3 * i + 1] = slot[i].y; host_pos[3 * i + 2] = slot[N + i].x;

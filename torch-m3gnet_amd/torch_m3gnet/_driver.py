@@ -1,6 +1,8 @@
-"""What the batched drivers (relax, dynamics, neb, phonons, elasticity) share on the host: argument checks, the model every driver
-evaluates, state allocation and the split of one structure's copies into engine sub-batches.  The FIRE loop they share is
-`relax.fire_loop`, beside `fire_step`; the status read after the last evaluation is `VerletGraph.raise_on_step_errors`."""
+"""What the batched drivers (relax, dynamics, replica_exchange, monte_carlo, trajectory, neb, phonons, elasticity) share on the host:
+argument checks, the model every driver evaluates, state allocation and read-back, the split of one structure's copies into engine
+sub-batches, the evaluation of a batch in engine groups (`GroupedEvaluation`: replica_exchange, monte_carlo) and the log and result
+dicts of an MD run (`MdLog`, `md_result`: dynamics, replica_exchange).  The optimiser loop relax and neb share is `relax.fire_loop`,
+beside `fire_step` / `lbfgs_step`; the status read after the last evaluation is `VerletGraph.raise_on_step_errors`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,8 +11,11 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _cuda, _lib
+from .data import MaterialGraphKey as K
 from .data.atomic_masses import masses_of
+from .data.graph_gpu import _ptr, _stream
+from .data.md import VerletGraph
 from .nn.modules import Gradient
 
 EV_A3_TO_GPA = 160.21766208
@@ -20,6 +25,13 @@ def positive(name: str, x) -> float:
     x = float(x)
     if not (math.isfinite(x) and x > 0.0):
         raise ValueError(f"{name} must be a finite number > 0; got {x}")
+    return x
+
+
+def non_negative(name: str, x) -> float:
+    x = float(x)
+    if not (math.isfinite(x) and x >= 0.0):
+        raise ValueError(f"{name} must be a finite number >= 0; got {x}")
     return x
 
 
@@ -67,6 +79,18 @@ def structure_masses(masses, z) -> list:
     return m
 
 
+def per_structure(name: str, x: np.ndarray, n_structs: int) -> np.ndarray:
+    """[S] view of `x` (checked at construction: 0-d or 1-d): the one value for every structure, or the caller's S values."""
+    if x.ndim != 0 and len(x) != n_structs:
+        raise ValueError(f"{name}: expected one value or one per structure ({n_structs}); got {len(x)}")
+    return np.broadcast_to(x, (n_structs,))
+
+
+def atom_offsets(z: list) -> np.ndarray:
+    """S + 1 atom offsets of a batch from its per-structure arrays (species, say)."""
+    return np.concatenate([[0], np.cumsum([len(a) for a in z])])
+
+
 def check_tensor(name: str, x: torch.Tensor, shape: tuple, dtype: torch.dtype, device=None) -> None:
     """`x` is a contiguous `dtype` tensor of `shape` (a string entry stands for any size), on `device` when one is given."""
     fits = x.dim() == len(shape) and all(isinstance(n, str) or d == n for d, n in zip(x.shape, shape))
@@ -101,6 +125,15 @@ def state_tensor(state_bytes, *sizes, device) -> torch.Tensor:
     return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
 
 
+def read_state(read, sizes: tuple, state: torch.Tensor, fields) -> dict:
+    """A state's arrays copied to the host by its m3g_*_read (waits for the stream).  `fields`: (name, dtype, shape) in the order of the
+    host pointers `read` takes after (*sizes, state, state_bytes)."""
+    out = {name: np.empty(shape, dtype) for name, dtype, shape in fields}
+    with _cuda.on_device(state.device):
+        _lib.check(read(*sizes, _ptr(state), state.numel(), *(a.ctypes.data for a in out.values()), _stream()))
+    return out
+
+
 def sub_batches(n_copies: int, n: int, max_atoms: int):
     """(first_copy, count) of the engine sub-batches of `n_copies` copies of one structure of `n` atoms: in order, at most `max_atoms`
     atoms each (at least one copy).  The engine's rounding depends on the composition of its batch, so a structure's sub-batches hold
@@ -122,3 +155,72 @@ class Driver:
         if model._engine is not None:
             self.model.engine.set_precision(model._engine.precision)
         self.device = torch.device(device)
+
+
+class GroupedEvaluation:
+    """The engine evaluation of a batch cut into groups of consecutive structures, one `VerletGraph` (one engine batch) per group: the
+    engine's fp32 rounding depends on the composition of its batch, so a structure's numbers are bitwise the same alone or beside
+    others only when its group holds nothing else.  `groups`: (first, last) structure spans that cover the batch in order."""
+
+    def __init__(self, model: Gradient, lat: list, z: list, groups: list, skin: float, device):
+        cfg = model.engine.cfg
+        self.model, self.spans = model, groups
+        self.graphs = [VerletGraph(lat[lo:hi], z[lo:hi], cfg.cutoff, cfg.threebody_cutoff, skin=skin, device=device) for lo, hi in groups]
+        self.device = self.graphs[0].device
+        self.offsets = atom_offsets(z)
+        self.N, self.S = int(self.offsets[-1]), len(z)
+        self.rows = [(int(self.offsets[lo]), int(self.offsets[hi])) for lo, hi in groups]
+
+    def lattices(self) -> torch.Tensor:
+        """[S,3,3] fp64, a copy of the graphs' cells."""
+        return torch.cat([vg.lattice for vg in self.graphs]).clone()
+
+    def buffers(self, forces: bool = True) -> dict:
+        """Whole-batch float32 tensors for `evaluate(into=...)`; without `forces` the energies only (forces and stresses None)."""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        return {K.TOTAL_ENERGY: torch.empty(self.S, **f32), K.FORCES: torch.empty(self.N, 3, **f32) if forces else None,
+                K.STRESSES: torch.empty(self.S, 6, **f32) if forces else None}
+
+    def evaluate(self, pos: torch.Tensor, into: dict | None = None, forces: bool = True) -> dict:
+        """Energies (and, with `forces`, forces and stresses) of the whole batch at `pos` [N,3]: every group's `VerletGraph.step` --
+        each waits for its skin test, as in `MolecularDynamics.run`: the only waits -- copied into the tensors of `into`, which is
+        returned.  `into` None (one group only): that group's own output tensors."""
+        if into is None:
+            (vg,) = self.graphs
+            return vg.step(self.model, pos, forces=forces)
+        for vg, (a, b), (lo, hi) in zip(self.graphs, self.rows, self.spans):
+            part = vg.step(self.model, pos[a:b], forces=forces)
+            into[K.TOTAL_ENERGY][lo:hi].copy_(part[K.TOTAL_ENERGY])
+            if forces:
+                into[K.FORCES][a:b].copy_(part[K.FORCES])
+                into[K.STRESSES][lo:hi].copy_(part[K.STRESSES])
+        return into
+
+    def raise_on_step_errors(self, what: str) -> None:
+        for vg in self.graphs:
+            vg.raise_on_step_errors(what)
+
+
+class MdLog:
+    """The log of an MD run: step, e_pot, ke (eV), t (K), p (GPa), v (A^3) of every structure at the steps `append` is called."""
+
+    def __init__(self):
+        self.rows = {key: [] for key in ("step", "e_pot", "ke", "t", "p", "v")}
+
+    def append(self, k: int, energies: torch.Tensor, obs: torch.Tensor) -> None:
+        """Step `k` at `energies` [S] and `DynState.obs` [S,4] (copies both to the host: waits)."""
+        obs = obs.cpu().numpy()
+        self.rows["step"].append(np.full(len(obs), k))
+        self.rows["e_pot"].append(energies.double().cpu().numpy())
+        for j, key in enumerate(("ke", "t", "p", "v")):
+            self.rows[key].append(obs[:, j] * (EV_A3_TO_GPA if key == "p" else 1.0))
+
+    def arrays(self) -> dict:
+        return {key: np.stack(val, axis=1) for key, val in self.rows.items()}   # [S, n_log]
+
+
+def md_result(s: int, a: int, b: int, p_host, st: dict, l_host, e, f, sv, logs: dict) -> dict:
+    """The dict `MolecularDynamics.run` returns for structure `s` (atoms a .. b) from the host copies of the batch; `st`: `DynState.read()`."""
+    return {"positions": p_host[a:b].copy(), "velocities": st["v"][a:b].copy(), "lattice": l_host[s].copy(),
+            "total_energy": float(e[s]), "forces": f[a:b].copy(), "stresses": sv[s].copy(), "n_steps": int(st["n_steps"][s]),
+            "error": bool(st["flags"][s] & _lib.DYN_ERROR), "log": {key: val[s].copy() for key, val in logs.items()}}

@@ -21,8 +21,8 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import (EV_A3_TO_GPA, Driver, batch_layout, check_tensor, integer, positive, state_tensor, structure_arrays,
-                      structure_masses)
+from ._driver import (EV_A3_TO_GPA, Driver, MdLog, atom_offsets, batch_layout, check_tensor, integer, md_result, non_negative,
+                      per_structure, positive, read_state, state_tensor, structure_arrays, structure_masses)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
 from .data.md import VerletGraph
@@ -107,11 +107,8 @@ class DynState:
 
     def read(self) -> dict:
         """flags / n_steps [S] and the velocities [N, 3], copied to the host (waits for the stream)."""
-        out = {"flags": np.empty(self.S, np.int32), "n_steps": np.empty(self.S, np.int64), "v": np.empty((self.N, 3))}
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_dyn_read(self.N, self.S, _ptr(self.state), self.state.numel(), out["flags"].ctypes.data,
-                                             out["n_steps"].ctypes.data, out["v"].ctypes.data, _stream()))
-        return out
+        return read_state(self.lib.m3g_dyn_read, (self.N, self.S), self.state,
+                          (("flags", np.int32, self.S), ("n_steps", np.int64, self.S), ("v", np.float64, (self.N, 3))))
 
 
 def dyn_step(state: DynState, forces: torch.Tensor, stresses: torch.Tensor | None = None, finish_only: bool = False) -> None:
@@ -146,10 +143,7 @@ class MolecularDynamics(Driver):
         self.timestep = positive("timestep", timestep)
         self.taut = positive("taut", 100.0 * self.timestep if taut is None else taut)
         self.taup = positive("taup", 1000.0 * self.timestep if taup is None else taup)
-        friction = float(friction)
-        if not (math.isfinite(friction) and friction >= 0.0):
-            raise ValueError(f"friction must be a finite number >= 0; got {friction}")
-        self.friction = friction
+        self.friction = non_negative("friction", friction)
         self.pressure = float(pressure)
         if not math.isfinite(self.pressure):
             raise ValueError(f"pressure must be finite; got {self.pressure}")
@@ -189,9 +183,7 @@ class MolecularDynamics(Driver):
         steps, loginterval = integer("steps", steps, 0), integer("loginterval", loginterval, 1)
         lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
         S = len(z)
-        temps = np.broadcast_to(self.temperature, (S,)) if self.temperature.ndim == 0 or len(self.temperature) == S else None
-        if temps is None:
-            raise ValueError(f"temperature: expected one value or one per structure ({S}); got {len(self.temperature)}")
+        temps = per_structure("temperature", self.temperature, S)
         seeds = structure_seeds(self.seed, S)
         m = structure_masses(masses, z)
         if velocities is None:
@@ -207,13 +199,13 @@ class MolecularDynamics(Driver):
         cfg = model.engine.cfg
         vg = VerletGraph(lat, z, cfg.cutoff, cfg.threebody_cutoff, skin=self.skin, device=self.device)
         pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=vg.device)
-        offsets = np.concatenate([[0], np.cumsum([len(a) for a in z])])
+        offsets = atom_offsets(z)
         lat64 = vg.lattice.clone()   # the NPT launches write the scaled cells here
         npt = self.ensemble == "npt_berendsen"
         dyn = DynState(pos_t, lat64, offsets, np.concatenate(m), torch.tensor(np.concatenate(vel), device=vg.device), temps, seeds,
                        **self._params())
         traj = observables.begin(lat, z, m, vg.device) if observables is not None else None
-        log = {key: [] for key in ("step", "e_pot", "ke", "t", "p", "v")}
+        log = MdLog()
         out = None
         for k in range(steps + 1):
             out = vg.step(model, pos_t)   # waits for the skin test (the previous dyn_step has been queued before it)
@@ -221,24 +213,15 @@ class MolecularDynamics(Driver):
                 traj_sample(traj, pos_t, lat64, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
             dyn_step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=(k == steps))
             if k % loginterval == 0 or k == steps:   # (host copies on log steps only)
-                obs = dyn.obs.cpu().numpy()
-                log["step"].append(np.full(S, k))
-                log["e_pot"].append(out[K.TOTAL_ENERGY].double().cpu().numpy())
-                for j, key in enumerate(("ke", "t", "p", "v")):
-                    log[key].append(obs[:, j] * (EV_PER_A3_IN_GPA if key == "p" else 1.0))
+                log.append(k, out[K.TOTAL_ENERGY], dyn.obs)
             if npt and k < steps:
                 vg.set_lattice(list(lat64.cpu().numpy()))   # (waits: the candidate search in the new cells needs them on the host)
         vg.raise_on_step_errors("molecular dynamics")
         st = dyn.read()
         e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
         p_host, l_host = pos_t.cpu().numpy(), lat64.cpu().numpy()
-        logs = {key: np.stack(val, axis=1) for key, val in log.items()}   # [S, n_log]
-        res = []
-        for s in range(S):
-            a, b = int(offsets[s]), int(offsets[s + 1])
-            res.append({"positions": p_host[a:b].copy(), "velocities": st["v"][a:b].copy(), "lattice": l_host[s].copy(),
-                        "total_energy": float(e[s]), "forces": f[a:b].copy(), "stresses": sv[s].copy(), "n_steps": int(st["n_steps"][s]),
-                        "error": bool(st["flags"][s] & _lib.DYN_ERROR), "log": {key: val[s].copy() for key, val in logs.items()}})
+        logs = log.arrays()
+        res = [md_result(s, int(offsets[s]), int(offsets[s + 1]), p_host, st, l_host, e, f, sv, logs) for s in range(S)]
         if traj is not None:
             for r, obs in zip(res, observables.results(traj, self.timestep)):
                 r["observables"] = obs

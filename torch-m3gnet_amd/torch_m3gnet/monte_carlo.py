@@ -18,10 +18,10 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import Driver, boolean, check_tensor, integer, positive, state_tensor, structure_arrays, structure_masses
+from ._driver import (Driver, GroupedEvaluation, boolean, check_tensor, integer, non_negative, per_structure, positive, read_state,
+                      state_tensor, structure_arrays, structure_masses)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
-from .data.md import VerletGraph
 from .dynamics import KB, DynState, dyn_step, maxwell_boltzmann, structure_seeds
 from .nn.modules import Gradient
 
@@ -55,13 +55,10 @@ class McState:
         """flags (int32), n_proposals, attempts, accepts, nonfinite, count (int64), mean, m2 (fp64) [S] and the last attempted pair
         [S, 2] (int32, rows relative to the structure), copied to the host (waits for the stream)."""
         S = self.S
-        out = {"flags": np.empty(S, np.int32), "n_proposals": np.empty(S, np.int64), "attempts": np.empty(S, np.int64),
-               "accepts": np.empty(S, np.int64), "nonfinite": np.empty(S, np.int64), "count": np.empty(S, np.int64), "mean": np.empty(S),
-               "m2": np.empty(S), "pair": np.empty((S, 2), np.int32)}
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_mc_read(self.N, S, _ptr(self.state), self.state.numel(), *(a.ctypes.data for a in out.values()),
-                                            _stream()))
-        return out
+        return read_state(self.lib.m3g_mc_read, (self.N, S), self.state,
+                          (("flags", np.int32, S), ("n_proposals", np.int64, S), ("attempts", np.int64, S), ("accepts", np.int64, S),
+                           ("nonfinite", np.int64, S), ("count", np.int64, S), ("mean", np.float64, S), ("m2", np.float64, S),
+                           ("pair", np.int32, (S, 2))))
 
 
 def _dyn_args(state: McState, dyn: DynState | None):
@@ -131,10 +128,7 @@ class SwapMonteCarlo(Driver):
         self.structure_batches = boolean("structure_batches", structure_batches)
         self.md_steps = integer("md_steps", md_steps, 0)
         self.timestep = positive("timestep", timestep)
-        friction = float(friction)
-        if not (np.isfinite(friction) and friction >= 0.0):
-            raise ValueError(f"friction must be a finite number >= 0; got {friction}")
-        self.friction = friction
+        self.friction = non_negative("friction", friction)
         t = np.asarray(temperature, dtype=np.float64)
         if t.ndim > 1 or t.size == 0 or not (np.isfinite(t).all() and (t > 0).all()):
             raise ValueError("temperature must be one finite value > 0 (K) or one per structure")
@@ -174,43 +168,24 @@ class SwapMonteCarlo(Driver):
         trials, loginterval = integer("trials", trials, 0), integer("loginterval", loginterval, 1)
         lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
         S = len(z)
-        temps = np.broadcast_to(self.temperature, (S,)) if self.temperature.ndim == 0 or len(self.temperature) == S else None
-        if temps is None:
-            raise ValueError(f"temperature: expected one value or one per structure ({S}); got {len(self.temperature)}")
+        temps = per_structure("temperature", self.temperature, S)
         active = self._mask(z, sites)
         seeds = structure_seeds(self.seed, S)
         hybrid = self.md_steps > 0
         m = structure_masses(masses, z)
-        model = self.model
-        cfg = model.engine.cfg
         groups = [(s, s + 1) for s in range(S)] if self.structure_batches else [(0, S)]
-        graphs = [VerletGraph(lat[lo:hi], z[lo:hi], cfg.cutoff, cfg.threebody_cutoff, skin=self.skin, device=self.device) for lo, hi in groups]
-        dev = graphs[0].device
-        offsets = np.concatenate([[0], np.cumsum([len(a) for a in z])])
-        N = int(offsets[-1])
-        rows = [(int(offsets[lo]), int(offsets[hi])) for lo, hi in groups]
+        ev = GroupedEvaluation(self.model, lat, z, groups, self.skin, self.device)
+        dev, offsets = ev.device, ev.offsets
         types = torch.tensor(np.concatenate(z) - 1, dtype=torch.int64, device=dev)   # the one array the swaps write and every engine reads
-        for vg, (a, b) in zip(graphs, rows):
+        for vg, (a, b) in zip(ev.graphs, ev.rows):
             vg.use_atom_types(types[a:b])
         pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=dev)
-        lat64 = torch.cat([vg.lattice for vg in graphs]).clone()
-        f32 = dict(dtype=torch.float32, device=dev)
-
-        def buffers():
-            return {K.TOTAL_ENERGY: torch.empty(S, **f32), K.FORCES: torch.empty(N, 3, **f32) if hybrid else None,
-                    K.STRESSES: torch.empty(S, 6, **f32) if hybrid else None}
+        lat64 = ev.lattices()
 
         def evaluate(into: dict) -> dict:
-            # (every vg.step waits for its skin test, as in MolecularDynamics.run: the loop's only waits)
-            for vg, (a, b), (lo, hi) in zip(graphs, rows, groups):
-                part = vg.step(model, pos_t[a:b], forces=hybrid)
-                into[K.TOTAL_ENERGY][lo:hi].copy_(part[K.TOTAL_ENERGY])
-                if hybrid:
-                    into[K.FORCES][a:b].copy_(part[K.FORCES])
-                    into[K.STRESSES][lo:hi].copy_(part[K.STRESSES])
-            return into
+            return ev.evaluate(pos_t, into, forces=hybrid)
 
-        cur, trial = buffers(), buffers()
+        cur, trial = ev.buffers(hybrid), ev.buffers(hybrid)
         mc = McState(offsets, temps, seeds, active, device=dev)
         dyn = None
         if hybrid:
@@ -218,7 +193,7 @@ class SwapMonteCarlo(Driver):
             dyn = DynState(pos_t, lat64, offsets, np.concatenate(m), torch.tensor(np.concatenate(vel), device=dev), temps, seeds,
                            ensemble="nvt_langevin", dt=self.timestep, friction=self.friction)
         history = torch.full((max(trials, 1), S, 3), -1, dtype=torch.int32, device=dev)
-        trial_log = torch.full((max(trials, 1), S), float("nan"), **f32)
+        trial_log = torch.full((max(trials, 1), S), float("nan"), dtype=torch.float32, device=dev)
         trace, trace_at = [], []
 
         def one_trial(t: int) -> None:
@@ -246,8 +221,7 @@ class SwapMonteCarlo(Driver):
                         dyn_step(dyn, cur[K.FORCES], cur[K.STRESSES])                 # starts the next step with the CURRENT forces
                 else:
                     dyn_step(dyn, cur[K.FORCES], cur[K.STRESSES], finish_only=(k == steps))
-        for vg in graphs:
-            vg.raise_on_step_errors("swap Monte Carlo")
+        ev.raise_on_step_errors("swap Monte Carlo")
         st = mc.read()
         dst = dyn.read() if hybrid else None
         e = cur[K.TOTAL_ENERGY].double().cpu().numpy()

@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import Driver, batch_layout, check_tensor, integer, positive, state_tensor, structure_arrays
+from ._driver import (Driver, atom_offsets, batch_layout, check_tensor, integer, positive, read_state, state_tensor,
+                      structure_arrays)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
 from .data.md import VerletGraph
@@ -35,20 +36,18 @@ FIRE_DEFAULTS = dict(dt=0.1, maxstep=0.2, dtmax=1.0, nmin=5, finc=1.1, fdec=0.5,
 LBFGS_DEFAULTS = dict(maxstep=0.2, memory=100, damping=1.0, alpha=70.0)
 
 
-class FireState:
-    """FIRE state of a batch on the device (m3g_fire_init): the generalized coordinates and velocities in fp64, the per-structure
-    dt, a, n, flags and step counts.  `pos` ([N,3] fp64) and, when `relax_cell`, `lattice` ([S,3,3] fp64) are the caller's tensors:
-    `fire_step` moves them IN PLACE (and `lattice32`, their fp32 copy).  `offsets`: S + 1 atom offsets, strictly increasing."""
+class OptimizerState:
+    """What `FireState` and `LbfgsState` share: an optimiser's state of a batch on the device over the caller's tensors.  `pos`
+    ([N,3] fp64) and, when `relax_cell`, `lattice` ([S,3,3] fp64) are moved IN PLACE by `step` (and `lattice32`, their fp32 copy);
+    `offsets`: S + 1 atom offsets, strictly increasing.  A subclass names its parameters (`NAME`, `DEFAULTS`), its m3g_<PREFIX>_state_bytes
+    / _init / _step / _read, builds its parameter struct (`_params`) and lists what `read()` returns (`_sizes`, `_fields`)."""
 
     def __init__(self, pos: torch.Tensor, lattice: torch.Tensor | None, offsets: Sequence[int], relax_cell: bool = True, fmax: float = 0.1,
-                 **fire_params):
-        unknown = set(fire_params) - set(FIRE_DEFAULTS)
+                 **params):
+        unknown = set(params) - set(self.DEFAULTS)
         if unknown:
-            raise TypeError(f"unknown FIRE parameters {sorted(unknown)}")
-        p = dict(FIRE_DEFAULTS, **fire_params)
-        self.params = _lib.M3GFireParams(dt=p["dt"], maxstep=p["maxstep"], dtmax=p["dtmax"], finc=p["finc"], fdec=p["fdec"],
-                                         astart=p["astart"], fa=p["fa"], fmax=positive("fmax", fmax), nmin=int(p["nmin"]),
-                                         relax_cell=1 if relax_cell else 0)
+            raise TypeError(f"unknown {self.NAME} parameters {sorted(unknown)}")
+        self.params = self._params(dict(self.DEFAULTS, **params), fmax, 1 if relax_cell else 0)
         self.offsets, self.N, self.S = batch_layout(pos, lattice, offsets)
         if relax_cell and lattice is None:
             raise ValueError("a cell relaxation needs the lattice")
@@ -57,109 +56,85 @@ class FireState:
         self.lattice32 = lattice.to(torch.float32) if lattice is not None else None
         self.device = pos.device
         self.lib = _lib.load_library()
-        self.state = state_tensor(self.lib.m3g_fire_state_bytes, self.N, self.S, device=self.device)
-        self.unconverged = torch.full((1,), self.S, dtype=torch.int32).pin_memory()   # written by every m3g_fire_step
+        state_bytes, init, self._step, self._read = (getattr(self.lib, f"m3g_{self.PREFIX}_{fn}") for fn in ("state_bytes", "init", "step", "read"))
+        self.state = state_tensor(state_bytes, *self._sizes(), device=self.device)
+        self.unconverged = torch.full((1,), self.S, dtype=torch.int32).pin_memory()   # written by every step's launch
         self._unconverged = self.unconverged.numpy()
         with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_fire_init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, _ptr(pos), _ptr(lattice),
-                                              _ptr(self.state), self.state.numel(), _stream()))
+            _lib.check(init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, _ptr(pos), _ptr(lattice), _ptr(self.state),
+                            self.state.numel(), _stream()))
+
+    def _sizes(self) -> tuple:
+        return self.N, self.S
 
     @property
     def n_unconverged(self) -> int:
-        """Structures neither converged nor failed after the last `fire_step` whose launch the host has waited for."""
+        """Structures neither converged nor failed after the last `step` whose launch the host has waited for."""
         return int(self._unconverged[0])
 
     def read(self) -> dict:
-        """flags / n_steps / dt / a / n [S] and the generalized coordinates X / velocities v [N + 3S, 3] (atom rows, then three cell
-        rows per structure), copied to the host (waits for the stream)."""
-        S, R = self.S, self.N + 3 * self.S
-        out = {"flags": np.empty(S, np.int32), "n_steps": np.empty(S, np.int32), "dt": np.empty(S), "a": np.empty(S), "n": np.empty(S, np.int32),
-               "x": np.empty((R, 3)), "v": np.empty((R, 3))}
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_fire_read(self.N, S, _ptr(self.state), self.state.numel(), *(out[k].ctypes.data for k in
-                                                                                                   ("flags", "n_steps", "dt", "a", "n", "x", "v")),
-                                              _stream()))
-        return out
+        return read_state(self._read, self._sizes(), self.state, self._fields())
 
     def step(self, forces: torch.Tensor, stresses: torch.Tensor | None = None, check_only: bool = False) -> None:
-        fire_step(self, forces, stresses, check_only)
+        """One iteration of the batch at `forces` [N,3] and `stresses` [S,6] (float32, pair-virial convention: the virial is
+        W = V * stresses) evaluated at `pos`: converged / failed structures are flagged and frozen, every other one takes a step.
+        Queued on the current stream; no wait."""
+        check_tensor("forces", forces, (self.N, 3), torch.float32)
+        if stresses is not None:
+            check_tensor("stresses", stresses, (self.S, 6), torch.float32)
+        with _cuda.on_device(self.device):
+            _lib.check(self._step(C.byref(self.params), self.N, self.S, _ptr(self.state), self.state.numel(), _ptr(forces),
+                                  _ptr(stresses), _ptr(self.pos), _ptr(self.lattice) if self.relax_cell else None,
+                                  _ptr(self.lattice32) if self.relax_cell else None, 1 if check_only else 0,
+                                  C.c_void_p(self.unconverged.data_ptr()), _stream()))
+
+
+class FireState(OptimizerState):
+    """FIRE state of a batch on the device (m3g_fire_init): the generalized coordinates and velocities in fp64, the per-structure
+    dt, a, n, flags and step counts.  `read()`: flags / n_steps / dt / a / n [S] and the generalized coordinates X / velocities v
+    [N + 3S, 3] (atom rows, then three cell rows per structure), copied to the host (waits for the stream)."""
+    NAME, PREFIX, DEFAULTS = "FIRE", "fire", FIRE_DEFAULTS
+
+    def _params(self, p: dict, fmax, relax_cell: int):
+        return _lib.M3GFireParams(dt=p["dt"], maxstep=p["maxstep"], dtmax=p["dtmax"], finc=p["finc"], fdec=p["fdec"], astart=p["astart"],
+                                  fa=p["fa"], fmax=positive("fmax", fmax), nmin=int(p["nmin"]), relax_cell=relax_cell)
+
+    def _fields(self):
+        S, R = self.S, self.N + 3 * self.S
+        return (("flags", np.int32, S), ("n_steps", np.int32, S), ("dt", np.float64, S), ("a", np.float64, S), ("n", np.int32, S),
+                ("x", np.float64, (R, 3)), ("v", np.float64, (R, 3)))
 
 
 def fire_step(state: FireState, forces: torch.Tensor, stresses: torch.Tensor | None = None, check_only: bool = False) -> None:
-    """One FIRE iteration of the batch (m3g_fire_step) at `forces` [N,3] and `stresses` [S,6] (float32, pair-virial convention: the
-    virial is W = V * stresses) evaluated at `state.pos`: converged / failed structures are flagged and frozen, every other one takes
-    a step.  Queued on the current stream; no wait."""
-    check_tensor("forces", forces, (state.N, 3), torch.float32)
-    if stresses is not None:
-        check_tensor("stresses", stresses, (state.S, 6), torch.float32)
-    with _cuda.on_device(state.device):
-        _lib.check(state.lib.m3g_fire_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
-                                           _ptr(stresses), _ptr(state.pos), _ptr(state.lattice) if state.relax_cell else None,
-                                           _ptr(state.lattice32) if state.relax_cell else None, 1 if check_only else 0,
-                                           C.c_void_p(state.unconverged.data_ptr()), _stream()))
+    """One FIRE iteration of the batch (m3g_fire_step): `OptimizerState.step`."""
+    state.step(forces, stresses, check_only)
 
 
-class LbfgsState:
+class LbfgsState(OptimizerState):
     """L-BFGS state of a batch on the device (m3g_lbfgs_init): the generalized coordinates, the previous point and gradient, the ring
-    of the newest `memory` pairs (s, y) and the per-structure Gram matrices in fp64, flags, step counts and history depths.  `pos`,
-    `lattice`, `offsets` as for `FireState`: `lbfgs_step` moves the caller's tensors IN PLACE."""
+    of the newest `memory` pairs (s, y) and the per-structure Gram matrices in fp64, flags, step counts and history depths.
+    `read()`: flags / n_steps / n_pairs (the history depth) [S] and the generalized coordinates X [N + 3S, 3]."""
+    NAME, PREFIX, DEFAULTS = "L-BFGS", "lbfgs", LBFGS_DEFAULTS
 
-    def __init__(self, pos: torch.Tensor, lattice: torch.Tensor | None, offsets: Sequence[int], relax_cell: bool = True, fmax: float = 0.1,
-                 **lbfgs_params):
-        unknown = set(lbfgs_params) - set(LBFGS_DEFAULTS)
-        if unknown:
-            raise TypeError(f"unknown L-BFGS parameters {sorted(unknown)}")
-        p = dict(LBFGS_DEFAULTS, **lbfgs_params)
+    def _params(self, p: dict, fmax, relax_cell: int):
         self.memory = integer("memory", p["memory"], 1)
         if self.memory > _lib.LBFGS_MAX_MEMORY:
             raise ValueError(f"memory must be <= {_lib.LBFGS_MAX_MEMORY}; got {self.memory}")
-        self.params = _lib.M3GLbfgsParams(maxstep=positive("maxstep", p["maxstep"]), damping=positive("damping", p["damping"]),
-                                          alpha=positive("alpha", p["alpha"]), fmax=positive("fmax", fmax), memory=self.memory,
-                                          relax_cell=1 if relax_cell else 0)
-        self.offsets, self.N, self.S = batch_layout(pos, lattice, offsets)
-        if relax_cell and lattice is None:
-            raise ValueError("a cell relaxation needs the lattice")
-        self.relax_cell = bool(relax_cell)
-        self.pos, self.lattice = pos, lattice
-        self.lattice32 = lattice.to(torch.float32) if lattice is not None else None
-        self.device = pos.device
-        self.lib = _lib.load_library()
-        self.state = state_tensor(self.lib.m3g_lbfgs_state_bytes, self.N, self.S, self.memory, device=self.device)
-        self.unconverged = torch.full((1,), self.S, dtype=torch.int32).pin_memory()   # written by every m3g_lbfgs_step
-        self._unconverged = self.unconverged.numpy()
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_lbfgs_init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, _ptr(pos), _ptr(lattice),
-                                               _ptr(self.state), self.state.numel(), _stream()))
+        return _lib.M3GLbfgsParams(maxstep=positive("maxstep", p["maxstep"]), damping=positive("damping", p["damping"]),
+                                   alpha=positive("alpha", p["alpha"]), fmax=positive("fmax", fmax), memory=self.memory,
+                                   relax_cell=relax_cell)
 
-    @property
-    def n_unconverged(self) -> int:
-        """Structures neither converged nor failed after the last `lbfgs_step` whose launch the host has waited for."""
-        return int(self._unconverged[0])
+    def _sizes(self) -> tuple:
+        return self.N, self.S, self.memory
 
-    def read(self) -> dict:
-        """flags / n_steps / n_pairs (the history depth) [S] and the generalized coordinates X [N + 3S, 3] (atom rows, then three
-        cell rows per structure), copied to the host (waits for the stream)."""
-        S, R = self.S, self.N + 3 * self.S
-        out = {"flags": np.empty(S, np.int32), "n_steps": np.empty(S, np.int32), "n_pairs": np.empty(S, np.int32), "x": np.empty((R, 3))}
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_lbfgs_read(self.N, S, self.memory, _ptr(self.state), self.state.numel(),
-                                               *(out[k].ctypes.data for k in ("flags", "n_steps", "n_pairs", "x")), _stream()))
-        return out
-
-    def step(self, forces: torch.Tensor, stresses: torch.Tensor | None = None, check_only: bool = False) -> None:
-        lbfgs_step(self, forces, stresses, check_only)
+    def _fields(self):
+        S = self.S
+        return (("flags", np.int32, S), ("n_steps", np.int32, S), ("n_pairs", np.int32, S), ("x", np.float64, (self.N + 3 * S, 3)))
 
 
 def lbfgs_step(state: LbfgsState, forces: torch.Tensor, stresses: torch.Tensor | None = None, check_only: bool = False) -> None:
-    """One L-BFGS iteration of the batch (m3g_lbfgs_step); arguments and units as `fire_step`.  Queued on the current stream; no wait."""
-    check_tensor("forces", forces, (state.N, 3), torch.float32)
-    if stresses is not None:
-        check_tensor("stresses", stresses, (state.S, 6), torch.float32)
-    with _cuda.on_device(state.device):
-        _lib.check(state.lib.m3g_lbfgs_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
-                                            _ptr(stresses), _ptr(state.pos), _ptr(state.lattice) if state.relax_cell else None,
-                                            _ptr(state.lattice32) if state.relax_cell else None, 1 if check_only else 0,
-                                            C.c_void_p(state.unconverged.data_ptr()), _stream()))
+    """One L-BFGS iteration of the batch (m3g_lbfgs_step): `OptimizerState.step`."""
+    state.step(forces, stresses, check_only)
 
 
 OPTIMIZERS = {"fire": (FireState, FIRE_DEFAULTS), "lbfgs": (LbfgsState, LBFGS_DEFAULTS)}   # name -> (state class, its parameters)
@@ -192,7 +167,7 @@ def _relax(model: Gradient, lat: list, pos: list, z: list, *, relax_cell: bool, 
     cfg = model.engine.cfg
     vg = VerletGraph(lat, z, cfg.cutoff, cfg.threebody_cutoff, skin=skin, device=device)
     pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=vg.device)
-    offsets = np.concatenate([[0], np.cumsum([len(a) for a in z])])
+    offsets = atom_offsets(z)
     lat64 = vg.lattice.clone()   # the optimiser's launch writes the relaxed cells here
     fire = OPTIMIZERS[optimizer][0](pos_t, lat64, offsets, relax_cell=relax_cell, fmax=fmax, **(optimizer_params or {}))
     out = fire_loop(vg, model, fire, steps)

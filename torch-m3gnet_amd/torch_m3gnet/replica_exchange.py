@@ -18,11 +18,11 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import Driver, boolean, check_tensor, integer, positive, state_tensor, structure_arrays, structure_masses
+from ._driver import (Driver, GroupedEvaluation, MdLog, boolean, check_tensor, integer, md_result, non_negative, positive, read_state,
+                      state_tensor, structure_arrays, structure_masses)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
-from .data.md import VerletGraph
-from .dynamics import EV_PER_A3_IN_GPA, KB, DynState, dyn_step, maxwell_boltzmann, structure_seeds
+from .dynamics import KB, DynState, dyn_step, maxwell_boltzmann, structure_seeds
 from .nn.modules import Gradient
 
 
@@ -62,13 +62,10 @@ class RemdState:
         """held / holder (int32 [S]), attempts / accepts (int64 [S], row o_g + k = pair (k, k+1)), count / mean / m2 of the energy at
         every index [S], round_trips [S] and the ladders' attempt counters [G], copied to the host (waits for the stream)."""
         S = self.S
-        out = {"held": np.empty(S, np.int32), "holder": np.empty(S, np.int32), "attempts": np.empty(S, np.int64),
-               "accepts": np.empty(S, np.int64), "count": np.empty(S, np.int64), "mean": np.empty(S), "m2": np.empty(S),
-               "round_trips": np.empty(S, np.int64), "n_attempts": np.empty(self.G, np.int64)}
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_remd_read(S, self.G, _ptr(self.state), self.state.numel(), *(a.ctypes.data for a in out.values()),
-                                              _stream()))
-        return out
+        return read_state(self.lib.m3g_remd_read, (S, self.G), self.state,
+                          (("held", np.int32, S), ("holder", np.int32, S), ("attempts", np.int64, S), ("accepts", np.int64, S),
+                           ("count", np.int64, S), ("mean", np.float64, S), ("m2", np.float64, S), ("round_trips", np.int64, S),
+                           ("n_attempts", np.int64, self.G)))
 
 
 def remd_exchange(state: RemdState, dyn: DynState, energies: torch.Tensor, history: torch.Tensor | None = None) -> None:
@@ -111,10 +108,7 @@ class ReplicaExchange(Driver):
         super().__init__(model, skin, device)
         self.ladder_batches = boolean("ladder_batches", ladder_batches)
         self.timestep = positive("timestep", timestep)
-        friction = float(friction)
-        if not (np.isfinite(friction) and friction >= 0.0):
-            raise ValueError(f"friction must be a finite number >= 0; got {friction}")
-        self.friction = friction
+        self.friction = non_negative("friction", friction)
         self.exchange_interval = integer("exchange_interval", exchange_interval, 1)
         self.seed = seed
         several = isinstance(temperatures, (list, tuple, np.ndarray)) and len(temperatures) > 0 and np.ndim(temperatures[0]) == 1
@@ -149,39 +143,23 @@ class ReplicaExchange(Driver):
         seeds, ladder_seeds = np.concatenate([k[:-1] for k in keys]), np.array([k[-1] for k in keys], dtype=np.uint64)
         lat_r, pos_r, z_r, m_r = ([x[g] for g in owner] for x in (lat, pos, z, m))
         vel = [maxwell_boltzmann(ms, t, int(sd)) for ms, t, sd in zip(m_r, temps, seeds)]
-        model = self.model
-        cfg = model.engine.cfg
-        # the ladders of every engine batch (see `ladder_batches`): replicas lo .. hi, atoms a .. b
+        # the ladders of every engine batch (see `ladder_batches`), as spans of replicas
         groups = [(g, g + 1) for g in range(G)] if self.ladder_batches else [(0, G)]
-        spans = [(int(l_off[first]), int(l_off[last])) for first, last in groups]
-        graphs = [VerletGraph(lat_r[lo:hi], z_r[lo:hi], cfg.cutoff, cfg.threebody_cutoff, skin=self.skin, device=self.device)
-                  for lo, hi in spans]
-        dev = graphs[0].device
+        ev = GroupedEvaluation(self.model, lat_r, z_r, [(int(l_off[first]), int(l_off[last])) for first, last in groups], self.skin,
+                               self.device)
+        dev, offsets = ev.device, ev.offsets
         pos_t = torch.tensor(np.concatenate(pos_r), dtype=torch.float64, device=dev)
-        offsets = np.concatenate([[0], np.cumsum([len(a) for a in z_r])])
-        N = int(offsets[-1])
-        lat64 = torch.cat([vg.lattice for vg in graphs]).clone()
+        lat64 = ev.lattices()
         dyn = DynState(pos_t, lat64, offsets, np.concatenate(m_r), torch.tensor(np.concatenate(vel), device=dev), temps, seeds,
                        ensemble="nvt_langevin", dt=self.timestep, friction=self.friction)
         remd = RemdState(l_off, temps, ladder_seeds, device=dev)
         n_attempts = (steps - 1) // self.exchange_interval if steps > 0 else 0
         history = torch.full((max(n_attempts, 1), S), -1, dtype=torch.int32, device=dev)
         t_kin = torch.full((max(n_attempts, 1), 2, S), float("nan"), dtype=torch.float64, device=dev)   # T before / after every attempt
-        rows = [(int(offsets[lo]), int(offsets[hi])) for lo, hi in spans]
-        if len(graphs) > 1:
-            out = {K.TOTAL_ENERGY: torch.empty(S, dtype=torch.float32, device=dev), K.FORCES: torch.empty(N, 3, dtype=torch.float32, device=dev),
-                   K.STRESSES: torch.empty(S, 6, dtype=torch.float32, device=dev)}
-        log = {key: [] for key in ("step", "e_pot", "ke", "t", "p", "v")}
+        whole = ev.buffers() if len(groups) > 1 else None   # (one group: the engine's own output tensors serve)
+        log = MdLog()
         for k in range(steps + 1):
-            # (every vg.step waits for its skin test, as in MolecularDynamics.run: the loop's only waits)
-            if len(graphs) == 1:
-                out = graphs[0].step(model, pos_t)
-            else:
-                for vg, (a, b), (lo, hi) in zip(graphs, rows, spans):
-                    part = vg.step(model, pos_t[a:b])
-                    out[K.TOTAL_ENERGY][lo:hi].copy_(part[K.TOTAL_ENERGY])
-                    out[K.FORCES][a:b].copy_(part[K.FORCES])
-                    out[K.STRESSES][lo:hi].copy_(part[K.STRESSES])
+            out = ev.evaluate(pos_t, whole)
             if 0 < k < steps and k % self.exchange_interval == 0:
                 a = k // self.exchange_interval - 1
                 dyn_step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=True)   # synchronous velocities, STARTED cleared
@@ -192,18 +170,13 @@ class ReplicaExchange(Driver):
             else:
                 dyn_step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=(k == steps))
             if k % loginterval == 0 or k == steps:
-                obs = dyn.obs.cpu().numpy()
-                log["step"].append(np.full(S, k))
-                log["e_pot"].append(out[K.TOTAL_ENERGY].double().cpu().numpy())
-                for j, key in enumerate(("ke", "t", "p", "v")):
-                    log[key].append(obs[:, j] * (EV_PER_A3_IN_GPA if key == "p" else 1.0))
-        for vg in graphs:
-            vg.raise_on_step_errors("replica-exchange molecular dynamics")
+                log.append(k, out[K.TOTAL_ENERGY], dyn.obs)
+        ev.raise_on_step_errors("replica-exchange molecular dynamics")
         st, ex = dyn.read(), remd.read()
         e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
         p_host, l_host, hist = pos_t.cpu().numpy(), lat64.cpu().numpy(), history[:n_attempts].cpu().numpy()
         t_host, target = t_kin[:n_attempts].cpu().numpy(), target_temperatures(dyn).cpu().numpy()
-        logs = {key: np.stack(val, axis=1) for key, val in log.items()}   # [S, n_log]
+        logs = log.arrays()
         res = []
         for g, t in enumerate(ladders):
             lo, hi = int(l_off[g]), int(l_off[g + 1])
@@ -211,12 +184,8 @@ class ReplicaExchange(Driver):
             replicas = []
             for idx in range(R):   # in the order of the temperature held at the end
                 s = int(ex["holder"][lo + idx])
-                a, b = int(offsets[s]), int(offsets[s + 1])
-                replicas.append({"positions": p_host[a:b].copy(), "velocities": st["v"][a:b].copy(), "lattice": l_host[s].copy(),
-                                 "total_energy": float(e[s]), "forces": f[a:b].copy(), "stresses": sv[s].copy(),
-                                 "n_steps": int(st["n_steps"][s]), "error": bool(st["flags"][s] & _lib.DYN_ERROR),
-                                 "log": {key: val[s].copy() for key, val in logs.items()}, "temperature": float(t[idx]), "target_temperature": float(target[s]),
-                                 "replica": s - lo})
+                replicas.append(dict(md_result(s, int(offsets[s]), int(offsets[s + 1]), p_host, st, l_host, e, f, sv, logs),
+                                     temperature=float(t[idx]), target_temperature=float(target[s]), replica=s - lo))
             count = ex["count"][lo:hi]
             attempts = ex["attempts"][lo:hi - 1]
             with np.errstate(invalid="ignore", divide="ignore"):

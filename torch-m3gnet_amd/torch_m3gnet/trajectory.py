@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import boolean, check_tensor, integer, positive, state_tensor
+from ._driver import atom_offsets, boolean, check_tensor, integer, positive, read_state, state_tensor
 from .data.graph_gpu import _ptr, _stream
 
 A2_FS_TO_CM2_S = 0.1
@@ -88,14 +88,10 @@ class TrajState:
         """The raw accumulators, copied to the host (waits for the stream): hist [S, P, rdf_bins] uint64, msd / vacf [S, max_species,
         n_lags] (sums: not yet divided by atom counts or lag_count), lag_count [S, n_lags], n_samples, volume_sum, flags [S]."""
         S, M, B, G = self.S, self.M, self.bins, self.lags
-        out = {"hist": np.zeros((S, self.P, B), np.uint64), "msd": np.zeros((S, M, G)), "vacf": np.zeros((S, M, G)),
-               "lag_count": np.zeros((S, G), np.int64), "n_samples": np.zeros(S, np.int64), "volume_sum": np.zeros(S),
-               "flags": np.zeros(S, np.int32)}
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_traj_read(C.byref(self.sizes), _ptr(self.state), self.state.numel(),
-                                              *[out[k].ctypes.data for k in ("hist", "msd", "vacf", "lag_count", "n_samples", "volume_sum",
-                                                                             "flags")], _stream()))
-        return out
+        return read_state(self.lib.m3g_traj_read, (C.byref(self.sizes),), self.state,   # (a switched-off observable: an array of no elements)
+                          (("hist", np.uint64, (S, self.P, B)), ("msd", np.float64, (S, M, G)), ("vacf", np.float64, (S, M, G)),
+                           ("lag_count", np.int64, (S, G)), ("n_samples", np.int64, S), ("volume_sum", np.float64, S),
+                           ("flags", np.int32, S)))
 
     def frame(self, lag: int = 0):
         """(positions, velocities) [N, 3] of the stored frame `lag` samples back (0: the last sample), copied to the host: the full-step
@@ -226,7 +222,7 @@ class TrajectoryObservables:
             elif r_max > half * (1.0 + 1e-12):   # (the rounding of the width itself: a / 2 of a cubic cell passes, as on the device)
                 raise ValueError(f"rdf_r_max = {r_max} A is above half the smallest perpendicular width of the cells ({half:.6g} A): "
                                  "the minimum image is not exact there")
-        offsets = np.concatenate([[0], np.cumsum([len(z) for z in atomic_numbers])])
+        offsets = atom_offsets(atomic_numbers)
         state = TrajState(int(offsets[-1]), offsets, np.concatenate(species), np.concatenate(masses), r_max, self.rdf_bins, self.n_lags,
                           self.remove_com, device=device)
         state.species_z, state.species_counts = zs_all, counts
