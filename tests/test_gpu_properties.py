@@ -708,6 +708,40 @@ def test_hyperparameter_sweep_against_oracle(l_max, n_max, dim, blocks, cut, tb_
             assert rel_err(out[K.MID_EDGE_FEATURES][b], o[f"mid_edge_features_{b}"]) < 1e-4, (kern, b)
 
 
+@pytest.mark.parametrize("batched", [False, True])
+def test_any_size_path_with_an_isolated_atom(batched):
+    """The any-size path (embedding_dim 96, one block) on a structure without edges -- one atom in a cell wider than the cutoff --
+    on its own, where every launch over edges or triplets is empty, and batched with a normal cell.  Energies against the fp64
+    oracle at the sweep's 1e-5 (forces of the normal cell at its 1e-4); the force on the isolated atom is exactly zero."""
+    from oracle import m3gnet_oracle as orc
+    from torch_m3gnet.data.material_graph import Batch, MaterialGraph
+    from torch_m3gnet.model.build import build_model
+
+    K = _K()
+    torch.manual_seed(11)
+    model = build_model(4.5, 4.0, 3, 3, 60, 96, 1, elemental_energies=torch.linspace(-1, 1, 60), energy_scale=1.7)
+    for m in model.model:
+        if type(m).__name__ == "ThreeBodyInteration":
+            m.nsb.factors = m.nsb.documented_factors()
+    model.engine.set_option("edge_kernel", 2)
+    lone = MaterialGraph.from_arrays(np.eye(3) * 20.0, np.array([[1.0, 2.0, 3.0]]), [8], 4.5, 4.0)
+    dense = random_cell_graph(14, 6.0, 20, cutoff=4.5, tb_cutoff=4.0, zmax=59)
+    assert lone[K.NUM_EDGES] == 0 and dense[K.NUM_TRIPLETS] > 0
+    out = model(Batch.from_data_list([lone, dense] if batched else [lone]).to(DEV))
+    p, cfg, c, og = _oracle_inputs(model, out)
+    p = {k: v.double() for k, v in p.items()}
+    c = orc.make_constants(cfg, model.model[1].elemental_energies.cpu(), dtype=torch.float64)
+    c.factors = model.model[6].nsb.factors.double()
+    o = orc.energy_forces(p, cfg, c, og, legendre_backward="exact")
+    e_err = float(((out[K.TOTAL_ENERGY].cpu().double() - o["total_energy"]).abs() / o["total_energy"].abs()).max())
+    print(f"E rel err {e_err:.2e}, |F| on the isolated atom {float(out[K.FORCES][0].abs().max()):.1e}")
+    assert e_err < 1e-5
+    assert torch.isfinite(out[K.FORCES]).all()
+    assert float(out[K.FORCES][0].abs().max()) == 0.0
+    if batched:
+        assert rel_err(out[K.FORCES], o["forces"]) < 1e-4
+
+
 # ---- PBC-consistent virial (SURVEY.md section 8(f) row 4) -------------------------------------------------------------
 def _strained_energy(params, cfg, consts, graph, eps):
     """fp64 oracle energy with positions and lattice strained by (1 + eps), topology and cell shifts fixed."""

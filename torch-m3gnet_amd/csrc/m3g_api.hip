@@ -448,25 +448,8 @@ extern "C" int m3g_plan_commit(m3g_plan* plan) {
   c.energy_scale = (float)cfg.energy_scale;
   c.inv_len = 1.f / c.length_scale;
   const double rc = cfg.cutoff / cfg.length_scale, rc3 = cfg.threebody_cutoff / cfg.length_scale;  // model/build.py:34-35
-  c.rc = (float)rc;
-  c.rc3 = (float)rc3;
-  const float pi_f = (float)M_PI;
-  const auto& em = plan->cvals.at("em");
-  const auto& dm = plan->cvals.at("dm");
-  for (int m = 0; m < R; ++m) {
-    c.a1[m] = ((float)(m + 1) * pi_f) / (float)rc;  // nn/featurizer.py:87-88
-    c.a2[m] = ((float)(m + 2) * pi_f) / (float)rc;
-    c.coeff[m] = plan->cvals.at("coeff")[m];
-    c.rec_mul[m] = m > 0 ? sqrtf(em[m] / dm[m - 1]) : 0.f;  // nn/featurizer.py:94-96
-    c.rec_div[m] = sqrtf(dm[m]);
-  }
-  for (int l = 0; l < L; ++l) {
-    c.ynorm[l] = (float)std::sqrt((2 * l + 1) / (4.0 * M_PI));  // nn/interaction.py:198
-    for (int n = 0; n < R; ++n) {
-      c.zeros[l][n] = plan->cvals.at("bessel_zeros")[l * R + n];
-      c.factors[l][n] = plan->cvals.at("factors")[l * R + n];
-    }
-  }
+  fill_radial_consts(c, R, rc, plan->cvals.at("coeff").data(), plan->cvals.at("em").data(), plan->cvals.at("dm").data());
+  fill_angular_consts(c, L, R, rc, rc3, plan->cvals.at("bessel_zeros").data(), plan->cvals.at("factors").data());
 
   // ---- weights ------------------------------------------------------------------------------------
   const WeightLayout& wl = plan->wl;
@@ -840,14 +823,7 @@ extern "C" int m3g_edge_featurizer(int32_t n_max, double scaled_cutoff, const fl
   if (!host_em || !host_dm || !host_coeff || (E > 0 && (!edge_distances || !edge_weights))) { set_error("null argument"); return M3G_ERR_VALUE; }
   Consts c{};
   c.R = n_max;
-  const float pi_f = (float)M_PI;
-  for (int m = 0; m < n_max; ++m) {
-    c.a1[m] = ((float)(m + 1) * pi_f) / (float)scaled_cutoff;
-    c.a2[m] = ((float)(m + 2) * pi_f) / (float)scaled_cutoff;
-    c.coeff[m] = host_coeff[m];
-    c.rec_mul[m] = m > 0 ? sqrtf(host_em[m] / host_dm[m - 1]) : 0.f;
-    c.rec_div[m] = sqrtf(host_dm[m]);
-  }
+  fill_radial_consts(c, n_max, scaled_cutoff, host_coeff, host_em, host_dm);
   launch_edge_featurizer(c, E, edge_distances, edge_weights, n_max, (hipStream_t)stream_);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;

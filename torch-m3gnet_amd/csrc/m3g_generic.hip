@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "m3g_internal.h"
+#include "m3g_basis.h"
 #include "m3g_device.h"
 
 namespace m3g {
@@ -30,6 +31,11 @@ struct GenConsts {
 #define GEN_IDX(n_total)                                              \
   const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; \
   if (gid >= (n_total)) return;
+// launch of such a kernel, one thread per element, over n elements; nothing to launch for n <= 0
+template <class... P, class... A>
+static void launch(void (*kernel)(P...), int64_t n, hipStream_t s, A... args) {
+  if (n > 0) hipLaunchKernelGGL(kernel, grid_for(n), dim3(256), 0, s, static_cast<P>(args)...);
+}
 
 // ---- dense products ---------------------------------------------------------------------------------------------------
 // C[n, j] = (beta ? C[n, j] : 0) + (bias ? bias[j] : 0) + sum_k A[n*lda + k] * B[k*sbk + j*sbj]     (any strides of B: W or W^T)
@@ -135,38 +141,10 @@ __global__ void __launch_bounds__(256) g_map(int64_t n, int op, const float* __r
   else Y[gid] *= x * (1.f - x);
 }
 static void map(hipStream_t s, int64_t n, int op, const float* X, float* Y) {
-  if (n > 0) hipLaunchKernelGGL(g_map, grid_for(n), dim3(256), 0, s, n, op, X, Y);
+  launch(g_map, n, s, n, op, X, Y);
 }
 
 // ---- S0 geometry and bases (nn/scale.py:24-29, nn/invariant.py:20-59, nn/featurizer.py:81-100, nn/interaction.py:268-350,389-400)
-__device__ __forceinline__ float g_sinc_cos_pi(float x, float& cos_px) {
-  const float px = 3.14159265358979323846f * x;
-  float sn;
-  sincosf(px, &sn, &cos_px);
-  return x == 0.f ? 1.f : sn / px;
-}
-__device__ __forceinline__ void g_bessel(int L, float x, float* j, float* dj) {   // j_l, j_l' for l < L (reference's x <= 1e-8 branch)
-  float seq[kGL + 1];
-  if (x > 1e-8f) {
-    float sn, cx;
-    sincosf(x, &sn, &cx);
-    const float sx = sn / x;
-    seq[0] = sx;
-    seq[1] = (sx - cx) / x;
-    for (int n = 1; n < L; ++n) seq[n + 1] = (float)(2 * n + 1) / x * seq[n] - seq[n - 1];
-    for (int l = 0; l < L; ++l) {
-      j[l] = seq[l];
-      dj[l] = l == 0 ? -seq[1] : seq[l - 1] - (float)(l + 1) / x * seq[l];
-    }
-  } else {
-    float dfact = 1.f;
-    for (int l = 0; l < L; ++l) {
-      if (l > 0) dfact *= (float)(2 * l + 1);
-      j[l] = l == 0 ? 1.f : x / dfact;
-      dj[l] = l == 1 ? 1.f / 3.f : 0.f;
-    }
-  }
-}
 __global__ void __launch_bounds__(256) g_geometry(GenConsts c, int64_t E, const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
                                                   const int32_t* __restrict__ batch, const float* __restrict__ pos,
                                                   const float* __restrict__ lattice, const int32_t* __restrict__ shift, float* __restrict__ u,
@@ -186,30 +164,20 @@ __global__ void __launch_bounds__(256) g_geometry(GenConsts c, int64_t E, const 
   const float d = sqrtf(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
   dist[e] = d;
   u[e * 3] = r[0] / d; u[e * 3 + 1] = r[1] / d; u[e * 3 + 2] = r[2] / d;
-  float hprev = 0.f, hpprev = 0.f;
+  float hm = 0.f, hpm = 0.f;
   for (int m = 0; m < c.R; ++m) {
-    float c1, c2;
-    const float s1 = g_sinc_cos_pi(c.a1[m] * d, c1), s2 = g_sinc_cos_pi(c.a2[m] * d, c2);
-    float f = c.coeff[m] * (s1 + s2);
-    float df = c.coeff[m] * ((c1 - s1) + (c2 - s2)) / d;
-    if (m > 0) { f = (f + c.rec_mul[m] * hprev) / c.rec_div[m]; df = (df + c.rec_mul[m] * hpprev) / c.rec_div[m]; }
-    h[e * c.R + m] = f;
-    hp[e * c.R + m] = df;
-    hprev = f; hpprev = df;
+    radial_term(c, m, d, hm, hpm);
+    h[e * c.R + m] = hm;
+    hp[e * c.R + m] = hpm;
   }
-  const float rho = d / c.rc3;
-  float f = 0.f, fp = 0.f;
-  if (rho <= 1.f) {
-    const float r2 = rho * rho, r3 = r2 * rho;
-    f = 1.f - 6.f * r3 * r2 + 15.f * r2 * r2 - 10.f * r3;
-    fp = (-30.f * r2 * r2 + 60.f * r3 - 30.f * r2) / c.rc3;
-  }
+  const Envelope env = envelope(d, c.rc3);
+  const float f = env.f, fp = env.fp;
   fc3[e] = f;
   fc3p[e] = fp;
   for (int l = 0; l < c.L; ++l)
     for (int n = 0; n < c.R; ++n) {
       float jl[kGL], djl[kGL];
-      g_bessel(c.L, c.zeros[l][n] * d / c.rc, jl, djl);
+      sph_bessel<kGL, false>(c.L, c.zeros[l][n] * d / c.rc, jl, djl);
       const float chi = jl[l] / c.factors[l][n];
       const float dchi = djl[l] * (c.zeros[l][n] / c.rc) / c.factors[l][n];
       q[e * c.C + l * c.R + n] = chi * f;
@@ -226,23 +194,6 @@ __global__ void __launch_bounds__(256) g_embed_x(int64_t N, int D, int num_types
   x[gid] = W[(int64_t)o * num_types + species_index(types[a], num_types, bad)];   // one_hot(types) @ W^T, W [D, num_types] (nn/featurizer.py:33-38)
 }
 
-// what the reference's LegendreCosPolynomial.backward returns per unit of its grad_output `go` (nn/interaction.py:373-382):
-// k_1 = 1, k_n = n P_{n-1} + x go k_{n-1}
-__device__ __forceinline__ float g_legendre_ref_k(int l, float x, const float* P, float go) {
-  if (l == 0) return 0.f;
-  float k = 1.f;
-  for (int n = 2; n <= l; ++n) k = (float)n * P[n - 1] + x * go * k;
-  return k;
-}
-__device__ __forceinline__ void g_legendre(int L, float x, float* P, float* dP) {
-  P[0] = 1.f; dP[0] = 0.f;
-  if (L > 1) { P[1] = x; dP[1] = 1.f; }
-  for (int n = 1; n < L - 1; ++n) {
-    P[n + 1] = ((float)(2 * n + 1) * x * P[n] - (float)n * P[n - 1]) / (float)(n + 1);
-    dP[n + 1] = ((float)(2 * n + 1) * (P[n] + x * dP[n]) - (float)n * dP[n - 1]) / (float)(n + 1);
-  }
-}
-
 // S3: Ssum[e1, c] = sum_{t in T1(e1)} Y_l(cos_t) q[e2, c] v[dst(e2), c]     (m = fc3 * Ssum; nn/interaction.py:187-217)
 __global__ void __launch_bounds__(256) g_threebody_fwd(GenConsts c, int64_t E, const int32_t* __restrict__ t1_ptr, const int32_t* __restrict__ t1_e2,
                                                        const int32_t* __restrict__ dst, const float* __restrict__ u, const float* __restrict__ q,
@@ -257,7 +208,7 @@ __global__ void __launch_bounds__(256) g_threebody_fwd(GenConsts c, int64_t E, c
     const int64_t e2 = t1_e2[t];
     const float cs = fminf(1.f, fmaxf(-1.f, ux * u[e2 * 3] + uy * u[e2 * 3 + 1] + uz * u[e2 * 3 + 2]));
     float P[kGL], dP[kGL];
-    g_legendre(c.L, cs, P, dP);
+    legendre<false>(c.L, cs, P, dP);
     const float y = c.ynorm[l] * P[l];
     const int64_t k = dst[e2];
     for (int n = 0; n < c.R; ++n) acc[n] += y * q[e2 * c.C + l * c.R + n] * v[k * c.C + l * c.R + n];
@@ -317,7 +268,7 @@ __global__ void __launch_bounds__(256) g_threebody_rev(GenConsts c, int64_t E, c
     const float vx = u[e2 * 3], vy = u[e2 * 3 + 1], vz = u[e2 * 3 + 2];
     const float raw = ux * vx + uy * vy + uz * vz;
     float P[kGL], dP[kGL];
-    g_legendre(c.L, fminf(1.f, fmaxf(-1.f, raw)), P, dP);
+    legendre<false>(c.L, fminf(1.f, fmaxf(-1.f, raw)), P, dP);
     const int64_t k = dst[e2];
     float dcos = 0.f;
     for (int l = 0; l < c.L; ++l)
@@ -331,7 +282,7 @@ __global__ void __launch_bounds__(256) g_threebody_rev(GenConsts c, int64_t E, c
         float G = 0.f;
         for (int n = 0; n < c.R; ++n) G += dm[e * C + l * c.R + n] * (q[e2 * C + l * c.R + n] * v[k * C + l * c.R + n]);
         const float g1 = c.ynorm[l] * G;
-        dcos += g1 * g_legendre_ref_k(l, fminf(1.f, fmaxf(-1.f, raw)), P, fce * g1);
+        dcos += g1 * legendre_ref_k<false>(c.L, l, fminf(1.f, fmaxf(-1.f, raw)), P, fce * g1);
       }
     }
     dcos = (raw >= -1.f && raw <= 1.f) ? fce * dcos : 0.f;
@@ -347,7 +298,7 @@ __global__ void __launch_bounds__(256) g_threebody_rev(GenConsts c, int64_t E, c
     const float vx = u[e1 * 3], vy = u[e1 * 3 + 1], vz = u[e1 * 3 + 2];
     const float raw = ux * vx + uy * vy + uz * vz;
     float P[kGL], dP[kGL];
-    g_legendre(c.L, fminf(1.f, fmaxf(-1.f, raw)), P, dP);
+    legendre<false>(c.L, fminf(1.f, fmaxf(-1.f, raw)), P, dP);
     const float f1 = fc3[e1];
     float dcos = 0.f;
     for (int l = 0; l < c.L; ++l)
@@ -363,7 +314,7 @@ __global__ void __launch_bounds__(256) g_threebody_rev(GenConsts c, int64_t E, c
         float G = 0.f;
         for (int n = 0; n < c.R; ++n) G += (f1 * dm[e1 * C + l * c.R + n]) * (q[e * C + l * c.R + n] * v[kd * C + l * c.R + n]);
         const float go = c.ynorm[l] * G;
-        dcos += go * g_legendre_ref_k(l, fminf(1.f, fmaxf(-1.f, raw)), P, go);
+        dcos += go * legendre_ref_k<false>(c.L, l, fminf(1.f, fmaxf(-1.f, raw)), P, go);
       }
     }
     dcos = (raw >= -1.f && raw <= 1.f) ? dcos : 0.f;
@@ -410,58 +361,84 @@ __global__ void __launch_bounds__(256) g_readout_seed(int64_t N, float energy_sc
   d_od[gid] = energy_scale * sg;
   d_og[gid] = energy_scale * od[gid] * sg * (1.f - sg);
 }
-__global__ void __launch_bounds__(256) g_add(int64_t n, const float* __restrict__ a, float* __restrict__ y) {
-  GEN_IDX(n);
-  y[gid] += a[gid];
-}
 
 // ---- weights ------------------------------------------------------------------------------------------------------------
+// Index g of every [2] below: 0 = the dense branch of a GatedMLP, 1 = its gate.  Loops over g launch dense before gate: where both
+// branches accumulate into one array (`beta`), that order is the order of the sum.
+struct GenMlpW { const float *w1[2], *b1[2], *w2[2], *b2[2], *wl; };   // conv GatedMLP: [D,3D], [D], [D,D], [D] per branch, W_l [D,R]
 struct GenBlockW {
-  const float *w1s, *b1s, *wd, *wg;   // ThreeBodyInteration: linear_sigmoid1 [C,D] [C], gated_mlp dense/gate [D,C]
-  struct Mlp { const float *w1d, *w1g, *b1d, *b1g, *w2d, *w2g, *b2d, *b2g, *wl; } e, n;   // [D,3D] x2, [D] x2, [D,D] x2, [D] x2, [D,R]
+  const float *w1s, *b1s, *wt[2];   // ThreeBodyInteration: linear_sigmoid1 [C,D] [C], gated_mlp dense / gate [D,C]
+  GenMlpW mlp[2];                   // 0: edge update, 1: node message
 };
+struct GenReadoutW { const float *w[2][3], *b[2][3]; };   // [g][layer]
 struct GenW {
   const float *emb, *adj, *elemental;
   GenBlockW blk[32];
-  const float *rw[2][3], *rb[2][3];   // readout [dense|gate][layer]
+  GenReadoutW ro;
 };
+
+// readout activations, [layer][g]: pre-activations p, hidden h = SiLU(p), outputs o [N].  The engine keeps p for the reverse pass and
+// shares one pair of hidden arrays between the layers; the stand-alone module forms h in place of p
+struct ReadoutBufs { float *p[2][2], *h[2][2], *o[2]; };
 
 struct GenWork {
   float *u, *d, *h, *hp, *fc3, *fc3p, *q, *qp;
   float* x[33];
   float* e[33];
   float* pe0;                       // [E,D] edge-embedding pre-activation
-  // saved per block; MLP index 0 = edge update, 1 = node message; every array contiguous [E,D] unless noted
-  struct Blk { float *v /*[N,C]*/, *Ssum /*[E,C]*/, *m /*[E,C]*/, *pd, *pg, *e1, *p1d[2], *p1g[2], *p2d[2], *p2g[2], *lin[2]; } b[32];
-  float *cat /*[E,3D]*/, *hd, *hg, *msg, *t0, *t1;     // scratch [E,D]
-  float *rp1d, *rp1g, *rp2d, *rp2g, *rod, *rog, *rh0, *rh1;   // readout [N,D] / [N]
-  float *dx, *dx2, *de, *dh /*[E,R]*/, *dd, *du, *dr, *dm, *dgq, *dp1d[2], *dp1g[2], *dTA /*[N,4D]*/, *dTB, *dv /*[N,C]*/;
+  // saved per block; MLP index m: 0 = edge update, 1 = node message; every array contiguous [E,D] unless noted
+  struct Blk { float *v /*[N,C]*/, *Ssum /*[E,C]*/, *m /*[E,C]*/, *p[2] /*three-body update*/, *e1, *p1[2][2], *p2[2][2] /*[m][g]*/, *lin[2]; } b[32];
+  float *cat /*[E,3D]*/, *hid[2], *msg, *t[2];     // scratch [E,D]
+  ReadoutBufs r;                                   // readout [N,D] / [N]
+  float *dx, *dx2, *de, *dh /*[E,R]*/, *dd, *du, *dr, *dm, *dgq, *dp1[2][2] /*[m][g]*/;
+  float *dT[2] /*[N,4D]: dp1 rows summed by centre / by neighbour*/, *dv /*[N,C]*/;
+  float* tail;                      // [N + 2 S + 64] stand-ins for optional outputs the caller did not ask for
   size_t total;
+};
+
+// scratch of the stand-alone stages: float arrays one after the other, unpadded (the sizes documented in include/m3gnet_hip.h are
+// exact sums)
+struct Packed {
+  float* p;
+  float* take(size_t n) { float* r = p; p += n; return r; }
 };
 
 }  // namespace
 
 static GenWork gen_carve(int D, int C, int R, int B, int64_t N, int64_t E, int64_t S, void* base) {
   GenWork w{};
-  Carve c{(char*)base};
-  auto take = [&](size_t n) { return (float*)c.take(n * sizeof(float)); };
+  Carve c{base};
   const size_t e = (size_t)E, n = (size_t)N;
-  w.u = take(e * 3); w.d = take(e); w.h = take(e * R); w.hp = take(e * R); w.fc3 = take(e); w.fc3p = take(e); w.q = take(e * C); w.qp = take(e * C);
-  for (int b = 0; b <= B; ++b) { w.x[b] = take(n * D); w.e[b] = take(e * D); }
-  w.pe0 = take(e * D);
+  w.u = c.take<float>(e * 3); w.d = c.take<float>(e); w.h = c.take<float>(e * R); w.hp = c.take<float>(e * R);
+  w.fc3 = c.take<float>(e); w.fc3p = c.take<float>(e); w.q = c.take<float>(e * C); w.qp = c.take<float>(e * C);
+  for (int b = 0; b <= B; ++b) { w.x[b] = c.take<float>(n * D); w.e[b] = c.take<float>(e * D); }
+  w.pe0 = c.take<float>(e * D);
   for (int b = 0; b < B; ++b) {
     auto& k = w.b[b];
-    k.v = take(n * C); k.Ssum = take(e * C); k.m = take(e * C); k.pd = take(e * D); k.pg = take(e * D); k.e1 = take(e * D);
-    for (int m = 0; m < 2; ++m) { k.p1d[m] = take(e * D); k.p1g[m] = take(e * D); k.p2d[m] = take(e * D); k.p2g[m] = take(e * D); k.lin[m] = take(e * D); }
+    k.v = c.take<float>(n * C); k.Ssum = c.take<float>(e * C); k.m = c.take<float>(e * C);
+    for (int g = 0; g < 2; ++g) k.p[g] = c.take<float>(e * D);
+    k.e1 = c.take<float>(e * D);
+    for (int m = 0; m < 2; ++m) {
+      for (int g = 0; g < 2; ++g) k.p1[m][g] = c.take<float>(e * D);
+      for (int g = 0; g < 2; ++g) k.p2[m][g] = c.take<float>(e * D);
+      k.lin[m] = c.take<float>(e * D);
+    }
   }
-  w.cat = take(e * 3 * D); w.hd = take(e * D); w.hg = take(e * D); w.msg = take(e * D); w.t0 = take(e * D); w.t1 = take(e * D);
-  w.rp1d = take(n * D); w.rp1g = take(n * D); w.rp2d = take(n * D); w.rp2g = take(n * D); w.rod = take(n); w.rog = take(n);
-  w.rh0 = take(n * D); w.rh1 = take(n * D);
-  w.dx = take(n * D); w.dx2 = take(n * D); w.de = take(e * D); w.dh = take(e * R); w.dd = take(e); w.du = take(e * 3); w.dr = take(e * 3);
-  w.dm = take(e * C); w.dgq = take(e * C);
-  for (int m = 0; m < 2; ++m) { w.dp1d[m] = take(e * D); w.dp1g[m] = take(e * D); }
-  w.dTA = take(n * 4 * D); w.dTB = take(n * 4 * D); w.dv = take(n * C);
-  take(n + (size_t)S * 2 + 64);   // tail scratch for optional outputs
+  w.cat = c.take<float>(e * 3 * D);
+  for (int g = 0; g < 2; ++g) w.hid[g] = c.take<float>(e * D);
+  w.msg = c.take<float>(e * D);
+  for (int g = 0; g < 2; ++g) w.t[g] = c.take<float>(e * D);
+  for (int i = 0; i < 2; ++i)
+    for (int g = 0; g < 2; ++g) w.r.p[i][g] = c.take<float>(n * D);
+  for (int g = 0; g < 2; ++g) w.r.o[g] = c.take<float>(n);
+  for (int g = 0; g < 2; ++g) w.r.h[0][g] = w.r.h[1][g] = c.take<float>(n * D);
+  w.dx = c.take<float>(n * D); w.dx2 = c.take<float>(n * D); w.de = c.take<float>(e * D); w.dh = c.take<float>(e * R);
+  w.dd = c.take<float>(e); w.du = c.take<float>(e * 3); w.dr = c.take<float>(e * 3); w.dm = c.take<float>(e * C); w.dgq = c.take<float>(e * C);
+  for (int m = 0; m < 2; ++m)
+    for (int g = 0; g < 2; ++g) w.dp1[m][g] = c.take<float>(e * D);
+  for (int side = 0; side < 2; ++side) w.dT[side] = c.take<float>(n * 4 * D);
+  w.dv = c.take<float>(n * C);
+  w.tail = c.take<float>(n + (size_t)S * 2 + 64);
   w.total = c.off;
   return w;
 }
@@ -498,25 +475,9 @@ static GenConsts gen_consts(const m3g_plan* plan) {
   c.L = cfg.l_max; c.R = cfg.n_max; c.C = c.L * c.R; c.D = cfg.embedding_dim; c.B = cfg.num_blocks; c.num_types = cfg.num_types;
   c.length_scale = (float)cfg.length_scale; c.energy_scale = (float)cfg.energy_scale;
   const double rc = cfg.cutoff / cfg.length_scale, rc3 = cfg.threebody_cutoff / cfg.length_scale;   // model/build.py:34-35
-  c.rc = (float)rc; c.rc3 = (float)rc3;
   c.ref_legendre = plan->opt.legendre_ref ? 1 : 0;
-  const float pi_f = (float)M_PI;
-  const auto& em = plan->cvals.at("em");
-  const auto& dm = plan->cvals.at("dm");
-  for (int m = 0; m < c.R; ++m) {
-    c.a1[m] = ((float)(m + 1) * pi_f) / (float)rc;  // nn/featurizer.py:87-88
-    c.a2[m] = ((float)(m + 2) * pi_f) / (float)rc;
-    c.coeff[m] = plan->cvals.at("coeff")[m];
-    c.rec_mul[m] = m > 0 ? sqrtf(em[m] / dm[m - 1]) : 0.f;
-    c.rec_div[m] = sqrtf(dm[m]);
-  }
-  for (int l = 0; l < c.L; ++l) {
-    c.ynorm[l] = (float)std::sqrt((2 * l + 1) / (4.0 * M_PI));
-    for (int n = 0; n < c.R; ++n) {
-      c.zeros[l][n] = plan->cvals.at("bessel_zeros")[l * c.R + n];
-      c.factors[l][n] = plan->cvals.at("factors")[l * c.R + n];
-    }
-  }
+  fill_radial_consts(c, c.R, rc, plan->cvals.at("coeff").data(), plan->cvals.at("em").data(), plan->cvals.at("dm").data());
+  fill_angular_consts(c, c.L, c.R, rc, rc3, plan->cvals.at("bessel_zeros").data(), plan->cvals.at("factors").data());
   return c;
 }
 
@@ -527,27 +488,28 @@ static GenW gen_weights(const m3g_plan* plan) {
   w.adj = at("model.5.linear.weight");
   w.elemental = at("__elemental");
   const int B = plan->cfg.num_blocks;
+  const char* br[2] = {"dense", "gate"};
   for (int b = 0; b < B; ++b) {
     const std::string tb = "model." + std::to_string(6 + 2 * b), cv = "model." + std::to_string(7 + 2 * b);
     GenBlockW& k = w.blk[b];
     k.w1s = at(tb + ".linear_sigmoid1.weight"); k.b1s = at(tb + ".linear_sigmoid1.bias");
-    k.wd = at(tb + ".gated_mlp.dense.0.weight"); k.wg = at(tb + ".gated_mlp.gate.0.weight");
-    const char* names[2] = {".concat_edge_update", ".concat_node_update"};
+    const char* names[2] = {".concat_edge_update.", ".concat_node_update."};
     const char* lins[2] = {".edge_linear.weight", ".node_linear.weight"};
+    for (int g = 0; g < 2; ++g) k.wt[g] = at(tb + ".gated_mlp." + br[g] + ".0.weight");
     for (int m = 0; m < 2; ++m) {
-      GenBlockW::Mlp& q = m == 0 ? k.e : k.n;
-      const std::string pre = cv + names[m];
-      q.w1d = at(pre + ".dense.0.weight"); q.w1g = at(pre + ".gate.0.weight"); q.b1d = at(pre + ".dense.0.bias"); q.b1g = at(pre + ".gate.0.bias");
-      q.w2d = at(pre + ".dense.2.weight"); q.w2g = at(pre + ".gate.2.weight"); q.b2d = at(pre + ".dense.2.bias"); q.b2g = at(pre + ".gate.2.bias");
+      GenMlpW& q = k.mlp[m];
+      for (int g = 0; g < 2; ++g) {
+        const std::string pre = cv + names[m] + br[g];
+        q.w1[g] = at(pre + ".0.weight"); q.b1[g] = at(pre + ".0.bias"); q.w2[g] = at(pre + ".2.weight"); q.b2[g] = at(pre + ".2.bias");
+      }
       q.wl = at(cv + lins[m]);
     }
   }
   const std::string ro = "model." + std::to_string(6 + 2 * B) + ".gated.";
-  const char* br[2] = {"dense", "gate"};
   for (int g = 0; g < 2; ++g)
     for (int i = 0; i < 3; ++i) {
-      w.rw[g][i] = at(ro + br[g] + "." + std::to_string(2 * i) + ".weight");
-      w.rb[g][i] = at(ro + br[g] + "." + std::to_string(2 * i) + ".bias");
+      w.ro.w[g][i] = at(ro + br[g] + "." + std::to_string(2 * i) + ".weight");
+      w.ro.b[g][i] = at(ro + br[g] + "." + std::to_string(2 * i) + ".bias");
     }
   return w;
 }
@@ -562,37 +524,64 @@ static void linear_t(hipStream_t s, int64_t n, int out, int in, const float* DY,
   gemm(s, n, in, out, DY, ldd, W, in, 1, nullptr, DX, ldx, beta);
 }
 static void gated(hipStream_t s, int64_t n, const float* pd, const float* pg, const float* lin, const float* base, float* y) {
-  if (n > 0) hipLaunchKernelGGL(g_gated, grid_for(n), dim3(256), 0, s, n, pd, pg, lin, base, y);
+  launch(g_gated, n, s, n, pd, pg, lin, base, y);
 }
 
-// one conv GatedMLP forward on the concat rows (nn/conv.py:68-97, nn/core.py:61-62): saves p1d, p1g, p2d, p2g, lin = W_l h (all [E,D]);
-// out = silu(p2d) sigmoid(p2g) lin (+ base)
-static void gen_mlp_forward(hipStream_t s, int64_t E, int D, int R, const GenBlockW::Mlp& q, const GenWork& w, const GenWork::Blk& k, int m,
+// ---- host chains, each used by the engine step (separate saved arrays) and by a stand-alone module (arrays aliased, in place) ----
+// ThreeBodyInteration around its aggregate m: before it v = sigmoid(W1 x + b1) (nn/interaction.py:204-205) ...
+static void threebody_gates(hipStream_t s, int64_t N, int C, int D, const GenBlockW& kw, const float* x, float* v) {
+  linear(s, N, C, D, x, D, kw.w1s, kw.b1s, v, C);
+  map(s, N * C, OP_SIGMOID, v, v);
+}
+// ... after it the gated update e_out = e_in + SiLU(Wd m) sigmoid(Wg m) (nn/interaction.py:220-221); p: the two pre-activations [E,D]
+static void threebody_update(hipStream_t s, int64_t E, int D, int C, const GenBlockW& kw, const float* m, float* const* p, const float* e_in,
+                             float* e_out) {
+  for (int g = 0; g < 2; ++g) linear(s, E, D, C, m, C, kw.wt[g], nullptr, p[g], D);
+  gated(s, E * D, p[0], p[1], nullptr, e_in, e_out);
+}
+
+// one conv GatedMLP forward on the concat rows (nn/conv.py:68-97, nn/core.py:61-62): saves p1, p2 (both branches), lin = W_l h (all
+// [E,D]); out = silu(p2 dense) sigmoid(p2 gate) lin (+ base)
+static void gen_mlp_forward(hipStream_t s, int64_t E, int D, int R, const GenMlpW& q, const GenWork& w, const GenWork::Blk& k, int m,
                             const float* base, float* out) {
-  linear(s, E, D, 3 * D, w.cat, 3 * D, q.w1d, q.b1d, k.p1d[m], D);
-  linear(s, E, D, 3 * D, w.cat, 3 * D, q.w1g, q.b1g, k.p1g[m], D);
-  map(s, E * D, OP_SILU, k.p1d[m], w.hd);
-  map(s, E * D, OP_SILU, k.p1g[m], w.hg);
-  linear(s, E, D, D, w.hd, D, q.w2d, q.b2d, k.p2d[m], D);
-  linear(s, E, D, D, w.hg, D, q.w2g, q.b2g, k.p2g[m], D);
+  for (int g = 0; g < 2; ++g) linear(s, E, D, 3 * D, w.cat, 3 * D, q.w1[g], q.b1[g], k.p1[m][g], D);
+  for (int g = 0; g < 2; ++g) map(s, E * D, OP_SILU, k.p1[m][g], w.hid[g]);
+  for (int g = 0; g < 2; ++g) linear(s, E, D, D, w.hid[g], D, q.w2[g], q.b2[g], k.p2[m][g], D);
   linear(s, E, D, R, w.h, R, q.wl, nullptr, k.lin[m], D);
-  gated(s, E * D, k.p2d[m], k.p2g[m], k.lin[m], base, out);
+  gated(s, E * D, k.p2[m][0], k.p2[m][1], k.lin[m], base, out);
+}
+// M3GNetConv.forward (nn/conv.py:63-97): e_out = e_in + edge GatedMLP, x_out = x_in + the node GatedMLP's messages summed by centre.
+// Needs of w: cat, hid, msg, h; of k: p1, p2, lin.  x_out may be x_in and e_out may be e_in (the stand-alone module)
+static int conv_forward(hipStream_t s, int64_t N, int64_t E, int D, int R, const Topo& t, const GenMlpW* mlp, const GenWork& w,
+                        const GenWork::Blk& k, const float* x_in, const float* e_in, float* x_out, float* e_out) {
+  launch(g_concat, E * 3 * D, s, E, D, t.src, t.dst, x_in, e_in, w.cat);
+  gen_mlp_forward(s, E, D, R, mlp[0], w, k, 0, e_in, e_out);             // edge update
+  launch(g_concat, E * 3 * D, s, E, D, t.src, t.dst, x_in, e_out, w.cat);
+  gen_mlp_forward(s, E, D, R, mlp[1], w, k, 1, nullptr, w.msg);          // node message
+  if (x_out != x_in && N > 0) M3G_HIP_CHECK(hipMemcpyAsync(x_out, x_in, sizeof(float) * N * D, hipMemcpyDeviceToDevice, s));
+  launch(g_segsum, N * D, s, N, D, t.row_ptr, nullptr, w.msg, D, x_out, D, 1);
+  return M3G_OK;
+}
+// AtomWiseReadout's two GatedMLP branches (nn/readout.py:39-58): two SiLU layers [D,D], then one output each
+static void readout_forward(hipStream_t s, int64_t N, int D, const GenReadoutW& W, const float* x, const ReadoutBufs& r) {
+  for (int i = 0; i < 2; ++i) {
+    for (int g = 0; g < 2; ++g) linear(s, N, D, D, i == 0 ? x : r.h[0][g], D, W.w[g][i], W.b[g][i], r.p[i][g], D);
+    for (int g = 0; g < 2; ++g) map(s, N * D, OP_SILU, r.p[i][g], r.h[i][g]);
+  }
+  for (int g = 0; g < 2; ++g) linear(s, N, 1, D, r.h[1][g], D, W.w[g][2], W.b[g][2], r.o[g], 1);
 }
 
 // reverse of gen_mlp_forward (oracle/staged.py _mlp2_backward): d_upd [E,D] upstream; de_out (+)= W1c^T d_p1; dh += (d_upd out) W_l;
-// leaves d_p1 in w.dp1d[m] / w.dp1g[m]
-static void gen_mlp_reverse(hipStream_t s, int64_t E, int D, int R, const GenBlockW::Mlp& q, const GenWork& w, const GenWork::Blk& k, int m,
+// leaves d_p1 in w.dp1[m]
+static void gen_mlp_reverse(hipStream_t s, int64_t E, int D, int R, const GenMlpW& q, const GenWork& w, const GenWork::Blk& k, int m,
                             const float* d_upd, float* de_out) {
-  // gating: d_p2d, d_p2g into t0 / t1, d_lin into msg
-  hipLaunchKernelGGL(g_gated_rev, grid_for(E * D), dim3(256), 0, s, E * D, k.p2d[m], k.p2g[m], k.lin[m], d_upd, w.t0, w.t1, w.msg);
+  // gating: d_p2 dense / gate into t[0] / t[1], d_lin into msg
+  launch(g_gated_rev, E * D, s, E * D, k.p2[m][0], k.p2[m][1], k.lin[m], d_upd, w.t[0], w.t[1], w.msg);
   linear_t(s, E, D, R, w.msg, D, q.wl, w.dh, R, /*beta=*/true);            // dL/dh += d_lin W_l          (W_l [D,R])
-  linear_t(s, E, D, D, w.t0, D, q.w2d, w.dp1d[m], D);                       // d hidden dense = d_p2d W2d
-  linear_t(s, E, D, D, w.t1, D, q.w2g, w.dp1g[m], D);
-  map(s, E * D, OP_MUL_DSILU, k.p1d[m], w.dp1d[m]);
-  map(s, E * D, OP_MUL_DSILU, k.p1g[m], w.dp1g[m]);
+  for (int g = 0; g < 2; ++g) linear_t(s, E, D, D, w.t[g], D, q.w2[g], w.dp1[m][g], D);   // d hidden = d_p2 W2
+  for (int g = 0; g < 2; ++g) map(s, E * D, OP_MUL_DSILU, k.p1[m][g], w.dp1[m][g]);
   // e-part of W1 (columns 2D..3D of [D,3D]): de_out[e,k] += sum_o d_p1[e,o] W1[o, 2D + k]
-  gemm(s, E, D, D, w.dp1d[m], D, q.w1d + 2 * D, 3 * D, 1, nullptr, de_out, D, /*beta=*/true);
-  gemm(s, E, D, D, w.dp1g[m], D, q.w1g + 2 * D, 3 * D, 1, nullptr, de_out, D, /*beta=*/true);
+  for (int g = 0; g < 2; ++g) gemm(s, E, D, D, w.dp1[m][g], D, q.w1[g] + 2 * D, 3 * D, 1, nullptr, de_out, D, /*beta=*/true);
 }
 
 int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes, hipStream_t s) {
@@ -604,53 +593,27 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
   w = gen_carve(D, C, R, B, N, E, S, workspace);
   const GenW W = gen_weights(plan);
   Topo t = topo_carve(N, E, T, S, const_cast<void*>(io->topo));
-  float* tail = (float*)((char*)workspace + w.total - ((N + S * 2 + 64) * sizeof(float) + 255) / 256 * 256);
-  float* ea = io->scaled_atomic_energies ? io->scaled_atomic_energies : tail;
-  float* st = io->scaled_total_energy ? io->scaled_total_energy : tail + N;
+  float* ea = io->scaled_atomic_energies ? io->scaled_atomic_energies : w.tail;
+  float* st = io->scaled_total_energy ? io->scaled_total_energy : w.tail + N;
   Consts cc{};   // the shared launchers read only these fields
   cc.energy_scale = c.energy_scale; cc.length_scale = c.length_scale; cc.B = B; cc.num_types = c.num_types;
 
   // ---------------- forward ----------------
-  if (E > 0)
-    hipLaunchKernelGGL(g_geometry, grid_for(E), dim3(256), 0, s, c, E, t.src, t.dst, t.batch, io->pos, io->lattice, io->edge_cell_shift, w.u, w.d, w.h,
-                       w.hp, w.fc3, w.fc3p, w.q, w.qp);
-  if (N > 0) hipLaunchKernelGGL(g_embed_x, grid_for(N * D), dim3(256), 0, s, N, D, c.num_types, io->atom_types, W.emb, w.x[0]);
+  launch(g_geometry, E, s, c, E, t.src, t.dst, t.batch, io->pos, io->lattice, io->edge_cell_shift, w.u, w.d, w.h, w.hp, w.fc3, w.fc3p, w.q, w.qp);
+  launch(g_embed_x, N * D, s, N, D, c.num_types, io->atom_types, W.emb, w.x[0]);
   linear(s, E, D, R, w.h, R, W.adj, nullptr, w.pe0, D);                     // e0 = SiLU(W_adj h), nn/featurizer.py:128-132
   map(s, E * D, OP_SILU, w.pe0, w.e[0]);
   for (int b = 0; b < B; ++b) {
     const GenBlockW& kw = W.blk[b];
     const GenWork::Blk& k = w.b[b];
-    linear(s, N, C, D, w.x[b], D, kw.w1s, kw.b1s, k.v, C);                  // v = sigmoid(W1 x + b1), nn/interaction.py:204-205
-    map(s, N * C, OP_SIGMOID, k.v, k.v);
-    if (E > 0) {
-      hipLaunchKernelGGL(g_threebody_fwd, grid_for(E * c.L), dim3(256), 0, s, c, E, t.t1_ptr, t.t1_e2, t.dst, w.u, w.q, k.v, k.Ssum);
-      hipLaunchKernelGGL(g_scale_rows, grid_for(E * C), dim3(256), 0, s, E, C, w.fc3, k.Ssum, k.m);
-    }
-    linear(s, E, D, C, k.m, C, kw.wd, nullptr, k.pd, D);                    // three-body gated update, nn/interaction.py:220-221
-    linear(s, E, D, C, k.m, C, kw.wg, nullptr, k.pg, D);
-    gated(s, E * D, k.pd, k.pg, nullptr, w.e[b], k.e1);
-    if (E > 0) hipLaunchKernelGGL(g_concat, grid_for(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, w.x[b], k.e1, w.cat);
-    gen_mlp_forward(s, E, D, R, kw.e, w, k, 0, k.e1, w.e[b + 1]);           // edge update
-    if (E > 0) hipLaunchKernelGGL(g_concat, grid_for(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, w.x[b], w.e[b + 1], w.cat);
-    gen_mlp_forward(s, E, D, R, kw.n, w, k, 1, nullptr, w.msg);             // node message
-    if (N > 0) {
-      M3G_HIP_CHECK(hipMemcpyAsync(w.x[b + 1], w.x[b], sizeof(float) * N * D, hipMemcpyDeviceToDevice, s));
-      hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.msg, (int64_t)D, w.x[b + 1], (int64_t)D, 1);
-    }
+    threebody_gates(s, N, C, D, kw, w.x[b], k.v);
+    launch(g_threebody_fwd, E * c.L, s, c, E, t.t1_ptr, t.t1_e2, t.dst, w.u, w.q, k.v, k.Ssum);
+    launch(g_scale_rows, E * C, s, E, C, w.fc3, k.Ssum, k.m);
+    threebody_update(s, E, D, C, kw, k.m, k.p, w.e[b], k.e1);
+    { int rc = conv_forward(s, N, E, D, R, t, kw.mlp, w, k, w.x[b], k.e1, w.x[b + 1], w.e[b + 1]); if (rc) return rc; }
   }
-  // readout (nn/readout.py:39-58)
-  const float* xB = w.x[B];
-  linear(s, N, D, D, xB, D, W.rw[0][0], W.rb[0][0], w.rp1d, D);
-  linear(s, N, D, D, xB, D, W.rw[1][0], W.rb[1][0], w.rp1g, D);
-  map(s, N * D, OP_SILU, w.rp1d, w.rh0);
-  map(s, N * D, OP_SILU, w.rp1g, w.rh1);
-  linear(s, N, D, D, w.rh0, D, W.rw[0][1], W.rb[0][1], w.rp2d, D);
-  linear(s, N, D, D, w.rh1, D, W.rw[1][1], W.rb[1][1], w.rp2g, D);
-  map(s, N * D, OP_SILU, w.rp2d, w.rh0);
-  map(s, N * D, OP_SILU, w.rp2g, w.rh1);
-  linear(s, N, 1, D, w.rh0, D, W.rw[0][2], W.rb[0][2], w.rod, 1);
-  linear(s, N, 1, D, w.rh1, D, W.rw[1][2], W.rb[1][2], w.rog, 1);
-  if (N > 0) hipLaunchKernelGGL(g_atomic_energy, grid_for(N), dim3(256), 0, s, N, c.num_types, c.energy_scale, io->atom_types, W.elemental, w.rod, w.rog, ea, t.flags);
+  readout_forward(s, N, D, W.ro, w.x[B], w.r);   // nn/readout.py:39-58
+  launch(g_atomic_energy, N, s, N, c.num_types, c.energy_scale, io->atom_types, W.elemental, w.r.o[0], w.r.o[1], ea, t.flags);
   M3G_HIP_CHECK(hipMemsetAsync(st, 0, sizeof(float) * S, s));
   launch_energy_sums(cc, t, ea, st, io->total_energy, s);
 
@@ -670,18 +633,14 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
     M3G_HIP_CHECK(hipGetLastError());
     return M3G_OK;
   }
-  // readout reverse: dL/d eps = energy_scale
-  if (N > 0) hipLaunchKernelGGL(g_readout_seed, grid_for(N), dim3(256), 0, s, N, c.energy_scale, w.rod, w.rog, w.rod, w.rog);   // in place: d_od, d_og
-  linear_t(s, N, 1, D, w.rod, 1, W.rw[0][2], w.rh0, D);                    // d hidden-2 dense = d_od w3d
-  linear_t(s, N, 1, D, w.rog, 1, W.rw[1][2], w.rh1, D);
-  map(s, N * D, OP_MUL_DSILU, w.rp2d, w.rh0);                               // d p2
-  map(s, N * D, OP_MUL_DSILU, w.rp2g, w.rh1);
-  linear_t(s, N, D, D, w.rh0, D, W.rw[0][1], w.rp2d, D);                    // d hidden-1 (re-using the p2 buffers)
-  linear_t(s, N, D, D, w.rh1, D, W.rw[1][1], w.rp2g, D);
-  map(s, N * D, OP_MUL_DSILU, w.rp1d, w.rp2d);                              // d p1
-  map(s, N * D, OP_MUL_DSILU, w.rp1g, w.rp2g);
-  linear_t(s, N, D, D, w.rp2d, D, W.rw[0][0], w.dx, D);
-  linear_t(s, N, D, D, w.rp2g, D, W.rw[1][0], w.dx, D, /*beta=*/true);
+  // readout reverse: dL/d eps = energy_scale; every gradient takes the place of an array the forward pass is done with
+  const ReadoutBufs& r = w.r;
+  launch(g_readout_seed, N, s, N, c.energy_scale, r.o[0], r.o[1], r.o[0], r.o[1]);                           // d_o in place
+  for (int g = 0; g < 2; ++g) linear_t(s, N, 1, D, r.o[g], 1, W.ro.w[g][2], r.h[1][g], D);                    // d hidden-2 = d_o w3
+  for (int g = 0; g < 2; ++g) map(s, N * D, OP_MUL_DSILU, r.p[1][g], r.h[1][g]);                              // d p2
+  for (int g = 0; g < 2; ++g) linear_t(s, N, D, D, r.h[1][g], D, W.ro.w[g][1], r.p[1][g], D);                 // d hidden-1 (in the p2 arrays)
+  for (int g = 0; g < 2; ++g) map(s, N * D, OP_MUL_DSILU, r.p[0][g], r.p[1][g]);                              // d p1
+  for (int g = 0; g < 2; ++g) linear_t(s, N, D, D, r.p[1][g], D, W.ro.w[g][0], w.dx, D, /*beta=*/g == 1);
   M3G_HIP_CHECK(hipMemsetAsync(w.de, 0, sizeof(float) * E * D, s));
   M3G_HIP_CHECK(hipMemsetAsync(w.dh, 0, sizeof(float) * E * R, s));
   M3G_HIP_CHECK(hipMemsetAsync(w.dd, 0, sizeof(float) * E, s));
@@ -692,36 +651,31 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
     const GenBlockW& kw = W.blk[b];
     const GenWork::Blk& k = w.b[b];
     // node-message MLP: d msg[e] = dx[centre(e)]
-    if (E > 0) hipLaunchKernelGGL(g_gather, grid_for(E * D), dim3(256), 0, s, E, D, t.src, dx_cur, (int64_t)D, w.hd, (int64_t)D, 0);
-    gen_mlp_reverse(s, E, D, R, kw.n, w, k, 1, w.hd, w.de);                 // de (dL/de2) += node MLP's contribution
+    launch(g_gather, E * D, s, E, D, t.src, dx_cur, D, w.hid[0], D, 0);
+    gen_mlp_reverse(s, E, D, R, kw.mlp[1], w, k, 1, w.hid[0], w.de);        // de (dL/de2) += node MLP's contribution
     // edge-update MLP with upstream dL/de2 (a copy: de itself receives the contribution)
-    if (E > 0) M3G_HIP_CHECK(hipMemcpyAsync(w.hg, w.de, sizeof(float) * E * D, hipMemcpyDeviceToDevice, s));
-    gen_mlp_reverse(s, E, D, R, kw.e, w, k, 0, w.hg, w.de);                 // de = dL/de1
+    if (E > 0) M3G_HIP_CHECK(hipMemcpyAsync(w.hid[1], w.de, sizeof(float) * E * D, hipMemcpyDeviceToDevice, s));
+    gen_mlp_reverse(s, E, D, R, kw.mlp[0], w, k, 0, w.hid[1], w.de);        // de = dL/de1
     // three-body gated update reverse: d_pd, d_pg -> dm
-    if (E > 0) hipLaunchKernelGGL(g_gated_rev, grid_for(E * D), dim3(256), 0, s, E * D, k.pd, k.pg, nullptr, w.de, w.t0, w.t1, nullptr);
-    linear_t(s, E, D, C, w.t0, D, kw.wd, w.dm, C);
-    linear_t(s, E, D, C, w.t1, D, kw.wg, w.dm, C, /*beta=*/true);
-    if (E > 0)
-      hipLaunchKernelGGL(g_threebody_rev, grid_for(E), dim3(256), 0, s, c, E, t.t1_ptr, t.t1_e2, t.t2_ptr, t.t2_e1, t.dst, w.u, w.fc3, w.fc3p, w.q, w.qp,
-                         k.v, k.Ssum, w.dm, w.dd, w.du, w.dgq);
+    launch(g_gated_rev, E * D, s, E * D, k.p[0], k.p[1], nullptr, w.de, w.t[0], w.t[1], nullptr);
+    for (int g = 0; g < 2; ++g) linear_t(s, E, D, C, w.t[g], D, kw.wt[g], w.dm, C, /*beta=*/g == 1);
+    launch(g_threebody_rev, E, s, c, E, t.t1_ptr, t.t1_e2, t.t2_ptr, t.t2_e1, t.dst, w.u, w.fc3, w.fc3p, w.q, w.qp, k.v, k.Ssum, w.dm, w.dd, w.du,
+           w.dgq);
     if (b > 0 && N > 0) {   // x^0 is the species embedding: its gradient is never needed
-      // d_TA / d_TB = dp1 rows summed by centre / by neighbour, columns [edge dense | edge gate | node dense | node gate]
-      for (int m = 0; m < 2; ++m) {
-        hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.dp1d[m], (int64_t)D, w.dTA + (2 * m) * D, (int64_t)4 * D, 0);
-        hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.dp1g[m], (int64_t)D, w.dTA + (2 * m + 1) * D, (int64_t)4 * D, 0);
-        hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.in_ptr, t.in_edge, w.dp1d[m], (int64_t)D, w.dTB + (2 * m) * D, (int64_t)4 * D, 0);
-        hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.in_ptr, t.in_edge, w.dp1g[m], (int64_t)D, w.dTB + (2 * m + 1) * D, (int64_t)4 * D, 0);
-      }
-      hipLaunchKernelGGL(g_segsum, grid_for(N * C), dim3(256), 0, s, N, C, t.in_ptr, t.in_edge, w.dgq, (int64_t)C, w.dv, (int64_t)C, 0);
+      // dT[side]: dp1 rows summed by centre (side 0) / by neighbour (side 1), columns [edge dense | edge gate | node dense | node gate]
+      const int32_t* const ptr[2] = {t.row_ptr, t.in_ptr};
+      const int32_t* const list[2] = {nullptr, t.in_edge};
+      for (int m = 0; m < 2; ++m)
+        for (int side = 0; side < 2; ++side)
+          for (int g = 0; g < 2; ++g)
+            launch(g_segsum, N * D, s, N, D, ptr[side], list[side], w.dp1[m][g], D, w.dT[side] + (2 * m + g) * D, 4 * D, 0);
+      launch(g_segsum, N * C, s, N, C, t.in_ptr, t.in_edge, w.dgq, C, w.dv, C, 0);
       map(s, N * C, OP_MUL_DSIGMOID_OF_V, k.v, w.dv);
       M3G_HIP_CHECK(hipMemcpyAsync(dx_alt, dx_cur, sizeof(float) * N * D, hipMemcpyDeviceToDevice, s));
-      const GenBlockW::Mlp* mm[2] = {&kw.e, &kw.n};
-      for (int m = 0; m < 2; ++m) {   // x_i part: columns 0..D of W1, x_j part: columns D..2D
-        gemm(s, N, D, D, w.dTA + (2 * m) * D, 4 * D, mm[m]->w1d, 3 * D, 1, nullptr, dx_alt, D, true);
-        gemm(s, N, D, D, w.dTA + (2 * m + 1) * D, 4 * D, mm[m]->w1g, 3 * D, 1, nullptr, dx_alt, D, true);
-        gemm(s, N, D, D, w.dTB + (2 * m) * D, 4 * D, mm[m]->w1d + D, 3 * D, 1, nullptr, dx_alt, D, true);
-        gemm(s, N, D, D, w.dTB + (2 * m + 1) * D, 4 * D, mm[m]->w1g + D, 3 * D, 1, nullptr, dx_alt, D, true);
-      }
+      for (int m = 0; m < 2; ++m)   // x_i part: columns 0..D of W1 (side 0), x_j part: columns D..2D (side 1)
+        for (int side = 0; side < 2; ++side)
+          for (int g = 0; g < 2; ++g)
+            gemm(s, N, D, D, w.dT[side] + (2 * m + g) * D, 4 * D, kw.mlp[m].w1[g] + side * D, 3 * D, 1, nullptr, dx_alt, D, true);
       linear_t(s, N, C, D, w.dv, C, kw.w1s, dx_alt, D, true);
       float* tmp = dx_cur; dx_cur = dx_alt; dx_alt = tmp;
     }
@@ -729,7 +683,7 @@ int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspac
   // edge embedding reverse: dh += (de * SiLU'(pe0)) W_adj
   map(s, E * D, OP_MUL_DSILU, w.pe0, w.de);
   linear_t(s, E, D, R, w.de, D, W.adj, w.dh, R, true);
-  if (E > 0) hipLaunchKernelGGL(g_geometry_rev, grid_for(E), dim3(256), 0, s, E, R, w.u, w.d, w.hp, w.dh, w.dd, w.du, w.dr);
+  launch(g_geometry_rev, E, s, E, R, w.u, w.d, w.hp, w.dh, w.dd, w.du, w.dr);
   launch_force_gather(c.length_scale, t, w.dr, io->forces, io->stresses, s);
   if (io->stresses) {
     if (plan->opt.stress_mode == 1) {
@@ -762,7 +716,7 @@ __global__ void __launch_bounds__(256) g_bessel_basis(GenConsts c, int64_t n, co
   const int64_t t = gid % n;
   const int cc = (int)(gid / n), l = cc / c.R, k = cc % c.R;
   float jl[kGL], djl[kGL];
-  g_bessel(c.L, c.zeros[l][k] * rs[t] / c.rc, jl, djl);
+  sph_bessel<kGL, false>(c.L, c.zeros[l][k] * rs[t] / c.rc, jl, djl);
   out[gid] = jl[l] / c.factors[l][k];
 }
 // per triplet and order l: m[e1, l*R+n] += chi_ln(d_ik) Y_l(cos) fc(d_ij) fc(d_ik) v[k, l*R+n]   (nn/interaction.py:188-217; the
@@ -775,20 +729,14 @@ __global__ void __launch_bounds__(256) g_threebody_standalone(GenConsts c, int64
   const int l = (int)(gid % c.L);
   const int64_t e1 = tei[t], e2 = tei[T + t];
   const float d1 = dist[e1], d2 = dist[e2];
-  auto fc = [&](float d) {
-    const float rho = d / c.rc3;
-    if (rho > 1.f) return 0.f;
-    const float r2 = rho * rho, r3 = r2 * rho;
-    return 1.f - 6.f * r3 * r2 + 15.f * r2 * r2 - 10.f * r3;
-  };
-  const float f = fc(d1) * fc(d2);
+  const float f = envelope(d1, c.rc3).f * envelope(d2, c.rc3).f;
   float P[kGL], dP[kGL];
-  g_legendre(c.L, angles[t], P, dP);
+  legendre<false>(c.L, angles[t], P, dP);
   const float y = c.ynorm[l] * P[l] * f;
   const int64_t k = ei[E + e2];
   for (int n = 0; n < c.R; ++n) {
     float jl[kGL], djl[kGL];
-    g_bessel(c.L, c.zeros[l][n] * d2 / c.rc, jl, djl);
+    sph_bessel<kGL, false>(c.L, c.zeros[l][n] * d2 / c.rc, jl, djl);
     atomicAdd(&m[e1 * c.C + l * c.R + n], jl[l] / c.factors[l][n] * y * v[k * c.C + l * c.R + n]);
   }
 }
@@ -807,11 +755,8 @@ __global__ void __launch_bounds__(256) g_scale(int64_t n, float a, const float* 
 }
 static GenConsts basis_consts(int l_max, int n_max, double rc, double rc3, const float* zeros, const float* factors) {
   GenConsts c{};
-  c.L = l_max; c.R = n_max; c.C = l_max * n_max; c.rc = (float)rc; c.rc3 = (float)rc3;
-  for (int l = 0; l < l_max; ++l) {
-    c.ynorm[l] = (float)std::sqrt((2 * l + 1) / (4.0 * M_PI));
-    for (int n = 0; n < n_max; ++n) { c.zeros[l][n] = zeros[l * n_max + n]; c.factors[l][n] = factors[l * n_max + n]; }
-  }
+  c.L = l_max; c.R = n_max; c.C = l_max * n_max;
+  fill_angular_consts(c, l_max, n_max, rc, rc3, zeros, factors);
   return c;
 }
 }  // namespace
@@ -832,7 +777,7 @@ extern "C" int m3g_linear(int64_t n, int32_t in, int32_t out, const float* X, co
 // y = a * b elementwise (the final dense(x) * gate(x) of GatedMLP.forward, nn/core.py:61-62)
 extern "C" int m3g_multiply(int64_t n, const float* a, const float* b, float* y, void* stream_) {
   if (n < 0 || (n > 0 && (!a || !b || !y))) { set_error("m3g_multiply: bad argument"); return M3G_ERR_VALUE; }
-  if (n > 0) hipLaunchKernelGGL(g_mul, grid_for(n), dim3(256), 0, (hipStream_t)stream_, n, a, b, y);
+  launch(g_mul, n, (hipStream_t)stream_, n, a, b, y);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }
@@ -844,7 +789,7 @@ extern "C" int m3g_bessel_basis(int32_t l_max, int32_t n_max, double cutoff, con
     return M3G_ERR_VALUE;
   }
   const GenConsts c = basis_consts(l_max, n_max, cutoff, cutoff, host_zeros, host_factors);
-  if (n > 0) hipLaunchKernelGGL(g_bessel_basis, grid_for(n * c.C), dim3(256), 0, (hipStream_t)stream_, c, n, rs, out);
+  launch(g_bessel_basis, n * c.C, (hipStream_t)stream_, c, n, rs, out);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }
@@ -862,18 +807,16 @@ extern "C" int m3g_three_body(int32_t l_max, int32_t n_max, int32_t D, double sc
   hipStream_t s = (hipStream_t)stream_;
   const GenConsts c = basis_consts(l_max, n_max, scaled_cutoff, scaled_threebody_cutoff, host_zeros, host_factors);
   const int C = c.C;
-  float* v = scratch;
-  float* m = v + (size_t)N * C;
-  float* pd = m + (size_t)E * C;
-  float* pg = pd + (size_t)E * D;
-  linear(s, N, C, D, x, D, w_sigmoid, b_sigmoid, v, C);
-  map(s, N * C, OP_SIGMOID, v, v);
+  GenBlockW kw{};
+  kw.w1s = w_sigmoid; kw.b1s = b_sigmoid; kw.wt[0] = w_dense; kw.wt[1] = w_gate;
+  Packed cur{scratch};
+  float* v = cur.take((size_t)N * C);
+  float* m = cur.take((size_t)E * C);
+  float* p[2] = {cur.take((size_t)E * D), cur.take((size_t)E * D)};
+  threebody_gates(s, N, C, D, kw, x, v);
   M3G_HIP_CHECK(hipMemsetAsync(m, 0, sizeof(float) * E * C, s));
-  if (T > 0) hipLaunchKernelGGL(g_threebody_standalone, grid_for(T * c.L), dim3(256), 0, s, c, T, E, edge_index, triplet_edge_index, edge_distances,
-                                triplet_angles, v, m);
-  linear(s, E, D, C, m, C, w_dense, nullptr, pd, D);
-  linear(s, E, D, C, m, C, w_gate, nullptr, pg, D);
-  gated(s, E * D, pd, pg, nullptr, edge_attr, edge_attr);
+  launch(g_threebody_standalone, T * c.L, s, c, T, E, edge_index, triplet_edge_index, edge_distances, triplet_angles, v, m);
+  threebody_update(s, E, D, C, kw, m, p, edge_attr, edge_attr);
   if (mid && E > 0) M3G_HIP_CHECK(hipMemcpyAsync(mid, m, sizeof(float) * E * C, hipMemcpyDeviceToDevice, s));
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
@@ -896,24 +839,21 @@ extern "C" int m3g_conv_block(int32_t D, int32_t R, int64_t N, int64_t E, int64_
   hipStream_t s = (hipStream_t)stream_;
   Topo t = topo_carve(N, E, T, S, const_cast<void*>(topo));
   GenWork w{};
-  GenWork::Blk k{};
-  float* p = scratch;
-  auto take = [&](size_t n) { float* r = p; p += n; return r; };
+  GenWork::Blk k{};   // nothing is kept for a reverse pass: the two MLPs share one set of activation arrays
+  Packed cur{scratch};
   const size_t ed = (size_t)E * D;
-  w.cat = take(3 * ed); w.hd = take(ed); w.hg = take(ed); w.msg = take(ed);
+  w.cat = cur.take(3 * ed); w.hid[0] = cur.take(ed); w.hid[1] = cur.take(ed); w.msg = cur.take(ed);
   w.h = const_cast<float*>(edge_weights);
-  k.p1d[0] = k.p1d[1] = take(ed); k.p1g[0] = k.p1g[1] = take(ed); k.p2d[0] = k.p2d[1] = take(ed); k.p2g[0] = k.p2g[1] = take(ed);
-  k.lin[0] = k.lin[1] = take(ed);
-  GenBlockW::Mlp q[2];
+  for (int g = 0; g < 2; ++g) k.p1[0][g] = k.p1[1][g] = cur.take(ed);
+  for (int g = 0; g < 2; ++g) k.p2[0][g] = k.p2[1][g] = cur.take(ed);
+  k.lin[0] = k.lin[1] = cur.take(ed);
+  GenMlpW q[2];
   for (int m = 0; m < 2; ++m) {
     const float* const* a = host_params + 9 * m;
-    q[m] = GenBlockW::Mlp{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]};
+    for (int g = 0; g < 2; ++g) { q[m].w1[g] = a[g]; q[m].b1[g] = a[2 + g]; q[m].w2[g] = a[4 + g]; q[m].b2[g] = a[6 + g]; }
+    q[m].wl = a[8];
   }
-  if (E > 0) hipLaunchKernelGGL(g_concat, grid_for(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, x, edge_attr, w.cat);
-  gen_mlp_forward(s, E, D, R, q[0], w, k, 0, edge_attr, edge_attr);   // e += GatedMLP(concat) * (W_e h)
-  if (E > 0) hipLaunchKernelGGL(g_concat, grid_for(E * 3 * D), dim3(256), 0, s, E, D, t.src, t.dst, x, edge_attr, w.cat);
-  gen_mlp_forward(s, E, D, R, q[1], w, k, 1, nullptr, w.msg);
-  if (N > 0) hipLaunchKernelGGL(g_segsum, grid_for(N * D), dim3(256), 0, s, N, D, t.row_ptr, nullptr, w.msg, (int64_t)D, x, (int64_t)D, 1);
+  { int rc = conv_forward(s, N, E, D, R, t, q, w, k, x, edge_attr, x, edge_attr); if (rc) return rc; }   // in place
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }
@@ -927,24 +867,18 @@ extern "C" int m3g_readout(int32_t D, int64_t N, int64_t S, const float* const* 
     return M3G_ERR_VALUE;
   }
   hipStream_t s = (hipStream_t)stream_;
-  const size_t nd = (size_t)N * D;
-  float* hd = scratch; float* hg = hd + nd; float* t0 = hg + nd; float* t1 = t0 + nd; float* od = t1 + nd; float* og = od + N;
-  const float* const* dp = host_params;
-  const float* const* gp = host_params + 6;
-  linear(s, N, D, D, x, D, dp[0], dp[1], hd, D);
-  linear(s, N, D, D, x, D, gp[0], gp[1], hg, D);
-  map(s, N * D, OP_SILU, hd, hd);
-  map(s, N * D, OP_SILU, hg, hg);
-  linear(s, N, D, D, hd, D, dp[2], dp[3], t0, D);
-  linear(s, N, D, D, hg, D, gp[2], gp[3], t1, D);
-  map(s, N * D, OP_SILU, t0, t0);
-  map(s, N * D, OP_SILU, t1, t1);
-  linear(s, N, 1, D, t0, D, dp[4], dp[5], od, 1);
-  linear(s, N, 1, D, t1, D, gp[4], gp[5], og, 1);
+  GenReadoutW W{};
+  ReadoutBufs r{};
+  Packed cur{scratch};
+  for (int i = 0; i < 2; ++i)
+    for (int g = 0; g < 2; ++g) r.p[i][g] = r.h[i][g] = cur.take((size_t)N * D);   // hidden in place of its pre-activation
+  for (int g = 0; g < 2; ++g) r.o[g] = cur.take((size_t)N);
+  for (int g = 0; g < 2; ++g)
+    for (int i = 0; i < 3; ++i) { W.w[g][i] = host_params[6 * g + 2 * i]; W.b[g][i] = host_params[6 * g + 2 * i + 1]; }
+  readout_forward(s, N, D, W, x, r);
   M3G_HIP_CHECK(hipMemsetAsync(scaled_total, 0, sizeof(float) * S, s));
-  if (N > 0) hipLaunchKernelGGL(g_atomic_energy_standalone, grid_for(N), dim3(256), 0, s, N, (float)energy_scale, elemental_per_atom, od, og, batch,
-                                scaled_atomic, scaled_total);
-  if (S > 0) hipLaunchKernelGGL(g_scale, grid_for(S), dim3(256), 0, s, S, (float)energy_scale, scaled_total, total);
+  launch(g_atomic_energy_standalone, N, s, N, (float)energy_scale, elemental_per_atom, r.o[0], r.o[1], batch, scaled_atomic, scaled_total);
+  launch(g_scale, S, s, S, (float)energy_scale, scaled_total, total);
   M3G_HIP_CHECK(hipGetLastError());
   return M3G_OK;
 }

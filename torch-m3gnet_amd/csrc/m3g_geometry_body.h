@@ -3,67 +3,25 @@
 // Reference: nn/scale.py:24-29, nn/invariant.py:20-59, nn/featurizer.py:81-100, nn/interaction.py:268-350,389-400.
 #pragma once
 #include "m3g_internal.h"
+#include "m3g_basis.h"
 
 namespace m3g {
 
-// torch.sinc: sin(pi x)/(pi x), and cos(pi x) from the same argument reduction
-__device__ __forceinline__ float sinc_cos_pi(float x, float& cos_px) {
-  const float kPi = 3.14159265358979323846f;
-  float px = kPi * x, sn;
-  sincosf(px, &sn, &cos_px);
-  return x == 0.f ? 1.f : sn / px;
-}
-
-// radial basis h_m(d) and dh_m/dd (nn/featurizer.py:84-96)
+// radial basis h_m(d) and dh_m/dd (nn/featurizer.py:84-96), zero beyond the model's n_max
 __device__ __forceinline__ void radial_basis(const Consts& c, float d, float* h, float* hp) {
+  float f = 0.f, df = 0.f;
 #pragma unroll
   for (int m = 0; m < kRCap; ++m) {
     if (m < c.R) {
-      float x1 = c.a1[m] * d, x2 = c.a2[m] * d;
-      float c1, c2;
-      float s1 = sinc_cos_pi(x1, c1), s2 = sinc_cos_pi(x2, c2);
-      float f = c.coeff[m] * (s1 + s2);
-      float df = c.coeff[m] * ((c1 - s1) + (c2 - s2)) / d;
-      if (m == 0) {
-        h[0] = f;
-        hp[0] = df;
-      } else {
-        h[m] = (f + c.rec_mul[m] * h[m - 1]) / c.rec_div[m];
-        hp[m] = (df + c.rec_mul[m] * hp[m - 1]) / c.rec_div[m];
-      }
+      if (m > 0) { f = h[m - 1]; df = hp[m - 1]; }   // (what f / df hold already; read back, the kernels compile as they always did)
+      radial_term(c, m, d, f, df);
+      h[m] = f;
+      hp[m] = df;
     } else {
       h[m] = 0.f;
       hp[m] = 0.f;
     }
   }
-}
-
-// j_l(x), j_l'(x) for l = 0..L-1, upward recurrence with the reference's x <= 1e-8 branch
-__device__ __forceinline__ void sph_bessel(int L, float x, float* j, float* dj) {
-  float seq[kLCap + 1];
-  if (x > 1e-8f) {
-    float sn, cx;
-    sincosf(x, &sn, &cx);
-    float sx = sn / x;
-    seq[0] = sx;
-    seq[1] = (sx - cx) / x;
-#pragma unroll
-    for (int n = 1; n < kLCap; ++n) seq[n + 1] = (float)(2 * n + 1) / x * seq[n] - seq[n - 1];
-#pragma unroll
-    for (int l = 0; l < kLCap; ++l) {
-      j[l] = seq[l];
-      dj[l] = l == 0 ? -seq[1] : seq[l - 1] - (float)(l + 1) / x * seq[l];
-    }
-  } else {
-    float dfact = 1.f;
-#pragma unroll
-    for (int l = 0; l < kLCap; ++l) {
-      if (l > 0) dfact *= (float)(2 * l + 1);
-      j[l] = l == 0 ? 1.f : x / dfact;
-      dj[l] = l == 1 ? 1.f / 3.f : 0.f;
-    }
-  }
-  (void)L;
 }
 
 struct GeomArgs {
@@ -121,13 +79,8 @@ __device__ __forceinline__ void geometry_body(const Consts& c, const GeomArgs& a
   *(float4*)(h + e * kRP) = float4{hh[0], hh[1], hh[2], hh[3]};
   *(float4*)(hp + e * kRP) = float4{hd[0], hd[1], hd[2], hd[3]};
   // three-body cutoff envelope (nn/interaction.py:389-400) and its derivative
-  float rho = d / c.rc3;
-  float f = 0.f, fp = 0.f;
-  if (rho <= 1.f) {
-    float r2 = rho * rho, r3 = r2 * rho;
-    f = 1.f - 6.f * r3 * r2 + 15.f * r2 * r2 - 10.f * r3;
-    fp = (-30.f * r2 * r2 + 60.f * r3 - 30.f * r2) / c.rc3;
-  }
+  const Envelope env = envelope(d, c.rc3);
+  const float f = env.f, fp = env.fp;
   fc3[e] = f;
   fc3p[e] = fp;
   // q[ar,c] = chi_ln(d) fc(d),  c = l*R + n  (nn/interaction.py:268-281), one row per ACTIVE edge (ar = act_id[e]): an edge
@@ -144,7 +97,7 @@ __device__ __forceinline__ void geometry_body(const Consts& c, const GeomArgs& a
       float jl[kLCap], djl[kLCap];
       // the argument differs per (l,n): z_ln * d / rc
       float x = c.zeros[l][n] * d / c.rc;
-      sph_bessel(L, x, jl, djl);
+      sph_bessel<kLCap, true>(kLCap, x, jl, djl);   // all kLCap orders: those beyond L fold away
       float chi = jl[l] / c.factors[l][n];
       float dchi = djl[l] * (c.zeros[l][n] / c.rc) / c.factors[l][n];
       qr[l * R + n] = chi * f;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <map>
@@ -241,6 +242,34 @@ struct Carve {
 };
 // the byte offset of a pointer taken from a Carve over a null base
 inline size_t carve_offset(const void* p) { return (size_t)(uintptr_t)p; }
+
+// ---- the fp32 basis constants, for Consts and the any-size path's GenConsts alike ---------------------------------------
+// fp32 arithmetic in the reference's order (see oracle make_constants / radial_basis): parity rests on these lines.
+// radial basis of n_max = R terms over the scaled cutoff rc (nn/featurizer.py:87-96)
+template <class C>
+inline void fill_radial_consts(C& c, int R, double rc, const float* coeff, const float* em, const float* dm) {
+  const float pi_f = (float)M_PI;
+  for (int m = 0; m < R; ++m) {
+    c.a1[m] = ((float)(m + 1) * pi_f) / (float)rc;
+    c.a2[m] = ((float)(m + 2) * pi_f) / (float)rc;
+    c.coeff[m] = coeff[m];
+    c.rec_mul[m] = m > 0 ? sqrtf(em[m] / dm[m - 1]) : 0.f;
+    c.rec_div[m] = sqrtf(dm[m]);
+  }
+}
+// three-body bases: the scaled cutoffs, sqrt((2l+1)/(4 pi)) (nn/interaction.py:198) and the [L, R] tables of Bessel roots and factors
+template <class C>
+inline void fill_angular_consts(C& c, int L, int R, double rc, double rc3, const float* zeros, const float* factors) {
+  c.rc = (float)rc;
+  c.rc3 = (float)rc3;
+  for (int l = 0; l < L; ++l) {
+    c.ynorm[l] = (float)std::sqrt((2 * l + 1) / (4.0 * M_PI));
+    for (int n = 0; n < R; ++n) {
+      c.zeros[l][n] = zeros[l * R + n];
+      c.factors[l][n] = factors[l * R + n];
+    }
+  }
+}
 
 // ---- device helper shared by the graph-side units -----------------------------------------------------------
 // One thread's binary search: the first index of the sorted a[0..n) whose key is not below `key`, n when there is none.  `key_of`

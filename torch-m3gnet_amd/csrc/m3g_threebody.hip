@@ -40,17 +40,6 @@ __device__ __forceinline__ void load_row(const float* __restrict__ row, float* o
   }
 }
 
-template <int L>
-__device__ __forceinline__ void legendre(float x, float* P, float* dP) {
-  P[0] = 1.f; dP[0] = 0.f;
-  if (L > 1) { P[1] = x; dP[1] = 1.f; }
-#pragma unroll
-  for (int n = 1; n < L - 1; ++n) {
-    P[n + 1] = ((float)(2 * n + 1) * x * P[n] - (float)n * P[n - 1]) / (float)(n + 1);
-    dP[n + 1] = ((float)(2 * n + 1) * (P[n] + x * dP[n]) - (float)n * dP[n - 1]) / (float)(n + 1);
-  }
-}
-
 struct TbArgs {
   int64_t E;
   const int32_t *act_list, *act_dst, *tb_win, *n_act;
@@ -139,7 +128,7 @@ __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_fwd(Consts c, TbArg
     }
     const float cs = fminf(1.f, fmaxf(-1.f, ux * vx + uy * vy + uz * vz));
     float P[L], dP[L];
-    legendre<L>(cs, P, dP);
+    legendre<true>(L, cs, P, dP);
 #pragma unroll
     for (int l = 0; l < L; ++l) {
       const float y = c.ynorm[l] * P[l];
@@ -176,23 +165,8 @@ struct TbRevArgs {
   const float *u, *fc3, *fc3p, *q, *qp, *v, *dm;
   float *dd, *du, *dgq;   // dd [A], du [A,3]: geometry gradients of the three-body term, one row per active edge
   int first;              // first reverse launch of the step (last block): dd/du are written, later launches accumulate
-  int ref_legendre;       // option "legendre_backward" = 1: the reference's own backward of P_l (below)
+  int ref_legendre;       // option "legendre_backward" = 1: the reference's own backward of P_l (m3g_basis.h: legendre_ref_k)
 };
-
-// LegendreCosPolynomial.backward (nn/interaction.py:373-382) multiplies grad_output in at EVERY level of its recurrence,
-//   grad_n = (n P_{n-1} + x grad_{n-1}) go   =>   grad_n = go k_n,  k_1 = 1,  k_n = n P_{n-1} + x go k_{n-1},
-// which is the derivative P_n' go only for n <= 1 (SURVEY finding 2).  The engine computes the true derivative; with the option
-// set, the list kernels return this k_n instead of P_n' so that forces and stresses reproduce the reference's own numbers.
-// `go` is the gradient arriving at legendre_cos(cos, l)'s output for ONE triplet and ONE l (the reference calls it once per l).
-template <int L>
-__device__ __forceinline__ float legendre_ref_k(int l, float x, const float* P, float go) {
-  if (l == 0) return 0.f;
-  float k = 1.f;
-#pragma unroll
-  for (int n = 2; n < L; ++n)
-    if (n <= l) k = (float)n * P[n - 1] + x * go * k;
-  return k;
-}
 
 template <int L, int R, int LIST, int CAP, int LPR>
 __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_rev(Consts c, TbRevArgs a) {
@@ -276,7 +250,7 @@ __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_rev(Consts c, TbRev
     const float raw = ux * vx + uy * vy + uz * vz;
     const float cs = fminf(1.f, fmaxf(-1.f, raw));
     float P[L], dP[L];
-    legendre<L>(cs, P, dP);
+    legendre<true>(L, cs, P, dP);
     float dcos = 0.f;
 #pragma unroll
     for (int l = 0; l < L; ++l) {
@@ -296,7 +270,7 @@ __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_rev(Consts c, TbRev
 #pragma unroll
         for (int nn = 0; nn < R; ++nn) G += dmv[l * R + nn] * pr[l * R + nn];
         const float g1 = c.ynorm[l] * G;
-        dcos += g1 * legendre_ref_k<L>(l, cs, P, fc * g1);
+        dcos += g1 * legendre_ref_k<true>(L, l, cs, P, fc * g1);
       }
     }
     dcos = (raw >= -1.f && raw <= 1.f) ? dcos : 0.f;   // torch.clamp passes the gradient only inside [-1, 1]
@@ -309,7 +283,7 @@ __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_rev(Consts c, TbRev
     const float raw = ux * vx + uy * vy + uz * vz;
     const float cs = fminf(1.f, fmaxf(-1.f, raw));
     float P[L], dP[L];
-    legendre<L>(cs, P, dP);
+    legendre<true>(L, cs, P, dP);
     float dcos = 0.f;
 #pragma unroll
     for (int l = 0; l < L; ++l) {
@@ -329,7 +303,7 @@ __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_rev(Consts c, TbRev
 #pragma unroll
         for (int nn = 0; nn < R; ++nn) G += pr[l * R + nn] * gv[l * R + nn];
         const float go = c.ynorm[l] * G;
-        dcos += go * legendre_ref_k<L>(l, cs, P, go);
+        dcos += go * legendre_ref_k<true>(L, l, cs, P, go);
       }
     }
     dcos = (raw >= -1.f && raw <= 1.f) ? dcos : 0.f;
