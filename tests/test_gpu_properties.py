@@ -666,7 +666,7 @@ def test_config5_full_size_through_properties():
 
 
 # ------------------------------------------------------------------ hyper-parameter sweep (padding paths, template variants)
-@pytest.mark.parametrize("l_max,n_max,dim,blocks,cut,tb_cut", [
+_SWEEP = [
     (1, 1, 8, 1, 4.0, 3.0),     # smallest everything: C = 1, one three-body k-step
     (2, 2, 33, 4, 4.5, 4.5),    # odd width (zero-padded to 64), 4 blocks, 3-body cutoff == cutoff
     (4, 4, 64, 2, 5.0, 3.5),    # largest supported bases: C = 16
@@ -678,34 +678,91 @@ def test_config5_full_size_through_properties():
     (5, 5, 32, 2, 4.5, 4.0),    # l_max = n_max = 5, C = 25
     (9, 10, 24, 1, 4.0, 3.5),   # the reference's Bessel-root table used to its limits: C = 90
     (2, 3, 20, 10, 4.0, 3.5),   # more than 8 blocks
-])
-def test_hyperparameter_sweep_against_oracle(l_max, n_max, dim, blocks, cut, tb_cut):
-    from oracle import m3gnet_oracle as orc
-    from torch_m3gnet.data.material_graph import Batch
+]
+
+
+def _sweep_model_and_cells(l_max, n_max, dim, blocks, cut, tb_cut):
     from torch_m3gnet.model.build import build_model
 
-    K = _K()
     torch.manual_seed(11)
     model = build_model(cut, tb_cut, l_max, n_max, 60, dim, blocks, elemental_energies=torch.linspace(-1, 1, 60), energy_scale=1.7)
     for m in model.model:
         if type(m).__name__ == "ThreeBodyInteration":
             m.nsb.factors = m.nsb.documented_factors()
     cells = [random_cell_graph(14 + 3 * s, 6.0 + 0.3 * s, 20 + s, cutoff=cut, tb_cutoff=tb_cut, zmax=59) for s in range(3)]
+    return model, cells
+
+
+def _sweep_oracle(model, out):
+    p, cfg, c, og = _oracle_inputs(model, out)
+    p = {k: v.double() for k, v in p.items()}
+    c = orc.make_constants(cfg, model.model[1].elemental_energies.cpu(), dtype=torch.float64)
+    c.factors = model.model[6].nsb.factors.double()
+    return orc.energy_forces(p, cfg, c, og, legendre_backward="exact")
+
+
+@pytest.mark.parametrize("l_max,n_max,dim,blocks,cut,tb_cut", _SWEEP)
+def test_hyperparameter_sweep_against_oracle(l_max, n_max, dim, blocks, cut, tb_cut):
+    from torch_m3gnet.data.material_graph import Batch
+
+    K = _K()
+    model, cells = _sweep_model_and_cells(l_max, n_max, dim, blocks, cut, tb_cut)
     big = l_max > 4 or n_max > 4 or dim > 64 or blocks > 8
     for kern in ((2,) if big else (1, 0, 2)):   # 1: MFMA kernels, 0: vector-ALU baseline, 2: any-size path
         model.engine.set_option("edge_kernel", kern)
         out = model(Batch.from_data_list([c.clone() for c in cells]).to(DEV))
-        p, cfg, c, og = _oracle_inputs(model, out)
-        p = {k: v.double() for k, v in p.items()}
-        c = orc.make_constants(cfg, model.model[1].elemental_energies.cpu(), dtype=torch.float64)
-        c.factors = model.model[6].nsb.factors.double()
-        o = orc.energy_forces(p, cfg, c, og, legendre_backward="exact")
+        o = _sweep_oracle(model, out)
         assert float(((out[K.TOTAL_ENERGY].cpu().double() - o["total_energy"]).abs() / o["total_energy"].abs()).max()) < 1e-5, kern
         assert rel_err(out[K.FORCES], o["forces"]) < 1e-4, kern
         assert rel_err(out[K.STRESSES], o["stresses"]) < 1e-4, kern
         assert rel_err(out[K.EDGE_ATTR], o["edge_attr"]) < 1e-5, kern
         for b in range(blocks):
             assert rel_err(out[K.MID_EDGE_FEATURES][b], o[f"mid_edge_features_{b}"]) < 1e-4, (kern, b)
+
+
+@pytest.mark.parametrize("l_max,n_max,dim,blocks,cut,tb_cut", _SWEEP[:5])
+def test_sweep_threebody_list_and_moment_paths_against_oracle(l_max, n_max, dim, blocks, cut, tb_cut):
+    """The sweep's first five configurations (its three cells, the MFMA edge kernels) with option "threebody_moments" 1 and 0.  The
+    lists of these cells are complete, so the default sends every l_max <= 3 configuration to the moment kernels and the list
+    kernels' instantiations for (1,1), (2,2) and (3,4) run only with the option off.  Both runs against the fp64 oracle at the
+    sweep's gates; where the moment path applies, also against each other at the tolerances of
+    test_threebody_moment_and_list_paths_agree (the two sum in different orders: bit-equal aggregates would mean the moment path
+    never ran)."""
+    from torch_m3gnet.data.material_graph import Batch
+
+    K = _K()
+    model, cells = _sweep_model_and_cells(l_max, n_max, dim, blocks, cut, tb_cut)
+    model.engine.set_option("edge_kernel", 1)
+    batch = Batch.from_data_list([c.clone() for c in cells]).to(DEV)
+    out, o = {}, None
+    try:
+        for moments in (1, 0):
+            model.engine.set_option("threebody_moments", moments)
+            g = model(batch)
+            torch.cuda.synchronize()
+            if o is None:
+                o = _sweep_oracle(model, g)
+            out[moments] = {k: g[k].detach().clone() for k in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES, K.MID_EDGE_FEATURES)}
+            e_err = float(((g[K.TOTAL_ENERGY].cpu().double() - o["total_energy"]).abs() / o["total_energy"].abs()).max())
+            f_err, s_err = rel_err(g[K.FORCES], o["forces"]), rel_err(g[K.STRESSES], o["stresses"])
+            m_err = max(rel_err(g[K.MID_EDGE_FEATURES][b], o[f"mid_edge_features_{b}"]) for b in range(blocks))
+            print(f"threebody_moments={moments}: E {e_err:.2e} F {f_err:.2e} S {s_err:.2e} mid_edge_features {m_err:.2e}")
+            assert e_err < 1e-5, moments
+            assert f_err < 1e-4, moments
+            assert s_err < 1e-4, moments
+            assert m_err < 1e-4, moments
+    finally:
+        model.engine.set_option("threebody_moments", 1)
+    a, b = out[1], out[0]
+    if l_max <= 3:
+        m_d, f_d, s_d = (rel_err(a[k], b[k]) for k in (K.MID_EDGE_FEATURES, K.FORCES, K.STRESSES))
+        e_d = float(((a[K.TOTAL_ENERGY] - b[K.TOTAL_ENERGY]).abs() / b[K.TOTAL_ENERGY].abs()).max())
+        print(f"moment vs list: mid_edge_features {m_d:.2e} F {f_d:.2e} S {s_d:.2e} E {e_d:.2e}")
+        assert not torch.equal(a[K.MID_EDGE_FEATURES], b[K.MID_EDGE_FEATURES]), "the moment path did not run"
+        assert m_d < 5e-6
+        assert f_d < 1e-5
+        assert s_d < 1e-5
+        assert e_d < 2e-6
 
 
 @pytest.mark.parametrize("batched", [False, True])

@@ -295,8 +295,8 @@ __device__ __forceinline__ int64_t lower_bound(const T* a, int64_t n, K key, Key
 #define M3G_DISPATCH_LR3(L_, R_, BODY) \
   switch ((L_) * 8 + (R_)) { M3G_LR_ROW(1, BODY) M3G_LR_ROW(2, BODY) M3G_LR_ROW(3, BODY) default: break; }
 
-constexpr int kTbRows = 128;
-constexpr int kTbCap = 255;   // staged three-body window: the rows of the workgroup + the other rows of the centres they belong to;
+constexpr int kTbRows = 128;  // active edge rows per three-body workgroup (m3g_threebody.hip; windows precomputed in the topology)
+constexpr int kTbCap = 255;  // staged three-body window: the rows of the workgroup + the other rows of the centres they belong to;
                                      // < 256 so a window-relative partner id fits a byte (rows beyond it are read from global memory)
 // staged partner ids per row and list (one byte each; longer lists continue from global memory).  Two instantiations of the
 // three-body kernels: the short lists of the usual 3-body cutoff (r_3 = 4 A: ~17 partners per active edge) and the long ones of
@@ -304,10 +304,17 @@ constexpr int kTbCap = 255;   // staged three-body window: the rows of the workg
 // ids per row takes the dense case from 61 to 24 us (forward) and 137 to 86 us (reverse) per launch, but costs the 10k-atom
 // Cu cell 25 % of its three-body reverse (LDS footprint -> fewer resident workgroups), hence the choice per launch.
 constexpr int kTbListShort = 32, kTbListLong = 96;
-constexpr int kTopoFlags = 16;     // Topo::flags words
-constexpr int kTbFastAtoms = 64;   // most centre atoms per workgroup window the moment path keeps sums for (more: the list path)
 constexpr int kTbCapShort = kTbRows + 64 < kTbCap ? kTbRows + 64 : kTbCap;   // window rows the short-list instantiation stages
-   // active edge rows per three-body workgroup (m3g_threebody.hip; windows precomputed in the topology)
+constexpr int kTbFastAtoms = 64;   // most centre atoms per workgroup window the moment path keeps sums for (more: the list path)
+static_assert(kTbCap <= 255 && kTbFastAtoms <= 255, "topo_hints_word packs the largest window (rows, atoms) in 8 bits each");
+// The window record of one three-body workgroup (Topo::tb_win): the compacted-row window [lo, hi) it stages in LDS, then the ranges
+// of its rows' partner lists in t1_e2c and in t2_e1c.  Word w of block b is tb_win[tb_win_at(b, w)]; the buffer holds a record
+// for every block index a grid can reach plus one.
+enum TbWinWord : int { kTbWinLo, kTbWinHi, kTbWinT1Lo, kTbWinT1Hi, kTbWinT2Lo, kTbWinT2Hi, kTbWinWords };
+template <class I>
+constexpr I tb_win_at(I blk, int word) { return kTbWinWords * blk + word; }
+constexpr int64_t tb_win_blocks(int64_t E) { return E / kTbRows + 1; }   // block indices with a window record
+constexpr int kTopoFlags = 16;     // Topo::flags words
 struct Topo {
   int64_t N, E, T, S;
   int32_t* src;      // [E] centre of each edge
@@ -335,8 +342,7 @@ struct Topo {
   uint8_t* t1_b;       // [T] the same partners as byte-sized ids relative to the LDS window of the row's workgroup
   uint8_t* t2_b;       //     (255: outside the staged window -> the kernels fall back to the int32 list)
   int32_t* act_dst;    // [A] neighbour atom of each active edge (saves a dependent load when staging)
-  int32_t* tb_win;     // [6 * blocks] per three-body workgroup: compacted-row window [lo, hi) staged in LDS, then the
-                       // ranges [t_lo, t_hi) of its rows' partner lists in t1_e2c and in t2_e1c
+  int32_t* tb_win;     // [kTbWinWords * blocks] the window record of each three-body workgroup (TbWinWord)
   int32_t* tb_fast;    // [2 * blocks] per three-body workgroup: {number of centre atoms spanned by its window, first of them} when every
                        // one of those atoms has COMPLETE partner lists (each active edge paired with every other active edge of its
                        // centre exactly once, in both roles) and there are at most kTbFastAtoms of them -- the workgroup may then use

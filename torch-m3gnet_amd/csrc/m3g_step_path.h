@@ -31,6 +31,15 @@ constexpr int64_t kFusedSumsMaxAtoms = 1024;   // (2,000 atoms: readout + sums 2
 // boundary does once for everybody.
 constexpr int64_t kNodeTbFusedMaxAtoms = 128;
 
+// The topology hints word (m3g_io.topo_hints; described in include/m3gnet_hip.h): M3G_TOPO_TB_COMPLETE, then the largest window the
+// moment kernels will meet, one byte each -- rows in bits 8-15, centre atoms in bits 16-23.  Formed from the certificate's
+// statistics (windows that may not use the moment path, largest window in rows and in atoms); 0 = no certificate.
+constexpr int32_t topo_hints_word(int32_t bad, int32_t rows, int32_t atoms) {
+  return (bad == 0 && rows > 0) ? (M3G_TOPO_TB_COMPLETE | ((rows & 0xff) << 8) | ((atoms & 0xff) << 16)) : 0;
+}
+constexpr int topo_hints_rows(int hints) { return (hints >> 8) & 0xff; }
+constexpr int topo_hints_atoms(int hints) { return (hints >> 16) & 0xff; }
+
 // ---- plan options (m3g_plan_set_option), all plain ints: their bytes are part of the captured-graph key ----
 struct Options {
   int precision = kPrecF32;      // option "precision" (default: exact fp32 MFMA products = the reference's arithmetic; 1 / 2 = the split modes, opt-in)
@@ -135,8 +144,8 @@ inline StepPath resolve_step_path(const Options& o, const ModelDims& m, int64_t 
   // the moment kernels apply when the topology build found every window complete (hint bit, read back by the caller once per
   // topology: m3g_topology_hints) and l_max <= 3 (their instantiations); no triplets: no three-body launch at all
   p.tb_hints = o.tb_moments && !o.legendre_ref ? topo_hints : 0;
-  p.moments = (p.tb_hints & M3G_TOPO_TB_COMPLETE) && m.L >= 1 && m.L <= 3 && m.R >= 1 && m.R <= 4 && ((p.tb_hints >> 8) & 0xff) > 0 &&
-              ((p.tb_hints >> 16) & 0xff) > 0;
+  p.moments = (p.tb_hints & M3G_TOPO_TB_COMPLETE) && m.L >= 1 && m.L <= 3 && m.R >= 1 && m.R <= 4 && topo_hints_rows(p.tb_hints) > 0 &&
+              topo_hints_atoms(p.tb_hints) > 0;
   // Long partner lists?  Triplets per edge is a host-side lower bound of triplets per ACTIVE edge (the number of active edges
   // lives on the device); either choice is correct, the wrong one only costs time (global-memory fallback or LDS footprint).
   p.long_lists = T > 24 * E;

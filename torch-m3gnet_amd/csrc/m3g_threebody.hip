@@ -65,6 +65,39 @@ __device__ __forceinline__ float group_sum(float x) {
 // row) 24 / 86 us per launch at 1, 20 / 53 at 2, 19 / 50 at 4, 23 / 70 at 8
 constexpr int kTbLprShort = 2, kTbLprLong = 4;
 
+// ---- what the list kernels and the moment path share (Args: TbRevArgs or TbMomArgs) -----------------------------------------------
+// the window record of row block blk (m3g_internal.h: TbWinWord); a kernel loads only the words it uses
+struct TbWindow { int lo, hi, t1_lo, t1_hi, t2_lo, t2_hi; };
+__device__ __forceinline__ TbWindow load_window(const int32_t* win, int blk) {
+  return TbWindow{win[tb_win_at(blk, kTbWinLo)],   win[tb_win_at(blk, kTbWinHi)],   win[tb_win_at(blk, kTbWinT1Lo)],
+                  win[tb_win_at(blk, kTbWinT1Hi)], win[tb_win_at(blk, kTbWinT2Lo)], win[tb_win_at(blk, kTbWinT2Hi)]};
+}
+// reverse: compact row rr's own data, requested before the barrier -- the geometry gradients so far (zero in the step's first
+// reverse launch), then its dm, q, q' rows and the v row of its neighbour atom kd
+template <int C, class Args>
+__device__ __forceinline__ void load_own_row(const Args& a, int rr, int64_t kd, float& dd0, float& du0, float& du1, float& du2, float* dmv,
+                                             float* qv, float* qpv, float* vv) {
+  dd0 = 0.f; du0 = 0.f; du1 = 0.f; du2 = 0.f;
+  if (!a.first) { dd0 = a.dd[rr]; du0 = a.du[(int64_t)rr * 3]; du1 = a.du[(int64_t)rr * 3 + 1]; du2 = a.du[(int64_t)rr * 3 + 2]; }
+  load_row<C>(a.dm + (int64_t)rr * kCP, dmv);
+  load_row<C>(a.q + (int64_t)rr * kCP, qv);
+  load_row<C>(a.qp + (int64_t)rr * kCP, qpv);
+  load_row<C>(a.v + kd * kCP, vv);
+}
+// a C-wide row padded with zeros to kCP, as 16-byte stores
+template <int C>
+__device__ __forceinline__ void store_padded_row(float* row, const float* val) {
+#pragma unroll
+  for (int k = 0; k < kCP; k += 4) {
+    float4 o;
+    o.x = k + 0 < C ? val[k + 0 < C ? k + 0 : 0] : 0.f;
+    o.y = k + 1 < C ? val[k + 1 < C ? k + 1 : 0] : 0.f;
+    o.z = k + 2 < C ? val[k + 2 < C ? k + 2 : 0] : 0.f;
+    o.w = k + 3 < C ? val[k + 3 < C ? k + 3 : 0] : 0.f;
+    *(float4*)(row + k) = o;
+  }
+}
+
 template <int L, int R, int LIST, int CAP, int LPR>
 __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_fwd(Consts c, TbArgs a) {
   constexpr int C = L * R;
@@ -81,8 +114,8 @@ __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_fwd(Consts c, TbArg
   const int A = *a.n_act;
   for (int blk = blockIdx.x; blk * kTbRows < A; blk += gridDim.x) {
   const int rb = blk * kTbRows;
-  const int lo = a.tb_win[6 * blk], hi_full = a.tb_win[6 * blk + 1];
-  const int t_lo = a.tb_win[6 * blk + 2], t_hi = a.tb_win[6 * blk + 3];
+  const TbWindow win = load_window(a.tb_win, blk);
+  const int lo = win.lo, hi_full = win.hi, t_lo = win.t1_lo, t_hi = win.t1_hi;
   // the rows' partner lists are one contiguous range: staged once, coalesced, as window-relative byte ids (precomputed
   // in the topology) -- a global load per triplet inside the loop serialises ~17 L2 round trips per thread
   const int n_list = (t_hi - t_lo) < kTbListCap ? (t_hi - t_lo) : kTbListCap;
@@ -137,18 +170,8 @@ __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_fwd(Consts c, TbArg
     }
   }
 #pragma unroll
-  for (int k = 0; k < C; ++k) acc[k] = group_sum<LPR>(acc[k]);
-  if (live && sub == 0) {
-#pragma unroll
-    for (int k = 0; k < kCP; k += 4) {
-      float4 o;
-      o.x = k + 0 < C ? fc * acc[k + 0 < C ? k + 0 : 0] : 0.f;
-      o.y = k + 1 < C ? fc * acc[k + 1 < C ? k + 1 : 0] : 0.f;
-      o.z = k + 2 < C ? fc * acc[k + 2 < C ? k + 2 : 0] : 0.f;
-      o.w = k + 3 < C ? fc * acc[k + 3 < C ? k + 3 : 0] : 0.f;
-      *(float4*)(a.m + (int64_t)r * kCP + k) = o;
-    }
-  }
+  for (int k = 0; k < C; ++k) acc[k] = fc * group_sum<LPR>(acc[k]);
+  if (live && sub == 0) store_padded_row<C>(a.m + (int64_t)r * kCP, acc);
   __syncthreads();   // the staged window is rewritten by the next row block
   }
 }
@@ -180,9 +203,8 @@ __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_rev(Consts c, TbRev
   const int A = *a.n_act;
   for (int blk = blockIdx.x; blk * kTbRows < A; blk += gridDim.x) {   // fixed grid walking the row blocks (see k_threebody_fwd)
   const int rb = blk * kTbRows;
-  const int lo = a.tb_win[6 * blk], hi_full = a.tb_win[6 * blk + 1];
-  const int t1_lo = a.tb_win[6 * blk + 2], t1_hi = a.tb_win[6 * blk + 3];
-  const int t2_lo = a.tb_win[6 * blk + 4], t2_hi = a.tb_win[6 * blk + 5];
+  const TbWindow win = load_window(a.tb_win, blk);
+  const int lo = win.lo, hi_full = win.hi, t1_lo = win.t1_lo, t1_hi = win.t1_hi, t2_lo = win.t2_lo, t2_hi = win.t2_hi;
   const int sub = threadIdx.x % LPR;
   const int r = rb + (int)threadIdx.x / LPR;
   const bool live = r < A;
@@ -214,13 +236,8 @@ __global__ void __launch_bounds__(kTbRows * LPR) k_threebody_rev(Consts c, TbRev
   const int t10 = a.t1_ptr[e], t11 = a.t1_ptr[e + 1], t20 = a.t2_ptr[e], t21 = a.t2_ptr[e + 1];
   const float ux = a.u[e * 3], uy = a.u[e * 3 + 1], uz = a.u[e * 3 + 2];
   const float fc = a.fc3[e], fcp = a.fc3p[e];
-  float dd0 = 0.f, du0 = 0.f, du1 = 0.f, du2 = 0.f;
-  if (!a.first) { dd0 = a.dd[rr]; du0 = a.du[(int64_t)rr * 3]; du1 = a.du[(int64_t)rr * 3 + 1]; du2 = a.du[(int64_t)rr * 3 + 2]; }
-  float dmv[C], gv[C], qv[C], qpv[C], vv[C];
-  load_row<C>(a.dm + (int64_t)rr * kCP, dmv);
-  load_row<C>(a.q + (int64_t)rr * kCP, qv);
-  load_row<C>(a.qp + (int64_t)rr * kCP, qpv);
-  load_row<C>(a.v + kd * kCP, vv);
+  float dd0, du0, du1, du2, dmv[C], gv[C], qv[C], qpv[C], vv[C];
+  load_own_row<C>(a, rr, kd, dd0, du0, du1, du2, dmv, qv, qpv, vv);
 #pragma unroll
   for (int k = 0; k < C; ++k) gv[k] = qv[k] * vv[k];
   __syncthreads();
@@ -443,7 +460,8 @@ __device__ __forceinline__ void tb_moments_body(const Consts& c, const TbMomArgs
   // index the grid can reach -- so nothing here waits for A: one dependent load less in a kernel that is a chain of them)
   for (int blk = vblock; blk < a.blocks; blk += vgrid) {
     const int rb = blk * kTbRows;
-    const int lo = a.tb_win[6 * blk], n = a.tb_win[6 * blk + 1] - lo;
+    const TbWindow win = load_window(a.tb_win, blk);
+    const int lo = win.lo, n = win.hi - lo;
     if (n <= 0) break;   // windows are in row order: the first empty one ends the list
     const int A = lo + n;   // rows of this block are < lo + n (the window covers them), rows >= A of the last block are not
     const int na = a.tb_fast[2 * blk], a0 = a.tb_fast[2 * blk + 1];   // (the launch is only made for graphs whose every window
@@ -484,11 +502,7 @@ __device__ __forceinline__ void tb_moments_body(const Consts& c, const TbMomArgs
     float dmv[C], qv[C], qpv[C], vv[C];
     if constexpr (REV) {
       fcp = a.fc3p[e];
-      if (!a.first) { dd0 = a.dd[rr]; du0 = a.du[(int64_t)rr * 3]; du1 = a.du[(int64_t)rr * 3 + 1]; du2 = a.du[(int64_t)rr * 3 + 2]; }
-      load_row<C>(a.dm + (int64_t)rr * kCP, dmv);
-      load_row<C>(a.q + (int64_t)rr * kCP, qv);
-      load_row<C>(a.qp + (int64_t)rr * kCP, qpv);
-      load_row<C>(a.v + kd * kCP, vv);
+      load_own_row<C>(a, rr, kd, dd0, du0, du1, du2, dmv, qv, qpv, vv);
     }
     __syncthreads();
     window_moments<L, R, kThreads>(na, s_arow, su, sg, s_mom);
@@ -499,9 +513,7 @@ __device__ __forceinline__ void tb_moments_body(const Consts& c, const TbMomArgs
       const float ux = su[own * 4 + 1], uy = su[own * 4 + 2], uz = su[own * 4 + 3], s2 = ux * ux + uy * uy + uz * uz;
       const float* g = sg + own * C;
       if constexpr (!REV) {
-        float acc[kCP];
-#pragma unroll
-        for (int k = 0; k < kCP; ++k) acc[k] = 0.f;
+        float acc[C];
 #pragma unroll
         for (int nn = 0; nn < R; ++nn) {
           const MomEval ev = mom_eval<L>(s_mom + (at * R + nn) * NM, ux, uy, uz, s2, g[nn], L >= 2 ? g[R + nn] : 0.f, L >= 3 ? g[2 * R + nn] : 0.f);
@@ -509,8 +521,7 @@ __device__ __forceinline__ void tb_moments_body(const Consts& c, const TbMomArgs
           if constexpr (L >= 2) acc[R + nn] = fc * c.ynorm[1] * ev.S1;
           if constexpr (L >= 3) acc[2 * R + nn] = fc * c.ynorm[2] * ev.S2;
         }
-#pragma unroll
-        for (int k = 0; k < kCP; k += 4) *(float4*)(a.m + (int64_t)r * kCP + k) = float4{acc[k], acc[k + 1], acc[k + 2], acc[k + 3]};
+        store_padded_row<C>(a.m + (int64_t)r * kCP, acc);
       } else {
         const float* ds = ss + own * C;   // fc dm of this row
         float dg[kCP], dfc = 0.f, ax = 0.f, ay = 0.f, az = 0.f;
@@ -643,55 +654,92 @@ static inline dim3 grid_rows(int64_t n) {
   const int64_t blocks = (n + kTbRows - 1) / kTbRows;
   return dim3((unsigned)(blocks < kTbGridCap ? blocks : kTbGridCap));
 }
-// (StepPath::moments: L, R outside M3G_DISPATCH_LR3's cases take the list kernels)
-// arguments of the moment kernels: forward (m = the aggregate to form) or reverse (m = nullptr: the gradient arrays of the workspace)
-static TbMomArgs tb_mom_args(const Topo& t, const Work& w, const float* v, int topo_hints, float* m, bool first) {
-  if (m) return TbMomArgs{(int)(t.E / kTbRows + 1), t.src, t.arow_ptr, t.tb_fast, t.act_list, t.act_dst, t.tb_win, t.n_act, t.flags, topo_hints, w.u, w.fc3, nullptr, w.q, nullptr, v, nullptr, m, nullptr, nullptr, nullptr, 0};
-  return TbMomArgs{(int)(t.E / kTbRows + 1), t.src, t.arow_ptr, t.tb_fast, t.act_list, t.act_dst, t.tb_win, t.n_act, t.flags, topo_hints, w.u, w.fc3, w.fc3p, w.q, w.qp, v, w.dm, nullptr, w.dd, w.du, w.dg, first ? 1 : 0};
+// the fields every three-body argument block sets the same way (A: TbArgs, TbRevArgs or TbMomArgs) ...
+template <class A>
+static A tb_args(const Topo& t, const Work& w, const float* v) {
+  A a{};
+  a.act_list = t.act_list; a.act_dst = t.act_dst; a.tb_win = t.tb_win; a.n_act = t.n_act;
+  a.u = w.u; a.fc3 = w.fc3; a.q = w.q; a.v = v;
+  return a;
 }
+// ... and the reverse ones (TbRevArgs, TbMomArgs): inputs, then the gradient arrays of the workspace
+template <class A>
+static void tb_reverse_fields(A& a, const Work& w, bool first) {
+  a.fc3p = w.fc3p; a.qp = w.qp; a.dm = w.dm;
+  a.dd = w.dd; a.du = w.du; a.dgq = w.dg; a.first = first ? 1 : 0;
+}
+// (StepPath::moments: L, R outside M3G_DISPATCH_LR3's cases take the list kernels)
+// arguments of the moment kernels: forward (m = the aggregate to form) or reverse (m = nullptr)
+static TbMomArgs tb_mom_args(const Topo& t, const Work& w, const float* v, int topo_hints, float* m, bool first) {
+  TbMomArgs a = tb_args<TbMomArgs>(t, w, v);
+  a.blocks = (int)tb_win_blocks(t.E);
+  a.src = t.src; a.arow_ptr = t.arow_ptr; a.tb_fast = t.tb_fast; a.flags = t.flags; a.hints = topo_hints;
+  a.m = m;
+  if (!m) tb_reverse_fields(a, w, first);
+  return a;
+}
+// window sizes of a moment launch, from the certified hints word, and the LDS they take
+struct MomDims { int rows, atoms; size_t lds; };
+template <int L, int R, bool REV>
+static MomDims mom_dims(int hints) {
+  return MomDims{topo_hints_rows(hints), topo_hints_atoms(hints), mom_lds_bytes<L, R, REV>(topo_hints_rows(hints), topo_hints_atoms(hints))};
+}
+// one launch of a stand-alone moment kernel: k_threebody_moments<L, R, REV> or (FINAL) k_threebody_moments_final<L, R>
+template <int L, int R, bool REV, bool FINAL>
+static void launch_moments_lr(const Consts& c, const TbMomArgs& a, int64_t E, hipStream_t s) {
+  const MomDims d = mom_dims<L, R, REV>(a.hints);
+  auto kernel = k_threebody_moments<L, R, REV>;
+  if constexpr (FINAL) kernel = k_threebody_moments_final<L, R>;
+  hipLaunchKernelGGL(kernel, grid_rows(E), dim3(kTbMomThreads), d.lds, s, c, a, d.rows, d.atoms);
+}
+template <bool REV, bool FINAL = false>
+static void launch_moments(const Consts& c, const TbMomArgs& a, int64_t E, hipStream_t s) {
+  M3G_DISPATCH_LR3(c.L, c.R, (launch_moments_lr<L, R, REV, FINAL>(c, a, E, s)));
+}
+// the two instantiations of the list kernels (m3g_internal.h: kTbListShort / kTbListLong), chosen per launch by StepPath::long_lists
+struct TbShortLists { static constexpr int LIST = kTbListShort, CAP = kTbCapShort, LPR = kTbLprShort; };
+struct TbLongLists { static constexpr int LIST = kTbListLong, CAP = kTbCap, LPR = kTbLprLong; };
+#define M3G_TB_LIST_LAUNCH(KERNEL, V, c, a, s) \
+  M3G_DISPATCH_LR((c).L, (c).R, hipLaunchKernelGGL((KERNEL<L, R, V::LIST, V::CAP, V::LPR>), grid_rows((a).E), dim3(kTbRows * V::LPR), 0, s, c, a))
+#define M3G_TB_LIST_DISPATCH(KERNEL, long_lists, c, a, s) \
+  if (long_lists) { M3G_TB_LIST_LAUNCH(KERNEL, TbLongLists, c, a, s); } else { M3G_TB_LIST_LAUNCH(KERNEL, TbShortLists, c, a, s); }
 
 void launch_threebody(const StepPath& p, const Consts& c, const Topo& t, const Work& w, const float* v, float* m, hipStream_t s) {
   if (t.E == 0) return;
   if (t.T == 0) return;   // no active edge: every consumer reads zeros through act_id < 0
-  const int topo_hints = p.tb_hints;
-  if (p.moments) {
-    const TbMomArgs a = tb_mom_args(t, w, v, topo_hints, m, false);
-    const int rows = (topo_hints >> 8) & 0xff, atoms = (topo_hints >> 16) & 0xff;
-    M3G_DISPATCH_LR3(c.L, c.R, hipLaunchKernelGGL((k_threebody_moments<L, R, false>), grid_rows(t.E), dim3(kTbMomThreads), (mom_lds_bytes<L, R, false>(rows, atoms)), s, c, a, rows, atoms));
-    return;
-  }
-  TbArgs a{t.E, t.act_list, t.act_dst, t.tb_win, t.n_act, t.t1_ptr, t.t1_e2c, t.t1_b, w.u, w.fc3, w.q, v, m};
-  if (p.long_lists) { M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_threebody_fwd<L, R, kTbListLong, kTbCap, kTbLprLong>), grid_rows(t.E), dim3(kTbRows * kTbLprLong), 0, s, c, a)); }
-  else { M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_threebody_fwd<L, R, kTbListShort, kTbCapShort, kTbLprShort>), grid_rows(t.E), dim3(kTbRows * kTbLprShort), 0, s, c, a)); }
+  if (p.moments) return launch_moments<false>(c, tb_mom_args(t, w, v, p.tb_hints, m, false), t.E, s);
+  TbArgs a = tb_args<TbArgs>(t, w, v);
+  a.E = t.E; a.t_ptr = t.t1_ptr; a.t_other = t.t1_e2c; a.t_bytes = t.t1_b; a.m = m;
+  M3G_TB_LIST_DISPATCH(k_threebody_fwd, p.long_lists, c, a, s);
 }
 
 // The in-launch wait of k_node_tb_reverse is deadlock-free only when all workgroups of the launch are resident together: ask the
 // runtime how many this kernel fits per CU at this LDS footprint (cached per instantiation, device and footprint); false = take the
 // two launches.
 template <int L, int R>
-static bool node_tb_launch(const Consts& c, const TbMomArgs& a, int rows, int atoms, const NodeRevArgs& na, int n_tb, int n_node, int32_t* done,
-                           int debug_polls, hipStream_t s) {
-  const size_t lds = mom_lds_bytes<L, R, true>(rows, atoms);
+static bool node_tb_launch(const Consts& c, const TbMomArgs& a, const NodeRevArgs& na, int n_tb, int n_node, int32_t* done, int debug_polls,
+                           hipStream_t s) {
+  const MomDims d = mom_dims<L, R, true>(a.hints);
   static std::mutex mu;
   static std::map<std::pair<int, size_t>, int> resident;   // (device, dynamic LDS bytes) -> workgroups the device holds at once
   int dev = 0, cap = 0;
   if (hipGetDevice(&dev) != hipSuccess) return false;
   {
     std::lock_guard<std::mutex> lock(mu);
-    auto it = resident.find(std::make_pair(dev, lds));
+    auto it = resident.find(std::make_pair(dev, d.lds));
     if (it == resident.end()) {
       int per_cu = 0, cus = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_node_tb_reverse<L, R>, 256, lds) != hipSuccess ||
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_node_tb_reverse<L, R>, 256, d.lds) != hipSuccess ||
           hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         per_cu = cus = 0;
-      it = resident.emplace(std::make_pair(dev, lds), per_cu * cus).first;
+      it = resident.emplace(std::make_pair(dev, d.lds), per_cu * cus).first;
     }
     cap = it->second;
   }
   if (n_tb + n_node > cap) return false;
   // (debug_polls, tests only: k > 0 bounds the wait at k polls; k < 0 makes the node role wait for an increment that never comes, |k| polls)
   const NodeTbArgs f{n_tb, done, debug_polls > 0 ? debug_polls : debug_polls < 0 ? -debug_polls : 1 << 22, debug_polls < 0 ? 1 : 0};
-  hipLaunchKernelGGL((k_node_tb_reverse<L, R>), dim3((unsigned)(n_tb + n_node)), dim3(256), lds, s, c, a, rows, atoms, na, f);
+  hipLaunchKernelGGL((k_node_tb_reverse<L, R>), dim3((unsigned)(n_tb + n_node)), dim3(256), d.lds, s, c, a, d.rows, d.atoms, na, f);
   return true;
 }
 
@@ -700,14 +748,13 @@ static bool node_tb_launch(const Consts& c, const TbMomArgs& a, int rows, int at
 bool launch_node_tb_reverse(const Consts& c, const float* W, const BlockW& bw, const Topo& t, const Work& w, const float* v, bool first,
                             const float* dx_new, float* dx_out, int dp1_packed, int block, hipStream_t s, int topo_hints, int debug_polls) {
   const TbMomArgs a = tb_mom_args(t, w, v, topo_hints, nullptr, first);
-  const int rows = (topo_hints >> 8) & 0xff, atoms = (topo_hints >> 16) & 0xff;
   const NodeRevArgs na = node_rev_args(c, W, bw, t, w, v, dx_new, dx_out, /*row_sums_in_seg=*/true, dp1_packed, /*with_v_term=*/true);
   // the three-body role walks its row blocks with at most 128 workgroups: each publishes once, and a publish is a write-back of
   // its XCD's L2 (one per row block -- 284 on the 864-atom cell -- cost 59 us instead of the 24 us of the two separate kernels);
   // beside the node role's gather a longer walk costs nothing
   const int n_tb = (int)std::min<unsigned>(grid_rows(t.E).x, 128u), n_node = (int)((t.N + kNodesRev - 1) / kNodesRev);
   bool launched = false;
-  M3G_DISPATCH_LR3(c.L, c.R, launched = (node_tb_launch<L, R>(c, a, rows, atoms, na, n_tb, n_node, w.sync + kSyncNodeRev + block, debug_polls, s)));
+  M3G_DISPATCH_LR3(c.L, c.R, launched = (node_tb_launch<L, R>(c, a, na, n_tb, n_node, w.sync + kSyncNodeRev + block, debug_polls, s)));
   return launched;
 }
 
@@ -717,26 +764,20 @@ void launch_threebody_reverse_final(const Consts& c, const Topo& t, const Work& 
   TbMomArgs a = tb_mom_args(t, w, v, topo_hints, nullptr, first);
   a.geom = GeomRev{t.E, w.u, w.d, w.hp, dh, dh_parts, w.dd, w.du, t.act_id};
   a.dr = w.dr;
-  const int rows = (topo_hints >> 8) & 0xff, atoms = (topo_hints >> 16) & 0xff;
-  M3G_DISPATCH_LR3(c.L, c.R, hipLaunchKernelGGL((k_threebody_moments_final<L, R>), grid_rows(t.E), dim3(kTbMomThreads), (mom_lds_bytes<L, R, true>(rows, atoms)), s, c, a, rows, atoms));
+  launch_moments<true, true>(c, a, t.E, s);
 }
 
 void launch_threebody_reverse(const StepPath& p, const Consts& c, const Topo& t, const Work& w, const float* v, bool first, hipStream_t s,
                               bool ref_legendre) {
   if (t.E == 0) return;
   if (t.T == 0) return;
-  const int topo_hints = p.tb_hints;
-  if (p.moments) {
-    const TbMomArgs a = tb_mom_args(t, w, v, topo_hints, nullptr, first);
-    const int rows = (topo_hints >> 8) & 0xff, atoms = (topo_hints >> 16) & 0xff;
-    M3G_DISPATCH_LR3(c.L, c.R, hipLaunchKernelGGL((k_threebody_moments<L, R, true>), grid_rows(t.E), dim3(kTbMomThreads), (mom_lds_bytes<L, R, true>(rows, atoms)), s, c, a, rows, atoms));
-    return;
-  }
-  TbRevArgs a{t.E, t.act_list, t.act_dst, t.tb_win, t.n_act, t.t1_ptr, t.t1_e2c, t.t2_ptr, t.t2_e1c, t.t1_b, t.t2_b, w.u, w.fc3, w.fc3p, w.q,
-              w.qp, v,
-              w.dm, w.dd, w.du, w.dg, first ? 1 : 0, ref_legendre ? 1 : 0};
-  if (p.long_lists) { M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_threebody_rev<L, R, kTbListLong, kTbCap, kTbLprLong>), grid_rows(t.E), dim3(kTbRows * kTbLprLong), 0, s, c, a)); }
-  else { M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_threebody_rev<L, R, kTbListShort, kTbCapShort, kTbLprShort>), grid_rows(t.E), dim3(kTbRows * kTbLprShort), 0, s, c, a)); }
+  if (p.moments) return launch_moments<true>(c, tb_mom_args(t, w, v, p.tb_hints, nullptr, first), t.E, s);
+  TbRevArgs a = tb_args<TbRevArgs>(t, w, v);
+  tb_reverse_fields(a, w, first);
+  a.E = t.E; a.ref_legendre = ref_legendre ? 1 : 0;
+  a.t1_ptr = t.t1_ptr; a.t1_other = t.t1_e2c; a.t1_bytes = t.t1_b;
+  a.t2_ptr = t.t2_ptr; a.t2_other = t.t2_e1c; a.t2_bytes = t.t2_b;
+  M3G_TB_LIST_DISPATCH(k_threebody_rev, p.long_lists, c, a, s);
 }
 
 }  // namespace m3g

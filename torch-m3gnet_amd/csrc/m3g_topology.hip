@@ -41,8 +41,8 @@ Topo topo_carve(int64_t N, int64_t E, int64_t T, int64_t S, void* base) {
   t.act_id = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
   t.arow_ptr = (int32_t*)c.take(sizeof(int32_t) * (N + 2));
   t.act_dst = (int32_t*)c.take(sizeof(int32_t) * (E + 1));
-  t.tb_win = (int32_t*)c.take(sizeof(int32_t) * 6 * (E / kTbRows + 2));
-  t.tb_fast = (int32_t*)c.take(sizeof(int32_t) * 2 * (E / kTbRows + 2));
+  t.tb_win = (int32_t*)c.take(sizeof(int32_t) * kTbWinWords * (tb_win_blocks(E) + 1));
+  t.tb_fast = (int32_t*)c.take(sizeof(int32_t) * 2 * (tb_win_blocks(E) + 1));
   t.t1_e2c = (int32_t*)c.take(sizeof(int32_t) * (T + 1));
   t.t2_e1c = (int32_t*)c.take(sizeof(int32_t) * (T + 1));
   t.t1_b = (uint8_t*)c.take((size_t)T + 16);
@@ -108,7 +108,7 @@ __device__ __forceinline__ void pair_with_lookup(int64_t n, int64_t i, const int
 // [lo, lo + n); the compacted partner is stored relative to lo, 255 when it falls outside
 __device__ __forceinline__ uint8_t partner_byte(int r, const int32_t* win, int partner_c) {
   const int blk = (r < 0 ? 0 : r) / kTbRows;
-  const int wlo = win[6 * blk], whi = win[6 * blk + 1];
+  const int wlo = win[tb_win_at(blk, kTbWinLo)], whi = win[tb_win_at(blk, kTbWinHi)];
   const int n = (whi - wlo) < kTbCap ? (whi - wlo) : kTbCap;
   const int d = partner_c - wlo;
   return (uint8_t)((r >= 0 && d >= 0 && d < n && d < 255) ? d : 255);
@@ -119,7 +119,7 @@ __device__ __forceinline__ uint8_t partner_byte(int r, const int32_t* win, int p
 // raises), but it must not be dereferenced -- act_list[hi - 1] would index padding: it reads as empty, lo = hi = na = a0 = 0.
 __device__ __forceinline__ bool tb_window_fits(int A, int64_t b, const int32_t* win, const int32_t* act_list,
                                                const int32_t* src, int& lo, int& hi, int& na, int& a0) {
-  lo = win[6 * b]; hi = win[6 * b + 1];
+  lo = win[tb_win_at(b, kTbWinLo)]; hi = win[tb_win_at(b, kTbWinHi)];
   if (lo < 0 || hi <= lo || hi > A) { lo = 0; hi = 0; na = 0; a0 = 0; return false; }
   a0 = src[act_list[lo]];
   na = src[act_list[hi - 1]] - a0 + 1;
@@ -137,11 +137,6 @@ __device__ __forceinline__ bool tb_stats_reduce(int& bad, int& rows, int& atoms)
   bad = 0; rows = 0; atoms = 0;
   for (int k = 0; k < (int)(blockDim.x >> 6); ++k) { bad += s_bad[k]; rows = max(rows, s_rows[k]); atoms = max(atoms, s_atoms[k]); }
   return true;
-}
-// the certificate's word from its statistics; the window sizes travel in one byte each
-__host__ __device__ inline int32_t hints_word(int32_t bad, int32_t rows, int32_t atoms) {
-  static_assert(kTbCap <= 255 && kTbFastAtoms <= 255, "m3g_topology_hints packs the largest window (rows, atoms) in 8 bits each");
-  return (bad == 0 && rows > 0) ? (M3G_TOPO_TB_COMPLETE | ((rows & 0xff) << 8) | ((atoms & 0xff) << 16)) : 0;
 }
 
 __global__ void k_convert_edges(int64_t N, int64_t E, const int64_t* __restrict__ ei, int32_t* src, int32_t* dst,
@@ -288,16 +283,16 @@ __global__ void k_tb_windows(int64_t blocks, const int32_t* __restrict__ n_act, 
   if (b >= blocks) return;
   const int A = *n_act;
   const int64_t rb = b * kTbRows;
-  int w[6] = {0, 0, 0, 0, 0, 0};
+  int w[kTbWinWords] = {};
   if (rb < A) {
     const int64_t rlast = rb + kTbRows - 1 < A ? rb + kTbRows - 1 : A - 1;
     const int ef = act_list[rb], el = act_list[rlast];
-    w[0] = arow_ptr[src[ef]];
-    w[1] = arow_ptr[src[el] + 1];
-    w[2] = t1_ptr[ef]; w[3] = t1_ptr[el + 1];
-    w[4] = t2_ptr[ef]; w[5] = t2_ptr[el + 1];
+    w[kTbWinLo] = arow_ptr[src[ef]];
+    w[kTbWinHi] = arow_ptr[src[el] + 1];
+    w[kTbWinT1Lo] = t1_ptr[ef]; w[kTbWinT1Hi] = t1_ptr[el + 1];
+    w[kTbWinT2Lo] = t2_ptr[ef]; w[kTbWinT2Hi] = t2_ptr[el + 1];
   }
-  for (int k = 0; k < 6; ++k) win[6 * b + k] = w[k];
+  for (int k = 0; k < kTbWinWords; ++k) win[tb_win_at(b, k)] = w[k];
 }
 // Are the partner lists of compacted row r complete -- every other active edge of its centre exactly once, as first AND as
 // second edge?  (Ascending order inside a row is what the sorted lists have; it makes "exactly once" a local test.)
@@ -353,7 +348,7 @@ __global__ void __launch_bounds__(1024) k_tb_stats(int64_t blocks, const int32_t
   for (int64_t b = threadIdx.x; b < blocks; b += blockDim.x) {
     if (b * kTbRows >= A) continue;
     const int na = fast[2 * b];
-    if (na > 0) { rows = max(rows, win[6 * b + 1] - win[6 * b]); atoms = max(atoms, na); }
+    if (na > 0) { rows = max(rows, win[tb_win_at(b, kTbWinHi)] - win[tb_win_at(b, kTbWinLo)]); atoms = max(atoms, na); }
     else ++bad;
   }
   if (tb_stats_reduce<16>(bad, rows, atoms)) { stats[0] = bad; stats[1] = rows; stats[2] = atoms; }
@@ -583,8 +578,8 @@ __global__ void __launch_bounds__(256) k_canon_active(int64_t N, int64_t E, cons
         act_list[cid] = e;
         act_dst[cid] = dst[e];
         const int b = cid / kTbRows;
-        if (cid % kTbRows == 0) { win[6 * b] = c0; win[6 * b + 2] = ta; win[6 * b + 4] = ta; }
-        if (cid % kTbRows == kTbRows - 1 || cid == A - 1) { win[6 * b + 1] = c1; win[6 * b + 3] = tb; win[6 * b + 5] = tb; }
+        if (cid % kTbRows == 0) { win[tb_win_at(b, kTbWinLo)] = c0; win[tb_win_at(b, kTbWinT1Lo)] = ta; win[tb_win_at(b, kTbWinT2Lo)] = ta; }
+        if (cid % kTbRows == kTbRows - 1 || cid == A - 1) { win[tb_win_at(b, kTbWinHi)] = c1; win[tb_win_at(b, kTbWinT1Hi)] = tb; win[tb_win_at(b, kTbWinT2Hi)] = tb; }
       }
     }
     run += __popcll(mask);
@@ -643,7 +638,7 @@ __global__ void __launch_bounds__(256) k_canon_finish(int64_t E, int64_t T, int6
     stats[0] = bad; stats[1] = rows; stats[2] = atoms;
     // the certificate's word stays with the buffer (flags[7] = stats[3]; the host forms the same word from the verdict with the same
     // function): every check has passed when this line is reached, so no launch is needed after the host has read the verdict
-    stats[3] = hints_word(bad, rows, atoms);
+    stats[3] = topo_hints_word(bad, rows, atoms);
   }
 }
 
@@ -682,9 +677,9 @@ static bool launch_hint_kernels(const Topo& t, hipStream_t s, bool trusted = fal
   if (!trusted)
     hipLaunchKernelGGL(k_tb_row_complete, grid(E), dim3(TPB), 0, s, t.n_act, t.act_list, t.src, t.arow_ptr, t.t1_ptr, t.t1_e2c, t.t2_ptr, t.t2_e1c, row_ok,
                        t.flags + 4);
-  hipLaunchKernelGGL(k_tb_fast, grid((E / kTbRows + 1) * 64), dim3(TPB), 0, s, E / kTbRows + 1, t.n_act, t.act_list, t.src, t.tb_win,
+  hipLaunchKernelGGL(k_tb_fast, grid(tb_win_blocks(E) * 64), dim3(TPB), 0, s, tb_win_blocks(E), t.n_act, t.act_list, t.src, t.tb_win,
                      trusted ? (const uint8_t*)nullptr : row_ok, t.tb_fast, t.flags + 4);
-  hipLaunchKernelGGL(k_tb_stats, dim3(1), dim3(1024), 0, s, E / kTbRows + 1, t.n_act, t.tb_win, t.tb_fast, t.flags + 4);
+  hipLaunchKernelGGL(k_tb_stats, dim3(1), dim3(1024), 0, s, tb_win_blocks(E), t.n_act, t.tb_win, t.tb_fast, t.flags + 4);
   return true;
 }
 // host_hints != NULL: also form the certificate of m3g_topology_hints and return its word.  For the lists the graph builders emit
@@ -706,7 +701,7 @@ static int topology_build(int64_t N, int64_t E, int64_t T, int64_t S, const int6
   M3G_HIP_CHECK(hipMemsetAsync(t.flags, 0, kTopoFlags * sizeof(int32_t), s));   // incl. the certified hints word [7] and the sticky error [8]
   // no window may use the three-body moment path until the certificate has been formed for THIS buffer (stale rows of an earlier
   // topology in the same memory must not survive a rebuild)
-  M3G_HIP_CHECK(hipMemsetAsync(t.tb_fast, 0, sizeof(int32_t) * 2 * (E / kTbRows + 2), s));
+  M3G_HIP_CHECK(hipMemsetAsync(t.tb_fast, 0, sizeof(int32_t) * 2 * (tb_win_blocks(E) + 1), s));
 
   size_t m = (size_t)std::max<int64_t>(std::max<int64_t>(E, T), 1);
   char* tmp = (char*)t.sort_tmp;
@@ -747,7 +742,7 @@ static int topology_build(int64_t N, int64_t E, int64_t T, int64_t S, const int6
     M3G_HIP_CHECK(prims::exclusive_scan<int32_t>(t.act_scan, t.act_scan, E + 1, cub_tmp, s));
     hipLaunchKernelGGL(k_active_scatter, grid(std::max(E, N) + 1), dim3(TPB), 0, s, N, E, t.t1_ptr, t.t2_ptr, t.act_scan, t.row_ptr, t.dst, t.act_list,
                        t.act_dst, t.act_id, t.arow_ptr, t.n_act);
-    hipLaunchKernelGGL(k_tb_windows, grid(E / kTbRows + 1), dim3(TPB), 0, s, E / kTbRows + 1, t.n_act, t.act_list, t.src, t.arow_ptr, t.t1_ptr, t.t2_ptr,
+    hipLaunchKernelGGL(k_tb_windows, grid(tb_win_blocks(E)), dim3(TPB), 0, s, tb_win_blocks(E), t.n_act, t.act_list, t.src, t.arow_ptr, t.t1_ptr, t.t2_ptr,
                        t.tb_win);
     if (E > 0) hipLaunchKernelGGL(k_pair_with_lookup, grid(E), dim3(TPB), 0, s, E, t.in_edge, t.act_id, t.in_pair, t.in_pos);
     if (T > 0) {
@@ -792,7 +787,7 @@ static int topology_build(int64_t N, int64_t E, int64_t T, int64_t S, const int6
     const bool assumed_ok = !(h[1] & 3) && !(try_mirrors && (h[0] & 8));
     if (assumed_ok) {
       if (hinted) {
-        *host_hints = hints_word(hs[0], hs[1], hs[2]);
+        *host_hints = topo_hints_word(hs[0], hs[1], hs[2]);
         // the same word stays with the buffer (flags[7]): the moment kernels run only when the word the caller hands to
         // m3g_energy_forces is the one certified for THIS topology buffer
         hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, s, t.flags + 7, *host_hints);
@@ -840,7 +835,7 @@ static int topology_build(int64_t N, int64_t E, int64_t T, int64_t S, const int6
       int r = downstream(symmetric, t1_keys);
       if (r) return r;
       // the optimistic certificate described other lists: none is valid for this buffer until m3g_topology_hints forms it
-      M3G_HIP_CHECK(hipMemsetAsync(t.tb_fast, 0, sizeof(int32_t) * 2 * (E / kTbRows + 2), s));
+      M3G_HIP_CHECK(hipMemsetAsync(t.tb_fast, 0, sizeof(int32_t) * 2 * (tb_win_blocks(E) + 1), s));
       M3G_HIP_CHECK(hipMemsetAsync(t.flags + 4, 0, 4 * sizeof(int32_t), s));
       if (host_hints) {
         M3G_HIP_CHECK(hipGetLastError());
@@ -886,7 +881,7 @@ static int canonical_fast_launch(int64_t N, int64_t E, int64_t T, int64_t S, con
                                  const int64_t* batch, const Topo& t, int32_t* verdict, hipStream_t s) {
   const int TPB = 256;
   auto blocks = [&](int64_t n) { return (n + TPB - 1) / TPB; };
-  const int64_t windows = E / kTbRows + 1, n_win = 6 * windows, n_fast = 2 * (E / kTbRows + 2);
+  const int64_t windows = tb_win_blocks(E), n_win = kTbWinWords * windows, n_fast = 2 * (tb_win_blocks(E) + 1);
   M3G_HIP_CHECK(hipMemsetAsync(t.flags, 0, kTopoFlags * sizeof(int32_t), s));
   const int64_t n1 = std::max(std::max(E, N + 1), std::max(S + 1, n_win));
   hipLaunchKernelGGL(k_canon_edges, dim3((unsigned)blocks(n1)), dim3(TPB), 0, s, N, E, S, edge_index, batch, t.src, t.dst, t.batch, t.row_ptr,
@@ -908,7 +903,7 @@ static int canonical_fast_launch(int64_t N, int64_t E, int64_t T, int64_t S, con
 static int canonical_fast_settle(const Topo& t, const int32_t* verdict, int32_t* host_flags, int32_t* host_hints, hipStream_t s, bool* done) {
   *done = false;
   if ((verdict[0] & 15) || (verdict[1] & 1)) return M3G_OK;   // malformed, not symmetric or not sorted: the general path decides what it is
-  *host_hints = hints_word(verdict[4], verdict[5], verdict[6]);   // (k_canon_finish has left the same word on the buffer, flags[7])
+  *host_hints = topo_hints_word(verdict[4], verdict[5], verdict[6]);   // (k_canon_finish has left the same word on the buffer, flags[7])
   (void)s;
   if (host_flags) host_flags[0] = verdict[0];
   *done = true;
@@ -1000,7 +995,7 @@ extern "C" int m3g_topology_hints(int64_t N, int64_t E, int64_t T, int64_t S, co
   int32_t h[3] = {0, 0, 0};
   M3G_HIP_CHECK(hipMemcpyAsync(h, t.flags + 4, sizeof(h), hipMemcpyDeviceToHost, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
-  *host_hints = hints_word(h[0], h[1], h[2]);
+  *host_hints = topo_hints_word(h[0], h[1], h[2]);
   // the same word stays with the buffer (flags[7]): the moment kernels run only when the word the caller hands to m3g_energy_forces
   // is the one certified for THIS topology buffer -- a stale word, or one copied from another buffer, flags an error instead
   hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, s, t.flags + 7, *host_hints);
