@@ -577,6 +577,66 @@ int m3g_dyn_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t s
  * half-step velocities of the step under way; after a finish_only call the full-step ones. */
 int m3g_dyn_state_view(int64_t n_atoms, int64_t n_structs, size_t* mass_offset, size_t* velocity_offset);
 
+/* ---- batched molecular dynamics, deterministic ensembles: Nose-Hoover chain NVT, isotropic MTK NPT (csrc/m3g_nhc.hip) -----------------
+ * Time-reversible thermostat and barostat with a conserved quantity (Martyna, Tuckerman, Tobias, Klein, Mol. Phys. 87, 1117 (1996);
+ * what ASE's NoseHooverChainNVT and LAMMPS' fix nvt / fix npt iso integrate), for a whole batch, each structure with its own target
+ * temperature.  A family of its own beside m3g_dyn_*: that family's structs, state layout and results do not change.  Units and
+ * constants as m3g_dyn_*; 2 KE = sum m |v|^2 / kappa in eV; thermostat and barostat velocities vxi, veps in 1/fs, their masses in
+ * eV fs^2.  Per structure of n atoms: g = 3 n - 3 with fix_com, else 3 n; kT = k_B T0; particle chain masses Q_1 = g kT taut^2,
+ * Q_k>1 = kT taut^2; barostat chain masses kT taup^2; W = (g + 3) kT taup^2; alpha = 1 + 3 / g.
+ * One step is T(h) B(h) A(dt) [forces] B(h) T(h), h = dt / 2:
+ *   chain half-step chain(Q, xi, vxi, K2, gkT, h) in chain_substeps equal parts d = h / n_c, each:  vxi_M += d/2 G_M;  k = M-1 .. 1:
+ *           vxi_k = (vxi_k e + d/2 G_k) e, e = exp(-d/4 vxi_k+1);  s = exp(-d vxi_1), K2 = s^2 K2;  xi += d vxi;  the vxi updates again
+ *           in ascending order with the new K2;  G_1 = (K2 - gkT) / Q_1, G_k = (Q_k-1 vxi_k-1^2 - kT) / Q_k.  The particle chain takes
+ *           K2 = 2 KE, gkT = g kT and scales every velocity by the product of the s; the barostat chain K2 = W veps^2, gkT = kT, veps;
+ *   T(h)    particle chain, then (NPT) barostat chain, then veps += h G_eps, G_eps = (alpha 2 KE + tr W - 3 V pressure) / W with
+ *           tr W = V (s_0 + s_1 + s_2) of the PAIR-VIRIAL stresses; the closing T(h) of a step runs the three in the opposite order;
+ *   B(h)    NVT v += h a;  NPT v = v exp(-2 y) + h a exp(-y) sinhc(y), y = alpha veps h / 2;  fix_com: v_i -= pbar / m_i after the
+ *           opening kick (pbar = sum_j m_j v_j / n);
+ *   A(dt)   NVT x += dt v;  NPT x = x exp(2 y) + dt v exp(y) sinhc(y), y = veps h, and lattice = exp(2 y) lattice;
+ *           sinhc(y) = sinh(y) / y as its series to y^6 (|y| << 1).
+ * One m3g_nhc_step at the forces F(x_k): the B(h) T(h) that close the step under way, obs[s] = {KE, T = 2 KE / (3 n k_B), P = (tr W +
+ * 2 KE) / (3 V), V, extended, 0} -- T in the 3 n convention of m3g_dyn_*, so its canonical mean is T0 g / (3 n); extended = g kT xi_1
+ * + kT sum_k>1 xi_k + 1/2 sum Q vxi^2, in NPT + pressure V + 1/2 W veps^2 + kT sum xib + 1/2 sum Qb vxib^2: E_pot + KE + extended is
+ * conserved -- then the T(h) B(h) A(dt) that open the next step (not with finish_only, which clears M3G_DYN_STARTED instead).  The
+ * kinetic energy after a uniform scale is known in closed form, so the atoms are passed over once per launch.  Flags are the
+ * M3G_DYN_* bits: a structure whose forces (NPT: or stresses) hold a non-finite value gets M3G_DYN_ERROR and is frozen, bitwise.  No
+ * atomics: every result is bitwise the same alone or in any batch. */
+typedef struct {
+  int32_t ensemble;         /* M3G_NHC_NVT, M3G_NHC_NPT_MTK */
+  int32_t fix_com;          /* 0 / 1: zero the total momentum at every start; g = 3 n - 3 */
+  int32_t chain_length;     /* M: 1 .. M3G_NHC_MAX_CHAIN thermostats per chain (particles, and in NPT the barostat) */
+  int32_t chain_substeps;   /* n_c: 1 .. 8 equal parts of every chain half-step */
+  double dt;                /* fs, > 0 */
+  double taut;              /* fs, > 0 */
+  double pressure;          /* eV/A^3, finite (NPT_MTK) */
+  double taup;              /* fs, > 0 (NPT_MTK) */
+} m3g_nhc_params;
+#define M3G_NHC_NVT 0
+#define M3G_NHC_NPT_MTK 1
+#define M3G_NHC_MAX_CHAIN 8
+#define M3G_NHC_OBS 6       /* columns of an obs row */
+/* The state buffer is caller-owned device memory, one carve: the chunk table, chunk partials, masses, velocities (fp64), target
+ * temperatures, flags, step counts, coefficients, then per structure xi[M], vxi[M], xib[M], vxib[M], veps.  Bad sizes (n_structs >
+ * n_atoms, either < 1, chain_length outside 1 .. M3G_NHC_MAX_CHAIN) -> M3G_ERR_VALUE. */
+int m3g_nhc_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t chain_length, size_t* bytes);
+/* Byte offsets of the masses [N] and the velocities [N,3] (fp64) inside a state buffer of these sizes, as m3g_dyn_state_view. */
+int m3g_nhc_state_view(int64_t n_atoms, int64_t n_structs, int32_t chain_length, size_t* mass_offset, size_t* velocity_offset);
+/* Arguments as m3g_dyn_init (no seeds: nothing here is random).  Validated on the host before any HIP call, with the reason in
+ * m3g_last_error: an unknown ensemble, chain_length or chain_substeps outside 1 .. 8, dt / taut (NPT: taup) not finite and > 0, a bad
+ * pressure or mass, bad offsets, a target temperature that is not finite and > 0 (the chain masses are proportional to it), or a
+ * structure of one atom with fix_com -> M3G_ERR_VALUE.  Chain positions and velocities and veps start at 0.  Waits for the stream. */
+int m3g_nhc_init(const m3g_nhc_params* params, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
+                 const double* host_temperatures, const double* vel, void* state, size_t state_bytes, void* stream);
+/* One call per force evaluation; arguments as m3g_dyn_step, obs [S, M3G_NHC_OBS] fp64 DEVICE or NULL.  params: those of m3g_nhc_init.
+ * Three launches whatever S and N, no allocation, copy or wait: capture-safe.  NPT without stresses or lattice -> M3G_ERR_VALUE. */
+int m3g_nhc_step(const m3g_nhc_params* params, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
+                 const float* stresses, double* pos, double* lattice, float* lattice32, int32_t finish_only, double* obs, void* stream);
+/* Flags and step counts [S], the velocities [N,3] and the chain rows [S, 4 M + 1] (xi, vxi, xib, vxib, veps) to HOST memory; every
+ * output may be NULL.  Waits for the stream. */
+int m3g_nhc_read(int64_t n_atoms, int64_t n_structs, int32_t chain_length, const void* state, size_t state_bytes, int32_t* host_flags,
+                 int64_t* host_steps, double* host_vel, double* host_chain, void* stream);
+
 /* ---- batched replica-exchange MD (parallel tempering) over an m3g_dyn_* batch (csrc/m3g_remd.hip) -----------------------------------
  * The S structures of an NVT_LANGEVIN batch are cut into G ladders by ladder_offsets [G+1] (0 = o_0 < ... < o_G = S): ladder g is the
  * contiguous run of R_g = o_{g+1} - o_g >= 2 replicas of one system, with strictly ascending temperatures T_g[0..R_g) > 0 and one
@@ -995,7 +1055,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     additive, same version: m3g_remd_state_bytes / _init / _exchange / _read / _target_view (batched
                              *     replica-exchange MD over an m3g_dyn_* batch);
                              *     additive, same version: m3g_mc_state_bytes / _init / _propose / _decide / _read (batched atom-swap
-                             *     Monte Carlo, alone or over an m3g_dyn_* batch) */
+                             *     Monte Carlo, alone or over an m3g_dyn_* batch);
+                             *     additive, same version: m3g_nhc_state_bytes / _state_view / _init / _step / _read (Nose-Hoover chain NVT
+                             *     and isotropic MTK NPT, a family beside m3g_dyn_*) */
 
 #ifdef __cplusplus
 }

@@ -202,18 +202,22 @@ class GroupedEvaluation:
 
 
 class MdLog:
-    """The log of an MD run: step, e_pot, ke (eV), t (K), p (GPa), v (A^3) of every structure at the steps `append` is called."""
+    """The log of an MD run: step, e_pot, ke (eV), t (K), p (GPa), v (A^3) of every structure at the steps `append` is called; with
+    `conserved` (the ensembles of `NhcState`, whose obs rows hold the extended energy in column 4) also conserved = e_pot + ke +
+    extended (eV)."""
 
-    def __init__(self):
-        self.rows = {key: [] for key in ("step", "e_pot", "ke", "t", "p", "v")}
+    def __init__(self, conserved: bool = False):
+        self.rows = {key: [] for key in ("step", "e_pot", "ke", "t", "p", "v") + (("conserved",) if conserved else ())}
 
     def append(self, k: int, energies: torch.Tensor, obs: torch.Tensor) -> None:
-        """Step `k` at `energies` [S] and `DynState.obs` [S,4] (copies both to the host: waits)."""
+        """Step `k` at `energies` [S] and `DynState.obs` [S,4] / `NhcState.obs` [S,6] (copies both to the host: waits)."""
         obs = obs.cpu().numpy()
         self.rows["step"].append(np.full(len(obs), k))
         self.rows["e_pot"].append(energies.double().cpu().numpy())
         for j, key in enumerate(("ke", "t", "p", "v")):
             self.rows[key].append(obs[:, j] * (EV_A3_TO_GPA if key == "p" else 1.0))
+        if "conserved" in self.rows:
+            self.rows["conserved"].append(self.rows["e_pot"][-1] + obs[:, 0] + obs[:, 4])
 
     def arrays(self) -> dict:
         return {key: np.stack(val, axis=1) for key, val in self.rows.items()}   # [S, n_log]
