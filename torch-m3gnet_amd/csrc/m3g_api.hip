@@ -595,8 +595,7 @@ int Step::enqueue_forward() const {
       else launch_edge_block_mfma(plan, p, c, t, w, b, s);
       (void)ST_NODE_SUM;   // the per-centre sums are consumed by the next node_pre / the readout
     } else {
-      if (t.N > 0) M3G_HIP_CHECK(hipMemcpyAsync(w.x[b + 1], w.x[b], sizeof(float) * t.N * kDP, hipMemcpyDeviceToDevice, s));
-      launch_edge_block(c, W, wl.blk[b], t, w, b, w.x[b + 1], s);
+      launch_edge_block(c, W, wl.blk[b], t, w, b, w.x[b], w.x[b + 1], s);   // x^(b+1) = x^b + per-centre message sums
     }
   }
   M3G_STAGE(ST_READOUT);

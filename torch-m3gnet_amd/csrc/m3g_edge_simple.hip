@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(256) k_edge_block(Consts c, int64_t E, const f
                                                     const float* __restrict__ h, const float* __restrict__ m,
                                                     const float* __restrict__ TA, const float* __restrict__ TB,
                                                     float* __restrict__ e_io, float* __restrict__ act,
-                                                    float* __restrict__ x_new, const int32_t* __restrict__ act_id) {
+                                                    float* __restrict__ msg_out, const int32_t* __restrict__ act_id) {
   __shared__ TileLds L;
   int tid = threadIdx.x, o = tid & 63, eg = tid >> 6;
   int64_t e0 = (int64_t)blockIdx.x * TE;
@@ -134,23 +134,25 @@ __global__ void __launch_bounds__(256) k_edge_block(Consts c, int64_t E, const f
   __syncthreads();
   float msg[EPW];
   mlp_forward(W, bw.n, 2 * kDP, 4 * kDP, L, TA, TB, act, e0, E, c.R, o, eg, msg);
-  // segment-sum onto the centre atom: combine the wave's consecutive edges that share a centre
-  float run = 0.f;
-  int cur = -1;
+  // the messages go out as rows; k_edge_block_node_sum adds each centre's rows in list order (no atomics: the sums, and with them
+  // every later stage, are the same bits on every run)
 #pragma unroll
   for (int j = 0; j < EPW; ++j) {
-    int le = eg * EPW + j;
-    if (e0 + le < E) {
-      int s = L.ss[le];
-      if (s != cur) {
-        if (cur >= 0) atomicAdd(&x_new[(int64_t)cur * kDP + o], run);
-        cur = s;
-        run = 0.f;
-      }
-      run += msg[j];
-    }
+    int64_t e = e0 + eg * EPW + j;
+    if (e < E) msg_out[e * kDP + o] = msg[j];
   }
-  if (cur >= 0) atomicAdd(&x_new[(int64_t)cur * kDP + o], run);
+}
+
+// x_new[i] = x[i] + the messages of the edges of centre i (row_ptr: edges are sorted by centre), one thread per (atom, feature)
+__global__ void __launch_bounds__(256) k_edge_block_node_sum(int64_t N, int64_t E, const int32_t* __restrict__ row_ptr, const float* __restrict__ x,
+                                                             const float* __restrict__ msg, float* __restrict__ x_new) {
+  const int o = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= N) return;
+  float acc = x[i * kDP + o];
+  const int64_t lo = E > 0 ? row_ptr[i] : 0, hi = E > 0 ? row_ptr[i + 1] : 0;   // (no edges: no row is read)
+  for (int64_t e = lo; e < hi; ++e) acc += msg[e * kDP + o];
+  x_new[i * kDP + o] = acc;
 }
 
 struct TileLdsRev {
@@ -290,10 +292,12 @@ __global__ void __launch_bounds__(256) k_edge_block_reverse(Consts c, int64_t E,
 }
 
 void launch_edge_block(const Consts& c, const float* W, const BlockW& bw, const Topo& t, const Work& w, int b,
-                       float* x_new, hipStream_t s) {
-  if (t.E == 0) return;
-  hipLaunchKernelGGL(k_edge_block, grid_for(t.E, TE), dim3(256), 0, s, c, t.E, W, bw, t.src, t.dst, w.h, w.m[b], w.TA, w.TB,
-                     w.e, w.act[b], x_new, t.act_id);
+                       const float* x_old, float* x_new, hipStream_t s) {
+  // (w.de is free until the reverse pass clears it: it carries the block's message rows from the edge kernel to the per-centre sums)
+  if (t.E > 0)
+    hipLaunchKernelGGL(k_edge_block, grid_for(t.E, TE), dim3(256), 0, s, c, t.E, W, bw, t.src, t.dst, w.h, w.m[b], w.TA, w.TB,
+                       w.e, w.act[b], w.de, t.act_id);
+  if (t.N > 0) hipLaunchKernelGGL(k_edge_block_node_sum, grid_for(t.N, 4), dim3(256), 0, s, t.N, t.E, t.row_ptr, x_old, w.de, x_new);
 }
 
 void launch_edge_block_reverse(const Consts& c, const float* W, const BlockW& bw, const Topo& t, const Work& w, int b,

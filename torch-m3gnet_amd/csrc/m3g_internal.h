@@ -491,7 +491,7 @@ void launch_rows_to_soa(const float* rows, float* soa, int64_t E, hipStream_t s)
 void launch_soa_to_rows(const float* soa, float* rows, int row_stride, int width, int64_t E, hipStream_t s);
 // edge_simple.hip
 void launch_edge_block(const Consts& c, const float* W, const BlockW& bw, const Topo& t, const Work& w, int b,
-                       float* x_new, hipStream_t s);
+                       const float* x_old, float* x_new, hipStream_t s);
 void launch_edge_block_reverse(const Consts& c, const float* W, const BlockW& bw, const Topo& t, const Work& w, int b,
                                const float* dx_new, hipStream_t s);
 

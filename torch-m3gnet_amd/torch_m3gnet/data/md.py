@@ -37,6 +37,11 @@ from .graph_gpu import _ptr, _stream, neighbor_list_gpu
 from .material_graph import Batch
 
 
+def _alloc(numel: int, dtype: torch.dtype, device) -> torch.Tensor:
+    """Where `_md_prepare` gets its capacity buffers (the one seam tests replace to own them)."""
+    return torch.empty(numel, dtype=dtype, device=device)
+
+
 class VerletGraph:
     def __init__(self, lattices: Sequence, atomic_numbers: Sequence, cutoff: float, threebody_cutoff: float, skin: float = 0.5,
                  device="cuda"):
@@ -311,10 +316,10 @@ class VerletGraph:
             _lib.check(self.lib.m3g_topology_bytes(N, cap_e, cap_t, S, C.byref(nb_topo)))
             _lib.check(self.lib.m3g_workspace_bytes(engine.plan, N, cap_e, cap_t, S, C.byref(nb_work)))
             b = {
-                "ei": torch.empty(2 * cap_e, dtype=torch.int64, device=dev), "shift": torch.empty(3 * cap_e, dtype=torch.int32, device=dev),
-                "tei": torch.empty(2 * cap_t, dtype=torch.int64, device=dev), "nti": torch.empty(N, dtype=torch.int64, device=dev),
-                "ntij": torch.empty(cap_e, dtype=torch.int32, device=dev), "pos32": torch.empty(N, 3, dtype=torch.float, device=dev),
-                "topo": torch.empty(nb_topo.value, dtype=torch.uint8, device=dev), "work": torch.empty(nb_work.value, dtype=torch.uint8, device=dev),
+                "ei": _alloc(2 * cap_e, torch.int64, dev), "shift": _alloc(3 * cap_e, torch.int32, dev),
+                "tei": _alloc(2 * cap_t, torch.int64, dev), "nti": _alloc(N, torch.int64, dev),
+                "ntij": _alloc(cap_e, torch.int32, dev), "pos32": _alloc(N * 3, torch.float, dev).view(N, 3),
+                "topo": _alloc(nb_topo.value, torch.uint8, dev), "work": _alloc(nb_work.value, torch.uint8, dev),
                 "cap_e": cap_e, "cap_t": cap_t, "plan_key": (engine.precision, nb_work.value),
             }
         cap_e, cap_t = b["cap_e"], b["cap_t"]
