@@ -637,6 +637,65 @@ int m3g_nhc_step(const m3g_nhc_params* params, int64_t n_atoms, int64_t n_struct
 int m3g_nhc_read(int64_t n_atoms, int64_t n_structs, int32_t chain_length, const void* state, size_t state_bytes, int32_t* host_flags,
                  int64_t* host_steps, double* host_vel, double* host_chain, void* stream);
 
+/* ---- batched molecular dynamics, flexible-cell MTK NPT: the anisotropic barostat (csrc/m3g_mtk.hip) ----------------------------------
+ * The fully flexible Martyna-Tobias-Klein barostat with Nose-Hoover chains (Martyna, Tobias, Klein, J. Chem. Phys. 101, 4177 (1994);
+ * Mol. Phys. 87, 1117 (1996)): the cell changes shape as well as size.  A third family beside m3g_dyn_* and m3g_nhc_*: their structs,
+ * state layouts and results do not change.  Units, flags, the 3 n temperature convention and the chain half-step are those of
+ * m3g_nhc_*.  Positions and lattice rows are row vectors, so a symmetric 3x3 matrix acts from the right; such matrices are 6 numbers
+ * in Voigt order xx, yy, zz, yz, zx, xy.  Per structure of n atoms: g = 3 n - 3 with fix_com, else 3 n; kT = k_B T0; Q_1 = g kT
+ * taut^2, Q_k>1 = kT taut^2; the barostat variable is a symmetric rate vg (1/fs); cell_mask FULL moves all 6 of its components
+ * (n_c = 6), ORTHORHOMBIC the diagonal only (n_c = 3; for cells whose vectors lie along the axes); W_g = (g + 3) kT taup^2 / 3 (the
+ * isotropic family's W / 3: vg = veps I has the same kinetic energy); barostat chain masses Qb_1 = n_c kT taup^2, Qb_k>1 = kT taup^2.
+ *   G       = mask o [K + W_vir - V pressure I + (tr K / g) I] / W_g, K = sum m v v^T / kappa (tr K = 2 KE), W_vir = V * the
+ *             PAIR-VIRIAL stresses; tr G / 3 is the isotropic family's G_eps;
+ *   T(h)    particle chain on tr K against g kT (scales v), barostat chain on W_g sum_ab vg_ab^2 against n_c kT (first thermostat;
+ *           kT for the rest; scales vg), then vg += h G; the closing T(h) of a step runs the three in the opposite order;
+ *   B(h)    v = v exp(-B) + h a phi1(-B), B = (vg + (tr vg / g) I) h;  fix_com: v_i -= pbar / m_i after the opening kick;
+ *   A(dt)   x = x exp(A) + dt v phi1(A), A = vg dt, and lattice = lattice exp(A);
+ *           phi1(A) = sum_k A^k / (k + 1)!; exp and phi1 by Horner at the fixed order 12, no eigensolver and no branch.
+ * One step is T(h) B(h) A(dt) [forces] B(h) T(h), h = dt / 2, split over calls as m3g_nhc_step: one m3g_mtk_step at the forces F(x_k)
+ * closes the step under way, writes obs[s] = {KE, T = 2 KE / (3 n k_B), P = tr / 3, V, extended, 0, then the pressure tensor (W_vir +
+ * K) / V in Voigt order}, and opens the next (not with finish_only, which clears M3G_DYN_STARTED instead).  extended = g kT xi_1 + kT
+ * sum_k>1 xi_k + 1/2 sum Q vxi^2 + pressure V + 1/2 W_g sum_ab vg_ab^2 + n_c kT xib_1 + kT sum_k>1 xib_k + 1/2 sum Qb vxib^2: E_pot +
+ * KE + extended is conserved.  A structure whose forces or stresses hold a non-finite value, or whose max |vg_ab| dt exceeds 0.05 at
+ * the end of the call's thermostat arithmetic (the series above are exact to fp64 below it), gets M3G_DYN_ERROR and is frozen, bitwise:
+ * nothing of that call is kept.  The pressure is hydrostatic only.  A symmetric vg does not forbid a slow rigid rotation of the cell
+ * (products of symmetric matrices are not symmetric); the physics does not see it.  No atomics: every result is bitwise the same alone
+ * or in any batch. */
+typedef struct {
+  int32_t cell_mask;        /* M3G_MTK_CELL_FULL, M3G_MTK_CELL_ORTHORHOMBIC */
+  int32_t fix_com;          /* 0 / 1: zero the total momentum at every start; g = 3 n - 3 */
+  int32_t chain_length;     /* M: 1 .. M3G_NHC_MAX_CHAIN thermostats per chain (particles and barostat) */
+  int32_t chain_substeps;   /* 1 .. 8 equal parts of every chain half-step */
+  double dt;                /* fs, > 0 */
+  double taut;              /* fs, > 0 */
+  double pressure;          /* eV/A^3, finite; hydrostatic */
+  double taup;              /* fs, > 0 */
+} m3g_mtk_params;
+#define M3G_MTK_CELL_FULL 0
+#define M3G_MTK_CELL_ORTHORHOMBIC 1
+#define M3G_MTK_OBS 12      /* columns of an obs row */
+/* The state buffer is caller-owned device memory, one carve: the chunk table, chunk partials, masses, velocities (fp64), target
+ * temperatures, flags, step counts, coefficients, then per structure xi[M], vxi[M], xib[M], vxib[M], vg[6].  Bad sizes as
+ * m3g_nhc_state_bytes -> M3G_ERR_VALUE. */
+int m3g_mtk_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t chain_length, size_t* bytes);
+/* Byte offsets of the masses [N] and the velocities [N,3] (fp64) inside a state buffer of these sizes, as m3g_dyn_state_view. */
+int m3g_mtk_state_view(int64_t n_atoms, int64_t n_structs, int32_t chain_length, size_t* mass_offset, size_t* velocity_offset);
+/* Arguments as m3g_nhc_init.  Validated on the host before any HIP call, with the reason in m3g_last_error: an unknown cell_mask,
+ * fix_com not 0 / 1, chain_length or chain_substeps outside 1 .. 8, dt / taut / taup not finite and > 0, a bad pressure or mass, bad
+ * offsets, a target temperature that is not finite and > 0, or a structure of one atom with fix_com -> M3G_ERR_VALUE.  Chain
+ * positions and velocities and vg start at 0.  Waits for the stream. */
+int m3g_mtk_init(const m3g_mtk_params* params, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
+                 const double* host_temperatures, const double* vel, void* state, size_t state_bytes, void* stream);
+/* One call per force evaluation; arguments as m3g_nhc_step, obs [S, M3G_MTK_OBS] fp64 DEVICE or NULL.  params: those of m3g_mtk_init.
+ * Three launches whatever S and N, no allocation, copy or wait: capture-safe.  Missing stresses or lattice -> M3G_ERR_VALUE. */
+int m3g_mtk_step(const m3g_mtk_params* params, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
+                 const float* stresses, double* pos, double* lattice, float* lattice32, int32_t finish_only, double* obs, void* stream);
+/* Flags and step counts [S], the velocities [N,3] and the chain rows [S, 4 M + 6] (xi, vxi, xib, vxib, vg) to HOST memory; every
+ * output may be NULL.  Waits for the stream. */
+int m3g_mtk_read(int64_t n_atoms, int64_t n_structs, int32_t chain_length, const void* state, size_t state_bytes, int32_t* host_flags,
+                 int64_t* host_steps, double* host_vel, double* host_chain, void* stream);
+
 /* ---- batched replica-exchange MD (parallel tempering) over an m3g_dyn_* batch (csrc/m3g_remd.hip) -----------------------------------
  * The S structures of an NVT_LANGEVIN batch are cut into G ladders by ladder_offsets [G+1] (0 = o_0 < ... < o_G = S): ladder g is the
  * contiguous run of R_g = o_{g+1} - o_g >= 2 replicas of one system, with strictly ascending temperatures T_g[0..R_g) > 0 and one
@@ -1057,7 +1116,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     additive, same version: m3g_mc_state_bytes / _init / _propose / _decide / _read (batched atom-swap
                              *     Monte Carlo, alone or over an m3g_dyn_* batch);
                              *     additive, same version: m3g_nhc_state_bytes / _state_view / _init / _step / _read (Nose-Hoover chain NVT
-                             *     and isotropic MTK NPT, a family beside m3g_dyn_*) */
+                             *     and isotropic MTK NPT, a family beside m3g_dyn_*);
+                             *     additive, same version: m3g_mtk_state_bytes / _state_view / _init / _step / _read (flexible-cell MTK NPT:
+                             *     the anisotropic barostat, a third MD family beside m3g_dyn_* and m3g_nhc_*) */
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 // Batched molecular dynamics, the deterministic ensembles: Nose-Hoover chain NVT and isotropic Martyna-Tobias-Klein NPT (Martyna,
 // Tuckerman, Tobias, Klein, Mol. Phys. 87, 1117 (1996)), every structure of a batch with its own target temperature, beside the
-// ensembles of m3g_dynamics.hip and on the same layers (the chunk table of m3g_chunks.h, the constants of m3g_dyn_state.h).
+// ensembles of m3g_dynamics.hip and on the same layers (the chunk table of m3g_chunks.h, the constants of m3g_dyn_state.h; the chain
+// half-step is m3g_nhc_chain.h, shared with m3g_mtk.hip).
 // One step is T(h) B(h) A(dt) [forces] B(h) T(h), h = dt/2: T the thermostat (and, NPT, barostat) half-step, B the kick, A the drift.
 // One call -- finish step k, observables, start step k+1 -- is three launches for the whole batch, as m3g_dyn_step:
 //   k_nhc_partials   one workgroup per chunk: the finish kick in registers (its two coefficients are those of the start's kick: the
@@ -15,10 +16,10 @@
 #include <cmath>
 
 #include "m3g_dyn_state.h"
+#include "m3g_nhc_chain.h"
 
 namespace m3g {
 namespace {
-constexpr int kMaxChain = M3G_NHC_MAX_CHAIN;
 // per structure: action (0 none, 1 finish only, 2 finish + start), finish?, lambda (finish only: s1), the finish kick (v, a), the start
 // kick (v, a: kept for the next call's finish), the drift (x, v), pbar [3]
 constexpr int kNhcCoef = 12;
@@ -58,35 +59,6 @@ __device__ inline double sinhc(double y) {
 
 // v after a kick (or x after a drift): both are linear maps with two coefficients of the structure
 __device__ inline double axpby(double v, double cv, double a, double ca) { return v * cv + a * ca; }
-
-// The chain half-step of length h in n_c equal parts (MTK 1996) on a chain of M thermostats of masses q0, qk, qk, ... driven by k2,
-// twice the kinetic energy it thermostats, against gkt: returns the scale of the thermostatted velocities; k2 leaves scaled.
-__device__ inline double chain_half_step(double q0, double qk, double* xi, double* vxi, int M, int n_c, double& k2, double gkt, double kt,
-                                         double h) {
-  const double d = h / n_c;
-  double scale = 1.0;
-  auto force = [&](int k) {
-    if (k == 0) return (k2 - gkt) / q0;
-    return ((k == 1 ? q0 : qk) * vxi[k - 1] * vxi[k - 1] - kt) / qk;
-  };
-  for (int part = 0; part < n_c; ++part) {
-    vxi[M - 1] += 0.5 * d * force(M - 1);
-    for (int k = M - 2; k >= 0; --k) {
-      const double e = exp(-0.25 * d * vxi[k + 1]);
-      vxi[k] = (vxi[k] * e + 0.5 * d * force(k)) * e;
-    }
-    const double s = exp(-d * vxi[0]);
-    scale *= s;
-    k2 = s * s * k2;
-    for (int k = 0; k < M; ++k) xi[k] += d * vxi[k];
-    for (int k = 0; k < M - 1; ++k) {
-      const double e = exp(-0.25 * d * vxi[k + 1]);
-      vxi[k] = (vxi[k] * e + 0.5 * d * force(k)) * e;
-    }
-    vxi[M - 1] += 0.5 * d * force(M - 1);
-  }
-  return scale;
-}
 
 __global__ void __launch_bounds__(kChunkRows) k_nhc_init(NhcView st, const double* __restrict__ vel) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -296,7 +268,6 @@ const char* nhc_params_error(const m3g_nhc_params* p) {
   }
   return nullptr;
 }
-bool chain_ok(int32_t M) { return M >= 1 && M <= kMaxChain; }
 }  // namespace
 }  // namespace m3g
 

@@ -204,14 +204,20 @@ class GroupedEvaluation:
 class MdLog:
     """The log of an MD run: step, e_pot, ke (eV), t (K), p (GPa), v (A^3) of every structure at the steps `append` is called; with
     `conserved` (the ensembles of `NhcState`, whose obs rows hold the extended energy in column 4) also conserved = e_pot + ke +
-    extended (eV)."""
+    extended (eV); with `cell` (the ensemble of `MtkCellState`, whose obs rows hold the pressure tensor in columns 6 .. 11) also
+    pressure_tensor [6] (GPa, Voigt order xx, yy, zz, yz, zx, xy) and lattice [3,3] (A)."""
 
-    def __init__(self, conserved: bool = False):
-        self.rows = {key: [] for key in ("step", "e_pot", "ke", "t", "p", "v") + (("conserved",) if conserved else ())}
+    def __init__(self, conserved: bool = False, cell: bool = False):
+        self.rows = {key: [] for key in ("step", "e_pot", "ke", "t", "p", "v") + (("conserved",) if conserved else ())
+                     + (("pressure_tensor", "lattice") if cell else ())}
 
-    def append(self, k: int, energies: torch.Tensor, obs: torch.Tensor) -> None:
-        """Step `k` at `energies` [S] and `DynState.obs` [S,4] / `NhcState.obs` [S,6] (copies both to the host: waits)."""
+    def append(self, k: int, energies: torch.Tensor, obs: torch.Tensor, lattice: torch.Tensor | None = None) -> None:
+        """Step `k` at `energies` [S] and `DynState.obs` [S,4] / `NhcState.obs` [S,6] / `MtkCellState.obs` [S,12] (copies both to the
+        host: waits), with `cell` also at the cells `lattice` [S,3,3] the observables were taken in."""
         obs = obs.cpu().numpy()
+        if "lattice" in self.rows:
+            self.rows["pressure_tensor"].append(obs[:, 6:12] * EV_A3_TO_GPA)
+            self.rows["lattice"].append(lattice.cpu().numpy())
         self.rows["step"].append(np.full(len(obs), k))
         self.rows["e_pot"].append(energies.double().cpu().numpy())
         for j, key in enumerate(("ke", "t", "p", "v")):

@@ -1,6 +1,7 @@
 """Batched molecular dynamics on the device: NVE, NVT (Berendsen, Langevin) and isotropic NPT Berendsen (C ABI: m3g_dyn_*,
 csrc/m3g_dynamics.hip), and the deterministic, time-reversible ensembles with a conserved quantity, Nose-Hoover chain NVT and
-isotropic Martyna-Tobias-Klein NPT (C ABI: m3g_nhc_*, csrc/m3g_nhc.hip).
+isotropic Martyna-Tobias-Klein NPT (C ABI: m3g_nhc_*, csrc/m3g_nhc.hip), and the flexible-cell Martyna-Tobias-Klein NPT whose cell
+changes shape as well as size (C ABI: m3g_mtk_*, csrc/m3g_mtk.hip).
 
 The m3gnet package the reference stands in for runs MD through `MolecularDynamics` (ASE's VelocityVerlet "nve", NVTBerendsen "nvt",
 NPTBerendsen "npt_berendsen") on one structure at a time.  `MolecularDynamics.run` takes a whole batch: every structure is integrated
@@ -9,7 +10,7 @@ Per step the energies, forces and (pair-virial) stresses come from `VerletGraph.
 wait -- and the integrator of the whole batch is three kernel launches (`dyn_step`); the host copies observables only on log steps.
 NPT moves the cells at every step, so the candidates are searched again at every step (`VerletGraph.set_lattice`), as in the
 variable-cell `Relaxer`.  The two deterministic ensembles run the same loop over an `NhcState` / `nhc_step` pair shaped like
-`DynState` / `dyn_step`.
+`DynState` / `dyn_step`, and the flexible-cell one over `MtkCellState` / `mtk_cell_step`.
 
 Units: A, fs, amu, eV; velocities in A/fs; `MolecularDynamics` takes the pressure in GPa and the compressibility in 1/GPa (ASE's
 NPTBerendsen convention), the C ABI in eV/A^3 and A^3/eV."""
@@ -37,6 +38,8 @@ EV_PER_A3_IN_GPA = EV_A3_TO_GPA
 ENSEMBLES = {"nve": _lib.DYN_NVE, "nvt_berendsen": _lib.DYN_NVT_BERENDSEN, "nvt_langevin": _lib.DYN_NVT_LANGEVIN,
              "npt_berendsen": _lib.DYN_NPT_BERENDSEN}
 NHC_ENSEMBLES = {"nvt_nose_hoover": _lib.NHC_NVT, "npt_mtk": _lib.NHC_NPT_MTK}   # the m3g_nhc_* family
+CELL_MASKS = {"full": _lib.MTK_CELL_FULL, "orthorhombic": _lib.MTK_CELL_ORTHORHOMBIC}
+MTK_CELL_ENSEMBLES = {"npt_mtk_cell": CELL_MASKS}   # the m3g_mtk_* family: one ensemble, its `cell_mask` values
 
 
 def maxwell_boltzmann(masses, temperature: float, seed: int = 0) -> np.ndarray:
@@ -190,6 +193,77 @@ def nhc_step(state: NhcState, forces: torch.Tensor, stresses: torch.Tensor | Non
                                           _ptr(state.obs), _stream()))
 
 
+class MtkCellState:
+    """State of a flexible-cell MTK NPT ("npt_mtk_cell") batch on the device (m3g_mtk_init), shaped like `NhcState`: `pos` [N,3] fp64
+    and `lattice` [S,3,3] fp64 (triclinic cells welcome) are the caller's tensors, moved IN PLACE by `mtk_cell_step` (with `lattice32`,
+    the fp32 copy of the cells); the `velocities` argument is copied, the `velocities` attribute is the live [N,3] fp64 view of the
+    integrator's own.  `cell_mask`: "full" (all six components of the symmetric cell rate move) or "orthorhombic" (its diagonal
+    only: for cells whose vectors lie along the axes).  dt, taut, taup in fs, pressure (hydrostatic) in eV/A^3; chains as `NhcState`.
+    `obs` [S,12] (KE eV, T K, P eV/A^3, V A^3, extended eV, 0, then the pressure tensor in Voigt order xx, yy, zz, yz, zx, xy) is
+    written by every `mtk_cell_step`; E_pot + KE + extended is the conserved quantity.  A structure whose cell rate times dt passes
+    0.05 is flagged like one with non-finite forces or stresses, and frozen."""
+
+    def __init__(self, pos: torch.Tensor, lattice: torch.Tensor, offsets: Sequence[int], masses, velocities: torch.Tensor, temperatures,
+                 cell_mask: str = "full", dt: float = 1.0, taut: float = 100.0, pressure: float = 0.0, taup: float = 1000.0,
+                 chain_length: int = 3, chain_substeps: int = 1, fix_com: bool = True):
+        self.cell_mask = cell_mask_name(cell_mask)
+        self.ensemble = "npt_mtk_cell"
+        self.chain_length = chain_count("chain_length", chain_length)
+        self.params = _lib.M3GMtkParams(cell_mask=CELL_MASKS[self.cell_mask], fix_com=1 if fix_com else 0, chain_length=self.chain_length,
+                                        chain_substeps=chain_count("chain_substeps", chain_substeps), dt=dt, taut=taut, pressure=pressure,
+                                        taup=taup)
+        if lattice is None:
+            raise ValueError("NPT needs the lattice")
+        self.offsets, self.N, self.S = batch_layout(pos, lattice, offsets)
+        if velocities.dtype != torch.float64 or tuple(velocities.shape) != (self.N, 3) or velocities.device != pos.device:
+            raise ValueError(f"velocities must be a [{self.N}, 3] float64 tensor on {pos.device}")
+        self.masses = np.ascontiguousarray(np.asarray(masses, dtype=np.float64).reshape(-1))
+        self.temperatures = np.ascontiguousarray(np.broadcast_to(np.asarray(temperatures, dtype=np.float64), (self.S,)))
+        if len(self.masses) != self.N:
+            raise ValueError(f"expected {self.N} masses")
+        self.pos, self.lattice = pos, lattice
+        self.lattice32 = lattice.to(torch.float32)
+        self.device = pos.device
+        self.lib = _lib.load_library()
+        self.state = state_tensor(self.lib.m3g_mtk_state_bytes, self.N, self.S, self.chain_length, device=self.device)
+        self.obs = torch.full((self.S, _lib.MTK_OBS), float("nan"), dtype=torch.float64, device=self.device)
+        mass_at, vel_at = C.c_size_t(), C.c_size_t()
+        _lib.check(self.lib.m3g_mtk_state_view(self.N, self.S, self.chain_length, C.byref(mass_at), C.byref(vel_at)))
+        self.velocities = self.state[vel_at.value:vel_at.value + 24 * self.N].view(torch.float64).view(self.N, 3)
+        vel = velocities.contiguous()
+        with _cuda.on_device(self.device):
+            _lib.check(self.lib.m3g_mtk_init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, self.masses.ctypes.data,
+                                             self.temperatures.ctypes.data, _ptr(vel), _ptr(self.state), self.state.numel(), _stream()))
+
+    def read(self) -> dict:
+        """flags / n_steps [S], the velocities [N, 3] and the chain rows [S, 4 M + 6] (xi, vxi, xib, vxib of the M thermostats, then
+        the six components of the cell rate vg), copied to the host (waits for the stream)."""
+        return read_state(self.lib.m3g_mtk_read, (self.N, self.S, self.chain_length), self.state,
+                          (("flags", np.int32, self.S), ("n_steps", np.int64, self.S), ("v", np.float64, (self.N, 3)),
+                           ("chain", np.float64, (self.S, 4 * self.chain_length + 6))))
+
+
+def mtk_cell_step(state: MtkCellState, forces: torch.Tensor, stresses: torch.Tensor, finish_only: bool = False) -> None:
+    """One MD call of the batch (m3g_mtk_step), the arguments of `nhc_step` (the stresses are required): finish the step that ends
+    at these forces, write `state.obs`, start the next one (not with `finish_only`).  Three launches, queued on the current stream;
+    no wait, capture-safe."""
+    check_tensor("forces", forces, (state.N, 3), torch.float32)
+    if stresses is None:
+        raise ValueError("npt_mtk_cell needs the stresses")
+    check_tensor("stresses", stresses, (state.S, 6), torch.float32)
+    with _cuda.on_device(state.device):
+        _lib.check(state.lib.m3g_mtk_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
+                                          _ptr(stresses), _ptr(state.pos), _ptr(state.lattice), _ptr(state.lattice32), 1 if finish_only else 0,
+                                          _ptr(state.obs), _stream()))
+
+
+def cell_mask_name(x) -> str:
+    """`cell_mask`: "full" or "orthorhombic"."""
+    if not isinstance(x, str) or x not in CELL_MASKS:
+        raise ValueError(f"unknown cell_mask {x!r}; expected one of {sorted(CELL_MASKS)}")
+    return x
+
+
 def chain_count(name: str, x) -> int:
     """`chain_length` / `chain_substeps`: an integer in 1 .. 8."""
     if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 1 <= x <= _lib.NHC_MAX_CHAIN:
@@ -205,20 +279,27 @@ class MolecularDynamics(Driver):
     "npt_berendsen" (`taut`, `taup`, `pressure` in GPa, `compressibility` in 1/GPa -- required), "nvt_nose_hoover" (a Nose-Hoover
     chain of `chain_length` thermostats of period `taut`, every chain half-step in `chain_substeps` equal parts) or "npt_mtk" (the
     isotropic Martyna-Tobias-Klein barostat of period `taup` at `pressure`, with a chain on the particles and one on the barostat; no
-    compressibility).  The last two are deterministic and time-reversible, sample the canonical and the isothermal-isobaric
+    compressibility), or "npt_mtk_cell" (the fully flexible Martyna-Tobias-Klein barostat: the same parameters as "npt_mtk" and
+    `cell_mask`, "full" -- the cell changes shape as well as size, all six components of its symmetric rate move -- or
+    "orthorhombic" -- its three lengths move independently, for cells whose vectors lie along the axes; the pressure is hydrostatic
+    only; a symmetric rate does not forbid a slow rigid rotation of the cell, which the physics does not see).  The last three are deterministic and time-reversible, sample the canonical and the isothermal-isobaric
     ensemble, need every temperature > 0, and their log gains `conserved` (eV): e_pot + ke + the thermostat and barostat terms,
-    constant up to the O(timestep^2) error of the integrator.  Their `t` is 2 KE / (3 n kB) like the others', so its canonical mean
+    constant up to the O(timestep^2) error of the integrator ("npt_mtk_cell" also `pressure_tensor` [6], GPa in Voigt order xx, yy,
+    zz, yz, zx, xy, and `lattice` [3,3] per logged step).  Their `t` is 2 KE / (3 n kB) like the others', so its canonical mean
     is temperature * g / (3 n) with g = 3 n - 3 under `fix_com`.  `temperature`: K, one value or one per structure (the target of
     the thermostats and the temperature of the starting velocities).  `fix_com` (zero the total momentum at every step) defaults to
     True where the ensemble allows it (not with Langevin).  `seed`: an integer, or one per structure."""
 
     def __init__(self, model: Gradient, ensemble: str = "nvt_langevin", timestep: float = 1.0, temperature=300.0, taut: float | None = None,
                  friction: float = 0.01, pressure: float = 0.0, taup: float | None = None, compressibility: float | None = None,
-                 fix_com: bool | None = None, skin: float = 0.5, seed=0, device="cuda", chain_length: int = 3, chain_substeps: int = 1):
+                 fix_com: bool | None = None, skin: float = 0.5, seed=0, device="cuda", chain_length: int = 3, chain_substeps: int = 1,
+                 cell_mask: str = "full"):
         super().__init__(model, skin, device)
-        if not isinstance(ensemble, str) or (ensemble not in ENSEMBLES and ensemble not in NHC_ENSEMBLES):
-            raise ValueError(f"unknown ensemble {ensemble!r}; expected one of {sorted(ENSEMBLES) + sorted(NHC_ENSEMBLES)}")
+        known = sorted(ENSEMBLES) + sorted(NHC_ENSEMBLES) + sorted(MTK_CELL_ENSEMBLES)
+        if not isinstance(ensemble, str) or ensemble not in known:
+            raise ValueError(f"unknown ensemble {ensemble!r}; expected one of {known}")
         self.ensemble = ensemble
+        self.cell_mask = cell_mask_name(cell_mask)
         self.chain_length, self.chain_substeps = chain_count("chain_length", chain_length), chain_count("chain_substeps", chain_substeps)
         self.timestep = positive("timestep", timestep)
         self.taut = positive("taut", 100.0 * self.timestep if taut is None else taut)
@@ -240,12 +321,15 @@ class MolecularDynamics(Driver):
         t = np.asarray(temperature, dtype=np.float64)
         if t.ndim > 1 or not (np.isfinite(t).all() and (t >= 0).all()):
             raise ValueError("temperature must be one finite value >= 0 (K) or one per structure")
-        if ensemble in NHC_ENSEMBLES and not (t > 0).all():
+        if (ensemble in NHC_ENSEMBLES or ensemble in MTK_CELL_ENSEMBLES) and not (t > 0).all():
             raise ValueError(f"{ensemble} needs every temperature > 0 (the thermostat masses are proportional to it)")
         self.temperature = t
         self.seed = seed
 
     def _params(self) -> dict:
+        if self.ensemble in MTK_CELL_ENSEMBLES:
+            return dict(cell_mask=self.cell_mask, dt=self.timestep, taut=self.taut, pressure=self.pressure / EV_PER_A3_IN_GPA, taup=self.taup,
+                        chain_length=self.chain_length, chain_substeps=self.chain_substeps, fix_com=self.fix_com)
         if self.ensemble in NHC_ENSEMBLES:
             return dict(ensemble=self.ensemble, dt=self.timestep, taut=self.taut, pressure=self.pressure / EV_PER_A3_IN_GPA, taup=self.taup,
                         chain_length=self.chain_length, chain_substeps=self.chain_substeps, fix_com=self.fix_com)
@@ -260,20 +344,27 @@ class MolecularDynamics(Driver):
         masses: [n_s] amu per structure (default: standard atomic weights).  Returns one dict per structure: positions (unwrapped),
         velocities, lattice, total_energy, forces, stresses (pair virial) at the final step, n_steps, error (its forces became
         non-finite: it was stopped where it stood), and `log`: arrays step, e_pot, ke (eV), t (K), p (GPa), v (A^3) (and `conserved`,
-        eV, with "nvt_nose_hoover" and "npt_mtk") every `loginterval` steps and at the last one.  observables: a `TrajectoryObservables`; the trajectory is then sampled on the
+        eV, with "nvt_nose_hoover", "npt_mtk" and "npt_mtk_cell"; the last also pressure_tensor and lattice) every `loginterval` steps and at the last one.  observables: a `TrajectoryObservables`; the trajectory is then sampled on the
         device before the integrator call of every `sample_interval`-th step (positions, forces and velocities are synchronous only
         there: the sampler completes the half-step velocities with the finish kick itself) and every dict gains "observables".
         With "nvt_nose_hoover" the sampler's own v + dt/2 a is the state between the closing kick and the closing thermostat
         half-step: a point on the trajectory of the cyclically permuted splitting, as good a sample of the same dynamics.  With
-        "npt_mtk" the closing kick is not the plain one (it carries the barostat's friction), so `observables` raises ValueError."""
+        "npt_mtk" and "npt_mtk_cell" the closing kick is not the plain one (it carries the barostat's friction), so `observables`
+        raises ValueError.  "npt_mtk_cell" with `cell_mask` "orthorhombic" needs every lattice diagonal to 1e-9 of its largest entry.
+        As in the other NPT ensembles the cells go to the host and the candidates are searched again at every step."""
         if observables is not None and not isinstance(observables, TrajectoryObservables):
             raise TypeError(f"observables must be a TrajectoryObservables; got {type(observables).__name__}")
-        if observables is not None and self.ensemble == "npt_mtk":
-            raise ValueError("observables are not supported with npt_mtk: its finish kick is not the sampler's v + dt/2 a")
+        if observables is not None and self.ensemble in ("npt_mtk", "npt_mtk_cell"):
+            raise ValueError(f"observables are not supported with {self.ensemble}: its finish kick is not the sampler's v + dt/2 a")
         steps, loginterval = integer("steps", steps, 0), integer("loginterval", loginterval, 1)
         lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
         S = len(z)
-        nhc = self.ensemble in NHC_ENSEMBLES
+        cell = self.ensemble in MTK_CELL_ENSEMBLES
+        nhc = self.ensemble in NHC_ENSEMBLES or cell   # (the deterministic ensembles: a conserved quantity, temperatures > 0)
+        if cell and self.cell_mask == "orthorhombic":
+            for s, L in enumerate(lat):
+                if np.abs(L - np.diag(np.diag(L))).max() > 1e-9 * np.abs(L).max():
+                    raise ValueError(f"structure {s}: cell_mask 'orthorhombic' needs a diagonal lattice (cell vectors along the axes)")
         if nhc and self.fix_com and min(len(a) for a in z) == 1:
             raise ValueError(f"{self.ensemble} with fix_com needs more than one atom per structure (g = 3 n - 3 degrees of freedom)")
         temps = per_structure("temperature", self.temperature, S)
@@ -294,22 +385,26 @@ class MolecularDynamics(Driver):
         pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=vg.device)
         offsets = atom_offsets(z)
         lat64 = vg.lattice.clone()   # the NPT launches write the scaled cells here
-        npt = self.ensemble in ("npt_berendsen", "npt_mtk")
+        npt = self.ensemble in ("npt_berendsen", "npt_mtk", "npt_mtk_cell")
         vel_t = torch.tensor(np.concatenate(vel), device=vg.device)
-        if nhc:
+        if cell:
+            dyn, step = MtkCellState(pos_t, lat64, offsets, np.concatenate(m), vel_t, temps, **self._params()), mtk_cell_step
+        elif nhc:
             dyn, step = NhcState(pos_t, lat64, offsets, np.concatenate(m), vel_t, temps, **self._params()), nhc_step
         else:
             dyn, step = DynState(pos_t, lat64, offsets, np.concatenate(m), vel_t, temps, seeds, **self._params()), dyn_step
         traj = observables.begin(lat, z, m, vg.device) if observables is not None else None
-        log = MdLog(conserved=nhc)
+        log = MdLog(conserved=nhc, cell=cell)
         out = None
         for k in range(steps + 1):
             out = vg.step(model, pos_t)   # waits for the skin test (the previous dyn_step has been queued before it)
             if traj is not None and k % observables.sample_interval == 0:
                 traj_sample(traj, pos_t, lat64, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
+            logged = k % loginterval == 0 or k == steps
+            lat_now = lat64.clone() if cell and logged else None   # (the cell of the observables: the call below moves it on)
             step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=(k == steps))
-            if k % loginterval == 0 or k == steps:   # (host copies on log steps only)
-                log.append(k, out[K.TOTAL_ENERGY], dyn.obs)
+            if logged:   # (host copies on log steps only)
+                log.append(k, out[K.TOTAL_ENERGY], dyn.obs, lat_now)
             if npt and k < steps:
                 vg.set_lattice(list(lat64.cpu().numpy()))   # (waits: the candidate search in the new cells needs them on the host)
         vg.raise_on_step_errors("molecular dynamics")
