@@ -696,6 +696,67 @@ int m3g_mtk_step(const m3g_mtk_params* params, int64_t n_atoms, int64_t n_struct
 int m3g_mtk_read(int64_t n_atoms, int64_t n_structs, int32_t chain_length, const void* state, size_t state_bytes, int32_t* host_flags,
                  int64_t* host_steps, double* host_vel, double* host_chain, void* stream);
 
+/* ---- batched path-integral molecular dynamics: ring polymers under PILE-L (csrc/m3g_pimd.hip) ---------------------------------------
+ * Nuclear quantum effects by imaginary-time path integrals (Ceriotti, Parrinello, Markland, Manolopoulos, J. Chem. Phys. 133, 124104
+ * (2010)).  A fourth family beside m3g_dyn_*, m3g_nhc_* and m3g_mtk_*: their structs, state layouts and results do not change.  Units,
+ * constants and flag bits as m3g_dyn_*; hbar = 0.6582119569 eV fs.  The S = R P structures of the batch are R ring polymers laid out
+ * ring by ring: bead j of ring g is structure g P + j, and all P beads of a ring hold the same number of atoms n_g with the same
+ * masses.  Temperatures, seeds, flags, step counts and obs rows are per RING.  Ring g at target temperature T samples
+ *   H_P = sum_j [KE_j + 1/2 sum_i m_i w_P^2 |q_i,j - q_i,j+1|^2 + V(q_j)],  w_P = P k_B T / hbar,  at temperature P T,
+ * so every bead feels the full force.  Normal modes: the real orthogonal C[j][k] = sqrt(1/P) (k = 0), sqrt(2/P) cos(2 pi j k / P)
+ * (0 < 2 k < P), sqrt(1/P) (-1)^j (2 k = P), sqrt(2/P) sin(2 pi j k / P) (2 k > P), applied as the direct O(P^2) product, any P in
+ * 1 .. M3G_PIMD_MAX_BEADS; mode frequencies w_k = 2 w_P sin(k pi / P).  One step is BAOAB, h = dt / 2:
+ *   B(h)   v += h kappa F / m for every bead;
+ *   A(h)   in normal modes: mode 0 drifts, x += h v; mode k >= 1 rotates exactly, x' = cos(w_k h) x + sin(w_k h) / w_k v,
+ *          v' = cos(w_k h) v - w_k sin(w_k h) x;
+ *   O(dt)  in normal modes (PILE_L only): v' = c1_k v + c2_k sqrt(P k_B T kappa / m_i) xi, c1_k = exp(-gamma_k dt), c2_k = sqrt(1 -
+ *          c1_k^2), gamma_0 = centroid_friction, gamma_k = 2 pile_lambda w_k.  xi: Philox4x64-10, key (seed_g, 3), counter (the ring's
+ *          count of starts before this one, the atom's index inside the ring, k, 0), u and Box-Muller as NVT_LANGEVIN of m3g_dyn_*;
+ *   A(h), back to beads, [forces], B(h).
+ * Thermostat NONE skips O (microcanonical ring-polymer MD, which conserves H_P); centroid_friction = 0 under PILE_L is TRPMD.  The
+ * step is split over calls as m3g_dyn_step: one m3g_pimd_step at the forces F(x_k) closes the step under way with B(h), writes
+ * obs[g] = {KE of all beads, T = 2 KE / (3 n P^2 k_B) (canonical mean: the target), E_spring, K_prim = 3 n P k_B T / 2 - E_spring / P,
+ * K_cv = 3 n k_B T / 2 - 1 / (2 P) sum_j sum_i (q_i,j - qbar_i) . F_i,j with qbar the centroid of the unwrapped positions, heat, 0, 0},
+ * then opens the next with B A O A (not with finish_only, which clears M3G_DYN_STARTED instead).  heat is the running sum, over the
+ * O steps of all earlier calls, of the ring kinetic energy the thermostat added: sum_j E_j + KE + E_spring - heat is conserved up to
+ * the integrator's O(dt^2).  A ring with a non-finite force on any bead gets M3G_DYN_ERROR and is frozen, all beads bitwise.  No
+ * atomics: every result is bitwise the same alone or in any batch. */
+typedef struct {
+  int32_t thermostat;         /* M3G_PIMD_NONE, M3G_PIMD_PILE_L */
+  int32_t n_beads;            /* P: 1 .. M3G_PIMD_MAX_BEADS, the same for every ring of the batch */
+  double dt;                  /* fs, > 0 */
+  double centroid_friction;   /* 1/fs, >= 0: gamma of mode 0 */
+  double pile_lambda;         /* >= 0: gamma_k = 2 pile_lambda w_k for k >= 1 */
+} m3g_pimd_params;
+#define M3G_PIMD_NONE 0
+#define M3G_PIMD_PILE_L 1
+#define M3G_PIMD_MAX_BEADS 64
+#define M3G_PIMD_OBS 8      /* columns of an obs row */
+/* The state buffer is caller-owned device memory, one carve: the chunk table over RINGS, chunk partials, masses, velocities (fp64),
+ * per ring the target temperature, seed, flags, step count and heat, the [P,P] table and per ring and mode cos(w_k h), sin(w_k h) /
+ * w_k, w_k sin(w_k h), c1_k, c2_k (formed on the host in fp64 by the init call).  Bad sizes (as m3g_dyn_state_bytes, n_beads outside
+ * 1 .. M3G_PIMD_MAX_BEADS or not a divisor of n_structs and n_atoms) -> M3G_ERR_VALUE. */
+int m3g_pimd_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t n_beads, size_t* bytes);
+/* Byte offsets of the masses [N] and the velocities [N,3] (fp64) inside a state buffer of these sizes, as m3g_dyn_state_view. */
+int m3g_pimd_state_view(int64_t n_atoms, int64_t n_structs, int32_t n_beads, size_t* mass_offset, size_t* velocity_offset);
+/* host_offsets [S+1], host_masses [N] as m3g_dyn_init; host_temperatures [R] (K), host_seeds [R], R = S / n_beads: HOST.  vel [N,3]
+ * DEVICE fp64.  Validated on the host before any HIP call, with the reason in m3g_last_error: n_beads outside 1 .. 64 or not a
+ * divisor of n_structs, beads of a ring with unequal atom counts or unequal masses, an unknown thermostat, dt not finite and > 0,
+ * centroid_friction or pile_lambda not finite and >= 0, a temperature not finite and > 0, a bad mass, bad offsets -> M3G_ERR_VALUE;
+ * a short state buffer -> M3G_ERR_SIZE.  Waits for the stream. */
+int m3g_pimd_init(const m3g_pimd_params* params, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
+                  const double* host_temperatures, const uint64_t* host_seeds, const double* vel, void* state, size_t state_bytes,
+                  void* stream);
+/* One call per force evaluation: forces [N,3] f32 DEVICE evaluated at pos [N,3] fp64 DEVICE (unwrapped, moved IN PLACE); obs
+ * [R, M3G_PIMD_OBS] fp64 DEVICE or NULL.  params: those of m3g_pimd_init.  Three launches whatever R, P and N, no allocation, copy,
+ * wait or atomics: capture-safe.  Missing forces or pos -> M3G_ERR_VALUE. */
+int m3g_pimd_step(const m3g_pimd_params* params, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
+                  double* pos, int32_t finish_only, double* obs, void* stream);
+/* Flags, step counts and heat [R] and the velocities [N,3] to HOST memory; every output may be NULL.  heat holds the O steps up to
+ * the one before the last call's.  Waits for the stream. */
+int m3g_pimd_read(int64_t n_atoms, int64_t n_structs, int32_t n_beads, const void* state, size_t state_bytes, int32_t* host_flags,
+                  int64_t* host_steps, double* host_heat, double* host_vel, void* stream);
+
 /* ---- batched replica-exchange MD (parallel tempering) over an m3g_dyn_* batch (csrc/m3g_remd.hip) -----------------------------------
  * The S structures of an NVT_LANGEVIN batch are cut into G ladders by ladder_offsets [G+1] (0 = o_0 < ... < o_G = S): ladder g is the
  * contiguous run of R_g = o_{g+1} - o_g >= 2 replicas of one system, with strictly ascending temperatures T_g[0..R_g) > 0 and one
@@ -1118,7 +1179,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     additive, same version: m3g_nhc_state_bytes / _state_view / _init / _step / _read (Nose-Hoover chain NVT
                              *     and isotropic MTK NPT, a family beside m3g_dyn_*);
                              *     additive, same version: m3g_mtk_state_bytes / _state_view / _init / _step / _read (flexible-cell MTK NPT:
-                             *     the anisotropic barostat, a third MD family beside m3g_dyn_* and m3g_nhc_*) */
+                             *     the anisotropic barostat, a third MD family beside m3g_dyn_* and m3g_nhc_*);
+                             *     additive, same version: m3g_pimd_state_bytes / _state_view / _init / _step / _read: path-integral MD,
+                             *     ring polymers under PILE-L, a fourth MD family */
 
 #ifdef __cplusplus
 }
