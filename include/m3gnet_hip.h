@@ -757,6 +757,63 @@ int m3g_pimd_step(const m3g_pimd_params* params, int64_t n_atoms, int64_t n_stru
 int m3g_pimd_read(int64_t n_atoms, int64_t n_structs, int32_t n_beads, const void* state, size_t state_bytes, int32_t* host_flags,
                   int64_t* host_steps, double* host_heat, double* host_vel, void* stream);
 
+/* ---- batched thermodynamic integration to an Einstein crystal (csrc/m3g_ti.hip) ---------------------------------------------------------
+ * Anharmonic Helmholtz free energies by Frenkel-Ladd integration, at fixed coupling or by non-equilibrium switching (Freitas, Asta,
+ * de Koning, Comput. Mater. Sci. 112, 333 (2016)).  A fifth family beside m3g_dyn_*, m3g_nhc_*, m3g_mtk_* and m3g_pimd_*: their
+ * structs, state layouts and results do not change.  Units, kappa, k_B and the flag bits are those of m3g_dyn_*.  Every structure
+ * moves under H(lambda) = KE + lambda E_model(x) + (1 - lambda) U_s(x), U_s = 1/2 sum_i k_i |x_i - r0_i|^2 (k_i in eV/A^2 per atom,
+ * r0 the reference sites), by BAOAB Langevin dynamics whose centre of mass is held exactly: with u_i = x_i - r0_i and G_i = lambda F_i
+ * - (1 - lambda) k_i u_i the force on atom i is G_i - (m_i / M) sum_j G_j, and the O step is v_i <- c1 v_i + sigma_i xi_i - pbar / M,
+ * c1 = exp(-friction dt), sigma_i = sqrt((1 - c1^2) k_B T kappa / m_i), pbar = sum_j m_j sigma_j xi_j (xi: Philox4x64-10 under key
+ * (seed, 4), counter (step, atom of the structure, 0, 0), the Box-Muller of m3g_dyn_*).  friction = 0 is velocity Verlet on the
+ * constrained force.  A structure follows its path (lambda_b, lambda_e, n_switch, n_discard) by its step index c: lambda = lambda_b +
+ * (lambda_e - lambda_b) g(min(c, n_switch) / n_switch) (lambda_b when n_switch = 0), g(t) = t (LINEAR) or t^5 (70 t^4 - 315 t^3 +
+ * 540 t^2 - 420 t + 126) (SMOOTH).  One m3g_ti_step at the forces and energies of x_k closes the step under way with B(h), h = dt / 2,
+ * forms D = dH/dlambda = E - U_s, adds (lambda - lambda_prev) (D + D_prev) / 2 to the work W (not on the first call of a path), puts D
+ * into Welford's count / mean / M2 and |u_i|^2 into per-atom sums when c >= n_discard, writes obs[s] = {KE, T = 2 KE / ((3 n - 3) k_B),
+ * U_s, D, lambda, W, 0, 0} and (not with finish_only) starts the next step with B(h) A(h) O(dt) A(h) and c += 1.  A non-finite force or
+ * energy flags the structure M3G_DYN_ERROR and leaves it untouched from then on.  No atomics: every result is bitwise the same alone
+ * or in any batch.  The calls remove no centre-of-mass velocity or displacement: the caller starts from sum m_i v_i = 0. */
+typedef struct {
+  int32_t schedule;   /* M3G_TI_LINEAR, M3G_TI_SMOOTH */
+  int32_t reserved;   /* 0 */
+  double dt;          /* fs, > 0 */
+  double friction;    /* 1/fs, >= 0 */
+} m3g_ti_params;
+#define M3G_TI_LINEAR 0
+#define M3G_TI_SMOOTH 1
+#define M3G_TI_OBS 8      /* columns of an obs row */
+/* The state buffer is caller-owned device memory, one carve: the chunk table, chunk partials, per atom the mass, velocity, reference
+ * site, spring constant and sum of |u|^2, per structure the temperature, total mass, seed, flags, step count, path, work and
+ * accumulators.  Bad sizes (as m3g_dyn_state_bytes, or fewer than two atoms per structure) -> M3G_ERR_VALUE. */
+int m3g_ti_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* bytes);
+/* Byte offsets of the masses [N] and the velocities [N,3] (fp64) inside a state buffer of these sizes, as m3g_dyn_state_view. */
+int m3g_ti_state_view(int64_t n_atoms, int64_t n_structs, size_t* mass_offset, size_t* velocity_offset);
+/* host_offsets [S+1], host_masses [N], host_springs [N] (eV/A^2), host_temperatures [S] (K), host_seeds [S]: HOST.  vel, reference
+ * [N,3] DEVICE fp64, both copied.  The path starts as lambda = 1 throughout (n_switch = n_discard = 0).  Validated on the host before
+ * any HIP call, with the reason in m3g_last_error: an unknown schedule, dt not finite and > 0, friction not finite and >= 0, a
+ * temperature not finite and > 0, a bad mass, a spring constant not finite and >= 0 or all of a structure's zero, bad offsets, a
+ * structure of fewer than two atoms (the held centre of mass leaves 3 n - 3 degrees of freedom) -> M3G_ERR_VALUE; a short state
+ * buffer -> M3G_ERR_SIZE.  Waits for the stream. */
+int m3g_ti_init(const m3g_ti_params* params, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
+                const double* host_springs, const double* host_temperatures, const uint64_t* host_seeds, const double* vel,
+                const double* reference, void* state, size_t state_bytes, void* stream);
+/* A new path for every structure that has not failed: host_lambda_begin, host_lambda_end [S] HOST, each in [0, 1] (equal: fixed
+ * coupling), n_switch, n_discard >= 0, else M3G_ERR_VALUE.  Sets c = 0, W = 0 and clears the accumulators and the per-atom sums; a
+ * step under way is finished by the next m3g_ti_step at the new path's lambda.  Waits for the stream. */
+int m3g_ti_path(int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const double* host_lambda_begin,
+                const double* host_lambda_end, int64_t n_switch, int64_t n_discard, void* stream);
+/* One call per force evaluation: forces [N,3] and energies [S] f32 DEVICE evaluated at pos [N,3] fp64 DEVICE (unwrapped, moved IN
+ * PLACE); obs [S, M3G_TI_OBS] fp64 DEVICE or NULL.  params: those of m3g_ti_init.  Three launches whatever S and N, no allocation,
+ * copy, wait or atomics: capture-safe.  Missing forces, energies or pos -> M3G_ERR_VALUE. */
+int m3g_ti_step(const m3g_ti_params* params, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
+                const float* energies, double* pos, int32_t finish_only, double* obs, void* stream);
+/* Flags, step counts, work, Welford count / mean / M2 of D [S], the velocities [N,3] and the per-atom sums of |u|^2 [N] (over the
+ * `count` samples) to HOST memory; every output may be NULL.  Waits for the stream. */
+int m3g_ti_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes, int32_t* host_flags, int64_t* host_steps,
+                double* host_work, int64_t* host_count, double* host_mean, double* host_m2, double* host_vel, double* host_msd_sum,
+                void* stream);
+
 /* ---- batched replica-exchange MD (parallel tempering) over an m3g_dyn_* batch (csrc/m3g_remd.hip) -----------------------------------
  * The S structures of an NVT_LANGEVIN batch are cut into G ladders by ladder_offsets [G+1] (0 = o_0 < ... < o_G = S): ladder g is the
  * contiguous run of R_g = o_{g+1} - o_g >= 2 replicas of one system, with strictly ascending temperatures T_g[0..R_g) > 0 and one
@@ -1181,7 +1238,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     additive, same version: m3g_mtk_state_bytes / _state_view / _init / _step / _read (flexible-cell MTK NPT:
                              *     the anisotropic barostat, a third MD family beside m3g_dyn_* and m3g_nhc_*);
                              *     additive, same version: m3g_pimd_state_bytes / _state_view / _init / _step / _read: path-integral MD,
-                             *     ring polymers under PILE-L, a fourth MD family */
+                             *     ring polymers under PILE-L, a fourth MD family;
+                             *     additive, same version: m3g_ti_state_bytes / _state_view / _init / _path / _step / _read: thermodynamic
+                             *     integration to an Einstein crystal under centre-of-mass-conserving Langevin dynamics, a fifth MD family */
 
 #ifdef __cplusplus
 }

@@ -98,10 +98,15 @@ class M3GPimdParams(C.Structure):   # m3g_pimd_params
                 ("pile_lambda", C.c_double)]
 
 
+class M3GTiParams(C.Structure):   # m3g_ti_params
+    _fields_ = [("schedule", C.c_int32), ("reserved", C.c_int32), ("dt", C.c_double), ("friction", C.c_double)]
+
+
 DYN_NVE, DYN_NVT_BERENDSEN, DYN_NVT_LANGEVIN, DYN_NPT_BERENDSEN = range(4)   # M3G_DYN_* ensembles
 NHC_NVT, NHC_NPT_MTK, NHC_MAX_CHAIN, NHC_OBS = 0, 1, 8, 6                   # M3G_NHC_* ensembles, M3G_NHC_MAX_CHAIN, M3G_NHC_OBS
 MTK_CELL_FULL, MTK_CELL_ORTHORHOMBIC, MTK_OBS = 0, 1, 12                    # M3G_MTK_CELL_* masks, M3G_MTK_OBS
 PIMD_NONE, PIMD_PILE_L, PIMD_MAX_BEADS, PIMD_OBS = 0, 1, 64, 8               # M3G_PIMD_* thermostats, M3G_PIMD_MAX_BEADS, M3G_PIMD_OBS
+TI_LINEAR, TI_SMOOTH, TI_OBS = 0, 1, 8                                      # M3G_TI_* schedules, M3G_TI_OBS
 DYN_STARTED, DYN_ERROR = 1, 2                                               # M3G_DYN_* flag bits
 MC_NO_PAIR, MC_PENDING, MC_ERR_ORDER = 1, 2, 4                              # M3G_MC_* flag bits
 NEB_ROWS = 5                                                                 # M3G_NEB_ROWS
@@ -261,6 +266,15 @@ SYMBOLS = {
                                 C.c_void_p, C.c_void_p]),
     "m3g_pimd_read": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p]),
+    "m3g_ti_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "m3g_ti_state_view": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "m3g_ti_init": (C.c_int, [C.POINTER(M3GTiParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "m3g_ti_path": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "m3g_ti_step": (C.c_int, [C.POINTER(M3GTiParams), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_int32, C.c_void_p, C.c_void_p]),
+    "m3g_ti_read": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_remd_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     "m3g_remd_init": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "m3g_remd_exchange": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
