@@ -4,8 +4,12 @@ TEST INFRASTRUCTURE ONLY (see oracle/m3gnet_oracle.py header for who may import 
 `m3gnet_oracle.energy_forces` restates the reference module by module and differentiates with
 autograd.  The engine instead runs the algebraically restructured pipeline below with a hand-derived
 reverse pass (DESIGN.md "Stages").  This file spells that pipeline out in plain torch so that
-  (1) tests/test_staged_oracle.py proves on the CPU (fp64) that it equals the module-by-module oracle,
-  (2) GPU parity tests can compare every engine stage buffer with the tensor of the same name here.
+  (1) tests/test_oracle_golden.py (test_staged_pipeline_equals_oracle_fp64) proves on the CPU (fp64) that it equals the
+      module-by-module oracle,
+  (2) GPU parity tests can compare every engine stage buffer with the tensor of the same name here,
+  (3) every separable term of the reverse pass can be switched off by name (`ablate`, REVERSE_TERMS, term_shares), so that
+      tests/test_reverse_terms_cpu.py can say how much of max|F| each term carries on an input -- which is how tightly a force
+      gate of 1e-4 of max|F| holds that term there.
 
 Restructuring facts used (all follow from the reference formulas):
   * chi_ln(d_ik) fc(d_ik) is a per-EDGE quantity q[e,c]; per triplet only Y_l(cos) remains
@@ -114,8 +118,40 @@ def _mlp2_backward(d_upd, sv, w, D):
     return MM(d_p1, w["w1c"]), d_p1, d_h
 
 
-def forward_backward(p: dict, cfg: OracleConfig, c: OracleConstants, graph: dict) -> dict:
-    """Energy + analytic forces.  Returns all stage buffers (names = DESIGN.md / csrc workspace names)."""
+# Separable terms of the reverse pass, by the name `forward_backward(..., ablate=...)` switches them off with; a switch acts in every
+# block.  The forces are linear in d_u, so what `angular` carries is the sum of what its halves carry; d_m = dm_dense + dm_gate adds up
+# the same way within one block only, since d_m of a block feeds d_m of the block before it (tests/test_reverse_terms_cpu.py).
+REVERSE_TERMS = {
+    "tb_cutoff": "B3: fc3p * d_fc1, the centre edge's three-body cutoff derivative",
+    "tb_basis": "B3: (d_g * v[dst] * qp).sum(1), the partner edge's radial-basis (and its cutoff's) derivative",
+    "angular": "B3: all of d_u (both index_add halves)",
+    "angular_t1": "B3: the half of d_u scattered to the centre edge t1",
+    "angular_t2": "B3: the half of d_u scattered to the partner edge t2",
+    "du_projection": "B0: the -(d_u . u) u part of the derivative of u = r / |r|",
+    "atom_gate": "B2: (d_v * v * (1 - v)) @ w1, the reverse of the per-atom sigmoid gate",
+    "dm": "B4: all of d_m, the reverse of the three-body gated update",
+    "dm_dense": "B4: MM(d_pd, wd), the SiLU half of d_m",
+    "dm_gate": "B4: MM(d_pg, wg), the sigmoid-gate half of d_m",
+    "node_ta": "B2: d_TA @ w1a of both conv MLPs (table gathered by the centre atom)",
+    "node_tb": "B2: d_TB @ w1b of both conv MLPs (table gathered by the neighbour atom)",
+    "dh_conv": "B4: d_h of the two conv MLPs' radial linear layers",
+    "dh_embed": "B1: d_h of the edge embedding",
+    "de_edge": "B4: the edge MLP's contribution to d_e (through w1c)",
+    "de_node": "B4: the node MLP's contribution to d_e (through w1c)",
+}
+
+
+def forward_backward(p: dict, cfg: OracleConfig, c: OracleConstants, graph: dict, ablate=frozenset()) -> dict:
+    """Energy + analytic forces.  Returns all stage buffers (names = DESIGN.md / csrc workspace names).
+    `ablate`: names of REVERSE_TERMS to leave out of the reverse pass (the forward pass never changes); with the default no returned
+    tensor changes in any bit."""
+    ablate = frozenset(ablate)
+    if ablate - REVERSE_TERMS.keys():
+        raise ValueError(f"unknown reverse terms: {sorted(ablate - REVERSE_TERMS.keys())}")
+
+    def on(*names):
+        return ablate.isdisjoint(names)
+
     dt = p["model.3.linear.weight"].dtype
     D, R, L, C, B = cfg.embedding_dim, cfg.n_max, cfg.l_max, cfg.l_max * cfg.n_max, cfg.num_blocks
     pos, lattice = graph["pos"].to(dt), graph["lattice"].to(dt)
@@ -237,40 +273,61 @@ def forward_backward(p: dict, cfg: OracleConfig, c: OracleConstants, graph: dict
         # ---- B4 edge block reverse ---------------------------------------------------------
         d_msg = d_x[src]
         de_n, dp1_n, dh_n = _mlp2_backward(d_msg, sv["sv_n"], w["n"], D)
-        d_e2 = d_e + de_n
+        d_e2 = d_e + de_n if on("de_node") else d_e
         de_e, dp1_e, dh_e = _mlp2_backward(d_e2, sv["sv_e"], w["e"], D)
-        d_e1 = d_e2 + de_e
-        d_h = d_h + dh_n + dh_e
+        d_e1 = d_e2 + de_e if on("de_edge") else d_e2
+        if on("dh_conv"):
+            d_h = d_h + dh_n + dh_e
         sgg = torch.sigmoid(sv["pg"])
         d_pd = d_e1 * sgg * _dsilu(sv["pd"])
         d_pg = d_e1 * _silu(sv["pd"]) * sgg * (1 - sgg)
-        d_m = MM(d_pd, sv["wd"]) + MM(d_pg, sv["wg"])  # [E,C]
+        if on("dm", "dm_dense", "dm_gate"):
+            d_m = MM(d_pd, sv["wd"]) + MM(d_pg, sv["wg"])  # [E,C]
+        elif on("dm", "dm_dense"):
+            d_m = MM(d_pd, sv["wd"])
+        elif on("dm", "dm_gate"):
+            d_m = MM(d_pg, sv["wg"])
+        else:
+            d_m = torch.zeros(E, C, dtype=dt)
         d_e = d_e1
         dp1 = torch.cat([dp1_e, dp1_n], dim=1)  # [E,4D]
         d_TA = torch.zeros(N, 4 * D, dtype=dt).index_add(0, src, dp1)
         d_TB = torch.zeros(N, 4 * D, dtype=dt).index_add(0, dst, dp1)
         # ---- B3 three-body reverse ---------------------------------------------------------
         d_fc1 = (d_m * sv["Ssum"]).sum(1)
-        d_d = d_d + fc3p * d_fc1
+        if on("tb_cutoff"):
+            d_d = d_d + fc3p * d_fc1
         d_S = fc3[:, None] * d_m  # [E,C]
         g = sv["g"]
         d_cos = (d_S[t1] * dYc * g[t2]).sum(1) * inside  # [T]
-        d_u = d_u.index_add(0, t1, d_cos[:, None] * u[t2]).index_add(0, t2, d_cos[:, None] * u[t1])
+        if on("angular", "angular_t1", "angular_t2"):
+            d_u = d_u.index_add(0, t1, d_cos[:, None] * u[t2]).index_add(0, t2, d_cos[:, None] * u[t1])
+        elif on("angular", "angular_t1"):
+            d_u = d_u.index_add(0, t1, d_cos[:, None] * u[t2])
+        elif on("angular", "angular_t2"):
+            d_u = d_u.index_add(0, t2, d_cos[:, None] * u[t1])
         d_g = torch.zeros(E, C, dtype=dt).index_add(0, t2, d_S[t1] * Yc)
         v = sv["v"]
-        d_d = d_d + (d_g * v[dst] * qp).sum(1)
+        if on("tb_basis"):
+            d_d = d_d + (d_g * v[dst] * qp).sum(1)
         d_v = torch.zeros(N, C, dtype=dt).index_add(0, dst, d_g * q)
         # ---- B2 node reverse -----------------------------------------------------------------
-        d_x = (d_x
-               + d_TA[:, : 2 * D] @ w["e"]["w1a"] + d_TA[:, 2 * D:] @ w["n"]["w1a"]
-               + d_TB[:, : 2 * D] @ w["e"]["w1b"] + d_TB[:, 2 * D:] @ w["n"]["w1b"]
-               + (d_v * v * (1 - v)) @ sv["w1"])
+        if on("node_ta"):
+            d_x = d_x + d_TA[:, : 2 * D] @ w["e"]["w1a"] + d_TA[:, 2 * D:] @ w["n"]["w1a"]
+        if on("node_tb"):
+            d_x = d_x + d_TB[:, : 2 * D] @ w["e"]["w1b"] + d_TB[:, 2 * D:] @ w["n"]["w1b"]
+        if on("atom_gate"):
+            d_x = d_x + (d_v * v * (1 - v)) @ sv["w1"]
         st[f"dm_{b}"], st[f"dx_in_{b}"], st[f"de_in_{b}"] = d_m, d_x, d_e
     # ---- B1 edge embedding reverse -----------------------------------------------------------
-    d_h = d_h + (d_e * _dsilu(pe0)) @ w_adj
+    if on("dh_embed"):
+        d_h = d_h + (d_e * _dsilu(pe0)) @ w_adj
     # ---- B0 geometry reverse -----------------------------------------------------------------
     d_d = d_d + (d_h * hp).sum(1)
-    d_r = d_d[:, None] * u + (d_u - (d_u * u).sum(1, keepdim=True) * u) / d[:, None]
+    if on("du_projection"):
+        d_r = d_d[:, None] * u + (d_u - (d_u * u).sum(1, keepdim=True) * u) / d[:, None]
+    else:
+        d_r = d_d[:, None] * u + d_u / d[:, None]
     grad_spos = torch.zeros(N, 3, dtype=dt).index_add(0, dst, d_r).index_add(0, src, -d_r)
     forces = -grad_spos / ls
     vir = torch.zeros(S, 3, 3, dtype=dt).index_add(0, batch, pos[:, :, None] * forces[:, None, :])
@@ -278,3 +335,12 @@ def forward_backward(p: dict, cfg: OracleConfig, c: OracleConstants, graph: dict
     voigt = torch.stack([vir[:, 0, 0], vir[:, 1, 1], vir[:, 2, 2], vir[:, 1, 2], vir[:, 2, 0], vir[:, 0, 1]], dim=1)
     st.update(dh=d_h, dd=d_d, du=d_u, dr=d_r, forces=forces, stresses=voigt / vol[:, None])
     return st
+
+
+def term_shares(p: dict, cfg: OracleConfig, c: OracleConstants, graph: dict, names=None) -> dict:
+    """{term: max|F - F_without_the_term| / max|F|} for every name of REVERSE_TERMS (or of `names`): the part of the largest force
+    component that a term carries on this input.  A force gate of g * max|F| holds a term of share s to g / s of itself."""
+    full = forward_backward(p, cfg, c, graph)["forces"]
+    top = float(full.abs().max())
+    return {name: float((full - forward_backward(p, cfg, c, graph, ablate={name})["forces"]).abs().max()) / top
+            for name in (REVERSE_TERMS if names is None else names)}

@@ -237,9 +237,11 @@ def test_dense_three_body_rows_beyond_the_staged_window():
     from torch_m3gnet.data.material_graph import Batch
     from oracle import m3gnet_oracle as orc
 
+    from reverse_term_cases import dense_cell
+
     K = _K()
     model = _default_model(seed=2, threebody_cutoff=5.0)
-    dense = random_cell_graph(24, 5.0, 5, cutoff=5.0, tb_cutoff=5.0, dmin=1.2)
+    dense = dense_cell()   # (the same cell under weights that give the three-body reverse 20 % of max|F|: tests/test_gpu_reverse_terms.py)
     per_centre = dense[K.NUM_TRIPLETS] / 24
     assert per_centre > 80 * 79, per_centre
     for graphs in ([dense], [random_cell_graph(6, 5.5, 1), dense]):
@@ -325,22 +327,14 @@ def test_one_sided_and_filtered_triplet_lists():
     centre, not only the symmetric list `compute_threebody` emits.  One-sided (e1 < e2 only) and randomly thinned lists
     contain edges that only ever appear as the partner e2: the engine must keep their rows (they were dropped before the
     round-2 topology fix, silently corrupting energies and forces)."""
-    from torch_m3gnet.data.material_graph import Batch
+    from reverse_term_cases import triplet_list_variants
 
     K = _K()
     model = _default_model(seed=2, energy_scale=2.0)
-    base = Batch.from_data_list([random_cell_graph(20, 6.5, s) for s in (7, 8)])
-    tei = base[K.TRIPLET_EDGE_INDEX]
-    gen = torch.Generator().manual_seed(0)
-    variants = {
-        "one_sided": tei[:, tei[0] < tei[1]],
-        "thinned": tei[:, torch.rand(tei.size(1), generator=gen) < 0.3],
-        "single_pair": tei[:, :1],
-    }
-    for name, sub in variants.items():
-        g = base.clone()
-        g[K.TRIPLET_EDGE_INDEX] = sub.contiguous()
-        g[K.NUM_TRIPLETS] = int(sub.size(1))
+    # (the lists are built in tests/reverse_term_cases.py; tests/test_gpu_reverse_terms.py runs the one-sided and the thinned one under
+    #  weights that give the three-body reverse a share of max|F| the force gate can see)
+    for name, g in triplet_list_variants().items():
+        sub = g[K.TRIPLET_EDGE_INDEX]
         only_e2 = set(sub[1].tolist()) - set(sub[0].tolist())
         assert name == "single_pair" or len(only_e2) > 0     # the case the fix is about really occurs
         out = model(g.to(DEV))
@@ -365,40 +359,23 @@ def test_asymmetric_edge_lists_take_the_sorted_incoming_lists():
     sort and still match the oracle.  Also: the same graph evaluated with a symmetric list afterwards (mirror path) agrees with
     the oracle too, and a multigraph cell (several images of the same neighbour) runs the mirror path on duplicate (i, j) pairs."""
     from oracle import m3gnet_oracle as orc
-    from torch_m3gnet.data.material_graph import Batch
-    from torch_m3gnet.data.neighbors import threebody_index
+    from reverse_term_cases import edge_list_variants
 
     K = _K()
     model = _default_model(seed=4, energy_scale=1.5)
-    cases = {"thinned": random_cell_graph(24, 7.0, 21), "multigraph": random_cell_graph(5, 3.9, 22, dmin=1.8)}
-    for name, cell in cases.items():
-        base = Batch.from_data_list([cell])
-        ei, shift = base[K.EDGE_INDEX], base[K.EDGE_CELL_SHIFT]
-        variants = {"symmetric": torch.ones(ei.size(1), dtype=torch.bool)}
-        if name == "thinned":
-            keep = torch.rand(ei.size(1), generator=torch.Generator().manual_seed(1)) < 0.85   # drops one direction of many pairs
-            variants["asymmetric"] = keep
-        for vname, keep in variants.items():
-            g = base.clone()
-            g[K.EDGE_INDEX] = ei[:, keep].contiguous()
-            g[K.EDGE_CELL_SHIFT] = shift[keep].contiguous()
-            # triplets of the remaining edges (distances from the positions, as the builders form them)
-            pos, lat = base[K.POS].double(), base[K.LATTICE][0].double()
-            src, dst = g[K.EDGE_INDEX]
-            d = (pos[dst] + g[K.EDGE_CELL_SHIFT].double() @ lat - pos[src]).norm(dim=1)
-            tei, nti, ntij = threebody_index(int(pos.size(0)), g[K.EDGE_INDEX].numpy(), d.float().numpy(), 4.0)
-            g[K.TRIPLET_EDGE_INDEX] = torch.from_numpy(tei)
-            g[K.NUM_TRIPLET_I], g[K.NUM_TRIPLET_IJ] = torch.from_numpy(nti), torch.from_numpy(ntij)
-            g[K.NUM_EDGES], g[K.NUM_TRIPLETS] = int(g[K.EDGE_INDEX].size(1)), int(tei.shape[1])
-            out = model(g.to(DEV))
-            p, cfg, c, og = _oracle_inputs(model, out)
-            p = {k: v.double() for k, v in p.items()}
-            c = orc.make_constants(cfg, model.model[1].elemental_energies.cpu(), dtype=torch.float64)
-            c.factors = model.model[6].nsb.factors.double()
-            o = orc.energy_forces(p, cfg, c, og, legendre_backward="exact")
-            assert float(((out[K.TOTAL_ENERGY].cpu().double() - o["total_energy"]).abs() / o["total_energy"].abs()).max()) < 1e-5, (name, vname)
-            assert rel_err(out[K.FORCES], o["forces"]) < 1e-4, (name, vname)
-            assert rel_err(out[K.NODE_FEATURES], o["x"]) < 1e-5, (name, vname)
+    # (the lists are built in tests/reverse_term_cases.py; tests/test_gpu_reverse_terms.py runs the asymmetric one under weighted models)
+    variants = edge_list_variants()
+    assert set(variants) == {("thinned", "symmetric"), ("thinned", "asymmetric"), ("multigraph", "symmetric")}
+    for (name, vname), g in variants.items():
+        out = model(g.to(DEV))
+        p, cfg, c, og = _oracle_inputs(model, out)
+        p = {k: v.double() for k, v in p.items()}
+        c = orc.make_constants(cfg, model.model[1].elemental_energies.cpu(), dtype=torch.float64)
+        c.factors = model.model[6].nsb.factors.double()
+        o = orc.energy_forces(p, cfg, c, og, legendre_backward="exact")
+        assert float(((out[K.TOTAL_ENERGY].cpu().double() - o["total_energy"]).abs() / o["total_energy"].abs()).max()) < 1e-5, (name, vname)
+        assert rel_err(out[K.FORCES], o["forces"]) < 1e-4, (name, vname)
+        assert rel_err(out[K.NODE_FEATURES], o["x"]) < 1e-5, (name, vname)
 
 
 def test_topology_hints_tell_complete_lists_from_the_rest():
