@@ -912,6 +912,58 @@ int m3g_mc_read(int64_t n_atoms, int64_t n_structs, const void* state, size_t st
                 int64_t* host_attempts, int64_t* host_accepts, int64_t* host_nonfinite, int64_t* host_count, double* host_mean, double* host_m2,
                 int32_t* host_pairs, void* stream);
 
+/* ---- batched reverse non-equilibrium MD over an m3g_dyn_* batch: imposed heat or momentum flux (csrc/m3g_rnemd.hip) -----------------
+ * Mueller-Plathe's method (J. Chem. Phys. 106, 6082 (1997); Phys. Rev. E 59, 4894 (1999)) with the unequal-mass exchange of
+ * Nieto-Draghi and Avalos (Mol. Phys. 101, 2303 (2003)).  A batch of S structures with N atoms in all (offsets [S+1] as m3g_dyn_init),
+ * each cut into n_slabs slabs along lattice direction `axis`.  The calls act on the m3g_dyn_* state of the same batch at a synchronous
+ * point, after a finish_only m3g_dyn_step, as m3g_remd_exchange does.
+ * Slab of a row: g_s = column `axis` of the inverse lattice (rows = lattice vectors), computed by m3g_rnemd_init on the host in fp64;
+ *   on the device f = (x g0 + y g1) + z g2, f -= floor(f), slab = min((int)(f n_slabs), n_slabs - 1): a wrapped f of exactly 1.0 lands
+ *   in the last slab.  No product is contracted with a sum anywhere in this family.  Slab 0 is the cold (sink) slab, slab n_slabs / 2
+ *   the hot (source) slab.
+ * Selection: the candidates of a slab are its rows with active != 0 and a finite key.  kind HEAT: key = m ((vx vx + vy vy) + vz vz);
+ *   MOMENTUM: key = v[flow_axis].  Slab 0 is ordered by (key descending, row ascending), slab n_slabs / 2 by (key ascending, row
+ *   ascending).  Pair p = 0 .. n_swaps - 1 takes the p-th entry of each list while both lists hold one, and is exchanged iff
+ *   key0 > keyMid strictly.
+ * Exchange of rows i (slab 0) and j: with mi == mj bitwise the velocity vectors (HEAT) or their flow_axis components (MOMENTUM) trade
+ *   places; else vcm = (mi vi + mj vj) / (mi + mj), vi' = 2 vcm - vi, vj' = 2 vcm - vj on those components.  Both conserve sum m v and
+ *   sum m |v|^2 exactly in real arithmetic.  `transferred` gains 0.5 mi (|vi|^2 - |vi'|^2) / kappa (HEAT, eV; |v|^2 = (vx vx + vy vy) +
+ *   vz vz, kappa of m3g_dyn_*) or mi (vi - vi') (MOMENTUM, amu A/fs), pairs in the order p = 0, 1, ...
+ * Sampling (do_sample): per slab the number of rows and the sums of m, m vx, m vy, m vz, m ((vx vx + vy vy) + vz vz) over ALL its rows
+ *   (inactive ones too), from the velocities BEFORE the exchange of the same call: per run of 64 consecutive rows of the
+ *   structure in row order from zero, the four runs of a chunk of 256 rows in row order from zero, the chunks' partials in chunk
+ *   order from zero, and that total added to the accumulator.
+ * A structure whose dyn flags carry M3G_DYN_ERROR or M3G_DYN_STARTED is left bitwise untouched: not exchanged, not sampled, none of
+ *   its counters advanced.  Otherwise n_calls advances at every call that swaps or samples, n_samples at every sampling one, and
+ *   last_pairs is rewritten by every swapping one.
+ * No atomics: every result of a structure depends on its own rows only, bitwise the same alone or in any batch. */
+typedef struct { int32_t kind, axis, flow_axis, n_slabs, n_swaps, reserved; } m3g_rnemd_params;   /* 24 bytes */
+#define M3G_RNEMD_HEAT 0
+#define M3G_RNEMD_MOMENTUM 1
+#define M3G_RNEMD_MAX_SWAPS 8
+#define M3G_RNEMD_MAX_SLABS 64
+/* Null `bytes`, bad sizes, n_slabs odd, < 2 or > M3G_RNEMD_MAX_SLABS -> M3G_ERR_VALUE. */
+int m3g_rnemd_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t n_slabs, size_t* bytes);
+/* host_offsets [S+1] int64, host_lattices [S,3,3] fp64 (rows = lattice vectors), host_active [N] uint8 or NULL (every row takes part):
+ * HOST.  Null pointers, bad sizes or offsets, an unknown kind, axis or flow_axis outside 0 .. 2, MOMENTUM with flow_axis == axis,
+ * n_slabs odd, < 2 or > 64, n_swaps < 1 or > 8, a singular or non-finite lattice -> M3G_ERR_VALUE, a short buffer -> M3G_ERR_SIZE,
+ * before any HIP call.  Waits for the stream. */
+int m3g_rnemd_init(const m3g_rnemd_params* params, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets,
+                   const double* host_lattices, const uint8_t* host_active, void* state, size_t state_bytes, void* stream);
+/* state: of m3g_rnemd_init; dyn_state: of m3g_dyn_init over the same batch; pos [N,3] fp64 DEVICE, unwrapped (the integrator's own);
+ * params: those of m3g_rnemd_init (n_swaps may differ from call to call).  do_swap / do_sample: exchange, accumulate the profile, or
+ * both (neither: nothing is launched).  TWO launches whatever N, S, n_slabs and n_swaps, no atomics, no allocation, copy or wait:
+ * capture-safe. */
+int m3g_rnemd_exchange(const m3g_rnemd_params* params, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes,
+                       void* dyn_state, size_t dyn_bytes, const double* pos, int32_t do_swap, int32_t do_sample, void* stream);
+/* To HOST memory, every output may be NULL: n_calls, n_exchanged (int64 [S]), transferred (fp64 [S]), n_samples (int64 [S]),
+ * last_pairs [S, n_swaps, 2] (int32: the rows, relative to the structure, exchanged by the last swapping call at params->n_swaps,
+ * slab-0 row first, -1 where pair p was not exchanged), slab count [S, n_slabs] (int64) and sums [S, n_slabs, 5] (fp64).  Waits for
+ * the stream. */
+int m3g_rnemd_read(const m3g_rnemd_params* params, int64_t n_atoms, int64_t n_structs, const void* state, size_t state_bytes,
+                   int64_t* host_n_calls, int64_t* host_n_exchanged, double* host_transferred, int64_t* host_n_samples,
+                   int32_t* host_last_pairs, int64_t* host_count, double* host_sums, void* stream);
+
 /* ---- trajectory observables: RDF, MSD and VACF accumulated on the device (csrc/m3g_trajectory.hip) ---------------------------------
  * Fed one frame per m3g_traj_sample (from the MD loop, or any frames): per structure and species pair (a <= b) the INTEGER histogram
  * of minimum-image pair distances below r_max in rdf_bins bins (unordered pairs i < j; bin = (int)(r rdf_bins / r_max) taken only
@@ -1240,7 +1292,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     additive, same version: m3g_pimd_state_bytes / _state_view / _init / _step / _read: path-integral MD,
                              *     ring polymers under PILE-L, a fourth MD family;
                              *     additive, same version: m3g_ti_state_bytes / _state_view / _init / _path / _step / _read: thermodynamic
-                             *     integration to an Einstein crystal under centre-of-mass-conserving Langevin dynamics, a fifth MD family */
+                             *     integration to an Einstein crystal under centre-of-mass-conserving Langevin dynamics, a fifth MD family;
+                             *     additive, same version: m3g_rnemd_state_bytes / _init / _exchange / _read (reverse non-equilibrium MD
+                             *     over an m3g_dyn_* batch: imposed heat or momentum flux, slab profiles) */
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,11 @@ class M3GTiParams(C.Structure):   # m3g_ti_params
     _fields_ = [("schedule", C.c_int32), ("reserved", C.c_int32), ("dt", C.c_double), ("friction", C.c_double)]
 
 
+class M3GRnemdParams(C.Structure):   # m3g_rnemd_params
+    _fields_ = [("kind", C.c_int32), ("axis", C.c_int32), ("flow_axis", C.c_int32), ("n_slabs", C.c_int32), ("n_swaps", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 DYN_NVE, DYN_NVT_BERENDSEN, DYN_NVT_LANGEVIN, DYN_NPT_BERENDSEN = range(4)   # M3G_DYN_* ensembles
 NHC_NVT, NHC_NPT_MTK, NHC_MAX_CHAIN, NHC_OBS = 0, 1, 8, 6                   # M3G_NHC_* ensembles, M3G_NHC_MAX_CHAIN, M3G_NHC_OBS
 MTK_CELL_FULL, MTK_CELL_ORTHORHOMBIC, MTK_OBS = 0, 1, 12                    # M3G_MTK_CELL_* masks, M3G_MTK_OBS
@@ -109,6 +114,7 @@ PIMD_NONE, PIMD_PILE_L, PIMD_MAX_BEADS, PIMD_OBS = 0, 1, 64, 8               # M
 TI_LINEAR, TI_SMOOTH, TI_OBS = 0, 1, 8                                      # M3G_TI_* schedules, M3G_TI_OBS
 DYN_STARTED, DYN_ERROR = 1, 2                                               # M3G_DYN_* flag bits
 MC_NO_PAIR, MC_PENDING, MC_ERR_ORDER = 1, 2, 4                              # M3G_MC_* flag bits
+RNEMD_HEAT, RNEMD_MOMENTUM, RNEMD_MAX_SWAPS, RNEMD_MAX_SLABS = 0, 1, 8, 64   # M3G_RNEMD_* kinds, M3G_RNEMD_MAX_SWAPS, M3G_RNEMD_MAX_SLABS
 NEB_ROWS = 5                                                                 # M3G_NEB_ROWS
 PH_MAX_MULTIPLICITY = 27                                                     # M3G_PH_MAX_MULTIPLICITY
 EIGH_MAX_N, EIGH_MAX_SWEEPS = 64, 30                                         # M3G_EIGH_MAX_N, M3G_EIGH_MAX_SWEEPS
@@ -289,6 +295,13 @@ SYMBOLS = {
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "m3g_mc_read": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_rnemd_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "m3g_rnemd_init": (C.c_int, [C.POINTER(M3GRnemdParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
+    "m3g_rnemd_exchange": (C.c_int, [C.POINTER(M3GRnemdParams), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "m3g_rnemd_read": (C.c_int, [C.POINTER(M3GRnemdParams), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_traj_state_bytes": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(C.c_size_t)]),
     "m3g_traj_init": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(M3GTrajParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p]),
