@@ -1018,6 +1018,68 @@ int m3g_traj_read(const m3g_traj_sizes* sizes, const void* state, size_t state_b
 int m3g_traj_frame(const m3g_traj_sizes* sizes, const void* state, size_t state_bytes, int32_t lag, double* host_pos, double* host_vel,
                    void* stream);
 
+/* ---- normal-mode analysis of MD: the trajectory projected on harmonic eigenvectors (csrc/m3g_nma.hip) -------------------------------
+ * Normal-mode decomposition (Ladd, Moran and Hoover, Phys. Rev. B 34, 5058 (1986); McGaughey and Kaviany, Phys. Rev. B 69, 094303
+ * (2004); the spectral energy density of Thomas et al., Phys. Rev. B 81, 081411 (2010)), fed one frame per m3g_nma_sample, as the
+ * trajectory observables above are.  Structure s: a unit cell of n_u atoms with masses m_b, repeated in a diagonal MD supercell
+ * (c1, c2, c3) in the order of the phonon family below: atom j = l n_u + b, l = (l1 c2 + l2) c3 + l3, N_c = c1 c2 c3 cells, N_s = N_c n_u
+ * atoms.  Equilibrium site r0_j = f_j L (L the unit cell, rows = lattice vectors) with f_j = f_b + (l1, l2, l3) the fractional
+ * coordinate in unit-cell units.  Q_s q-points in fractional coordinates of the unit cell's reciprocal lattice, each with an
+ * eigenvector matrix E[q] [3 n_u, 3 n_u] complex128 (interleaved re, im; row-major): column nu is the mode, rows 3b .. 3b + 2 belong
+ * to atom b -- what m3g_eigh_batched returns for a dynamical matrix of m3g_ph_dynmat (phonopy's convention: the phase on atomic
+ * positions).  Mode velocity and mode displacement:
+ *   Qdot[q,nu] = N_c^(-1/2) sum_j sqrt(m_j) exp(-2 pi i q.f_j) sum_a conj(E[q][3b+a, nu]) v[j,a]
+ *   Q   [q,nu] = the same with u_j = r_j - r0_j - (mass-weighted mean of r - r0 over the structure) in place of v
+ * v: `vel` as given, or with `forces` vel + kick kappa F / m (the completion of m3g_traj_sample); with remove_com minus the
+ * structure's mass-weighted mean velocity.  Positions are the integrator's unwrapped ones.
+ * Two stages, no 3 N_s x 3 N_s projector: W[q,b,a] = N_c^(-1/2) sqrt(m_b) sum_l phase v (per thread the cells l = g, g + G', ... in
+ * order with G' = floor(256 / 3 n_u) groups, then the groups in order; the same for u), then Qdot = E[q]^H W with E[q] in LDS (rows in
+ * order).  The phase table exp(-2 pi i q.f_j), Q_s N_s 16 bytes per structure, is built once by the init call on the host in fp64
+ * from x = (q0 f0 + q1 f1) + q2 f2 reduced by its nearest integer.
+ * Accumulators per structure: n_samples; kinetic_sum = sum_t sum_j m_j |v_j|^2 (from the velocities of stage 1, not from the modes:
+ * with unitary E and all commensurate q it equals the sum over modes of qdot2_sum); per mode qdot2_sum = sum_t |Qdot|^2 and q2_sum =
+ * sum_t |Q|^2; a ring of the last n_lags Qdot; acf[mode, lag] = sum_t conj(Qdot(t - lag)) Qdot(t); lag_count[lag]; flags.
+ * A sample with a non-finite position, velocity or force in a structure sets M3G_NMA_NONFINITE in that structure's flags and is not
+ * accumulated; a flagged structure accumulates nothing more.  The others are unaffected.
+ * No atomics, fixed-order sums over the structure's own rows: every number is bitwise the same alone or in any batch. */
+typedef struct {
+  int64_t n_atoms;       /* N = sum_s N_s */
+  int64_t n_structs;     /* S */
+  int64_t n_unit_atoms;  /* U = sum_s n_u */
+  int64_t n_qpoints;     /* sum_s Q_s (every structure has at least one) */
+  int64_t n_modes;       /* sum_s Q_s 3 n_u */
+  int64_t n_eig;         /* sum_s Q_s (3 n_u)^2: complex elements of the eigenvector matrices */
+  int64_t n_phase;       /* sum_s Q_s N_s: complex elements of the phase table */
+  int32_t max_n;         /* max_s 3 n_u, 3 .. M3G_NMA_MAX_N */
+  int32_t n_lags;        /* 0 (no autocorrelation) .. M3G_NMA_MAX_LAGS: ring and acf of n_lags * n_modes * 16 bytes each */
+} m3g_nma_sizes;
+typedef struct { int32_t remove_com, reserved; } m3g_nma_params;
+#define M3G_NMA_MAX_N 64         /* 3 n_u at most: E[q] is 64 KiB of LDS there (M3G_EIGH_MAX_N) */
+#define M3G_NMA_MAX_LAGS 4096
+#define M3G_NMA_NONFINITE 1      /* flag: a sample of the structure held a non-finite position, velocity or force */
+/* Sizes outside their limits or inconsistent among themselves -> M3G_ERR_VALUE. */
+int m3g_nma_state_bytes(const m3g_nma_sizes* sizes, size_t* bytes);
+/* HOST: host_unit_offsets [S+1] and host_q_offsets [S+1] (int64, from 0, strictly increasing), host_supercells [S,3] (int32, >= 1),
+ * host_lattices [S,3,3] fp64 (unit cells), host_frac [U,3] fp64 (f_b), host_masses [U] fp64 (amu, > 0), host_qpoints [sum Q_s, 3] fp64,
+ * host_eigenvectors [n_eig] complex128 (structure after structure, q after q).  Everything is checked on the host before any HIP
+ * call (sizes that do not follow from the offsets and supercells, non-finite values, remove_com not 0 / 1) -> M3G_ERR_VALUE; a short
+ * state buffer -> M3G_ERR_SIZE.  Uploads the tables and zeroes the accumulators.  Waits for the stream. */
+int m3g_nma_init(const m3g_nma_sizes* sizes, const m3g_nma_params* params, const int64_t* host_unit_offsets, const int32_t* host_supercells,
+                 const double* host_lattices, const double* host_frac, const double* host_masses, const int64_t* host_q_offsets,
+                 const double* host_qpoints, const double* host_eigenvectors, void* state, size_t state_bytes, void* stream);
+/* One sample: pos, vel [N,3] fp64, forces [N,3] f32 or NULL, all DEVICE; kick finite.  THREE launches whatever the batch, the
+ * q-points and the lags; the ring positions and the counts live in the state buffer: no allocation, copy or wait, capture-safe. */
+int m3g_nma_sample(const m3g_nma_sizes* sizes, const m3g_nma_params* params, void* state, size_t state_bytes, const double* pos,
+                   const double* vel, const float* forces, double kick, void* stream);
+/* The accumulators to HOST memory; every output may be NULL: n_samples [S] int64, kinetic_sum [S] fp64, qdot2_sum and q2_sum [n_modes]
+ * fp64, acf [n_modes, n_lags] complex128, lag_count [S, n_lags] int64, flags [S] int32 (M3G_NMA_*).  Modes run structure after
+ * structure, q after q, nu fastest.  Waits for the stream. */
+int m3g_nma_read(const m3g_nma_sizes* sizes, const void* state, size_t state_bytes, int64_t* host_n_samples, double* host_kinetic_sum,
+                 double* host_qdot2_sum, double* host_q2_sum, double* host_acf, int64_t* host_lag_count, int32_t* host_flags, void* stream);
+/* Qdot and Q [n_modes] complex128 of the last sample every structure accumulated (zeros before its first) to HOST memory.  Waits for
+ * the stream. */
+int m3g_nma_frame(const m3g_nma_sizes* sizes, const void* state, size_t state_bytes, double* host_qdot, double* host_q, void* stream);
+
 /* ---- batched nudged elastic band: climbing-image NEB force projection (csrc/m3g_neb.hip) ----------------------------------------
  * Replaces ASE's NEB.get_forces (NEB(images, k, climb, method="improvedtangent"), the forces an ASE optimiser drives on the host, one
  * image at a time) for a whole batch of bands.  A band has M >= 3 images: fixed endpoints 0 and M-1 (given once, to m3g_neb_init) and

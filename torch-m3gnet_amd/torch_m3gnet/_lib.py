@@ -134,6 +134,18 @@ class M3GTrajParams(C.Structure):   # m3g_traj_params
 TRAJ_RDF_RANGE, TRAJ_MAX_SPECIES, TRAJ_MAX_BINS, TRAJ_MAX_LAGS = 1, 8, 4096, 4096   # M3G_TRAJ_RDF_RANGE and the limits of m3g_traj_sizes
 
 
+class M3GNmaSizes(C.Structure):   # m3g_nma_sizes
+    _fields_ = [("n_atoms", C.c_int64), ("n_structs", C.c_int64), ("n_unit_atoms", C.c_int64), ("n_qpoints", C.c_int64),
+                ("n_modes", C.c_int64), ("n_eig", C.c_int64), ("n_phase", C.c_int64), ("max_n", C.c_int32), ("n_lags", C.c_int32)]
+
+
+class M3GNmaParams(C.Structure):   # m3g_nma_params
+    _fields_ = [("remove_com", C.c_int32), ("reserved", C.c_int32)]
+
+
+NMA_MAX_N, NMA_MAX_LAGS, NMA_NONFINITE = 64, 4096, 1                          # M3G_NMA_MAX_N, M3G_NMA_MAX_LAGS, M3G_NMA_NONFINITE
+
+
 class M3GPhSizes(C.Structure):   # m3g_ph_sizes
     _fields_ = [("n_structs", C.c_int64), ("n_unit_atoms", C.c_int64), ("n_super_atoms", C.c_int64), ("n_pairs", C.c_int64)]
 
@@ -310,6 +322,14 @@ SYMBOLS = {
     "m3g_traj_read": (C.c_int, [C.POINTER(M3GTrajSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_traj_frame": (C.c_int, [C.POINTER(M3GTrajSizes), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_nma_state_bytes": (C.c_int, [C.POINTER(M3GNmaSizes), C.POINTER(C.c_size_t)]),
+    "m3g_nma_init": (C.c_int, [C.POINTER(M3GNmaSizes), C.POINTER(M3GNmaParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "m3g_nma_sample": (C.c_int, [C.POINTER(M3GNmaSizes), C.POINTER(M3GNmaParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_double, C.c_void_p]),
+    "m3g_nma_read": (C.c_int, [C.POINTER(M3GNmaSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_nma_frame": (C.c_int, [C.POINTER(M3GNmaSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_neb_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     "m3g_neb_init": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -300,6 +300,8 @@ class PhononResult:
         self.n_atoms, self.supercell = n, tuple(int(k) for k in state.supercells[s])
         self.lattice = state.lattices[s].copy()
         self.masses = state.masses[state.unit_offsets[s]:state.unit_offsets[s + 1]].copy()
+        self.positions = state.positions[state.unit_offsets[s]:state.unit_offsets[s + 1]].copy()
+        self.atomic_numbers = None   # (set by `Phonons.run`, which knows them: `NormalModeAnalysis` builds its MD supercell from them)
         self.force_constants = phi.reshape(n, ns, 3, 3)
         self.residual_fmax = residual_fmax
         self.error = nonfinite != 0
@@ -474,6 +476,9 @@ class Phonons(Driver):
         res_f = [float(norms[int(st.row_offsets[s]):int(st.row_offsets[s] + st.super_sizes[s])].max()) for s in range(st.S)]
         phi, sums, bad = st.phi.cpu().numpy(), st.sums.cpu().numpy(), st.nonfinite.cpu().numpy()
         self.forces = forces   # (the displaced batch's forces, kept for inspection)
-        return [PhononResult(st, s, self.asr, self.max_qpoints, self.cutoff_frequency, res_f[s],
-                             phi[int(st.pair_offsets[s]):int(st.pair_offsets[s + 1])], sums[int(st.unit_offsets[s]):int(st.unit_offsets[s + 1])],
-                             int(bad[s]), self.eigensolver) for s in range(st.S)]
+        res = [PhononResult(st, s, self.asr, self.max_qpoints, self.cutoff_frequency, res_f[s],
+                            phi[int(st.pair_offsets[s]):int(st.pair_offsets[s + 1])], sums[int(st.unit_offsets[s]):int(st.unit_offsets[s + 1])],
+                            int(bad[s]), self.eigensolver) for s in range(st.S)]
+        for r, a in zip(res, z):
+            r.atomic_numbers = a.copy()
+        return res
