@@ -964,6 +964,83 @@ int m3g_rnemd_read(const m3g_rnemd_params* params, int64_t n_atoms, int64_t n_st
                    int64_t* host_n_calls, int64_t* host_n_exchanged, double* host_transferred, int64_t* host_n_samples,
                    int32_t* host_last_pairs, int64_t* host_count, double* host_sums, void* stream);
 
+/* ---- batched collective-variable biasing: metadynamics, restraints and walls (csrc/m3g_meta.hip) -----------------------------------
+ * A bias layer over any MD family: one m3g_meta_bias takes the integrator's unwrapped pos [N,3] (fp64) and the engine's forces [N,3]
+ * (f32) and writes forces_out [N,3] (f32, may be `forces` itself), which goes to m3g_dyn_step / m3g_nhc_step unchanged.  The S
+ * structures (offsets [S+1] as m3g_dyn_init) are cut into G walker groups by group_offsets [G+1] (structure indices, 0 .. S, strictly
+ * increasing; a group of one walker is legal); the walkers of a group share one hill list of at most max_hills hills.
+ * Collective variables: n_cv = 1 .. M3G_META_MAX_CV per call, one set for the whole batch.  membership [n_cv, N] uint8: 0 none, 1 = A,
+ *   2 = B, 3 = both; weights [N] fp64 >= 0 (the masses, usually); c_X = sum_X w x / sum_X w over UNWRAPPED positions, no minimum image.
+ *   M3G_CV_DISTANCE      s = |c_A - c_B|; at distance 0 the gradient is zero.
+ *   M3G_CV_PROJECTION    s = (c_A - c_B - origin_s) . direction, direction a unit vector (|n|^2 within 1e-12 of 1), origin [3] per
+ *                        structure and CV; an empty B means c_B = 0.
+ *   M3G_CV_COORDINATION  s = sum_{i in A} sum_{j in B, j != i} f(r_ij), sigma(r) = 1 / (1 + (r^2 / r0^2)^power), power = 1 .. 6 by
+ *                        repeated multiplication, f = (sigma(r) - sigma(r_cut)) / (1 - sigma(r_cut)) for r < r_cut and 0 from r_cut
+ *                        on.  r_ij under the minimum image of the FIXED cell given at init (rint of the fractional difference,
+ *                        fp64: exact below half the smallest perpendicular width of the cell, which r_cut must not exceed).
+ *                        O(|A| |B|) per call.  NVE / NVT only: the cells never change.
+ * Bias of structure s: V = V_hills + sum_k [ kappa_sk / 2 (s_k - centre_sk)^2 + walls ], walls [S, n_cv, 4] = (lower, kappa_lower,
+ *   upper, kappa_upper): kappa_lower / 2 (s - lower)^2 where s < lower, kappa_upper / 2 (s - upper)^2 where s > upper; a kappa of 0
+ *   switches its term off.  V_hills(s) = sum_h w_h exp(-1/2 sum_k (s_k - c_hk)^2 / sigma_gk^2) over the hills of the structure's group.
+ * Deposits (calls with deposit != 0): every walker appends a hill at its own s of height height_g exp(-V_hills(s) inv_kdt_g) --
+ *   inv_kdt = 1 / (kB DeltaT): well-tempered; 0: plain metadynamics -- with V_hills over the list as it stood BEFORE the call, as are
+ *   the forces and the obs row of that call.  Walker r of a group of R writes slot c R + r, c the deposits it has made.  A group whose
+ *   list cannot take R more hills sets the sticky M3G_META_FULL on its walkers, deposits nothing and goes on.
+ * A walker with a non-finite CV (or a non-finite position in any of its groups' rows) gets M3G_META_ERROR (sticky), no bias force
+ *   in that call -- forces_out = forces -- an obs row of its CVs and zeros, and on a deposit appends a hill of height 0 at centre 0.
+ * obs [S, M3G_META_OBS] fp64 or NULL: s_0, s_1, V, V_hills, V_restraints + walls, dV/ds_0, dV/ds_1, the height deposited (0: none).
+ * All arithmetic is fp64, no product is contracted with a sum; the only f32 operation is forces_out = (float)(forces - sum_k dV/ds_k
+ *   ds_k/dx).  Rows that belong to no group of any CV pass through bitwise.  Sums: rows over a chunk of 256 in a fixed tree, chunks
+ *   lane-strided over 64 lanes in chunk order, then a butterfly; COORDINATION rows walk their partners in row order; hills
+ *   lane-strided in list order, then the butterfly.  No atomics: a group's results are bitwise the same alone or in any batch. */
+#define M3G_META_MAX_CV 2
+#define M3G_META_OBS 8
+#define M3G_CV_DISTANCE 0
+#define M3G_CV_PROJECTION 1
+#define M3G_CV_COORDINATION 2
+#define M3G_META_ERROR 1
+#define M3G_META_FULL 2
+typedef struct {
+  int32_t n_cv, reserved;
+  int64_t max_hills;                       /* per group, as given to m3g_meta_state_bytes */
+  int32_t kind[M3G_META_MAX_CV];           /* M3G_CV_* */
+  int32_t power[M3G_META_MAX_CV];          /* COORDINATION */
+  double r0[M3G_META_MAX_CV], r_cut[M3G_META_MAX_CV];   /* COORDINATION */
+  double direction[M3G_META_MAX_CV][3];    /* PROJECTION */
+} m3g_meta_params;                         /* 112 bytes */
+/* Null `bytes`, bad sizes (1 <= n_groups <= n_structs <= n_atoms), n_cv outside 1 .. 2, max_hills < 0 -> M3G_ERR_VALUE. */
+int m3g_meta_state_bytes(int64_t n_atoms, int64_t n_structs, int64_t n_groups, int32_t n_cv, int64_t max_hills, size_t* bytes);
+/* The byte offset, within the state, of the COORDINATION gradients [n_cv, N, 3] fp64 (d s_k / d x_i as the last m3g_meta_bias left
+ * them; only the rows with membership != 0 of a COORDINATION CV are ever written). */
+int m3g_meta_state_view(int64_t n_atoms, int64_t n_structs, int64_t n_groups, int32_t n_cv, int64_t max_hills, size_t* gradient_offset);
+/* All arrays HOST: offsets [S+1], group_offsets [G+1] int64; lattices [S,3,3] fp64 (rows = lattice vectors); membership [n_cv,N] uint8;
+ * weights [N]; origins [S,n_cv,3], centres [S,n_cv], kappas [S,n_cv], walls [S,n_cv,4] (each may be NULL: zeros); sigmas [G,n_cv],
+ * heights [G], inv_kdt [G].  Validated before any HIP call, the reason in m3g_last_error: null pointers, bad sizes, offsets or
+ * lattices, an unknown kind, n_cv outside 1 .. 2, a direction that is no unit vector, power outside 1 .. 6, r0 or r_cut not finite
+ * and > 0, r_cut above half the smallest perpendicular width of any cell, membership > 3, an empty group A (B too for DISTANCE and
+ * COORDINATION) in any structure, a weight that is negative or a group of a centre CV whose total weight is not > 0, sigma <= 0, a
+ * negative kappa, height or inv_kdt, a restraint or wall that is on without a finite position -> M3G_ERR_VALUE; a short buffer ->
+ * M3G_ERR_SIZE.  The hill lists start empty.  Waits for the stream. */
+int m3g_meta_init(const m3g_meta_params* params, int64_t n_atoms, int64_t n_structs, int64_t n_groups, const int64_t* host_offsets,
+                  const int64_t* host_group_offsets, const double* host_lattices, const uint8_t* host_membership, const double* host_weights,
+                  const double* host_origins, const double* host_centres, const double* host_kappas, const double* host_walls,
+                  const double* host_sigmas, const double* host_heights, const double* host_inv_kdt, void* state, size_t state_bytes,
+                  void* stream);
+/* params: those of m3g_meta_init.  pos, forces, forces_out, obs: DEVICE.  THREE launches whatever N, S, G and the number of hills, no
+ * atomics, no allocation, copy or wait: capture-safe. */
+int m3g_meta_bias(const m3g_meta_params* params, int64_t n_atoms, int64_t n_structs, int64_t n_groups, void* state, size_t state_bytes,
+                  const double* pos, const float* forces, float* forces_out, int32_t deposit, double* obs, void* stream);
+/* Replaces the hill lists (a restart): HOST group_offsets [G+1] (those of init), counts [G] (each a multiple of the group's walkers,
+ * <= max_hills), centres [G, max_hills, n_cv], heights [G, max_hills] (finite below the count).  Waits for the stream. */
+int m3g_meta_set_hills(const m3g_meta_params* params, int64_t n_atoms, int64_t n_structs, int64_t n_groups, void* state, size_t state_bytes,
+                       const int64_t* host_group_offsets, const int64_t* host_counts, const double* host_centres, const double* host_heights,
+                       void* stream);
+/* To HOST memory, every output may be NULL: flags [S] (int32, M3G_META_*), deposits made [S] and hill counts [G] (int64), centres
+ * [G, max_hills, n_cv] and heights [G, max_hills] (fp64; beyond the count zeros, or what m3g_meta_set_hills was given).  Waits for the stream. */
+int m3g_meta_read(const m3g_meta_params* params, int64_t n_atoms, int64_t n_structs, int64_t n_groups, const void* state, size_t state_bytes,
+                  int32_t* host_flags, int64_t* host_deposits, int64_t* host_hill_counts, double* host_centres, double* host_heights,
+                  void* stream);
+
 /* ---- trajectory observables: RDF, MSD and VACF accumulated on the device (csrc/m3g_trajectory.hip) ---------------------------------
  * Fed one frame per m3g_traj_sample (from the MD loop, or any frames): per structure and species pair (a <= b) the INTEGER histogram
  * of minimum-image pair distances below r_max in rdf_bins bins (unordered pairs i < j; bin = (int)(r rdf_bins / r_max) taken only
@@ -1356,7 +1433,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     additive, same version: m3g_ti_state_bytes / _state_view / _init / _path / _step / _read: thermodynamic
                              *     integration to an Einstein crystal under centre-of-mass-conserving Langevin dynamics, a fifth MD family;
                              *     additive, same version: m3g_rnemd_state_bytes / _init / _exchange / _read (reverse non-equilibrium MD
-                             *     over an m3g_dyn_* batch: imposed heat or momentum flux, slab profiles) */
+                             *     over an m3g_dyn_* batch: imposed heat or momentum flux, slab profiles);
+                             *     additive, same version: m3g_meta_state_bytes / _state_view / _init / _bias / _set_hills / _read
+                             *     (collective-variable biasing over any MD family: metadynamics, restraints, walls) */
 
 #ifdef __cplusplus
 }

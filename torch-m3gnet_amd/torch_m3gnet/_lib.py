@@ -107,6 +107,11 @@ class M3GRnemdParams(C.Structure):   # m3g_rnemd_params
                 ("reserved", C.c_int32)]
 
 
+class M3GMetaParams(C.Structure):   # m3g_meta_params
+    _fields_ = [("n_cv", C.c_int32), ("reserved", C.c_int32), ("max_hills", C.c_int64), ("kind", C.c_int32 * 2), ("power", C.c_int32 * 2),
+                ("r0", C.c_double * 2), ("r_cut", C.c_double * 2), ("direction", (C.c_double * 3) * 2)]
+
+
 DYN_NVE, DYN_NVT_BERENDSEN, DYN_NVT_LANGEVIN, DYN_NPT_BERENDSEN = range(4)   # M3G_DYN_* ensembles
 NHC_NVT, NHC_NPT_MTK, NHC_MAX_CHAIN, NHC_OBS = 0, 1, 8, 6                   # M3G_NHC_* ensembles, M3G_NHC_MAX_CHAIN, M3G_NHC_OBS
 MTK_CELL_FULL, MTK_CELL_ORTHORHOMBIC, MTK_OBS = 0, 1, 12                    # M3G_MTK_CELL_* masks, M3G_MTK_OBS
@@ -115,7 +120,9 @@ TI_LINEAR, TI_SMOOTH, TI_OBS = 0, 1, 8                                      # M3
 DYN_STARTED, DYN_ERROR = 1, 2                                               # M3G_DYN_* flag bits
 MC_NO_PAIR, MC_PENDING, MC_ERR_ORDER = 1, 2, 4                              # M3G_MC_* flag bits
 RNEMD_HEAT, RNEMD_MOMENTUM, RNEMD_MAX_SWAPS, RNEMD_MAX_SLABS = 0, 1, 8, 64   # M3G_RNEMD_* kinds, M3G_RNEMD_MAX_SWAPS, M3G_RNEMD_MAX_SLABS
-NEB_ROWS = 5                                                                 # M3G_NEB_ROWS
+META_MAX_CV, META_OBS, META_ERROR, META_FULL = 2, 8, 1, 2                    # M3G_META_MAX_CV, M3G_META_OBS, M3G_META_* flag bits
+CV_DISTANCE, CV_PROJECTION, CV_COORDINATION = range(3)                       # M3G_CV_* kinds
+NEB_ROWS = 5                                                              # M3G_NEB_ROWS
 PH_MAX_MULTIPLICITY = 27                                                     # M3G_PH_MAX_MULTIPLICITY
 EIGH_MAX_N, EIGH_MAX_SWEEPS = 64, 30                                         # M3G_EIGH_MAX_N, M3G_EIGH_MAX_SWEEPS
 EIGH_SWEEPS_MASK, EIGH_NONFINITE, EIGH_NOT_CONVERGED = 0xff, 0x100, 0x200    # M3G_EIGH_* info bits
@@ -314,6 +321,17 @@ SYMBOLS = {
                                      C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "m3g_rnemd_read": (C.c_int, [C.POINTER(M3GRnemdParams), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_meta_state_bytes": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_size_t)]),
+    "m3g_meta_state_view": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_size_t)]),
+    "m3g_meta_init": (C.c_int, [C.POINTER(M3GMetaParams), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_size_t, C.c_void_p]),
+    "m3g_meta_bias": (C.c_int, [C.POINTER(M3GMetaParams), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "m3g_meta_set_hills": (C.c_int, [C.POINTER(M3GMetaParams), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_meta_read": (C.c_int, [C.POINTER(M3GMetaParams), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_traj_state_bytes": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(C.c_size_t)]),
     "m3g_traj_init": (C.c_int, [C.POINTER(M3GTrajSizes), C.POINTER(M3GTrajParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p]),
