@@ -368,6 +368,7 @@ static const OptionRow kOptions[] = {
     {"small_tiles_fwd", &Options::small_tiles_fwd, 0, INT_MAX, "small_tiles_fwd must be >= 0", nullptr},   // the forward kernel's threshold alone (set after small_tiles)
     {"dp1_by_dst", &Options::dp1_by_dst, 0, 1, nullptr, nullptr},   // 0: dp1 rows of the exact-fp32 fused path in edge order (A/B tests; bit-identical either way)
     {"split_node_tiles", &Options::split_node_tiles, 0, INT_MAX, "split_node_tiles must be >= 0", nullptr},
+    {"species_tables", &Options::species_tables, 0, 1, nullptr, nullptr},   // 0: block 0's node kernel in every step (A/B tests; bit-identical either way)
     {"fuse_node_tb", &Options::fuse_node_tb, 0, 1, nullptr, nullptr},   // 0: three-body reverse and node reverse as two launches (A/B tests; bit-identical either way)
     {"debug_node_tb_polls", &Options::debug_node_tb_polls, INT_MIN, INT_MAX, nullptr, nullptr},   // test hook: bound (k > 0) or force (k < 0) the time-out of k_node_tb_reverse's wait
     {"split_tail", &Options::split_tail, 0, 2, "split_tail must be 0 (never), 1 (a single left-over tile) or 2 (one or two)", nullptr},   // 0: every tile whole (A/B tests)
@@ -499,6 +500,7 @@ extern "C" int m3g_plan_commit(m3g_plan* plan) {
   if (!plan->d_weights) M3G_HIP_CHECK(hipMalloc((void**)&plan->d_weights, wl.total * sizeof(float)));
   M3G_HIP_CHECK(hipMemcpy(plan->d_weights, blob.data(), wl.total * sizeof(float), hipMemcpyHostToDevice));
   { int rc = pack_mfma_images(plan); if (rc) return rc; }
+  { int rc = build_species_tables(plan); if (rc) return rc; }   // from what was just uploaded: changed weights never meet stale tables
   plan->committed = true;
   return M3G_OK;
 }
@@ -567,7 +569,9 @@ int Step::enqueue_forward() const {
   {
     M3G_STAGE(ST_GEOM);
     // small systems: the geometry stage and block 0's node tables (independent of each other) as two roles of one launch
-    if (p.geom_with_node_pre) launch_geometry_node_pre(plan, c, t, w, io->pos, io->lattice, io->edge_cell_shift, io->atom_types, W + wl.emb, s);
+    // ... or, with block 0's rows taken from the per-species tables, the geometry stage and that copy, at any size
+    if (p.block0 == kBlock0ExpandBesideGeom) launch_geometry_species(plan, c, t, w, io->pos, io->lattice, io->edge_cell_shift, io->atom_types, s);
+    else if (p.block0 == kBlock0Kernel && p.geom_with_node_pre) launch_geometry_node_pre(plan, c, t, w, io->pos, io->lattice, io->edge_cell_shift, io->atom_types, W + wl.emb, s);
     else launch_geometry(c, t, io->pos, io->lattice, io->edge_cell_shift, w, s);
   }
   {
@@ -583,7 +587,9 @@ int Step::enqueue_forward() const {
     {
       M3G_STAGE(ST_NODE_PRE);
       // MFMA path: block b > 0 forms x^b = x^(b-1) + per-centre message sums of block b-1 while loading it
-      if (mfma && b == 0 && p.geom_with_node_pre) { /* formed beside the geometry stage */ }
+      if (mfma && b == 0 && p.block0 == kBlock0ExpandBesideGeom) { /* copied beside the geometry stage */ }
+      else if (mfma && b == 0 && p.block0 == kBlock0ExpandAlone) launch_species_expand(plan, c, t, w, io->atom_types, s);
+      else if (mfma && b == 0 && p.geom_with_node_pre) { /* formed beside the geometry stage */ }
       else if (mfma) launch_node_pre_mfma(plan, p.node_split, c, t, w, b, b > 0 ? w.x[b - 1] : nullptr, w.x[b], w.v[b], w.TAb[b], w.TBb[b],
                                           b == 0 ? io->atom_types : nullptr, W + wl.emb, s);
       else launch_node_pre(c, W, wl.blk[b], t, w, nullptr, w.x[b], w.v[b], w.TA, w.TB, s);
@@ -592,7 +598,8 @@ int Step::enqueue_forward() const {
     M3G_STAGE(ST_EDGE_FWD);
     if (mfma) {
       if (p.fwd_split) launch_edge_fwd_split(plan, p, c, t, w, b, s);
-      else launch_edge_block_mfma(plan, p, c, t, w, b, s);
+      // (the last block's output image has one reader on the exact-fp32 path with both layers saved: the optional edge_attr output)
+      else launch_edge_block_mfma(plan, p, c, t, w, b, s, /*e_out_read=*/b + 1 < c.B || io->edge_attr != nullptr);
       (void)ST_NODE_SUM;   // the per-centre sums are consumed by the next node_pre / the readout
     } else {
       launch_edge_block(c, W, wl.blk[b], t, w, b, w.x[b], w.x[b + 1], s);   // x^(b+1) = x^b + per-centre message sums

@@ -101,7 +101,10 @@ __device__ __forceinline__ void mlp_forward_mfma(const float* lds, const MfmaMlp
 
 // FIRST: block 0 forms its input e0 = SiLU(W_adj h) (nn/featurizer.py:128-132) from the radial basis instead of reading
 // an embedded-edge image that a separate kernel would have to write (256 B/edge) first
-template <int TBS, bool ST = false, bool FIRST = false, int PREC = kPrecBf16x3, int SAVE = 0>
+// STORE_E = false: the block's output image e_out goes unstored -- the LAST block of a step whose reverse kernels start from the saved
+// activations (SAVE == 2: k_edge_rev_f32 / k_edge_rev_split read no edge-feature image) and whose caller did not ask for edge_attr,
+// the image's only other reader (256 B per edge)
+template <int TBS, bool ST = false, bool FIRST = false, int PREC = kPrecBf16x3, int SAVE = 0, bool STORE_E = true>
 __global__ void __launch_bounds__(64 * fwd_waves<PREC>()) k_edge_block_mfma(FwdArgs a, MfmaFwdLayout L) {
   __shared__ __attribute__((aligned(16))) float lds[kFwdLdsFloats + 4];  // + tile-queue head
   int* q_head = reinterpret_cast<int*>(lds + kFwdLdsFloats);
@@ -165,7 +168,7 @@ __global__ void __launch_bounds__(64 * fwd_waves<PREC>()) k_edge_block_mfma(FwdA
     mlp_forward_mfma<ST, 2, PREC, SAVE>(lds, L.mlp[0], 0, a, ci, cj, hb, x, out, lv, st, p1_tile, p2_tile);  // edge update (nn/conv.py:68-75)
     static_for<4>([&]<int blk>() {
       x[blk] += out[blk];
-      *(f32x4*)(e_otile + blk * 256) = x[blk];
+      if constexpr (STORE_E) *(f32x4*)(e_otile + blk * 256) = x[blk];
     });
     st.template mark<6>();  // e2 residual + store
     mlp_forward_mfma<ST, 7, PREC, SAVE>(lds, L.mlp[1], 1, a, ci, cj, hb, x, out, lv, st, SAVE >= 1 ? p1_tile + kP1TileFloats : nullptr,
@@ -696,7 +699,9 @@ void launch_embed_edges_reverse_soa(const float* adj, const float* h, const floa
 
 // the persistent forward kernel.  p.fwd_save = 0 in an energy-only call: nothing is saved for a reverse pass that will not run (2 KB
 // per edge and block of stores)
-void launch_edge_block_mfma(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, hipStream_t s) {
+// e_out_read = false: nobody will read the image this block writes (see STORE_E)
+void launch_edge_block_mfma(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, hipStream_t s,
+                            bool e_out_read) {
   const int64_t tiles = tiles_for(t.E);
   const MfmaFwdLayout L = mfma_fwd_layout();
   const int prec = plan->opt.precision;
@@ -713,6 +718,7 @@ void launch_edge_block_mfma(const m3g_plan* plan, const StepPath& p, const Const
 #define M3G_FWD_BY_MODE(ST_, FIRST_)                                                               \
   if (prec == kPrecBf16x3) { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecBf16x3, 0); }                        \
   else if (prec == kPrecF16x3) { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecF16x3, 0); }                     \
+  else if (save == 2 && !ST_ && !e_out_read) { hipLaunchKernelGGL((k_edge_block_mfma<TBS, false, FIRST_, kPrecF32, 2, false>), grid, dim3(64 * fwd_waves<kPrecF32>()), 0, s, a, L); } \
   else if (save == 2) { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecF32, 2); }                                \
   else if (save == 1) { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecF32, 1); }                                \
   else { M3G_FWD_LAUNCH(ST_, FIRST_, kPrecF32, 0); }

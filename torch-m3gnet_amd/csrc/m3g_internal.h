@@ -162,6 +162,12 @@ MfmaRevF32Layout mfma_rev_f32_layout();
 // TA, 0 for TB, b_sigmoid1)
 constexpr int kNodeRowBlocks = 33;
 constexpr int kNodeImgFloats = kNodeRowBlocks * 16 * 64 + kNodeRowBlocks * 16;
+// per-species rows of block 0 (m3g_plan::d_species_tab, build_species_tables): four arrays of num_types rows one after the other,
+// x^0 [kDP] | v^0 [kCP] | TA^0 [4*kDP] | TB^0 [4*kDP], each with the row stride of its per-atom twin in Work
+constexpr int kSpeciesRowFloats = kDP + kCP + 2 * 4 * kDP;
+constexpr size_t species_tab_v(int num_types) { return (size_t)num_types * kDP; }
+constexpr size_t species_tab_ta(int num_types) { return (size_t)num_types * (kDP + kCP); }
+constexpr size_t species_tab_tb(int num_types) { return (size_t)num_types * (kDP + kCP + 4 * kDP); }
 // k_readout_mfma image (floats): exact-fp32 chain images (f32_chain_image) of the readout GatedMLP (nn/readout.py:39-58)
 // and its transposes, then the small vectors
 struct ReadoutImg {
@@ -197,6 +203,8 @@ struct m3g_plan {
   float* d_mfma_revf_h = nullptr;  // the same layout holding fp16 parts of the scaled weights (f16x3 mode)
   float* d_mfma_revf32 = nullptr;  // [num_blocks][MfmaRevF32Layout.total] (fused fp32 reverse kernel)
   float* d_node_img[m3g::kNumPrec] = {nullptr, nullptr, nullptr};   // [num_blocks][kNodeImgFloats]: node-table weights as MFMA A-operand images (k_node_pre_mfma)
+  float* d_species_tab[m3g::kNumPrec] = {nullptr, nullptr, nullptr};   // [num_types][kSpeciesRowFloats]: block 0's node rows per species, formed by
+                                                                       // k_node_pre_mfma at every commit from d_node_img, the embedding and w_scale_inv
   m3g::Options opt;           // every option of m3g_plan_set_option that shapes the step (m3g_step_path.h)
   float w_scale_inv = 1.f;       // f16x3 mode: 1 / (the power of two all chain-image weights were multiplied by), set by pack_mfma_images
   int device = -1;               // HIP device the plan's buffers live on (set by m3g_plan_commit)
@@ -438,6 +446,11 @@ void launch_node_pre_mfma(const m3g_plan* plan, bool split, const Consts& c, con
                           float* v, float* TA, float* TB, const int64_t* types, const float* emb, hipStream_t s);
 void launch_geometry_node_pre(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, const float* pos, const float* lattice,
                               const int32_t* shift, const int64_t* types, const float* emb, hipStream_t s);
+// block 0 from the plan's per-species tables (StepPath::block0), and the tables themselves (m3g_plan_commit, after pack_mfma_images)
+void launch_species_expand(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, const int64_t* types, hipStream_t s);
+void launch_geometry_species(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, const float* pos, const float* lattice,
+                             const int32_t* shift, const int64_t* types, hipStream_t s);
+int build_species_tables(m3g_plan* plan);
 void launch_energy_sums(const Consts& c, const Topo& t, const float* scaled_atomic, float* scaled_total, float* total, hipStream_t s);
 // (p.readout, p.readout_sums; without the latter the caller forms the energy sums: launch_energy_sums or, deferred, k_struct_stress)
 void launch_readout_mfma(const m3g_plan* plan, const StepPath& p, const Consts& c, const WeightLayout& wl, const Topo& t, const int64_t* types,
@@ -470,7 +483,8 @@ bool launch_node_tb_reverse(const Consts& c, const float* W, const BlockW& bw, c
 // pack_mfma.hip / edge_mfma.hip
 int pack_mfma_images(m3g_plan* plan);
 void free_mfma_images(m3g_plan* plan);
-void launch_edge_block_mfma(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, hipStream_t s);
+void launch_edge_block_mfma(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, hipStream_t s,
+                            bool e_out_read = true);
 void launch_edge_rev_node_mlp(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,
                               hipStream_t s);
 void launch_edge_rev_edge_mlp(const m3g_plan* plan, const StepPath& p, const Consts& c, const Topo& t, const Work& w, int b, const float* dx_new,

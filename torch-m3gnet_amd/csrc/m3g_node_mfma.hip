@@ -204,6 +204,67 @@ __global__ void __launch_bounds__(256) k_geometry_node_pre(Consts c, GeomArgs ga
   else node_pre_split_body(na, (int64_t)blockIdx.x - n_geo);
 }
 
+// ---------------------------------------------------------------------------------------------- block 0 from the species tables
+// Block 0's x^0 is the species embedding, so its rows x^0, v^0, TA^0, TB^0 are functions of the committed weights and the atom's
+// species alone: build_species_tables() runs k_node_pre_mfma once per commit and precision on num_types pseudo atoms (types 0 ..
+// num_types-1; a row of an MFMA tile depends on nothing but its own x row), and a step only copies each atom's rows out of the
+// tables (StepPath::block0).  An atom's rows are kSpeciesRowFloats / 4 = 148 16-byte pieces: x 0-15, v 16-19, TA 20-83, TB 84-147.
+struct SpeciesArgs {
+  int64_t N;
+  const int64_t* types;
+  int num_types;
+  const float* tab;   // m3g_plan::d_species_tab of the call's precision
+  float *x, *v, *TA, *TB;
+};
+constexpr int kSpeciesRowVecs = kSpeciesRowFloats / 4, kSpeciesVecsPerThread = 4;
+// One 16-byte piece per thread and round, consecutive threads on consecutive pieces; no LDS, every load of a thread in flight at
+// once.  An out-of-range species is clamped like everywhere else (the readout kernels report it).
+__device__ __forceinline__ void species_expand_body(const SpeciesArgs& a, int64_t vblock) {
+  const int64_t total = a.N * kSpeciesRowVecs;
+  const int64_t first = vblock * (256 * kSpeciesVecsPerThread) + threadIdx.x;
+  const float* __restrict__ tab = a.tab;
+  const int64_t* __restrict__ types = a.types;
+  const int nt = a.num_types;
+  f32x4 t[kSpeciesVecsPerThread];
+  float* dst[kSpeciesVecsPerThread];
+  static_for<kSpeciesVecsPerThread>([&]<int j>() {
+    const int64_t i = first + j * 256;
+    dst[j] = nullptr;
+    if (i >= total) return;
+    const int64_t atom = i / kSpeciesRowVecs;
+    const int piece = (int)(i - atom * kSpeciesRowVecs);
+    bool bad;
+    const int64_t ty = species_index(types[atom], nt, bad);
+    const float* src;
+    if (piece < 16) {
+      src = tab + ty * kDP + 4 * piece;
+      dst[j] = a.x + atom * kDP + 4 * piece;
+    } else if (piece < 20) {
+      src = tab + species_tab_v(nt) + ty * kCP + 4 * (piece - 16);
+      dst[j] = a.v + atom * kCP + 4 * (piece - 16);
+    } else if (piece < 84) {
+      src = tab + species_tab_ta(nt) + ty * (4 * kDP) + 4 * (piece - 20);
+      dst[j] = a.TA + atom * (4 * kDP) + 4 * (piece - 20);
+    } else {
+      src = tab + species_tab_tb(nt) + ty * (4 * kDP) + 4 * (piece - 84);
+      dst[j] = a.TB + atom * (4 * kDP) + 4 * (piece - 84);
+    }
+    t[j] = *(const f32x4*)src;
+  });
+  static_for<kSpeciesVecsPerThread>([&]<int j>() {
+    if (dst[j]) *(f32x4*)dst[j] = t[j];
+  });
+}
+static_assert(kSpeciesRowVecs == 16 + 4 + 64 + 64, "species_expand_body: the pieces of a row");
+
+__global__ void __launch_bounds__(256) k_species_expand(SpeciesArgs a) { species_expand_body(a, blockIdx.x); }
+// ... as the second workgroup role of the geometry launch, at any size (the pattern of k_geometry_node_pre: no dependency, no fence)
+template <int L, int R>
+__global__ void __launch_bounds__(256) k_geometry_species(Consts c, GeomArgs ga, int n_geo, SpeciesArgs sa) {
+  if ((int)blockIdx.x < n_geo) geometry_body<true, L, R>(c, ga, blockIdx.x);
+  else species_expand_body(sa, (int64_t)blockIdx.x - n_geo);
+}
+
 // ---------------------------------------------------------------------------------------------- readout
 // S5 (nn/readout.py:39-58) and its reverse on the matrix pipe, per 16-atom tile: both layers of the dense and the gate
 // branch as exact-fp32 MFMA chains (this stage seeds the reverse pass), the final 64 -> 1 products as lane-local dots + a lane-quarter sum, then (forces wanted) the
@@ -516,6 +577,56 @@ void launch_geometry_node_pre(const m3g_plan* plan, const Consts& c, const Topo&
   const NodePreArgs na{c.C, t.N, plan->d_node_img[kPrecF32], nullptr, w.seg_head, w.seg_first, t.row_ptr, w.x[0], w.v[0], w.TAb[0], w.TBb[0], types, emb,
                        c.num_types};
   M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_geometry_node_pre<L, R>), dim3((unsigned)(n_geo + 3 * tiles)), dim3(256), 0, s, c, ga, n_geo, na));
+}
+
+// block 0's rows copied out of the per-species tables of the plan's precision (StepPath::block0): t.N > 0
+static SpeciesArgs species_args(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, const int64_t* types) {
+  return SpeciesArgs{t.N, types, c.num_types, plan->d_species_tab[plan->opt.precision], w.x[0], w.v[0], w.TAb[0], w.TBb[0]};
+}
+static unsigned species_expand_blocks(int64_t N) {
+  constexpr int64_t per = 256 * kSpeciesVecsPerThread;
+  return (unsigned)((N * kSpeciesRowVecs + per - 1) / per);
+}
+void launch_species_expand(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, const int64_t* types, hipStream_t s) {
+  hipLaunchKernelGGL(k_species_expand, dim3(species_expand_blocks(t.N)), dim3(256), 0, s, species_args(plan, c, t, w, types));
+}
+// ... beside the geometry stage, in its launch (t.E > 0)
+void launch_geometry_species(const m3g_plan* plan, const Consts& c, const Topo& t, const Work& w, const float* pos, const float* lattice,
+                             const int32_t* shift, const int64_t* types, hipStream_t s) {
+  const int n_geo = (int)((t.E + 255) / 256);
+  const GeomArgs ga = geometry_args(t, pos, lattice, shift, w);
+  const SpeciesArgs sa = species_args(plan, c, t, w, types);
+  M3G_DISPATCH_LR(c.L, c.R, hipLaunchKernelGGL((k_geometry_species<L, R>), dim3((unsigned)n_geo + species_expand_blocks(t.N)), dim3(256), 0, s, c, ga, n_geo, sa));
+}
+
+// The tables themselves (called by m3g_plan_commit after the weights and images are on the device, which is idle): the step's own
+// kernel, image, embedding and weight scale, per precision, on num_types atoms of species 0 .. num_types-1 -- the rows are bit for
+// bit what that kernel writes for an atom of the species.  Every row of every table is written: nothing of an earlier commit stays.
+int build_species_tables(m3g_plan* plan) {
+  const int nt = plan->cfg.num_types;
+  if (plan->cfg.num_blocks == 0) return M3G_OK;   // no block, no node rows
+  std::vector<int64_t> iota(nt);
+  for (int i = 0; i < nt; ++i) iota[i] = i;
+  int64_t* d_types = nullptr;
+  M3G_HIP_CHECK(hipMalloc((void**)&d_types, sizeof(int64_t) * nt));
+  hipError_t e = hipMemcpy(d_types, iota.data(), sizeof(int64_t) * nt, hipMemcpyHostToDevice);
+  const int64_t tiles = (nt + 15) / 16;
+  const int wgs = 3 * (int)std::min<int64_t>((tiles + 3) / 4, 256);   // (launch_node_pre_mfma's grid)
+  for (int prec = 0; prec < kNumPrec && e == hipSuccess; ++prec) {
+    float*& tab = plan->d_species_tab[prec];
+    if (!tab) e = hipMalloc((void**)&tab, sizeof(float) * (size_t)nt * kSpeciesRowFloats);
+    if (e != hipSuccess) break;
+    M3G_PREC_SWITCH(prec,
+                    hipLaunchKernelGGL((k_node_pre_mfma<PREC>), dim3(wgs), dim3(256), 0, nullptr, plan->consts.C, (int64_t)nt, plan->d_node_img[prec],
+                                       nullptr, nullptr, nullptr, nullptr, tab, tab + species_tab_v(nt), tab + species_tab_ta(nt),
+                                       tab + species_tab_tb(nt), d_types, plan->d_weights + plan->wl.emb, nt,
+                                       prec == kPrecF16x3 ? plan->w_scale_inv : 1.f));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  (void)hipFree(d_types);
+  M3G_HIP_CHECK(e);
+  return M3G_OK;
 }
 
 }  // namespace m3g

@@ -178,7 +178,7 @@ static void chain_image_p(int prec, float wscale, float* img, int OB, int KS, F 
 
 void free_mfma_images(m3g_plan* plan) {
   auto drop = [](float*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-  for (int prec = 0; prec < kNumPrec; ++prec) { drop(plan->d_mfma_fwd[prec]); drop(plan->d_mfma_rev[prec]); drop(plan->d_node_img[prec]); }
+  for (int prec = 0; prec < kNumPrec; ++prec) { drop(plan->d_mfma_fwd[prec]); drop(plan->d_mfma_rev[prec]); drop(plan->d_node_img[prec]); drop(plan->d_species_tab[prec]); }
   drop(plan->d_mfma_revf);
   drop(plan->d_mfma_revf_h);
   drop(plan->d_mfma_revf32);

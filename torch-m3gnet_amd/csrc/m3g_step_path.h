@@ -53,6 +53,9 @@ struct Options {
                                  // the gather of whole 1-KB rows is not what bounds the node reverse; off by default
   int split_node_tiles = 128;    // option "split_node_tiles": 16-atom tiles (2,048 atoms) up to which the node tables and the readout take their split forms
                                  // (m3g_node_mfma.hip; measured at 625 tiles: node tables 58 -> 85 us, readout 28 -> 36 us per step -- not beyond)
+  int species_tables = 1;        // option "species_tables": block 0's node rows (x^0, v^0, TA^0, TB^0) depend on the committed weights and the
+                                 // atom's species only -- formed once per species at commit (m3g_plan::d_species_tab) and copied per atom
+                                 // beside the geometry stage; 0 = block 0's node kernel in every step (A/B tests; bit-identical either way)
   int fuse_node_tb = 1;          // option "fuse_node_tb": three-body reverse (moment path) + node reverse of a block as two workgroup roles of
                                  // one launch (k_node_tb_reverse, m3g_threebody.hip)
   int debug_node_tb_polls = 0;   // option "debug_node_tb_polls" (tests): see launch_node_tb_reverse
@@ -75,7 +78,7 @@ struct Options {
   // launches of a step are launch-bound.  The caller must then keep every buffer of the call alive and at the same address.
   int graph_replay = 0;
 };
-static_assert(sizeof(Options) == 20 * sizeof(int), "Options: twenty ints, no padding (its bytes are compared as a key)");
+static_assert(sizeof(Options) == 21 * sizeof(int), "Options: twenty-one ints, no padding (its bytes are compared as a key)");
 
 // dp1 hand-over formats of k_node_reverse: fp32 rows, 24-bit floating rows (bf16x3 fused kernel), 24-bit fixed-point rows + scales
 // (f16x3 fused kernel)
@@ -93,6 +96,12 @@ enum RevTail {
   kTailNodeTb,         // CANDIDATE: both as two roles of one launch, if the runtime says all its workgroups are resident; else separate
   kTailFinalTb,        // block 0: the step's last three-body reverse also forms dE/dr of every edge (no k_geometry_reverse)
 };
+// how block 0's node rows are formed (its x^0 is the species embedding: nothing in them depends on the call's geometry)
+enum Block0Tables {
+  kBlock0Kernel = 0,         // the node kernel, like every other block (beside the geometry stage where geom_with_node_pre says so)
+  kBlock0ExpandBesideGeom,   // rows of the plan's per-species tables copied per atom, as the second workgroup role of the geometry launch
+  kBlock0ExpandAlone,        // ... in a launch of their own (stage profiler on, or no edge and so no geometry launch)
+};
 enum StressKernel { kStressNone = 0, kStressInGather /* the force gather's last workgroup */, kStressPair, kStressRef };
 
 struct ModelDims { int L, R, C, B; };
@@ -109,6 +118,7 @@ struct StepPath {
   bool moments = false;        // three-body moment kernels (else the list kernels)
   bool long_lists = false;     // list kernels: the long-list instantiation
   bool geom_with_node_pre = false;   // geometry stage and block 0's node tables as two roles of one launch
+  int block0 = kBlock0Kernel;  // Block0Tables; anything else: the per-species tables replace the node kernel of block 0, whatever geom_with_node_pre says
   bool node_split = false;     // node tables: a tile and pass per workgroup (else groups of four tiles)
   bool fwd_split = false;      // forward edge kernel: split-tile (else persistent)
   int rev_edge = kRevValu;
@@ -157,6 +167,8 @@ inline StepPath resolve_step_path(const Options& o, const ModelDims& m, int64_t 
   if (mfma) {
     p.node_split = f32 && small_nodes;
     p.geom_with_node_pre = !profile && p.node_split && m.B != 0 && E != 0 && N != 0;
+    // the copy role needs no LDS and few registers: it sits beside the geometry role at any size
+    if (o.species_tables && m.B != 0 && N != 0) p.block0 = !profile && E != 0 ? kBlock0ExpandBesideGeom : kBlock0ExpandAlone;
     // the split-tile kernels cover the exact-fp32 default only (not: another precision / an A-B option of the persistent kernels / stamps)
     p.fwd_split = etiles > 0 && etiles <= o.small_tiles_fwd && f32 && p.fwd_save != 1 && !stamps;
     p.rev_edge = !p.fused_rev ? kRevPair : !f32 ? kRevFused : (etiles > 0 && etiles <= o.small_tiles && saves_p2 && !stamps) ? kRevSplit : kRevF32;
