@@ -1,6 +1,9 @@
 // The device state of m3g_dyn_* (m3g_dynamics.hip) and its random generator, shared with the callers that work on that state between
 // two m3g_dyn_step calls: m3g_remd.hip (the target temperatures, velocities, flags and chunk table of a replica-exchange batch) and
 // m3g_mc.hip (the flags, masses and velocities of a hybrid Monte Carlo batch; its own draws use philox4x64_10 and uniform53 too).
+// The five step families (m3g_dynamics.hip, m3g_nhc.hip, m3g_mtk.hip, m3g_pimd.hip, m3g_ti.hip) include it through
+// m3g_integrator.h, where the Box-Muller draw over this generator, the list of its key words and what their kernels and entry
+// points share now live; the constants, DynView, Philox and uniform53 stay here.
 #pragma once
 #include "m3g_chunks.h"
 #include "m3g_internal.h"

@@ -9,24 +9,14 @@
 //                    (lambda sum m v + dt/2 kappa sum F) / n -- no second pass over the atoms --, the new cell and the observables;
 //   k_dyn_apply      one workgroup per chunk: the finish kick and the start step of every atom (Philox4x64-10 for Langevin).
 // No atomics: every result depends on the structure's own rows only, so it is bitwise the same alone or in any batch.  No allocation,
-// copy or wait in m3g_dyn_step (capture-safe).
+// copy or wait in m3g_dyn_step (capture-safe).  What the five step families spell alike -- the partials body (shared with m3g_nhc_*),
+// the Box-Muller draw, the cell volume, the checks and copies of the entry points -- is m3g_integrator.h.
 #include <cmath>
 
-#include "m3g_dyn_state.h"
+#include "m3g_integrator.h"
 
 namespace m3g {
 namespace {
-// three standard normals of atom `local` (its index inside its structure) at start k of a structure seeded `seed`
-__device__ inline void gaussian3(uint64_t seed, uint64_t k, uint64_t local, double xi[3]) {
-  uint64_t c[4] = {k, local, 0, 0};
-  philox4x64_10(c, seed, 0);
-  constexpr double kTwoPi = 6.283185307179586;
-  const double r0 = sqrt(-2.0 * log(uniform53(c[0]))), r1 = sqrt(-2.0 * log(uniform53(c[2])));
-  xi[0] = r0 * cos(kTwoPi * uniform53(c[1]));
-  xi[1] = r0 * sin(kTwoPi * uniform53(c[1]));
-  xi[2] = r1 * cos(kTwoPi * uniform53(c[3]));
-}
-
 __global__ void __launch_bounds__(kChunkRows) k_dyn_init(DynView st, const double* __restrict__ vel) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < 3 * st.N) st.v[i] = vel[i];
@@ -38,31 +28,8 @@ __global__ void __launch_bounds__(kChunkRows) k_dyn_init(DynView st, const doubl
 }
 
 __global__ void __launch_bounds__(kChunkRows) k_dyn_partials(DynView st, double half_dt, const float* __restrict__ forces) {
-  __shared__ double sh[kPart][kChunkRows];
-  const int c = blockIdx.x, t = threadIdx.x;
-  if (c >= st.ch.n_chunks()) return;
-  const int s = st.ch.structure(c);
-  const int fl = st.flags[s];
-  if (fl & M3G_DYN_ERROR) return;   // frozen: finalize reads nothing of it
-  const int64_t i = st.ch.row(c, t);
-  double val[kPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (st.ch.holds(s, i)) {
-    const double m = st.mass[i];
-    double f[3], v[3];
-    for (int k = 0; k < 3; ++k) {
-      f[k] = forces[3 * i + k];
-      v[k] = st.v[3 * i + k];
-      if (fl & M3G_DYN_STARTED) v[k] += half_dt * (kKappa * f[k] / m);   // the finish kick (written by k_dyn_apply)
-    }
-    val[0] = m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    for (int k = 0; k < 3; ++k) {
-      val[1 + k] = m * v[k];
-      val[4 + k] = f[k];
-    }
-    val[7] = (std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2])) ? 0.0 : 1.0;
-  }
-  chunk_tree_reduce<kPart>(sh, val, t);
-  if (t < kPart) st.partial[kPart * c + t] = sh[t][0];
+  // the finish kick (written by k_dyn_apply)
+  md_partials(st, forces, [=](int, double v, double f, double m) { return v + half_dt * (kKappa * f / m); });
 }
 
 __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_dyn_finalize(DynView st, m3g_dyn_params p, int32_t finish_only, double c1,
@@ -96,8 +63,8 @@ __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_dyn_finalize(DynView
   const double temp = two_ke / (3.0 * n * kBoltzmann);
   double vol = NAN, trw = NAN;
   double* L = lattice ? lattice + 9 * s : nullptr;
-  if (L) vol = fabs(L[0] * (L[4] * L[8] - L[5] * L[7]) - L[1] * (L[3] * L[8] - L[5] * L[6]) + L[2] * (L[3] * L[7] - L[4] * L[6]));
-  if (L && sv) trw = vol * (((double)sv[0] + (double)sv[1]) + (double)sv[2]);   // tr W, W = V * stresses
+  if (L) vol = cell_volume(L);
+  if (L && sv) trw = virial_trace(vol, sv);
   if (obs) {
     obs[4 * s] = ke;
     obs[4 * s + 1] = temp;
@@ -162,7 +129,7 @@ __global__ void __launch_bounds__(kChunkRows) k_dyn_apply(DynView st, m3g_dyn_pa
   for (int k = 0; k < 3; ++k) x[k] = pos[3 * i + k];
   if (p.ensemble == M3G_DYN_NVT_LANGEVIN) {   // B A O A
     double xi[3];
-    gaussian3(st.seed[s], (uint64_t)(st.steps[s] - 1), (uint64_t)(i - st.ch.offsets[s]), xi);
+    gaussian3(st.seed[s], kLangevinKey, (uint64_t)(st.steps[s] - 1), (uint64_t)(i - st.ch.offsets[s]), 0, xi);   // (start, atom of its structure)
     const double sigma = sqrt(coef[7] / m);
     for (int k = 0; k < 3; ++k) {
       v[k] += h * a[k];
@@ -217,43 +184,30 @@ extern "C" int m3g_dyn_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* b
 }
 
 extern "C" int m3g_dyn_state_view(int64_t n_atoms, int64_t n_structs, size_t* mass_offset, size_t* velocity_offset) {
-  if (!mass_offset || !velocity_offset || !batch_sizes_ok(n_atoms, n_structs)) { set_error("m3g_dyn_state_view: null argument or bad sizes"); return M3G_ERR_VALUE; }
-  const DynView at = dyn_view(n_atoms, n_structs, nullptr).view;   // (over a null state: the offsets)
-  *mass_offset = carve_offset(at.mass);
-  *velocity_offset = carve_offset(at.v);
-  return M3G_OK;
+  return state_view_offsets("m3g_dyn_state_view", batch_sizes_ok(n_atoms, n_structs), [&] { return dyn_view(n_atoms, n_structs, nullptr).view; },
+                            mass_offset, velocity_offset);
 }
 
 extern "C" int m3g_dyn_init(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
                             const double* host_temperatures, const uint64_t* host_seeds, const double* vel, void* state, size_t state_bytes,
                             void* stream_) {
   if (const char* why = dyn_params_error(p)) { set_error("m3g_dyn_init: invalid parameters: %s", why); return M3G_ERR_VALUE; }
-  if (!batch_sizes_ok(n_atoms, n_structs) || !host_offsets || !host_masses || !host_temperatures || !host_seeds || !vel || !state) {
-    set_error("m3g_dyn_init: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
+  constexpr const char* fn = "m3g_dyn_init";
   const int64_t N = n_atoms, S = n_structs;
-  if (!offsets_ok("m3g_dyn_init", host_offsets, N, S)) return M3G_ERR_VALUE;
+  if (!init_args_ok(fn, N, S, host_offsets && host_masses && host_temperatures && host_seeds && vel && state)) return M3G_ERR_VALUE;
+  if (!offsets_ok(fn, host_offsets, N, S)) return M3G_ERR_VALUE;
   for (int64_t i = 0; i < N; ++i)
-    if (!finite_positive(host_masses[i])) { set_error("m3g_dyn_init: mass of atom %lld is not finite and > 0", (long long)i); return M3G_ERR_VALUE; }
+    if (!mass_ok(fn, host_masses, i)) return M3G_ERR_VALUE;
   for (int64_t s = 0; s < S; ++s)
-    if (!(std::isfinite(host_temperatures[s]) && host_temperatures[s] >= 0.0)) {
-      set_error("m3g_dyn_init: temperature of structure %lld is not finite and >= 0", (long long)s);
-      return M3G_ERR_VALUE;
-    }
+    if (!temperature_ok(fn, host_temperatures, s, "structure", true)) return M3G_ERR_VALUE;
   const auto [st, total] = dyn_view(N, S, state);
-  if (state_bytes < total) { set_error("m3g_dyn_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits(fn, state_bytes, total, true)) return M3G_ERR_SIZE;
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync(st.mass, host_masses, 8 * N, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st.t0, host_temperatures, 8 * S, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st.seed, host_seeds, 8 * S, hipMemcpyHostToDevice, s));
+  if (int rc = upload_batch(table, st, host_offsets, host_masses, host_temperatures, host_seeds, s)) return rc;
   const int64_t work = 3 * N > S ? 3 * N : S;
   hipLaunchKernelGGL(k_dyn_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, st, vel);
-  M3G_HIP_CHECK(hipGetLastError());
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
-  return M3G_OK;
+  return launched_and_synced(s);   // (the host tables above go out of scope)
 }
 
 extern "C" int m3g_dyn_step(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
@@ -263,14 +217,13 @@ extern "C" int m3g_dyn_step(const m3g_dyn_params* p, int64_t n_atoms, int64_t n_
   if (!batch_sizes_ok(N, S) || !state || !forces || !pos) { set_error("m3g_dyn_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (p->ensemble == M3G_DYN_NPT_BERENDSEN && (!stresses || !lattice)) { set_error("m3g_dyn_step: NPT needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
   const auto [st, total] = dyn_view(N, S, state);
-  if (state_bytes < total) { set_error("m3g_dyn_step: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_dyn_step", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   const double c1 = langevin_c1(p);
-  const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
-  hipLaunchKernelGGL(k_dyn_partials, grid, dim3(kChunkRows), 0, s, st, 0.5 * p->dt, forces);
-  hipLaunchKernelGGL(k_dyn_finalize, grid_for(S, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, *p,
-                     finish_only, c1, stresses, lattice, lattice32, obs);
-  hipLaunchKernelGGL(k_dyn_apply, grid, dim3(kChunkRows), 0, s, st, *p, c1, forces, pos);
+  const auto [chunks, waves] = step_grids(N, S);
+  hipLaunchKernelGGL(k_dyn_partials, chunks, dim3(kChunkRows), 0, s, st, 0.5 * p->dt, forces);
+  hipLaunchKernelGGL(k_dyn_finalize, waves, dim3(kFinalizeThreads), 0, s, st, *p, finish_only, c1, stresses, lattice, lattice32, obs);
+  hipLaunchKernelGGL(k_dyn_apply, chunks, dim3(kChunkRows), 0, s, st, *p, c1, forces, pos);
   M3G_RETURN_LAUNCH_STATUS();
 }
 
@@ -279,11 +232,9 @@ extern "C" int m3g_dyn_read(int64_t n_atoms, int64_t n_structs, const void* stat
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !state) { set_error("m3g_dyn_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = dyn_view(N, S, (void*)state);
-  if (state_bytes < total) { set_error("m3g_dyn_read: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_dyn_read", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
-  M3G_HIP_CHECK(read_back(host_steps, st.steps, S, s));
-  M3G_HIP_CHECK(read_back(host_vel, st.v, 3 * N, s));
+  if (int rc = read_head(st, host_flags, host_steps, host_vel, s)) return rc;
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;
 }

@@ -16,10 +16,11 @@
 //   k_mtk_apply      one workgroup per chunk: the finish kick and lambda, the opening kick, pbar / m, the drift.  The only writer of
 //                    velocities and positions, after the verdict: a flagged structure keeps its bits.
 // No atomics: every result depends on the structure's own rows only, so it is bitwise the same alone or in any batch.  No allocation,
-// copy or wait in m3g_mtk_step (capture-safe).
+// copy or wait in m3g_mtk_step (capture-safe).  The row prologue and the epilogue of the partials, the cell volume and the checks and
+// copies of the entry points are m3g_integrator.h.
 #include <cmath>
 
-#include "m3g_dyn_state.h"
+#include "m3g_integrator.h"
 #include "m3g_nhc_chain.h"
 
 namespace m3g {
@@ -99,16 +100,12 @@ __global__ void __launch_bounds__(kChunkRows) k_mtk_init(MtkView st, const doubl
 }
 
 __global__ void __launch_bounds__(kChunkRows) k_mtk_partials(MtkView st, const float* __restrict__ forces) {
-  __shared__ double sh[kMtkPart][kChunkRows];
   const int c = blockIdx.x, t = threadIdx.x;
-  if (c >= st.ch.n_chunks()) return;
-  const int s = st.ch.structure(c);
-  const int fl = st.flags[s];
-  if (fl & M3G_DYN_ERROR) return;   // frozen: finalize reads nothing of it
-  const int64_t i = st.ch.row(c, t);
+  const auto [live, s, fl, i, holds] = chunk_row(st, c, t);
+  if (!live) return;
   double val[kMtkPart];
   for (int k = 0; k < kMtkPart; ++k) val[k] = 0.0;
-  if (st.ch.holds(s, i)) {
+  if (holds) {
     const double* coef = st.coef + kMtkCoef * s;
     const double m = st.mass[i];
     double f[3], a[3], v[3];
@@ -128,10 +125,9 @@ __global__ void __launch_bounds__(kChunkRows) k_mtk_partials(MtkView st, const f
       val[kPMv + k] = m * v[k];
       val[kPF + k] = f[k];
     }
-    val[kPBad] = (std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2])) ? 0.0 : 1.0;
+    val[kPBad] = (std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2])) ? 0.0 : 1.0;   // (not forces_finite: it moves this kernel's compares)
   }
-  chunk_tree_reduce<kMtkPart>(sh, val, t);
-  if (t < kMtkPart) st.partial[kMtkPart * c + t] = sh[t][0];
+  reduce_store<kMtkPart>(val, c, t, st.partial);
 }
 
 __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_mtk_finalize(MtkView st, m3g_mtk_params p, int32_t finish_only,
@@ -176,7 +172,7 @@ __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_mtk_finalize(MtkView
       const double qbk = kt * p.taup * p.taup, qb0 = n_cell * qbk, wg = (g + 3.0) * qbk / 3.0;
       double K[6], W[6];
       for (int k = 0; k < 6; ++k) K[k] = acc[kPK + k] / kKappa;
-      const double vol = fabs(L[0] * (L[4] * L[8] - L[5] * L[7]) - L[1] * (L[3] * L[8] - L[5] * L[6]) + L[2] * (L[3] * L[7] - L[4] * L[6]));
+      const double vol = cell_volume(L);
       for (int k = 0; k < 6; ++k) W[k] = vol * (double)sv[k];   // the virial, W = V * stresses
       auto kick_vg = [&]() {   // vg += h G
         const double iso = (K[0] + K[1] + K[2]) / g - vol * p.pressure;
@@ -353,49 +349,34 @@ extern "C" int m3g_mtk_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t c
 }
 
 extern "C" int m3g_mtk_state_view(int64_t n_atoms, int64_t n_structs, int32_t chain_length, size_t* mass_offset, size_t* velocity_offset) {
-  if (!mass_offset || !velocity_offset || !batch_sizes_ok(n_atoms, n_structs) || !chain_ok(chain_length)) {
-    set_error("m3g_mtk_state_view: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
-  const MtkView at = mtk_view(n_atoms, n_structs, chain_length, nullptr).view;   // (over a null state: the offsets)
-  *mass_offset = carve_offset(at.mass);
-  *velocity_offset = carve_offset(at.v);
-  return M3G_OK;
+  return state_view_offsets("m3g_mtk_state_view", batch_sizes_ok(n_atoms, n_structs) && chain_ok(chain_length),
+                            [&] { return mtk_view(n_atoms, n_structs, chain_length, nullptr).view; }, mass_offset, velocity_offset);
 }
 
 extern "C" int m3g_mtk_init(const m3g_mtk_params* p, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
                             const double* host_temperatures, const double* vel, void* state, size_t state_bytes, void* stream_) {
   if (const char* why = mtk_params_error(p)) { set_error("m3g_mtk_init: invalid parameters: %s", why); return M3G_ERR_VALUE; }
-  if (!batch_sizes_ok(n_atoms, n_structs) || !host_offsets || !host_masses || !host_temperatures || !vel || !state) {
-    set_error("m3g_mtk_init: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
+  constexpr const char* fn = "m3g_mtk_init";
   const int64_t N = n_atoms, S = n_structs;
-  if (!offsets_ok("m3g_mtk_init", host_offsets, N, S)) return M3G_ERR_VALUE;
+  if (!init_args_ok(fn, N, S, host_offsets && host_masses && host_temperatures && vel && state)) return M3G_ERR_VALUE;
+  if (!offsets_ok(fn, host_offsets, N, S)) return M3G_ERR_VALUE;
   for (int64_t i = 0; i < N; ++i)
-    if (!finite_positive(host_masses[i])) { set_error("m3g_mtk_init: mass of atom %lld is not finite and > 0", (long long)i); return M3G_ERR_VALUE; }
+    if (!mass_ok(fn, host_masses, i)) return M3G_ERR_VALUE;
   for (int64_t s = 0; s < S; ++s) {
-    if (!finite_positive(host_temperatures[s])) {   // (the chain and barostat masses are proportional to it)
-      set_error("m3g_mtk_init: temperature of structure %lld is not finite and > 0", (long long)s);
-      return M3G_ERR_VALUE;
-    }
+    if (!temperature_ok(fn, host_temperatures, s)) return M3G_ERR_VALUE;   // (the chain and barostat masses are proportional to it)
     if (p->fix_com && host_offsets[s + 1] - host_offsets[s] == 1) {
       set_error("m3g_mtk_init: structure %lld holds one atom, which fix_com leaves no degree of freedom", (long long)s);
       return M3G_ERR_VALUE;
     }
   }
   const auto [st, total] = mtk_view(N, S, p->chain_length, state);
-  if (state_bytes < total) { set_error("m3g_mtk_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits(fn, state_bytes, total, true)) return M3G_ERR_SIZE;
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync(st.mass, host_masses, 8 * N, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st.t0, host_temperatures, 8 * S, hipMemcpyHostToDevice, s));
+  if (int rc = upload_batch(table, st, host_offsets, host_masses, host_temperatures, nullptr, s)) return rc;
   const int64_t work = 3 * N > S ? 3 * N : S;
   hipLaunchKernelGGL(k_mtk_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, st, vel);
-  M3G_HIP_CHECK(hipGetLastError());
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
-  return M3G_OK;
+  return launched_and_synced(s);   // (the host tables above go out of scope)
 }
 
 extern "C" int m3g_mtk_step(const m3g_mtk_params* p, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
@@ -405,13 +386,12 @@ extern "C" int m3g_mtk_step(const m3g_mtk_params* p, int64_t n_atoms, int64_t n_
   if (!batch_sizes_ok(N, S) || !state || !forces || !pos) { set_error("m3g_mtk_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (!stresses || !lattice) { set_error("m3g_mtk_step: needs the stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
   const auto [st, total] = mtk_view(N, S, p->chain_length, state);
-  if (state_bytes < total) { set_error("m3g_mtk_step: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_mtk_step", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
-  const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
-  hipLaunchKernelGGL(k_mtk_partials, grid, dim3(kChunkRows), 0, s, st, forces);
-  hipLaunchKernelGGL(k_mtk_finalize, grid_for(S, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, *p, finish_only, stresses, lattice,
-                     lattice32, obs);
-  hipLaunchKernelGGL(k_mtk_apply, grid, dim3(kChunkRows), 0, s, st, p->fix_com, forces, pos);
+  const auto [chunks, waves] = step_grids(N, S);
+  hipLaunchKernelGGL(k_mtk_partials, chunks, dim3(kChunkRows), 0, s, st, forces);
+  hipLaunchKernelGGL(k_mtk_finalize, waves, dim3(kFinalizeThreads), 0, s, st, *p, finish_only, stresses, lattice, lattice32, obs);
+  hipLaunchKernelGGL(k_mtk_apply, chunks, dim3(kChunkRows), 0, s, st, p->fix_com, forces, pos);
   M3G_RETURN_LAUNCH_STATUS();
 }
 
@@ -420,11 +400,9 @@ extern "C" int m3g_mtk_read(int64_t n_atoms, int64_t n_structs, int32_t chain_le
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !chain_ok(chain_length) || !state) { set_error("m3g_mtk_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = mtk_view(N, S, chain_length, (void*)state);
-  if (state_bytes < total) { set_error("m3g_mtk_read: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_mtk_read", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
-  M3G_HIP_CHECK(read_back(host_steps, st.steps, S, s));
-  M3G_HIP_CHECK(read_back(host_vel, st.v, 3 * N, s));
+  if (int rc = read_head(st, host_flags, host_steps, host_vel, s)) return rc;
   M3G_HIP_CHECK(read_back(host_chain, st.chain, (size_t)chain_row(chain_length) * S, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;

@@ -12,10 +12,11 @@
 //   k_nhc_apply      one workgroup per chunk: v = lambda (finish-kicked v), the start kick, the centre-of-mass momentum in closed
 //                    form (it is linear in sum m v and sum F of the same partials), the drift.
 // No atomics: every result depends on the structure's own rows only, so it is bitwise the same alone or in any batch.  No allocation,
-// copy or wait in m3g_nhc_step (capture-safe).
+// copy or wait in m3g_nhc_step (capture-safe).  The partials body (shared with m3g_dyn_*), the cell volume and the checks and copies
+// of the entry points are m3g_integrator.h.
 #include <cmath>
 
-#include "m3g_dyn_state.h"
+#include "m3g_integrator.h"
 #include "m3g_nhc_chain.h"
 
 namespace m3g {
@@ -72,32 +73,11 @@ __global__ void __launch_bounds__(kChunkRows) k_nhc_init(NhcView st, const doubl
 }
 
 __global__ void __launch_bounds__(kChunkRows) k_nhc_partials(NhcView st, const float* __restrict__ forces) {
-  __shared__ double sh[kPart][kChunkRows];
-  const int c = blockIdx.x, t = threadIdx.x;
-  if (c >= st.ch.n_chunks()) return;
-  const int s = st.ch.structure(c);
-  const int fl = st.flags[s];
-  if (fl & M3G_DYN_ERROR) return;   // frozen: finalize reads nothing of it
-  const int64_t i = st.ch.row(c, t);
-  double val[kPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (st.ch.holds(s, i)) {
+  // the finish kick (written by k_nhc_apply)
+  md_partials(st, forces, [&](int s, double v, double f, double m) {
     const double* coef = st.coef + kNhcCoef * s;
-    const double m = st.mass[i], cv = coef[kKickV], ca = coef[kKickA];
-    double f[3], v[3];
-    for (int k = 0; k < 3; ++k) {
-      f[k] = forces[3 * i + k];
-      v[k] = st.v[3 * i + k];
-      if (fl & M3G_DYN_STARTED) v[k] = axpby(v[k], cv, kKappa * f[k] / m, ca);   // the finish kick (written by k_nhc_apply)
-    }
-    val[0] = m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    for (int k = 0; k < 3; ++k) {
-      val[1 + k] = m * v[k];
-      val[4 + k] = f[k];
-    }
-    val[7] = (std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2])) ? 0.0 : 1.0;
-  }
-  chunk_tree_reduce<kPart>(sh, val, t);
-  if (t < kPart) st.partial[kPart * c + t] = sh[t][0];
+    return axpby(v, coef[kKickV], kKappa * f / m, coef[kKickA]);
+  });
 }
 
 __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_nhc_finalize(NhcView st, m3g_nhc_params p, int32_t finish_only,
@@ -143,8 +123,8 @@ __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_nhc_finalize(NhcView
   double k2 = acc[0] / kKappa;   // twice the kinetic energy, eV
   double vol = NAN, trw = NAN;
   double* L = lattice ? lattice + 9 * s : nullptr;
-  if (L) vol = fabs(L[0] * (L[4] * L[8] - L[5] * L[7]) - L[1] * (L[3] * L[8] - L[5] * L[6]) + L[2] * (L[3] * L[7] - L[4] * L[6]));
-  if (L && sv) trw = vol * (((double)sv[0] + (double)sv[1]) + (double)sv[2]);   // tr W, W = V * stresses
+  if (L) vol = cell_volume(L);
+  if (L && sv) trw = virial_trace(vol, sv);
   auto g_eps = [&]() { return (alpha * k2 + trw - 3.0 * vol * p.pressure) / wb; };
   auto baro_chain = [&]() {
     double kb2 = wb * veps * veps;
@@ -280,49 +260,34 @@ extern "C" int m3g_nhc_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t c
 }
 
 extern "C" int m3g_nhc_state_view(int64_t n_atoms, int64_t n_structs, int32_t chain_length, size_t* mass_offset, size_t* velocity_offset) {
-  if (!mass_offset || !velocity_offset || !batch_sizes_ok(n_atoms, n_structs) || !chain_ok(chain_length)) {
-    set_error("m3g_nhc_state_view: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
-  const NhcView at = nhc_view(n_atoms, n_structs, chain_length, nullptr).view;   // (over a null state: the offsets)
-  *mass_offset = carve_offset(at.mass);
-  *velocity_offset = carve_offset(at.v);
-  return M3G_OK;
+  return state_view_offsets("m3g_nhc_state_view", batch_sizes_ok(n_atoms, n_structs) && chain_ok(chain_length),
+                            [&] { return nhc_view(n_atoms, n_structs, chain_length, nullptr).view; }, mass_offset, velocity_offset);
 }
 
 extern "C" int m3g_nhc_init(const m3g_nhc_params* p, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
                             const double* host_temperatures, const double* vel, void* state, size_t state_bytes, void* stream_) {
   if (const char* why = nhc_params_error(p)) { set_error("m3g_nhc_init: invalid parameters: %s", why); return M3G_ERR_VALUE; }
-  if (!batch_sizes_ok(n_atoms, n_structs) || !host_offsets || !host_masses || !host_temperatures || !vel || !state) {
-    set_error("m3g_nhc_init: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
+  constexpr const char* fn = "m3g_nhc_init";
   const int64_t N = n_atoms, S = n_structs;
-  if (!offsets_ok("m3g_nhc_init", host_offsets, N, S)) return M3G_ERR_VALUE;
+  if (!init_args_ok(fn, N, S, host_offsets && host_masses && host_temperatures && vel && state)) return M3G_ERR_VALUE;
+  if (!offsets_ok(fn, host_offsets, N, S)) return M3G_ERR_VALUE;
   for (int64_t i = 0; i < N; ++i)
-    if (!finite_positive(host_masses[i])) { set_error("m3g_nhc_init: mass of atom %lld is not finite and > 0", (long long)i); return M3G_ERR_VALUE; }
+    if (!mass_ok(fn, host_masses, i)) return M3G_ERR_VALUE;
   for (int64_t s = 0; s < S; ++s) {
-    if (!finite_positive(host_temperatures[s])) {   // (the chain masses are proportional to it)
-      set_error("m3g_nhc_init: temperature of structure %lld is not finite and > 0", (long long)s);
-      return M3G_ERR_VALUE;
-    }
+    if (!temperature_ok(fn, host_temperatures, s)) return M3G_ERR_VALUE;   // (the chain masses are proportional to it)
     if (p->fix_com && host_offsets[s + 1] - host_offsets[s] == 1) {
       set_error("m3g_nhc_init: structure %lld holds one atom, which fix_com leaves no degree of freedom", (long long)s);
       return M3G_ERR_VALUE;
     }
   }
   const auto [st, total] = nhc_view(N, S, p->chain_length, state);
-  if (state_bytes < total) { set_error("m3g_nhc_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits(fn, state_bytes, total, true)) return M3G_ERR_SIZE;
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync(st.mass, host_masses, 8 * N, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st.t0, host_temperatures, 8 * S, hipMemcpyHostToDevice, s));
+  if (int rc = upload_batch(table, st, host_offsets, host_masses, host_temperatures, nullptr, s)) return rc;
   const int64_t work = 3 * N > S ? 3 * N : S;
   hipLaunchKernelGGL(k_nhc_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, st, vel);
-  M3G_HIP_CHECK(hipGetLastError());
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
-  return M3G_OK;
+  return launched_and_synced(s);   // (the host tables above go out of scope)
 }
 
 extern "C" int m3g_nhc_step(const m3g_nhc_params* p, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
@@ -332,13 +297,12 @@ extern "C" int m3g_nhc_step(const m3g_nhc_params* p, int64_t n_atoms, int64_t n_
   if (!batch_sizes_ok(N, S) || !state || !forces || !pos) { set_error("m3g_nhc_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (p->ensemble == M3G_NHC_NPT_MTK && (!stresses || !lattice)) { set_error("m3g_nhc_step: NPT needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
   const auto [st, total] = nhc_view(N, S, p->chain_length, state);
-  if (state_bytes < total) { set_error("m3g_nhc_step: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_nhc_step", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
-  const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
-  hipLaunchKernelGGL(k_nhc_partials, grid, dim3(kChunkRows), 0, s, st, forces);
-  hipLaunchKernelGGL(k_nhc_finalize, grid_for(S, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, *p, finish_only, stresses, lattice,
-                     lattice32, obs);
-  hipLaunchKernelGGL(k_nhc_apply, grid, dim3(kChunkRows), 0, s, st, p->fix_com, forces, pos);
+  const auto [chunks, waves] = step_grids(N, S);
+  hipLaunchKernelGGL(k_nhc_partials, chunks, dim3(kChunkRows), 0, s, st, forces);
+  hipLaunchKernelGGL(k_nhc_finalize, waves, dim3(kFinalizeThreads), 0, s, st, *p, finish_only, stresses, lattice, lattice32, obs);
+  hipLaunchKernelGGL(k_nhc_apply, chunks, dim3(kChunkRows), 0, s, st, p->fix_com, forces, pos);
   M3G_RETURN_LAUNCH_STATUS();
 }
 
@@ -347,11 +311,9 @@ extern "C" int m3g_nhc_read(int64_t n_atoms, int64_t n_structs, int32_t chain_le
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !chain_ok(chain_length) || !state) { set_error("m3g_nhc_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = nhc_view(N, S, chain_length, (void*)state);
-  if (state_bytes < total) { set_error("m3g_nhc_read: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_nhc_read", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
-  M3G_HIP_CHECK(read_back(host_steps, st.steps, S, s));
-  M3G_HIP_CHECK(read_back(host_vel, st.v, 3 * N, s));
+  if (int rc = read_head(st, host_flags, host_steps, host_vel, s)) return rc;
   M3G_HIP_CHECK(read_back(host_chain, st.chain, (size_t)chain_row(chain_length) * S, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;

@@ -20,18 +20,18 @@
 // inverse pass those rows hold normal-mode coordinates, and the mode loop in between draws the noise of (atom, mode) once for the
 // three components.  x and v go through the table one after the other: P fp64 values live, not 2 P.
 // No atomics: every result depends on the ring's own rows only, so it is bitwise the same alone or in any batch.  No allocation,
-// copy or wait in m3g_pimd_step (capture-safe).
+// copy or wait in m3g_pimd_step (capture-safe).  The Box-Muller draw and its key word, the row prologue, verdict and epilogue of the
+// partials and the checks and copies of the entry points are m3g_integrator.h.
 #include <cmath>
 #include <vector>
 
-#include "m3g_dyn_state.h"
+#include "m3g_integrator.h"
 
 namespace m3g {
 namespace {
 constexpr double kHbar = 0.6582119569;   // eV fs
 constexpr int kPimdPart = 4;    // per chunk: sum m |v|^2, sum m |q_j - q_j+1|^2, sum (q - centroid) . F, non-finite forces
 constexpr int kPimdMode = 5;    // per ring and mode: cos(w h), sin(w h) / w, w sin(w h), c1, c2
-constexpr uint64_t kPimdKey = 3;   // second Philox key word (0, 1, 2: Langevin, replica exchange, swap Monte Carlo)
 enum PimdAct : int32_t { kActNone = 0, kActFinishOnly = 1, kActStep = 2, kActFinishKick = 4 };   // action | finish kick?
 
 struct PimdView {
@@ -63,26 +63,14 @@ inline Carved<PimdView> pimd_view(int64_t N, int64_t S, int P, void* state) {
   return {st, c.off};
 }
 
-// where thread t of chunk c works: atom `local` of ring g, whose bead j is row first + j n of the batch
+// where the thread on row i of ring g's table works: atom `local` of the ring, whose bead j is row first + j n of the batch
 struct RingRow {
   bool holds;
   int64_t first, n, local;
 };
-__device__ inline RingRow ring_row(const PimdView& st, int c, int g, int t) {
-  const int64_t i = st.ch.row(c, t), o = st.ch.offsets[g];
+__device__ inline RingRow ring_row(const PimdView& st, int g, int64_t i) {
+  const int64_t o = st.ch.offsets[g];
   return {st.ch.holds(g, i), st.P * o + (i - o), st.ch.offsets[g + 1] - o, i - o};
-}
-
-// three standard normals of (atom `local`, mode k) at start `step` of a ring seeded `seed`: the Box-Muller of gaussian3 in
-// m3g_dynamics.hip on the block of counter (step, local, k, 0) under key (seed, kPimdKey)
-__device__ inline void mode_gaussian3(uint64_t seed, uint64_t step, uint64_t local, uint64_t k, double xi[3]) {
-  uint64_t c[4] = {step, local, k, 0};
-  philox4x64_10(c, seed, kPimdKey);
-  constexpr double kTwoPi = 6.283185307179586;
-  const double r0 = sqrt(-2.0 * log(uniform53(c[0]))), r1 = sqrt(-2.0 * log(uniform53(c[2])));
-  xi[0] = r0 * cos(kTwoPi * uniform53(c[1]));
-  xi[1] = r0 * sin(kTwoPi * uniform53(c[1]));
-  xi[2] = r1 * cos(kTwoPi * uniform53(c[3]));
 }
 
 __global__ void __launch_bounds__(kChunkRows) k_pimd_init(PimdView st, int64_t chunks, const double* __restrict__ vel) {
@@ -99,13 +87,11 @@ __global__ void __launch_bounds__(kChunkRows) k_pimd_init(PimdView st, int64_t c
 
 __global__ void __launch_bounds__(kChunkRows) k_pimd_partials(PimdView st, double half_dt, const float* __restrict__ forces,
                                                               const double* __restrict__ pos) {
-  __shared__ double sh[kPimdPart][kChunkRows];
   const int c = blockIdx.x, t = threadIdx.x;
-  if (c >= st.ch.n_chunks()) return;
-  const int g = st.ch.structure(c);
-  const int fl = st.flags[g];
-  if (fl & M3G_DYN_ERROR) return;   // frozen: finalize reads nothing of it
-  const RingRow at = ring_row(st, c, g, t);
+  const ChunkRow row = chunk_row(st, c, t);
+  if (!row.live) return;
+  const int fl = row.fl;
+  const RingRow at = ring_row(st, row.s, row.i);
   double val[kPimdPart] = {0.0, 0.0, 0.0, 0.0};
   if (at.holds) {
     const int P = st.P;
@@ -129,7 +115,7 @@ __global__ void __launch_bounds__(kChunkRows) k_pimd_partials(PimdView st, doubl
         else d2 += (q[k] - prev[k]) * (q[k] - prev[k]);
         prev[k] = q[k];
       }
-      if (!(std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2]))) bad += 1.0;
+      if (!forces_finite(f)) bad += 1.0;
     }
     for (int k = 0; k < 3; ++k) d2 += (q0[k] - prev[k]) * (q0[k] - prev[k]);   // the bond that closes the ring (0 when P = 1)
     val[0] = m * v2;
@@ -137,8 +123,7 @@ __global__ void __launch_bounds__(kChunkRows) k_pimd_partials(PimdView st, doubl
     val[2] = qf;
     val[3] = bad;
   }
-  chunk_tree_reduce<kPimdPart>(sh, val, t);
-  if (t < kPimdPart) st.partial[kPimdPart * c + t] = sh[t][0];
+  reduce_store<kPimdPart>(val, c, t, st.partial);
 }
 
 __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_pimd_finalize(PimdView st, int32_t finish_only, double* __restrict__ obs) {
@@ -224,7 +209,7 @@ __global__ void __launch_bounds__(kChunkRows) k_pimd_apply(PimdView st, int32_t 
     }
     __syncthreads();
   }
-  const RingRow at = ring_row(st, c, g, t);
+  const RingRow at = ring_row(st, g, st.ch.row(c, t));
   double added[1] = {0.0};
   if (at.holds) {
     const double m = st.mass[at.first];
@@ -255,7 +240,7 @@ __global__ void __launch_bounds__(kChunkRows) k_pimd_apply(PimdView st, int32_t 
       for (int w = 0; w < P; ++w) {   // A(h) O(dt) A(h) of mode w
         const double cs = mode[w], sw = mode[P + w], ws = mode[2 * P + w], c1 = mode[3 * P + w], c2 = mode[4 * P + w];
         double xi[3] = {0.0, 0.0, 0.0};
-        if (thermostat == M3G_PIMD_PILE_L) mode_gaussian3(seed, start, (uint64_t)at.local, (uint64_t)w, xi);
+        if (thermostat == M3G_PIMD_PILE_L) gaussian3(seed, kPimdKey, start, (uint64_t)at.local, (uint64_t)w, xi);
         for (int k = 0; k < 3; ++k) {
           double xm = x[w * stride + k], vm = v[w * stride + k];
           for (int half = 0; half < 2; ++half) {
@@ -317,30 +302,22 @@ extern "C" int m3g_pimd_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t 
 }
 
 extern "C" int m3g_pimd_state_view(int64_t n_atoms, int64_t n_structs, int32_t n_beads, size_t* mass_offset, size_t* velocity_offset) {
-  if (!mass_offset || !velocity_offset || !ring_sizes_ok(n_atoms, n_structs, n_beads)) {
-    set_error("m3g_pimd_state_view: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
-  const PimdView at = pimd_view(n_atoms, n_structs, n_beads, nullptr).view;   // (over a null state: the offsets)
-  *mass_offset = carve_offset(at.mass);
-  *velocity_offset = carve_offset(at.v);
-  return M3G_OK;
+  return state_view_offsets("m3g_pimd_state_view", ring_sizes_ok(n_atoms, n_structs, n_beads),
+                            [&] { return pimd_view(n_atoms, n_structs, n_beads, nullptr).view; }, mass_offset, velocity_offset);
 }
 
 extern "C" int m3g_pimd_init(const m3g_pimd_params* p, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
                              const double* host_temperatures, const uint64_t* host_seeds, const double* vel, void* state, size_t state_bytes,
                              void* stream_) {
   if (const char* why = pimd_params_error(p)) { set_error("m3g_pimd_init: invalid parameters: %s", why); return M3G_ERR_VALUE; }
-  if (!batch_sizes_ok(n_atoms, n_structs) || !host_offsets || !host_masses || !host_temperatures || !host_seeds || !vel || !state) {
-    set_error("m3g_pimd_init: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
+  constexpr const char* fn = "m3g_pimd_init";
   const int64_t N = n_atoms, S = n_structs;
+  if (!init_args_ok(fn, N, S, host_offsets && host_masses && host_temperatures && host_seeds && vel && state)) return M3G_ERR_VALUE;
   const int P = p->n_beads;
   if (S % P != 0) { set_error("m3g_pimd_init: n_structs (%lld) is not a multiple of n_beads (%d)", (long long)S, P); return M3G_ERR_VALUE; }
-  if (!offsets_ok("m3g_pimd_init", host_offsets, N, S)) return M3G_ERR_VALUE;
+  if (!offsets_ok(fn, host_offsets, N, S)) return M3G_ERR_VALUE;
   for (int64_t i = 0; i < N; ++i)
-    if (!finite_positive(host_masses[i])) { set_error("m3g_pimd_init: mass of atom %lld is not finite and > 0", (long long)i); return M3G_ERR_VALUE; }
+    if (!mass_ok(fn, host_masses, i)) return M3G_ERR_VALUE;
   const int64_t R = S / P;
   std::vector<int64_t> ring_offsets(R + 1, 0);
   for (int64_t g = 0; g < R; ++g) {
@@ -357,14 +334,11 @@ extern "C" int m3g_pimd_init(const m3g_pimd_params* p, int64_t n_atoms, int64_t 
           return M3G_ERR_VALUE;
         }
     }
-    if (!finite_positive(host_temperatures[g])) {   // (the spring constant and the noise are proportional to it)
-      set_error("m3g_pimd_init: temperature of ring %lld is not finite and > 0", (long long)g);
-      return M3G_ERR_VALUE;
-    }
+    if (!temperature_ok(fn, host_temperatures, g, "ring")) return M3G_ERR_VALUE;   // (the spring constant and the noise are proportional to it)
     ring_offsets[g + 1] = ring_offsets[g] + n;
   }
   const auto [st, total] = pimd_view(N, S, P, state);
-  if (state_bytes < total) { set_error("m3g_pimd_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits(fn, state_bytes, total, true)) return M3G_ERR_SIZE;
   // the orthogonal matrix C[j][k] of the normal modes and, per ring, the coefficients of A(h) and O(dt) of every mode
   std::vector<double> table((size_t)P * P), mode((size_t)kPimdMode * P * R);
   const double h = 0.5 * p->dt;
@@ -394,17 +368,12 @@ extern "C" int m3g_pimd_init(const m3g_pimd_params* p, int64_t n_atoms, int64_t 
   }
   const ChunkTable chunks(ring_offsets.data(), R);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = chunks.upload(st.ch, ring_offsets.data(), s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync(st.mass, host_masses, 8 * N, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st.t0, host_temperatures, 8 * R, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st.seed, host_seeds, 8 * R, hipMemcpyHostToDevice, s));
+  if (int rc = upload_batch(chunks, st, ring_offsets.data(), host_masses, host_temperatures, host_seeds, s)) return rc;   // (per ring)
   M3G_HIP_CHECK(hipMemcpyAsync(st.table, table.data(), 8 * table.size(), hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync(st.mode, mode.data(), 8 * mode.size(), hipMemcpyHostToDevice, s));
   const int64_t work = 3 * N;   // (>= R and >= the chunk bound)
   hipLaunchKernelGGL(k_pimd_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, st, chunk_bound(N / P, R), vel);
-  M3G_HIP_CHECK(hipGetLastError());
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
-  return M3G_OK;
+  return launched_and_synced(s);   // (the host tables above go out of scope)
 }
 
 extern "C" int m3g_pimd_step(const m3g_pimd_params* p, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
@@ -415,13 +384,12 @@ extern "C" int m3g_pimd_step(const m3g_pimd_params* p, int64_t n_atoms, int64_t 
   if (!ring_sizes_ok(N, S, P) || !state) { set_error("m3g_pimd_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (!forces || !pos) { set_error("m3g_pimd_step: missing forces or pos"); return M3G_ERR_VALUE; }
   const auto [st, total] = pimd_view(N, S, P, state);
-  if (state_bytes < total) { set_error("m3g_pimd_step: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_pimd_step", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
-  const int64_t R = S / P;
   const double h = 0.5 * p->dt;
-  const dim3 grid((unsigned)chunk_bound(N / P, R));   // workgroups beyond the table's chunk count return at once
+  const auto [grid, waves] = step_grids(N / P, S / P);   // (over rings)
   hipLaunchKernelGGL(k_pimd_partials, grid, dim3(kChunkRows), 0, s, st, h, forces, pos);
-  hipLaunchKernelGGL(k_pimd_finalize, grid_for(R, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, finish_only, obs);
+  hipLaunchKernelGGL(k_pimd_finalize, waves, dim3(kFinalizeThreads), 0, s, st, finish_only, obs);
   if (P <= 8) hipLaunchKernelGGL(k_pimd_apply<8>, grid, dim3(kChunkRows), 0, s, st, p->thermostat, h, forces, pos);
   else if (P <= 16) hipLaunchKernelGGL(k_pimd_apply<16>, grid, dim3(kChunkRows), 0, s, st, p->thermostat, h, forces, pos);
   else if (P <= 32) hipLaunchKernelGGL(k_pimd_apply<32>, grid, dim3(kChunkRows), 0, s, st, p->thermostat, h, forces, pos);
@@ -434,13 +402,10 @@ extern "C" int m3g_pimd_read(int64_t n_atoms, int64_t n_structs, int32_t n_beads
   const int64_t N = n_atoms, S = n_structs;
   if (!ring_sizes_ok(N, S, n_beads) || !state) { set_error("m3g_pimd_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = pimd_view(N, S, n_beads, (void*)state);
-  if (state_bytes < total) { set_error("m3g_pimd_read: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_pimd_read", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
-  const int64_t R = S / n_beads;
-  M3G_HIP_CHECK(read_back(host_flags, st.flags, R, s));
-  M3G_HIP_CHECK(read_back(host_steps, st.steps, R, s));
-  M3G_HIP_CHECK(read_back(host_heat, st.heat, R, s));
-  M3G_HIP_CHECK(read_back(host_vel, st.v, 3 * N, s));
+  if (int rc = read_head(st, host_flags, host_steps, host_vel, s)) return rc;   // (flags and steps per ring)
+  M3G_HIP_CHECK(read_back(host_heat, st.heat, S / n_beads, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;
 }

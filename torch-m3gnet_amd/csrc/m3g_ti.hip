@@ -16,17 +16,17 @@
 //                  the atoms --, the work, the accumulators, the observables and the coefficients of the apply;
 //   k_ti_apply     one workgroup per chunk: the finish kick and B A O A of every atom by the constrained force.
 // No atomics: every result depends on the structure's own rows only, so it is bitwise the same alone or in any batch.  No allocation,
-// copy or wait in m3g_ti_step (capture-safe).
+// copy or wait in m3g_ti_step (capture-safe).  The Box-Muller draw and its key word, the epilogue of the partials and the checks and
+// copies of the entry points are m3g_integrator.h.
 #include <cmath>
 #include <vector>
 
-#include "m3g_dyn_state.h"
+#include "m3g_integrator.h"
 
 namespace m3g {
 namespace {
 constexpr int kTiPart = 12;   // per chunk: sum m |w|^2, sum m w [3], sum G [3], sum k |u|^2, sum m sigma xi [3], non-finite forces
 constexpr int kTiCoef = 12;   // per structure: action, finish kick?, lambda, sum G / M [3], pbar / M [3], sample?, noise^2, unused
-constexpr uint64_t kTiKey = 4;   // second Philox key word (0 .. 3: Langevin, replica exchange, swap Monte Carlo, path integrals)
 enum TiPath : int { kPathSwitch = 0, kPathDiscard = 1, kPathIndex = 2, kPathWords = 3 };   // per structure: n_switch, n_discard, c
 
 struct TiView {
@@ -64,18 +64,6 @@ inline Carved<TiView> ti_view(int64_t N, int64_t S, void* state) {
   st.flags = c.take<int32_t>(S);
   st.has_prev = c.take<int32_t>(S);
   return {st, c.off};
-}
-
-// three standard normals of atom `local` at start k of a structure seeded `seed`: the Box-Muller of gaussian3 in m3g_dynamics.hip
-// under key (seed, kTiKey)
-__device__ inline void ti_gaussian3(uint64_t seed, uint64_t k, uint64_t local, double xi[3]) {
-  uint64_t c[4] = {k, local, 0, 0};
-  philox4x64_10(c, seed, kTiKey);
-  constexpr double kTwoPi = 6.283185307179586;
-  const double r0 = sqrt(-2.0 * log(uniform53(c[0]))), r1 = sqrt(-2.0 * log(uniform53(c[2])));
-  xi[0] = r0 * cos(kTwoPi * uniform53(c[1]));
-  xi[1] = r0 * sin(kTwoPi * uniform53(c[1]));
-  xi[2] = r1 * cos(kTwoPi * uniform53(c[3]));
 }
 
 // lambda of structure s at its step index: lambda_b + (lambda_e - lambda_b) g(min(c, n_switch) / n_switch)
@@ -131,7 +119,6 @@ __global__ void __launch_bounds__(kChunkRows) k_ti_init(TiView st, const double*
 
 __global__ void __launch_bounds__(kChunkRows) k_ti_partials(TiView st, int32_t schedule, double half_dt, double c1, const float* __restrict__ forces,
                                                             const double* __restrict__ pos) {
-  __shared__ double sh[kTiPart][kChunkRows];
   const int c = blockIdx.x, t = threadIdx.x;
   if (c >= st.ch.n_chunks()) return;
   const int s = st.ch.structure(c);
@@ -159,14 +146,13 @@ __global__ void __launch_bounds__(kChunkRows) k_ti_partials(TiView st, int32_t s
     val[7] = k * u2;
     if (c1 < 1.0) {   // the momentum the noise of the coming O step carries (steps: the number of that start)
       double xi[3];
-      ti_gaussian3(st.seed[s], (uint64_t)st.steps[s], (uint64_t)(i - st.ch.offsets[s]), xi);
+      gaussian3(st.seed[s], kTiKey, (uint64_t)st.steps[s], (uint64_t)(i - st.ch.offsets[s]), 0, xi);   // (start, atom of its structure)
       const double sigma = sqrt((1.0 - c1 * c1) * kBoltzmann * st.t0[s] * kKappa / m);
       for (int a = 0; a < 3; ++a) val[8 + a] = m * (sigma * xi[a]);
     }
     val[11] = (std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2])) ? 0.0 : 1.0;
   }
-  chunk_tree_reduce<kTiPart>(sh, val, t);
-  if (t < kTiPart) st.partial[kTiPart * c + t] = sh[t][0];
+  reduce_store<kTiPart>(val, c, t, st.partial);
 }
 
 __global__ void __launch_bounds__(kWave * kFinalizeWaves) k_ti_finalize(TiView st, int32_t schedule, int32_t finish_only, double half_dt,
@@ -274,7 +260,7 @@ __global__ void __launch_bounds__(kChunkRows) k_ti_apply(TiView st, double h, do
     return;
   }
   double xi[3] = {0.0, 0.0, 0.0};
-  if (c1 < 1.0) ti_gaussian3(st.seed[s], (uint64_t)(st.steps[s] - 1), (uint64_t)(i - st.ch.offsets[s]), xi);
+  if (c1 < 1.0) gaussian3(st.seed[s], kTiKey, (uint64_t)(st.steps[s] - 1), (uint64_t)(i - st.ch.offsets[s]), 0, xi);
   const double sigma = sqrt(coef[10] / m);
   for (int j = 0; j < 3; ++j) {   // B A O A
     v[j] += h * a[j];
@@ -312,29 +298,21 @@ extern "C" int m3g_ti_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* by
 }
 
 extern "C" int m3g_ti_state_view(int64_t n_atoms, int64_t n_structs, size_t* mass_offset, size_t* velocity_offset) {
-  if (!mass_offset || !velocity_offset || !ti_sizes_ok(n_atoms, n_structs)) {
-    set_error("m3g_ti_state_view: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
-  const TiView at = ti_view(n_atoms, n_structs, nullptr).view;   // (over a null state: the offsets)
-  *mass_offset = carve_offset(at.mass);
-  *velocity_offset = carve_offset(at.v);
-  return M3G_OK;
+  return state_view_offsets("m3g_ti_state_view", ti_sizes_ok(n_atoms, n_structs), [&] { return ti_view(n_atoms, n_structs, nullptr).view; },
+                            mass_offset, velocity_offset);
 }
 
 extern "C" int m3g_ti_init(const m3g_ti_params* p, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_masses,
                            const double* host_springs, const double* host_temperatures, const uint64_t* host_seeds, const double* vel,
                            const double* reference, void* state, size_t state_bytes, void* stream_) {
   if (const char* why = ti_params_error(p)) { set_error("m3g_ti_init: invalid parameters: %s", why); return M3G_ERR_VALUE; }
-  if (!batch_sizes_ok(n_atoms, n_structs) || !host_offsets || !host_masses || !host_springs || !host_temperatures || !host_seeds || !vel ||
-      !reference || !state) {
-    set_error("m3g_ti_init: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
+  constexpr const char* fn = "m3g_ti_init";
   const int64_t N = n_atoms, S = n_structs;
-  if (!offsets_ok("m3g_ti_init", host_offsets, N, S)) return M3G_ERR_VALUE;
+  if (!init_args_ok(fn, N, S, host_offsets && host_masses && host_springs && host_temperatures && host_seeds && vel && reference && state))
+    return M3G_ERR_VALUE;
+  if (!offsets_ok(fn, host_offsets, N, S)) return M3G_ERR_VALUE;
   for (int64_t i = 0; i < N; ++i) {
-    if (!finite_positive(host_masses[i])) { set_error("m3g_ti_init: mass of atom %lld is not finite and > 0", (long long)i); return M3G_ERR_VALUE; }
+    if (!mass_ok(fn, host_masses, i)) return M3G_ERR_VALUE;
     if (!(std::isfinite(host_springs[i]) && host_springs[i] >= 0.0)) {
       set_error("m3g_ti_init: spring constant of atom %lld is not finite and >= 0", (long long)i);
       return M3G_ERR_VALUE;
@@ -346,10 +324,7 @@ extern "C" int m3g_ti_init(const m3g_ti_params* p, int64_t n_atoms, int64_t n_st
       set_error("m3g_ti_init: structure %lld needs at least two atoms (the held centre of mass leaves 3 n - 3 degrees of freedom)", (long long)s);
       return M3G_ERR_VALUE;
     }
-    if (!finite_positive(host_temperatures[s])) {
-      set_error("m3g_ti_init: temperature of structure %lld is not finite and > 0", (long long)s);
-      return M3G_ERR_VALUE;
-    }
+    if (!temperature_ok(fn, host_temperatures, s)) return M3G_ERR_VALUE;
     double m = 0.0, k = 0.0;
     for (int64_t i = host_offsets[s]; i < host_offsets[s + 1]; ++i) {
       m += host_masses[i];
@@ -359,20 +334,15 @@ extern "C" int m3g_ti_init(const m3g_ti_params* p, int64_t n_atoms, int64_t n_st
     mtot[s] = m;
   }
   const auto [st, total] = ti_view(N, S, state);
-  if (state_bytes < total) { set_error("m3g_ti_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits(fn, state_bytes, total, true)) return M3G_ERR_SIZE;
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync(st.mass, host_masses, 8 * N, hipMemcpyHostToDevice, s));
+  if (int rc = upload_batch(table, st, host_offsets, host_masses, host_temperatures, host_seeds, s)) return rc;
   M3G_HIP_CHECK(hipMemcpyAsync(st.spring, host_springs, 8 * N, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st.t0, host_temperatures, 8 * S, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync(st.mtot, mtot.data(), 8 * S, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipMemcpyAsync(st.seed, host_seeds, 8 * S, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_ti_init, grid_for(3 * N, kChunkRows), dim3(kChunkRows), 0, s, st, vel, reference);   // (3 N >= S)
   hipLaunchKernelGGL(k_ti_path, dim3((unsigned)chunk_bound(N, S)), dim3(kChunkRows), 0, s, st, (int64_t)0, (int64_t)0, 1);
-  M3G_HIP_CHECK(hipGetLastError());
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
-  return M3G_OK;
+  return launched_and_synced(s);   // (the host tables above go out of scope)
 }
 
 extern "C" int m3g_ti_path(int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const double* host_lambda_begin,
@@ -384,14 +354,12 @@ extern "C" int m3g_ti_path(int64_t n_atoms, int64_t n_structs, void* state, size
     for (const double lam : {host_lambda_begin[s], host_lambda_end[s]})
       if (!(lam >= 0.0 && lam <= 1.0)) { set_error("m3g_ti_path: lambda of structure %lld is not in [0, 1]", (long long)s); return M3G_ERR_VALUE; }
   const auto [st, total] = ti_view(N, S, state);
-  if (state_bytes < total) { set_error("m3g_ti_path: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_ti_path", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   M3G_HIP_CHECK(hipMemcpyAsync(st.lam_b, host_lambda_begin, 8 * S, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync(st.lam_e, host_lambda_end, 8 * S, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_ti_path, dim3((unsigned)chunk_bound(N, S)), dim3(kChunkRows), 0, s, st, n_switch, n_discard, 0);
-  M3G_HIP_CHECK(hipGetLastError());
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the caller's host arrays)
-  return M3G_OK;
+  return launched_and_synced(s);   // (the caller's host arrays)
 }
 
 extern "C" int m3g_ti_step(const m3g_ti_params* p, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
@@ -401,14 +369,13 @@ extern "C" int m3g_ti_step(const m3g_ti_params* p, int64_t n_atoms, int64_t n_st
   if (!ti_sizes_ok(N, S) || !state) { set_error("m3g_ti_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (!forces || !energies || !pos) { set_error("m3g_ti_step: missing forces, energies or pos"); return M3G_ERR_VALUE; }
   const auto [st, total] = ti_view(N, S, state);
-  if (state_bytes < total) { set_error("m3g_ti_step: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_ti_step", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   const double h = 0.5 * p->dt, c1 = std::exp(-p->friction * p->dt);   // (friction 0: c1 = 1, no noise drawn)
-  const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
-  hipLaunchKernelGGL(k_ti_partials, grid, dim3(kChunkRows), 0, s, st, p->schedule, h, c1, forces, pos);
-  hipLaunchKernelGGL(k_ti_finalize, grid_for(S, kFinalizeWaves), dim3(kWave * kFinalizeWaves), 0, s, st, p->schedule, finish_only, h, c1,
-                     energies, obs);
-  hipLaunchKernelGGL(k_ti_apply, grid, dim3(kChunkRows), 0, s, st, h, c1, forces, pos);
+  const auto [chunks, waves] = step_grids(N, S);
+  hipLaunchKernelGGL(k_ti_partials, chunks, dim3(kChunkRows), 0, s, st, p->schedule, h, c1, forces, pos);
+  hipLaunchKernelGGL(k_ti_finalize, waves, dim3(kFinalizeThreads), 0, s, st, p->schedule, finish_only, h, c1, energies, obs);
+  hipLaunchKernelGGL(k_ti_apply, chunks, dim3(kChunkRows), 0, s, st, h, c1, forces, pos);
   M3G_RETURN_LAUNCH_STATUS();
 }
 
@@ -418,15 +385,13 @@ extern "C" int m3g_ti_read(int64_t n_atoms, int64_t n_structs, const void* state
   const int64_t N = n_atoms, S = n_structs;
   if (!ti_sizes_ok(N, S) || !state) { set_error("m3g_ti_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = ti_view(N, S, (void*)state);
-  if (state_bytes < total) { set_error("m3g_ti_read: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_ti_read", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
-  M3G_HIP_CHECK(read_back(host_steps, st.steps, S, s));
+  if (int rc = read_head(st, host_flags, host_steps, host_vel, s)) return rc;
   M3G_HIP_CHECK(read_back(host_work, st.work, S, s));
   M3G_HIP_CHECK(read_back(host_count, st.count, S, s));
   M3G_HIP_CHECK(read_back(host_mean, st.mean, S, s));
   M3G_HIP_CHECK(read_back(host_m2, st.m2, S, s));
-  M3G_HIP_CHECK(read_back(host_vel, st.v, 3 * N, s));
   M3G_HIP_CHECK(read_back(host_msd_sum, st.msd, N, s));
   M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;

@@ -1,5 +1,6 @@
 """What the batched drivers (relax, dynamics, replica_exchange, monte_carlo, trajectory, neb, phonons, elasticity) share on the host:
-argument checks, the model every driver evaluates, state allocation and read-back, the split of one structure's copies into engine
+argument checks, the model every driver evaluates, state allocation and read-back, the device state of the five MD step families
+(`IntegratorState`: dynamics, path_integral, free_energy), the split of one structure's copies into engine
 sub-batches, the evaluation of a batch in engine groups (`GroupedEvaluation`: replica_exchange, monte_carlo) and the log and result
 dicts of an MD run (`MdLog`, `md_result`: dynamics, replica_exchange).  The optimiser loop relax and neb share is `relax.fire_loop`,
 beside `fire_step` / `lbfgs_step`; the status read after the last evaluation is `VerletGraph.raise_on_step_errors`."""
@@ -132,6 +133,84 @@ def read_state(read, sizes: tuple, state: torch.Tensor, fields) -> dict:
     with _cuda.on_device(state.device):
         _lib.check(read(*sizes, _ptr(state), state.numel(), *(a.ctypes.data for a in out.values()), _stream()))
     return out
+
+
+class IntegratorState:
+    """What the device states of the five MD step families share (`DynState`, `NhcState`, `MtkCellState`, `PimdState`, `TiState`; C
+    ABI m3g_<FAMILY>_*, device side csrc/m3g_integrator.h).  A subclass's constructor sets `params`, then calls, between its own
+    checks, `_layout`, `_rows`, `_host_arrays`, `_allocate` and `_init`; it supplies `_fields()` for `read()`."""
+    FAMILY = ""      # "dyn": the entry points m3g_dyn_state_bytes, _state_view, _init, _step and _read
+    OBS = 0          # columns of an `obs` row
+    CELLS = False    # the step takes the lattice and its fp32 copy
+    SECOND = None    # the step's float32 input after the forces: (name, shape of a structure's row, ValueError text if it is required)
+
+    def _entry(self, name: str):
+        return getattr(self.lib, f"m3g_{self.FAMILY}_{name}")
+
+    def _layout(self, pos: torch.Tensor, lattice: torch.Tensor | None, offsets) -> None:
+        """offsets, N, S of the batch over the caller's `pos` / `lattice` (moved in place), and `lattice32`, the fp32 copy of the cells."""
+        self.offsets, self.N, self.S = batch_layout(pos, lattice, offsets)
+        self.pos, self.lattice = pos, lattice
+        self.lattice32 = lattice.to(torch.float32) if lattice is not None else None
+        self.device = pos.device
+
+    def _rows(self, name: str, x: torch.Tensor) -> None:
+        if x.dtype != torch.float64 or tuple(x.shape) != (self.N, 3) or x.device != self.pos.device:
+            raise ValueError(f"{name} must be a [{self.N}, 3] float64 tensor on {self.pos.device}")
+
+    def _host_arrays(self, masses, temperatures, seeds=None, units: int | None = None) -> bool:
+        """`masses` [N], `temperatures` and (where the family draws) `seeds`, one per unit (structure; `units`: ring), as contiguous
+        host arrays; whether the masses and seeds have those lengths."""
+        units = self.S if units is None else units
+        self.masses = np.ascontiguousarray(np.asarray(masses, dtype=np.float64).reshape(-1))
+        self.temperatures = np.ascontiguousarray(np.broadcast_to(np.asarray(temperatures, dtype=np.float64), (units,)))
+        if seeds is not None:
+            self.seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+        return len(self.masses) == self.N and (seeds is None or len(self.seeds) == units)
+
+    def _allocate(self, state_tensor, *sizes, units: int | None = None) -> None:
+        """The state tensor of the family's `state_bytes(*sizes)` from `state_tensor` (the name the subclass's module imported: every
+        driver module allocates through its own), the NaN `obs` [units, OBS] and `velocities`, the live [N,3] fp64 view of the
+        integrator's own velocities inside the state (the family's `state_view`)."""
+        self.sizes = sizes
+        self.lib = _lib.load_library()
+        self.state = state_tensor(self._entry("state_bytes"), *sizes, device=self.device)
+        self.obs = torch.full((self.S if units is None else units, self.OBS), float("nan"), dtype=torch.float64, device=self.device)
+        # what every step call passes unchanged: the entry point, and pointers to what is this object's own (not the caller's tensors)
+        self._step, self._step_head = self._entry("step"), (C.byref(self.params), self.N, self.S, _ptr(self.state), self.state.numel())
+        self._own = (_ptr(self.lattice32), _ptr(self.obs))
+        mass_at, vel_at = C.c_size_t(), C.c_size_t()
+        _lib.check(self._entry("state_view")(*sizes, C.byref(mass_at), C.byref(vel_at)))
+        self.velocities = self.state[vel_at.value:vel_at.value + 24 * self.N].view(torch.float64).view(self.N, 3)
+
+    def _init(self, *arrays) -> None:
+        """The family's init: (params, N, S, offsets, masses, *arrays, state, bytes, stream); host arrays and device tensors (copied)."""
+        held = [a if isinstance(a, np.ndarray) else a.contiguous() for a in arrays]
+        with _cuda.on_device(self.device):
+            _lib.check(self._entry("init")(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, self.masses.ctypes.data,
+                                           *(a.ctypes.data if isinstance(a, np.ndarray) else _ptr(a) for a in held), _ptr(self.state),
+                                           self.state.numel(), _stream()))
+
+    def read(self) -> dict:
+        """The arrays `_fields()` lists, copied to the host by the family's read (waits for the stream)."""
+        return read_state(self._entry("read"), self.sizes, self.state, self._fields())
+
+    def step(self, forces: torch.Tensor, finish_only: bool, second: torch.Tensor | None = None) -> None:
+        """The family's step at `forces` [N,3] float32 and, where the family has SECOND = (name, row shape, needed), at `second`
+        [S, *row shape] float32: None goes on as a null pointer unless `needed`, the ValueError text for a missing one, is set."""
+        check_tensor("forces", forces, (self.N, 3), torch.float32)
+        inputs = (_ptr(forces),)
+        if self.SECOND is not None:
+            name, row, needed = self.SECOND
+            if second is not None:
+                check_tensor(name, second, (self.S,) + row, torch.float32)
+            elif needed:
+                raise ValueError(needed)
+            inputs = (_ptr(forces), _ptr(second))
+        lattice32, obs = self._own
+        cells = (_ptr(self.lattice), lattice32) if self.CELLS else ()
+        with _cuda.on_device(self.device):
+            _lib.check(self._step(*self._step_head, *inputs, _ptr(self.pos), *cells, 1 if finish_only else 0, obs, _stream()))
 
 
 def sub_batches(n_copies: int, n: int, max_atoms: int):

@@ -16,18 +16,16 @@ Units: A, fs, amu, eV; velocities in A/fs; `MolecularDynamics` takes the pressur
 NPTBerendsen convention), the C ABI in eV/A^3 and A^3/eV."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Sequence
 
 import numpy as np
 import torch
 
-from . import _cuda, _lib
-from ._driver import (EV_A3_TO_GPA, Driver, MdLog, atom_offsets, batch_layout, check_tensor, integer, md_result, non_negative,
-                      per_structure, positive, read_state, state_tensor, structure_arrays, structure_masses)
+from . import _lib
+from ._driver import (EV_A3_TO_GPA, Driver, IntegratorState, MdLog, atom_offsets, integer, md_result, non_negative, per_structure,
+                      positive, state_tensor, structure_arrays, structure_masses)
 from .data import MaterialGraphKey as K
-from .data.graph_gpu import _ptr, _stream
 from .data.md import VerletGraph
 from .nn.modules import Gradient
 from .trajectory import TrajectoryObservables, traj_sample
@@ -69,7 +67,7 @@ def structure_seeds(seed, n_structs: int) -> np.ndarray:
     return np.array([np.random.SeedSequence([int(seed), s]).generate_state(1, np.uint64)[0] for s in range(n_structs)], dtype=np.uint64)
 
 
-class DynState:
+class DynState(IntegratorState):
     """MD state of a batch on the device (m3g_dyn_init): masses, velocities (fp64), target temperatures, seeds, flags and step counts.
     `pos` ([N,3] fp64, unwrapped) and `lattice` ([S,3,3] fp64, may be None except in NPT) are the caller's tensors: `dyn_step` moves
     them IN PLACE (and `lattice32`, their fp32 copy).  The `velocities` ARGUMENT [N,3] fp64 device holds the starting velocities: copied.  `offsets`: S + 1 atom offsets, strictly
@@ -77,6 +75,7 @@ class DynState:
     A^3/eV.  `obs` [S,4] (KE eV, T K, P eV/A^3, V A^3) is written by every `dyn_step`.  The `velocities` ATTRIBUTE is not the
     argument: it is a live [N,3] fp64 view into the state buffer, the integrator's own velocities on the device (between two
     `dyn_step` calls the half-step velocities of the step under way), which every `dyn_step` changes."""
+    FAMILY, OBS, CELLS, SECOND = "dyn", 4, True, ("stresses", (6,), None)
 
     def __init__(self, pos: torch.Tensor, lattice: torch.Tensor | None, offsets: Sequence[int], masses, velocities: torch.Tensor,
                  temperatures, seeds, ensemble: str = "nve", dt: float = 1.0, taut: float = 100.0, friction: float = 0.01,
@@ -86,51 +85,28 @@ class DynState:
         self.ensemble = ensemble
         self.params = _lib.M3GDynParams(ensemble=ENSEMBLES[ensemble], fix_com=1 if fix_com else 0, dt=dt, taut=taut, friction=friction,
                                         pressure=pressure, taup=taup, compressibility=compressibility)
-        self.offsets, self.N, self.S = batch_layout(pos, lattice, offsets)
+        self._layout(pos, lattice, offsets)
         if ensemble == "npt_berendsen" and lattice is None:
             raise ValueError("NPT needs the lattice")
-        if velocities.dtype != torch.float64 or tuple(velocities.shape) != (self.N, 3) or velocities.device != pos.device:
-            raise ValueError(f"velocities must be a [{self.N}, 3] float64 tensor on {pos.device}")
-        self.masses = np.ascontiguousarray(np.asarray(masses, dtype=np.float64).reshape(-1))
-        self.temperatures = np.ascontiguousarray(np.broadcast_to(np.asarray(temperatures, dtype=np.float64), (self.S,)))
-        self.seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
-        if len(self.masses) != self.N or len(self.seeds) != self.S:
+        self._rows("velocities", velocities)
+        if not self._host_arrays(masses, temperatures, seeds):
             raise ValueError(f"expected {self.N} masses and {self.S} seeds")
-        self.pos, self.lattice = pos, lattice
-        self.lattice32 = lattice.to(torch.float32) if lattice is not None else None
-        self.device = pos.device
-        self.lib = _lib.load_library()
-        self.state = state_tensor(self.lib.m3g_dyn_state_bytes, self.N, self.S, device=self.device)
-        self.obs = torch.full((self.S, 4), float("nan"), dtype=torch.float64, device=self.device)
-        mass_at, vel_at = C.c_size_t(), C.c_size_t()
-        _lib.check(self.lib.m3g_dyn_state_view(self.N, self.S, C.byref(mass_at), C.byref(vel_at)))
-        self.velocities = self.state[vel_at.value:vel_at.value + 24 * self.N].view(torch.float64).view(self.N, 3)
-        vel = velocities.contiguous()
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_dyn_init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, self.masses.ctypes.data,
-                                             self.temperatures.ctypes.data, self.seeds.ctypes.data, _ptr(vel), _ptr(self.state),
-                                             self.state.numel(), _stream()))
+        self._allocate(state_tensor, self.N, self.S)
+        self._init(self.temperatures, self.seeds, velocities)
 
-    def read(self) -> dict:
-        """flags / n_steps [S] and the velocities [N, 3], copied to the host (waits for the stream)."""
-        return read_state(self.lib.m3g_dyn_read, (self.N, self.S), self.state,
-                          (("flags", np.int32, self.S), ("n_steps", np.int64, self.S), ("v", np.float64, (self.N, 3))))
+    def _fields(self):
+        """`read()`: flags / n_steps [S] and the velocities [N, 3], copied to the host (waits for the stream)."""
+        return ("flags", np.int32, self.S), ("n_steps", np.int64, self.S), ("v", np.float64, (self.N, 3))
 
 
 def dyn_step(state: DynState, forces: torch.Tensor, stresses: torch.Tensor | None = None, finish_only: bool = False) -> None:
     """One MD call of the batch (m3g_dyn_step) at `forces` [N,3] and `stresses` [S,6] (float32, pair-virial convention; required in
     NPT) evaluated at `state.pos`: finish the step that ends here, write `state.obs`, start the next one (not with `finish_only`).
     Queued on the current stream; no wait, capture-safe."""
-    check_tensor("forces", forces, (state.N, 3), torch.float32)
-    if stresses is not None:
-        check_tensor("stresses", stresses, (state.S, 6), torch.float32)
-    with _cuda.on_device(state.device):
-        _lib.check(state.lib.m3g_dyn_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
-                                          _ptr(stresses), _ptr(state.pos), _ptr(state.lattice), _ptr(state.lattice32), 1 if finish_only else 0,
-                                          _ptr(state.obs), _stream()))
+    state.step(forces, finish_only, stresses)
 
 
-class NhcState:
+class NhcState(IntegratorState):
     """State of a Nose-Hoover chain NVT ("nvt_nose_hoover") or MTK NPT ("npt_mtk") batch on the device (m3g_nhc_init), shaped like
     `DynState`: `pos` [N,3] fp64 and `lattice` [S,3,3] fp64 (may be None in NVT) are the caller's tensors, moved IN PLACE by `nhc_step`
     (with `lattice32`, the fp32 copy of the cells); the `velocities` argument is copied, the `velocities` attribute is the live
@@ -139,6 +115,7 @@ class NhcState:
     proportional to it.  `obs` [S,6] (KE eV, T K, P eV/A^3, V A^3, extended eV, 0) is written by every `nhc_step`; T = 2 KE / (3 n kB)
     as in the other ensembles, so its canonical mean is T0 g / (3 n) with g = 3 n - 3 under `fix_com`.  E_pot + KE + extended is
     the conserved quantity."""
+    FAMILY, OBS, CELLS, SECOND = "nhc", _lib.NHC_OBS, True, ("stresses", (6,), None)
 
     def __init__(self, pos: torch.Tensor, lattice: torch.Tensor | None, offsets: Sequence[int], masses, velocities: torch.Tensor,
                  temperatures, ensemble: str = "nvt_nose_hoover", dt: float = 1.0, taut: float = 100.0, pressure: float = 0.0,
@@ -150,50 +127,29 @@ class NhcState:
         self.params = _lib.M3GNhcParams(ensemble=NHC_ENSEMBLES[ensemble], fix_com=1 if fix_com else 0, chain_length=self.chain_length,
                                         chain_substeps=chain_count("chain_substeps", chain_substeps), dt=dt, taut=taut, pressure=pressure,
                                         taup=taup)
-        self.offsets, self.N, self.S = batch_layout(pos, lattice, offsets)
+        self._layout(pos, lattice, offsets)
         if ensemble == "npt_mtk" and lattice is None:
             raise ValueError("NPT needs the lattice")
-        if velocities.dtype != torch.float64 or tuple(velocities.shape) != (self.N, 3) or velocities.device != pos.device:
-            raise ValueError(f"velocities must be a [{self.N}, 3] float64 tensor on {pos.device}")
-        self.masses = np.ascontiguousarray(np.asarray(masses, dtype=np.float64).reshape(-1))
-        self.temperatures = np.ascontiguousarray(np.broadcast_to(np.asarray(temperatures, dtype=np.float64), (self.S,)))
-        if len(self.masses) != self.N:
+        self._rows("velocities", velocities)
+        if not self._host_arrays(masses, temperatures):
             raise ValueError(f"expected {self.N} masses")
-        self.pos, self.lattice = pos, lattice
-        self.lattice32 = lattice.to(torch.float32) if lattice is not None else None
-        self.device = pos.device
-        self.lib = _lib.load_library()
-        self.state = state_tensor(self.lib.m3g_nhc_state_bytes, self.N, self.S, self.chain_length, device=self.device)
-        self.obs = torch.full((self.S, _lib.NHC_OBS), float("nan"), dtype=torch.float64, device=self.device)
-        mass_at, vel_at = C.c_size_t(), C.c_size_t()
-        _lib.check(self.lib.m3g_nhc_state_view(self.N, self.S, self.chain_length, C.byref(mass_at), C.byref(vel_at)))
-        self.velocities = self.state[vel_at.value:vel_at.value + 24 * self.N].view(torch.float64).view(self.N, 3)
-        vel = velocities.contiguous()
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_nhc_init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, self.masses.ctypes.data,
-                                             self.temperatures.ctypes.data, _ptr(vel), _ptr(self.state), self.state.numel(), _stream()))
+        self._allocate(state_tensor, self.N, self.S, self.chain_length)
+        self._init(self.temperatures, velocities)
 
-    def read(self) -> dict:
-        """flags / n_steps [S], the velocities [N, 3] and the chain rows [S, 4 M + 1] (xi, vxi, xib, vxib of the M thermostats, then
-        veps), copied to the host (waits for the stream)."""
-        return read_state(self.lib.m3g_nhc_read, (self.N, self.S, self.chain_length), self.state,
-                          (("flags", np.int32, self.S), ("n_steps", np.int64, self.S), ("v", np.float64, (self.N, 3)),
-                           ("chain", np.float64, (self.S, 4 * self.chain_length + 1))))
+    def _fields(self):
+        """`read()`: flags / n_steps [S], the velocities [N, 3] and the chain rows [S, 4 M + 1] (xi, vxi, xib, vxib of the M
+        thermostats, then veps), copied to the host (waits for the stream)."""
+        return (("flags", np.int32, self.S), ("n_steps", np.int64, self.S), ("v", np.float64, (self.N, 3)),
+                ("chain", np.float64, (self.S, 4 * self.chain_length + 1)))
 
 
 def nhc_step(state: NhcState, forces: torch.Tensor, stresses: torch.Tensor | None = None, finish_only: bool = False) -> None:
     """One MD call of the batch (m3g_nhc_step), the arguments of `dyn_step`: finish the step that ends at these forces, write
     `state.obs`, start the next one (not with `finish_only`).  Three launches, queued on the current stream; no wait, capture-safe."""
-    check_tensor("forces", forces, (state.N, 3), torch.float32)
-    if stresses is not None:
-        check_tensor("stresses", stresses, (state.S, 6), torch.float32)
-    with _cuda.on_device(state.device):
-        _lib.check(state.lib.m3g_nhc_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
-                                          _ptr(stresses), _ptr(state.pos), _ptr(state.lattice), _ptr(state.lattice32), 1 if finish_only else 0,
-                                          _ptr(state.obs), _stream()))
+    state.step(forces, finish_only, stresses)
 
 
-class MtkCellState:
+class MtkCellState(IntegratorState):
     """State of a flexible-cell MTK NPT ("npt_mtk_cell") batch on the device (m3g_mtk_init), shaped like `NhcState`: `pos` [N,3] fp64
     and `lattice` [S,3,3] fp64 (triclinic cells welcome) are the caller's tensors, moved IN PLACE by `mtk_cell_step` (with `lattice32`,
     the fp32 copy of the cells); the `velocities` argument is copied, the `velocities` attribute is the live [N,3] fp64 view of the
@@ -202,6 +158,7 @@ class MtkCellState:
     `obs` [S,12] (KE eV, T K, P eV/A^3, V A^3, extended eV, 0, then the pressure tensor in Voigt order xx, yy, zz, yz, zx, xy) is
     written by every `mtk_cell_step`; E_pot + KE + extended is the conserved quantity.  A structure whose cell rate times dt passes
     0.05 is flagged like one with non-finite forces or stresses, and frozen."""
+    FAMILY, OBS, CELLS, SECOND = "mtk", _lib.MTK_OBS, True, ("stresses", (6,), "npt_mtk_cell needs the stresses")
 
     def __init__(self, pos: torch.Tensor, lattice: torch.Tensor, offsets: Sequence[int], masses, velocities: torch.Tensor, temperatures,
                  cell_mask: str = "full", dt: float = 1.0, taut: float = 100.0, pressure: float = 0.0, taup: float = 1000.0,
@@ -214,47 +171,25 @@ class MtkCellState:
                                         taup=taup)
         if lattice is None:
             raise ValueError("NPT needs the lattice")
-        self.offsets, self.N, self.S = batch_layout(pos, lattice, offsets)
-        if velocities.dtype != torch.float64 or tuple(velocities.shape) != (self.N, 3) or velocities.device != pos.device:
-            raise ValueError(f"velocities must be a [{self.N}, 3] float64 tensor on {pos.device}")
-        self.masses = np.ascontiguousarray(np.asarray(masses, dtype=np.float64).reshape(-1))
-        self.temperatures = np.ascontiguousarray(np.broadcast_to(np.asarray(temperatures, dtype=np.float64), (self.S,)))
-        if len(self.masses) != self.N:
+        self._layout(pos, lattice, offsets)
+        self._rows("velocities", velocities)
+        if not self._host_arrays(masses, temperatures):
             raise ValueError(f"expected {self.N} masses")
-        self.pos, self.lattice = pos, lattice
-        self.lattice32 = lattice.to(torch.float32)
-        self.device = pos.device
-        self.lib = _lib.load_library()
-        self.state = state_tensor(self.lib.m3g_mtk_state_bytes, self.N, self.S, self.chain_length, device=self.device)
-        self.obs = torch.full((self.S, _lib.MTK_OBS), float("nan"), dtype=torch.float64, device=self.device)
-        mass_at, vel_at = C.c_size_t(), C.c_size_t()
-        _lib.check(self.lib.m3g_mtk_state_view(self.N, self.S, self.chain_length, C.byref(mass_at), C.byref(vel_at)))
-        self.velocities = self.state[vel_at.value:vel_at.value + 24 * self.N].view(torch.float64).view(self.N, 3)
-        vel = velocities.contiguous()
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_mtk_init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, self.masses.ctypes.data,
-                                             self.temperatures.ctypes.data, _ptr(vel), _ptr(self.state), self.state.numel(), _stream()))
+        self._allocate(state_tensor, self.N, self.S, self.chain_length)
+        self._init(self.temperatures, velocities)
 
-    def read(self) -> dict:
-        """flags / n_steps [S], the velocities [N, 3] and the chain rows [S, 4 M + 6] (xi, vxi, xib, vxib of the M thermostats, then
-        the six components of the cell rate vg), copied to the host (waits for the stream)."""
-        return read_state(self.lib.m3g_mtk_read, (self.N, self.S, self.chain_length), self.state,
-                          (("flags", np.int32, self.S), ("n_steps", np.int64, self.S), ("v", np.float64, (self.N, 3)),
-                           ("chain", np.float64, (self.S, 4 * self.chain_length + 6))))
+    def _fields(self):
+        """`read()`: flags / n_steps [S], the velocities [N, 3] and the chain rows [S, 4 M + 6] (xi, vxi, xib, vxib of the M
+        thermostats, then the six components of the cell rate vg), copied to the host (waits for the stream)."""
+        return (("flags", np.int32, self.S), ("n_steps", np.int64, self.S), ("v", np.float64, (self.N, 3)),
+                ("chain", np.float64, (self.S, 4 * self.chain_length + 6)))
 
 
 def mtk_cell_step(state: MtkCellState, forces: torch.Tensor, stresses: torch.Tensor, finish_only: bool = False) -> None:
     """One MD call of the batch (m3g_mtk_step), the arguments of `nhc_step` (the stresses are required): finish the step that ends
     at these forces, write `state.obs`, start the next one (not with `finish_only`).  Three launches, queued on the current stream;
     no wait, capture-safe."""
-    check_tensor("forces", forces, (state.N, 3), torch.float32)
-    if stresses is None:
-        raise ValueError("npt_mtk_cell needs the stresses")
-    check_tensor("stresses", stresses, (state.S, 6), torch.float32)
-    with _cuda.on_device(state.device):
-        _lib.check(state.lib.m3g_mtk_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
-                                          _ptr(stresses), _ptr(state.pos), _ptr(state.lattice), _ptr(state.lattice32), 1 if finish_only else 0,
-                                          _ptr(state.obs), _stream()))
+    state.step(forces, finish_only, stresses)
 
 
 def cell_mask_name(x) -> str:

@@ -17,7 +17,6 @@ reference), reversible-scaling temperature sweeps, and quantum corrections (clas
 Units as in `dynamics`: A, fs, amu, eV, K; spring constants in eV/A^2."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Sequence
 
@@ -25,8 +24,8 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import (Driver, GroupedEvaluation, batch_layout, boolean, check_tensor, integer, non_negative, positive, read_state,
-                      state_tensor, structure_arrays, structure_masses)
+from ._driver import (Driver, GroupedEvaluation, IntegratorState, boolean, integer, non_negative, positive, state_tensor,
+                      structure_arrays, structure_masses)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
 from .dynamics import KAPPA, KB, maxwell_boltzmann, structure_seeds
@@ -65,7 +64,7 @@ def einstein_free_energy(masses, spring_constants, temperature: float, volume: f
             "f_com": float(1.5 * kt * math.log(2.0 * math.pi * s2) + kt * math.log(n_cells / volume))}
 
 
-class TiState:
+class TiState(IntegratorState):
     """State of a thermodynamic-integration batch on the device (m3g_ti_init), shaped like `PimdState`: `pos` [N,3] fp64 (unwrapped)
     is the caller's tensor, moved IN PLACE by `ti_step`; the `velocities` and `reference` arguments [N,3] fp64 are copied, the
     `velocities` attribute is the live view of the integrator's own.  `offsets`: S + 1 atom offsets (two atoms per structure at
@@ -73,43 +72,27 @@ class TiState:
     (or one temperature for all).  dt in fs, `friction` in 1/fs (0: velocity Verlet on the constrained force).  Neither centre-of-mass
     velocity nor displacement is removed here: start from sum m v = 0.  The path starts as lambda = 1 throughout; `ti_path` sets
     another.  `obs` [S,8] (KE eV, T = 2 KE / ((3 n - 3) kB) K, U_s, dH/dlambda, lambda, work, 0, 0) is written by every `ti_step`."""
+    FAMILY, OBS, SECOND = "ti", _lib.TI_OBS, ("energies", (), None)
 
     def __init__(self, pos: torch.Tensor, offsets: Sequence[int], masses, springs, velocities: torch.Tensor, reference: torch.Tensor,
                  temperatures, seeds, schedule: str = "smooth", dt: float = 1.0, friction: float = 0.01):
         self.schedule = schedule_name(schedule)
         self.params = _lib.M3GTiParams(schedule=SCHEDULES[self.schedule], reserved=0, dt=dt, friction=friction)
-        self.offsets, self.N, self.S = batch_layout(pos, None, offsets)
-        for name, x in (("velocities", velocities), ("reference", reference)):
-            if x.dtype != torch.float64 or tuple(x.shape) != (self.N, 3) or x.device != pos.device:
-                raise ValueError(f"{name} must be a [{self.N}, 3] float64 tensor on {pos.device}")
-        self.masses = np.ascontiguousarray(np.asarray(masses, dtype=np.float64).reshape(-1))
+        self._layout(pos, None, offsets)
+        self._rows("velocities", velocities)
+        self._rows("reference", reference)
         self.springs = np.ascontiguousarray(np.asarray(springs, dtype=np.float64).reshape(-1))
-        self.temperatures = np.ascontiguousarray(np.broadcast_to(np.asarray(temperatures, dtype=np.float64), (self.S,)))
-        self.seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
-        if len(self.masses) != self.N or len(self.springs) != self.N or len(self.seeds) != self.S:
+        if not self._host_arrays(masses, temperatures, seeds) or len(self.springs) != self.N:
             raise ValueError(f"expected {self.N} masses, {self.N} springs and {self.S} seeds (one per structure)")
-        self.pos = pos
-        self.device = pos.device
-        self.lib = _lib.load_library()
-        sizes = (self.N, self.S)
-        self.state = state_tensor(self.lib.m3g_ti_state_bytes, *sizes, device=self.device)
-        self.obs = torch.full((self.S, _lib.TI_OBS), float("nan"), dtype=torch.float64, device=self.device)
-        mass_at, vel_at = C.c_size_t(), C.c_size_t()
-        _lib.check(self.lib.m3g_ti_state_view(*sizes, C.byref(mass_at), C.byref(vel_at)))
-        self.velocities = self.state[vel_at.value:vel_at.value + 24 * self.N].view(torch.float64).view(self.N, 3)
-        vel, ref = velocities.contiguous(), reference.contiguous()
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_ti_init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, self.masses.ctypes.data,
-                                            self.springs.ctypes.data, self.temperatures.ctypes.data, self.seeds.ctypes.data, _ptr(vel),
-                                            _ptr(ref), _ptr(self.state), self.state.numel(), _stream()))
+        self._allocate(state_tensor, self.N, self.S)
+        self._init(self.springs, self.temperatures, self.seeds, velocities, reference)
 
-    def read(self) -> dict:
-        """flags / n_steps / work / count / mean / m2 [S] (Welford's accumulators of dH/dlambda), the velocities [N, 3] and the per-atom
-        sums of |x - r0|^2 over the `count` samples [N], copied to the host (waits for the stream)."""
-        return read_state(self.lib.m3g_ti_read, (self.N, self.S), self.state,
-                          (("flags", np.int32, self.S), ("n_steps", np.int64, self.S), ("work", np.float64, self.S),
-                           ("count", np.int64, self.S), ("mean", np.float64, self.S), ("m2", np.float64, self.S),
-                           ("v", np.float64, (self.N, 3)), ("msd_sum", np.float64, self.N)))
+    def _fields(self):
+        """`read()`: flags / n_steps / work / count / mean / m2 [S] (Welford's accumulators of dH/dlambda), the velocities [N, 3] and
+        the per-atom sums of |x - r0|^2 over the `count` samples [N], copied to the host (waits for the stream)."""
+        return (("flags", np.int32, self.S), ("n_steps", np.int64, self.S), ("work", np.float64, self.S),
+                ("count", np.int64, self.S), ("mean", np.float64, self.S), ("m2", np.float64, self.S),
+                ("v", np.float64, (self.N, 3)), ("msd_sum", np.float64, self.N))
 
 
 def ti_path(state: TiState, lambda_begin, lambda_end, n_switch: int, n_discard: int = 0) -> None:
@@ -127,11 +110,7 @@ def ti_step(state: TiState, forces: torch.Tensor, energies: torch.Tensor, finish
     """One call of the batch (m3g_ti_step) at the model's `forces` [N,3] and `energies` [S] (float32) evaluated at `state.pos`: finish
     the step that ends here, add to the work and the statistics, write `state.obs`, start the next step (not with `finish_only`).
     Three launches, queued on the current stream; no wait, capture-safe."""
-    check_tensor("forces", forces, (state.N, 3), torch.float32)
-    check_tensor("energies", energies, (state.S,), torch.float32)
-    with _cuda.on_device(state.device):
-        _lib.check(state.lib.m3g_ti_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
-                                         _ptr(energies), _ptr(state.pos), 1 if finish_only else 0, _ptr(state.obs), _stream()))
+    state.step(forces, finish_only, energies)
 
 
 LOG_KEYS = ("stage", "step", "temperature", "lambda", "dh_dlambda", "spring_energy", "potential", "work")

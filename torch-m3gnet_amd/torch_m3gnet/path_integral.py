@@ -15,17 +15,15 @@ exchange statistics, and `TrajectoryObservables` on beads.
 Units as in `dynamics`: A, fs, amu, eV, K; velocities in A/fs."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Sequence
 
 import numpy as np
 import torch
 
-from . import _cuda, _lib
-from ._driver import (Driver, GroupedEvaluation, batch_layout, boolean, check_tensor, integer, non_negative, per_structure, positive,
-                      read_state, state_tensor, structure_arrays, structure_masses)
+from . import _lib
+from ._driver import (Driver, GroupedEvaluation, IntegratorState, boolean, integer, non_negative, per_structure, positive,
+                      state_tensor, structure_arrays, structure_masses)
 from .data import MaterialGraphKey as K
-from .data.graph_gpu import _ptr, _stream
 from .dynamics import maxwell_boltzmann, structure_seeds
 from .nn.modules import Gradient
 
@@ -47,59 +45,40 @@ def thermostat_name(x) -> str:
     return x
 
 
-class PimdState:
+class PimdState(IntegratorState):
     """State of a batch of ring polymers on the device (m3g_pimd_init), shaped like `NhcState`: `pos` [N,3] fp64 (unwrapped) is the
     caller's tensor, moved IN PLACE by `pimd_step`; the `velocities` argument [N,3] fp64 is copied, the `velocities` attribute is the
     live view of the integrator's own.  `offsets`: S + 1 atom offsets of the S = R P structures, ring by ring (bead j of ring g is
     structure g P + j; all beads of a ring hold the same atoms, so the same `masses`).  `temperatures` and `seeds`: one per RING (or
     one temperature for all).  dt in fs, `centroid_friction` in 1/fs.  `obs` [R,8] (KE of all beads eV, T = 2 KE / (3 n P^2 kB) K,
     E_spring, K_prim, K_cv, heat, 0, 0) is written by every `pimd_step`."""
+    FAMILY, OBS = "pimd", _lib.PIMD_OBS
 
     def __init__(self, pos: torch.Tensor, offsets: Sequence[int], masses, velocities: torch.Tensor, temperatures, seeds, n_beads: int,
                  thermostat: str = "pile_l", dt: float = 0.5, centroid_friction: float = 0.01, pile_lambda: float = 0.5):
         self.n_beads, self.thermostat = bead_count(n_beads), thermostat_name(thermostat)
         self.params = _lib.M3GPimdParams(thermostat=THERMOSTATS[self.thermostat], n_beads=self.n_beads, dt=dt,
                                          centroid_friction=centroid_friction, pile_lambda=pile_lambda)
-        self.offsets, self.N, self.S = batch_layout(pos, None, offsets)
+        self._layout(pos, None, offsets)
         if self.S % self.n_beads:
             raise ValueError(f"the batch holds {self.S} structures, which is not a multiple of n_beads = {self.n_beads}")
         self.R = self.S // self.n_beads
-        if velocities.dtype != torch.float64 or tuple(velocities.shape) != (self.N, 3) or velocities.device != pos.device:
-            raise ValueError(f"velocities must be a [{self.N}, 3] float64 tensor on {pos.device}")
-        self.masses = np.ascontiguousarray(np.asarray(masses, dtype=np.float64).reshape(-1))
-        self.temperatures = np.ascontiguousarray(np.broadcast_to(np.asarray(temperatures, dtype=np.float64), (self.R,)))
-        self.seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
-        if len(self.masses) != self.N or len(self.seeds) != self.R:
+        self._rows("velocities", velocities)
+        if not self._host_arrays(masses, temperatures, seeds, units=self.R):
             raise ValueError(f"expected {self.N} masses and {self.R} seeds (one per ring)")
-        self.pos = pos
-        self.device = pos.device
-        self.lib = _lib.load_library()
-        sizes = (self.N, self.S, self.n_beads)
-        self.state = state_tensor(self.lib.m3g_pimd_state_bytes, *sizes, device=self.device)
-        self.obs = torch.full((self.R, _lib.PIMD_OBS), float("nan"), dtype=torch.float64, device=self.device)
-        mass_at, vel_at = C.c_size_t(), C.c_size_t()
-        _lib.check(self.lib.m3g_pimd_state_view(*sizes, C.byref(mass_at), C.byref(vel_at)))
-        self.velocities = self.state[vel_at.value:vel_at.value + 24 * self.N].view(torch.float64).view(self.N, 3)
-        vel = velocities.contiguous()
-        with _cuda.on_device(self.device):
-            _lib.check(self.lib.m3g_pimd_init(C.byref(self.params), self.N, self.S, self.offsets.ctypes.data, self.masses.ctypes.data,
-                                              self.temperatures.ctypes.data, self.seeds.ctypes.data, _ptr(vel), _ptr(self.state),
-                                              self.state.numel(), _stream()))
+        self._allocate(state_tensor, self.N, self.S, self.n_beads, units=self.R)
+        self._init(self.temperatures, self.seeds, velocities)
 
-    def read(self) -> dict:
-        """flags / n_steps / heat [R] and the velocities [N, 3], copied to the host (waits for the stream)."""
-        return read_state(self.lib.m3g_pimd_read, (self.N, self.S, self.n_beads), self.state,
-                          (("flags", np.int32, self.R), ("n_steps", np.int64, self.R), ("heat", np.float64, self.R),
-                           ("v", np.float64, (self.N, 3))))
+    def _fields(self):
+        """`read()`: flags / n_steps / heat [R] and the velocities [N, 3], copied to the host (waits for the stream)."""
+        return (("flags", np.int32, self.R), ("n_steps", np.int64, self.R), ("heat", np.float64, self.R),
+                ("v", np.float64, (self.N, 3)))
 
 
 def pimd_step(state: PimdState, forces: torch.Tensor, finish_only: bool = False) -> None:
     """One call of the batch (m3g_pimd_step) at `forces` [N,3] float32 evaluated at `state.pos`: finish the step that ends here, write
     `state.obs`, start the next one (not with `finish_only`).  Three launches, queued on the current stream; no wait, capture-safe."""
-    check_tensor("forces", forces, (state.N, 3), torch.float32)
-    with _cuda.on_device(state.device):
-        _lib.check(state.lib.m3g_pimd_step(C.byref(state.params), state.N, state.S, _ptr(state.state), state.state.numel(), _ptr(forces),
-                                           _ptr(state.pos), 1 if finish_only else 0, _ptr(state.obs), _stream()))
+    state.step(forces, finish_only)
 
 
 LOG_KEYS = ("time", "temperature", "ring_kinetic", "spring_energy", "potential", "kinetic_primitive", "kinetic_centroid_virial",
