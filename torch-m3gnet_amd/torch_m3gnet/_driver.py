@@ -1,9 +1,12 @@
 """What the batched drivers (relax, dynamics, replica_exchange, monte_carlo, trajectory, neb, phonons, elasticity) share on the host:
 argument checks, the model every driver evaluates, state allocation and read-back, the device state of the five MD step families
-(`IntegratorState`: dynamics, path_integral, free_energy), the split of one structure's copies into engine
-sub-batches, the evaluation of a batch in engine groups (`GroupedEvaluation`: replica_exchange, monte_carlo) and the log and result
-dicts of an MD run (`MdLog`, `md_result`: dynamics, replica_exchange).  The optimiser loop relax and neb share is `relax.fire_loop`,
-beside `fire_step` / `lbfgs_step`; the status read after the last evaluation is `VerletGraph.raise_on_step_errors`."""
+(`IntegratorState`: dynamics, path_integral, free_energy), the split of one structure's copies into engine sub-batches, the
+evaluation of a batch in engine groups (`GroupedEvaluation`) and the run of the eight drivers that integrate (dynamics, transport,
+normal_modes, metadynamics, replica_exchange, monte_carlo, path_integral, free_energy): `MdBatch`, `md_loop` -- the one place that
+says when a step only finishes, how a synchronous point restarts and which steps are logged --, `MdLog` / `md_results`,
+`derived_keys` and `replicated`; their Langevin warm-up is `dynamics.langevin_warm_up`, beside the `DynState` it makes.  The optimiser
+loop relax and neb share is `relax.fire_loop`, beside `fire_step` / `lbfgs_step`; the status read after the last evaluation is
+`VerletGraph.raise_on_step_errors`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -90,6 +93,27 @@ def per_structure(name: str, x: np.ndarray, n_structs: int) -> np.ndarray:
 def atom_offsets(z: list) -> np.ndarray:
     """S + 1 atom offsets of a batch from its per-structure arrays (species, say)."""
     return np.concatenate([[0], np.cumsum([len(a) for a in z])])
+
+
+def structure_seeds(seed, n_structs: int) -> np.ndarray:
+    """Per-structure 64-bit Philox keys: `seed` itself when it is a sequence of S integers, else derived from (seed, s)."""
+    if np.ndim(seed) == 1:
+        seeds = np.asarray(seed, dtype=np.uint64)
+        if len(seeds) != n_structs:
+            raise ValueError(f"seed: expected one per structure ({n_structs}); got {len(seeds)}")
+        return seeds
+    return np.array([np.random.SeedSequence([int(seed), s]).generate_state(1, np.uint64)[0] for s in range(n_structs)], dtype=np.uint64)
+
+
+def derived_keys(seed, n_inputs: int, per_input) -> list:
+    """`per_input` keys (one count, or one per input) for every input: a copy's keys derive from its input's own seed only, so an
+    input's run does not depend on its neighbours."""
+    return [structure_seeds(int(sd), int(n)) for sd, n in zip(structure_seeds(seed, n_inputs), np.broadcast_to(per_input, (n_inputs,)))]
+
+
+def replicated(xs, copies: int) -> list:
+    """Every entry of `xs` `copies` times, the copies of an entry side by side."""
+    return [x for x in xs for _ in range(copies)]
 
 
 def check_tensor(name: str, x: torch.Tensor, shape: tuple, dtype: torch.dtype, device=None) -> None:
@@ -252,7 +276,7 @@ class GroupedEvaluation:
 
     def lattices(self) -> torch.Tensor:
         """[S,3,3] fp64, a copy of the graphs' cells."""
-        return torch.cat([vg.lattice for vg in self.graphs]).clone()
+        return (torch.cat([vg.lattice for vg in self.graphs]) if len(self.graphs) > 1 else self.graphs[0].lattice).clone()
 
     def buffers(self, forces: bool = True) -> dict:
         """Whole-batch float32 tensors for `evaluate(into=...)`; without `forces` the energies only (forces and stresses None)."""
@@ -280,6 +304,54 @@ class GroupedEvaluation:
             vg.raise_on_step_errors(what)
 
 
+class MdBatch(GroupedEvaluation):
+    """The batch of an MD run (one group covering everything is the bare `VerletGraph`): beside the groups' graphs `pos` [N,3] fp64
+    from the host positions and, with `cells`, `lattice` [S,3,3] fp64 -- the tensors an integrator state moves in place --, `atoms`,
+    the (a, b) rows of every structure, and `whole`, the buffers of `evaluate` (one group: None, the engine's own tensors serve)."""
+
+    def __init__(self, model: Gradient, lat: list, pos: list, z: list, groups: list, skin: float, device, cells: bool = True,
+                 whole: bool = True):
+        super().__init__(model, lat, z, groups, skin, device)
+        self.atoms = [(int(a), int(b)) for a, b in zip(self.offsets, self.offsets[1:])]
+        self.pos = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=self.device)
+        self.lattice = self.lattices() if cells else None
+        self.whole = self.buffers() if whole and len(groups) > 1 else None
+
+
+def md_loop(batch: MdBatch, state, steps: int, second=K.STRESSES, *, log=None, loginterval: int = 1, first_logged: int = 0,
+            before=None, sync_at=None, at_sync=None, after=None, into: dict | None = None) -> dict:
+    """`steps` steps of `state` (an `IntegratorState`) over `batch`: steps + 1 evaluations (into `into`, default `batch.whole`; each
+    waits for its skin test, the only waits), each followed by `state.step(forces, finish_only, out[second])`, which finishes the
+    step that ends there and, but at the last, starts the next.  Returns the last evaluation.  `before(k, out, logged)` runs between
+    the two (samplers, reads, the clone of a cell about to move) and may return forces to integrate in place of the engine's.  Where
+    `sync_at(k)` holds the step is finished, `at_sync(k, out)` acts on the synchronous velocities, the next step is started from
+    the same forces without a second finish kick (not after the last), and what `at_sync` returned, if anything, is called.
+    `log(j, out)` follows the integrator call for j = k - `first_logged` >= 0 at every multiple of `loginterval` and at the last step
+    (host copies happen there only); `after(k, out)` closes the step."""
+    into = batch.whole if into is None else into
+    out = None
+    for k in range(steps + 1):
+        out = batch.evaluate(batch.pos, into)
+        j = k - first_logged
+        logged = log is not None and j >= 0 and (j % loginterval == 0 or k == steps)
+        forces = before(k, out, logged) if before is not None else None
+        forces, extra = out[K.FORCES] if forces is None else forces, None if second is None else out[second]
+        if sync_at is not None and sync_at(k):
+            state.step(forces, True, extra)        # synchronous velocities, STARTED cleared
+            resumed = at_sync(k, out)
+            if k < steps:
+                state.step(forces, False, extra)   # starts the next step: no second finish kick
+            if resumed is not None:
+                resumed()
+        else:
+            state.step(forces, k == steps, extra)
+        if logged:
+            log(j, out)
+        if after is not None:
+            after(k, out)
+    return out
+
+
 class MdLog:
     """The log of an MD run: step, e_pot, ke (eV), t (K), p (GPa), v (A^3) of every structure at the steps `append` is called; with
     `conserved` (the ensembles of `NhcState`, whose obs rows hold the extended energy in column 4) also conserved = e_pot + ke +
@@ -304,12 +376,22 @@ class MdLog:
         if "conserved" in self.rows:
             self.rows["conserved"].append(self.rows["e_pot"][-1] + obs[:, 0] + obs[:, 4])
 
+    def of(self, state):
+        """The `log` of `md_loop` that appends `state.obs` beside the energies."""
+        return lambda j, out: self.append(j, out[K.TOTAL_ENERGY], state.obs)
+
     def arrays(self) -> dict:
         return {key: np.stack(val, axis=1) for key, val in self.rows.items()}   # [S, n_log]
 
 
-def md_result(s: int, a: int, b: int, p_host, st: dict, l_host, e, f, sv, logs: dict) -> dict:
-    """The dict `MolecularDynamics.run` returns for structure `s` (atoms a .. b) from the host copies of the batch; `st`: `DynState.read()`."""
-    return {"positions": p_host[a:b].copy(), "velocities": st["v"][a:b].copy(), "lattice": l_host[s].copy(),
-            "total_energy": float(e[s]), "forces": f[a:b].copy(), "stresses": sv[s].copy(), "n_steps": int(st["n_steps"][s]),
-            "error": bool(st["flags"][s] & _lib.DYN_ERROR), "log": {key: val[s].copy() for key, val in logs.items()}}
+def md_results(batch: MdBatch, dyn, out: dict, log: MdLog, what: str) -> list:
+    """The tail of an MD run: the graphs' status (raises for `what`), `dyn.read()` (waits), the last evaluation `out`, the positions
+    and the cells copied to the host, and the dict `MolecularDynamics.run` returns for every structure."""
+    batch.raise_on_step_errors(what)
+    st = dyn.read()
+    e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
+    p_host, l_host, logs = batch.pos.cpu().numpy(), batch.lattice.cpu().numpy(), log.arrays()
+    return [{"positions": p_host[a:b].copy(), "velocities": st["v"][a:b].copy(), "lattice": l_host[s].copy(),
+             "total_energy": float(e[s]), "forces": f[a:b].copy(), "stresses": sv[s].copy(), "n_steps": int(st["n_steps"][s]),
+             "error": bool(st["flags"][s] & _lib.DYN_ERROR), "log": {key: val[s].copy() for key, val in logs.items()}}
+            for s, (a, b) in enumerate(batch.atoms)]

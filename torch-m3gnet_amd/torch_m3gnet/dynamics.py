@@ -23,10 +23,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._driver import (EV_A3_TO_GPA, Driver, IntegratorState, MdLog, atom_offsets, integer, md_result, non_negative, per_structure,
-                      positive, state_tensor, structure_arrays, structure_masses)
+from ._driver import (EV_A3_TO_GPA, Driver, IntegratorState, MdBatch, MdLog, integer, md_loop, md_results, non_negative, per_structure,
+                      positive, state_tensor, structure_arrays, structure_masses, structure_seeds)
 from .data import MaterialGraphKey as K
-from .data.md import VerletGraph
 from .nn.modules import Gradient
 from .trajectory import TrajectoryObservables, traj_sample
 
@@ -55,16 +54,6 @@ def maxwell_boltzmann(masses, temperature: float, seed: int = 0) -> np.ndarray:
     if temperature == 0.0 or t_now == 0.0:
         return np.zeros_like(v)
     return v * np.sqrt(temperature / t_now)
-
-
-def structure_seeds(seed, n_structs: int) -> np.ndarray:
-    """Per-structure 64-bit Philox keys: `seed` itself when it is a sequence of S integers, else derived from (seed, s)."""
-    if np.ndim(seed) == 1:
-        seeds = np.asarray(seed, dtype=np.uint64)
-        if len(seeds) != n_structs:
-            raise ValueError(f"seed: expected one per structure ({n_structs}); got {len(seeds)}")
-        return seeds
-    return np.array([np.random.SeedSequence([int(seed), s]).generate_state(1, np.uint64)[0] for s in range(n_structs)], dtype=np.uint64)
 
 
 class DynState(IntegratorState):
@@ -104,6 +93,17 @@ def dyn_step(state: DynState, forces: torch.Tensor, stresses: torch.Tensor | Non
     NPT) evaluated at `state.pos`: finish the step that ends here, write `state.obs`, start the next one (not with `finish_only`).
     Queued on the current stream; no wait, capture-safe."""
     state.step(forces, finish_only, stresses)
+
+
+def langevin_warm_up(batch: MdBatch, masses: list, temperature: float, seeds, equilibration: int, **common) -> DynState:
+    """`equilibration` Langevin steps of `batch` from Maxwell-Boltzmann velocities (`masses`: [n_s] per structure; `common`: dt and
+    friction): the `DynState`, ended on full-step velocities, which seed the run proper (`velocities=warm.velocities`: copied on the
+    device)."""
+    vel = [maxwell_boltzmann(ms, temperature, int(sd)) for ms, sd in zip(masses, seeds)]
+    warm = DynState(batch.pos, batch.lattice, batch.offsets, np.concatenate(masses), torch.tensor(np.concatenate(vel), device=batch.device),
+                    temperature, seeds, ensemble="nvt_langevin", **common)
+    md_loop(batch, warm, equilibration)
+    return warm
 
 
 class NhcState(IntegratorState):
@@ -314,40 +314,29 @@ class MolecularDynamics(Driver):
             for s, (v, a) in enumerate(zip(vel, z)):
                 if v.shape != (len(a), 3) or not np.isfinite(v).all():
                     raise ValueError(f"structure {s}: velocities must be a finite [{len(a)}, 3] array")
-        model = self.model
-        cfg = model.engine.cfg
-        vg = VerletGraph(lat, z, cfg.cutoff, cfg.threebody_cutoff, skin=self.skin, device=self.device)
-        pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=vg.device)
-        offsets = atom_offsets(z)
-        lat64 = vg.lattice.clone()   # the NPT launches write the scaled cells here
+        batch = MdBatch(self.model, lat, pos, z, [(0, S)], self.skin, self.device)
+        (vg,), pos_t, lat64 = batch.graphs, batch.pos, batch.lattice   # (the NPT launches write the scaled cells into lat64)
         npt = self.ensemble in ("npt_berendsen", "npt_mtk", "npt_mtk_cell")
         vel_t = torch.tensor(np.concatenate(vel), device=vg.device)
-        if cell:
-            dyn, step = MtkCellState(pos_t, lat64, offsets, np.concatenate(m), vel_t, temps, **self._params()), mtk_cell_step
-        elif nhc:
-            dyn, step = NhcState(pos_t, lat64, offsets, np.concatenate(m), vel_t, temps, **self._params()), nhc_step
-        else:
-            dyn, step = DynState(pos_t, lat64, offsets, np.concatenate(m), vel_t, temps, seeds, **self._params()), dyn_step
+        keys = () if nhc else (seeds,)   # (the deterministic ensembles draw nothing)
+        dyn = (MtkCellState if cell else NhcState if nhc else DynState)(pos_t, lat64, batch.offsets, np.concatenate(m), vel_t, temps, *keys,
+                                                                        **self._params())
         traj = observables.begin(lat, z, m, vg.device) if observables is not None else None
-        log = MdLog(conserved=nhc, cell=cell)
-        out = None
-        for k in range(steps + 1):
-            out = vg.step(model, pos_t)   # waits for the skin test (the previous dyn_step has been queued before it)
+        log, cells = MdLog(conserved=nhc, cell=cell), []
+
+        def before(k, out, logged):
             if traj is not None and k % observables.sample_interval == 0:
                 traj_sample(traj, pos_t, lat64, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
-            logged = k % loginterval == 0 or k == steps
-            lat_now = lat64.clone() if cell and logged else None   # (the cell of the observables: the call below moves it on)
-            step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=(k == steps))
-            if logged:   # (host copies on log steps only)
-                log.append(k, out[K.TOTAL_ENERGY], dyn.obs, lat_now)
+            if cell and logged:
+                cells.append(lat64.clone())   # (the cell of the observables: the integrator call moves it on)
+
+        def after(k, out):
             if npt and k < steps:
                 vg.set_lattice(list(lat64.cpu().numpy()))   # (waits: the candidate search in the new cells needs them on the host)
-        vg.raise_on_step_errors("molecular dynamics")
-        st = dyn.read()
-        e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
-        p_host, l_host = pos_t.cpu().numpy(), lat64.cpu().numpy()
-        logs = log.arrays()
-        res = [md_result(s, int(offsets[s]), int(offsets[s + 1]), p_host, st, l_host, e, f, sv, logs) for s in range(S)]
+
+        out = md_loop(batch, dyn, steps, before=before, after=after, loginterval=loginterval,
+                      log=lambda k, out: log.append(k, out[K.TOTAL_ENERGY], dyn.obs, cells.pop() if cell else None))
+        res = md_results(batch, dyn, out, log, "molecular dynamics")
         if traj is not None:
             for r, obs in zip(res, observables.results(traj, self.timestep)):
                 r["observables"] = obs

@@ -24,11 +24,11 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import (Driver, GroupedEvaluation, IntegratorState, boolean, integer, non_negative, positive, state_tensor,
-                      structure_arrays, structure_masses)
+from ._driver import (Driver, IntegratorState, MdBatch, boolean, derived_keys, integer, md_loop, non_negative, positive, replicated,
+                      state_tensor, structure_arrays, structure_masses)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
-from .dynamics import KAPPA, KB, maxwell_boltzmann, structure_seeds
+from .dynamics import KAPPA, KB, maxwell_boltzmann
 from .nn.modules import Gradient
 from .path_integral import HBAR
 
@@ -178,36 +178,31 @@ class FreeEnergy(Driver):
                 raise ValueError(f"spring_constant: structure {s} needs {len(zs)} finite values > 0")
         return out
 
-    def _batch(self, lat, pos, z, m, copies: int):
-        """The engine groups, the positions tensor and what `TiState` takes besides the springs, of `copies` copies of every input."""
+    def _batch(self, lat, pos, z, m, springs, copies: int):
+        """The `MdBatch` of `copies` copies of every input and their `TiState`, every atom tied to its starting site by `springs`."""
         G = len(z)
         groups = [(g * copies, (g + 1) * copies) for g in range(G)] if self.structure_batches else [(0, G * copies)]
-        rep = lambda xs: [x for x in xs for _ in range(copies)]   # noqa: E731
-        ev = GroupedEvaluation(self.model, rep(lat), rep(z), groups, self.skin, self.device)
-        # a copy's keys derive from its structure's own seed only: its velocity seed, then the key of its thermostat
-        keys = [structure_seeds(int(sd), 2 * copies) for sd in structure_seeds(self.seed, G)]
+        rep = lambda xs: replicated(xs, copies)   # noqa: E731
+        ev = MdBatch(self.model, rep(lat), rep(pos), rep(z), groups, self.skin, self.device, cells=False)
+        keys = derived_keys(self.seed, G, 2 * copies)   # of every copy: its velocity seed, then the key of its thermostat
         vel = [maxwell_boltzmann(m[g], self.temperature, int(keys[g][2 * r])) for g in range(G) for r in range(copies)]
         seeds = np.array([keys[g][2 * r + 1] for g in range(G) for r in range(copies)], dtype=np.uint64)
-        return ev, np.concatenate(rep(pos)), np.concatenate(rep(m)), np.concatenate(vel), seeds
+        state = TiState(ev.pos, ev.offsets, np.concatenate(rep(m)), np.concatenate(rep(springs)),
+                        torch.tensor(np.concatenate(vel), dtype=torch.float64, device=ev.device), ev.pos.clone(), self.temperature, seeds,
+                        schedule=self.schedule, dt=self.timestep, friction=self.friction)
+        return ev, state
 
-    def _state(self, ev, sites, masses, vel, seeds, springs) -> TiState:
-        f64 = dict(dtype=torch.float64, device=ev.device)
-        pos_t = torch.tensor(sites, **f64)
-        return TiState(pos_t, ev.offsets, masses, springs, torch.tensor(vel, **f64), pos_t.clone(), self.temperature, seeds,
-                       schedule=self.schedule, dt=self.timestep, friction=self.friction)
-
-    def _stage(self, ev, state: TiState, whole, n_steps: int, rows: dict | None, stage: int, loginterval: int) -> None:
+    def _stage(self, ev: MdBatch, state: TiState, n_steps: int, rows: dict | None, stage: int, loginterval: int) -> None:
         """`n_steps` steps of the state's current path (n_steps + 1 evaluations, the last one finishing only)."""
-        for k in range(n_steps + 1):
-            out = ev.evaluate(state.pos, whole)
-            ti_step(state, out[K.FORCES], out[K.TOTAL_ENERGY], finish_only=(k == n_steps))
-            if rows is not None and (k % loginterval == 0 or k == n_steps):   # (host copies on log steps only)
-                obs = state.obs.cpu().numpy()
-                rows["stage"].append(np.full(ev.S, stage))
-                rows["step"].append(np.full(ev.S, k))
-                rows["potential"].append(out[K.TOTAL_ENERGY].double().cpu().numpy())
-                for key, col in (("temperature", 1), ("spring_energy", 2), ("dh_dlambda", 3), ("lambda", 4), ("work", 5)):
-                    rows[key].append(obs[:, col])
+        def log(k, out):
+            obs = state.obs.cpu().numpy()
+            rows["stage"].append(np.full(ev.S, stage))
+            rows["step"].append(np.full(ev.S, k))
+            rows["potential"].append(out[K.TOTAL_ENERGY].double().cpu().numpy())
+            for key, col in (("temperature", 1), ("spring_energy", 2), ("dh_dlambda", 3), ("lambda", 4), ("work", 5)):
+                rows[key].append(obs[:, col])
+
+        md_loop(ev, state, n_steps, K.TOTAL_ENERGY, log=None if rows is None else log, loginterval=loginterval)
 
     def _inputs(self, lattices, positions, atomic_numbers, masses, n_cells):
         lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
@@ -220,10 +215,9 @@ class FreeEnergy(Driver):
     def _msd_springs(self, lat, pos, z, m) -> list:
         """k_Z = 3 kB T / <|u|^2> per species and input structure, from `msd_steps` steps at lambda = 1 (the second half sampled)."""
         R = self.replicas
-        ev, sites, masses, vel, seeds = self._batch(lat, pos, z, m, R)
-        state = self._state(ev, sites, masses, vel, seeds, np.ones(len(masses)))   # (lambda = 1: the springs pull at nothing)
+        ev, state = self._batch(lat, pos, z, m, [np.ones(len(a)) for a in z], R)   # (lambda = 1: the springs pull at nothing)
         ti_path(state, 1.0, 1.0, 0, self.msd_steps // 2)
-        self._stage(ev, state, ev.buffers() if len(ev.graphs) > 1 else None, self.msd_steps, None, 0, 1)
+        self._stage(ev, state, self.msd_steps, None, 0, 1)
         ev.raise_on_step_errors("the mean-square-displacement run of the free-energy driver")
         st = state.read()
         out = []
@@ -264,15 +258,13 @@ class FreeEnergy(Driver):
         loginterval = integer("loginterval", loginterval, 1)
         lat, pos, z, m, springs, closed = self._prepare(lattices, positions, atomic_numbers, masses, n_cells)
         G, R = len(z), self.replicas
-        ev, sites, mass_all, vel, seeds = self._batch(lat, pos, z, m, R)
-        state = self._state(ev, sites, mass_all, vel, seeds, np.concatenate([springs[g] for g in range(G) for _ in range(R)]))
-        whole = ev.buffers() if len(ev.graphs) > 1 else None   # (one group: the engine's own output tensors serve)
+        ev, state = self._batch(lat, pos, z, m, springs, R)
         rows = {key: [] for key in LOG_KEYS}
         work = []
         for stage, (lb, le, n) in enumerate(((1.0, 1.0, equilibration), (1.0, 0.0, switch_steps), (0.0, 0.0, equilibration),
                                              (0.0, 1.0, switch_steps))):
             ti_path(state, lb, le, n if lb != le else 0)
-            self._stage(ev, state, whole, n, rows, stage, loginterval)
+            self._stage(ev, state, n, rows, stage, loginterval)
             if lb != le:
                 work.append(state.read()["work"])
         ev.raise_on_step_errors("thermodynamic integration")
@@ -307,13 +299,11 @@ class FreeEnergy(Driver):
         G, J = len(z), n_lambda
         x, w = np.polynomial.legendre.leggauss(J)
         nodes, weights = 0.5 * (x + 1.0), 0.5 * w
-        ev, sites, mass_all, vel, seeds = self._batch(lat, pos, z, m, J)
-        state = self._state(ev, sites, mass_all, vel, seeds, np.concatenate([springs[g] for g in range(G) for _ in range(J)]))
-        whole = ev.buffers() if len(ev.graphs) > 1 else None
+        ev, state = self._batch(lat, pos, z, m, springs, J)
         rows = {key: [] for key in LOG_KEYS}
         ladder = np.tile(nodes, G)
         ti_path(state, ladder, ladder, 0, equilibration)
-        self._stage(ev, state, whole, equilibration + steps, rows, 0, loginterval)
+        self._stage(ev, state, equilibration + steps, rows, 0, loginterval)
         ev.raise_on_step_errors("thermodynamic integration")
         st = state.read()
         logs = {key: np.stack(val, axis=1) for key, val in rows.items()}

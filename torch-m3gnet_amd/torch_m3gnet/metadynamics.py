@@ -23,11 +23,11 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import (Driver, GroupedEvaluation, MdLog, check_tensor, integer, md_result, non_negative, positive, read_state, state_tensor,
-                      structure_arrays, structure_masses)
+from ._driver import (Driver, MdBatch, MdLog, check_tensor, derived_keys, integer, md_loop, md_results, non_negative, positive, read_state,
+                      replicated, state_tensor, structure_arrays, structure_masses)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
-from .dynamics import KB, DynState, dyn_step, maxwell_boltzmann, structure_seeds
+from .dynamics import KB, DynState, maxwell_boltzmann
 from .nn.modules import Gradient
 
 KINDS = {"distance": _lib.CV_DISTANCE, "projection": _lib.CV_PROJECTION, "coordination": _lib.CV_COORDINATION}
@@ -260,7 +260,7 @@ def walker_keys(seed, n_inputs: int, copies: int):
     """(velocity seeds, thermostat keys), each [n_inputs, copies]: a copy's keys derive from its input's own seed only (as
     `FreeEnergy` derives them), so an input's run does not depend on its neighbours.  `MolecularDynamics.run` of one structure with
     `velocities=[maxwell_boltzmann(m, T, velocity seed)]` and `seed=[thermostat key]` is the same unbiased trajectory."""
-    keys = np.stack([structure_seeds(int(sd), 2 * copies) for sd in structure_seeds(seed, n_inputs)])
+    keys = np.stack(derived_keys(seed, n_inputs, 2 * copies))
     return keys[:, 0::2].copy(), keys[:, 1::2].copy()
 
 
@@ -281,15 +281,13 @@ class _BiasedLangevin(Driver):
         lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
         m = structure_masses(masses, z)
         G = len(z)
-        rep = lambda xs: [x for x in xs for _ in range(copies)]   # noqa: E731
-        ev = GroupedEvaluation(self.model, rep(lat), rep(z), [(g * copies, (g + 1) * copies) for g in range(G)], self.skin, self.device)
-        dev = ev.device
+        rep = lambda xs: replicated(xs, copies)   # noqa: E731
+        ev = MdBatch(self.model, rep(lat), rep(pos), rep(z), [(g * copies, (g + 1) * copies) for g in range(G)], self.skin, self.device)
+        dev, pos_t = ev.device, ev.pos
         v_seeds, t_keys = walker_keys(self.seed, G, copies)
         vel = [maxwell_boltzmann(m[g], self.temperature, int(v_seeds[g, r])) for g in range(G) for r in range(copies)]
         m_all = np.concatenate(rep(m))
-        pos_t = torch.tensor(np.concatenate(rep(pos)), dtype=torch.float64, device=dev)
-        lat64 = ev.lattices()
-        dyn = DynState(pos_t, lat64, ev.offsets, m_all, torch.tensor(np.concatenate(vel), device=dev), self.temperature, t_keys.reshape(-1),
+        dyn = DynState(pos_t, ev.lattice, ev.offsets, m_all, torch.tensor(np.concatenate(vel), device=dev), self.temperature, t_keys.reshape(-1),
                        ensemble="nvt_langevin", dt=self.timestep, friction=self.friction)
         origins = np.zeros((ev.S, len(self.cvs), 3))   # "projection" without an origin: the CV starts at 0
         for s in range(ev.S):
@@ -299,25 +297,19 @@ class _BiasedLangevin(Driver):
                     centre = lambda idx: (w[list(idx), None] * x[list(idx)]).sum(0) / w[list(idx)].sum() if idx else np.zeros(3)   # noqa: E731
                     origins[s, k] = centre(cv.a) - centre(cv.b)
         bias = BiasState(ev.offsets, np.stack(rep(lat)), self.cvs, m_all, origins=origins, device=dev, **bias_args(G, ev.S))
-        whole = ev.buffers() if len(ev.graphs) > 1 else None
         trace = torch.zeros(steps + 1, ev.S, _lib.META_OBS, dtype=torch.float64, device=dev)
-        log = MdLog()
-        last = equilibration + steps
-        for k in range(last + 1):
-            out = ev.evaluate(pos_t, whole)
+
+        def biased(k, out, logged):
             j = k - equilibration
-            biased = bias_forces(bias, pos_t, out[K.FORCES], deposit=(pace > 0 and j > 0 and j % pace == 0))
+            forces = bias_forces(bias, pos_t, out[K.FORCES], deposit=(pace > 0 and j > 0 and j % pace == 0))
             if j >= 0:
                 trace[j].copy_(bias.obs)
-            dyn_step(dyn, biased, out[K.STRESSES], finish_only=(k == last))
-            if j >= 0 and (j % loginterval == 0 or j == steps):
-                log.append(j, out[K.TOTAL_ENERGY], dyn.obs)
-        ev.raise_on_step_errors(type(self).__name__)
-        st, bs = dyn.read(), bias.read()
-        e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
-        p_host, l_host, logs = pos_t.cpu().numpy(), lat64.cpu().numpy(), log.arrays()
-        runs = [md_result(s, int(ev.offsets[s]), int(ev.offsets[s + 1]), p_host, st, l_host, e, f, sv, logs) for s in range(ev.S)]
-        return runs, trace.cpu().numpy().transpose(1, 0, 2), bs, bias
+            return forces
+
+        log = MdLog()
+        out = md_loop(ev, dyn, equilibration + steps, before=biased, log=log.of(dyn), loginterval=loginterval, first_logged=equilibration)
+        runs = md_results(ev, dyn, out, log, type(self).__name__)
+        return runs, trace.cpu().numpy().transpose(1, 0, 2), bias.read(), bias
 
 
 class Metadynamics(_BiasedLangevin):

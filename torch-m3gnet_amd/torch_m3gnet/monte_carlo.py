@@ -18,11 +18,11 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import (Driver, GroupedEvaluation, boolean, check_tensor, integer, non_negative, per_structure, positive, read_state,
-                      state_tensor, structure_arrays, structure_masses)
+from ._driver import (Driver, MdBatch, boolean, check_tensor, integer, md_loop, non_negative, per_structure, positive, read_state,
+                      state_tensor, structure_arrays, structure_masses, structure_seeds)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
-from .dynamics import KB, DynState, dyn_step, maxwell_boltzmann, structure_seeds
+from .dynamics import KB, DynState, maxwell_boltzmann
 from .nn.modules import Gradient
 
 
@@ -174,13 +174,11 @@ class SwapMonteCarlo(Driver):
         hybrid = self.md_steps > 0
         m = structure_masses(masses, z)
         groups = [(s, s + 1) for s in range(S)] if self.structure_batches else [(0, S)]
-        ev = GroupedEvaluation(self.model, lat, z, groups, self.skin, self.device)
-        dev, offsets = ev.device, ev.offsets
+        ev = MdBatch(self.model, lat, pos, z, groups, self.skin, self.device, whole=False)   # (two sets of buffers of its own, below)
+        dev, offsets, pos_t, lat64 = ev.device, ev.offsets, ev.pos, ev.lattice
         types = torch.tensor(np.concatenate(z) - 1, dtype=torch.int64, device=dev)   # the one array the swaps write and every engine reads
         for vg, (a, b) in zip(ev.graphs, ev.rows):
             vg.use_atom_types(types[a:b])
-        pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=dev)
-        lat64 = ev.lattices()
 
         def evaluate(into: dict) -> dict:
             return ev.evaluate(pos_t, into, forces=hybrid)
@@ -210,17 +208,9 @@ class SwapMonteCarlo(Driver):
             evaluate(cur)
             for t in range(trials):
                 one_trial(t)
-        else:
-            steps = trials * self.md_steps
-            for k in range(steps + 1):
-                evaluate(cur)
-                if k > 0 and k % self.md_steps == 0:
-                    dyn_step(dyn, cur[K.FORCES], cur[K.STRESSES], finish_only=True)   # synchronous velocities, STARTED cleared
-                    one_trial(k // self.md_steps - 1)
-                    if k < steps:
-                        dyn_step(dyn, cur[K.FORCES], cur[K.STRESSES])                 # starts the next step with the CURRENT forces
-                else:
-                    dyn_step(dyn, cur[K.FORCES], cur[K.STRESSES], finish_only=(k == steps))
+        else:   # a trial at every `md_steps`-th synchronous point, the last step's too; the restart takes the CURRENT forces
+            md_loop(ev, dyn, trials * self.md_steps, into=cur, sync_at=lambda k: k > 0 and k % self.md_steps == 0,
+                    at_sync=lambda k, out: one_trial(k // self.md_steps - 1))
         ev.raise_on_step_errors("swap Monte Carlo")
         st = mc.read()
         dst = dyn.read() if hybrid else None

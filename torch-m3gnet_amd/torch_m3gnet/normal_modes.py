@@ -29,12 +29,11 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import (Driver, MdLog, atom_offsets, boolean, check_tensor, integer, md_result, non_negative, positive, read_state,
-                      state_tensor)
+from ._driver import (Driver, MdBatch, MdLog, boolean, check_tensor, integer, md_loop, md_results, non_negative, positive, read_state,
+                      state_tensor, structure_seeds)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
-from .data.md import VerletGraph
-from .dynamics import KAPPA, KB, DynState, dyn_step, maxwell_boltzmann, structure_seeds
+from .dynamics import KAPPA, KB, DynState, langevin_warm_up
 from .nn.modules import Gradient
 from .phonons import _check_supercells
 
@@ -377,40 +376,23 @@ class NormalModeAnalysis(Driver):
             z.append(np.tile(z_u[s], len(cell)))
             m.append(np.tile(m_u[s], len(cell)))
         seeds = structure_seeds(self.seed, S)
-        vel = [maxwell_boltzmann(ms, self.temperature, int(sd)) for ms, sd in zip(m, seeds)]
-        model = self.model
-        cfg = model.engine.cfg
-        vg = VerletGraph(lat, z, cfg.cutoff, cfg.threebody_cutoff, skin=self.skin, device=self.device)
-        dev = vg.device
-        pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=dev)
-        offsets = atom_offsets(z)
-        lat64 = vg.lattice.clone()
-        m_all = np.concatenate(m)
+        batch = MdBatch(self.model, lat, pos, z, [(0, S)], self.skin, self.device)
         common = dict(dt=self.timestep, friction=self.friction)
-        warm = DynState(pos_t, lat64, offsets, m_all, torch.tensor(np.concatenate(vel), device=dev), self.temperature, seeds,
-                        ensemble="nvt_langevin", **common)
-        for k in range(equilibration + 1):
-            out = vg.step(model, pos_t)
-            dyn_step(warm, out[K.FORCES], out[K.STRESSES], finish_only=(k == equilibration))   # ends on full-step velocities
-        dyn = DynState(pos_t, lat64, offsets, m_all, warm.velocities, self.temperature, seeds ^ np.uint64(0x9E3779B97F4A7C15),
-                       ensemble=self.production, **common)   # (other noise than the equilibration's)
-        log = MdLog()
-        for k in range(steps + 1):
-            out = vg.step(model, pos_t)
+        warm = langevin_warm_up(batch, m, self.temperature, seeds, equilibration, **common)
+        dyn = DynState(batch.pos, batch.lattice, batch.offsets, np.concatenate(m), warm.velocities, self.temperature,
+                       seeds ^ np.uint64(0x9E3779B97F4A7C15), ensemble=self.production, **common)   # (other noise than the equilibration's)
+
+        def sample(k, out, logged):
             if k % self.sample_interval == 0:
-                nma_sample(nma, pos_t, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
-            dyn_step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=(k == steps))
-            if k % loginterval == 0 or k == steps:
-                log.append(k, out[K.TOTAL_ENERGY], dyn.obs)
-        vg.raise_on_step_errors("normal-mode analysis")
-        st, acc = dyn.read(), nma.read()
-        e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
-        p_host, l_host = pos_t.cpu().numpy(), lat64.cpu().numpy()
-        logs = log.arrays()
+                nma_sample(nma, batch.pos, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
+
+        log = MdLog()
+        out = md_loop(batch, dyn, steps, before=sample, log=log.of(dyn), loginterval=loginterval)
+        runs = md_results(batch, dyn, out, log, "normal-mode analysis")
+        acc = nma.read()
         sample_time = self.sample_interval * self.timestep
         res = []
-        for s, ph in enumerate(phonon_results):
-            r = md_result(s, int(offsets[s]), int(offsets[s + 1]), p_host, st, l_host, e, f, sv, logs)
+        for s, (ph, r) in enumerate(zip(phonon_results, runs)):
             mine = nma.of_structure(acc, s)
             stats = mode_statistics(mine)
             with np.errstate(divide="ignore", invalid="ignore"):

@@ -21,10 +21,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._driver import (Driver, GroupedEvaluation, IntegratorState, boolean, integer, non_negative, per_structure, positive,
-                      state_tensor, structure_arrays, structure_masses)
+from ._driver import (Driver, IntegratorState, MdBatch, boolean, derived_keys, integer, md_loop, non_negative, per_structure, positive,
+                      replicated, state_tensor, structure_arrays, structure_masses)
 from .data import MaterialGraphKey as K
-from .dynamics import maxwell_boltzmann, structure_seeds
+from .dynamics import maxwell_boltzmann
 from .nn.modules import Gradient
 
 HBAR = 0.6582119569   # eV fs
@@ -141,30 +141,27 @@ class PathIntegralMD(Driver):
         temps = per_structure("temperature", self.temperature, G)
         m = structure_masses(masses, z_r[::P])
         # a ring's keys derive from its own seed only: P velocity seeds of its beads, then the key of its thermostat
-        keys = [structure_seeds(int(sd), P + 1) for sd in structure_seeds(self.seed, G)]
+        keys = derived_keys(self.seed, G, P + 1)
         vel = [maxwell_boltzmann(m[g], P * temps[g], int(keys[g][j])) for g in range(G) for j in range(P)]
         groups = [(g * P, (g + 1) * P) for g in range(G)] if self.ring_batches else [(0, G * P)]
-        ev = GroupedEvaluation(self.model, lat_r, z_r, groups, self.skin, self.device)
-        dev, offsets = ev.device, ev.offsets
-        pos_t = torch.tensor(np.concatenate(pos_r), dtype=torch.float64, device=dev)
-        state = PimdState(pos_t, offsets, np.concatenate([m[g] for g in range(G) for _ in range(P)]),
-                          torch.tensor(np.concatenate(vel), device=dev), temps, np.array([k[-1] for k in keys], dtype=np.uint64), P,
-                          thermostat=self.thermostat, dt=self.timestep, centroid_friction=self.centroid_friction,
-                          pile_lambda=self.pile_lambda)
-        whole = ev.buffers() if len(groups) > 1 else None   # (one group: the engine's own output tensors serve)
+        ev = MdBatch(self.model, lat_r, pos_r, z_r, groups, self.skin, self.device, cells=False)
+        pos_t, offsets = ev.pos, ev.offsets
+        state = PimdState(pos_t, offsets, np.concatenate(replicated(m, P)), torch.tensor(np.concatenate(vel), device=ev.device), temps,
+                          np.array([k[-1] for k in keys], dtype=np.uint64), P, thermostat=self.thermostat, dt=self.timestep,
+                          centroid_friction=self.centroid_friction, pile_lambda=self.pile_lambda)
         rows = {key: [] for key in LOG_KEYS}
-        for k in range(steps + 1):
-            out = ev.evaluate(pos_t, whole)
-            pimd_step(state, out[K.FORCES], finish_only=(k == steps))
-            if k % loginterval == 0 or k == steps:   # (host copies on log steps only)
-                obs = state.obs.cpu().numpy()
-                e_sum = out[K.TOTAL_ENERGY].double().cpu().numpy().reshape(G, P).sum(1)
-                rows["time"].append(np.full(G, k * self.timestep))
-                for key, col in (("ring_kinetic", 0), ("temperature", 1), ("spring_energy", 2), ("kinetic_primitive", 3),
-                                 ("kinetic_centroid_virial", 4)):
-                    rows[key].append(obs[:, col])
-                rows["potential"].append(e_sum / P)
-                rows["conserved"].append(e_sum + obs[:, 0] + obs[:, 2] - obs[:, 5])
+
+        def log(k, out):
+            obs = state.obs.cpu().numpy()
+            e_sum = out[K.TOTAL_ENERGY].double().cpu().numpy().reshape(G, P).sum(1)
+            rows["time"].append(np.full(G, k * self.timestep))
+            for key, col in (("ring_kinetic", 0), ("temperature", 1), ("spring_energy", 2), ("kinetic_primitive", 3),
+                             ("kinetic_centroid_virial", 4)):
+                rows[key].append(obs[:, col])
+            rows["potential"].append(e_sum / P)
+            rows["conserved"].append(e_sum + obs[:, 0] + obs[:, 2] - obs[:, 5])
+
+        md_loop(ev, state, steps, None, log=log, loginterval=loginterval)
         ev.raise_on_step_errors("path-integral molecular dynamics")
         st = state.read()
         p_host = pos_t.cpu().numpy()

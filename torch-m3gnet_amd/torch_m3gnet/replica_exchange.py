@@ -18,11 +18,11 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import (Driver, GroupedEvaluation, MdLog, boolean, check_tensor, integer, md_result, non_negative, positive, read_state,
-                      state_tensor, structure_arrays, structure_masses)
+from ._driver import (Driver, MdBatch, MdLog, boolean, check_tensor, derived_keys, integer, md_loop, md_results, non_negative, positive,
+                      read_state, state_tensor, structure_arrays, structure_masses)
 from .data import MaterialGraphKey as K
 from .data.graph_gpu import _ptr, _stream
-from .dynamics import KB, DynState, dyn_step, maxwell_boltzmann, structure_seeds
+from .dynamics import KB, DynState, maxwell_boltzmann
 from .nn.modules import Gradient
 
 
@@ -139,44 +139,33 @@ class ReplicaExchange(Driver):
         temps = np.concatenate(ladders)
         S = len(owner)
         # a ladder's keys derive from its own seed only: R Langevin keys of its replicas, then the key of its exchange stream
-        keys = [structure_seeds(int(sd), len(t) + 1) for sd, t in zip(structure_seeds(self.seed, G), ladders)]
+        keys = derived_keys(self.seed, G, [len(t) + 1 for t in ladders])
         seeds, ladder_seeds = np.concatenate([k[:-1] for k in keys]), np.array([k[-1] for k in keys], dtype=np.uint64)
         lat_r, pos_r, z_r, m_r = ([x[g] for g in owner] for x in (lat, pos, z, m))
         vel = [maxwell_boltzmann(ms, t, int(sd)) for ms, t, sd in zip(m_r, temps, seeds)]
         # the ladders of every engine batch (see `ladder_batches`), as spans of replicas
         groups = [(g, g + 1) for g in range(G)] if self.ladder_batches else [(0, G)]
-        ev = GroupedEvaluation(self.model, lat_r, z_r, [(int(l_off[first]), int(l_off[last])) for first, last in groups], self.skin,
-                               self.device)
-        dev, offsets = ev.device, ev.offsets
-        pos_t = torch.tensor(np.concatenate(pos_r), dtype=torch.float64, device=dev)
-        lat64 = ev.lattices()
-        dyn = DynState(pos_t, lat64, offsets, np.concatenate(m_r), torch.tensor(np.concatenate(vel), device=dev), temps, seeds,
+        ev = MdBatch(self.model, lat_r, pos_r, z_r, [(int(l_off[first]), int(l_off[last])) for first, last in groups], self.skin, self.device)
+        dev = ev.device
+        dyn = DynState(ev.pos, ev.lattice, ev.offsets, np.concatenate(m_r), torch.tensor(np.concatenate(vel), device=dev), temps, seeds,
                        ensemble="nvt_langevin", dt=self.timestep, friction=self.friction)
         remd = RemdState(l_off, temps, ladder_seeds, device=dev)
         n_attempts = (steps - 1) // self.exchange_interval if steps > 0 else 0
         history = torch.full((max(n_attempts, 1), S), -1, dtype=torch.int32, device=dev)
         t_kin = torch.full((max(n_attempts, 1), 2, S), float("nan"), dtype=torch.float64, device=dev)   # T before / after every attempt
-        whole = ev.buffers() if len(groups) > 1 else None   # (one group: the engine's own output tensors serve)
+
+        def exchange(k, out):
+            a = k // self.exchange_interval - 1
+            t_kin[a, 0].copy_(dyn.obs[:, 1])
+            remd_exchange(remd, dyn, out[K.TOTAL_ENERGY], history)
+            return lambda: t_kin[a, 1].copy_(dyn.obs[:, 1])
+
         log = MdLog()
-        for k in range(steps + 1):
-            out = ev.evaluate(pos_t, whole)
-            if 0 < k < steps and k % self.exchange_interval == 0:
-                a = k // self.exchange_interval - 1
-                dyn_step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=True)   # synchronous velocities, STARTED cleared
-                t_kin[a, 0].copy_(dyn.obs[:, 1])
-                remd_exchange(remd, dyn, out[K.TOTAL_ENERGY], history)
-                dyn_step(dyn, out[K.FORCES], out[K.STRESSES])                     # starts the next step: no second finish kick
-                t_kin[a, 1].copy_(dyn.obs[:, 1])
-            else:
-                dyn_step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=(k == steps))
-            if k % loginterval == 0 or k == steps:
-                log.append(k, out[K.TOTAL_ENERGY], dyn.obs)
-        ev.raise_on_step_errors("replica-exchange molecular dynamics")
-        st, ex = dyn.read(), remd.read()
-        e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
-        p_host, l_host, hist = pos_t.cpu().numpy(), lat64.cpu().numpy(), history[:n_attempts].cpu().numpy()
+        out = md_loop(ev, dyn, steps, sync_at=lambda k: 0 < k < steps and k % self.exchange_interval == 0, at_sync=exchange, log=log.of(dyn),
+                      loginterval=loginterval)
+        runs = md_results(ev, dyn, out, log, "replica-exchange molecular dynamics")
+        ex, hist = remd.read(), history[:n_attempts].cpu().numpy()
         t_host, target = t_kin[:n_attempts].cpu().numpy(), target_temperatures(dyn).cpu().numpy()
-        logs = log.arrays()
         res = []
         for g, t in enumerate(ladders):
             lo, hi = int(l_off[g]), int(l_off[g + 1])
@@ -184,8 +173,7 @@ class ReplicaExchange(Driver):
             replicas = []
             for idx in range(R):   # in the order of the temperature held at the end
                 s = int(ex["holder"][lo + idx])
-                replicas.append(dict(md_result(s, int(offsets[s]), int(offsets[s + 1]), p_host, st, l_host, e, f, sv, logs),
-                                     temperature=float(t[idx]), target_temperature=float(target[s]), replica=s - lo))
+                replicas.append(dict(runs[s], temperature=float(t[idx]), target_temperature=float(target[s]), replica=s - lo))
             count = ex["count"][lo:hi]
             attempts = ex["attempts"][lo:hi - 1]
             with np.errstate(invalid="ignore", divide="ignore"):

@@ -22,12 +22,10 @@ import numpy as np
 import torch
 
 from . import _cuda, _lib
-from ._driver import (Driver, MdLog, atom_offsets, check_tensor, integer, md_result, non_negative, positive, read_state, state_tensor,
-                      structure_arrays, structure_masses)
-from .data import MaterialGraphKey as K
+from ._driver import (Driver, MdBatch, MdLog, check_tensor, integer, md_loop, md_results, non_negative, positive, read_state, state_tensor,
+                      structure_arrays, structure_masses, structure_seeds)
 from .data.graph_gpu import _ptr, _stream
-from .data.md import VerletGraph
-from .dynamics import KAPPA, KB, DynState, dyn_step, maxwell_boltzmann, structure_seeds
+from .dynamics import KAPPA, KB, DynState, langevin_warm_up
 from .nn.modules import Gradient
 
 KINDS = {"heat": _lib.RNEMD_HEAT, "momentum": _lib.RNEMD_MOMENTUM}
@@ -198,66 +196,50 @@ class ReverseNEMD(Driver):
         S = len(z)
         seeds = structure_seeds(self.seed, S)
         m = structure_masses(masses, z)
-        vel = [maxwell_boltzmann(ms, self.temperature, int(sd)) for ms, sd in zip(m, seeds)]
-        model = self.model
-        cfg = model.engine.cfg
-        vg = VerletGraph(lat, z, cfg.cutoff, cfg.threebody_cutoff, skin=self.skin, device=self.device)
-        dev = vg.device
-        pos_t = torch.tensor(np.concatenate(pos), dtype=torch.float64, device=dev)
-        offsets = atom_offsets(z)
-        lat64 = vg.lattice.clone()
-        m_all = np.concatenate(m)
+        batch = MdBatch(self.model, lat, pos, z, [(0, S)], self.skin, self.device)
+        dev, pos_t, offsets, spans = batch.device, batch.pos, batch.offsets, batch.atoms
         common = dict(dt=self.timestep, friction=self.friction)
-        warm = DynState(pos_t, lat64, offsets, m_all, torch.tensor(np.concatenate(vel), device=dev), self.temperature, seeds,
-                        ensemble="nvt_langevin", **common)
-        for k in range(equilibration + 1):
-            out = vg.step(model, pos_t)
-            dyn_step(warm, out[K.FORCES], out[K.STRESSES], finish_only=(k == equilibration))   # ends on full-step velocities
-        dyn = DynState(pos_t, lat64, offsets, m_all, warm.velocities, self.temperature, seeds, ensemble="nve", **common)
+        warm = langevin_warm_up(batch, m, self.temperature, seeds, equilibration, **common)
+        m_all = np.concatenate(m)
+        dyn = DynState(pos_t, batch.lattice, offsets, m_all, warm.velocities, self.temperature, seeds, ensemble="nve", **common)
         rn = RnemdState(offsets, np.stack(lat), self.kind, self.params.axis, self.params.n_slabs, self.params.n_swaps,
                         flow_axis=self.params.flow_axis, device=dev)
         mass_t = torch.tensor(m_all, device=dev)[:, None]
-        spans = [(int(offsets[s]), int(offsets[s + 1])) for s in range(S)]
         momentum = lambda: torch.stack([(mass_t[a:b] * dyn.velocities[a:b]).sum(0) for a, b in spans])
         ke, mom = [], []
         base = np.zeros(S)
         ends = {discard + (steps - discard) * (j + 1) // blocks for j in range(blocks - 1)} - {discard}   # where a block ends, but the last
         marks = [(np.zeros((S, self.params.n_slabs), dtype=np.int64), np.zeros((S, self.params.n_slabs, 5)))]
-        log = MdLog()
-        for k in range(steps + 1):
-            out = vg.step(model, pos_t)
-            swap = 0 < k < steps and k % self.swap_interval == 0
-            sample = 0 < k < steps and k % self.sample_interval == 0 and k >= discard
+        swap = lambda k: 0 < k < steps and k % self.swap_interval == 0
+        sample = lambda k: 0 < k < steps and k % self.sample_interval == 0 and k >= discard
+
+        def reads(k, out, logged):
+            nonlocal base
             if k == discard and k > 0:
                 base = rn.read()["transferred"]   # (waits, once: what was transferred before `discard` does not count)
             if k in ends:   # (waits: the samples of step k itself belong to the next block)
                 now = rn.read()
                 marks.append((now["count"], now["sums"]))
-            if swap or sample:
-                dyn_step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=True)   # synchronous velocities, STARTED cleared
-                ke.append([dyn.obs[:, 0].clone()])
-                mom.append([momentum()])
-                rnemd_exchange(rn, dyn, pos_t, swap=swap, sample=sample)
-                mom[-1].append(momentum())                                        # (before the next step's kick changes it)
-                dyn_step(dyn, out[K.FORCES], out[K.STRESSES])                     # starts the next step: no second finish kick
-                ke[-1].append(dyn.obs[:, 0].clone())
-            else:
-                dyn_step(dyn, out[K.FORCES], out[K.STRESSES], finish_only=(k == steps))
-            if k % loginterval == 0 or k == steps:
-                log.append(k, out[K.TOTAL_ENERGY], dyn.obs)
-        vg.raise_on_step_errors("reverse non-equilibrium molecular dynamics")
-        st, ex = dyn.read(), rn.read()
-        e, f, sv = (out[key].double().cpu().numpy() for key in (K.TOTAL_ENERGY, K.FORCES, K.STRESSES))
-        p_host, l_host = pos_t.cpu().numpy(), lat64.cpu().numpy()
+
+        def exchange(k, out):
+            ke.append([dyn.obs[:, 0].clone()])
+            mom.append([momentum()])
+            rnemd_exchange(rn, dyn, pos_t, swap=swap(k), sample=sample(k))
+            mom[-1].append(momentum())   # (before the next step's kick changes it)
+            return lambda: ke[-1].append(dyn.obs[:, 0].clone())
+
+        log = MdLog()
+        out = md_loop(batch, dyn, steps, before=reads, sync_at=lambda k: swap(k) or sample(k), at_sync=exchange, log=log.of(dyn),
+                      loginterval=loginterval)
+        runs = md_results(batch, dyn, out, log, "reverse non-equilibrium molecular dynamics")
+        ex = rn.read()
         ke_host = torch.stack([torch.stack(pair) for pair in ke]).cpu().numpy() if ke else np.zeros((0, 2, S))
         mom_host = torch.stack([torch.stack(pair) for pair in mom]).cpu().numpy() if mom else np.zeros((0, 2, S, 3))
-        logs = log.arrays()
         marks.append((ex["count"], ex["sums"]))
         time = (steps - discard) * self.timestep
         res = []
-        for s, (a, b) in enumerate(spans):
+        for s, r in enumerate(runs):
             moved = float(ex["transferred"][s] - base[s])
-            r = md_result(s, a, b, p_host, st, l_host, e, f, sv, logs)
             r.update(transport_coefficients(self.kind, lat[s], self.params.axis, self.params.flow_axis, ex["count"][s], ex["sums"][s], moved,
                                             time))
             r.update(transferred=moved, n_exchanged=int(ex["n_exchanged"][s]), n_calls=int(ex["n_calls"][s]),
