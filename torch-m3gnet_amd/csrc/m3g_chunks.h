@@ -1,6 +1,14 @@
-// The device and C-ABI layer the batched drivers share: m3g_relax.hip (FIRE), m3g_lbfgs.hip, m3g_dynamics.hip, m3g_remd.hip, m3g_mc.hip,
-// m3g_neb.hip, m3g_phonons.hip, m3g_elastic.hip and m3g_trajectory.hip.  Every state buffer is described once, by the function that
-// carves its view (chunk_view below, then the driver's own regions; see Carved), and read back through read_back.  The chunk table: the N atoms of S structures cut into chunks of <= kChunkRows atoms that never straddle a
+// The device and C-ABI layer all sixteen batched drivers share.  Eight of them include it themselves: m3g_relax.hip (FIRE),
+// m3g_lbfgs.hip, m3g_neb.hip, m3g_phonons.hip, m3g_elastic.hip, m3g_trajectory.hip, m3g_nma.hip and m3g_meta.hip.  m3g_remd.hip,
+// m3g_mc.hip and m3g_rnemd.hip, which work on the state of m3g_dyn_*, reach it through m3g_dyn_state.h; the five step families
+// m3g_dynamics.hip, m3g_nhc.hip, m3g_mtk.hip, m3g_pimd.hip and m3g_ti.hip through m3g_integrator.h, which includes
+// m3g_dyn_state.h.  (m3g_eigh.hip, no driver, includes it too, for kWave and its checks.)  Here is one copy of what their C entry
+// points spell alike on the host: the checks of an init (init_args_ok, batch32_sizes_ok, structure_fits_int32, offsets_ok,
+// lattice_ok, mass_ok, temperature_ok), the size check of a state buffer (state_fits), the tails of a launch, of an init and of
+// a read (M3G_RETURN_LAUNCH_STATUS, launched_and_synced, upload_image, read_all), and the constants kKappa, kBoltzmann and kTwoPi.
+// Every state buffer is described once, by the function that carves its view (chunk_view below, then the driver's own regions;
+// see Carved), and read back through read_back.
+// The chunk table: the N atoms of S structures cut into chunks of <= kChunkRows atoms that never straddle a
 // structure, so a reduction over a chunk's rows (chunk_tree_reduce) followed by one over a structure's chunks in chunk order
 // (wave_chunk_sum, or a serial walk) depends on that structure's own rows only -- bitwise the same alone or in any batch.  Device
 // side: the offsets [S+1] (int64), the structure of every chunk and its first atom, and every structure's first chunk ([S] = the
@@ -11,6 +19,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <vector>
 
 #include "m3g_internal.h"
@@ -19,6 +28,9 @@ namespace m3g {
 constexpr int kChunkRows = 256;       // atoms per chunk == threads per workgroup of the row kernels
 constexpr int kWave = 64;
 constexpr int kFinalizeWaves = 4;     // structures (one wave each) per workgroup of the wave-per-structure kernels
+constexpr double kKappa = 9.648533215665e-3;   // A/fs^2 per eV/(A amu)
+constexpr double kBoltzmann = 8.617333262e-5;  // eV/K
+constexpr double kTwoPi = 6.283185307179586;
 
 // chunks of a batch, at most (a bound that needs no offsets, so launch grids and buffer sizes follow from N and S alone)
 inline int64_t chunk_bound(int64_t N, int64_t S) { return (N + kChunkRows - 1) / kChunkRows + S; }
@@ -124,8 +136,62 @@ inline bool lattice_ok(const char* fn, const double* L, int64_t s) {
   return true;
 }
 
+// The checks of m3g_*_init, each naming the caller `fn`; they set the library error and return false.  They come in pieces
+// because every init keeps the order of its checks, its own between them: the first thing wrong is the one reported.
+inline bool init_args_ok(const char* fn, int64_t N, int64_t S, bool pointers) {
+  if (batch_sizes_ok(N, S) && pointers) return true;
+  set_error("%s: null argument or bad sizes", fn);
+  return false;
+}
+// a batch whose structure indices fit int32_t as well
+inline bool batch32_sizes_ok(int64_t N, int64_t S) { return batch_sizes_ok(N, S) && S <= INT32_MAX; }
+// ... and a structure whose row indices do
+inline bool structure_fits_int32(const char* fn, const int64_t* host_offsets, int64_t s) {
+  if (host_offsets[s + 1] - host_offsets[s] <= INT32_MAX) return true;
+  set_error("%s: structure %lld holds too many atoms", fn, (long long)s);
+  return false;
+}
+// `of`: what a mass belongs to (a unit atom in m3g_nma_init)
+inline bool mass_ok(const char* fn, const double* host_masses, int64_t i, const char* of = "atom") {
+  if (finite_positive(host_masses[i])) return true;
+  set_error("%s: mass of %s %lld is not finite and > 0", fn, of, (long long)i);
+  return false;
+}
+// `of`: what a temperature belongs to (a ring in m3g_pimd_init); `zero_ok`: m3g_dyn_init alone takes T = 0
+inline bool temperature_ok(const char* fn, const double* host_temperatures, int64_t s, const char* of = "structure", bool zero_ok = false) {
+  const double t = host_temperatures[s];
+  if (zero_ok ? std::isfinite(t) && t >= 0.0 : finite_positive(t)) return true;
+  set_error("%s: temperature of %s %lld is not finite and %s 0", fn, of, (long long)s, zero_ok ? ">=" : ">");
+  return false;
+}
+// the caller's state buffer holds the carved view (init says both sizes); `which` names the buffer of a call that takes two
+inline bool state_fits(const char* fn, size_t state_bytes, size_t total, bool say_sizes = false, const char* which = "") {
+  if (state_bytes >= total) return true;
+  if (say_sizes) set_error("%s: state buffer too small (%zu < %zu)", fn, state_bytes, total);
+  else set_error("%s: %s%sstate buffer too small", fn, which, *which ? " " : "");
+  return false;
+}
+
 // the tail of a call that launched (a macro, as M3G_HIP_CHECK: the error names the caller's file and line)
 #define M3G_RETURN_LAUNCH_STATUS() do { M3G_HIP_CHECK(hipGetLastError()); return M3G_OK; } while (0)
+
+// the tail of an init (or of m3g_ti_path) after its launches: only now may the host arrays the copies read go out of scope
+inline int launched_and_synced(hipStream_t s) {
+  M3G_HIP_CHECK(hipGetLastError());
+  M3G_HIP_CHECK(hipStreamSynchronize(s));
+  return M3G_OK;
+}
+
+// The tail of m3g_*_read: every read-back of the list queued on s (read_back: a null destination or an empty region is skipped),
+// then the wait.  rb() makes an entry and keeps read_back's rule that the host and the device element types agree.
+struct ReadBack { void* host; const void* dev; size_t bytes; };
+template <class T>
+inline ReadBack rb(T* host, const T* dev, size_t count) { return {host, dev, sizeof(T) * count}; }
+inline int read_all(hipStream_t s, std::initializer_list<ReadBack> list) {
+  for (const ReadBack& r : list) M3G_HIP_CHECK(read_back((char*)r.host, (const char*)r.dev, r.bytes, s));
+  M3G_HIP_CHECK(hipStreamSynchronize(s));
+  return M3G_OK;
+}
 
 // The host side of the table.  upload() queues asynchronous copies from these vectors: keep the object alive until the stream has
 // been synchronised.
@@ -152,4 +218,18 @@ struct ChunkTable {
     return M3G_OK;
   }
 };
+
+// The tail of an init that filled a host image of its state (a buffer carved as the state is, so every region stands at its offset):
+// the chunk table of `host_offsets` into `ch`, the image's bytes from the region `first` up to `end` -- pointers into the device
+// state, as its view names them -- in one copy to the same place of the state, then the wait: only now may the image and the
+// caller's arrays go out of scope.  (m3g_remd_init, whose state has no chunk table, sends its whole image itself.)
+inline int upload_image(const std::vector<char>& image, const void* state, const void* first, const void* end, const ChunkView& ch,
+                        const int64_t* host_offsets, hipStream_t s) {
+  const ChunkTable table(host_offsets, ch.S);
+  if (int rc = table.upload(ch, host_offsets, s)) return rc;
+  const size_t begin = (size_t)((const char*)first - (const char*)state), bytes = (size_t)((const char*)end - (const char*)first);
+  M3G_HIP_CHECK(hipMemcpyAsync((void*)first, image.data() + begin, bytes, hipMemcpyHostToDevice, s));
+  M3G_HIP_CHECK(hipStreamSynchronize(s));
+  return M3G_OK;
+}
 }  // namespace m3g

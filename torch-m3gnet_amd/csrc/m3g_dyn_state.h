@@ -3,15 +3,14 @@
 // m3g_mc.hip (the flags, masses and velocities of a hybrid Monte Carlo batch; its own draws use philox4x64_10 and uniform53 too).
 // The five step families (m3g_dynamics.hip, m3g_nhc.hip, m3g_mtk.hip, m3g_pimd.hip, m3g_ti.hip) include it through
 // m3g_integrator.h, where the Box-Muller draw over this generator, the list of its key words and what their kernels and entry
-// points share now live; the constants, DynView, Philox and uniform53 stay here.
+// points share now live; DynView, its sizes, Philox and uniform53 stay here.  kKappa and kBoltzmann are in m3g_chunks.h, where the
+// samplers that take no dynamics state (m3g_trajectory.hip, m3g_nma.hip) find them too.
 #pragma once
 #include "m3g_chunks.h"
 #include "m3g_internal.h"
 
 namespace m3g {
-constexpr double kKappa = 9.648533215665e-3;   // A/fs^2 per eV/(A amu)
-constexpr double kBoltzmann = 8.617333262e-5;  // eV/K
-constexpr int kPart = 8;    // per chunk: sum m|v|^2, sum m v [3], sum F [3], non-finite forces
+constexpr int kPart = 8;   // per chunk: sum m|v|^2, sum m v [3], sum F [3], non-finite forces
 constexpr int kCoef = 8;    // per structure: action (0 none, 1 finish only, 2 finish + start), finish?, lambda, mu, pbar [3], noise^2
 
 struct DynView {

@@ -319,8 +319,7 @@ constexpr const char* kSizesMsg = "bad sizes (need 1 <= n_structs <= n_atoms, 1 
 int el_call_ok(const char* name, const m3g_el_sizes* sizes, const void* state, size_t state_bytes, bool pointers, int mode) {
   if (!el_sizes_ok(sizes) || !state || !pointers) { set_error("%s: null argument or %s", name, kSizesMsg); return M3G_ERR_VALUE; }
   if (mode >= 0 && sizes->mode != mode) { set_error("%s: the state was made for the other mode (M3G_EL_MODE_*)", name); return M3G_ERR_VALUE; }
-  if (state_bytes < el_view(*sizes, nullptr).bytes) { set_error("%s: state buffer too small", name); return M3G_ERR_SIZE; }
-  return M3G_OK;
+  return state_fits(name, state_bytes, el_view(*sizes, nullptr).bytes) ? M3G_OK : M3G_ERR_SIZE;
 }
 }  // namespace
 }  // namespace m3g
@@ -390,7 +389,7 @@ extern "C" int m3g_el_init(const m3g_el_sizes* sizes, const int64_t* host_offset
     else if (c < 6) D[3 * kVoigt[c][0] + kVoigt[c][1]] = D[3 * kVoigt[c][1] + kVoigt[c][0]] = 0.5 * d;
   }
   const auto [st, total] = el_view(z, state);
-  if (state_bytes < total) { set_error("m3g_el_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_el_init", state_bytes, total, true)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   M3G_HIP_CHECK(hipMemcpyAsync((void*)st.row_off, row_off.data(), 8 * (S + 1), hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync((void*)st.unit_off, host_offsets, 8 * (S + 1), hipMemcpyHostToDevice, s));

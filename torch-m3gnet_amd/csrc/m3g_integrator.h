@@ -3,8 +3,10 @@
 // m3g_rnemd.hip work on the state of m3g_dyn_* and include m3g_dyn_state.h alone).  All five have the same skeleton: a carved state
 // view; k_*_init, k_*_partials, k_*_finalize, k_*_apply; the C entry points state_bytes, state_view, init, step, read.  Here is one
 // copy of what they spell alike: on the device the Box-Muller draw, the row prologue, verdict and epilogue of the partials kernels,
-// the 8-sum partials body of m3g_dyn_* and m3g_nhc_*, the cell volume and tr W; on the host the checks of init, the size check of
-// a state buffer, the upload, the offsets of state_view, the grids of a step and the head of read.  Everything a family does on
+// the 8-sum partials body of m3g_dyn_* and m3g_nhc_*, the cell volume and tr W; on the host what only the integrators have: the
+// upload of a batch, the offsets of state_view, the grids of a step and the head of read.  (The checks of init, the size check of
+// a state buffer and the tail of an init are shared with the eleven drivers that do not integrate: m3g_chunks.h, which this
+// header reaches through m3g_dyn_state.h.)  Everything a family does on
 // its own stays in its file, and so does an idiom where the shared copy would change a kernel's vector instructions or registers:
 // the compiler's listing decides (profiles/integrator_layer.txt names each).
 // Contraction: unlike m3g_chunks.h ("no device function here multiplies") the device helpers below do multiply.  That rule is about
@@ -26,7 +28,6 @@ constexpr uint64_t kLangevinKey = 0, kPimdKey = 3, kTiKey = 4;
 __device__ inline void gaussian3(uint64_t seed, uint64_t key1, uint64_t c0, uint64_t c1, uint64_t c2, double xi[3]) {
   uint64_t c[4] = {c0, c1, c2, 0};
   philox4x64_10(c, seed, key1);
-  constexpr double kTwoPi = 6.283185307179586;
   const double r0 = sqrt(-2.0 * log(uniform53(c[0]))), r1 = sqrt(-2.0 * log(uniform53(c[2])));
   xi[0] = r0 * cos(kTwoPi * uniform53(c[1]));
   xi[1] = r0 * sin(kTwoPi * uniform53(c[1]));
@@ -95,33 +96,7 @@ __device__ inline double cell_volume(const double* L) {
 __device__ inline double virial_trace(double vol, const float* sv) { return vol * (((double)sv[0] + (double)sv[1]) + (double)sv[2]); }
 
 // ---- the C entry points (host) ---------------------------------------------------------------------------------------------------
-// The checks of m3g_*_init, each naming the caller `fn`; they set the library error and return false.  They come in pieces
-// because every init keeps the order of its checks, its own between them: the first thing wrong is the one reported.
-inline bool init_args_ok(const char* fn, int64_t N, int64_t S, bool pointers) {
-  if (batch_sizes_ok(N, S) && pointers) return true;
-  set_error("%s: null argument or bad sizes", fn);
-  return false;
-}
-inline bool mass_ok(const char* fn, const double* host_masses, int64_t i) {
-  if (finite_positive(host_masses[i])) return true;
-  set_error("%s: mass of atom %lld is not finite and > 0", fn, (long long)i);
-  return false;
-}
-// `of`: what a temperature belongs to (a ring in m3g_pimd_init); `zero_ok`: m3g_dyn_init alone takes T = 0
-inline bool temperature_ok(const char* fn, const double* host_temperatures, int64_t s, const char* of = "structure", bool zero_ok = false) {
-  const double t = host_temperatures[s];
-  if (zero_ok ? std::isfinite(t) && t >= 0.0 : finite_positive(t)) return true;
-  set_error("%s: temperature of %s %lld is not finite and %s 0", fn, of, (long long)s, zero_ok ? ">=" : ">");
-  return false;
-}
-// the caller's state buffer holds the carved view (init says both sizes)
-inline bool state_fits(const char* fn, size_t state_bytes, size_t total, bool say_sizes = false) {
-  if (state_bytes >= total) return true;
-  if (say_sizes) set_error("%s: state buffer too small (%zu < %zu)", fn, state_bytes, total);
-  else set_error("%s: state buffer too small", fn);
-  return false;
-}
-
+// (The checks of init, state_fits and launched_and_synced are in m3g_chunks.h, shared with the drivers that do not integrate.)
 // Queues the chunk table, the masses [N], the temperatures [S of the table] and, where the view has seeds, those.  Asynchronous
 // copies from the caller's arrays and from `table`: keep them alive until the stream has been synchronised.
 template <class View>
@@ -131,13 +106,6 @@ inline int upload_batch(const ChunkTable& table, const View& st, const int64_t* 
   M3G_HIP_CHECK(hipMemcpyAsync(st.mass, host_masses, 8 * st.N, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync(st.t0, host_temperatures, 8 * st.ch.S, hipMemcpyHostToDevice, s));
   if constexpr (requires { st.seed; }) M3G_HIP_CHECK(hipMemcpyAsync(st.seed, host_seeds, 8 * st.ch.S, hipMemcpyHostToDevice, s));
-  return M3G_OK;
-}
-
-// the tail of an init (or of m3g_ti_path) after its launches: only now may the host arrays the copies read go out of scope
-inline int launched_and_synced(hipStream_t s) {
-  M3G_HIP_CHECK(hipGetLastError());
-  M3G_HIP_CHECK(hipStreamSynchronize(s));
   return M3G_OK;
 }
 

@@ -465,22 +465,17 @@ extern "C" int m3g_lbfgs_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t
 extern "C" int m3g_lbfgs_init(const m3g_lbfgs_params* p, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* pos,
                               const double* lattice, void* state, size_t state_bytes, void* stream_) {
   if (!lbfgs_params_ok(p)) { set_error("m3g_lbfgs_init: %s", kBadParams); return M3G_ERR_VALUE; }
-  if (!batch_sizes_ok(n_atoms, n_structs) || !host_offsets || !pos || !state || (p->relax_cell && !lattice)) {
-    set_error("m3g_lbfgs_init: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
   const int64_t N = n_atoms, S = n_structs;
+  if (!init_args_ok("m3g_lbfgs_init", N, S, host_offsets && pos && state && (lattice || !p->relax_cell))) return M3G_ERR_VALUE;
   if (!offsets_ok("m3g_lbfgs_init", host_offsets, N, S)) return M3G_ERR_VALUE;
   const auto [st, total] = lbfgs_view(N, S, p->memory, state);
-  if (state_bytes < total) { set_error("m3g_lbfgs_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_lbfgs_init", state_bytes, total, true)) return M3G_ERR_SIZE;
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
   if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
   const int64_t work = 3 * N > S ? 3 * N : S;
   hipLaunchKernelGGL(k_lbfgs_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, st, pos, lattice);
-  M3G_HIP_CHECK(hipGetLastError());
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
-  return M3G_OK;
+  return launched_and_synced(s);   // (the host tables above go out of scope)
 }
 
 extern "C" int m3g_lbfgs_step(const m3g_lbfgs_params* p, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
@@ -491,7 +486,7 @@ extern "C" int m3g_lbfgs_step(const m3g_lbfgs_params* p, int64_t n_atoms, int64_
   if (!batch_sizes_ok(N, S) || !state || !forces || !pos) { set_error("m3g_lbfgs_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (p->relax_cell && (!stresses || !lattice)) { set_error("m3g_lbfgs_step: a cell relaxation needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
   const auto [st, total] = lbfgs_view(N, S, p->memory, state);
-  if (state_bytes < total) { set_error("m3g_lbfgs_step: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_lbfgs_step", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
   const size_t lds = 2 * sizeof(double) * (size_t)st.M;
@@ -508,12 +503,7 @@ extern "C" int m3g_lbfgs_read(int64_t n_atoms, int64_t n_structs, int32_t memory
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !state || memory < 1 || memory > kMaxMemory) { set_error("m3g_lbfgs_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = lbfgs_view(N, S, memory, (void*)state);
-  if (state_bytes < total) { set_error("m3g_lbfgs_read: state buffer too small"); return M3G_ERR_SIZE; }
-  hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
-  M3G_HIP_CHECK(read_back(host_steps, st.steps, S, s));
-  M3G_HIP_CHECK(read_back(host_pairs, st.count, S, s));
-  M3G_HIP_CHECK(read_back(host_x, st.x, 3 * st.R, s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));
-  return M3G_OK;
+  if (!state_fits("m3g_lbfgs_read", state_bytes, total)) return M3G_ERR_SIZE;
+  return read_all((hipStream_t)stream_,
+                  {rb(host_flags, st.flags, S), rb(host_steps, st.steps, S), rb(host_pairs, st.count, S), rb(host_x, st.x, 3 * st.R)});
 }

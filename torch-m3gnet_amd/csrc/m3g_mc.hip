@@ -198,14 +198,13 @@ __global__ void __launch_bounds__(kChunkRows) k_mc_commit(McView st, const float
   if (stresses && c == st.ch.chunks_begin(s) && t < 6) stresses[6 * (int64_t)s + t] = trial_stresses[6 * (int64_t)s + t];
 }
 
-bool mc_sizes_ok(int64_t N, int64_t S) { return batch_sizes_ok(N, S) && S <= INT32_MAX; }
 }  // namespace
 }  // namespace m3g
 
 using namespace m3g;
 
 extern "C" int m3g_mc_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* bytes) {
-  if (!bytes || !mc_sizes_ok(n_atoms, n_structs)) { set_error("m3g_mc_state_bytes: null argument or bad sizes"); return M3G_ERR_VALUE; }
+  if (!bytes || !batch32_sizes_ok(n_atoms, n_structs)) { set_error("m3g_mc_state_bytes: null argument or bad sizes"); return M3G_ERR_VALUE; }
   *bytes = mc_view(n_atoms, n_structs, nullptr).bytes;
   return M3G_OK;
 }
@@ -213,21 +212,18 @@ extern "C" int m3g_mc_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* by
 extern "C" int m3g_mc_init(int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* host_temperatures,
                            const uint64_t* host_seeds, const uint8_t* host_active, void* state, size_t state_bytes, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
-  if (!mc_sizes_ok(N, S) || !host_offsets || !host_temperatures || !host_seeds || !host_active || !state) {
+  if (!batch32_sizes_ok(N, S) || !host_offsets || !host_temperatures || !host_seeds || !host_active || !state) {
     set_error("m3g_mc_init: null argument or bad sizes");
     return M3G_ERR_VALUE;
   }
   if (!offsets_ok("m3g_mc_init", host_offsets, N, S)) return M3G_ERR_VALUE;
   for (int64_t s = 0; s < S; ++s) {
-    if (!finite_positive(host_temperatures[s])) {
-      set_error("m3g_mc_init: temperature of structure %lld is not finite and > 0", (long long)s);
-      return M3G_ERR_VALUE;
-    }
-    if (host_offsets[s + 1] - host_offsets[s] > INT32_MAX) { set_error("m3g_mc_init: structure %lld holds too many atoms", (long long)s); return M3G_ERR_VALUE; }
+    if (!temperature_ok("m3g_mc_init", host_temperatures, s)) return M3G_ERR_VALUE;
+    if (!structure_fits_int32("m3g_mc_init", host_offsets, s)) return M3G_ERR_VALUE;
   }
   const auto [st, total] = mc_view(N, S, state);
-  if (state_bytes < total) { set_error("m3g_mc_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
-  std::vector<char> image(total, 0);   // counters, statistics and flags start at zero (the chunk table's part is not sent: upload() below)
+  if (!state_fits("m3g_mc_init", state_bytes, total, true)) return M3G_ERR_SIZE;
+  std::vector<char> image(total, 0);   // counters, statistics and flags start at zero (the chunk table's part is not sent: upload_image)
   const McView im = mc_view(N, S, image.data()).view;
   for (int64_t i = 0; i < N; ++i) ((uint8_t*)im.active)[i] = host_active[i] ? 1 : 0;
   std::memcpy((void*)im.temps, host_temperatures, 8 * S);
@@ -237,23 +233,17 @@ extern "C" int m3g_mc_init(int64_t n_atoms, int64_t n_structs, const int64_t* ho
     for (int64_t i = host_offsets[s]; i < host_offsets[s + 1]; ++i) n_p += host_active[i] ? 1 : 0;
     if (n_p < 2) im.flags[s] = M3G_MC_NO_PAIR;   // (the species are the device's to look at: k_mc_propose)
   }
-  const ChunkTable table(host_offsets, S);
-  hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
-  const size_t table_bytes = (size_t)((const char*)im.active - image.data());   // everything after the chunk table goes in one copy
-  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.active, im.active, total - table_bytes, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host image and tables above go out of scope)
-  return M3G_OK;
+  return upload_image(image, state, st.active, (const char*)state + total, st.ch, host_offsets, (hipStream_t)stream_);   // all after the table
 }
 
 extern "C" int m3g_mc_propose(int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, int64_t* atom_types, void* dyn_state,
                               size_t dyn_bytes, const float* energies, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
-  if (!mc_sizes_ok(N, S) || !state || !atom_types || !energies) { set_error("m3g_mc_propose: null argument or bad sizes"); return M3G_ERR_VALUE; }
+  if (!batch32_sizes_ok(N, S) || !state || !atom_types || !energies) { set_error("m3g_mc_propose: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = mc_view(N, S, state);
   const auto [dyn, dyn_total] = dyn_state ? dyn_view(N, S, dyn_state) : Carved<DynView>{};
-  if (state_bytes < total) { set_error("m3g_mc_propose: Monte Carlo state buffer too small"); return M3G_ERR_SIZE; }
-  if (dyn_bytes < dyn_total) { set_error("m3g_mc_propose: dynamics state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_mc_propose", state_bytes, total, false, "Monte Carlo")) return M3G_ERR_SIZE;
+  if (!state_fits("m3g_mc_propose", dyn_bytes, dyn_total, false, "dynamics")) return M3G_ERR_SIZE;
   hipLaunchKernelGGL(k_mc_propose, dim3((unsigned)S), dim3(kWave), 0, (hipStream_t)stream_, st, atom_types, dyn.flags, dyn.mass,
                      dyn.v, energies);
   M3G_RETURN_LAUNCH_STATUS();
@@ -263,7 +253,7 @@ extern "C" int m3g_mc_decide(int64_t n_atoms, int64_t n_structs, void* state, si
                              size_t dyn_bytes, const float* trial_energies, const float* trial_forces, const float* trial_stresses,
                              float* energies, float* forces, float* stresses, int32_t* history, int64_t history_rows, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
-  if (!mc_sizes_ok(N, S) || !state || !atom_types || !trial_energies || !energies || history_rows < 0) {
+  if (!batch32_sizes_ok(N, S) || !state || !atom_types || !trial_energies || !energies || history_rows < 0) {
     set_error("m3g_mc_decide: null argument or bad sizes");
     return M3G_ERR_VALUE;
   }
@@ -273,8 +263,8 @@ extern "C" int m3g_mc_decide(int64_t n_atoms, int64_t n_structs, void* state, si
   }
   const auto [st, total] = mc_view(N, S, state);
   const auto [dyn, dyn_total] = dyn_state ? dyn_view(N, S, dyn_state) : Carved<DynView>{};
-  if (state_bytes < total) { set_error("m3g_mc_decide: Monte Carlo state buffer too small"); return M3G_ERR_SIZE; }
-  if (dyn_bytes < dyn_total) { set_error("m3g_mc_decide: dynamics state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_mc_decide", state_bytes, total, false, "Monte Carlo")) return M3G_ERR_SIZE;
+  if (!state_fits("m3g_mc_decide", dyn_bytes, dyn_total, false, "dynamics")) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   hipLaunchKernelGGL(k_mc_verdict, dim3((unsigned)S), dim3(kWave), 0, s, st, atom_types, dyn.mass, dyn.v, trial_energies, energies, history,
                      history_rows);
@@ -287,19 +277,11 @@ extern "C" int m3g_mc_read(int64_t n_atoms, int64_t n_structs, const void* state
                            int64_t* host_attempts, int64_t* host_accepts, int64_t* host_nonfinite, int64_t* host_count, double* host_mean,
                            double* host_m2, int32_t* host_pairs, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
-  if (!mc_sizes_ok(N, S) || !state) { set_error("m3g_mc_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
+  if (!batch32_sizes_ok(N, S) || !state) { set_error("m3g_mc_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = mc_view(N, S, (void*)state);
-  if (state_bytes < total) { set_error("m3g_mc_read: state buffer too small"); return M3G_ERR_SIZE; }
-  hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
-  M3G_HIP_CHECK(read_back(host_counters, st.counter, S, s));
-  M3G_HIP_CHECK(read_back(host_attempts, st.attempts, S, s));
-  M3G_HIP_CHECK(read_back(host_accepts, st.accepts, S, s));
-  M3G_HIP_CHECK(read_back(host_nonfinite, st.nonfinite, S, s));
-  M3G_HIP_CHECK(read_back(host_count, st.count, S, s));
-  M3G_HIP_CHECK(read_back(host_mean, st.mean, S, s));
-  M3G_HIP_CHECK(read_back(host_m2, st.m2, S, s));
-  M3G_HIP_CHECK(read_back(host_pairs, st.pair, 2 * S, s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));
-  return M3G_OK;
+  if (!state_fits("m3g_mc_read", state_bytes, total)) return M3G_ERR_SIZE;
+  return read_all((hipStream_t)stream_,
+                  {rb(host_flags, st.flags, S), rb(host_counters, st.counter, S), rb(host_attempts, st.attempts, S), rb(host_accepts, st.accepts, S),
+                   rb(host_nonfinite, st.nonfinite, S), rb(host_count, st.count, S), rb(host_mean, st.mean, S), rb(host_m2, st.m2, S),
+                   rb(host_pairs, st.pair, 2 * S)});
 }

@@ -364,7 +364,7 @@ __global__ void __launch_bounds__(kChunkRows) k_meta_apply(MetaView st, m3g_meta
 }
 
 bool meta_sizes_ok(int64_t N, int64_t S, int64_t G, int32_t n_cv, int64_t max_hills) {
-  return batch_sizes_ok(N, S) && S <= INT32_MAX && G >= 1 && G <= S && n_cv >= 1 && n_cv <= kMaxCv && max_hills >= 0 &&
+  return batch32_sizes_ok(N, S) && G >= 1 && G <= S && n_cv >= 1 && n_cv <= kMaxCv && max_hills >= 0 &&
          max_hills <= (int64_t)1 << 40;
 }
 
@@ -504,11 +504,9 @@ extern "C" int m3g_meta_init(const m3g_meta_params* params, int64_t n_atoms, int
     if (!(std::isfinite(host_inv_kdt[g]) && host_inv_kdt[g] >= 0.0)) { set_error("%s: inv_kdt of group %lld is not finite and >= 0", fn, (long long)g); return M3G_ERR_VALUE; }
   }
   const auto [st, total] = meta_view(N, S, G, n_cv, params->max_hills, state);
-  if (state_bytes < total) { set_error("%s: state buffer too small (%zu < %zu)", fn, state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits(fn, state_bytes, total, true)) return M3G_ERR_SIZE;
   // the host image of everything between the chunk table and the per-call regions; deposit counts and flags start at zero
-  const size_t image_begin = carve_offset(meta_view(N, S, G, n_cv, params->max_hills, nullptr).view.group_offsets);
-  const size_t image_end = carve_offset(meta_view(N, S, G, n_cv, params->max_hills, nullptr).view.partial);
-  std::vector<char> image(image_end, 0);
+  std::vector<char> image(carve_offset(meta_view(N, S, G, n_cv, params->max_hills, nullptr).view.partial), 0);
   const MetaView im = meta_view(N, S, G, n_cv, params->max_hills, image.data()).view;
   std::memcpy(im.group_offsets, host_group_offsets, 8 * (G + 1));
   for (int64_t g = 0; g < G; ++g)
@@ -524,14 +522,10 @@ extern "C" int m3g_meta_init(const m3g_meta_params* params, int64_t n_atoms, int
   std::memcpy(im.sigma, host_sigmas, 8 * n_cv * G);
   std::memcpy(im.height, host_heights, 8 * G);
   std::memcpy(im.inv_kdt, host_inv_kdt, 8 * G);
-  const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync(st.group_offsets, image.data() + image_begin, image_end - image_begin, hipMemcpyHostToDevice, s));
   const size_t hills_begin = carve_offset(meta_view(N, S, G, n_cv, params->max_hills, nullptr).view.hill_centres);
   if (total > hills_begin) M3G_HIP_CHECK(hipMemsetAsync(st.hill_centres, 0, total - hills_begin, s));   // an empty list reads as zeros
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host image and tables above go out of scope)
-  return M3G_OK;
+  return upload_image(image, state, st.group_offsets, st.partial, st.ch, host_offsets, s);
 }
 
 extern "C" int m3g_meta_bias(const m3g_meta_params* params, int64_t n_atoms, int64_t n_structs, int64_t n_groups, void* state, size_t state_bytes,
@@ -540,7 +534,7 @@ extern "C" int m3g_meta_bias(const m3g_meta_params* params, int64_t n_atoms, int
   if (int rc = meta_call_ok("m3g_meta_bias", params, N, S, G, state)) return rc;
   if (!pos || !forces || !forces_out) { set_error("m3g_meta_bias: missing pos, forces or forces_out"); return M3G_ERR_VALUE; }
   const auto [st, total] = meta_view(N, S, G, params->n_cv, params->max_hills, state);
-  if (state_bytes < total) { set_error("m3g_meta_bias: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_meta_bias", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_meta_partials, grid, dim3(kChunkRows), 0, s, st, *params, pos);
@@ -574,7 +568,7 @@ extern "C" int m3g_meta_set_hills(const m3g_meta_params* params, int64_t n_atoms
     for (int64_t q = host_group_offsets[g]; q < host_group_offsets[g + 1]; ++q) deposits[q] = host_counts[g] / R;
   }
   const auto [st, total] = meta_view(N, S, G, n_cv, H, state);
-  if (state_bytes < total) { set_error("%s: state buffer too small", fn); return M3G_ERR_SIZE; }
+  if (!state_fits(fn, state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   M3G_HIP_CHECK(hipMemcpyAsync(st.deposits, deposits.data(), 8 * S, hipMemcpyHostToDevice, s));
   if (G * H > 0) {
@@ -591,7 +585,7 @@ extern "C" int m3g_meta_read(const m3g_meta_params* params, int64_t n_atoms, int
   const int64_t N = n_atoms, S = n_structs, G = n_groups;
   if (int rc = meta_call_ok("m3g_meta_read", params, N, S, G, state)) return rc;
   const auto [st, total] = meta_view(N, S, G, params->n_cv, params->max_hills, (void*)state);
-  if (state_bytes < total) { set_error("m3g_meta_read: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_meta_read", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   std::vector<int64_t> deposits(S), groups(G + 1);
   M3G_HIP_CHECK(read_back(host_flags, (const int32_t*)st.flags, S, s));

@@ -208,7 +208,7 @@ extern "C" int m3g_neb_init(int64_t n_atoms, int64_t n_images, int64_t n_bands, 
     ep_rows += 2 * n;
   }
   const auto [st, total] = neb_view(N, I, B, state);
-  if (state_bytes < total) { set_error("m3g_neb_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_neb_init", state_bytes, total, true)) return M3G_ERR_SIZE;
   const ChunkTable table(host_image_offsets, I);
   hipStream_t s = (hipStream_t)stream_;
   if (int rc = table.upload(st.ch, host_image_offsets, s)) return rc;
@@ -231,7 +231,7 @@ extern "C" int m3g_neb_forces(int64_t n_atoms, int64_t n_images, int64_t n_bands
     return M3G_ERR_VALUE;
   }
   const auto [st, total] = neb_view(N, I, B, state);
-  if (state_bytes < total) { set_error("m3g_neb_forces: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_neb_forces", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   const dim3 grid((unsigned)chunk_bound(N, I));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_neb_partials, grid, dim3(kChunkRows), 0, s, st, pos, forces);

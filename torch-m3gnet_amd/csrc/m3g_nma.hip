@@ -26,7 +26,6 @@
 
 namespace m3g {
 namespace {
-constexpr double kKappa = 9.648533215665e-3;   // A/fs^2 per eV/(A amu) (m3g_dynamics.hip)
 constexpr int kMaxN = M3G_NMA_MAX_N;
 constexpr int kMaxLags = M3G_NMA_MAX_LAGS;
 constexpr int kPart = 8;                       // per chunk: sum m, sum m (r - r0) [3], sum m v [3], rows with a non-finite value
@@ -295,7 +294,7 @@ extern "C" int m3g_nma_init(const m3g_nma_sizes* sizes, const m3g_nma_params* pa
     return M3G_ERR_VALUE;
   }
   for (int64_t u = 0; u < U; ++u) {
-    if (!finite_positive(host_masses[u])) { set_error("%s: mass of unit atom %lld is not finite and > 0", fn, (long long)u); return M3G_ERR_VALUE; }
+    if (!mass_ok(fn, host_masses, u, "unit atom")) return M3G_ERR_VALUE;
     for (int k = 0; k < 3; ++k)
       if (!std::isfinite(host_frac[3 * u + k])) { set_error("%s: fractional coordinate of unit atom %lld is not finite", fn, (long long)u); return M3G_ERR_VALUE; }
   }
@@ -304,13 +303,10 @@ extern "C" int m3g_nma_init(const m3g_nma_sizes* sizes, const m3g_nma_params* pa
   for (int64_t k = 0; k < 2 * eig; ++k)
     if (!std::isfinite(host_eigenvectors[k])) { set_error("%s: an eigenvector element is not finite", fn); return M3G_ERR_VALUE; }
   const auto [st, total] = nma_view(*sizes, state);
-  if (state_bytes < total) { set_error("%s: state buffer too small (%zu < %zu)", fn, state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits(fn, state_bytes, total, true)) return M3G_ERR_SIZE;
   // the tables from n_unit up to the accumulators, built in a host image of that part of the state and sent in one copy
-  const NmaView at = nma_view(*sizes, nullptr).view;
-  const size_t image_begin = carve_offset(at.n_unit), image_end = carve_offset(at.done);
-  std::vector<char> image(image_end, 0);
+  std::vector<char> image(carve_offset(nma_view(*sizes, nullptr).view.done), 0);
   const NmaView im = nma_view(*sizes, image.data()).view;
-  const double two_pi = 6.283185307179586476925286766559;
   int64_t mode_at = 0, eig_at = 0, phase_at = 0;
   for (int64_t s = 0; s < S; ++s) {
     const int64_t nu = host_unit_offsets[s + 1] - host_unit_offsets[s], ns = offsets[s + 1] - offsets[s];
@@ -336,7 +332,7 @@ extern "C" int m3g_nma_init(const m3g_nma_sizes* sizes, const m3g_nma_params* pa
       for (int64_t j = 0; j < ns; ++j) {
         double x = (q[0] * f[3 * j] + q[1] * f[3 * j + 1]) + q[2] * f[3 * j + 2];
         x -= std::rint(x);   // exp(-2 pi i x) has period 1 in x: the argument stays within pi
-        ((double2*)im.phase)[phase_at + j] = make_double2(std::cos(two_pi * x), -std::sin(two_pi * x));
+        ((double2*)im.phase)[phase_at + j] = make_double2(std::cos(kTwoPi * x), -std::sin(kTwoPi * x));
       }
       eig_at += 9 * nu * nu;
       phase_at += ns;
@@ -344,13 +340,9 @@ extern "C" int m3g_nma_init(const m3g_nma_sizes* sizes, const m3g_nma_params* pa
     }
   }
   std::memcpy((void*)im.eig, host_eigenvectors, 16 * (size_t)eig);
-  const ChunkTable table(offsets.data(), S);
   hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(st.ch, offsets.data(), s)) return rc;
-  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.n_unit, image.data() + image_begin, image_end - image_begin, hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemsetAsync(st.done, 0, (size_t)((const char*)st.part - (const char*)st.done), s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host image and tables above go out of scope)
-  return M3G_OK;
+  return upload_image(image, state, st.n_unit, st.done, st.ch, offsets.data(), s);
 }
 
 extern "C" int m3g_nma_sample(const m3g_nma_sizes* sizes, const m3g_nma_params* params, void* state, size_t state_bytes, const double* pos,
@@ -360,7 +352,7 @@ extern "C" int m3g_nma_sample(const m3g_nma_sizes* sizes, const m3g_nma_params* 
   if (!state || !pos || !vel) { set_error("m3g_nma_sample: null argument"); return M3G_ERR_VALUE; }
   if (forces && !std::isfinite(kick)) { set_error("m3g_nma_sample: kick must be finite"); return M3G_ERR_VALUE; }
   const auto [st, total] = nma_view(*sizes, state);
-  if (state_bytes < total) { set_error("m3g_nma_sample: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_nma_sample", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   const dim3 chunks((unsigned)chunk_bound(sizes->n_atoms, sizes->n_structs)), per_q((unsigned)sizes->n_qpoints);
   hipLaunchKernelGGL(k_nma_com, chunks, dim3(kChunkRows), 0, s, st, pos, vel, forces, kick);   // workgroups beyond the chunk count return at once
@@ -382,18 +374,12 @@ extern "C" int m3g_nma_read(const m3g_nma_sizes* sizes, const void* state, size_
   if (const char* why = nma_error(sizes)) { set_error("m3g_nma_read: %s", why); return M3G_ERR_VALUE; }
   if (!state) { set_error("m3g_nma_read: null argument"); return M3G_ERR_VALUE; }
   const auto [st, total] = nma_view(*sizes, (void*)state);
-  if (state_bytes < total) { set_error("m3g_nma_read: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_nma_read", state_bytes, total)) return M3G_ERR_SIZE;
   const size_t S = sizes->n_structs, M = sizes->n_modes, G = sizes->n_lags;
-  hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back(host_n_samples, st.done, S, s));
-  M3G_HIP_CHECK(read_back(host_kinetic_sum, st.kinetic_sum, S, s));
-  M3G_HIP_CHECK(read_back(host_qdot2_sum, st.qdot2_sum, M, s));
-  M3G_HIP_CHECK(read_back(host_q2_sum, st.q2_sum, M, s));
-  M3G_HIP_CHECK(read_back((double2*)host_acf, st.acf, M * G, s));
-  M3G_HIP_CHECK(read_back(host_lag_count, st.lag_count, S * G, s));
-  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));
-  return M3G_OK;
+  return read_all((hipStream_t)stream_,
+                  {rb(host_n_samples, st.done, S), rb(host_kinetic_sum, st.kinetic_sum, S), rb(host_qdot2_sum, st.qdot2_sum, M),
+                   rb(host_q2_sum, st.q2_sum, M), rb((double2*)host_acf, st.acf, M * G), rb(host_lag_count, st.lag_count, S * G),
+                   rb(host_flags, st.flags, S)});
 }
 
 extern "C" int m3g_nma_frame(const m3g_nma_sizes* sizes, const void* state, size_t state_bytes, double* host_qdot, double* host_q,
@@ -401,10 +387,7 @@ extern "C" int m3g_nma_frame(const m3g_nma_sizes* sizes, const void* state, size
   if (const char* why = nma_error(sizes)) { set_error("m3g_nma_frame: %s", why); return M3G_ERR_VALUE; }
   if (!state || !host_qdot || !host_q) { set_error("m3g_nma_frame: null argument"); return M3G_ERR_VALUE; }
   const auto [st, total] = nma_view(*sizes, (void*)state);
-  if (state_bytes < total) { set_error("m3g_nma_frame: state buffer too small"); return M3G_ERR_SIZE; }
-  hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back((double2*)host_qdot, st.last_qdot, (size_t)sizes->n_modes, s));
-  M3G_HIP_CHECK(read_back((double2*)host_q, st.last_q, (size_t)sizes->n_modes, s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));
-  return M3G_OK;
+  if (!state_fits("m3g_nma_frame", state_bytes, total)) return M3G_ERR_SIZE;
+  return read_all((hipStream_t)stream_,
+                  {rb((double2*)host_qdot, st.last_qdot, sizes->n_modes), rb((double2*)host_q, st.last_q, sizes->n_modes)});
 }

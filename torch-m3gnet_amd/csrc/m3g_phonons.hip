@@ -469,7 +469,7 @@ extern "C" int m3g_ph_init(const m3g_ph_sizes* sizes, const int64_t* host_unit_o
       }
   }
   const auto [st, total] = ph_view(z, state);
-  if (state_bytes < total) { set_error("m3g_ph_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_ph_init", state_bytes, total, true)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   M3G_HIP_CHECK(hipMemcpyAsync((void*)st.row_off, row_off.data(), 8 * (S + 1), hipMemcpyHostToDevice, s));
   M3G_HIP_CHECK(hipMemcpyAsync((void*)st.unit_off, host_unit_offsets, 8 * (S + 1), hipMemcpyHostToDevice, s));
@@ -489,7 +489,7 @@ extern "C" int m3g_ph_init(const m3g_ph_sizes* sizes, const int64_t* host_unit_o
 extern "C" int m3g_ph_displace(const m3g_ph_sizes* sizes, const void* state, size_t state_bytes, double* pos, void* stream_) {
   if (!ph_sizes_ok(sizes) || !state || !pos) { set_error("m3g_ph_displace: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = ph_view(*sizes, state);
-  if (state_bytes < total) { set_error("m3g_ph_displace: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_ph_displace", state_bytes, total)) return M3G_ERR_SIZE;
   hipLaunchKernelGGL(k_ph_displace, grid_for(st.rows, 256), dim3(256), 0, (hipStream_t)stream_, st, pos);
   M3G_RETURN_LAUNCH_STATUS();
 }
@@ -501,7 +501,7 @@ extern "C" int m3g_ph_force_constants(const m3g_ph_sizes* sizes, const void* sta
     return M3G_ERR_VALUE;
   }
   const auto [st, total] = ph_view(*sizes, state);
-  if (state_bytes < total) { set_error("m3g_ph_force_constants: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_ph_force_constants", state_bytes, total)) return M3G_ERR_SIZE;
   hipLaunchKernelGGL(k_ph_force_constants, dim3((unsigned)st.U), dim3(kFcThreads), 0, (hipStream_t)stream_, st, forces, (int)asr, phi, sums,
                      nonfinite);
   M3G_RETURN_LAUNCH_STATUS();
@@ -518,7 +518,7 @@ int dynmat_call(const char* fn, const m3g_ph_sizes* sizes, const void* state, si
     return M3G_ERR_VALUE;
   }
   const auto [st, total] = ph_view(*sizes, state);
-  if (state_bytes < total) { set_error("%s: state buffer too small", fn); return M3G_ERR_SIZE; }
+  if (!state_fits(fn, state_bytes, total)) return M3G_ERR_SIZE;
   if (n_q == 0) return M3G_OK;
   const int64_t pairs = (int64_t)max_unit_atoms * (max_unit_atoms + 1) / 2;
   const int64_t per_q = (pairs + kDynThreads - 1) / kDynThreads;

@@ -260,22 +260,17 @@ extern "C" int m3g_fire_state_bytes(int64_t n_atoms, int64_t n_structs, size_t* 
 extern "C" int m3g_fire_init(const m3g_fire_params* p, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets, const double* pos,
                              const double* lattice, void* state, size_t state_bytes, void* stream_) {
   if (!fire_params_ok(p)) { set_error("m3g_fire_init: invalid FIRE parameters (fmax, dt, maxstep, dtmax, finc, fdec > 0; astart, fa in [0, 1])"); return M3G_ERR_VALUE; }
-  if (!batch_sizes_ok(n_atoms, n_structs) || !host_offsets || !pos || !state || (p->relax_cell && !lattice)) {
-    set_error("m3g_fire_init: null argument or bad sizes");
-    return M3G_ERR_VALUE;
-  }
   const int64_t N = n_atoms, S = n_structs;
+  if (!init_args_ok("m3g_fire_init", N, S, host_offsets && pos && state && (lattice || !p->relax_cell))) return M3G_ERR_VALUE;
   if (!offsets_ok("m3g_fire_init", host_offsets, N, S)) return M3G_ERR_VALUE;
   const auto [st, total] = fire_view(N, S, state);
-  if (state_bytes < total) { set_error("m3g_fire_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_fire_init", state_bytes, total, true)) return M3G_ERR_SIZE;
   const ChunkTable table(host_offsets, S);
   hipStream_t s = (hipStream_t)stream_;
   if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
   const int64_t work = 3 * N > S ? 3 * N : S;
   hipLaunchKernelGGL(k_fire_init, grid_for(work, kChunkRows), dim3(kChunkRows), 0, s, st, pos, lattice, p->dt, p->astart);
-  M3G_HIP_CHECK(hipGetLastError());
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host tables above go out of scope)
-  return M3G_OK;
+  return launched_and_synced(s);   // (the host tables above go out of scope)
 }
 
 extern "C" int m3g_fire_step(const m3g_fire_params* p, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes, const float* forces,
@@ -286,7 +281,7 @@ extern "C" int m3g_fire_step(const m3g_fire_params* p, int64_t n_atoms, int64_t 
   if (!batch_sizes_ok(N, S) || !state || !forces || !pos) { set_error("m3g_fire_step: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (p->relax_cell && (!stresses || !lattice)) { set_error("m3g_fire_step: a cell relaxation needs stresses and the fp64 lattice"); return M3G_ERR_VALUE; }
   const auto [st, total] = fire_view(N, S, state);
-  if (state_bytes < total) { set_error("m3g_fire_step: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_fire_step", state_bytes, total)) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   const dim3 grid((unsigned)chunk_bound(N, S));   // workgroups beyond the table's chunk count return at once
   hipLaunchKernelGGL(k_fire_partials, grid, dim3(kChunkRows), 0, s, st, p->relax_cell, forces);
@@ -300,16 +295,8 @@ extern "C" int m3g_fire_read(int64_t n_atoms, int64_t n_structs, const void* sta
   const int64_t N = n_atoms, S = n_structs;
   if (!batch_sizes_ok(N, S) || !state) { set_error("m3g_fire_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = fire_view(N, S, (void*)state);
-  if (state_bytes < total) { set_error("m3g_fire_read: state buffer too small"); return M3G_ERR_SIZE; }
-  hipStream_t s = (hipStream_t)stream_;
+  if (!state_fits("m3g_fire_read", state_bytes, total)) return M3G_ERR_SIZE;
   const int64_t R = N + 3 * S;
-  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
-  M3G_HIP_CHECK(read_back(host_steps, st.steps, S, s));
-  M3G_HIP_CHECK(read_back(host_dt, st.dt, S, s));
-  M3G_HIP_CHECK(read_back(host_a, st.a, S, s));
-  M3G_HIP_CHECK(read_back(host_n, st.n, S, s));
-  M3G_HIP_CHECK(read_back(host_x, st.x, 3 * R, s));
-  M3G_HIP_CHECK(read_back(host_v, st.v, 3 * R, s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));
-  return M3G_OK;
+  return read_all((hipStream_t)stream_, {rb(host_flags, st.flags, S), rb(host_steps, st.steps, S), rb(host_dt, st.dt, S), rb(host_a, st.a, S),
+                                         rb(host_n, st.n, S), rb(host_x, st.x, 3 * R), rb(host_v, st.v, 3 * R)});
 }

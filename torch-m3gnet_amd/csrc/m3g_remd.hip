@@ -159,7 +159,7 @@ extern "C" int m3g_remd_init(int64_t n_structs, int64_t n_ladders, const int64_t
       }
   }
   const size_t total = remd_view(S, G, nullptr).bytes;
-  if (state_bytes < total) { set_error("m3g_remd_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_remd_init", state_bytes, total, true)) return M3G_ERR_SIZE;
   std::vector<char> image(total, 0);   // counts, means, accepts and the attempt counters start at zero
   const RemdView im = remd_view(S, G, image.data()).view;
   std::memcpy((void*)im.offsets, host_ladder_offsets, 8 * (G + 1));
@@ -187,8 +187,8 @@ extern "C" int m3g_remd_exchange(int64_t n_atoms, int64_t n_structs, int64_t n_l
   }
   const auto [st, remd_total] = remd_view(S, G, remd_state);
   const auto [dyn, dyn_total] = dyn_view(N, S, dyn_state);
-  if (remd_bytes < remd_total) { set_error("m3g_remd_exchange: replica-exchange state buffer too small"); return M3G_ERR_SIZE; }
-  if (dyn_bytes < dyn_total) { set_error("m3g_remd_exchange: dynamics state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_remd_exchange", remd_bytes, remd_total, false, "replica-exchange")) return M3G_ERR_SIZE;
+  if (!state_fits("m3g_remd_exchange", dyn_bytes, dyn_total, false, "dynamics")) return M3G_ERR_SIZE;
   hipStream_t s = (hipStream_t)stream_;
   hipLaunchKernelGGL(k_remd_decide, dim3((unsigned)G), dim3(kWave), 0, s, st, dyn.t0, dyn.flags, energies, history, history_rows);
   hipLaunchKernelGGL(k_remd_rescale, dim3((unsigned)chunk_bound(N, S)), dim3(kChunkRows), 0, s, dyn, st.scale);
@@ -201,17 +201,9 @@ extern "C" int m3g_remd_read(int64_t n_structs, int64_t n_ladders, const void* s
   const int64_t S = n_structs, G = n_ladders;
   if (!remd_sizes_ok(S, G) || !state) { set_error("m3g_remd_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   const auto [st, total] = remd_view(S, G, (void*)state);
-  if (state_bytes < total) { set_error("m3g_remd_read: state buffer too small"); return M3G_ERR_SIZE; }
-  hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back(host_held, st.held, S, s));
-  M3G_HIP_CHECK(read_back(host_holder, st.holder, S, s));
-  M3G_HIP_CHECK(read_back(host_attempts, st.attempts, S, s));
-  M3G_HIP_CHECK(read_back(host_accepts, st.accepts, S, s));
-  M3G_HIP_CHECK(read_back(host_count, st.count, S, s));
-  M3G_HIP_CHECK(read_back(host_mean, st.mean, S, s));
-  M3G_HIP_CHECK(read_back(host_m2, st.m2, S, s));
-  M3G_HIP_CHECK(read_back(host_round_trips, st.trips, S, s));
-  M3G_HIP_CHECK(read_back(host_counters, st.counter, G, s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));
-  return M3G_OK;
+  if (!state_fits("m3g_remd_read", state_bytes, total)) return M3G_ERR_SIZE;
+  return read_all((hipStream_t)stream_,
+                  {rb(host_held, st.held, S), rb(host_holder, st.holder, S), rb(host_attempts, st.attempts, S), rb(host_accepts, st.accepts, S),
+                   rb(host_count, st.count, S), rb(host_mean, st.mean, S), rb(host_m2, st.m2, S), rb(host_round_trips, st.trips, S),
+                   rb(host_counters, st.counter, G)});
 }

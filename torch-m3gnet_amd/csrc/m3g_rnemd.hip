@@ -282,7 +282,6 @@ __global__ void __launch_bounds__(kFinalizeWaves * kWave) k_rnemd_finalize(Rnemd
   }
 }
 
-bool rnemd_sizes_ok(int64_t N, int64_t S) { return batch_sizes_ok(N, S) && S <= INT32_MAX; }
 bool rnemd_slabs_ok(int32_t n_slabs) { return n_slabs >= 2 && n_slabs <= kMaxSlabs && n_slabs % 2 == 0; }
 
 bool rnemd_params_ok(const char* fn, const m3g_rnemd_params* p) {
@@ -302,7 +301,7 @@ bool rnemd_params_ok(const char* fn, const m3g_rnemd_params* p) {
 using namespace m3g;
 
 extern "C" int m3g_rnemd_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t n_slabs, size_t* bytes) {
-  if (!bytes || !rnemd_sizes_ok(n_atoms, n_structs) || !rnemd_slabs_ok(n_slabs)) {
+  if (!bytes || !batch32_sizes_ok(n_atoms, n_structs) || !rnemd_slabs_ok(n_slabs)) {
     set_error("m3g_rnemd_state_bytes: null argument or bad sizes");
     return M3G_ERR_VALUE;
   }
@@ -313,7 +312,7 @@ extern "C" int m3g_rnemd_state_bytes(int64_t n_atoms, int64_t n_structs, int32_t
 extern "C" int m3g_rnemd_init(const m3g_rnemd_params* params, int64_t n_atoms, int64_t n_structs, const int64_t* host_offsets,
                               const double* host_lattices, const uint8_t* host_active, void* state, size_t state_bytes, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
-  if (!params || !rnemd_sizes_ok(N, S) || !host_offsets || !host_lattices || !state) {
+  if (!params || !batch32_sizes_ok(N, S) || !host_offsets || !host_lattices || !state) {
     set_error("m3g_rnemd_init: null argument or bad sizes");
     return M3G_ERR_VALUE;
   }
@@ -321,11 +320,11 @@ extern "C" int m3g_rnemd_init(const m3g_rnemd_params* params, int64_t n_atoms, i
   if (!offsets_ok("m3g_rnemd_init", host_offsets, N, S)) return M3G_ERR_VALUE;
   for (int64_t s = 0; s < S; ++s) {
     if (!lattice_ok("m3g_rnemd_init", host_lattices + 9 * s, s)) return M3G_ERR_VALUE;
-    if (host_offsets[s + 1] - host_offsets[s] > INT32_MAX) { set_error("m3g_rnemd_init: structure %lld holds too many atoms", (long long)s); return M3G_ERR_VALUE; }
+    if (!structure_fits_int32("m3g_rnemd_init", host_offsets, s)) return M3G_ERR_VALUE;
   }
   const auto [st, total] = rnemd_view(N, S, params->n_slabs, state);
-  if (state_bytes < total) { set_error("m3g_rnemd_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
-  std::vector<char> image(total, 0);   // counters and accumulators start at zero (the chunk table's part is not sent: upload() below)
+  if (!state_fits("m3g_rnemd_init", state_bytes, total, true)) return M3G_ERR_SIZE;
+  std::vector<char> image(total, 0);   // counters and accumulators start at zero (the chunk table's part is not sent: upload_image)
   const RnemdView im = rnemd_view(N, S, params->n_slabs, image.data()).view;
   for (int64_t i = 0; i < N; ++i) ((uint8_t*)im.active)[i] = (!host_active || host_active[i]) ? 1 : 0;
   for (int64_t s = 0; s < S; ++s) {
@@ -334,27 +333,21 @@ extern "C" int m3g_rnemd_init(const m3g_rnemd_params* params, int64_t n_atoms, i
     for (int k = 0; k < 3; ++k) ((double*)im.g)[3 * s + k] = inv[3 * k + params->axis];
   }
   for (int64_t q = 0; q < S * kMaxSwaps * 2; ++q) im.last_pairs[q] = -1;
-  const ChunkTable table(host_offsets, S);
-  hipStream_t s = (hipStream_t)stream_;
-  if (int rc = table.upload(st.ch, host_offsets, s)) return rc;
-  const size_t table_bytes = (size_t)((const char*)im.active - image.data());   // everything after the chunk table goes in one copy
-  M3G_HIP_CHECK(hipMemcpyAsync((void*)st.active, im.active, total - table_bytes, hipMemcpyHostToDevice, s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));   // (the host image and tables above go out of scope)
-  return M3G_OK;
+  return upload_image(image, state, st.active, (const char*)state + total, st.ch, host_offsets, (hipStream_t)stream_);   // all after the table
 }
 
 extern "C" int m3g_rnemd_exchange(const m3g_rnemd_params* params, int64_t n_atoms, int64_t n_structs, void* state, size_t state_bytes,
                                   void* dyn_state, size_t dyn_bytes, const double* pos, int32_t do_swap, int32_t do_sample, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
-  if (!params || !rnemd_sizes_ok(N, S) || !state || !dyn_state || !pos) {
+  if (!params || !batch32_sizes_ok(N, S) || !state || !dyn_state || !pos) {
     set_error("m3g_rnemd_exchange: null argument or bad sizes");
     return M3G_ERR_VALUE;
   }
   if (!rnemd_params_ok("m3g_rnemd_exchange", params)) return M3G_ERR_VALUE;
   const auto [st, total] = rnemd_view(N, S, params->n_slabs, state);
   const auto [dyn, dyn_total] = dyn_view(N, S, dyn_state);
-  if (state_bytes < total) { set_error("m3g_rnemd_exchange: rNEMD state buffer too small"); return M3G_ERR_SIZE; }
-  if (dyn_bytes < dyn_total) { set_error("m3g_rnemd_exchange: dynamics state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_rnemd_exchange", state_bytes, total, false, "rNEMD")) return M3G_ERR_SIZE;
+  if (!state_fits("m3g_rnemd_exchange", dyn_bytes, dyn_total, false, "dynamics")) return M3G_ERR_SIZE;
   if (!do_swap && !do_sample) return M3G_OK;   // nothing asked for
   hipStream_t s = (hipStream_t)stream_;
   hipLaunchKernelGGL(k_rnemd_chunks, dim3((unsigned)chunk_bound(N, S)), dim3(kChunkRows), 0, s, st, *params, dyn.flags, dyn.mass, dyn.v, pos,
@@ -368,18 +361,12 @@ extern "C" int m3g_rnemd_read(const m3g_rnemd_params* params, int64_t n_atoms, i
                               int64_t* host_n_calls, int64_t* host_n_exchanged, double* host_transferred, int64_t* host_n_samples,
                               int32_t* host_last_pairs, int64_t* host_count, double* host_sums, void* stream_) {
   const int64_t N = n_atoms, S = n_structs;
-  if (!params || !rnemd_sizes_ok(N, S) || !state) { set_error("m3g_rnemd_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
+  if (!params || !batch32_sizes_ok(N, S) || !state) { set_error("m3g_rnemd_read: null argument or bad sizes"); return M3G_ERR_VALUE; }
   if (!rnemd_params_ok("m3g_rnemd_read", params)) return M3G_ERR_VALUE;
   const auto [st, total] = rnemd_view(N, S, params->n_slabs, (void*)state);
-  if (state_bytes < total) { set_error("m3g_rnemd_read: state buffer too small"); return M3G_ERR_SIZE; }
-  hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back(host_n_calls, st.n_calls, S, s));
-  M3G_HIP_CHECK(read_back(host_n_exchanged, st.n_exchanged, S, s));
-  M3G_HIP_CHECK(read_back(host_transferred, st.transferred, S, s));
-  M3G_HIP_CHECK(read_back(host_n_samples, st.n_samples, S, s));
-  M3G_HIP_CHECK(read_back(host_last_pairs, st.last_pairs, S * params->n_swaps * 2, s));
-  M3G_HIP_CHECK(read_back(host_count, st.count, S * params->n_slabs, s));
-  M3G_HIP_CHECK(read_back(host_sums, st.sums, S * params->n_slabs * kTerms, s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));
-  return M3G_OK;
+  if (!state_fits("m3g_rnemd_read", state_bytes, total)) return M3G_ERR_SIZE;
+  return read_all((hipStream_t)stream_,
+                  {rb(host_n_calls, st.n_calls, S), rb(host_n_exchanged, st.n_exchanged, S), rb(host_transferred, st.transferred, S),
+                   rb(host_n_samples, st.n_samples, S), rb(host_last_pairs, st.last_pairs, S * params->n_swaps * 2),
+                   rb(host_count, st.count, S * params->n_slabs), rb(host_sums, st.sums, S * params->n_slabs * kTerms)});
 }

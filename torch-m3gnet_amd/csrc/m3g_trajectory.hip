@@ -22,7 +22,6 @@
 
 namespace m3g {
 namespace {
-constexpr double kKappa = 9.648533215665e-3;   // A/fs^2 per eV/(A amu) (m3g_dynamics.hip)
 constexpr int kTile = kChunkRows;              // atoms per RDF tile == threads per workgroup
 constexpr int kLagBlock = 8;                   // lags per workgroup of k_traj_partials (2 kLagBlock columns of 256 doubles in LDS: 32 KB)
 constexpr int kComPart = 7;                    // per chunk: sum m, sum m r [3], sum m v [3]
@@ -321,11 +320,11 @@ extern "C" int m3g_traj_init(const m3g_traj_sizes* sizes, const m3g_traj_params*
         set_error("m3g_traj_init: species index of atom %lld is outside 0 .. max_species - 1", (long long)i);
         return M3G_ERR_VALUE;
       }
-      if (!finite_positive(host_masses[i])) { set_error("m3g_traj_init: mass of atom %lld is not finite and > 0", (long long)i); return M3G_ERR_VALUE; }
+      if (!mass_ok("m3g_traj_init", host_masses, i)) return M3G_ERR_VALUE;
       if (host_species[i] >= nspec[s]) nspec[s] = host_species[i] + 1;
     }
   const auto [st, total] = traj_view(*sizes, state);
-  if (state_bytes < total) { set_error("m3g_traj_init: state buffer too small (%zu < %zu)", state_bytes, total); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_traj_init", state_bytes, total, true)) return M3G_ERR_SIZE;
   std::vector<TilePair> pairs;
   if (sizes->rdf_bins > 0)
     for (int64_t s = 0; s < S; ++s)
@@ -353,7 +352,7 @@ extern "C" int m3g_traj_sample(const m3g_traj_sizes* sizes, const m3g_traj_param
   if (!state || !pos || (rdf && !lattice) || (lags && !vel)) { set_error("m3g_traj_sample: null argument"); return M3G_ERR_VALUE; }
   if (forces && !std::isfinite(kick)) { set_error("m3g_traj_sample: kick must be finite"); return M3G_ERR_VALUE; }
   const auto [st, total] = traj_view(*sizes, state);
-  if (state_bytes < total) { set_error("m3g_traj_sample: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_traj_sample", state_bytes, total)) return M3G_ERR_SIZE;
   const int64_t N = sizes->n_atoms, S = sizes->n_structs;
   hipStream_t s = (hipStream_t)stream_;
   if (rdf) {   // workgroups beyond the table's pair count return at once
@@ -381,18 +380,12 @@ extern "C" int m3g_traj_read(const m3g_traj_sizes* sizes, const void* state, siz
   if (const char* why = traj_error(sizes, &kNoRdf)) { set_error("m3g_traj_read: %s", why); return M3G_ERR_VALUE; }
   if (!state) { set_error("m3g_traj_read: null argument"); return M3G_ERR_VALUE; }
   const auto [st, total] = traj_view(*sizes, (void*)state);
-  if (state_bytes < total) { set_error("m3g_traj_read: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_traj_read", state_bytes, total)) return M3G_ERR_SIZE;
   const size_t S = sizes->n_structs, M = sizes->max_species, B = sizes->rdf_bins, G = sizes->n_lags;
-  hipStream_t s = (hipStream_t)stream_;
-  M3G_HIP_CHECK(read_back((unsigned long long*)host_hist, st.hist, S * species_pairs((int)M) * B, s));
-  M3G_HIP_CHECK(read_back(host_msd, st.msd, S * M * G, s));
-  M3G_HIP_CHECK(read_back(host_vacf, st.vacf, S * M * G, s));
-  M3G_HIP_CHECK(read_back(host_lag_count, st.lag_count, S * G, s));
-  M3G_HIP_CHECK(read_back(host_n_samples, st.n_samples, S, s));
-  M3G_HIP_CHECK(read_back(host_volume_sum, st.volume, S, s));
-  M3G_HIP_CHECK(read_back(host_flags, st.flags, S, s));
-  M3G_HIP_CHECK(hipStreamSynchronize(s));
-  return M3G_OK;
+  return read_all((hipStream_t)stream_,
+                  {rb((unsigned long long*)host_hist, st.hist, S * species_pairs((int)M) * B), rb(host_msd, st.msd, S * M * G),
+                   rb(host_vacf, st.vacf, S * M * G), rb(host_lag_count, st.lag_count, S * G), rb(host_n_samples, st.n_samples, S),
+                   rb(host_volume_sum, st.volume, S), rb(host_flags, st.flags, S)});
 }
 
 extern "C" int m3g_traj_frame(const m3g_traj_sizes* sizes, const void* state, size_t state_bytes, int32_t lag, double* host_pos, double* host_vel,
@@ -400,7 +393,7 @@ extern "C" int m3g_traj_frame(const m3g_traj_sizes* sizes, const void* state, si
   if (const char* why = traj_error(sizes, &kNoRdf)) { set_error("m3g_traj_frame: %s", why); return M3G_ERR_VALUE; }
   if (!state || !host_pos || !host_vel || sizes->n_lags == 0) { set_error("m3g_traj_frame: null argument or no ring (n_lags == 0)"); return M3G_ERR_VALUE; }
   const auto [st, total] = traj_view(*sizes, (void*)state);
-  if (state_bytes < total) { set_error("m3g_traj_frame: state buffer too small"); return M3G_ERR_SIZE; }
+  if (!state_fits("m3g_traj_frame", state_bytes, total)) return M3G_ERR_SIZE;
   const int64_t N = sizes->n_atoms, G = sizes->n_lags;
   hipStream_t s = (hipStream_t)stream_;
   int64_t ctr[kCounters];
