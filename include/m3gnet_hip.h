@@ -1095,6 +1095,70 @@ int m3g_traj_read(const m3g_traj_sizes* sizes, const void* state, size_t state_b
 int m3g_traj_frame(const m3g_traj_sizes* sizes, const void* state, size_t state_bytes, int32_t lag, double* host_pos, double* host_vel,
                    void* stream);
 
+/* ---- scattering observables: S(q), F(q,t) and current correlations accumulated on the device (csrc/m3g_scattering.hip) ----------------
+ * The reciprocal-space companion of the trajectory observables above, fed one frame per m3g_sq_sample.  Structure s has its own list
+ * of Q_s integer Miller triples h != 0.  With L the CURRENT cell (rows = lattice vectors), q = 2 pi h L^-T, so that q . r = 2 pi h . f
+ * with f = r L^-1: every h is commensurate with every cell, so a moving cell (NPT) needs no special case.  Per species a (local
+ * indices as in m3g_traj_*):
+ *   rho_a(q) = sum_{j in a} exp(-i q . r_j)        j_a(q) = sum_{j in a} v_j exp(-i q . r_j)
+ *   j_L = qhat . j                                 j_T = j - qhat j_L            (qhat from the cell current at that sample)
+ * v is `vel` as given, or with `forces` vel + kick kappa F / m, the completion of m3g_traj_sample.  With remove_com positions and
+ * velocities are relative to the structure's mass-weighted centre of mass: under Langevin dynamics the centre of mass diffuses,
+ * and a displacement d of it multiplies rho(q, t) by exp(-i q . d), a spurious phase that would decay F(q,t) at a rate that is no
+ * property of the material.
+ * Phases: positions are the integrator's unwrapped ones; f is reduced to f - rint(f) in fp64 before h . f is formed, h . f is
+ * reduced again, and sincospi only ever sees an argument in [-1, 1].
+ * Accumulated over a ring of the last n_lags samples, per structure, q, species pair (a <= b, row-major upper triangle as the RDF's
+ * histogram rows) and lag l -- sums only, normalisation is the caller's:
+ *   F_sum [q,ab,l] += Re[rho_a(t) rho_b*(t-l) + rho_b(t) rho_a*(t-l)] / 2
+ *   CL_sum[q,ab,l] += Re[j_L,a(t) j_L,b*(t-l) + j_L,b(t) j_L,a*(t-l)] / 2
+ *   CT_sum[q,ab,l] += 1/2 Re[j_T,a(t) . j_T,b*(t-l) + j_T,b(t) . j_T,a*(t-l)] / 2     (the mean over the two transverse directions)
+ * with lag_count[s,l] and n_samples[s] per structure.  A sample whose cell is not invertible (|det| < 1e-12 or not finite) sets
+ * M3G_SQ_CELL in the structure's flags and takes no part in any sum, now or as the older frame of a later lag; n_samples and
+ * lag_count do not count it.  No float atomics, fixed-order sums: every number depends on the structure's own rows only, bitwise
+ * the same alone or in any batch. */
+typedef struct {
+  int64_t n_atoms;       /* N */
+  int64_t n_structs;     /* S */
+  int64_t n_q;           /* total number of q-vectors over the structures, >= 1 */
+  int32_t max_species;   /* 1 .. 4 (M3G_SQ_MAX_SPECIES): species indices are local, 0 .. max_species - 1 */
+  int32_t n_lags;        /* 1 .. 4096: ring of n_lags entries of 80 bytes per (q, species) */
+} m3g_sq_sizes;
+typedef struct {
+  int32_t remove_com;    /* 0 / 1 */
+  int32_t reserved;      /* 0 */
+} m3g_sq_params;
+#define M3G_SQ_MAX_INDEX 128     /* |h_k| at most */
+#define M3G_SQ_MAX_Q 4096        /* q-vectors of one structure at most */
+#define M3G_SQ_MAX_SPECIES 4
+#define M3G_SQ_MAX_LAGS 4096
+#define M3G_SQ_CELL 1            /* a sample saw a cell that is not invertible: it was left out */
+/* Sizes outside their limits -> M3G_ERR_VALUE.  The size follows from `sizes` alone: the per-chunk partial sums are laid out for
+ * min(n_q, M3G_SQ_MAX_Q) vectors in every one of the ceil(N / 256) + S chunks a batch of these sizes can have (64 max_species bytes
+ * each). */
+int m3g_sq_state_bytes(const m3g_sq_sizes* sizes, size_t* bytes);
+/* HOST host_offsets [S+1], host_species [N], host_masses [N] as m3g_traj_init; host_q_offsets [S+1] (int64, 0 = o_0 <= o_1 <= ... <=
+ * o_S = n_q: a structure without vectors is legal and costs nothing), host_hkl [n_q,3] int32.  Everything is checked on the host
+ * before any HIP call -> M3G_ERR_VALUE: h = 0, |h_k| > M3G_SQ_MAX_INDEX, more than M3G_SQ_MAX_Q vectors in one structure, offsets
+ * that do not end at n_q; a short state buffer -> M3G_ERR_SIZE.  Uploads the tables, zeroes the accumulators, waits for the stream. */
+int m3g_sq_init(const m3g_sq_sizes* sizes, const m3g_sq_params* params, const int64_t* host_offsets, const int32_t* host_species,
+                const double* host_masses, const int64_t* host_q_offsets, const int32_t* host_hkl, void* state, size_t state_bytes,
+                void* stream);
+/* One sample: pos [N,3], lattice [S,3,3], vel [N,3] fp64, forces [N,3] f32 or NULL, all DEVICE.  Three launches (four with
+ * remove_com) whatever S, Q, N and n_lags; the ring position lives in the state buffer (the two counters of m3g_traj_sample): no
+ * allocation, copy or wait, capture-safe. */
+int m3g_sq_sample(const m3g_sq_sizes* sizes, const m3g_sq_params* params, void* state, size_t state_bytes, const double* pos,
+                  const double* lattice, const double* vel, const float* forces, double kick, void* stream);
+/* The accumulators to HOST memory; every output may be NULL: f, cl, ct [n_q, P, n_lags] fp64 with P = max_species (max_species + 1)
+ * / 2; lag_count [S, n_lags] int64; n_samples [S] int64; flags [S] int32 (M3G_SQ_*).  Waits for the stream. */
+int m3g_sq_read(const m3g_sq_sizes* sizes, const void* state, size_t state_bytes, double* host_f, double* host_cl, double* host_ct,
+                int64_t* host_lag_count, int64_t* host_n_samples, int32_t* host_flags, void* stream);
+/* The stored ring entry `lag` samples back (0: the last sample; < n_lags and < the samples taken, else M3G_ERR_VALUE) to HOST
+ * memory, complex numbers as (re, im) pairs of fp64: rho, j_L [n_q, max_species], j_T [n_q, max_species, 3]; every output may be
+ * NULL.  The first stage (densities and projected currents) on its own.  Waits for the stream. */
+int m3g_sq_frame(const m3g_sq_sizes* sizes, const void* state, size_t state_bytes, int32_t lag, double* host_rho, double* host_jl,
+                 double* host_jt, void* stream);
+
 /* ---- normal-mode analysis of MD: the trajectory projected on harmonic eigenvectors (csrc/m3g_nma.hip) -------------------------------
  * Normal-mode decomposition (Ladd, Moran and Hoover, Phys. Rev. B 34, 5058 (1986); McGaughey and Kaviany, Phys. Rev. B 69, 094303
  * (2004); the spectral energy density of Thomas et al., Phys. Rev. B 81, 081411 (2010)), fed one frame per m3g_nma_sample, as the
@@ -1435,7 +1499,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     additive, same version: m3g_rnemd_state_bytes / _init / _exchange / _read (reverse non-equilibrium MD
                              *     over an m3g_dyn_* batch: imposed heat or momentum flux, slab profiles);
                              *     additive, same version: m3g_meta_state_bytes / _state_view / _init / _bias / _set_hills / _read
-                             *     (collective-variable biasing over any MD family: metadynamics, restraints, walls) */
+                             *     (collective-variable biasing over any MD family: metadynamics, restraints, walls);
+                             *     additive, same version: m3g_sq_state_bytes / _init / _sample / _read / _frame (scattering observables:
+                             *     S(q), F(q,t) and the longitudinal and transverse current correlations) */
 
 #ifdef __cplusplus
 }

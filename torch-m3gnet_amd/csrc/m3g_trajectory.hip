@@ -19,12 +19,12 @@
 
 #include "m3g_chunks.h"
 #include "m3g_internal.h"
+#include "m3g_sampled_row.h"
 
 namespace m3g {
 namespace {
 constexpr int kTile = kChunkRows;              // atoms per RDF tile == threads per workgroup
 constexpr int kLagBlock = 8;                   // lags per workgroup of k_traj_partials (2 kLagBlock columns of 256 doubles in LDS: 32 KB)
-constexpr int kComPart = 7;                    // per chunk: sum m, sum m r [3], sum m v [3]
 constexpr int kMaxSpecies = 8, kMaxBins = 4096, kMaxLags = 4096;
 constexpr size_t kHistLds = 48 * 1024;         // the histogram of one structure is privatised in LDS up to this size
 enum { kDone = 0, kBegun = 1, kPairs = 2, kCounters = 4 };   // int64 words: frames stored, frames begun, tile pairs in the table
@@ -159,37 +159,10 @@ __global__ void __launch_bounds__(kTile) k_traj_rdf(TrajView st, double r_max, c
   }
 }
 
-// position and full-step velocity of row i: v + kick kappa F / m, the finish kick of k_dyn_apply (m3g_dynamics.hip)
-__device__ inline void sampled_row(const TrajView& st, int64_t i, const double* __restrict__ pos, const double* __restrict__ vel,
-                                   const float* __restrict__ forces, double kick, double (&r)[3], double (&v)[3]) {
-  const double m = st.mass[i];
-  for (int k = 0; k < 3; ++k) {
-    r[k] = pos[3 * i + k];
-    v[k] = vel[3 * i + k];
-    if (forces) v[k] += kick * (kKappa * (double)forces[3 * i + k] / m);
-  }
-}
-
+// (sampled_row and the body of k_traj_com: m3g_sampled_row.h, shared with m3g_scattering.hip)
 __global__ void __launch_bounds__(kChunkRows) k_traj_com(TrajView st, const double* __restrict__ pos, const double* __restrict__ vel,
                                                           const float* __restrict__ forces, double kick) {
-  __shared__ double sh[kComPart][kChunkRows];
-  const int c = blockIdx.x, t = threadIdx.x;
-  if (c >= st.ch.n_chunks()) return;
-  const int s = st.ch.structure(c);
-  const int64_t i = st.ch.row(c, t);
-  double val[kComPart] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (st.ch.holds(s, i)) {
-    double r[3], v[3];
-    sampled_row(st, i, pos, vel, forces, kick, r, v);
-    const double m = st.mass[i];
-    val[0] = m;
-    for (int k = 0; k < 3; ++k) {
-      val[1 + k] = m * r[k];
-      val[4 + k] = m * v[k];
-    }
-  }
-  chunk_tree_reduce<kComPart>(sh, val, t);
-  if (t < kComPart) st.com[kComPart * c + t] = sh[t][0];
+  com_chunk_partials(st.ch, st.mass, st.com, pos, vel, forces, kick);
 }
 
 __global__ void __launch_bounds__(kChunkRows) k_traj_store(TrajView st, int32_t remove_com, const double* __restrict__ pos,
@@ -204,7 +177,7 @@ __global__ void __launch_bounds__(kChunkRows) k_traj_store(TrajView st, int32_t 
   const int64_t i = st.ch.row(c, t);
   if (!st.ch.holds(s, i)) return;
   double r[3], v[3];
-  sampled_row(st, i, pos, vel, forces, kick, r, v);
+  sampled_row(st.mass, i, pos, vel, forces, kick, r, v);
   if (remove_com)
     for (int k = 0; k < 3; ++k) {
       r[k] -= acc[1 + k] / acc[0];

@@ -141,6 +141,17 @@ class M3GTrajParams(C.Structure):   # m3g_traj_params
 TRAJ_RDF_RANGE, TRAJ_MAX_SPECIES, TRAJ_MAX_BINS, TRAJ_MAX_LAGS = 1, 8, 4096, 4096   # M3G_TRAJ_RDF_RANGE and the limits of m3g_traj_sizes
 
 
+class M3GSqSizes(C.Structure):   # m3g_sq_sizes
+    _fields_ = [("n_atoms", C.c_int64), ("n_structs", C.c_int64), ("n_q", C.c_int64), ("max_species", C.c_int32), ("n_lags", C.c_int32)]
+
+
+class M3GSqParams(C.Structure):   # m3g_sq_params
+    _fields_ = [("remove_com", C.c_int32), ("reserved", C.c_int32)]
+
+
+SQ_MAX_INDEX, SQ_MAX_Q, SQ_MAX_SPECIES, SQ_MAX_LAGS, SQ_CELL = 128, 4096, 4, 4096, 1   # M3G_SQ_MAX_*, M3G_SQ_CELL
+
+
 class M3GNmaSizes(C.Structure):   # m3g_nma_sizes
     _fields_ = [("n_atoms", C.c_int64), ("n_structs", C.c_int64), ("n_unit_atoms", C.c_int64), ("n_qpoints", C.c_int64),
                 ("n_modes", C.c_int64), ("n_eig", C.c_int64), ("n_phase", C.c_int64), ("max_n", C.c_int32), ("n_lags", C.c_int32)]
@@ -340,6 +351,14 @@ SYMBOLS = {
     "m3g_traj_read": (C.c_int, [C.POINTER(M3GTrajSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_traj_frame": (C.c_int, [C.POINTER(M3GTrajSizes), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_sq_state_bytes": (C.c_int, [C.POINTER(M3GSqSizes), C.POINTER(C.c_size_t)]),
+    "m3g_sq_init": (C.c_int, [C.POINTER(M3GSqSizes), C.POINTER(M3GSqParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "m3g_sq_sample": (C.c_int, [C.POINTER(M3GSqSizes), C.POINTER(M3GSqParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_double, C.c_void_p]),
+    "m3g_sq_read": (C.c_int, [C.POINTER(M3GSqSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p]),
+    "m3g_sq_frame": (C.c_int, [C.POINTER(M3GSqSizes), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_nma_state_bytes": (C.c_int, [C.POINTER(M3GNmaSizes), C.POINTER(C.c_size_t)]),
     "m3g_nma_init": (C.c_int, [C.POINTER(M3GNmaSizes), C.POINTER(M3GNmaParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -27,6 +27,7 @@ from ._driver import (EV_A3_TO_GPA, Driver, IntegratorState, MdBatch, MdLog, int
                       positive, state_tensor, structure_arrays, structure_masses, structure_seeds)
 from .data import MaterialGraphKey as K
 from .nn.modules import Gradient
+from .scattering import ScatteringObservables, sq_sample
 from .trajectory import TrajectoryObservables, traj_sample
 
 KAPPA = 9.648533215665e-3    # A/fs^2 per eV/(A amu)
@@ -206,6 +207,20 @@ def chain_count(name: str, x) -> int:
     return int(x)
 
 
+def _split_observables(observables):
+    """(TrajectoryObservables or None, ScatteringObservables or None) of the `observables` argument of `MolecularDynamics.run`: one
+    object, or a list / tuple holding at most one of each kind."""
+    found = {TrajectoryObservables: None, ScatteringObservables: None}
+    items = observables if isinstance(observables, (list, tuple)) else () if observables is None else (observables,)
+    for item in items:
+        kind = next((k for k in found if isinstance(item, k)), None)
+        if kind is None or found[kind] is not None:
+            raise TypeError("observables must be a TrajectoryObservables, a ScatteringObservables, or a list holding at most one of each; "
+                            f"got {'a second ' if kind else ''}{type(item).__name__}")
+        found[kind] = item
+    return found[TrajectoryObservables], found[ScatteringObservables]
+
+
 class MolecularDynamics(Driver):
     """Batched counterpart of m3gnet's `MolecularDynamics`.
 
@@ -273,23 +288,24 @@ class MolecularDynamics(Driver):
                     pressure=self.pressure / EV_PER_A3_IN_GPA, taup=self.taup, compressibility=beta, fix_com=self.fix_com)
 
     def run(self, lattices: Sequence, positions: Sequence, atomic_numbers: Sequence, steps: int, velocities: Sequence | None = None,
-            masses: Sequence | None = None, loginterval: int = 10, observables: TrajectoryObservables | None = None) -> list:
+            masses: Sequence | None = None, loginterval: int = 10, observables=None) -> list:
         """Integrate every structure (lattices: [3,3] rows = lattice vectors, positions: [n_s,3] Cartesian, atomic_numbers: [n_s])
         for `steps` steps.  velocities: [n_s,3] A/fs per structure (default: Maxwell-Boltzmann at the temperature, zero momentum);
         masses: [n_s] amu per structure (default: standard atomic weights).  Returns one dict per structure: positions (unwrapped),
         velocities, lattice, total_energy, forces, stresses (pair virial) at the final step, n_steps, error (its forces became
         non-finite: it was stopped where it stood), and `log`: arrays step, e_pot, ke (eV), t (K), p (GPa), v (A^3) (and `conserved`,
-        eV, with "nvt_nose_hoover", "npt_mtk" and "npt_mtk_cell"; the last also pressure_tensor and lattice) every `loginterval` steps and at the last one.  observables: a `TrajectoryObservables`; the trajectory is then sampled on the
+        eV, with "nvt_nose_hoover", "npt_mtk" and "npt_mtk_cell"; the last also pressure_tensor and lattice) every `loginterval` steps and at the last one.  observables: a `TrajectoryObservables`, a `ScatteringObservables`, or a list / tuple
+        holding at most one of each; the trajectory is then sampled on the
         device before the integrator call of every `sample_interval`-th step (positions, forces and velocities are synchronous only
-        there: the sampler completes the half-step velocities with the finish kick itself) and every dict gains "observables".
+        there: the sampler completes the half-step velocities with the finish kick itself) and every dict gains "observables"
+        (trajectory) and / or "scattering".
         With "nvt_nose_hoover" the sampler's own v + dt/2 a is the state between the closing kick and the closing thermostat
         half-step: a point on the trajectory of the cyclically permuted splitting, as good a sample of the same dynamics.  With
         "npt_mtk" and "npt_mtk_cell" the closing kick is not the plain one (it carries the barostat's friction), so `observables`
         raises ValueError.  "npt_mtk_cell" with `cell_mask` "orthorhombic" needs every lattice diagonal to 1e-9 of its largest entry.
         As in the other NPT ensembles the cells go to the host and the candidates are searched again at every step."""
-        if observables is not None and not isinstance(observables, TrajectoryObservables):
-            raise TypeError(f"observables must be a TrajectoryObservables; got {type(observables).__name__}")
-        if observables is not None and self.ensemble in ("npt_mtk", "npt_mtk_cell"):
+        observables, scattering = _split_observables(observables)
+        if (observables is not None or scattering is not None) and self.ensemble in ("npt_mtk", "npt_mtk_cell"):
             raise ValueError(f"observables are not supported with {self.ensemble}: its finish kick is not the sampler's v + dt/2 a")
         steps, loginterval = integer("steps", steps, 0), integer("loginterval", loginterval, 1)
         lat, pos, z = structure_arrays(lattices, positions, atomic_numbers)
@@ -322,11 +338,14 @@ class MolecularDynamics(Driver):
         dyn = (MtkCellState if cell else NhcState if nhc else DynState)(pos_t, lat64, batch.offsets, np.concatenate(m), vel_t, temps, *keys,
                                                                         **self._params())
         traj = observables.begin(lat, z, m, vg.device) if observables is not None else None
+        sq = scattering.begin(lat, z, m, vg.device) if scattering is not None else None
         log, cells = MdLog(conserved=nhc, cell=cell), []
 
         def before(k, out, logged):
             if traj is not None and k % observables.sample_interval == 0:
                 traj_sample(traj, pos_t, lat64, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
+            if sq is not None and k % scattering.sample_interval == 0:
+                sq_sample(sq, pos_t, lat64, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
             if cell and logged:
                 cells.append(lat64.clone())   # (the cell of the observables: the integrator call moves it on)
 
@@ -340,4 +359,7 @@ class MolecularDynamics(Driver):
         if traj is not None:
             for r, obs in zip(res, observables.results(traj, self.timestep)):
                 r["observables"] = obs
+        if sq is not None:
+            for r, obs in zip(res, scattering.results(sq, self.timestep)):
+                r["scattering"] = obs
         return res

@@ -148,6 +148,19 @@ def rdf_from_counts(hist, counts, n_samples: int, volume_sum: float, r_max: floa
     return {"r": 0.5 * (edges[1:] + edges[:-1]), "r_edges": edges, "g": g, "g_total": g_total, "coordination": cn}
 
 
+def hann_cosine_transform(c, dt: float):
+    """(f_k, 2 int_0^T c(t) w(t) cos(2 pi f_k t) dt) of a function sampled every `dt` along the last axis of `c` [..., G]: w = (1 + cos(pi
+    t / T)) / 2 (Hann), T the longest lag, f_k = k / (2 G dt) in 1/fs, the integral by the trapezoid rule.  The transform behind the
+    VDOS here and the spectra of `scattering.py`."""
+    c = np.asarray(c, dtype=np.float64)
+    G = c.shape[-1]
+    time = np.arange(G) * dt
+    freq = np.arange(G) / (2.0 * G * dt)
+    window = 0.5 * (1.0 + np.cos(np.pi * time / time[-1])) if G > 1 else np.ones(1)
+    kernel = np.cos(2.0 * np.pi * freq[:, None] * time[None, :])
+    return freq, 2.0 * _trapezoid(kernel * (c * window)[..., None, :], time)
+
+
 def correlations_from_sums(msd_sum, vacf_sum, lag_count, counts, dt: float, fit_window=(0.2, 0.8)) -> dict:
     """MSD, VACF, diffusion coefficients and VDOS of one structure from its accumulated sums [n_sp, n_lags] (module docstring); `dt`:
     the time between two samples (fs)."""
@@ -166,15 +179,13 @@ def correlations_from_sums(msd_sum, vacf_sum, lag_count, counts, dt: float, fit_
     freq = np.arange(G) / (2.0 * G * dt)   # 1/fs
     vdos = np.full((n_sp, G), np.nan)
     have = lag_count > 0
-    window = 0.5 * (1.0 + np.cos(np.pi * time / time[-1])) if G > 1 else np.ones(1)
-    kernel = np.cos(2.0 * np.pi * freq[:, None] * time[None, :])
     for a in range(n_sp):
         if fit.sum() >= 2:
             d_msd[a] = np.polyfit(time[fit], msd[a][fit], 1)[0] / 6.0
         if have.all() and G > 1:
             d_vacf[a] = _trapezoid(vacf[a], time) / 3.0
             with np.errstate(divide="ignore", invalid="ignore"):
-                vdos[a] = 2.0 * _trapezoid(kernel * (vacf[a] / vacf[a][0] * window)[None, :], time)
+                vdos[a] = hann_cosine_transform(vacf[a] / vacf[a][0], dt)[1]
     return {"time": time, "msd": msd, "vacf": vacf, "lag_count": lag_count.copy(), "diffusion_msd": d_msd, "diffusion_vacf": d_vacf,
             "diffusion_msd_cm2_s": d_msd * A2_FS_TO_CM2_S, "diffusion_vacf_cm2_s": d_vacf * A2_FS_TO_CM2_S,
             "vdos_frequency": freq * 1e3, "vdos": vdos}
