@@ -246,7 +246,8 @@ int m3g_distance_angle(double length_scale, int64_t n_atoms, int64_t n_edges, in
                        const float* pos, const float* lattice, const int32_t* edge_cell_shift, const void* topo,
                        const int64_t* triplet_edge_index, float* scratch_unit_vectors /* [E,3] */,
                        float* edge_distances, float* triplet_angles, void* stream);
-/* EdgeFeaturizer.forward (nn/featurizer.py:81-100); host_em/dm/coeff are HOST arrays [n_max] */
+/* EdgeFeaturizer.forward (nn/featurizer.py:81-100); host_em/dm/coeff are HOST arrays [n_max]; n_max in 1..10, the degrees
+ * m3g_plan_commit accepts (1..4 on the kernel of the MFMA path, 5..10 on the any-size path's radial basis: the same terms) */
 int m3g_edge_featurizer(int32_t n_max, double scaled_cutoff, const float* host_em, const float* host_dm,
                         const float* host_coeff, int64_t n_edges, const float* edge_distances, float* edge_weights,
                         void* stream);
@@ -268,7 +269,9 @@ int m3g_multiply(int64_t n, const float* a, const float* b, float* y, void* stre
 int m3g_bessel_basis(int32_t l_max, int32_t n_max, double cutoff, const float* host_zeros, const float* host_factors, int64_t n,
                      const float* rs, float* out, void* stream);
 /* ThreeBodyInteration.forward (nn/interaction.py:187-223): edge_attr [E,D] updated in place from the graph's edge_distances,
- * triplet_angles and node features; scratch (N*C + E*C + 2*E*D) floats, C = l_max*n_max; mid (or NULL) receives the aggregate [E,C] */
+ * triplet_angles and node features; scratch EXACTLY (N*C + E*C + 2*E*D) floats, C = l_max*n_max, never NULL (one float serves when
+ * that is 0); mid (or NULL) receives the aggregate [E,C].  The indices are NOT range-checked on the device: the caller passes
+ * edge_index < N and triplet_edge_index < E (torch_m3gnet.nn checks them on the host before the call) */
 int m3g_three_body(int32_t l_max, int32_t n_max, int32_t embedding_dim, double scaled_cutoff, double scaled_threebody_cutoff,
                    const float* host_zeros, const float* host_factors, int64_t n_atoms, int64_t n_edges, int64_t n_triplets,
                    const int64_t* edge_index, const int64_t* triplet_edge_index, const float* edge_distances, const float* triplet_angles,
@@ -276,13 +279,16 @@ int m3g_three_body(int32_t l_max, int32_t n_max, int32_t embedding_dim, double s
                    float* edge_attr, float* mid, void* stream);
 /* M3GNetConv.forward (nn/conv.py:63-97): x [N,D] and edge_attr [E,D] updated in place.  host_params: HOST array of 18 DEVICE pointers,
  * edge MLP {dense.0.weight, gate.0.weight, dense.0.bias, gate.0.bias, dense.2.weight, gate.2.weight, dense.2.bias, gate.2.bias,
- * edge_linear.weight}, then the node MLP likewise (node_linear.weight last) */
+ * edge_linear.weight}, then the node MLP likewise (node_linear.weight last).  scratch: m3g_conv_block_scratch_bytes, i.e.
+ * (11*E*D + 1024) floats: eleven [E,D] activation arrays, and 1024 floats so that the buffer is never empty */
 int m3g_conv_block_scratch_bytes(int32_t embedding_dim, int64_t n_edges, size_t* bytes);
 int m3g_conv_block(int32_t embedding_dim, int32_t n_max, int64_t n_atoms, int64_t n_edges, int64_t n_triplets, int64_t n_structs,
                    const void* topo, const float* const* host_params, const float* edge_weights, float* x, float* edge_attr, float* scratch,
                    size_t scratch_bytes, void* stream);
 /* AtomWiseReadout.forward (nn/readout.py:39-58).  host_params: HOST array of 12 DEVICE pointers {dense.0.weight, dense.0.bias,
- * dense.2.weight, dense.2.bias, dense.4.weight, dense.4.bias, gate.0.weight, ...}; scratch (6*N*D + 2*N) floats */
+ * dense.2.weight, dense.2.bias, dense.4.weight, dense.4.bias, gate.0.weight, ...}; scratch EXACTLY (4*N*D + 2*N) floats (two hidden
+ * layers of two branches, in place of their pre-activations, and the two outputs; may be NULL when N = 0).  batch is NOT
+ * range-checked on the device: the caller passes batch < n_structs (torch_m3gnet.nn checks it on the host before the call) */
 int m3g_readout(int32_t embedding_dim, int64_t n_atoms, int64_t n_structs, const float* const* host_params, double energy_scale,
                 const float* x, const float* elemental_energies_per_atom, const int64_t* batch, float* scaled_atomic_energies,
                 float* scaled_total_energy, float* total_energy, float* scratch, void* stream);

@@ -810,7 +810,8 @@ extern "C" int m3g_distance_angle(double length_scale, int64_t N, int64_t E, int
                                   const float* lattice, const int32_t* shift, const void* topo,
                                   const int64_t* triplet_edge_index, float* scratch_u, float* edge_distances,
                                   float* triplet_angles, void* stream_) {
-  if (!topo || !edge_distances || (E > 0 && !scratch_u)) { set_error("m3g_distance_angle: null argument"); return M3G_ERR_VALUE; }
+  // (a graph without edges has empty outputs: their pointers may be null)
+  if (!topo || (E > 0 && (!edge_distances || !scratch_u))) { set_error("m3g_distance_angle: null argument"); return M3G_ERR_VALUE; }
   hipStream_t s = (hipStream_t)stream_;
   Topo t = topo_carve(N, E, T, S, const_cast<void*>(topo));
   launch_distance_only((float)length_scale, t, pos, lattice, shift, scratch_u, edge_distances, s);
@@ -825,8 +826,13 @@ extern "C" int m3g_distance_angle(double length_scale, int64_t N, int64_t E, int
 extern "C" int m3g_edge_featurizer(int32_t n_max, double scaled_cutoff, const float* host_em, const float* host_dm,
                                    const float* host_coeff, int64_t E, const float* edge_distances, float* edge_weights,
                                    void* stream_) {
-  if (n_max < 1 || n_max > kRCap) { set_error("m3g_edge_featurizer: n_max must be in 1..%d", kRCap); return M3G_ERR_UNSUPPORTED; }
+  if (n_max < 1 || n_max > kRAnyCap) { set_error("m3g_edge_featurizer: n_max must be in 1..%d", kRAnyCap); return M3G_ERR_UNSUPPORTED; }
   if (!host_em || !host_dm || !host_coeff || (E > 0 && (!edge_distances || !edge_weights))) { set_error("null argument"); return M3G_ERR_VALUE; }
+  if (n_max > kRCap) {   // beyond the MFMA path's tables: the any-size path's radial basis, the same terms
+    generic_edge_featurizer(n_max, scaled_cutoff, host_coeff, host_em, host_dm, E, edge_distances, edge_weights, (hipStream_t)stream_);
+    M3G_HIP_CHECK(hipGetLastError());
+    return M3G_OK;
+  }
   Consts c{};
   c.R = n_max;
   fill_radial_consts(c, n_max, scaled_cutoff, host_coeff, host_em, host_dm);

@@ -18,7 +18,7 @@ namespace m3g {
 
 namespace {
 
-constexpr int kGL = 9, kGR = 10, kGC = kGL * kGR;   // the reference's table: l_max + 1 <= 10 rows, n_max <= 10 columns
+constexpr int kGL = 9, kGR = kRAnyCap, kGC = kGL * kGR;   // the reference's table: l_max + 1 <= 10 rows, n_max <= 10 columns
 
 struct GenConsts {
   int L, R, C, D, B, num_types;
@@ -710,14 +710,36 @@ __global__ void __launch_bounds__(256) g_mul(int64_t n, const float* __restrict_
   GEN_IDX(n);
   y[gid] = a[gid] * b[gid];
 }
+// j_l(x) for the stand-alone modules: the upward recurrence of sph_bessel (m3g_basis.h) on the same fp32 argument, carried in fp64
+// and rounded once.  In fp32 the recurrence multiplies the rounding of sin x and cos x by (2l - 1)!! / x^l -- 8,000 at l = 8, x = 2 --
+// so its result moves by a factor of several with the last bit of the libm's sin and cos: ThreeBodyInteration at l_max = 9 was
+// 1.2e-5 of max |edge_attr| from fp64 where float32 on a CPU is 2e-6 .. 1.4e-5 depending on that bit (profiles/standalone_modules.txt).
+// The engine step keeps the fp32 form (m3g_basis.h: its order of operations is the reference's, and it runs per edge per step); a
+// module called on its own is not on that path and need not carry the noise.
+__device__ __forceinline__ float sph_bessel_wide(int l, float xf) {
+  if (!(xf > 1e-8f)) {   // the reference's small-argument branch, as sph_bessel has it
+    float dfact = 1.f;
+    for (int k = 1; k <= l; ++k) dfact *= (float)(2 * k + 1);
+    return l == 0 ? 1.f : xf / dfact;
+  }
+  const double x = (double)xf;
+  double sn, cx;
+  sincos(x, &sn, &cx);
+  double prev = sn / x, cur = (prev - cx) / x;
+  if (l == 0) return (float)prev;
+  for (int n = 1; n < l; ++n) {
+    const double next = (double)(2 * n + 1) / x * cur - prev;
+    prev = cur;
+    cur = next;
+  }
+  return (float)cur;
+}
 // chi[l, n, t] = j_l(z_ln r_t / rc) / factors[l, n]   (NormalizedSphericalBessel.forward, nn/interaction.py:268-281)
 __global__ void __launch_bounds__(256) g_bessel_basis(GenConsts c, int64_t n, const float* __restrict__ rs, float* __restrict__ out) {
   GEN_IDX(n * c.C);
   const int64_t t = gid % n;
   const int cc = (int)(gid / n), l = cc / c.R, k = cc % c.R;
-  float jl[kGL], djl[kGL];
-  sph_bessel<kGL, false>(c.L, c.zeros[l][k] * rs[t] / c.rc, jl, djl);
-  out[gid] = jl[l] / c.factors[l][k];
+  out[gid] = sph_bessel_wide(l, c.zeros[l][k] * rs[t] / c.rc) / c.factors[l][k];
 }
 // per triplet and order l: m[e1, l*R+n] += chi_ln(d_ik) Y_l(cos) fc(d_ij) fc(d_ik) v[k, l*R+n]   (nn/interaction.py:188-217; the
 // module takes cos(theta) and the distances from the graph, so the sum runs over the caller's triplet list: float atomics)
@@ -734,11 +756,8 @@ __global__ void __launch_bounds__(256) g_threebody_standalone(GenConsts c, int64
   legendre<false>(c.L, angles[t], P, dP);
   const float y = c.ynorm[l] * P[l] * f;
   const int64_t k = ei[E + e2];
-  for (int n = 0; n < c.R; ++n) {
-    float jl[kGL], djl[kGL];
-    sph_bessel<kGL, false>(c.L, c.zeros[l][n] * d2 / c.rc, jl, djl);
-    atomicAdd(&m[e1 * c.C + l * c.R + n], jl[l] / c.factors[l][n] * y * v[k * c.C + l * c.R + n]);
-  }
+  for (int n = 0; n < c.R; ++n)
+    atomicAdd(&m[e1 * c.C + l * c.R + n], sph_bessel_wide(l, c.zeros[l][n] * d2 / c.rc) / c.factors[l][n] * y * v[k * c.C + l * c.R + n]);
 }
 __global__ void __launch_bounds__(256) g_atomic_energy_standalone(int64_t N, float energy_scale, const float* __restrict__ elemental_per_atom,
                                                                   const float* __restrict__ od, const float* __restrict__ og,
@@ -753,6 +772,15 @@ __global__ void __launch_bounds__(256) g_scale(int64_t n, float a, const float* 
   GEN_IDX(n);
   y[gid] = a * x[gid];
 }
+// h[e, m] = h_m(d_e), m < R <= kGR   (EdgeFeaturizer.forward, nn/featurizer.py:81-100: the radial loop of g_geometry on its own)
+__global__ void __launch_bounds__(256) g_radial_basis(GenConsts c, int64_t E, const float* __restrict__ d, float* __restrict__ h) {
+  GEN_IDX(E);
+  float hm = 0.f, hpm = 0.f;
+  for (int m = 0; m < c.R; ++m) {
+    radial_term(c, m, d[gid], hm, hpm);
+    h[gid * c.R + m] = hm;
+  }
+}
 static GenConsts basis_consts(int l_max, int n_max, double rc, double rc3, const float* zeros, const float* factors) {
   GenConsts c{};
   c.L = l_max; c.R = n_max; c.C = l_max * n_max;
@@ -760,6 +788,15 @@ static GenConsts basis_consts(int l_max, int n_max, double rc, double rc3, const
   return c;
 }
 }  // namespace
+
+// the radial basis for the degrees the MFMA path's Consts do not hold (kRCap < n_max <= kRAnyCap, checked by m3g_edge_featurizer)
+void generic_edge_featurizer(int n_max, double rc, const float* coeff, const float* em, const float* dm, int64_t E, const float* d, float* out,
+                             hipStream_t s) {
+  GenConsts c{};
+  c.R = n_max;
+  fill_radial_consts(c, n_max, rc, coeff, em, dm);
+  launch(g_radial_basis, E, s, c, E, d, out);
+}
 }  // namespace m3g
 
 using namespace m3g;
@@ -858,7 +895,7 @@ extern "C" int m3g_conv_block(int32_t D, int32_t R, int64_t N, int64_t E, int64_
   return M3G_OK;
 }
 // AtomWiseReadout.forward (nn/readout.py:39-58).  host_params: 12 DEVICE pointers {dense.0.w, dense.0.b, dense.2.w, dense.2.b,
-// dense.4.w, dense.4.b, gate.0.w, ...}; elemental_per_atom = graph["elemental_energies"] [N].  scratch: (6*N*D + 2*N) floats.
+// dense.4.w, dense.4.b, gate.0.w, ...}; elemental_per_atom = graph["elemental_energies"] [N].  scratch: (4*N*D + 2*N) floats.
 extern "C" int m3g_readout(int32_t D, int64_t N, int64_t S, const float* const* host_params, double energy_scale, const float* x,
                            const float* elemental_per_atom, const int64_t* batch, float* scaled_atomic, float* scaled_total, float* total,
                            float* scratch, void* stream_) {

@@ -17,6 +17,7 @@ namespace m3g {
 constexpr int kDP = 64;      // padded feature width (embedding_dim <= kDP; zero padding is exact)
 constexpr int kLCap = 4;     // l_max <= kLCap
 constexpr int kRCap = 4;     // n_max <= kRCap
+constexpr int kRAnyCap = 10; // n_max of the any-size path (m3g_generic.hip): the columns of the reference's Bessel-root table
 constexpr int kCP = 16;      // padded l_max*n_max
 constexpr int kRP = 4;       // padded n_max
 
@@ -431,6 +432,8 @@ size_t generic_workspace_bytes(const m3g_plan* plan, int64_t N, int64_t E, int64
 int generic_commit(m3g_plan* plan);
 void generic_free(m3g_plan* plan);
 int generic_energy_forces(const m3g_plan* plan, const m3g_io* io, void* workspace, size_t workspace_bytes, hipStream_t s);
+void generic_edge_featurizer(int n_max, double rc, const float* coeff, const float* em, const float* dm, int64_t E, const float* d, float* out,
+                             hipStream_t s);   // kRCap < n_max <= kRAnyCap
 void launch_triplet_angles(const Topo& t, const int64_t* tei, const float* u, float* out, hipStream_t s);
 void launch_distance_only(float length_scale, const Topo& t, const float* pos, const float* lattice,
                           const int32_t* shift, float* u, float* d, hipStream_t s);

@@ -212,6 +212,46 @@ class _Topology:
 
 
 # ----------------------------------------------------------------------------------------------
+_OUT_OF_RANGE = "graph index out of range (edge_index / triplet_edge_index / batch)"   # (the text `_Topology._raise_on` gives)
+
+
+def check_index_ranges(n_atoms: int, n_edges: int, n_structs: int, edge_index=None, triplet_edge_index=None, batch=None) -> None:
+    """Host-side range check of a graph's index tensors (CPU or GPU tensors; None: not checked), for the modules whose kernels index
+    with the caller's own lists instead of a `_Topology` (m3g_three_body, m3g_readout: no range check on the device).  edge_index
+    [2, n_edges] must lie in [0, n_atoms), triplet_edge_index [2, T] in [0, n_edges), batch [n_atoms] in [0, n_structs); otherwise
+    ValueError with the text of the fused path's refusal -- raised before any kernel of the library is enqueued."""
+    for t, bound, shape, name in ((edge_index, n_atoms, (2, n_edges), K.EDGE_INDEX), (triplet_edge_index, n_edges, (2, None), K.TRIPLET_EDGE_INDEX),
+                                  (batch, n_structs, (n_atoms,), K.BATCH)):
+        if t is None:
+            continue
+        if t.dim() != len(shape) or any(want is not None and int(have) != int(want) for have, want in zip(t.shape, shape)):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} does not match the graph's sizes (expected {shape})")
+        if t.dtype.is_floating_point or t.dtype == torch.bool or t.is_complex():
+            raise ValueError(f"{name}: an integer tensor is required")
+        if t.numel() == 0:
+            continue
+        lo, hi = torch.aminmax(t)
+        if int(lo) < 0 or int(hi) >= bound:
+            raise ValueError(_OUT_OF_RANGE)
+
+
+def _indices_already_checked(graph, n_atoms: int, n_edges: int, n_structs: int) -> bool:
+    """True where the graph carries a `_Topology` built from its present index tensors (its build has range-checked all three)."""
+    cached = graph.get("_m3g_topology") if isinstance(graph, dict) else None
+    if cached is None or any(key not in graph for key in (K.EDGE_INDEX, K.TRIPLET_EDGE_INDEX, K.BATCH, K.LATTICE)):
+        return False
+    if cached[0] != _Topology.signature(graph):
+        return False
+    topo = cached[1].finish()
+    return (topo.N, topo.E, topo.S) == (n_atoms, n_edges, n_structs)
+
+
+def _require_rows(t: torch.Tensor, shape, name: str) -> None:
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+# ----------------------------------------------------------------------------------------------
 class ScaleLength(torch.nn.Module):
     """pos, lattice -> scaled_pos, scaled_lattice (reference nn/scale.py:8-29).  In the fused path the
     division happens inside the geometry kernel; standalone it is a device-side elementwise op."""
@@ -466,9 +506,21 @@ class ThreeBodyInteration(torch.nn.Module):
         _require_cuda(x, K.NODE_FEATURES)
         dev = x.device
         x, e_new = _f32(x), _f32(e).clone()
-        ei, tei = graph[K.EDGE_INDEX].contiguous().long(), graph[K.TRIPLET_EDGE_INDEX].contiguous().long()
+        ei, tei = graph[K.EDGE_INDEX], graph[K.TRIPLET_EDGE_INDEX]
         d, ang = _f32(graph[K.EDGE_DISTANCES]), _f32(graph[K.TRIPLET_ANGLES])
+        if x.dim() != 2 or ei.dim() != 2 or tei.dim() != 2:
+            raise ValueError("ThreeBodyInteration.forward: x [N,D], edge_index [2,E] and triplet_edge_index [2,T] are required")
         N, E, T, D, Cc = x.size(0), ei.size(1), tei.size(1), x.size(1), self.degree
+        if D != self.num_node_features or self.num_edge_features != D:
+            raise ValueError("ThreeBodyInteration.forward: m3g_three_body updates edge_attr of the node features' width "
+                             f"(num_node_features = num_edge_features = x.size(1)); got {self.num_node_features}, {self.num_edge_features}, {D}")
+        _require_rows(e_new, (E, D), K.EDGE_ATTR)
+        _require_rows(d, (E,), K.EDGE_DISTANCES)
+        _require_rows(ang, (T,), K.TRIPLET_ANGLES)
+        # the kernel indexes dist[e], edge_index[1][e], v[k] and its aggregate with these lists as they are: checked here, on the host
+        if not _indices_already_checked(graph, N, E, int(graph[K.LATTICE].size(0)) if K.LATTICE in graph else -1):
+            check_index_ranges(N, E, 0, edge_index=ei, triplet_edge_index=tei)
+        ei, tei = ei.contiguous().long(), tei.contiguous().long()
         z, f = self.nsb._host_tables()
         scratch = torch.empty(N * Cc + E * Cc + 2 * E * D + 16, dtype=torch.float, device=dev)
         mid = torch.empty(E, Cc, dtype=torch.float, device=dev)
@@ -538,9 +590,16 @@ class AtomWiseReadout(torch.nn.Module):
         dev = x.device
         x = _f32(x)
         N, D = x.shape
-        batch = graph[K.BATCH].contiguous().long()
+        batch = graph[K.BATCH]
         S = int(graph[K.LATTICE].size(0))
         elem = _f32(graph[K.ELEMENTAL_ENERGIES])
+        if D != self.in_features:
+            raise ValueError(f"AtomWiseReadout.forward: x has {D} features, the module {self.in_features}")
+        _require_rows(elem, (N,), K.ELEMENTAL_ENERGIES)
+        # the kernel adds into scaled_total[batch[a]] as it is: checked here, on the host
+        if not _indices_already_checked(graph, N, int(graph[K.EDGE_INDEX].size(1)) if K.EDGE_INDEX in graph else -1, S):
+            check_index_ranges(N, 0, S, batch=batch)
+        batch = batch.contiguous().long()
         tensors = []
         for seq in (self.gated.dense, self.gated.gate):
             for i in (0, 2, 4):
@@ -548,7 +607,7 @@ class AtomWiseReadout(torch.nn.Module):
         params, keep = _param_ptr_array([t.to(dev) for t in tensors])
         ea = torch.empty(N, dtype=torch.float, device=dev)
         st, tot = torch.empty(S, dtype=torch.float, device=dev), torch.empty(S, dtype=torch.float, device=dev)
-        scratch = torch.empty(6 * N * D + 2 * N + 16, dtype=torch.float, device=dev)
+        scratch = torch.empty(4 * N * D + 2 * N + 16, dtype=torch.float, device=dev)   # (+16: never an empty buffer)
         with _cuda.on_device(dev):
             _lib.check(_lib.load_library().m3g_readout(D, N, S, params, float(self.scale), _ptr(x), _ptr(elem), _ptr(batch), _ptr(ea), _ptr(st),
                                                        _ptr(tot), _ptr(scratch), _stream()))
