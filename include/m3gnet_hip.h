@@ -1165,6 +1165,81 @@ int m3g_sq_read(const m3g_sq_sizes* sizes, const void* state, size_t state_bytes
 int m3g_sq_frame(const m3g_sq_sizes* sizes, const void* state, size_t state_bytes, int32_t lag, double* host_rho, double* host_jl,
                  double* host_jt, void* stream);
 
+/* ---- local-order observables: Steinhardt q_l, their neighbour average, solid-like atoms and clusters (csrc/m3g_local_order.hip) -------
+ * The per-atom companion of the two families above, fed one frame per m3g_lo_sample; positions and cells only, no velocities.
+ * Neighbours: for structure s with cut-off r_cut[s] (A), atom j != i is a neighbour of i when the minimum-image distance r_ij <
+ *   r_cut[s] (strict); all species count.  Minimum image as in the RDF of m3g_traj_*: the fractional difference minus its rint, in
+ *   fp64, valid only while r_cut <= half the smallest perpendicular width of the CURRENT cell -- checked per sample on the device with
+ *   the allowance 1 + 1e-12 of M3G_TRAJ_RDF_RANGE.  N_b(i) is the neighbour count; the list of an atom holds its first
+ *   M3G_LO_MAX_NEIGHBORS neighbours in ascending structure-local index j, the count is kept uncapped.
+ * Spherical harmonics Y_lm(rhat) with the Condon-Shortley phase, orthonormal on the sphere; only m = 0 .. l is stored, since
+ *   Y_l,-m = (-1)^m Y_lm*.
+ * Per atom:  q_lm(i) = (1/N_b) sum_{j in nb(i)} Y_lm(rhat_ij)   (j ascending),
+ *            q_l(i)  = sqrt( 4 pi / (2l+1) ( |q_l0|^2 + 2 sum_{m>0} |q_lm|^2 ) );      N_b(i) = 0: q_lm = 0, q_l = 0.
+ * Neighbour average (Lechner and Dellago, J. Chem. Phys. 129, 114707 (2008)):
+ *            qbar_lm(i) = ( q_lm(i) + sum_{j in nb(i)} q_lm(j) ) / (N_b(i) + 1), j ascending; qbar_l from qbar_lm as q_l from q_lm.
+ * Global:    Q_lm = sum_i N_b(i) q_lm(i) / sum_i N_b(i) over the structure, Q_l as above; 0 when the structure has no bond.
+ * Solid-like bond (ten Wolde, Ruiz-Montero and Frenkel, J. Chem. Phys. 104, 9932 (1996)), L = solid_degree:
+ *            s_ij = Re sum_{m=-L..L} q_Lm(i) q_Lm*(j) / ( |q_L(i)| |q_L(j)| ),  |q_L(i)|^2 = sum_m |q_Lm(i)|^2,  -1 <= s_ij <= 1;
+ *            the bond is connected when s_ij > solid_threshold (a zero norm: not connected); n_conn(i) counts the connected bonds of
+ *            i, and atom i is solid-like when n_conn(i) >= solid_bonds.
+ * Clusters:  two solid-like atoms that are neighbours belong to the same cluster; its label is the smallest structure-local atom
+ *            index in it, non-solid atoms carry -1.  Per sample: n_solid, n_clusters, largest_cluster.
+ * Accumulated per structure over the samples: per species and degree integer histograms (hist_bins bins on [0, 1], the last bin closed)
+ * of q_l and qbar_l and the sums of q_l, q_l^2, qbar_l, qbar_l^2; per species a histogram of N_b (0 .. 32); and for the first
+ * series_cap samples a series row (n_solid, n_clusters, largest_cluster; Q_l and the mean of qbar_l over the atoms per degree).
+ * A sample of a structure that raises any M3G_LO_* flag takes no part in any histogram, sum or series row of that structure
+ * (n_skipped counts it, n_samples the others); the flags are sticky and the per-atom frame is still written as computed.  No float
+ * atomics, fixed-order sums: every number depends on the structure's own rows only, bitwise the same alone or in any batch. */
+typedef struct {
+  int64_t n_atoms;       /* N */
+  int64_t n_structs;     /* S */
+  int32_t max_species;   /* 1 .. 4 (M3G_LO_MAX_SPECIES): species indices are local, 0 .. max_species - 1 */
+  int32_t n_degrees;     /* 1 .. 3 (M3G_LO_MAX_DEGREES) */
+  int32_t hist_bins;     /* 1 .. 1024 (M3G_LO_MAX_BINS) */
+  int32_t series_cap;    /* 1 .. 65536 (M3G_LO_MAX_SERIES): later samples enter the histograms and sums, not the series */
+} m3g_lo_sizes;
+#define M3G_LO_MAX_DEGREE 12
+#define M3G_LO_MAX_DEGREES 3
+#define M3G_LO_MAX_NEIGHBORS 32
+#define M3G_LO_MAX_SPECIES 4
+#define M3G_LO_MAX_BINS 1024
+#define M3G_LO_MAX_SERIES 65536
+typedef struct {
+  int32_t degrees[M3G_LO_MAX_DEGREES];   /* the first n_degrees: distinct, each 1 .. 12 (M3G_LO_MAX_DEGREE); the others are ignored */
+  int32_t solid_degree;                  /* one of them */
+  int32_t solid_bonds;                   /* 1 .. 32 */
+  double solid_threshold;                /* -1 .. 1 */
+} m3g_lo_params;
+#define M3G_LO_CELL 1            /* a sample saw a cell that is singular (|det| < 1e-12) or not finite */
+#define M3G_LO_RANGE 2           /* r_cut beyond half the smallest perpendicular width of a sample's cell */
+#define M3G_LO_NEIGHBORS 4       /* an atom had more than M3G_LO_MAX_NEIGHBORS neighbours */
+#define M3G_LO_NONFINITE 8       /* a pair distance was not finite, or 0 */
+/* Sizes outside their limits -> M3G_ERR_VALUE.  The size follows from `sizes` alone: 936 + 224 n_degrees bytes per atom for the lists
+ * and the frame beside the accumulators. */
+int m3g_lo_state_bytes(const m3g_lo_sizes* sizes, size_t* bytes);
+/* HOST host_offsets [S+1] and host_species [N] as m3g_traj_init, host_r_cut [S] (A, finite and > 0).  Everything is checked on the
+ * host before any HIP call -> M3G_ERR_VALUE; a short state buffer -> M3G_ERR_SIZE.  Uploads the tables (the normalisation of Y_lm
+ * among them, computed here in fp64), zeroes the accumulators, waits for the stream. */
+int m3g_lo_init(const m3g_lo_sizes* sizes, const m3g_lo_params* params, const int64_t* host_offsets, const int32_t* host_species,
+                const double* host_r_cut, void* state, size_t state_bytes, void* stream);
+/* One sample: pos [N,3] (unwrapped or not), lattice [S,3,3] fp64, both DEVICE.  Six launches whatever S, N and the species; the
+ * counters live in the state buffer (the two counters of m3g_traj_sample): no allocation, copy or wait, capture-safe on one stream. */
+int m3g_lo_sample(const m3g_lo_sizes* sizes, const m3g_lo_params* params, void* state, size_t state_bytes, const double* pos,
+                  const double* lattice, void* stream);
+/* The accumulators to HOST memory; every output may be NULL: hist_q, hist_qbar [S, max_species, n_degrees, hist_bins] uint64;
+ * hist_nb [S, max_species, 33] uint64; moments [S, max_species, n_degrees, 4] fp64 (sums of q_l, q_l^2, qbar_l, qbar_l^2);
+ * series_counts [S, series_cap, 3] int64 (n_solid, n_clusters, largest_cluster); series_order [S, series_cap, 2, n_degrees] fp64 (Q_l,
+ * mean qbar_l); n_samples, n_skipped [S] int64; flags [S] int32 (M3G_LO_*).  Series rows from n_samples on are zero.  Waits. */
+int m3g_lo_read(const m3g_lo_sizes* sizes, const void* state, size_t state_bytes, uint64_t* host_hist_q, uint64_t* host_hist_qbar,
+                uint64_t* host_hist_nb, double* host_moments, int64_t* host_series_counts, double* host_series_order,
+                int64_t* host_n_samples, int64_t* host_n_skipped, int32_t* host_flags, void* stream);
+/* The per-atom arrays of the last sample to HOST memory (before any sample: M3G_ERR_VALUE); every output may be NULL: qlm
+ * [N, n_degrees, 13, 2] fp64 ((re, im) of m = 0 .. 12, zero beyond l), ql, qbar [N, n_degrees] fp64, n_neighbors (uncapped), n_conn,
+ * solid (0 / 1), label [N] int32.  Waits for the stream. */
+int m3g_lo_frame(const m3g_lo_sizes* sizes, const void* state, size_t state_bytes, double* host_qlm, double* host_ql, double* host_qbar,
+                 int32_t* host_n_neighbors, int32_t* host_n_conn, int32_t* host_solid, int32_t* host_label, void* stream);
+
 /* ---- normal-mode analysis of MD: the trajectory projected on harmonic eigenvectors (csrc/m3g_nma.hip) -------------------------------
  * Normal-mode decomposition (Ladd, Moran and Hoover, Phys. Rev. B 34, 5058 (1986); McGaughey and Kaviany, Phys. Rev. B 69, 094303
  * (2004); the spectral energy density of Thomas et al., Phys. Rev. B 81, 081411 (2010)), fed one frame per m3g_nma_sample, as the
@@ -1507,7 +1582,9 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     additive, same version: m3g_meta_state_bytes / _state_view / _init / _bias / _set_hills / _read
                              *     (collective-variable biasing over any MD family: metadynamics, restraints, walls);
                              *     additive, same version: m3g_sq_state_bytes / _init / _sample / _read / _frame (scattering observables:
-                             *     S(q), F(q,t) and the longitudinal and transverse current correlations) */
+                             *     S(q), F(q,t) and the longitudinal and transverse current correlations);
+                             *     additive, same version: m3g_lo_state_bytes / _init / _sample / _read / _frame (local-order observables:
+                             *     Steinhardt q_l, their neighbour average, solid-like atoms and their clusters) */
 
 #ifdef __cplusplus
 }

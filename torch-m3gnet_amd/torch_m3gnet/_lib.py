@@ -151,6 +151,19 @@ class M3GSqParams(C.Structure):   # m3g_sq_params
 
 SQ_MAX_INDEX, SQ_MAX_Q, SQ_MAX_SPECIES, SQ_MAX_LAGS, SQ_CELL = 128, 4096, 4, 4096, 1   # M3G_SQ_MAX_*, M3G_SQ_CELL
 
+LO_MAX_DEGREE, LO_MAX_DEGREES, LO_MAX_NEIGHBORS, LO_MAX_SPECIES, LO_MAX_BINS, LO_MAX_SERIES = 12, 3, 32, 4, 1024, 65536   # M3G_LO_MAX_*
+LO_CELL, LO_RANGE, LO_NEIGHBORS, LO_NONFINITE = 1, 2, 4, 8   # M3G_LO_* flags
+
+
+class M3GLoSizes(C.Structure):   # m3g_lo_sizes
+    _fields_ = [("n_atoms", C.c_int64), ("n_structs", C.c_int64), ("max_species", C.c_int32), ("n_degrees", C.c_int32),
+                ("hist_bins", C.c_int32), ("series_cap", C.c_int32)]
+
+
+class M3GLoParams(C.Structure):   # m3g_lo_params
+    _fields_ = [("degrees", C.c_int32 * LO_MAX_DEGREES), ("solid_degree", C.c_int32), ("solid_bonds", C.c_int32),
+                ("solid_threshold", C.c_double)]
+
 
 class M3GNmaSizes(C.Structure):   # m3g_nma_sizes
     _fields_ = [("n_atoms", C.c_int64), ("n_structs", C.c_int64), ("n_unit_atoms", C.c_int64), ("n_qpoints", C.c_int64),
@@ -359,6 +372,12 @@ SYMBOLS = {
     "m3g_sq_read": (C.c_int, [C.POINTER(M3GSqSizes), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p]),
     "m3g_sq_frame": (C.c_int, [C.POINTER(M3GSqSizes), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_lo_state_bytes": (C.c_int, [C.POINTER(M3GLoSizes), C.POINTER(C.c_size_t)]),
+    "m3g_lo_init": (C.c_int, [C.POINTER(M3GLoSizes), C.POINTER(M3GLoParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                              C.c_void_p]),
+    "m3g_lo_sample": (C.c_int, [C.POINTER(M3GLoSizes), C.POINTER(M3GLoParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m3g_lo_read": (C.c_int, [C.POINTER(M3GLoSizes), C.c_void_p, C.c_size_t] + [C.c_void_p] * 10),
+    "m3g_lo_frame": (C.c_int, [C.POINTER(M3GLoSizes), C.c_void_p, C.c_size_t] + [C.c_void_p] * 8),
     "m3g_nma_state_bytes": (C.c_int, [C.POINTER(M3GNmaSizes), C.POINTER(C.c_size_t)]),
     "m3g_nma_init": (C.c_int, [C.POINTER(M3GNmaSizes), C.POINTER(M3GNmaParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

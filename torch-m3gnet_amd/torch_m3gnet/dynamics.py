@@ -27,6 +27,7 @@ from ._driver import (EV_A3_TO_GPA, Driver, IntegratorState, MdBatch, MdLog, int
                       positive, state_tensor, structure_arrays, structure_masses, structure_seeds)
 from .data import MaterialGraphKey as K
 from .nn.modules import Gradient
+from .local_order import LocalOrderObservables, lo_sample
 from .scattering import ScatteringObservables, sq_sample
 from .trajectory import TrajectoryObservables, traj_sample
 
@@ -221,6 +222,19 @@ def _split_observables(observables):
     return found[TrajectoryObservables], found[ScatteringObservables]
 
 
+def _take_local_order(observables):
+    """(LocalOrderObservables or None, what is left of the `observables` argument for `_split_observables`): at most one of them, alone
+    or anywhere in the list / tuple."""
+    if isinstance(observables, LocalOrderObservables):
+        return observables, None
+    if not isinstance(observables, (list, tuple)):
+        return None, observables
+    mine = [item for item in observables if isinstance(item, LocalOrderObservables)]
+    if len(mine) > 1:
+        raise TypeError("observables must hold at most one of each kind; got a second LocalOrderObservables")
+    return (mine[0] if mine else None), [item for item in observables if not isinstance(item, LocalOrderObservables)]
+
+
 class MolecularDynamics(Driver):
     """Batched counterpart of m3gnet's `MolecularDynamics`.
 
@@ -294,16 +308,18 @@ class MolecularDynamics(Driver):
         masses: [n_s] amu per structure (default: standard atomic weights).  Returns one dict per structure: positions (unwrapped),
         velocities, lattice, total_energy, forces, stresses (pair virial) at the final step, n_steps, error (its forces became
         non-finite: it was stopped where it stood), and `log`: arrays step, e_pot, ke (eV), t (K), p (GPa), v (A^3) (and `conserved`,
-        eV, with "nvt_nose_hoover", "npt_mtk" and "npt_mtk_cell"; the last also pressure_tensor and lattice) every `loginterval` steps and at the last one.  observables: a `TrajectoryObservables`, a `ScatteringObservables`, or a list / tuple
+        eV, with "nvt_nose_hoover", "npt_mtk" and "npt_mtk_cell"; the last also pressure_tensor and lattice) every `loginterval` steps and at the last one.  observables: a `TrajectoryObservables`, a `ScatteringObservables`, a `LocalOrderObservables`, or a list / tuple
         holding at most one of each; the trajectory is then sampled on the
         device before the integrator call of every `sample_interval`-th step (positions, forces and velocities are synchronous only
         there: the sampler completes the half-step velocities with the finish kick itself) and every dict gains "observables"
-        (trajectory) and / or "scattering".
+        (trajectory), "scattering" and / or "local_order".
         With "nvt_nose_hoover" the sampler's own v + dt/2 a is the state between the closing kick and the closing thermostat
         half-step: a point on the trajectory of the cyclically permuted splitting, as good a sample of the same dynamics.  With
-        "npt_mtk" and "npt_mtk_cell" the closing kick is not the plain one (it carries the barostat's friction), so `observables`
-        raises ValueError.  "npt_mtk_cell" with `cell_mask` "orthorhombic" needs every lattice diagonal to 1e-9 of its largest entry.
+        "npt_mtk" and "npt_mtk_cell" the closing kick is not the plain one (it carries the barostat's friction), so those two kinds
+        raise ValueError; a `LocalOrderObservables` reads positions and cells only (the current ones, before the integrator call
+        of every `sample_interval`-th step) and runs with every ensemble.  "npt_mtk_cell" with `cell_mask` "orthorhombic" needs every lattice diagonal to 1e-9 of its largest entry.
         As in the other NPT ensembles the cells go to the host and the candidates are searched again at every step."""
+        local, observables = _take_local_order(observables)
         observables, scattering = _split_observables(observables)
         if (observables is not None or scattering is not None) and self.ensemble in ("npt_mtk", "npt_mtk_cell"):
             raise ValueError(f"observables are not supported with {self.ensemble}: its finish kick is not the sampler's v + dt/2 a")
@@ -339,6 +355,7 @@ class MolecularDynamics(Driver):
                                                                         **self._params())
         traj = observables.begin(lat, z, m, vg.device) if observables is not None else None
         sq = scattering.begin(lat, z, m, vg.device) if scattering is not None else None
+        lo = local.begin(lat, z, m, vg.device) if local is not None else None
         log, cells = MdLog(conserved=nhc, cell=cell), []
 
         def before(k, out, logged):
@@ -346,6 +363,8 @@ class MolecularDynamics(Driver):
                 traj_sample(traj, pos_t, lat64, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
             if sq is not None and k % scattering.sample_interval == 0:
                 sq_sample(sq, pos_t, lat64, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
+            if lo is not None and k % local.sample_interval == 0:
+                lo_sample(lo, pos_t, lat64)
             if cell and logged:
                 cells.append(lat64.clone())   # (the cell of the observables: the integrator call moves it on)
 
@@ -362,4 +381,7 @@ class MolecularDynamics(Driver):
         if sq is not None:
             for r, obs in zip(res, scattering.results(sq, self.timestep)):
                 r["scattering"] = obs
+        if lo is not None:
+            for r, obs in zip(res, local.results(lo, self.timestep)):
+                r["local_order"] = obs
         return res
