@@ -1540,6 +1540,16 @@ int m3g_debug_live_handles(const m3g_plan* plan, int32_t* out);
  * temporary storage and wait for the stream: diagnostics only. */
 int m3g_debug_exclusive_scan(int32_t elem_bytes, int64_t n, const void* in, void* out, void* stream);
 int m3g_debug_radix_sort(int32_t key_bytes, int64_t n, void* keys, int32_t* vals, int32_t begin_bit, int32_t end_bit, void* stream);
+/* Test hook, host only (no device call): where each array of the topology buffer lies, from the very function the builds carve the
+ * buffer with.  Regions in the buffer's order:
+ *   src, dst, row_ptr, in_ptr, in_edge, in_pair, in_pos, t1_ptr, t1_e2, t2_ptr, t2_e1, act_list, act_scan, act_id, arow_ptr, act_dst,
+ *   tb_win, tb_fast, t1_e2c, t2_e1c, t1_b, t2_b, batch, struct_ptr, flags
+ * byte_offset[i] from the start of the buffer, n_elems[i] the documented length (E, N + 1, T, 2 E for in_pair, 6 and 2 words per window
+ * record over n_edges / 128 + 1 records for tb_win and tb_fast, 16 for flags; act_list and act_dst: E, of which the first A =
+ * m3g_topology_active_edges are written) -- not the padded allocation --, elem_bytes[i] 4 (int32) or 1 (t1_b, t2_b).  *n_regions is
+ * the number of regions (25); at most max_regions entries are written, so a call with max_regions = 0 asks for the count alone. */
+int m3g_debug_topology_layout(int64_t n_atoms, int64_t n_edges, int64_t n_triplets, int64_t n_structs, int32_t max_regions,
+                              int64_t* byte_offset, int64_t* n_elems, int32_t* elem_bytes, int32_t* n_regions);
 
 /* Measurement: what ONE m3g_energy_forces call with these arguments puts on a stream -- kernel launches and other operations (memsets,
  * copies) -- counted by capturing the call's own launch sequence into a HIP graph on an internal stream (nothing executes, no buffer
@@ -1584,7 +1594,8 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     additive, same version: m3g_sq_state_bytes / _init / _sample / _read / _frame (scattering observables:
                              *     S(q), F(q,t) and the longitudinal and transverse current correlations);
                              *     additive, same version: m3g_lo_state_bytes / _init / _sample / _read / _frame (local-order observables:
-                             *     Steinhardt q_l, their neighbour average, solid-like atoms and their clusters) */
+                             *     Steinhardt q_l, their neighbour average, solid-like atoms and their clusters);
+                             *     additive, same version: m3g_debug_topology_layout (test hook: the regions of the topology buffer) */
 
 #ifdef __cplusplus
 }

@@ -251,6 +251,35 @@ def test_dense_three_body_rows_beyond_the_staged_window():
         assert rel_err(g[K.TOTAL_ENERGY], o["total_energy"]) < 1e-5
         assert rel_err(g[K.FORCES], o["forces"]) < 1e-4
         assert rel_err(g[K.STRESSES], o["stresses"]) < 1e-4
+    # Windows of 193..255 rows under the SHORT-list instantiation (T <= 24 E), which stages kTbCapShort = 192 rows: byte-sized
+    # partner ids of 192..254 are then valid ids of rows that are not staged.  No other engine-vs-oracle input of the suite has such
+    # a window (tests/topology_cases.py: STAGED_WINDOW_CELL, found by search; tests/test_topology_cpu.py asserts the regime).  Once
+    # with the default selection (the moment kernels: its certificate holds) and once with the list kernels.
+    import topology_cases as tc
+    from helpers import set_options
+    from torch_m3gnet.data.material_graph import MaterialGraph
+    from torch_m3gnet.data.synthetic import random_cell_arrays
+
+    cell = tc.STAGED_WINDOW_CELL
+    rows = tc.window_rows(tc.reference("24 atoms in 6.5 A"))
+    assert tc.case("24 atoms in 6.5 A").T <= 24 * tc.case("24 atoms in 6.5 A").E and ((rows >= 193) & (rows <= 255)).any()
+    model = _default_model(seed=2, cutoff=cell["cutoff"], threebody_cutoff=cell["tb_cutoff"])
+    lat, pos, z = random_cell_arrays(cell["n_atoms"], cell["box"], cell["seed"])
+    staged = MaterialGraph.from_arrays(lat, pos, z, cell["cutoff"], cell["tb_cutoff"])
+    assert int(staged[K.NUM_TRIPLETS]) == tc.case("24 atoms in 6.5 A").T
+    o = None
+    try:
+        for moments in (1, 0):
+            set_options(model, threebody_moments=moments)
+            g = model(Batch.from_data_list([staged.clone()]).to(DEV))
+            if o is None:
+                p, cfg, c, og = _oracle_inputs(model, g)
+                o = orc.energy_forces(p, cfg, c, og, legendre_backward="exact")
+            errs = [rel_err(g[K.TOTAL_ENERGY], o["total_energy"]), rel_err(g[K.FORCES], o["forces"]), rel_err(g[K.STRESSES], o["stresses"])]
+            print(f"staged-window cell, threebody_moments={moments}: E {errs[0]:.2e} F {errs[1]:.2e} stress {errs[2]:.2e}")
+            assert errs[0] < 1e-5 and errs[1] < 1e-4 and errs[2] < 1e-4, (moments, errs)
+    finally:
+        set_options(model, threebody_moments=1)
 
 
 def test_scales_and_elemental_energies():

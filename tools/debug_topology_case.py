@@ -1,48 +1,58 @@
+"""Case `n` of tests/checkers/fuzz_topology_build.py (same random stream) through the general and the canonical topology build: which
+regions of the two buffers differ, and where.  The layout is the library's own (m3g_debug_topology_layout).
+Usage: python tools/debug_topology_case.py CASE"""
+import ctypes as C
 import sys
 from pathlib import Path
-import numpy as np, torch
-ROOT = Path('/root/repo') if Path('/root/repo/tests').exists() else Path.cwd()
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
 for p in (ROOT, ROOT / "torch-m3gnet_amd", ROOT / "tests", ROOT / "tests/checkers"):
     sys.path.insert(0, str(p))
-from fuzz_graph_build import random_cell
-from test_gpu_graph_build import _topology_buffers
-from torch_m3gnet.data import MaterialGraphKey as K
-from torch_m3gnet.data.graph_gpu import batch_from_arrays
-target = int(sys.argv[1])
-rng = np.random.default_rng(0)
-for c in range(target + 1):
-    cutoff = float(rng.uniform(2.5, 9.0))
-    tb = float(rng.uniform(0.5, 1.0) * cutoff) if rng.random() < 0.8 else cutoff
-    cells = [random_cell(rng) for _ in range(int(rng.integers(1, 7)))]
-    if min(abs(np.linalg.det(l)) for l, _ in cells) < 4.0:
-        continue
-    g = batch_from_arrays([l for l, _ in cells], [p for _, p in cells], [np.full(len(p), 14) for _, p in cells], cutoff, tb, device="cuda")
-    if c < target: continue
-    N, E, T, S = int(g[K.NUM_NODES]), int(g[K.NUM_EDGES]), int(g[K.NUM_TRIPLETS]), len(cells)
-    (a, ha, fa), (b, hb, fb), path = _topology_buffers(g)
-    al = lambda x: (x + 255) // 256 * 256
-    W = E // 128 + 2
-    layout = [("src", (E+1)*4), ("dst", (E+1)*4), ("row_ptr", (N+1)*4), ("in_ptr", (N+1)*4), ("in_edge", (E+1)*4), ("in_pair", 2*(E+1)*4), ("in_pos", (E+1)*4),
-              ("t1_ptr", (E+1)*4), ("t1_e2", (T+1)*4), ("t2_ptr", (E+1)*4), ("t2_e1", (T+1)*4), ("act_list", (E+1)*4), ("act_scan", (E+2)*4), ("act_id", (E+1)*4),
-              ("arow_ptr", (N+2)*4), ("act_dst", (E+1)*4), ("tb_win", 6*W*4), ("tb_fast", 2*W*4), ("t1_e2c", (T+1)*4), ("t2_e1c", (T+1)*4), ("t1_b", T+16), ("t2_b", T+16),
-              ("batch", (N+1)*4), ("struct_ptr", (S+2)*4), ("flags", 64)]
-    print("N E T S", N, E, T, S, "bytes", a.numel())
-    off = 0
-    for name, nb in layout:
-        seg_a, seg_b = a[off:off+nb], b[off:off+nb]
-        if not torch.equal(seg_a, seg_b):
-            bad = torch.nonzero(seg_a != seg_b).flatten()
-            print(name, "differs at", bad.numel(), "bytes; first byte", int(bad[0]), "-> element", int(bad[0]) // (1 if name.endswith('_b') else 4))
-            if not name.endswith('_b'):
-                ia = seg_a[: nb // 4 * 4].view(torch.int32); ib = seg_b[: nb // 4 * 4].view(torch.int32)
-                idx = torch.nonzero(ia != ib).flatten()[:8]
-                print("   idx", idx.tolist(), "general", ia[idx].tolist(), "canonical", ib[idx].tolist())
-        off += al(nb)
-    print("total accounted", off)
-    off = 0
-    for name, nb in layout:
-        if name in ("flags", "tb_win", "tb_fast"):
-            ia = a[off:off+nb].view(torch.int32); ib = b[off:off+nb].view(torch.int32)
-            print(name, "general", ia[:12].tolist(), "canonical", ib[:12].tolist())
-        off += al(nb)
-    print("hints", hex(ha), hex(hb), "path", path)
+from fuzz_graph_build import random_cell  # noqa: E402
+from test_gpu_graph_build import _topology_buffers  # noqa: E402
+from topology_reference import REGIONS  # noqa: E402
+from torch_m3gnet import _lib  # noqa: E402
+from torch_m3gnet.data import MaterialGraphKey as K  # noqa: E402
+from torch_m3gnet.data.graph_gpu import batch_from_arrays  # noqa: E402
+
+
+def layout(N, E, T, S):
+    """[(region, byte offset, documented elements, bytes per element)]"""
+    off, n, b = (C.c_int64 * 32)(), (C.c_int64 * 32)(), (C.c_int32 * 32)()
+    count = C.c_int32()
+    _lib.check(_lib.load_library().m3g_debug_topology_layout(N, E, T, S, 32, off, n, b, C.byref(count)))
+    assert count.value == len(REGIONS)
+    return [(name, int(off[i]), int(n[i]), int(b[i])) for i, name in enumerate(REGIONS)]
+
+
+def main():
+    target = int(sys.argv[1])
+    rng = np.random.default_rng(0)
+    for c in range(target + 1):
+        cutoff = float(rng.uniform(2.5, 9.0))
+        tb = float(rng.uniform(0.5, 1.0) * cutoff) if rng.random() < 0.8 else cutoff
+        cells = [random_cell(rng) for _ in range(int(rng.integers(1, 7)))]
+        if min(abs(np.linalg.det(l)) for l, _ in cells) < 4.0:
+            continue
+        g = batch_from_arrays([l for l, _ in cells], [p for _, p in cells], [np.full(len(p), 14) for _, p in cells], cutoff, tb, device="cuda")
+        if c < target:
+            continue
+        N, E, T, S = int(g[K.NUM_NODES]), int(g[K.NUM_EDGES]), int(g[K.NUM_TRIPLETS]), len(cells)
+        (a, ha, fa), (b, hb, fb), path = _topology_buffers(g)
+        print("N E T S", N, E, T, S, "bytes", a.numel())
+        for name, off, n, width in layout(N, E, T, S):
+            dt = torch.uint8 if width == 1 else torch.int32
+            ia, ib = a[off:off + n * width].view(dt), b[off:off + n * width].view(dt)
+            if not torch.equal(ia, ib):
+                idx = torch.nonzero(ia != ib).flatten()
+                print(name, "differs at", idx.numel(), "elements:", idx[:8].tolist(), "general", ia[idx[:8]].tolist(), "canonical", ib[idx[:8]].tolist())
+            if name in ("flags", "tb_win", "tb_fast"):
+                print(name, "general", ia[:12].tolist(), "canonical", ib[:12].tolist())
+        print("hints", hex(ha), hex(hb), "path", path)
+
+
+if __name__ == "__main__":
+    main()

@@ -359,10 +359,13 @@ struct Topo {
   int32_t* n_act;      // device scalar A (= flags + 2)
   int32_t* batch;    // [N]
   int32_t* struct_ptr;  // [S+1] atoms of structure s: struct_ptr[s] .. struct_ptr[s+1] (valid when `batch` is non-decreasing, flags[3] == 0)
-  int32_t* flags;    // [kTopoFlags] [0] malformed-graph bits; [2] = A; [3] != 0: `batch` is not sorted (per-structure sums then use atomics);
+  int32_t* flags;    // [kTopoFlags] [0] malformed-graph bits (bits 0-2; bit 3, "sort the incoming edges after all", is the build's own and
+                     // cleared before it returns: 0 after a build of well-formed lists); [1] the build's order / symmetry verdicts, 0 after
+                     // it; [2] = A; [3] != 0: `batch` is not sorted (per-structure sums then use atomics);
                      // [4] three-body workgroups that may NOT use the moment path, [5] largest window (rows), [6] most atoms per window
                      // (m3g_topology_hints packs 4..6 for the caller); [7] the hints word m3g_topology_hints certified for this
-                     // buffer (0 after a build); [8] sticky error bits set by the hot call (M3G_TOPO_ERR_*, m3g_topology_status)
+                     // buffer (0 after a build); [8] sticky error bits set by the hot call (M3G_TOPO_ERR_*, m3g_topology_status);
+                     // [9..15] reserved, 0
   void* sort_tmp;    // scratch for the radix sorts
   size_t sort_tmp_bytes;
   size_t total_bytes;

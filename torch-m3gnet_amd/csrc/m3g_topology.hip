@@ -170,14 +170,29 @@ __global__ void k_convert_triplets(int64_t E, int64_t T, const int64_t* __restri
 }
 // order[0] |= 2 when some triplet (e1, e2) has no mirror (e2, e1) in the SORTED key list: the list is one-sided.  The mirror can
 // only sit in the row of e2, rows[e2] .. rows[e2 + 1] (a handful of slots), so the search stays inside that row.
+// A pair that is listed more than once needs its mirror as often: a symmetric list has its second-edge lists copied from the
+// first-edge lists, and (a, b) twice beside (b, a) once would give b one partner a where it has two.  Copies are neighbours in the
+// sorted list: the FIRST copy of a pair alone counts its copies and those of its mirror (each run of equal keys is walked once, by
+// one thread), and only when it or its mirror has an equal neighbour.
 __global__ void k_check_symmetric(int64_t T, const uint64_t* __restrict__ sorted_keys, const int32_t* __restrict__ rows, int32_t* order) {
   int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (t >= T) return;
+  // (bit 0, raised by k_convert_triplets a launch earlier: the keys are not sorted, the caller discards this verdict and asks again
+  // on the sorted keys -- no walk through runs of a list that is in no order)
+  if (order[0] & 1) return;
   const uint64_t k = sorted_keys[t], want = (k << 32) | (k >> 32);
   const int64_t e2 = (int64_t)(k & 0xffffffffu);
   const int64_t begin = rows[e2], end = rows[e2 + 1];
   const int64_t at = begin + lower_bound(sorted_keys + begin, end - begin, want);
-  if (at >= end || sorted_keys[at] != want) atomicOr(order, 2);
+  bool ok = at < end && sorted_keys[at] == want;
+  const bool first = t == 0 || sorted_keys[t - 1] != k;
+  if (ok && first && ((t + 1 < T && sorted_keys[t + 1] == k) || (at + 1 < end && sorted_keys[at + 1] == want))) {
+    int64_t n_own = 1, n_mirror = 1;
+    for (int64_t i = t + 1; i < T && sorted_keys[i] == k; ++i) ++n_own;
+    for (int64_t i = at + 1; i < end && sorted_keys[i] == want; ++i) ++n_mirror;
+    ok = n_own == n_mirror;
+  }
+  if (!ok) atomicOr(order, 2);
 }
 
 // Incoming-edge lists without a sort, for SYMMETRIC edge lists (every i -> j has its j -> i, with multiplicity: what any full
@@ -797,6 +812,8 @@ static int topology_build(int64_t N, int64_t E, int64_t T, int64_t S, const int6
       if (try_mirrors && (h[0] & 8)) {   // not a symmetric edge list (or very long rows): the stable sort after all
         int rc2 = sort_in_edges();       // (clobbers keysA / keysB: the triplet keys are formed again below)
         if (rc2) return rc2;
+        // bit 3 has done its work and is no malformed-graph bit: the buffer keeps the others only (the kernels below raise those again)
+        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, s, t.flags, h[0] & ~8);
       }
       M3G_HIP_CHECK(hipMemsetAsync(order, 0, sizeof(int32_t), s));
       hipLaunchKernelGGL(k_convert_triplets, grid(T), dim3(TPB), 0, s, E, T, triplet_edge_index, t.src, keysA, 0, t.flags, order);
@@ -1008,6 +1025,37 @@ extern "C" int m3g_topology_data_bytes(int64_t N, int64_t E, int64_t T, int64_t 
   if (rc) return rc;
   const Topo t = topo_carve(N, E, T, S, nullptr);
   *bytes = t.total_bytes - align_up(t.sort_tmp_bytes);
+  return M3G_OK;
+}
+// The documented regions of the buffer in the order of struct Topo's carve, from topo_carve itself (host only): a test or a tool that
+// reads the buffer takes its layout from here, so it cannot drift from what the builds write.  n_elems is the documented length of
+// struct Topo's comments (E, N + 1, T, ...), not the padded allocation.
+extern "C" int m3g_debug_topology_layout(int64_t N, int64_t E, int64_t T, int64_t S, int32_t max_regions, int64_t* byte_offset,
+                                         int64_t* n_elems, int32_t* elem_bytes, int32_t* n_regions) {
+  if (!n_regions || max_regions < 0 || (max_regions > 0 && (!byte_offset || !n_elems || !elem_bytes))) {
+    set_error("m3g_debug_topology_layout: bad argument");
+    return M3G_ERR_VALUE;
+  }
+  size_t total = 0;
+  int rc = m3g_topology_bytes(N, E, T, S, &total);
+  if (rc) return rc;
+  const Topo t = topo_carve(N, E, T, S, nullptr);
+  const int64_t W = tb_win_blocks(E);
+  struct Region { const void* at; int64_t n; int32_t bytes; };
+  const Region regions[] = {
+      {t.src, E, 4},         {t.dst, E, 4},         {t.row_ptr, N + 1, 4},  {t.in_ptr, N + 1, 4},   {t.in_edge, E, 4},
+      {t.in_pair, 2 * E, 4}, {t.in_pos, E, 4},      {t.t1_ptr, E + 1, 4},   {t.t1_e2, T, 4},        {t.t2_ptr, E + 1, 4},
+      {t.t2_e1, T, 4},       {t.act_list, E, 4},    {t.act_scan, E + 1, 4}, {t.act_id, E, 4},       {t.arow_ptr, N + 1, 4},
+      {t.act_dst, E, 4},     {t.tb_win, kTbWinWords * W, 4},                {t.tb_fast, 2 * W, 4},  {t.t1_e2c, T, 4},
+      {t.t2_e1c, T, 4},      {t.t1_b, T, 1},        {t.t2_b, T, 1},         {t.batch, N, 4},        {t.struct_ptr, S + 1, 4},
+      {t.flags, kTopoFlags, 4}};
+  const int32_t n = (int32_t)(sizeof(regions) / sizeof(regions[0]));
+  *n_regions = n;
+  for (int32_t i = 0; i < n && i < max_regions; ++i) {
+    byte_offset[i] = (int64_t)carve_offset(regions[i].at);
+    n_elems[i] = regions[i].n;
+    elem_bytes[i] = regions[i].bytes;
+  }
   return M3G_OK;
 }
 extern "C" int m3g_topology_debug_last_path(int32_t* path) {
