@@ -1240,6 +1240,77 @@ int m3g_lo_read(const m3g_lo_sizes* sizes, const void* state, size_t state_bytes
 int m3g_lo_frame(const m3g_lo_sizes* sizes, const void* state, size_t state_bytes, double* host_qlm, double* host_ql, double* host_qbar,
                  int32_t* host_n_neighbors, int32_t* host_n_conn, int32_t* host_solid, int32_t* host_label, void* stream);
 
+/* ---- thermodynamic fluctuation observables and Green-Kubo stress correlations (csrc/m3g_thermo.hip) ---------------------------------
+ * The per-structure companion of the three families above, fed one sample per m3g_thermo_sample at the synchronous point of a step:
+ * the engine's energies and pair-virial stresses, the cell, and the kinetic part from one of two sources.
+ * (a) `vel` (with `forces`: v = vel + kick kappa F / m, the completion of m3g_traj_sample).  Over the rows of structure s, with the
+ *     Voigt order c = xx, yy, zz, yz, zx, xy:  R_c = sum m v_a v_b,  M = sum m,  Q_a = sum m v_a  (a fixed tree inside a 256-row
+ *     chunk, then the chunks in order);  K_c = R_c / kappa, or with remove_com (R_c - Q_a Q_b / M) / kappa  (eV);
+ *     ke = ((K_xx + K_yy) + K_zz) / 2;  P_c = (double)stresses[s][c] + K_c / V;  p = ((P_xx + P_yy) + P_zz) / 3.
+ * (b) `kinetic` (a device fp64 value per structure, kinetic[s * kinetic_stride]: the obs row of an integrator):  ke is read; with
+ *     `pressure_tensor` P_c = pressure_tensor[s * tensor_stride + c] and p as in (a); without it no tensor is defined (n_lags must
+ *     be 0) and p = (V ((s_xx + s_yy) + s_zz) + 2 ke) / (3 V) with s = (double)stresses[s]: the pressure of m3g_nhc_step.
+ * V = |det L| of `lattice` [s] (rows = lattice vectors).  The row of the sample, x [M3G_THERMO_ROW = 11], fp64:
+ *     x0 = e_pot = (double)energies[s];  x1 = ke;  x2 = V;  x3 = h = (e_pot + ke) + p_ext[s] V;  x4 = p;
+ *     x5 .. x10 = the Green-Lagrange strain eps = (A A^T - 1) / 2 against the reference cell L0, A = L0^-1 L (A_ij = sum_k
+ *     L0inv_ik L_kj, (A A^T)_ij = sum_k A_ik A_jk, k ascending), components xx, yy, zz, yz, zx, xy (tensor components, no factor 2);
+ *     L0^-1 is formed once by the init call on the host in fp64 (adjugate over determinant).
+ * The tensor of the sample, u [M3G_THERMO_TENSOR = 7] = (P_xx, P_yy, P_zz, P_yz, P_zx, P_xy, p); (b) without a tensor: not formed.
+ * A sample of a structure whose x or u holds a non-finite value (or, in (a), that has a row with a non-finite velocity) sets
+ * M3G_THERMO_NONFINITE (sticky), is counted in n_skipped, enters no accumulator and EMPTIES the ring of that structure, so that no
+ * lag spans the gap.  Otherwise, with n = n_samples + 1 (Welford; exactly this order, i <= j, the 66 co-moments row-major over the
+ * upper triangle, (i, j) at i * 11 - i (i - 1) / 2 + (j - i)):
+ *     d_i = x_i - mean_i;   mean_i <- mean_i + d_i / n;   C_ij <- C_ij + d_i * (x_j - mean_j)   with the NEW mean_j;   n_samples <- n
+ * so that Cov(x_i, x_j) = C_ij / n_samples (the fluctuation formulas want the population form).  With n_lags > 0 u is pushed into
+ * the structure's ring of the last n_lags tensors, and for every lag l = 0 .. min(entries in the ring, n_lags) - 1 and component c:
+ *     uu[l][c] += u_c(now) * u_c(now - l);   now[l][c] += u_c(now);   old[l][c] += u_c(now - l);   lag_count[l] += 1
+ * (lag 0 is the sample against itself), from which the mean-subtracted correlation at lag l is uu / k - (now / k)(old / k), k =
+ * lag_count[l].  The row is kept as the last row whether the sample was skipped or not.  fp64 throughout, no float atomics,
+ * fixed-order sums: every number depends on the structure's own rows only, bitwise the same alone or in any batch. */
+typedef struct {
+  int64_t n_atoms;     /* N */
+  int64_t n_structs;   /* S */
+  int32_t n_lags;      /* 0 .. 4096 (M3G_THERMO_MAX_LAGS); 0: no stress correlations, no ring */
+} m3g_thermo_sizes;
+typedef struct {
+  int32_t remove_com;  /* 0 / 1: mode (a) subtracts the centre-of-mass term Q_a Q_b / M */
+} m3g_thermo_params;
+#define M3G_THERMO_ROW 11
+#define M3G_THERMO_COMOMENTS 66
+#define M3G_THERMO_TENSOR 7
+#define M3G_THERMO_MAX_LAGS 4096
+#define M3G_THERMO_NONFINITE 1   /* a sample held a non-finite value: skipped, the ring emptied */
+/* Sizes outside their limits -> M3G_ERR_VALUE.  The size follows from `sizes` alone, every region rounded up to 256 bytes: the
+ * chunk table; masses [N], p_ext [S], L0^-1 [S,9] fp64; two int64 counters; flags [S] int32; n_samples, n_skipped [S] int64;
+ * ring fill and ring position [S] int32; mean [S,11], co-moments [S,66], last row [S,11] fp64; lag_uu, lag_now, lag_old
+ * [S, n_lags, 7] fp64, lag_count [S, n_lags] int64, the ring [S, n_lags, 7] fp64; 11 fp64 partials per chunk. */
+int m3g_thermo_state_bytes(const m3g_thermo_sizes* sizes, size_t* bytes);
+/* HOST host_offsets [S+1] and host_masses [N] (amu, finite and > 0) as m3g_traj_init; host_p_ext [S] (eV/A^3, finite): the external
+ * pressure of the enthalpy; host_reference_cells [S,3,3] (A, finite, |det| >= 1e-12): the L0 of the strain.  Everything is checked
+ * on the host before any HIP call -> M3G_ERR_VALUE; a short state buffer -> M3G_ERR_SIZE.  Uploads the tables, zeroes the
+ * accumulators, waits for the stream. */
+int m3g_thermo_init(const m3g_thermo_sizes* sizes, const m3g_thermo_params* params, const int64_t* host_offsets, const double* host_masses,
+                    const double* host_p_ext, const double* host_reference_cells, void* state, size_t state_bytes, void* stream);
+/* One sample, all pointers DEVICE: energies [S] and stresses [S,6] float32 (pair-virial convention of the integrators), lattice
+ * [S,3,3] fp64; then exactly one of vel [N,3] fp64 (mode (a); forces [N,3] float32 or NULL, kick finite) and kinetic (mode (b);
+ * kinetic_stride >= 1 doubles between structures; pressure_tensor or NULL, tensor_stride >= 6; forces must be NULL) -- both or
+ * neither, or n_lags > 0 in mode (b) without a tensor -> M3G_ERR_VALUE.  Two launches in mode (a), one in mode (b), whatever S, N
+ * and n_lags; ring positions and counts live in the state buffer: no allocation, copy or wait, capture-safe on one stream. */
+int m3g_thermo_sample(const m3g_thermo_sizes* sizes, const m3g_thermo_params* params, void* state, size_t state_bytes,
+                      const float* energies, const float* stresses, const double* lattice, const double* vel, const float* forces,
+                      double kick, const double* kinetic, int64_t kinetic_stride, const double* pressure_tensor, int64_t tensor_stride,
+                      void* stream);
+/* The accumulators to HOST memory; every output may be NULL: mean [S,11], comoments [S,66] fp64; lag_uu, lag_now, lag_old
+ * [S, n_lags, 7] fp64; lag_count [S, n_lags], n_samples, n_skipped [S] int64; flags [S] int32 (M3G_THERMO_*).  Waits. */
+int m3g_thermo_read(const m3g_thermo_sizes* sizes, const void* state, size_t state_bytes, double* host_mean, double* host_comoments,
+                    double* host_lag_uu, double* host_lag_now, double* host_lag_old, int64_t* host_lag_count, int64_t* host_n_samples,
+                    int64_t* host_n_skipped, int32_t* host_flags, void* stream);
+/* The last row [S,11] and the ring entry `lag` samples back [S,7] (0: the last one pushed; a structure whose ring holds no such
+ * entry: NaN) to HOST memory; either may be NULL.  host_tensor needs n_lags > 0 and 0 <= lag < n_lags; before any sample:
+ * M3G_ERR_VALUE.  Waits for the stream. */
+int m3g_thermo_frame(const m3g_thermo_sizes* sizes, const void* state, size_t state_bytes, int32_t lag, double* host_row,
+                     double* host_tensor, void* stream);
+
 /* ---- normal-mode analysis of MD: the trajectory projected on harmonic eigenvectors (csrc/m3g_nma.hip) -------------------------------
  * Normal-mode decomposition (Ladd, Moran and Hoover, Phys. Rev. B 34, 5058 (1986); McGaughey and Kaviany, Phys. Rev. B 69, 094303
  * (2004); the spectral energy density of Thomas et al., Phys. Rev. B 81, 081411 (2010)), fed one frame per m3g_nma_sample, as the
@@ -1595,6 +1666,8 @@ int m3g_count_launches(const m3g_plan* plan, const m3g_io* io, void* workspace, 
                              *     S(q), F(q,t) and the longitudinal and transverse current correlations);
                              *     additive, same version: m3g_lo_state_bytes / _init / _sample / _read / _frame (local-order observables:
                              *     Steinhardt q_l, their neighbour average, solid-like atoms and their clusters);
+                             *     additive, same version: m3g_thermo_state_bytes / _init / _sample / _read / _frame (thermodynamic
+                             *     fluctuation observables: Welford co-moments of e_pot, ke, V, h, p and the strain; stress correlations);
                              *     additive, same version: m3g_debug_topology_layout (test hook: the regions of the topology buffer) */
 
 #ifdef __cplusplus

@@ -1,6 +1,6 @@
-// The device and C-ABI layer all eighteen batched drivers share.  Ten of them include it themselves: m3g_relax.hip (FIRE),
+// The device and C-ABI layer all nineteen batched drivers share.  Eleven of them include it themselves: m3g_relax.hip (FIRE),
 // m3g_lbfgs.hip, m3g_neb.hip, m3g_phonons.hip, m3g_elastic.hip, m3g_trajectory.hip, m3g_scattering.hip, m3g_local_order.hip,
-// m3g_nma.hip and m3g_meta.hip.  m3g_remd.hip,
+// m3g_thermo.hip, m3g_nma.hip and m3g_meta.hip.  m3g_remd.hip,
 // m3g_mc.hip and m3g_rnemd.hip, which work on the state of m3g_dyn_*, reach it through m3g_dyn_state.h; the five step families
 // m3g_dynamics.hip, m3g_nhc.hip, m3g_mtk.hip, m3g_pimd.hip and m3g_ti.hip through m3g_integrator.h, which includes
 // m3g_dyn_state.h.  (m3g_eigh.hip, no driver, includes it too, for kWave and its checks.)  Here is one copy of what their C entry

@@ -165,6 +165,17 @@ class M3GLoParams(C.Structure):   # m3g_lo_params
                 ("solid_threshold", C.c_double)]
 
 
+THERMO_ROW, THERMO_COMOMENTS, THERMO_TENSOR, THERMO_MAX_LAGS, THERMO_NONFINITE = 11, 66, 7, 4096, 1   # M3G_THERMO_*
+
+
+class M3GThermoSizes(C.Structure):   # m3g_thermo_sizes
+    _fields_ = [("n_atoms", C.c_int64), ("n_structs", C.c_int64), ("n_lags", C.c_int32)]
+
+
+class M3GThermoParams(C.Structure):   # m3g_thermo_params
+    _fields_ = [("remove_com", C.c_int32)]
+
+
 class M3GNmaSizes(C.Structure):   # m3g_nma_sizes
     _fields_ = [("n_atoms", C.c_int64), ("n_structs", C.c_int64), ("n_unit_atoms", C.c_int64), ("n_qpoints", C.c_int64),
                 ("n_modes", C.c_int64), ("n_eig", C.c_int64), ("n_phase", C.c_int64), ("max_n", C.c_int32), ("n_lags", C.c_int32)]
@@ -380,6 +391,14 @@ SYMBOLS = {
     "m3g_lo_sample": (C.c_int, [C.POINTER(M3GLoSizes), C.POINTER(M3GLoParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_lo_read": (C.c_int, [C.POINTER(M3GLoSizes), C.c_void_p, C.c_size_t] + [C.c_void_p] * 10),
     "m3g_lo_frame": (C.c_int, [C.POINTER(M3GLoSizes), C.c_void_p, C.c_size_t] + [C.c_void_p] * 8),
+    "m3g_thermo_state_bytes": (C.c_int, [C.POINTER(M3GThermoSizes), C.POINTER(C.c_size_t)]),
+    "m3g_thermo_init": (C.c_int, [C.POINTER(M3GThermoSizes), C.POINTER(M3GThermoParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "m3g_thermo_sample": (C.c_int, [C.POINTER(M3GThermoSizes), C.POINTER(M3GThermoParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                    C.c_void_p]),
+    "m3g_thermo_read": (C.c_int, [C.POINTER(M3GThermoSizes), C.c_void_p, C.c_size_t] + [C.c_void_p] * 10),
+    "m3g_thermo_frame": (C.c_int, [C.POINTER(M3GThermoSizes), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m3g_nma_state_bytes": (C.c_int, [C.POINTER(M3GNmaSizes), C.POINTER(C.c_size_t)]),
     "m3g_nma_init": (C.c_int, [C.POINTER(M3GNmaSizes), C.POINTER(M3GNmaParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -29,6 +29,7 @@ from .data import MaterialGraphKey as K
 from .nn.modules import Gradient
 from .local_order import LocalOrderObservables, lo_sample
 from .scattering import ScatteringObservables, sq_sample
+from .thermo import ThermoObservables, thermo_sample
 from .trajectory import TrajectoryObservables, traj_sample
 
 KAPPA = 9.648533215665e-3    # A/fs^2 per eV/(A amu)
@@ -235,6 +236,19 @@ def _take_local_order(observables):
     return (mine[0] if mine else None), [item for item in observables if not isinstance(item, LocalOrderObservables)]
 
 
+def _take_thermo(observables):
+    """(ThermoObservables or None, what is left of the `observables` argument for `_take_local_order`): at most one of them, alone or
+    anywhere in the list / tuple."""
+    if isinstance(observables, ThermoObservables):
+        return observables, None
+    if not isinstance(observables, (list, tuple)):
+        return None, observables
+    mine = [item for item in observables if isinstance(item, ThermoObservables)]
+    if len(mine) > 1:
+        raise TypeError("observables must hold at most one of each kind; got a second ThermoObservables")
+    return (mine[0] if mine else None), [item for item in observables if not isinstance(item, ThermoObservables)]
+
+
 class MolecularDynamics(Driver):
     """Batched counterpart of m3gnet's `MolecularDynamics`.
 
@@ -308,17 +322,24 @@ class MolecularDynamics(Driver):
         masses: [n_s] amu per structure (default: standard atomic weights).  Returns one dict per structure: positions (unwrapped),
         velocities, lattice, total_energy, forces, stresses (pair virial) at the final step, n_steps, error (its forces became
         non-finite: it was stopped where it stood), and `log`: arrays step, e_pot, ke (eV), t (K), p (GPa), v (A^3) (and `conserved`,
-        eV, with "nvt_nose_hoover", "npt_mtk" and "npt_mtk_cell"; the last also pressure_tensor and lattice) every `loginterval` steps and at the last one.  observables: a `TrajectoryObservables`, a `ScatteringObservables`, a `LocalOrderObservables`, or a list / tuple
+        eV, with "nvt_nose_hoover", "npt_mtk" and "npt_mtk_cell"; the last also pressure_tensor and lattice) every `loginterval` steps and at the last one.  observables: a `TrajectoryObservables`, a `ScatteringObservables`, a `LocalOrderObservables`, a `ThermoObservables`, or a list / tuple
         holding at most one of each; the trajectory is then sampled on the
         device before the integrator call of every `sample_interval`-th step (positions, forces and velocities are synchronous only
         there: the sampler completes the half-step velocities with the finish kick itself) and every dict gains "observables"
-        (trajectory), "scattering" and / or "local_order".
+        (trajectory), "scattering", "local_order" and / or "thermo".
         With "nvt_nose_hoover" the sampler's own v + dt/2 a is the state between the closing kick and the closing thermostat
-        half-step: a point on the trajectory of the cyclically permuted splitting, as good a sample of the same dynamics.  With
+        half-step: a point on the trajectory of the cyclically permuted splitting, as good a sample of the same dynamics (so the
+        kinetic energy a `ThermoObservables` sees there is not the logged `ke`, which is taken after that half-step).  With
         "npt_mtk" and "npt_mtk_cell" the closing kick is not the plain one (it carries the barostat's friction), so those two kinds
         raise ValueError; a `LocalOrderObservables` reads positions and cells only (the current ones, before the integrator call
-        of every `sample_interval`-th step) and runs with every ensemble.  "npt_mtk_cell" with `cell_mask` "orthorhombic" needs every lattice diagonal to 1e-9 of its largest entry.
+        of every `sample_interval`-th step) and runs with every ensemble.  A `ThermoObservables` runs with every ensemble too: with "npt_mtk" and
+        "npt_mtk_cell" it reads the kinetic energy (and, "npt_mtk_cell", the pressure tensor) from the integrator's own observables
+        after the integrator call, beside the cell, energies and stresses of the same step; "npt_mtk" states no pressure tensor,
+        so `ThermoObservables(n_lags > 0)` raises ValueError there.  "npt_mtk_cell" with `cell_mask` "orthorhombic" needs every lattice diagonal to 1e-9 of its largest entry.
         As in the other NPT ensembles the cells go to the host and the candidates are searched again at every step."""
+        thermo, observables = _take_thermo(observables)
+        if thermo is not None and thermo.n_lags > 0 and self.ensemble == "npt_mtk":
+            raise ValueError("ThermoObservables(n_lags > 0) is not supported with npt_mtk: its integrator states no pressure tensor")
         local, observables = _take_local_order(observables)
         observables, scattering = _split_observables(observables)
         if (observables is not None or scattering is not None) and self.ensemble in ("npt_mtk", "npt_mtk_cell"):
@@ -356,6 +377,10 @@ class MolecularDynamics(Driver):
         traj = observables.begin(lat, z, m, vg.device) if observables is not None else None
         sq = scattering.begin(lat, z, m, vg.device) if scattering is not None else None
         lo = local.begin(lat, z, m, vg.device) if local is not None else None
+        mtk = self.ensemble in ("npt_mtk", "npt_mtk_cell")   # (the kinetic part comes from the integrator's own obs row)
+        th = thermo.begin(lat, z, m, vg.device, self.pressure / EV_PER_A3_IN_GPA if npt else 0.0, self.ensemble,
+                          self.cell_mask, self.fix_com) if thermo is not None else None
+        th_cell = torch.empty_like(lat64) if th is not None and mtk else None
         log, cells = MdLog(conserved=nhc, cell=cell), []
 
         def before(k, out, logged):
@@ -365,10 +390,19 @@ class MolecularDynamics(Driver):
                 sq_sample(sq, pos_t, lat64, dyn.velocities, out[K.FORCES], 0.0 if k == 0 else 0.5 * self.timestep)
             if lo is not None and k % local.sample_interval == 0:
                 lo_sample(lo, pos_t, lat64)
+            if th is not None and k % thermo.sample_interval == 0:
+                if mtk:
+                    th_cell.copy_(lat64)   # (the cell of the sample: the integrator call moves it on)
+                else:
+                    thermo_sample(th, out[K.TOTAL_ENERGY], out[K.STRESSES], lat64, dyn.velocities, out[K.FORCES],
+                                  0.0 if k == 0 else 0.5 * self.timestep)
             if cell and logged:
                 cells.append(lat64.clone())   # (the cell of the observables: the integrator call moves it on)
 
         def after(k, out):
+            if th is not None and mtk and k % thermo.sample_interval == 0:   # ke (and the pressure tensor) as the integrator states them
+                thermo_sample(th, out[K.TOTAL_ENERGY], out[K.STRESSES], th_cell, kinetic=dyn.obs[:, 0],
+                              pressure_tensor=dyn.obs[:, 6:12] if cell else None)
             if npt and k < steps:
                 vg.set_lattice(list(lat64.cpu().numpy()))   # (waits: the candidate search in the new cells needs them on the host)
 
@@ -384,4 +418,7 @@ class MolecularDynamics(Driver):
         if lo is not None:
             for r, obs in zip(res, local.results(lo, self.timestep)):
                 r["local_order"] = obs
+        if th is not None:
+            for r, obs in zip(res, thermo.results(th, self.timestep)):
+                r["thermo"] = obs
         return res
